@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- BN254 G1 MSM throughput on MI355X (BASELINE.json metric, configs[1]: 2^20 random points/scalars).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one MSM over the rank's shard (2^20 points per GPU, weak scaling: the N-GPU job is one 2^20*N-point MSM
 sharded by point range) + the partial-sum exchange (all_gather of 96-byte Jacobian partials over RCCL, folded on
 device).  Scalars and bases are resident in HBM before the timed region; prints ONE JSON line on rank 0.
-Extra keys: "roofline" (dominant kernel = bucket accumulation, HIP-event timed inside the library on the launch
-stream), "cpu_baseline" (oracle/cpu_ref.c = restatement of the reference's best_multiexp on the host cores),
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, ms_per_step, ...); at N > 1 the
+line also carries the ranks' and devices' evidence (verify_exchange).  --dump-outputs DIR writes the last timed step's result
+(dump_outputs).  Only with --full (each trimmed by its --no-* option): "value_cold", "result_checked" at N = 1, "roofline" (dominant
+kernel = bucket accumulation, HIP-event timed inside the library on the launch stream), "cpu_baseline" (oracle/cpu_ref.c =
+restatement of the reference's best_multiexp on the host cores),
 "phases_ms", "ntt", "wrapper_replay" (MSM+NTT call mix of one wrapper-circuit proof at k = 22, device-resident), "value_2p22",
 "wrapper_replay_k24" (the same mix at k = 24 = BASELINE configs[4], one card + the 8-card projection), "prover_flow_k13_wide" / "prover_flow_k15_wide".
 """
@@ -82,6 +85,11 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--log-n", type=int, default=20, help="log2 points per GPU (BASELINE configs[1] = 20)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: value_cold, the result check, roofline / phases, general path, batch of 8, the NTT / "
+                         "replay / configs[4] extras and the CPU baseline (the --no-* options below trim this set); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result (the MSM's G1 point) to DIR/msm_g1_affine.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the NTT / wrapper-replay extras")
     ap.add_argument("--no-general-path", action="store_true", help="skip the unregistered-bases MSM (rocprofv3 runs: keeps per-kernel averages to the headline path)")
@@ -92,7 +100,12 @@ def parse_args(argv=None):
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU rehearsal of the --gpus N launcher: the ranks rendezvous over gloo, time an empty step and rank 0 prints a line that is "
                          "marked as a self-test (no GPU work, no metric)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def structured_point(lib, _lib, F, torch, d_scalars, n, t0: int, d: int, stream, dev):
@@ -123,6 +136,20 @@ def affine_words(lib, _lib, jac_words: np.ndarray) -> np.ndarray:
     out = np.zeros((jac.shape[0], 8), dtype=np.uint64)
     _lib.check(lib.zkhip_g1_batch_normalize(jac.ctypes.data, jac.shape[0], out.ctypes.data))
     return out
+
+
+def dump_outputs(out_dir: str, F, jac_words: np.ndarray) -> None:
+    """--dump-outputs: what the timed path returned in its last step -- one G1 point, the MSM's result (at N > 1 the fold of the ranks'
+    partials) -- as DIR/msm_g1_affine.npy, float64 (2, 16): the affine x and y as canonical integers, 16 little-endian 16-bit limbs each
+    (exact in float64, and a difference of one in any limb exceeds np.allclose's default tolerance).  The affine form, not the 96 Jacobian
+    bytes the caller receives, because Z is not unique: two builds that agree on the point may differ there.  Infinity is all zeros."""
+    os.makedirs(out_dir, exist_ok=True)
+    arr = np.zeros((2, 16), dtype=np.float64)
+    pt = F.g1_decode_jacobian(np.asarray(jac_words, dtype=np.uint64)[:12])
+    if pt is not None:
+        for row, v in enumerate(pt):
+            arr[row] = [(v >> (16 * j)) & 0xFFFF for j in range(16)]
+    np.save(os.path.join(out_dir, "msm_g1_affine.npy"), arr)
 
 
 def verify_exchange(lib, _lib, F, torch, dist, dev, stream, cpu_group, world, d_scalars, n, t0: int, d: int, d_partial, d_gather, d_final,
@@ -355,18 +382,20 @@ def main() -> None:
         _lib.check(lib.zkhip_msm_g1_prepared_device(handle, 0, d_scalars.data_ptr(), n, d_out.data_ptr(), stream))
 
     # (round 4, advisor) first the figure WITHOUT the pre-warm, for comparison with the lines of rounds 1-2: K steps straight after the W warm-up
-    # steps, bracketed the same way -- reported as value_cold, never as value
-    if use_dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t_cold = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    if use_dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    elapsed_cold = time.perf_counter() - t_cold
+    # steps, bracketed the same way -- reported as value_cold, never as value (--full only: the headline does not need it)
+    elapsed_cold = float("nan")
+    if args.full:
+        if use_dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t_cold = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        if use_dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        elapsed_cold = time.perf_counter() - t_cold
     # the rendezvous comes BEFORE the pre-warm so that no host-side idle gap separates the pre-warm from the timed region (each rank pre-warms
     # for the same wall time, then starts its K steps; the closing barrier and the max over ranks absorb the skew)
     if use_dist:
@@ -390,6 +419,8 @@ def main() -> None:
     mpoints = world * n * args.steps / elapsed / 1e6
     if exchange and world == 1:   # forced exchange at N = 1: the fold of one partial must be that partial (as an affine point)
         assert F.g1_decode_jacobian(d_final.cpu().numpy().view(np.uint64)[:12]) == F.g1_decode_jacobian(d_out.cpu().numpy().view(np.uint64)[:12])
+    if args.dump_outputs and rank == 0:   # before anything else reuses d_out
+        dump_outputs(args.dump_outputs, F, (d_final if exchange else d_out).cpu().numpy().view(np.uint64))
 
     result = {
         "metric": "BN254 G1 MSM Mpoints/sec",
@@ -398,8 +429,7 @@ def main() -> None:
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
-        "value_cold": round(world * n * args.steps / elapsed_cold / 1e6, 3),
-        "clock_prewarm": {"untimed_steps_after_the_warmup": extra_warm + args.steps, "ms": PREWARM_MS, "value_cold_is": "the K steps straight after the W warm-up steps (no pre-warm), same bracketing",
+        "clock_prewarm": {"untimed_steps_after_the_warmup": extra_warm + (args.steps if args.full else 0), "ms": PREWARM_MS,
                           "why": "the card needs 30-40 ms of continuous work to reach its clocks after idling; steady-state throughput is the metric (DESIGN.md section 7)"},
         "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True,
@@ -413,6 +443,9 @@ def main() -> None:
                    "points_per_gpu": n, "prepare_bases_ms_one_time": round(t_prep * 1e3, 2),
                    "parallelism": f"point-range shard x{world} + all_gather(96 B) + fold"},
     }
+    if args.full:
+        result["value_cold"] = round(world * n * args.steps / elapsed_cold / 1e6, 3)
+        result["clock_prewarm"]["value_cold_is"] = "the K steps straight after the W warm-up steps (no pre-warm), same bracketing"
 
     if use_dist:
         # the N-rank line carries its own evidence (ranks, devices, results): see verify_exchange
@@ -420,14 +453,14 @@ def main() -> None:
                               0x9E3779B97F4A7C15F39CC0605CEDC835, d_out, d_gather, d_final)
         result.update({k: ver[k] for k in ("ranks_seen", "devices", "distinct_devices", "result_checked") if k in ver})
         result["exchange_backend"] = ver["backend"]
-    elif world == 1:
+    elif world == 1 and args.full:
         want = structured_point(lib, _lib, F, torch, d_scalars, n, 0x5A4B534E41500002, 0x9E3779B97F4A7C15F39CC0605CEDC835, stream, dev)
         ok = bool(np.array_equal(affine_words(lib, _lib, d_out.cpu().numpy().view(np.uint64)[:12])[0], want))
         result["result_checked"] = {"msm_equals_structured_identity": ok, "ok": ok}
         if not ok:
             fail("the timed MSM's result is not [sum a_i (t0 + i d)] G", 5)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel (bucket accumulation), HIP events on the launch stream ---------
         # Measured in the headline's state (round 4 review, item 4): prepared MSMs only, back to back behind the timed region's own pre-warm,
         # the library's phase events APPENDED call after call (zkhip_profile_enable(2)) and read back once at the end -- no host read-back and
@@ -563,7 +596,7 @@ def main() -> None:
     # ---- BASELINE configs[4]: the wrapper circuit at k + 2 (2^24 points) sharded over the GPUs of the node -------------------------
     # N > 1: every rank takes 2^24 / N points (2^21 at N = 8) -- the stated config, next to the weak-scaling headline above.
     # N = 1: the same 2^24-point MSM through the C ABI's own multi-GPU path with 8 virtual shards of 2^21 points on the one card.
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         try:
             c4 = config4_leg(lib, _lib, F, torch, dist, dev, stream, rank, world, gather_fold_device, cpu_group=cpu_group)
             if rank == 0:
@@ -575,7 +608,7 @@ def main() -> None:
     # N > 1, last: the SAME configs[4] MSM driven by ONE process over all N cards through the C ABI (zkhip_init([0..N-1]) + registered shards) --
     # the path a Rust host would use -- on rank 0, while the other ranks have released their buffers and wait on the host (gloo) so that
     # their cards are idle.  Re-initialising the library drops rank 0's earlier handles: nothing below needs them.
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         del d_bases, d_scalars
         torch.cuda.synchronize()
         if rank != 0:
@@ -600,7 +633,7 @@ def main() -> None:
                 result["config4_wrapper_k24_msm"]["single_process_c_abi"] = {"error": repr(exc)}
         dist.barrier(group=cpu_group)
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         result.update(extras(lib, _lib, F, torch, dev, stream))
         # the wrapper-size MSM (BASELINE configs[3]: k = 22, /root/reference/aggregator/benches/wrapper_circuit.rs:21) beside the headline
         if "msm_2^22" in result:
@@ -610,7 +643,7 @@ def main() -> None:
         except Exception as exc:   # an extra: never fail the bench line
             result["wrapper_replay_k24"] = {"error": repr(exc)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.log_n, d_scalars, d_bases, d_out, n)
 
     if rank == 0:

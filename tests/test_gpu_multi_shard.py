@@ -519,7 +519,7 @@ def test_bench_multi_gpu_control_flow_on_rccl_with_one_rank():
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         env["MASTER_PORT"] = str(sk.getsockname()[1])
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-general-path"],
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline", "--no-general-path"],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-2000:]
     line = [l for l in run.stdout.splitlines() if l.startswith("{")][-1]

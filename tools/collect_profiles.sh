@@ -39,6 +39,6 @@ python3 $R/tools/marker_summary.py $O/${TAG}_marker $O/${TAG}_marker_trace.txt |
 unset ZKHIP_ROCTX
 rm -rf $O/${TAG}_marker
 echo "marker done"
-rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof_full -- python3 $R/bench.py --no-cpu-baseline > $O/${TAG}_prof_full.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof_full -- python3 $R/bench.py --full --no-cpu-baseline > $O/${TAG}_prof_full.log 2>&1
 (cd $R && $S stats $O/${TAG}_prof_full $O/${TAG}_kernel_stats_bench_full.csv); rm -rf $O/${TAG}_prof_full
 echo "stats full done; summaries written"

@@ -20,5 +20,5 @@ for path in sys.argv[2:]:
     d = json.load(open(path)); d["commit"] = sys.argv[1]; json.dump(d, open(path, "w"), indent=1)
 PY
 fi
-cd $R && python3 bench.py > $O/${TAG}_bench_final.json 2> $O/${TAG}_bench_final.err
+cd $R && python3 bench.py --full > $O/${TAG}_bench_final.json 2> $O/${TAG}_bench_final.err
 tail -c 600 $O/${TAG}_bench_final.json

@@ -189,6 +189,34 @@ int zkhip_fr_eval_rows_device(const zkhip_vm_program *prog, const void *const *d
  * launching anything (no device needed), e.g. at keygen, so that the first proof does not pay the seconds of compilation. */
 int zkhip_vm_jit_source(const zkhip_vm_program *prog, uint32_t n_columns, uint32_t log_rows, char *buf, size_t cap, size_t *len);
 int zkhip_vm_jit_compile(const zkhip_vm_program *prog, uint32_t n_columns, uint32_t log_rows, size_t *code_bytes);
+/* Window form: `count` rows starting at global row `row0` of a 2^log_rows domain, e.g. one device's share of the rows.  With
+ * o_i = rotations[i] * rot_scale (signed, not reduced), halo_lo = max(0, max_i(-o_i)) and halo_hi = max(0, max_i(o_i)), each d_windows[c]
+ * is a WINDOW BUFFER of W = halo_lo + count + halo_hi elements: element t = column_c[(row0 - halo_lo + t) mod 2^log_rows] (valid for W >
+ * 2^log_rows too: the values repeat).  Operand COLUMN@rot at local row i reads window[i + halo_lo + o_rot]; ROWPOW is
+ * omega^((row0 + i) mod 2^log_rows); PREV and the result are d_out[i], i < count.  Both executors (interpreter and compiled; the compiled one
+ * for windows of at least 2^18 rows, one code object for every row0 / count).  ZKHIP_EINVAL for row0 >= 2^log_rows, count == 0 or
+ * count > 2^log_rows, a null window, or a program zkhip_fr_eval_rows_device rejects. */
+int zkhip_fr_eval_rows_window_device(const zkhip_vm_program *prog, const void *const *d_windows, uint32_t n_columns, uint32_t log_rows,
+                                     uint64_t row0, uint64_t count, int accumulate, void *d_out, void *stream);
+/* The quotient numerator sharded by rows over the devices of zkhip_init.  Column c is ZKHIP_COL_COEFF (2^k coefficients on the primary
+ * device, taken to the extended coset with coeff_to_extended(ext_omega, zeta) on the device that owns it) or ZKHIP_COL_EXTENDED (2^ext_k
+ * coset values already on the primary: the proving key's fixed / sigma / l_0 / l_last / l_active cosets).  d_out (2^ext_k elements on the
+ * primary) receives, byte for byte, what zkhip_coeff_to_extended_device on every COEFF column followed by
+ * zkhip_fr_eval_rows_device(prog, ..., ext_k, accumulate = 0) writes (PREV reads 0), for every device count.
+ * With S devices: rows are cut by shard_range(2^ext_k, j, S) and the COEFF columns, in argument order, by shard_range(n_coeff, j, S); each
+ * owner pulls its COEFF columns from the primary and transforms them; device j fills its window buffers (peer copies from the owners and
+ * from the primary), runs the window kernel and copies its rows into d_out.  S = 1: the transforms and the whole-domain launch, no copies.
+ * Asynchronous on `stream` like every `_device` call; back-to-back calls on one stream, and calls on different streams, are safe.
+ * Scratch is kept until zkhip_shutdown (S = 1: per caller stream; S > 1: per device); a second call of the same shape allocates nothing.
+ * No host thread waits for a device, except when S > 1 and a call needs more scratch than any call before it: then the previous call's
+ * copies are waited for before the buffers they read are replaced.  With zkhip_profile_enable the call records the phases transform,
+ * exchange, rows_compiled | rows_interpreted (the primary's executor) and gather on `stream`, for every S (exchange and gather are empty
+ * intervals when S = 1).  ZKHIP_EINVAL: a null pointer, a form other than 0 / 1, k > ext_k, ext_k > 28, a program
+ * zkhip_fr_eval_rows_device rejects. */
+#define ZKHIP_COL_COEFF    0u
+#define ZKHIP_COL_EXTENDED 1u
+int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program *prog, const void *const *d_columns, const uint32_t *forms, uint32_t n_columns,
+                                      uint32_t k, uint32_t ext_k, const uint64_t ext_omega[4], const uint64_t zeta[4], void *d_out, void *stream);
 /* out[row] = sum_p weights[p] * progs[p](row): `n_progs` independent row programs over the same columns, run side by side in one launch
  * (one grid row per program) and combined with zkhip_fr_linear_combination_device's kernel.  Programs that read ZKHIP_SRC_ROWPOW must
  * name the same omega.  For programs that are

@@ -35,8 +35,10 @@ BLIND = 5
 _SIDE_STREAM = None
 
 
-def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None):
-    """pk_file: path -- the proving key is written there (`ProvingKey::write`, RawBytesUnchecked), read back, and the READ key is what the
+def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False):
+    """sharded_quotient: the single-program quotient goes through zkhip_fr_eval_rows_sharded_device (rows cut over the devices of zkhip_init; the
+    key's cosets EXTENDED, the proof's columns COEFF, transformed inside the call) instead of coeff_to_extended + the whole-domain launch.
+    pk_file: path -- the proving key is written there (`ProvingKey::write`, RawBytesUnchecked), read back, and the READ key is what the
     prover uses (the reference's wrapper does the same through build/*_pk.bin: /root/reference/aggregator/src/wrapper.rs:967-989, :1007-1034)"""
     from zksnap_circuits_halo2_amd import keygen as KG
 
@@ -290,12 +292,23 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             for i in range(lo, hi):
                 KG._copy_device(ext[i].data_ptr(), key_cosets[i], ek)
         lap("keygen_coeff_to_extended")
-        for lo, hi in proof_ranges:
-            extend_range(lo, hi)
+        if sharded_quotient and ncol > 96 and ek < 18:
+            raise ValueError("sharded_quotient: the sum-of-programs quotient of the wide circuits is not sharded")
+        if not sharded_quotient:
+            for lo, hi in proof_ranges:
+                extend_range(lo, hi)
         lap("coeff_to_extended")
 
         # ---- quotient ---------------------------------------------------------------------------------------------------------------
-        if ncol > 96 and ek < 18:
+        if sharded_quotient:
+            prog = E.evaluate_h_program(cs, k, ek, beta, gamma, theta, y)
+            key = {i for lo, hi in pk_ranges for i in range(lo, hi)}
+            h_ext = torch.empty((en, 4), dtype=torch.int64, device=dev)
+            E.evaluate_rows_sharded_device(prog, [(ext[i].data_ptr(), E.COL_EXTENDED) if i in key else (coeff[i].data_ptr(), E.COL_COEFF) for i in range(ncol)],
+                                           k, ek, dom, h_ext.data_ptr())
+            n_insns = len(prog.insns)
+            n_regs = 1 + max([ins[1] for ins in prog.insns] + [o[1] for ins in prog.insns for o in ins[2:5] if o[0] == E.SRC_REG])
+        elif ncol > 96 and ek < 18:
             # hundreds of columns over a few thousand rows: as one program a handful of wavefronts walk thousands of instructions; as a sum of
             # programs over runs of the y-fold's terms (evaluate_h_parts + zkhip_fr_eval_rows_sum_device) they run side by side in one launch
             parts, weights = E.evaluate_h_parts(cs, k, ek, beta, gamma, theta, y, 16)
@@ -382,7 +395,7 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             print(f"  {'prover steps (no setup/witness)':28s} {prove_ms:9.3f} ms")
             print("  checks:", checks)
         return {"timings_ms": t, "prove_ms": prove_ms, "checks": checks, "columns": ncol, "proof_columns": n_proof_cols, "msms": n_msm, "queries": len(queries),
-                "program_insns": n_insns, "program_registers": n_regs,
+                "program_insns": n_insns, "program_registers": n_regs, "h_commitments": [affine(c) for c in h_commit],
                 "keygen_ms": t.get("keygen_vk", 0.0) + t.get("keygen_pk", 0.0) + t.get("keygen_device", 0.0), "pk_file_bytes": pk_bytes}
     finally:
         torch.cuda.synchronize()

@@ -1,0 +1,195 @@
+#!/usr/bin/env python3
+"""Measurement only: the quotient numerator sharded by rows (zkhip_fr_eval_rows_sharded_device) on the wrapper shape of
+tools/quotient_time.py -- k = 22, extended_k = 24, the proving key's 16 cosets EXTENDED, the proof's 13 columns COEFF -- on one card, in one
+process.  Prints
+  (a) the current composition: zkhip_coeff_to_extended_device per COEFF column + the whole-domain zkhip_fr_eval_rows_device;
+  (b) the sharded entry on one device (S = 1);
+  (c) the whole-domain launch against 8 windows of 2^21 rows run one after another (zkhip_fr_eval_rows_window_device), per executor (the
+      interpreter in a child process with ZKHIP_VM_JIT=0);
+  (d) S = 3 and S = 8 contexts of the same card: wall time (NOT a speed claim: every context is the same card) and the bytes each device
+      receives / sends, COMPUTED from the copy plan (exchange_bytes restates it), not counted from the copies the library issues;
+  (e) the 8-card projection of the quotient phase at k = 24, from one card's measured transform share and window kernel plus an ASSUMED
+      xGMI rate.
+`quotient_shard_time.py` (everything) | `quotient_shard_time.py windows` (only (c), the executor the environment selects)."""
+import ctypes as C
+import os
+import random
+import subprocess
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import torch  # noqa: E402
+
+import zksnap_circuits_halo2_amd as Z  # noqa: E402
+from zksnap_circuits_halo2_amd import _lib, evaluation as E, fields as F  # noqa: E402
+
+lib = _lib.load()
+LINK_GBPS = 64.0                     # assumed xGMI rate (bench.py's projection assumes the same)
+REPS = 5
+
+
+def wrapper_cs():
+    gates = [[E.Fixed(i) * (E.Advice(i, 0) + E.Advice(i, 1) * E.Advice(i, 2) - E.Advice(i, 3))] for i in range(4)]
+    lookups = [E.Lookup([E.Advice(4)], [E.Fixed(5)])]
+    perm = [("advice", i) for i in range(5)] + [("fixed", 4), ("instance", 0)]
+    return E.ConstraintSystem(num_fixed=6, num_advice=5, num_instance=1, gates=gates, lookups=lookups, permutation_columns=perm,
+                              blinding_factors=5, degree=4)
+
+
+cs = wrapper_cs()
+qc = E.quotient_columns(cs)
+KEY = set(range(qc.fixed, qc.advice)) | {qc.l0, qc.l_last, qc.l_active_row} | set(range(qc.sigma, qc.perm_product))
+FORMS = [E.COL_EXTENDED if i in KEY else E.COL_COEFF for i in range(qc.total)]
+rng = random.Random(1)
+CH = tuple(rng.randrange(F.R_MOD) for _ in range(4))
+
+
+def rand(rows):
+    t = torch.randint(0, 1 << 62, (rows, 4), dtype=torch.int64, device="cuda")
+    t[:, 3] &= (1 << 61) - 1
+    return t
+
+
+def timed(fn, reps=REPS):
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e3
+
+
+def shard_range(n, j, S):
+    base, extra = divmod(n, S)
+    lo = j * base + min(j, extra)
+    return lo, lo + base + (1 if j < extra else 0)
+
+
+def init(S):
+    os.environ["ZKHIP_TEST_DUPLICATE_DEVICES"] = "1"       # S contexts of card 0 (zkhip_init reads it)
+    lib.zkhip_shutdown()
+    _lib.check(lib.zkhip_init((C.c_int * S)(*([0] * S)), S))
+
+
+def windows_of(prog, cols, ek, row0, count):
+    lo, hi = prog.halos(ek)
+    idx = (torch.arange(row0 - lo, row0 + count + hi, device="cuda") % (1 << ek))
+    return [c[idx].contiguous() for c in cols]
+
+
+def whole_vs_windows(prog, ek, parts=8):
+    cols = [rand(1 << ek) for _ in range(qc.total)]
+    out = torch.zeros((1 << ek, 4), dtype=torch.int64, device="cuda")
+    ptrs = [c.data_ptr() for c in cols]
+    whole = timed(lambda: prog.run_device(ptrs, ek, out.data_ptr()))
+    count = (1 << ek) // parts
+    wins = [windows_of(prog, cols, ek, j * count, count) for j in range(parts)]
+    wptrs = [[w.data_ptr() for w in ws] for ws in wins]
+    out2 = torch.zeros_like(out)
+
+    def run_windows():
+        for j in range(parts):
+            prog.run_window_device(wptrs[j], ek, j * count, count, out2[j * count:].data_ptr())
+    win = timed(run_windows)
+    assert torch.equal(out, out2), "windows differ from the whole-domain launch"
+    return whole, win
+
+
+def exchange_bytes(n_cols, n_coeff, k, ek, halo, S, j):
+    """bytes device j receives from other devices: its COEFF columns (pulled from the primary), the window pieces of every column it does
+    not hold itself, and (a secondary) nothing more -- its results leave it (sent bytes: count * 32)"""
+    N = 1 << ek
+    lo, hi = shard_range(N, j, S)
+    W = halo + (hi - lo)
+    olo, ohi = shard_range(n_coeff, j, S)
+    pulled = (ohi - olo) * (1 << k) * 32 if j else 0
+    n_ext = n_cols - n_coeff
+    remote_cols = (n_ext if j else 0) + (n_coeff - (ohi - olo))
+    return pulled + remote_cols * W * 32, (hi - lo) * 32 if j else 0
+
+
+def main():
+    k, ek = 22, 24
+    prog = E.evaluate_h_program(cs, k, ek, *CH)
+    lo, hi = prog.halos(ek)
+    dom = Z.EvaluationDomain(4, k)
+    print(f"wrapper shape: k={k} extended_k={ek} columns={qc.total} ({FORMS.count(E.COL_COEFF)} COEFF, {FORMS.count(E.COL_EXTENDED)} EXTENDED) "
+          f"insns={len(prog.insns)} halos=({lo}, {hi})  box: {torch.cuda.get_device_name(0)}, one process", flush=True)
+    torch.manual_seed(3)
+    cols = [rand(1 << (ek if f == E.COL_EXTENDED else k)) for f in FORMS]
+    coeff_idx = [i for i, f in enumerate(FORMS) if f == E.COL_COEFF]
+    ext = {i: torch.empty((1 << ek, 4), dtype=torch.int64, device="cuda") for i in coeff_idx}
+    out_a = torch.zeros((1 << ek, 4), dtype=torch.int64, device="cuda")
+    out_b = torch.zeros_like(out_a)
+    init(1)
+
+    def composition():
+        for i in coeff_idx:
+            _lib.check(lib.zkhip_coeff_to_extended_device(cols[i].data_ptr(), 1 << k, k, ext[i].data_ptr(), 1 << ek, ek, 1, dom.extended_omega.ctypes.data,
+                                                          dom.g_coset.ctypes.data, None))
+        prog.run_device([(ext[i] if i in ext else cols[i]).data_ptr() for i in range(qc.total)], ek, out_a.data_ptr())
+
+    columns = [(c.data_ptr(), f) for c, f in zip(cols, FORMS)]
+    sharded = lambda out: E.evaluate_rows_sharded_device(prog, columns, k, ek, dom, out.data_ptr())
+    ta = timed(composition)
+    tb = timed(lambda: sharded(out_b))
+    assert torch.equal(out_a, out_b)
+    print(f"(a) composition (13 coeff_to_extended + whole-domain launch)    {ta:8.3f} ms")
+    print(f"(b) sharded entry, S = 1                                        {tb:8.3f} ms   (b)/(a) = {tb / ta:.4f}", flush=True)
+    del ext
+    # (c)
+    tw, tn = whole_vs_windows(prog, ek)
+    print(f"(c) compiled     : whole-domain 2^{ek} {tw:8.3f} ms   8 windows of 2^{ek - 3} in sequence {tn:8.3f} ms   ratio {tn / tw:.4f}", flush=True)
+    env = dict(os.environ, ZKHIP_VM_JIT="0")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "windows"], capture_output=True, text=True, env=env, timeout=900)
+    if r.returncode != 0:
+        raise SystemExit("interpreter child failed: " + r.stdout[-2000:] + r.stderr[-2000:])
+    print(r.stdout.strip().replace("(c) compiled     ", "(c) interpreter  "), flush=True)
+    # (d)
+    nC = len(coeff_idx)
+    for S in (3, 8):
+        init(S)
+        out_d = torch.zeros_like(out_a)
+        td = timed(lambda: sharded(out_d))
+        assert torch.equal(out_d, out_a), S
+        moved = [exchange_bytes(qc.total, nC, k, ek, lo + hi, S, j) for j in range(S)]
+        print(f"(d) S = {S} contexts of ONE card: {td:8.3f} ms wall (not a speed claim); per device received / sent MB, COMPUTED from the copy plan: "
+              + " ".join(f"{a / 2**20:.0f}/{b / 2**20:.0f}" for a, b in moved), flush=True)
+    init(1)
+    del cols, out_a, out_b
+    torch.cuda.empty_cache()
+    # (e) k = 24 on 8 cards
+    k8, ek8, S = 24, 26, 8
+    prog8 = E.evaluate_h_program(cs, k8, ek8, *CH)
+    dom8 = Z.EvaluationDomain(4, k8)
+    share = -(-nC // S)
+    src = rand(1 << k8)
+    dst = torch.empty((share, 1 << ek8, 4), dtype=torch.int64, device="cuda")
+
+    def transforms():
+        for b in range(share):
+            _lib.check(lib.zkhip_coeff_to_extended_device(src.data_ptr(), 1 << k8, k8, dst[b].data_ptr(), 1 << ek8, ek8, 1, dom8.extended_omega.ctypes.data,
+                                                          dom8.g_coset.ctypes.data, None))
+    t_tr = timed(transforms, 3)
+    del dst
+    count = (1 << ek8) // S
+    wcols = [rand(count + lo + hi) for _ in range(qc.total)]
+    wout = torch.zeros((count, 4), dtype=torch.int64, device="cuda")
+    wp = [w.data_ptr() for w in wcols]
+    t_win = timed(lambda: prog8.run_window_device(wp, ek8, 3 * count, count, wout.data_ptr()), 3)
+    recv = max(exchange_bytes(qc.total, nC, k8, ek8, lo + hi, S, j)[0] for j in range(S))
+    t_link = recv / (LINK_GBPS * 1e9) * 1e3
+    print(f"(e) PROJECTION, ASSUMED link rate {LINK_GBPS:.0f} GB/s -- quotient phase at k = {k8} on {S} cards (unmeasured on multi-GPU hardware): "
+          f"per device {share} coset transform(s) 2^{k8}->2^{ek8} {t_tr:.3f} ms (measured) + window kernel 2^{ek8 - 3} rows {t_win:.3f} ms (measured) "
+          f"+ exchange {recv / 2**20:.0f} MB (computed from the copy plan) / {LINK_GBPS:.0f} GB/s = {t_link:.3f} ms (assumed rate) -> {t_tr + t_win + t_link:.3f} ms", flush=True)
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] == ["windows"]:
+        prog = E.evaluate_h_program(cs, 22, 24, *CH)
+        tw, tn = whole_vs_windows(prog, 24)
+        print(f"(c) compiled     : whole-domain 2^24 {tw:8.3f} ms   8 windows of 2^21 in sequence {tn:8.3f} ms   ratio {tn / tw:.4f}")
+    else:
+        main()

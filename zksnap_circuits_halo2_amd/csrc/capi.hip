@@ -57,6 +57,7 @@ static char g_prof_names[PROF_POOL][24];
 static int g_prof_calls[PROF_POOL / 2][2];   // mode 2: (base, marks) per recorded call
 static int g_prof_ncalls = 0;
 static bool g_prof_full = false;             // mode 2: the pool ran out, the current call records nothing
+static bool g_prof_hold = false;             // the inner marks of a call's phase are not recorded (prof_hold)
 
 void prof_begin(hipStream_t stream) {
   if (!g_prof_mode) return;
@@ -84,12 +85,18 @@ void prof_begin(hipStream_t stream) {
 }
 
 void prof_mark(hipStream_t stream, const char* name) {
-  if (!g_prof_mode || !g_prof_ev_ready || g_prof_n >= PROF_MAX) return;
+  if (!g_prof_mode || !g_prof_ev_ready || g_prof_n >= PROF_MAX || g_prof_hold) return;
   snprintf(g_prof_names[g_prof_base + g_prof_n], sizeof(g_prof_names[0]), "%s", name);
   g_prof_n++;
   (void)hipEventRecord(g_prof_ev[g_prof_base + g_prof_n], stream);
 }
 
+
+// RAII: while alive, the marks of the kernels a phase is made of (the transforms' passes) are dropped: the phase is one interval
+struct prof_hold {
+  prof_hold() { g_prof_hold = true; }
+  ~prof_hold() { g_prof_hold = false; }
+};
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s failed: %s", #x, hipGetErrorString(e_)); return ZKHIP_EHIP; } } while (0)
 
@@ -151,10 +158,11 @@ struct dev_buf {       // grow-only device scratch (hipFree waits for the device
 
 struct scratch {       // one user at a time: the calls of one stream
   dev_buf ws, scalars, bases, poly, poly2, small, ntt_tmp, vm, gather;
+  dev_buf q_ext;                       // zkhip_fr_eval_rows_sharded_device on one device: the extended cosets of the COEFF columns
   vm_staging vm_stage;                 // pinned host staging of the row programs' blobs (rowvm.hip)
   arg_ring args;                       // pinned slots for the small host arrays of `_device` calls (lists of column addresses, coefficients)
   uint64_t last_use = 0;
-  void release() { ws.release(); scalars.release(); bases.release(); poly.release(); poly2.release(); small.release(); ntt_tmp.release(); vm.release(); gather.release(); vm_stage.release(); args.release(); }
+  void release() { ws.release(); scalars.release(); bases.release(); poly.release(); poly2.release(); small.release(); ntt_tmp.release(); vm.release(); gather.release(); q_ext.release(); vm_stage.release(); args.release(); }
 };
 
 constexpr int STREAM_PIECES_MAX = 64;      // pieces of one chunked host-buffer MSM
@@ -227,6 +235,11 @@ struct device_ctx {
   // the caller's stream: the scalars are complete) and records `fan_done` for the caller's stream to wait on before the fold
   hipStream_t fan = nullptr;
   hipEvent_t fan_ready = nullptr, fan_done = nullptr;
+  // the sharded quotient numerator (zkhip_fr_eval_rows_sharded_device): the extended cosets of the COEFF columns this device owns, its window
+  // buffers and (secondaries) its rows' results; `q_transformed` follows its transforms, `q_done` its last step (the next call's first steps wait on it)
+  dev_buf q_ext, q_win, q_out;
+  hipEvent_t q_transformed = nullptr, q_done = nullptr;
+  bool q_done_live = false;
 };
 
 struct shard_t {       // points [lo, lo + n) of a registered array, prepared on device `dev`
@@ -392,6 +405,9 @@ static void destroy_device_ctx(device_ctx* d) {
   if (d->fan_ready) (void)hipEventDestroy(d->fan_ready);
   if (d->fan_done) (void)hipEventDestroy(d->fan_done);
   if (d->fan) (void)hipStreamDestroy(d->fan);
+  if (d->q_transformed) (void)hipEventDestroy(d->q_transformed);
+  if (d->q_done) (void)hipEventDestroy(d->q_done);
+  d->q_ext.release(); d->q_win.release(); d->q_out.release();
   d->fixed_table.release();
   d->gather.release();
   delete d;
@@ -1753,6 +1769,220 @@ int zkhip_fr_eval_rows_sum_device(const zkhip_vm_program* progs, const uint64_t*
   if ((rc = row_vm_device_multi(progs, n_progs, d_columns, n_columns, log_rows, partial.data(), sc->vm.p, sc->vm.cap, s, &sc->vm_stage)) != ZKHIP_OK) return rc;
   if ((rc = sc->ws.reserve(lincomb_workspace_bytes(n_progs, rows))) != ZKHIP_OK) return rc;
   return fr_linear_combination_device((const void* const*)partial.data(), (const uint32_t*)weights, n_progs, rows, (uint32_t*)d_out, sc->ws.p, sc->ws.cap, s, &sc->args);
+}
+
+// Row program over window buffers: `count` rows from global row `row0` of a 2^log_rows domain (include/zkhip.h; rowvm.hip row_vm_window_device)
+int zkhip_fr_eval_rows_window_device(const zkhip_vm_program* prog, const void* const* d_windows, uint32_t n_columns, uint32_t log_rows, uint64_t row0,
+                                     uint64_t count, int accumulate, void* d_out, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if ((rc = row_vm_validate(prog, n_columns, log_rows, accumulate)) != ZKHIP_OK) return rc;
+  if (!d_out || (n_columns && !d_windows)) { set_error("eval_rows_window: null pointer"); return ZKHIP_EINVAL; }
+  const uint64_t rows = (uint64_t)1 << log_rows;
+  if (row0 >= rows || count == 0 || count > rows) { set_error("eval_rows_window: row0 %llu / count %llu outside a domain of 2^%u rows", (unsigned long long)row0,
+                                                              (unsigned long long)count, log_rows); return ZKHIP_EINVAL; }
+  for (uint32_t i = 0; i < n_columns; i++)
+    if (!d_windows[i]) { set_error("eval_rows_window: window %u is null", i); return ZKHIP_EINVAL; }
+  uint64_t lo = 0, hi = 0;
+  row_vm_halos(prog, &lo, &hi);
+  if (lo + hi >= ((uint64_t)1 << 31)) { set_error("eval_rows_window: halos %llu + %llu too wide", (unsigned long long)lo, (unsigned long long)hi); return ZKHIP_EINVAL; }
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->vm.reserve(row_vm_workspace_bytes(prog, n_columns, log_rows))) != ZKHIP_OK) return rc;
+  return row_vm_window_device(prog, d_windows, n_columns, log_rows, row0, count, accumulate, (uint32_t*)d_out, sc->vm.p, sc->vm.cap, s, &sc->vm_stage);
+}
+
+// The quotient numerator re-cut by rows over the devices of zkhip_init.  Device j of S: rows shard_range(2^ext_k, j, S),
+// COEFF columns shard_range(n_coeff, j, S) in argument order.  Steps, all enqueued from this thread (nothing here waits for a device):
+//   A  every device's stream waits for the caller's stream (entry event) and for the previous call's last steps on every device
+//      (its transforms overwrite q_ext, which the previous call's window copies read);
+//   B  each owner pulls its COEFF columns from the primary and runs coeff_to_extended into q_ext (its own twiddle plan), records q_transformed;
+//   C  device j waits for every owner's q_transformed, fills its window buffers with peer copies (COEFF columns from their owner's q_ext,
+//      EXTENDED columns from the primary), runs the window kernel and copies its `count` results into d_out;
+//   D  the caller's stream waits for every device's q_done.
+// S = 1 is the composition itself: the transforms into the caller stream's scratch set and the whole-domain launch, no window copies.  The result is the same bytes for
+// every S: each transform runs on one device, each row's program reads the same values.
+int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* const* d_columns, const uint32_t* forms, uint32_t n_columns, uint32_t k,
+                                      uint32_t ext_k, const uint64_t ext_omega[4], const uint64_t zeta[4], void* d_out, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if (!prog || !d_out || !ext_omega || !zeta || (n_columns && (!d_columns || !forms))) { set_error("eval_rows_sharded: null pointer"); return ZKHIP_EINVAL; }
+  if (k > ext_k || ext_k > 28) { set_error("eval_rows_sharded: k = %u, ext_k = %u out of range", k, ext_k); return ZKHIP_EINVAL; }
+  if ((rc = row_vm_validate(prog, n_columns, ext_k, 0)) != ZKHIP_OK) return rc;
+  std::vector<uint32_t> coeff_cols;                        // argument indices of the COEFF columns
+  for (uint32_t i = 0; i < n_columns; i++) {
+    if (!d_columns[i]) { set_error("eval_rows_sharded: column %u is null", i); return ZKHIP_EINVAL; }
+    if (forms[i] > ZKHIP_COL_EXTENDED) { set_error("eval_rows_sharded: column %u has form %u", i, forms[i]); return ZKHIP_EINVAL; }
+    if (forms[i] == ZKHIP_COL_COEFF) coeff_cols.push_back(i);
+  }
+  uint64_t halo_lo = 0, halo_hi = 0;
+  row_vm_halos(prog, &halo_lo, &halo_hi);
+  if (halo_lo + halo_hi >= ((uint64_t)1 << 31)) { set_error("eval_rows_sharded: halos too wide"); return ZKHIP_EINVAL; }
+  hipStream_t s = caller_stream(stream);
+  const int S = (int)g_ctx.devs.size();
+  const size_t N = (size_t)1 << ext_k, n_in = (size_t)1 << k, nC = coeff_cols.size();
+  uint32_t scales[24];
+  coset_scales(zeta, nullptr, scales);
+  device_ctx& P = primary();
+  scratch* sc = scratch_for(P, s);
+  prof_begin(s);
+  if (S == 1) {
+    // the cosets go to the caller stream's scratch set: calls on other streams have sets of their own, calls on this one are ordered by it
+    if ((rc = sc->q_ext.reserve(std::max<size_t>(nC, 1) * N * 32)) != ZKHIP_OK) return rc;
+    std::vector<const void*> cols(d_columns, d_columns + n_columns);
+    {
+      prof_hold hold;
+      for (size_t c = 0; c < nC; c++) {
+        uint32_t* dst = (uint32_t*)sc->q_ext.p + c * N * 8;
+        if ((rc = run_transform(sc, (const uint32_t*)d_columns[coeff_cols[c]], (uint32_t)n_in, (uint32_t)n_in, dst, (uint32_t)N, (uint32_t)N, 1, ext_k,
+                                (const uint32_t*)ext_omega, scales, 3, nullptr, 0, s)) != ZKHIP_OK) return rc;
+        cols[coeff_cols[c]] = dst;
+      }
+    }
+    prof_mark(s, "transform");
+    prof_mark(s, "exchange");                              // (empty on one device: the same four phases for every S)
+    if ((rc = sc->vm.reserve(row_vm_workspace_bytes(prog, n_columns, ext_k))) != ZKHIP_OK) return rc;
+    int compiled = 0;
+    if ((rc = row_vm_device(prog, cols.data(), n_columns, ext_k, 0, (uint32_t*)d_out, sc->vm.p, sc->vm.cap, s, &sc->vm_stage, &compiled)) != ZKHIP_OK) return rc;
+    prof_mark(s, compiled ? "rows_compiled" : "rows_interpreted");
+    prof_mark(s, "gather");
+    return ZKHIP_OK;
+  }
+  std::unique_lock<std::mutex> fan(g_fanout_mu);
+  std::vector<hipStream_t> st(S, nullptr);                  // the stream device j works on: the caller's for the primary, its fan stream otherwise
+  std::vector<scratch*> dsc(S, nullptr);
+  std::vector<size_t> row_lo(S), row_n(S), own_lo(S), own_n(S);
+  std::vector<bool> used(S, false);                        // streams that hold enqueued work (drained on an error)
+  // on an error after something was enqueued: wait for every stream that holds this call's work, so that nothing outlives the call's buffers
+  struct drain_t {
+    std::vector<hipStream_t>* st; std::vector<bool>* used; std::vector<device_ctx*>* devs; bool armed = true;
+    ~drain_t() {
+      if (!armed) return;
+      for (size_t j = 0; j < st->size(); j++)
+        if ((*used)[j]) { (void)hipSetDevice((*devs)[j]->device); (void)hipStreamSynchronize((*st)[j]); }
+      (void)hipSetDevice((*devs)[0]->device);
+      (void)hipGetLastError();
+    }
+  } drain{&st, &used, &g_ctx.devs};
+  auto set_dev = [&](int j) -> int {
+    if (hipSetDevice(g_ctx.devs[(size_t)j]->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", g_ctx.devs[(size_t)j]->device); return ZKHIP_ENODEV; }
+    return ZKHIP_OK;
+  };
+  // A: streams, scratch, events; every device's first step waits for the entry event and for the previous call's last steps
+  bool grows = false;
+  for (int j = 0; j < S; j++) {
+    device_ctx* D = g_ctx.devs[(size_t)j];
+    size_t lo, hi, olo, ohi;
+    shard_range(N, j, S, &lo, &hi);
+    shard_range(nC, j, S, &olo, &ohi);
+    grows |= D->q_ext.cap < std::max<size_t>(ohi - olo, 1) * N * 32 || D->q_win.cap < std::max<size_t>(n_columns, 1) * (halo_lo + hi - lo + halo_hi) * 32 ||
+             (j > 0 && D->q_out.cap < std::max<size_t>(hi - lo, 1) * 32);
+  }
+  // a buffer about to be replaced may still be read by another device's copies of the previous call: the ONE place this call blocks the host
+  // thread, and only when a shape needs more scratch than any earlier call (a second call of the same shape allocates nothing and never waits)
+  if (grows)
+    for (auto* D : g_ctx.devs) if (D->q_done_live) HIPCHK(hipEventSynchronize(D->q_done));
+  if (!P.fan_ready) HIPCHK(hipEventCreateWithFlags(&P.fan_ready, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(P.fan_ready, s));
+  for (int j = 0; j < S; j++) {
+    device_ctx* D = g_ctx.devs[(size_t)j];
+    if ((rc = set_dev(j)) != ZKHIP_OK) return rc;
+    if (j > 0 && !D->fan) {
+      HIPCHK(hipStreamCreateWithFlags(&D->fan, hipStreamNonBlocking));
+      HIPCHK(hipEventCreateWithFlags(&D->fan_done, hipEventDisableTiming));
+    }
+    if (!D->q_transformed) HIPCHK(hipEventCreateWithFlags(&D->q_transformed, hipEventDisableTiming));
+    if (!D->q_done) HIPCHK(hipEventCreateWithFlags(&D->q_done, hipEventDisableTiming));
+    st[j] = j == 0 ? s : D->fan;
+    dsc[j] = j == 0 ? sc : scratch_for(*D, D->fan);
+    shard_range(N, j, S, &row_lo[j], &row_n[j]);
+    row_n[j] -= row_lo[j];
+    shard_range(nC, j, S, &own_lo[j], &own_n[j]);
+    own_n[j] -= own_lo[j];
+    const size_t W = halo_lo + row_n[j] + halo_hi;
+    if ((rc = D->q_ext.reserve(std::max<size_t>(own_n[j], 1) * N * 32)) != ZKHIP_OK) return rc;
+    if ((rc = D->q_win.reserve(std::max<size_t>(n_columns, 1) * W * 32)) != ZKHIP_OK) return rc;
+    if (j > 0 && (rc = D->q_out.reserve(std::max<size_t>(row_n[j], 1) * 32)) != ZKHIP_OK) return rc;
+    if ((rc = dsc[j]->vm.reserve(row_vm_workspace_bytes(prog, n_columns, ext_k))) != ZKHIP_OK) return rc;
+  }
+  for (int j = 0; j < S; j++) {
+    if ((rc = set_dev(j)) != ZKHIP_OK) return rc;
+    if (j > 0) HIPCHK(hipStreamWaitEvent(st[j], P.fan_ready, 0));
+    for (int i = 0; i < S; i++)
+      if (g_ctx.devs[(size_t)i]->q_done_live) HIPCHK(hipStreamWaitEvent(st[j], g_ctx.devs[(size_t)i]->q_done, 0));
+  }
+  // B: the transforms, each on its owner
+  for (int j = 0; j < S; j++) {
+    device_ctx* D = g_ctx.devs[(size_t)j];
+    if ((rc = set_dev(j)) != ZKHIP_OK) return rc;
+    used[j] = true;
+    prof_hold hold;
+    uint32_t* ext = (uint32_t*)D->q_ext.p;
+    for (size_t c = 0; c < own_n[j]; c++) {
+      const uint32_t* src = (const uint32_t*)d_columns[coeff_cols[own_lo[j] + c]];
+      if (j == 0) {
+        if ((rc = run_transform(dsc[j], src, (uint32_t)n_in, (uint32_t)n_in, ext + c * N * 8, (uint32_t)N, (uint32_t)N, 1, ext_k, (const uint32_t*)ext_omega, scales, 3,
+                                nullptr, 0, st[j])) != ZKHIP_OK) return rc;
+      } else {
+        HIPCHK(hipMemcpyPeerAsync(ext + c * N * 8, D->device, src, P.device, n_in * 32, st[j]));
+      }
+    }
+    if (j > 0 && own_n[j] &&
+        (rc = run_transform(dsc[j], ext, (uint32_t)n_in, (uint32_t)N, ext, (uint32_t)N, (uint32_t)N, (uint32_t)own_n[j], ext_k, (const uint32_t*)ext_omega, scales, 3,
+                            nullptr, 0, st[j])) != ZKHIP_OK) return rc;
+    HIPCHK(hipEventRecord(D->q_transformed, st[j]));
+  }
+  if ((rc = set_dev(0)) != ZKHIP_OK) return rc;
+  prof_mark(s, "transform");
+  // C: windows, the window kernel, the results into d_out
+  std::vector<const void*> win(n_columns ? n_columns : 1);
+  for (int j = 0; j < S; j++) {
+    device_ctx* D = g_ctx.devs[(size_t)j];
+    if ((rc = set_dev(j)) != ZKHIP_OK) return rc;
+    for (int i = 0; i < S; i++)
+      if (own_n[i]) HIPCHK(hipStreamWaitEvent(st[j], g_ctx.devs[(size_t)i]->q_transformed, 0));
+    const size_t W = halo_lo + row_n[j] + halo_hi;
+    const size_t start = (size_t)((((int64_t)row_lo[j] - (int64_t)halo_lo) % (int64_t)N + (int64_t)N) % (int64_t)N);
+    for (uint32_t c = 0; c < n_columns; c++) {
+      const uint32_t* src;
+      int src_dev;
+      if (forms[c] == ZKHIP_COL_EXTENDED) { src = (const uint32_t*)d_columns[c]; src_dev = P.device; }
+      else {
+        const size_t ci = (size_t)(std::lower_bound(coeff_cols.begin(), coeff_cols.end(), c) - coeff_cols.begin());
+        int o = 0;
+        while (ci >= own_lo[o] + own_n[o]) o++;
+        src = (const uint32_t*)g_ctx.devs[(size_t)o]->q_ext.p + (ci - own_lo[o]) * N * 8;
+        src_dev = g_ctx.devs[(size_t)o]->device;
+      }
+      uint32_t* dst = (uint32_t*)D->q_win.p + (size_t)c * W * 8;
+      win[c] = dst;
+      for (size_t t = 0, pos = start; t < W;) {              // at most ceil(W / N) + 1 pieces
+        const size_t len = std::min(W - t, N - pos);
+        HIPCHK(hipMemcpyPeerAsync(dst + t * 8, D->device, src + pos * 8, src_dev, len * 32, st[j]));
+        t += len;
+        pos = 0;
+      }
+    }
+    if (j == 0) prof_mark(s, "exchange");
+    uint32_t* out = j == 0 ? (uint32_t*)d_out + row_lo[0] * 8 : (uint32_t*)D->q_out.p;
+    int compiled = 0;
+    if ((rc = row_vm_window_device(prog, win.data(), n_columns, ext_k, row_lo[j], row_n[j], 0, out, dsc[j]->vm.p, dsc[j]->vm.cap, st[j], &dsc[j]->vm_stage,
+                                   &compiled)) != ZKHIP_OK) return rc;
+    if (j == 0) prof_mark(s, compiled ? "rows_compiled" : "rows_interpreted");
+    else HIPCHK(hipMemcpyPeerAsync((uint32_t*)d_out + row_lo[j] * 8, P.device, out, D->device, row_n[j] * 32, st[j]));
+    HIPCHK(hipEventRecord(D->q_done, st[j]));
+    D->q_done_live = true;
+  }
+  // D: the caller's stream waits for every device
+  if ((rc = set_dev(0)) != ZKHIP_OK) return rc;
+  for (int j = 1; j < S; j++) HIPCHK(hipStreamWaitEvent(s, g_ctx.devs[(size_t)j]->q_done, 0));
+  prof_mark(s, "gather");
+  drain.armed = false;
+  return ZKHIP_OK;
 }
 
 // The straight-line HIP source rowvm_jit.hip generates for `prog` (buf may be NULL: *len receives the size needed, NUL included), and a

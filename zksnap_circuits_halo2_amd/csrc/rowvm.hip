@@ -14,6 +14,7 @@
 // Register invariant: N-form limbs, value < 2r.  fe_mul(a < 2r, 32b < 64r) < (128/169 + 1) r < 2r; sums and differences are brought
 // back under 2r with one conditional subtraction of 2r.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -37,9 +38,12 @@ struct vm_launch {
   const uint32_t* pow_lo;       // omega^j, j < 2^POW_LO_BITS (nullptr: ROWPOW unused)
   const uint32_t* pow_hi;       // omega^(j << POW_LO_BITS)
   uint32_t* out;
-  uint64_t rows;
+  uint64_t rows;                // rows this launch computes: the domain, or a window's `count`
   uint32_t accumulate;
   const struct vm_part* parts;  // nullptr, or one record per blockIdx.y: several programs over the same columns in ONE launch (row_vm_device_multi)
+  uint64_t wrap;                // column index mask: domain - 1 for whole columns, all ones for window buffers (offsets include halo_lo)
+  uint64_t row0;                // global row of local row 0 (0 for whole columns)
+  uint64_t dom_mask;            // domain - 1: ROWPOW is omega^((row0 + row) & dom_mask)
 };
 // what differs between the programs of a multi-program launch (the column table, the power tables and the rows are shared)
 struct vm_part {
@@ -160,7 +164,7 @@ __device__ __forceinline__ void vm_load_words(const vm_launch& L, uint32_t opnd,
   const uint64_t col_base = ((vm_c64)L.cols)[is_col ? index : 0u];
   const uint32_t off = ((vm_c32)L.rot_off)[is_col ? rot : 0u];
   const uint64_t base = is_col ? col_base : (uint64_t)(L.consts + (size_t)(is_const ? index : 0u) * 8);
-  const uint64_t rr = (row + off) & (is_col ? L.rows - 1 : 0ull);
+  const uint64_t rr = (row + off) & (is_col ? L.wrap : 0ull);
   const vm_g128 p = (vm_g128)(base + rr * 32);
   const vm_u128 lo = p[0], hi = p[1];
   w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w; w[4] = hi.x; w[5] = hi.y; w[6] = hi.z; w[7] = hi.w;
@@ -239,16 +243,16 @@ __device__ __forceinline__ vm_decoded vm_decode(const vm_launch& L, uint32_t pc)
   d.off_a = q2.x; d.off_b = q2.y; d.mask_a = q2.z; d.mask_b = q2.w;
   return d;
 }
-__device__ __forceinline__ void vm_load_resolved(uint64_t base, uint32_t off, uint32_t mask, uint64_t row, uint64_t rows, uint32_t (&w)[8]) {
-  const uint64_t rr = (row + off) & (rows - 1) & (uint64_t)(int64_t)(int32_t)mask;      // mask = 0: the base itself (a constant / a dummy)
+__device__ __forceinline__ void vm_load_resolved(uint64_t base, uint32_t off, uint32_t mask, uint64_t row, uint64_t wrap, uint32_t (&w)[8]) {
+  const uint64_t rr = (row + off) & wrap & (uint64_t)(int64_t)(int32_t)mask;      // mask = 0: the base itself (a constant / a dummy)
   const vm_g128 p = (vm_g128)(base + rr * 32);
   const vm_u128 lo = p[0], hi = p[1];
   w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w; w[4] = hi.x; w[5] = hi.y; w[6] = hi.z; w[7] = hi.w;
 }
 // issue the loads of an instruction's operands a / b -- unconditionally (see vm_load_words)
 __device__ __forceinline__ void vm_prefetch(const vm_launch& L, const vm_decoded& d, uint64_t row, uint32_t (&wa)[8], uint32_t (&wb)[8]) {
-  vm_load_resolved(d.base_a, d.off_a, d.mask_a, row, L.rows, wa);
-  vm_load_resolved(d.base_b, d.off_b, d.mask_b, row, L.rows, wb);
+  vm_load_resolved(d.base_a, d.off_a, d.mask_a, row, L.wrap, wa);
+  vm_load_resolved(d.base_b, d.off_b, d.mask_b, row, L.wrap, wb);
 }
 
 template <int R>
@@ -272,9 +276,10 @@ __global__ void __launch_bounds__(VM_THREADS) k_row_vm(const vm_launch L0) {
   for (int i = 0; i < R; i++) r[i] = fe_zero();
   vm_lds_put(s_prev, L.accumulate ? load_ext(L.out, row) : fe_zero());      // (a lane reads back only what it wrote: no barrier)
   if (L.pow_lo) {
+    const uint64_t prow = (L.row0 + row) & L.dom_mask;       // the global row (a window's rows wrap past the domain's end)
     uint32_t w[8];
-    load_words(L.pow_lo + (row & ((1u << POW_LO_BITS) - 1)) * 8, w);
-    vm_lds_put(s_pow, fe_mul<Fr>(load_ext(L.pow_hi, row >> POW_LO_BITS), fe_unpack<5>(w)));
+    load_words(L.pow_lo + (prow & ((1u << POW_LO_BITS) - 1)) * 8, w);
+    vm_lds_put(s_pow, fe_mul<Fr>(load_ext(L.pow_hi, prow >> POW_LO_BITS), fe_unpack<5>(w)));
   } else {
     vm_lds_put(s_pow, fe_zero());
   }
@@ -425,10 +430,15 @@ void vm_staging::release() {
 // its device address, the constants at `o_const` and the rotation offsets at `o_rot` from its start.
 // micro-ops: the instruction + its operands' resolved addresses; a product's second factor is fetched scaled by 2^5 -- free for a column /
 // constant (the other unpacking shift), a repack for a register -- so the memory operand goes second where the host did not put it there
-static void vm_fill_region(const zkhip_vm_program* p, const void* const* d_columns, uint64_t rows, unsigned char* region, uint64_t dev, size_t o_const, size_t o_rot) {
+// window = true: the columns are window buffers (rowvm_window below) and a rotation's offset is halo_lo + rotation * rot_scale, not reduced.
+static void vm_fill_region(const zkhip_vm_program* p, const void* const* d_columns, uint64_t rows, unsigned char* region, uint64_t dev, size_t o_const, size_t o_rot,
+                           bool window = false) {
   static_assert(sizeof(zkhip_vm_insn) == 16, "instruction layout");
   std::vector<uint32_t> rot_rows(p->n_rotations ? p->n_rotations : 1, 0u);
+  uint64_t halo_lo = 0, halo_hi = 0;
+  if (window) row_vm_halos(p, &halo_lo, &halo_hi);
   for (uint32_t i = 0; i < p->n_rotations; i++) {
+    if (window) { rot_rows[i] = (uint32_t)((int64_t)halo_lo + (int64_t)p->rotations[i] * (int64_t)p->rot_scale); continue; }
     const int64_t off = ((int64_t)p->rotations[i] * (int64_t)p->rot_scale) % (int64_t)rows;
     rot_rows[i] = (uint32_t)(off < 0 ? off + (int64_t)rows : off);
   }
@@ -572,6 +582,7 @@ int row_vm_device_multi(const zkhip_vm_program* progs, uint32_t n_progs, const v
   L.rows = rows;
   L.accumulate = 0;
   L.parts = (const vm_part*)(d + o_parts);
+  L.wrap = rows - 1; L.row0 = 0; L.dom_mask = rows - 1;
   if (omega) {
     const uint32_t n_lo = 1u << POW_LO_BITS, n_hi = (uint32_t)((rows >> POW_LO_BITS) ? (rows >> POW_LO_BITS) : 1);
     hipLaunchKernelGGL(k_vm_pow_table, dim3((n_lo + 255) / 256), dim3(256), 0, stream, (const fe_arg*)(d + o_omega), 0u, n_lo, (uint32_t*)(d + o_lo));
@@ -582,9 +593,24 @@ int row_vm_device_multi(const zkhip_vm_program* progs, uint32_t n_progs, const v
   return vm_launch_kernel(L, top, n_progs, stream);
 }
 
-int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, int accumulate,
-                  uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging) {
+void row_vm_halos(const zkhip_vm_program* p, uint64_t* lo, uint64_t* hi) {
+  int64_t l = 0, h = 0;
+  for (uint32_t i = 0; i < p->n_rotations; i++) {
+    const int64_t o = (int64_t)p->rotations[i] * (int64_t)p->rot_scale;
+    l = std::max(l, -o);
+    h = std::max(h, o);
+  }
+  *lo = (uint64_t)l;
+  *hi = (uint64_t)h;
+}
+
+// The whole-domain launch (window = false: row0 = 0, count = 2^log_rows, columns indexed modulo the domain) and the window launch (columns
+// are window buffers of halo_lo + count + halo_hi elements, indexed row + halo_lo + offset without a mask).  *compiled (if given): 1 when
+// the run-time compiled kernel took the call, 0 for the interpreter.
+static int row_vm_run(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, bool window, uint64_t row0, uint64_t count,
+                      int accumulate, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, int* compiled) {
   const uint64_t rows = (uint64_t)1 << log_rows;
+  if (compiled) *compiled = 0;
   if (ws_bytes < row_vm_workspace_bytes(p, n_columns, log_rows)) { set_error("eval_rows: workspace too small"); return ZKHIP_EINVAL; }
   // one host blob, one copy
   const size_t o_prog = 0;
@@ -619,7 +645,7 @@ int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint3
   struct { unsigned char* p; unsigned char* data() const { return p; } } blob{blob_p};
   for (uint32_t i = 0; i < n_columns; i++)
     if (!d_columns[i]) { set_error("eval_rows: column %u is null", i); return ZKHIP_EINVAL; }
-  vm_fill_region(p, d_columns, rows, blob.data(), (uint64_t)(char*)ws, o_const, o_rot);
+  vm_fill_region(p, d_columns, rows, blob.data(), (uint64_t)(char*)ws, o_const, o_rot, window);
   for (uint32_t i = 0; i < n_columns; i++) std::memcpy(blob.data() + o_cols + (size_t)i * 8, &d_columns[i], 8);
   if (p->omega) std::memcpy(blob.data() + o_omega, p->omega, 32);
   char* d = (char*)ws;
@@ -637,8 +663,11 @@ int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint3
   L.pow_lo = nullptr;
   L.pow_hi = nullptr;
   L.out = d_out;
-  L.rows = rows;
+  L.rows = window ? count : rows;
   L.accumulate = accumulate ? 1u : 0u;
+  L.wrap = window ? ~0ull : rows - 1;
+  L.row0 = window ? row0 : 0;
+  L.dom_mask = rows - 1;
   if (p->omega) {
     const uint32_t n_lo = 1u << POW_LO_BITS, n_hi = (uint32_t)((rows >> POW_LO_BITS) ? (rows >> POW_LO_BITS) : 1);
     hipLaunchKernelGGL(k_vm_pow_table, dim3((n_lo + 255) / 256), dim3(256), 0, stream, (const fe_arg*)(d + o_omega), 0u, n_lo, (uint32_t*)(d + o_lo));
@@ -648,11 +677,23 @@ int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint3
   }
   // a short program over many rows runs as compiled straight-line code when a kernel for its shape exists or can be built (rowvm_jit.hip);
   // any failure there leaves nothing launched and the interpreter below takes the call
-  if (row_vm_jit_wanted(p, n_columns, log_rows) &&
-      row_vm_jit_launch(p, d_columns, n_columns, log_rows, accumulate, L.consts, L.pow_lo, L.pow_hi, d_out, stream) == ZKHIP_OK)
+  if ((window ? row_vm_jit_wanted_window(p, n_columns, count) : row_vm_jit_wanted(p, n_columns, log_rows)) &&
+      row_vm_jit_launch(p, d_columns, n_columns, log_rows, window, L.row0, L.rows, accumulate, L.consts, L.pow_lo, L.pow_hi, d_out, stream) == ZKHIP_OK) {
+    if (compiled) *compiled = 1;
     return ZKHIP_OK;
+  }
   // smallest register-file variant that holds every register the program names
   return vm_launch_kernel(L, vm_top_register(p), 1, stream);
+}
+
+int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, int accumulate,
+                  uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, int* compiled) {
+  return row_vm_run(p, d_columns, n_columns, log_rows, false, 0, (uint64_t)1 << log_rows, accumulate, d_out, ws, ws_bytes, stream, staging, compiled);
+}
+
+int row_vm_window_device(const zkhip_vm_program* p, const void* const* d_windows, uint32_t n_columns, uint32_t log_rows, uint64_t row0, uint64_t count,
+                         int accumulate, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, int* compiled) {
+  return row_vm_run(p, d_windows, n_columns, log_rows, true, row0, count, accumulate, d_out, ws, ws_bytes, stream, staging, compiled);
 }
 
 int fr_pointwise_mul_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t* d_out, hipStream_t stream) {

@@ -87,6 +87,7 @@ struct gen {
   int tmp = 0;
   const zkhip_vm_program* p;
   uint64_t rows;
+  bool window = false;                 // columns are window buffers: index row + rot_rows[rot], no mask
   std::vector<uint32_t> rot_rows;
 
   void line(const std::string& s) { body += "  " + s + "\n"; }
@@ -114,7 +115,8 @@ struct gen {
       case ZKHIP_SRC_COLUMN: {
         const std::string t = fresh();
         const uint32_t off = rot_rows[o.rot];
-        line("const fe " + t + " = ldx<" + sh + ">(A.cols[" + std::to_string(o.index) + "], (row + " + std::to_string(off) + "ull) & (A.rows - 1));");
+        if (window) line("const fe " + t + " = ldx<" + sh + ">(A.cols[" + std::to_string(o.index) + "], row + " + std::to_string(off) + "ull);");
+        else line("const fe " + t + " = ldx<" + sh + ">(A.cols[" + std::to_string(o.index) + "], (row + " + std::to_string(off) + "ull) & (A.rows - 1));");
         v.expr = t;
         break;
       }
@@ -277,14 +279,19 @@ std::string cat(const char* const* chunks) {
   return s;
 }
 
-// the whole translation unit for program p over 2^log_rows rows; empty on a program the generator does not take
-std::string generate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows) {
+// the whole translation unit for program p over 2^log_rows rows; empty on a program the generator does not take.  window: the kernel
+// computes A.rows rows from global row A.row0 over window buffers (row_vm_window_device); one code object serves every row0 and count.
+std::string generate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, bool window = false) {
   gen g;
   g.p = p;
   g.rows = (uint64_t)1 << log_rows;
+  g.window = window;
   for (int i = 0; i < ZKHIP_VM_REGS; i++) { g.bound[i] = 0.0; g.used[i] = false; }
   g.rot_rows.assign(p->n_rotations ? p->n_rotations : 1, 0u);
+  uint64_t halo_lo = 0, halo_hi = 0;
+  row_vm_halos(p, &halo_lo, &halo_hi);
   for (uint32_t i = 0; i < p->n_rotations; i++) {
+    if (window) { g.rot_rows[i] = (uint32_t)((int64_t)halo_lo + (int64_t)p->rotations[i] * (int64_t)p->rot_scale); continue; }
     const int64_t off = ((int64_t)p->rotations[i] * (int64_t)p->rot_scale) % (int64_t)g.rows;
     g.rot_rows[i] = (uint32_t)(off < 0 ? off + (int64_t)g.rows : off);
   }
@@ -310,7 +317,8 @@ std::string generate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log
   src += cat(JIT_HDR_FP29);
   src += JIT_PRELUDE_HELPERS;
   src += "struct jit_args { const uint32_t* cols[" + std::to_string(n_columns ? n_columns : 1) +
-         "]; const uint32_t* consts; const uint32_t* pow_lo; const uint32_t* pow_hi; uint32_t* out; uint64_t rows; uint32_t accumulate; };\n";
+         "]; const uint32_t* consts; const uint32_t* pow_lo; const uint32_t* pow_hi; uint32_t* out; uint64_t rows; uint32_t accumulate;" +
+         std::string(window ? " uint64_t row0;" : "") + " };\n";
   src += "extern \"C\" __global__ void __launch_bounds__(256) zk_row_jit(const jit_args A) {\n";
   src += "  const uint64_t row = (uint64_t)blockIdx.x * 256 + threadIdx.x;\n  if (row >= A.rows) return;\n";
   std::string decl = "  fe";
@@ -319,9 +327,11 @@ std::string generate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log
     if (g.used[i]) { decl += std::string(any ? ", " : " ") + "r" + std::to_string(i) + " = fe_zero()"; any = true; }
   if (any) src += decl + ";\n";
   if (uses_prev) src += "  const fe vprev = A.accumulate ? ldx<0>(A.out, row) : fe_zero();\n";
-  if (uses_pow)
-    src += "  const fe vpow = fe_mul<Fr, false>(ldx<0>(A.pow_hi, row >> " + std::to_string(JIT_POW_LO_BITS) + "), ldx<5>(A.pow_lo, row & " +
+  if (uses_pow) {
+    const std::string prow = window ? "((A.row0 + row) & " + std::to_string(g.rows - 1) + "ull)" : std::string("row");
+    src += "  const fe vpow = fe_mul<Fr, false>(ldx<0>(A.pow_hi, " + prow + " >> " + std::to_string(JIT_POW_LO_BITS) + "), ldx<5>(A.pow_lo, " + prow + " & " +
            std::to_string((1u << JIT_POW_LO_BITS) - 1) + "ull));\n";
+  }
   src += g.body;
   src += "}\n";
   return src;
@@ -330,12 +340,13 @@ std::string generate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log
 // ---- cache ---------------------------------------------------------------------------------------------------------------------------------
 struct compiled { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; bool failed = false; };
 std::mutex g_jit_mu;
-std::map<std::string, compiled> g_jit_cache;       // key: device | rows | columns | the instruction bytes | scaled rotations | result register
+std::map<std::string, compiled> g_jit_cache;       // key: device | rows | window flag | columns | the instruction bytes | scaled rotations | result register
 
-std::string cache_key(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, int device) {
+std::string cache_key(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, int device, bool window) {
   std::string k;
   auto put = [&](const void* d, size_t n) { k.append((const char*)d, n); };
-  put(&device, sizeof(device)); put(&log_rows, sizeof(log_rows)); put(&n_columns, sizeof(n_columns));
+  const uint8_t w = window ? 1 : 0;                     // (never row0 / count: they are kernel arguments)
+  put(&device, sizeof(device)); put(&log_rows, sizeof(log_rows)); put(&w, 1); put(&n_columns, sizeof(n_columns));
   put(&p->n_insns, sizeof(p->n_insns)); put(p->insns, (size_t)p->n_insns * sizeof(zkhip_vm_insn));
   put(&p->n_rotations, sizeof(p->n_rotations));
   if (p->n_rotations) put(p->rotations, (size_t)p->n_rotations * 4);
@@ -351,13 +362,20 @@ bool row_vm_jit_wanted(const zkhip_vm_program* p, uint32_t n_columns, uint32_t l
   return m == 2 || log_rows >= 18;
 }
 
+// a window launch: the same limits, the row count is the window's
+bool row_vm_jit_wanted_window(const zkhip_vm_program* p, uint32_t n_columns, uint64_t count) {
+  const int m = jit_mode();
+  if (m == 0 || p->n_insns > JIT_MAX_INSNS || n_columns > JIT_MAX_COLUMNS) return false;
+  return m == 2 || count >= ((uint64_t)1 << 18);
+}
+
 // Launches the compiled kernel for p (compiling it on first use).  ZKHIP_OK: launched.  Any other status: nothing was launched and the caller
 // runs the interpreter (the reason is in set_error's text for the log, not an error of the call).
-int row_vm_jit_launch(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, int accumulate, const uint32_t* d_consts,
-                      const uint32_t* d_pow_lo, const uint32_t* d_pow_hi, uint32_t* d_out, hipStream_t stream) {
+int row_vm_jit_launch(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, bool window, uint64_t row0, uint64_t count,
+                      int accumulate, const uint32_t* d_consts, const uint32_t* d_pow_lo, const uint32_t* d_pow_hi, uint32_t* d_out, hipStream_t stream) {
   int device = 0;
   if (hipGetDevice(&device) != hipSuccess) return ZKHIP_EHIP;
-  const std::string key = cache_key(p, n_columns, log_rows, device);
+  const std::string key = cache_key(p, n_columns, log_rows, device, window);
   compiled c;
   {
     std::lock_guard<std::mutex> g(g_jit_mu);
@@ -366,7 +384,7 @@ int row_vm_jit_launch(const zkhip_vm_program* p, const void* const* d_columns, u
       compiled n;
       n.failed = true;
       const rtc_api& R = rtc();
-      const std::string src = R.ok ? generate(p, n_columns, log_rows) : std::string();
+      const std::string src = R.ok ? generate(p, n_columns, log_rows, window) : std::string();
       if (!src.empty()) {
         rtc_program prog = nullptr;
         if (R.create(&prog, src.c_str(), "zk_row_jit.hip", 0, nullptr, nullptr) == 0) {
@@ -395,7 +413,7 @@ int row_vm_jit_launch(const zkhip_vm_program* p, const void* const* d_columns, u
   }
   if (c.failed) { set_error("eval_rows: no compiled kernel for this program (hiprtc missing, compilation failed, or unsupported shape)"); return ZKHIP_EINVAL; }
   // kernel arguments: the jit_args struct by value
-  std::vector<unsigned char> args((size_t)(n_columns ? n_columns : 1) * 8 + 4 * 8 + 8 + 8, 0);
+  std::vector<unsigned char> args((size_t)(n_columns ? n_columns : 1) * 8 + 4 * 8 + 8 + 8 + 8, 0);
   size_t o = 0;
   for (uint32_t i = 0; i < n_columns; i++) { std::memcpy(args.data() + o, &d_columns[i], 8); o += 8; }
   if (n_columns == 0) o += 8;
@@ -403,10 +421,11 @@ int row_vm_jit_launch(const zkhip_vm_program* p, const void* const* d_columns, u
   std::memcpy(args.data() + o, &d_pow_lo, 8); o += 8;
   std::memcpy(args.data() + o, &d_pow_hi, 8); o += 8;
   std::memcpy(args.data() + o, &d_out, 8); o += 8;
-  const uint64_t rows = (uint64_t)1 << log_rows;
+  const uint64_t rows = window ? count : (uint64_t)1 << log_rows;
   std::memcpy(args.data() + o, &rows, 8); o += 8;
   const uint32_t acc = accumulate ? 1u : 0u;
   std::memcpy(args.data() + o, &acc, 4); o += 8;
+  if (window) { std::memcpy(args.data() + o, &row0, 8); o += 8; }
   size_t arg_size = o;
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &arg_size, HIP_LAUNCH_PARAM_END};
   const unsigned blocks = (unsigned)((rows + 255) / 256);

@@ -167,13 +167,20 @@ int row_vm_device_multi(const zkhip_vm_program* progs, uint32_t n_progs, const v
 // rowvm_jit.hip: row programs compiled at run time with hiprtc (straight-line code per program shape, cached per device); row_vm_device
 // tries it first for short programs over many rows and runs the interpreter otherwise
 bool row_vm_jit_wanted(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows);
-int row_vm_jit_launch(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, int accumulate, const uint32_t* d_consts,
-                      const uint32_t* d_pow_lo, const uint32_t* d_pow_hi, uint32_t* d_out, hipStream_t stream);
+bool row_vm_jit_wanted_window(const zkhip_vm_program* p, uint32_t n_columns, uint64_t count);
+int row_vm_jit_launch(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, bool window, uint64_t row0, uint64_t count,
+                      int accumulate, const uint32_t* d_consts, const uint32_t* d_pow_lo, const uint32_t* d_pow_hi, uint32_t* d_out, hipStream_t stream);
 void row_vm_jit_clear();
 int row_vm_jit_source(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, std::string* out);
 int row_vm_jit_compile_only(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, size_t* code_bytes);
 int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, int accumulate,
-                  uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging = nullptr);
+                  uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging = nullptr, int* compiled = nullptr);
+// Window form: `count` rows from global row `row0` of a 2^log_rows domain.  Column i is a window buffer of halo_lo + count + halo_hi elements,
+// element t = column[(row0 - halo_lo + t) mod 2^log_rows]; halos from row_vm_halos (o = rotation * rot_scale, not reduced: halo_lo = max(0, -o),
+// halo_hi = max(0, o) over the rotations).  ROWPOW is omega^((row0 + i) mod 2^log_rows); PREV / the output are out[i], i < count.
+void row_vm_halos(const zkhip_vm_program* p, uint64_t* lo, uint64_t* hi);
+int row_vm_window_device(const zkhip_vm_program* p, const void* const* d_windows, uint32_t n_columns, uint32_t log_rows, uint64_t row0, uint64_t count,
+                         int accumulate, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging = nullptr, int* compiled = nullptr);
 int fr_pointwise_mul_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t* d_out, hipStream_t stream);
 int fr_gather_mul_device(const uint32_t* d_a, uint32_t a_len, const uint32_t* d_ia, const uint32_t* d_b, uint32_t b_len, const uint32_t* d_ib, size_t n,
                          uint32_t* d_out, hipStream_t stream);

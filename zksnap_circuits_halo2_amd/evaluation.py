@@ -222,6 +222,23 @@ class RowProgram:
         _lib.check(_lib.load().zkhip_fr_eval_rows_device(C.byref(prog), ptrs, len(d_columns), log_rows, int(accumulate), d_out, stream))
         del keep
 
+    def halos(self, log_rows: int) -> Tuple[int, int]:
+        """(halo_lo, halo_hi) of a window over a 2^log_rows domain: with o = rotation * rot_scale (not reduced), halo_lo = max(0, -min o) and
+        halo_hi = max(0, max o).  A window buffer of `count` rows holds halo_lo + count + halo_hi elements (include/zkhip.h)."""
+        assert 0 <= log_rows <= 28
+        offs = [r * self.rot_scale for r in self.rotations]
+        return max([0] + [-o for o in offs]), max([0] + offs)
+
+    def run_window_device(self, d_windows: Sequence[int], log_rows: int, row0: int, count: int, d_out: int, accumulate: bool = False,
+                          stream: int = 0) -> None:
+        """`count` rows from global row `row0` of a 2^log_rows domain over window buffers (zkhip_fr_eval_rows_window_device): window t of
+        column c is column_c[(row0 - halo_lo + t) mod 2^log_rows], t < halo_lo + count + halo_hi; d_out receives `count` elements."""
+        assert len(d_windows) >= self.n_columns, "program reads more columns than were passed"
+        ptrs = (C.c_void_p * max(len(d_windows), 1))(*d_windows)
+        prog, keep = self._marshal()
+        _lib.check(_lib.load().zkhip_fr_eval_rows_window_device(C.byref(prog), ptrs, len(d_windows), log_rows, row0, count, int(accumulate), d_out, stream))
+        del keep
+
 
 def compile_graph(g: Graph, result: int, rot_scale: int = 1, omega: Optional[int] = None) -> RowProgram:
     """Lower the calculations `result` depends on to a RowProgram: creation order is a valid schedule (operands precede their
@@ -444,6 +461,23 @@ def run_programs_sum_device(progs: Sequence[RowProgram], weights: Sequence[int],
     w = F.fr_encode(list(weights))
     ptrs = (C.c_void_p * max(len(columns), 1))(*columns)
     _lib.check(lib.zkhip_fr_eval_rows_sum_device(arr, w.ctypes.data, len(progs), ptrs, len(columns), log_rows, C.c_void_p(out), C.c_void_p(stream)))
+
+
+COL_COEFF, COL_EXTENDED = 0, 1          # column forms of zkhip_fr_eval_rows_sharded_device
+
+
+def evaluate_rows_sharded_device(prog: RowProgram, columns: Sequence[Tuple[int, int]], k: int, ext_k: int, dom, d_out: int, stream: int = 0) -> None:
+    """The quotient numerator sharded by rows over the devices of zkhip_init (zkhip_fr_eval_rows_sharded_device).  `columns`: (device
+    address, form) per column -- COL_COEFF: 2^k coefficients, taken to the extended coset of `dom` (its extended_omega, g_coset) on the
+    device that owns the column; COL_EXTENDED: 2^ext_k coset values.  d_out receives the 2^ext_k values zkhip_fr_eval_rows_device would
+    write over the extended columns."""
+    assert len(columns) >= prog.n_columns, "program reads more columns than were passed"
+    ptrs = (C.c_void_p * max(len(columns), 1))(*[c[0] for c in columns])
+    forms = (C.c_uint32 * max(len(columns), 1))(*[c[1] for c in columns])
+    p, keep = prog._marshal()
+    _lib.check(_lib.load().zkhip_fr_eval_rows_sharded_device(C.byref(p), ptrs, forms, len(columns), k, ext_k, dom.extended_omega.ctypes.data,
+                                                             dom.g_coset.ctypes.data, d_out, stream))
+    del keep
 
 
 def linear_combination_program(coeffs: Sequence[int]) -> RowProgram:

@@ -211,12 +211,49 @@ int zkhip_fr_eval_rows_window_device(const zkhip_vm_program *prog, const void *c
  * No host thread waits for a device, except when S > 1 and a call needs more scratch than any call before it: then the previous call's
  * copies are waited for before the buffers they read are replaced.  With zkhip_profile_enable the call records the phases transform,
  * exchange, rows_compiled | rows_interpreted (the primary's executor) and gather on `stream`, for every S (exchange and gather are empty
- * intervals when S = 1).  ZKHIP_EINVAL: a null pointer, a form other than 0 / 1, k > ext_k, ext_k > 28, a program
+ * intervals when S = 1).  ZKHIP_EINVAL: a null pointer, a form other than 0 / 1 / 2, k > ext_k, ext_k > 28, a program
  * zkhip_fr_eval_rows_device rejects. */
 #define ZKHIP_COL_COEFF    0u
 #define ZKHIP_COL_EXTENDED 1u
+/* ZKHIP_COL_ROW_SHARDS: d_columns[c] is a HOST pointer to a zkhip_row_shard_ref naming column `col` of a row-shard set (below).  Device j
+ * passes its own window of that column to the window kernel, offset by (set halo_lo - program halo_lo) elements: no copy (S = 1: the whole-domain
+ * launch reads the same buffer from offset halo_lo).  ZKHIP_EINVAL, nothing enqueued, when the pointer is device memory, the set is not live,
+ * was made under another device count, has another ext_k, has halos narrower than the program's, or `col` is out of range. */
+#define ZKHIP_COL_ROW_SHARDS 2u
 int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program *prog, const void *const *d_columns, const uint32_t *forms, uint32_t n_columns,
                                       uint32_t k, uint32_t ext_k, const uint64_t ext_omega[4], const uint64_t zeta[4], void *d_out, void *stream);
+/* Row-shard sets: n_cols columns of a 2^ext_k domain cut by rows over the S devices zkhip_init has at creation, rows of device j =
+ * shard_range(2^ext_k, j, S) (the sharded evaluator's cut).  Device j holds, per column, one window buffer in the layout of
+ * zkhip_fr_eval_rows_window_device: halo_lo + count_j + halo_hi elements, element t = column[(row0_j - halo_lo + t) mod 2^ext_k] (also when the
+ * window is longer than the domain); one allocation per device, [col][W_j].  What they are for: the proving key's cosets stay on the device
+ * that evaluates their rows, from keygen / key load on, and the quotient pulls nothing from the primary for them.
+ * The `_device` calls are asynchronous on `stream` like the evaluator (secondaries start behind an entry event, the caller's stream waits for
+ * them): a set written on a stream and read by a call on the same stream needs no host sync.  _scatter_device / _gather_device: a whole column
+ * (2^ext_k elements on the primary) into / out of the set.  _upload: each device's window straight from host memory (hipMemcpy over that
+ * device's own link, device after device; the host buffer may be reused on return; waits for the set's earlier work first).  _window: the
+ * address, device ordinal, row0 and count of one shard's window of one column.  _destroy waits for the work enqueued on the set (its own
+ * events, not the devices) and frees it; zkhip_shutdown frees every set.  ZKHIP_EINVAL with a message, nothing enqueued: a handle the library
+ * did not issue or has freed, a set made under another device count, col / shard out of range, a null pointer. */
+typedef struct zkhip_row_shards zkhip_row_shards;
+typedef struct { const zkhip_row_shards *set; uint32_t col; } zkhip_row_shard_ref;
+int zkhip_row_shards_create(uint32_t ext_k, uint32_t n_cols, uint32_t halo_lo, uint32_t halo_hi, zkhip_row_shards **out);
+int zkhip_row_shards_destroy(zkhip_row_shards *set);
+int zkhip_row_shards_window(const zkhip_row_shards *set, uint32_t shard, uint32_t col, void **d_window, int *device, uint64_t *row0, uint64_t *count);
+int zkhip_row_shards_scatter_device(zkhip_row_shards *set, uint32_t col, const void *d_src, void *stream);
+int zkhip_row_shards_gather_device(const zkhip_row_shards *set, uint32_t col, void *d_dst, void *stream);
+int zkhip_row_shards_upload(zkhip_row_shards *set, uint32_t col, const void *host_src);
+/* Columns col0 .. col0 + n_polys - 1 of the set = coeff_to_extended(ext_omega, zeta) of n_polys polynomials of 2^k coefficients on the primary
+ * (polynomial i at d_coeff + i * coeff_stride elements): the bytes of zkhip_coeff_to_extended_device followed by a scatter.  The polynomials
+ * are spread over the devices by shard_range(n_polys, j, S); each owner transforms one at a time into a 2^ext_k scratch of its own (its own
+ * twiddle plan) and sends every device its window.  Nothing of n_polys x 2^ext_k is allocated. */
+int zkhip_coeff_to_extended_row_shards_device(const void *d_coeff, uint32_t k, uint32_t n_polys, size_t coeff_stride, const uint64_t ext_omega[4],
+                                              const uint64_t zeta[4], zkhip_row_shards *set, uint32_t col0, void *stream);
+/* Columns col0, col0 + 1, col0 + 2 of the set = the proving key's l0, l_last (row u) and l_active_row (rows < u) on the extended coset, for a
+ * 2^k domain with generator omega: l_i(X) = omega^i (X^n - 1) / (n (X - omega^i)) at X = zeta ext_omega^t, l_active = the shorter of
+ * sum_{i<u} l_i and 1 - sum_{i>=u} l_i.  Every device writes its own windows (one kernel, no transform, no copy); the bytes equal
+ * zkhip_ifft_scaled + zkhip_coeff_to_extended of the indicator columns.  ZKHIP_EINVAL unless 1 <= u < 2^k and k <= the set's ext_k. */
+int zkhip_lagrange_cosets_row_shards_device(uint32_t k, uint64_t usable_rows, const uint64_t omega[4], const uint64_t ext_omega[4], const uint64_t zeta[4],
+                                            zkhip_row_shards *set, uint32_t col0, void *stream);
 /* out[row] = sum_p weights[p] * progs[p](row): `n_progs` independent row programs over the same columns, run side by side in one launch
  * (one grid row per program) and combined with zkhip_fr_linear_combination_device's kernel.  Programs that read ZKHIP_SRC_ROWPOW must
  * name the same omega.  For programs that are

@@ -35,13 +35,18 @@ BLIND = 5
 _SIDE_STREAM = None
 
 
-def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False):
+def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False,
+        sharded_key=False):
     """sharded_quotient: the single-program quotient goes through zkhip_fr_eval_rows_sharded_device (rows cut over the devices of zkhip_init; the
     key's cosets EXTENDED, the proof's columns COEFF, transformed inside the call) instead of coeff_to_extended + the whole-domain launch.
+    sharded_key (needs sharded_quotient): the device key keeps its cosets as a row-shard set (keygen_device / from_host with row_shards) and the
+    quotient reads them as COL_ROW_SHARDS, where they lie -- nothing of the key crosses between devices during the proof.
     pk_file: path -- the proving key is written there (`ProvingKey::write`, RawBytesUnchecked), read back, and the READ key is what the
     prover uses (the reference's wrapper does the same through build/*_pk.bin: /root/reference/aggregator/src/wrapper.rs:967-989, :1007-1034)"""
     from zksnap_circuits_halo2_amd import keygen as KG
 
+    if sharded_key and not sharded_quotient:
+        raise ValueError("sharded_key needs sharded_quotient")
     lib = _lib.load()
     dev = torch.device("cuda", 0)
     n, u = 1 << k, (1 << k) - (BLIND + 1)
@@ -184,7 +189,7 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
         if pk_file is None:
             # the key is produced in HBM and stays there (keygen.keygen_device): sigma columns by gather, commitments against the
             # registered g_lagrange, transforms in place
-            dpk = KG.keygen_device(params, cs, [host(f) for f in fixed], assembly)
+            dpk = KG.keygen_device(params, cs, [host(f) for f in fixed], assembly, row_shards=sharded_key)
             vk = dpk.vk
             lap("keygen_device")
         else:
@@ -204,7 +209,7 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             assert same, "ProvingKey::read(ProvingKey::write(pk)) differs from pk"
             pk = pk2
             lap("pk_file_round_trip")
-            dpk = KG.DeviceProvingKey.from_host(pk, cs)
+            dpk = KG.DeviceProvingKey.from_host(pk, cs, row_shards=sharded_key)
             del pk, pk2
             lap("pk_upload")
 
@@ -290,7 +295,8 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
 
         for lo, hi in pk_ranges:
             for i in range(lo, hi):
-                KG._copy_device(ext[i].data_ptr(), key_cosets[i], ek)
+                if not sharded_key:
+                    KG._copy_device(ext[i].data_ptr(), key_cosets[i], ek)
         lap("keygen_coeff_to_extended")
         if sharded_quotient and ncol > 96 and ek < 18:
             raise ValueError("sharded_quotient: the sum-of-programs quotient of the wide circuits is not sharded")
@@ -304,7 +310,8 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             prog = E.evaluate_h_program(cs, k, ek, beta, gamma, theta, y)
             key = {i for lo, hi in pk_ranges for i in range(lo, hi)}
             h_ext = torch.empty((en, 4), dtype=torch.int64, device=dev)
-            E.evaluate_rows_sharded_device(prog, [(ext[i].data_ptr(), E.COL_EXTENDED) if i in key else (coeff[i].data_ptr(), E.COL_COEFF) for i in range(ncol)],
+            key_form = (lambda i: (key_cosets[i], E.COL_ROW_SHARDS)) if sharded_key else (lambda i: (ext[i].data_ptr(), E.COL_EXTENDED))
+            E.evaluate_rows_sharded_device(prog, [key_form(i) if i in key else (coeff[i].data_ptr(), E.COL_COEFF) for i in range(ncol)],
                                            k, ek, dom, h_ext.data_ptr())
             n_insns = len(prog.insns)
             n_regs = 1 + max([ins[1] for ins in prog.insns] + [o[1] for ins in prog.insns for o in ins[2:5] if o[0] == E.SRC_REG])

@@ -9,8 +9,14 @@ process.  Prints
   (d) S = 3 and S = 8 contexts of the same card: wall time (NOT a speed claim: every context is the same card) and the bytes each device
       receives / sends, COMPUTED from the copy plan (exchange_bytes restates it), not counted from the copies the library issues;
   (e) the 8-card projection of the quotient phase at k = 24, from one card's measured transform share and window kernel plus an ASSUMED
-      xGMI rate.
-`quotient_shard_time.py` (everything) | `quotient_shard_time.py windows` (only (c), the executor the environment selects)."""
+      xGMI rate, for both key forms;
+  (f) the key as a row-shard set (ZKHIP_COL_ROW_SHARDS): S = 1 against EXTENDED and against the composition, 5 repetitions each,
+      interleaved, in this process; S = 3 / 8 wall time on contexts of one card (not a speed claim) and the exchange bytes of both key
+      forms from the copy plan;
+  (g) the closed-form Lagrange kernel (zkhip_lagrange_cosets_row_shards_device) against the ifft + coeff_to_extended of the three
+      indicator columns it replaces, at ext_k = 24.
+`quotient_shard_time.py` (everything) | `quotient_shard_time.py windows` (only (c), the executor the environment selects) |
+`quotient_shard_time.py rowshards` (only (f) and (g)) | `quotient_shard_time.py keygen` (keygen_device at k = 22 with and without row_shards)."""
 import ctypes as C
 import os
 import random
@@ -19,6 +25,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import zksnap_circuits_halo2_amd as Z  # noqa: E402
@@ -97,17 +104,42 @@ def whole_vs_windows(prog, ek, parts=8):
     return whole, win
 
 
-def exchange_bytes(n_cols, n_coeff, k, ek, halo, S, j):
+def exchange_bytes(n_cols, n_coeff, k, ek, halo, S, j, key_shards=False):
     """bytes device j receives from other devices: its COEFF columns (pulled from the primary), the window pieces of every column it does
-    not hold itself, and (a secondary) nothing more -- its results leave it (sent bytes: count * 32)"""
+    not hold itself -- with key_shards the key's n_cols - n_coeff columns are already in its own windows -- and (a secondary) nothing more:
+    its results leave it (sent bytes: count * 32)"""
     N = 1 << ek
     lo, hi = shard_range(N, j, S)
     W = halo + (hi - lo)
     olo, ohi = shard_range(n_coeff, j, S)
     pulled = (ohi - olo) * (1 << k) * 32 if j else 0
-    n_ext = n_cols - n_coeff
+    n_ext = 0 if key_shards else n_cols - n_coeff
     remote_cols = (n_ext if j else 0) + (n_coeff - (ohi - olo))
     return pulled + remote_cols * W * 32, (hi - lo) * 32 if j else 0
+
+
+def primary_sent_bytes(n_cols, n_coeff, k, ek, halo, S, j, key_shards=False):
+    """bytes that leave the primary for device j (j > 0): j's COEFF columns, the windows of the COEFF columns the primary owns and (key
+    EXTENDED) the windows of the key's columns"""
+    if j == 0:
+        return 0
+    N = 1 << ek
+    lo, hi = shard_range(N, j, S)
+    W = halo + (hi - lo)
+    olo, ohi = shard_range(n_coeff, j, S)
+    own0 = shard_range(n_coeff, 0, S)[1]
+    n_ext = 0 if key_shards else n_cols - n_coeff
+    return (ohi - olo) * (1 << k) * 32 + (own0 + n_ext) * W * 32
+
+
+def plan_line(n_cols, n_coeff, k, ek, halo, S):
+    """per device received / sent-out-of-the-primary MB for both key forms, COMPUTED from the copy plan"""
+    parts = []
+    for key in (False, True):
+        moved = [(exchange_bytes(n_cols, n_coeff, k, ek, halo, S, j, key)[0], primary_sent_bytes(n_cols, n_coeff, k, ek, halo, S, j, key)) for j in range(S)]
+        parts.append(("row-shard key" if key else "EXTENDED key") + ": " + " ".join(f"{a / 2**20:.0f}/{b / 2**20:.0f}" for a, b in moved)
+                     + f" (primary sends {sum(b for _, b in moved) / 2**30:.2f} GiB)")
+    return "per device received / sent out of the primary MB, COMPUTED from the copy plan -- " + "; ".join(parts)
 
 
 def main():
@@ -179,11 +211,126 @@ def main():
     wout = torch.zeros((count, 4), dtype=torch.int64, device="cuda")
     wp = [w.data_ptr() for w in wcols]
     t_win = timed(lambda: prog8.run_window_device(wp, ek8, 3 * count, count, wout.data_ptr()), 3)
-    recv = max(exchange_bytes(qc.total, nC, k8, ek8, lo + hi, S, j)[0] for j in range(S))
-    t_link = recv / (LINK_GBPS * 1e9) * 1e3
-    print(f"(e) PROJECTION, ASSUMED link rate {LINK_GBPS:.0f} GB/s -- quotient phase at k = {k8} on {S} cards (unmeasured on multi-GPU hardware): "
-          f"per device {share} coset transform(s) 2^{k8}->2^{ek8} {t_tr:.3f} ms (measured) + window kernel 2^{ek8 - 3} rows {t_win:.3f} ms (measured) "
-          f"+ exchange {recv / 2**20:.0f} MB (computed from the copy plan) / {LINK_GBPS:.0f} GB/s = {t_link:.3f} ms (assumed rate) -> {t_tr + t_win + t_link:.3f} ms", flush=True)
+    for key in (False, True):
+        recv = max(exchange_bytes(qc.total, nC, k8, ek8, lo + hi, S, j, key)[0] for j in range(S))
+        t_link = recv / (LINK_GBPS * 1e9) * 1e3
+        print(f"(e) PROJECTION, ASSUMED link rate {LINK_GBPS:.0f} GB/s, key {'as row shards' if key else 'EXTENDED'} -- quotient phase at k = {k8} on {S} cards "
+              f"(unmeasured on multi-GPU hardware): per device {share} coset transform(s) 2^{k8}->2^{ek8} {t_tr:.3f} ms (measured) + window kernel "
+              f"2^{ek8 - 3} rows {t_win:.3f} ms (measured) + exchange {recv / 2**20:.0f} MB (computed from the copy plan) / {LINK_GBPS:.0f} GB/s = "
+              f"{t_link:.3f} ms (assumed rate) -> {t_tr + t_win + t_link:.3f} ms", flush=True)
+    print("(e) k = 24 on 8 cards, " + plan_line(qc.total, nC, k8, ek8, lo + hi, S), flush=True)
+
+
+def row_shard_key():
+    """(f) and (g)"""
+    k, ek = 22, 24
+    prog = E.evaluate_h_program(cs, k, ek, *CH)
+    lo, hi = prog.halos(ek)
+    dom = Z.EvaluationDomain(4, k)
+    torch.manual_seed(3)
+    cols = [rand(1 << (ek if f == E.COL_EXTENDED else k)) for f in FORMS]
+    coeff_idx = [i for i, f in enumerate(FORMS) if f == E.COL_COEFF]
+    key_idx = [i for i, f in enumerate(FORMS) if f == E.COL_EXTENDED]
+    nC = len(coeff_idx)
+    init(1)
+    ext = {i: torch.empty((1 << ek, 4), dtype=torch.int64, device="cuda") for i in coeff_idx}
+    out_a = torch.zeros((1 << ek, 4), dtype=torch.int64, device="cuda")
+    out_b, out_c = torch.zeros_like(out_a), torch.zeros_like(out_a)
+
+    def composition():
+        for i in coeff_idx:
+            _lib.check(lib.zkhip_coeff_to_extended_device(cols[i].data_ptr(), 1 << k, k, ext[i].data_ptr(), 1 << ek, ek, 1, dom.extended_omega.ctypes.data,
+                                                          dom.g_coset.ctypes.data, None))
+        prog.run_device([(ext[i] if i in ext else cols[i]).data_ptr() for i in range(qc.total)], ek, out_a.data_ptr())
+
+    def shards_of_key():
+        rs = E.RowShards(ek, len(key_idx), lo, hi)
+        for c, i in enumerate(key_idx):
+            rs.scatter_device(c, cols[i].data_ptr())
+        return rs
+
+    extended_cols = [(c.data_ptr(), f) for c, f in zip(cols, FORMS)]
+    rs = shards_of_key()
+    rs_cols = [(rs.ref(key_idx.index(i)), E.COL_ROW_SHARDS) if i in key_idx else (cols[i].data_ptr(), E.COL_COEFF) for i in range(qc.total)]
+    runs = {"composition": (composition, out_a),
+            "EXTENDED key": (lambda: E.evaluate_rows_sharded_device(prog, extended_cols, k, ek, dom, out_b.data_ptr()), out_b),
+            "row-shard key": (lambda: E.evaluate_rows_sharded_device(prog, rs_cols, k, ek, dom, out_c.data_ptr()), out_c)}
+    times = {name: [] for name in runs}
+    for fn, _ in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(REPS):                                    # interleaved: every repetition runs all three, one after another
+        for name, (fn, _) in runs.items():
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    assert torch.equal(out_a, out_b) and torch.equal(out_a, out_c)
+    print(f"(f) S = 1, k={k} ext_k={ek}, {REPS} interleaved repetitions each (ms, sorted): "
+          + "; ".join(f"{name} " + " ".join(f"{t:.3f}" for t in sorted(v)) for name, v in times.items()), flush=True)
+    rs.destroy()
+    del ext
+    torch.cuda.empty_cache()
+    for S in (3, 8):
+        init(S)
+        rs = shards_of_key()
+        rs_cols = [(rs.ref(key_idx.index(i)), E.COL_ROW_SHARDS) if i in key_idx else (cols[i].data_ptr(), E.COL_COEFF) for i in range(qc.total)]
+        out_d = torch.zeros_like(out_a)
+        te = timed(lambda: E.evaluate_rows_sharded_device(prog, extended_cols, k, ek, dom, out_d.data_ptr()))
+        assert torch.equal(out_d, out_a), S
+        out_d.zero_()
+        tr = timed(lambda: E.evaluate_rows_sharded_device(prog, rs_cols, k, ek, dom, out_d.data_ptr()))
+        assert torch.equal(out_d, out_a), S
+        rs.destroy()
+        print(f"(f) S = {S} contexts of ONE card (wall time, NOT a speed claim): EXTENDED key {te:8.3f} ms, row-shard key {tr:8.3f} ms; "
+              + plan_line(qc.total, nC, k, ek, lo + hi, S), flush=True)
+    init(1)
+    del cols, out_a, out_b, out_c
+    torch.cuda.empty_cache()
+    # (g) the Lagrange kernel against the three transforms it replaces
+    n, N = 1 << k, 1 << ek
+    u = n - (cs.blinding_factors + 1)
+    ind = torch.zeros((3, n, 4), dtype=torch.int64, device="cuda")
+    l_ext = torch.empty((3, N, 4), dtype=torch.int64, device="cuda")
+    one = torch.from_numpy(F.fr_encode([1]).view("int64")).cuda()[0]
+
+    def transforms():
+        ind.zero_()
+        ind[0, 0], ind[1, u], ind[2, :u] = one, one, one
+        _lib.check(lib.zkhip_ifft_scaled_batch_device(ind.data_ptr(), dom.omega_inv.ctypes.data, k, dom.ifft_divisor.ctypes.data, 3, n, None))
+        _lib.check(lib.zkhip_coeff_to_extended_device(ind.data_ptr(), n, k, l_ext.data_ptr(), N, ek, 3, dom.extended_omega.ctypes.data, dom.g_coset.ctypes.data, None))
+
+    rs = E.RowShards(ek, 3, lo, hi)
+    kernel = lambda: _lib.check(lib.zkhip_lagrange_cosets_row_shards_device(k, u, dom.omega.ctypes.data, dom.extended_omega.ctypes.data,
+                                                                            dom.g_coset.ctypes.data, rs.handle, 0, None))
+    tt, tk = timed(transforms), timed(kernel)
+    same = all(np.array_equal(rs.download(c), l_ext[c].cpu().numpy().view(np.uint64)) for c in range(3))
+    rs.destroy()
+    print(f"(g) l0 / l_last / l_active_row at k={k} ext_k={ek} (u = {u}): indicator columns + ifft_scaled + coeff_to_extended {tt:8.3f} ms, "
+          f"closed-form kernel {tk:8.3f} ms (equal bytes: {same})", flush=True)
+    assert same
+
+
+def keygen_timing():
+    """keygen_device at k = 22 on the wrapper shape's key (6 fixed, 7 sigma columns), warm, with and without row_shards"""
+    from zksnap_circuits_halo2_amd import keygen as KG
+    k = 22
+    n = 1 << k
+    init(1)
+    fixed = [rand(n).cpu().numpy().view(np.uint64) for _ in range(cs.num_fixed)]
+    asm = KG.Assembly(n, len(cs.permutation_columns))
+    rg = random.Random(5)
+    for _ in range(1000):
+        asm.copy(rg.randrange(len(cs.permutation_columns)), rg.randrange(n - 8), rg.randrange(len(cs.permutation_columns)), rg.randrange(n - 8))
+    with Z.ParamsKZG.setup(k, 0xBEEF) as params:
+        res = {}
+        for rs in (False, True, False, True):                # the first of each is the warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pk = KG.keygen_device(params, cs, fixed, asm, row_shards=rs)
+            res[rs] = (time.perf_counter() - t0) * 1e3
+            pk.free()
+    print(f"keygen_device k={k} (6 fixed + 7 sigma columns), warm: default {res[False]:.1f} ms, row_shards {res[True]:.1f} ms (one device)", flush=True)
 
 
 if __name__ == "__main__":
@@ -191,5 +338,10 @@ if __name__ == "__main__":
         prog = E.evaluate_h_program(cs, 22, 24, *CH)
         tw, tn = whole_vs_windows(prog, 24)
         print(f"(c) compiled     : whole-domain 2^24 {tw:8.3f} ms   8 windows of 2^21 in sequence {tn:8.3f} ms   ratio {tn / tw:.4f}")
+    elif sys.argv[1:] == ["rowshards"]:
+        row_shard_key()
+    elif sys.argv[1:] == ["keygen"]:
+        keygen_timing()
     else:
         main()
+        row_shard_key()

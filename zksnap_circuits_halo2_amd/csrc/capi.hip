@@ -258,6 +258,20 @@ struct registered_t {  // one zkhip_register_bases call
   ~registered_t();
 };
 
+// A row-shard set (zkhip_row_shards_create): n_cols columns of a 2^ext_k domain cut by rows over the S devices of zkhip_init, device j holding
+// [col][W_j] window buffers (W_j = halo_lo + count_j + halo_hi) in one allocation.  `last` keeps, per device, one event per stream that has
+// enqueued work on the set: destroy waits for those, not for the devices.
+struct row_shards_t {
+  uint32_t ext_k = 0, n_cols = 0;
+  uint64_t halo_lo = 0, halo_hi = 0;
+  int S = 0;
+  std::vector<void*> mem;
+  std::vector<uint64_t> row0, count;
+  std::vector<std::map<hipStream_t, hipEvent_t>> last;
+  uint64_t W(int j) const { return halo_lo + count[(size_t)j] + halo_hi; }
+  uint32_t* window(int j, uint32_t col) const { return (uint32_t*)mem[(size_t)j] + (size_t)col * W(j) * 8; }
+};
+
 struct context {
   bool ready = false;
   std::vector<device_ctx*> devs;       // devs[0] = primary
@@ -266,6 +280,8 @@ struct context {
   std::map<const void*, std::shared_ptr<registered_t>> registered;
   std::map<uint64_t, prepared_bases*> handles;          // zkhip_prepare_bases_device handles (primary device)
   uint64_t next_handle = 1;
+  std::map<uintptr_t, row_shards_t*> sets;              // live row-shard sets by handle (handles are never reused)
+  uintptr_t next_set = 0x10;
 };
 
 static std::recursive_mutex g_mu;
@@ -413,6 +429,120 @@ static void destroy_device_ctx(device_ctx* d) {
   delete d;
 }
 
+// ---- row-shard sets (g_mu held) ----------------------------------------------------------------------------------------
+static void wait_row_shards(row_shards_t* R) {
+  for (size_t j = 0; j < R->last.size() && j < g_ctx.devs.size(); j++) {
+    (void)hipSetDevice(g_ctx.devs[j]->device);
+    for (auto& kv : R->last[j]) (void)hipEventSynchronize(kv.second);
+  }
+  if (!g_ctx.devs.empty()) (void)hipSetDevice(primary().device);
+}
+
+static void free_row_shards(row_shards_t* R) {
+  wait_row_shards(R);
+  for (size_t j = 0; j < R->mem.size(); j++) {
+    if (j < g_ctx.devs.size()) (void)hipSetDevice(g_ctx.devs[j]->device);
+    for (auto& kv : R->last[j]) (void)hipEventDestroy(kv.second);
+    if (R->mem[j]) (void)hipFree(R->mem[j]);
+  }
+  if (!g_ctx.devs.empty()) (void)hipSetDevice(primary().device);
+  (void)hipGetLastError();
+  delete R;
+}
+
+// the live set behind a handle, made under the current device count (else ZKHIP_EINVAL with a message, nothing touched)
+static row_shards_t* find_row_shards(const zkhip_row_shards* h, const char* who) {
+  auto it = g_ctx.sets.find((uintptr_t)h);
+  if (!h || it == g_ctx.sets.end()) { set_error("%s: not a live row-shard set (destroyed, freed by zkhip_shutdown, or never issued)", who); return nullptr; }
+  if (it->second->S != (int)g_ctx.devs.size()) { set_error("%s: set made over %d devices, zkhip_init has %zu", who, it->second->S, g_ctx.devs.size()); return nullptr; }
+  return it->second;
+}
+
+// device j is current; the set's event for `st` on device j follows the work just enqueued there
+static int touch_row_shards(row_shards_t* R, int j, hipStream_t st) {
+  auto& m = R->last[(size_t)j];
+  auto it = m.find(st);
+  if (it == m.end()) {
+    hipEvent_t e = nullptr;
+    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    it = m.emplace(st, e).first;
+  }
+  HIPCHK(hipEventRecord(it->second, st));
+  return ZKHIP_OK;
+}
+
+// window pieces: dst[t] = src[(start + t) mod N] for t < W, as at most ceil(W / N) + 1 copies on `st`
+static int copy_window(uint32_t* dst, int dst_dev, const uint32_t* src, int src_dev, size_t start, size_t W, size_t N, hipStream_t st) {
+  for (size_t t = 0, pos = start; t < W;) {
+    const size_t len = std::min(W - t, N - pos);
+    HIPCHK(hipMemcpyPeerAsync(dst + t * 8, dst_dev, src + pos * 8, src_dev, len * 32, st));
+    t += len;
+    pos = 0;
+  }
+  return ZKHIP_OK;
+}
+
+static inline size_t window_start(uint64_t row0, uint64_t halo_lo, size_t N) {
+  return (size_t)((((int64_t)row0 - (int64_t)halo_lo) % (int64_t)N + (int64_t)N) % (int64_t)N);
+}
+
+// One multi-device `_device` call over a set (g_fanout_mu and g_mu held): st[j] is the caller's stream on the primary and device j's fan
+// stream elsewhere; every secondary starts behind an entry event on the caller's stream, and `end` makes the caller's stream wait for them.
+// On an error after something was enqueued the destructor waits for those streams, so that nothing outlives the call's buffers.
+struct fan_call {
+  std::vector<hipStream_t> st;
+  std::vector<bool> used;
+  bool armed = true;
+  int begin(hipStream_t s) {
+    const int S = (int)g_ctx.devs.size();
+    st.assign((size_t)S, nullptr);
+    used.assign((size_t)S, false);
+    st[0] = s;
+    if (S == 1) return ZKHIP_OK;
+    device_ctx& P = primary();
+    if (!P.fan_ready) HIPCHK(hipEventCreateWithFlags(&P.fan_ready, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(P.fan_ready, s));
+    for (int j = 1; j < S; j++) {
+      device_ctx* D = g_ctx.devs[(size_t)j];
+      if (hipSetDevice(D->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", D->device); return ZKHIP_ENODEV; }
+      if (!D->fan) {
+        HIPCHK(hipStreamCreateWithFlags(&D->fan, hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&D->fan_done, hipEventDisableTiming));
+      }
+      st[(size_t)j] = D->fan;
+      HIPCHK(hipStreamWaitEvent(D->fan, P.fan_ready, 0));
+    }
+    (void)hipSetDevice(P.device);
+    return ZKHIP_OK;
+  }
+  int dev(int j) {
+    used[(size_t)j] = true;
+    if (hipSetDevice(g_ctx.devs[(size_t)j]->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", g_ctx.devs[(size_t)j]->device); return ZKHIP_ENODEV; }
+    return ZKHIP_OK;
+  }
+  int end() {
+    const int S = (int)st.size();
+    for (int j = 1; j < S; j++) {
+      if (!used[(size_t)j]) continue;
+      device_ctx* D = g_ctx.devs[(size_t)j];
+      if (hipSetDevice(D->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", D->device); return ZKHIP_ENODEV; }
+      HIPCHK(hipEventRecord(D->fan_done, D->fan));
+    }
+    if (hipSetDevice(primary().device) != hipSuccess) { set_error("hipSetDevice(%d) failed", primary().device); return ZKHIP_ENODEV; }
+    for (int j = 1; j < S; j++)
+      if (used[(size_t)j]) HIPCHK(hipStreamWaitEvent(st[0], g_ctx.devs[(size_t)j]->fan_done, 0));
+    armed = false;
+    return ZKHIP_OK;
+  }
+  ~fan_call() {
+    if (!armed) return;
+    for (size_t j = 0; j < st.size(); j++)
+      if (used[j]) { (void)hipSetDevice(g_ctx.devs[j]->device); (void)hipStreamSynchronize(st[j]); }
+    if (!g_ctx.devs.empty()) (void)hipSetDevice(primary().device);
+    (void)hipGetLastError();
+  }
+};
+
 }  // namespace zkhip
 
 using namespace zkhip;
@@ -503,6 +633,8 @@ void zkhip_shutdown(void) {
   g_ctx.registered.clear();                                  // last references: tables are freed by ~registered_t
   for (auto& kv : g_ctx.handles) release_prepared(kv.second);
   g_ctx.handles.clear();
+  for (auto& kv : g_ctx.sets) free_row_shards(kv.second);
+  g_ctx.sets.clear();
   for (auto d : g_ctx.devs) destroy_device_ctx(d);
   g_ctx.devs.clear();
   g_ctx.ready = false;
@@ -1813,15 +1945,43 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
   if (!prog || !d_out || !ext_omega || !zeta || (n_columns && (!d_columns || !forms))) { set_error("eval_rows_sharded: null pointer"); return ZKHIP_EINVAL; }
   if (k > ext_k || ext_k > 28) { set_error("eval_rows_sharded: k = %u, ext_k = %u out of range", k, ext_k); return ZKHIP_EINVAL; }
   if ((rc = row_vm_validate(prog, n_columns, ext_k, 0)) != ZKHIP_OK) return rc;
-  std::vector<uint32_t> coeff_cols;                        // argument indices of the COEFF columns
-  for (uint32_t i = 0; i < n_columns; i++) {
-    if (!d_columns[i]) { set_error("eval_rows_sharded: column %u is null", i); return ZKHIP_EINVAL; }
-    if (forms[i] > ZKHIP_COL_EXTENDED) { set_error("eval_rows_sharded: column %u has form %u", i, forms[i]); return ZKHIP_EINVAL; }
-    if (forms[i] == ZKHIP_COL_COEFF) coeff_cols.push_back(i);
-  }
   uint64_t halo_lo = 0, halo_hi = 0;
   row_vm_halos(prog, &halo_lo, &halo_hi);
   if (halo_lo + halo_hi >= ((uint64_t)1 << 31)) { set_error("eval_rows_sharded: halos too wide"); return ZKHIP_EINVAL; }
+  std::vector<uint32_t> coeff_cols;                        // argument indices of the COEFF columns
+  std::vector<const row_shards_t*> rs_set(n_columns, nullptr);   // ZKHIP_COL_ROW_SHARDS columns: the set and column behind the reference
+  std::vector<uint32_t> rs_col(n_columns, 0);
+  uint32_t n_copied = 0;                                   // columns whose windows this call fills (COEFF and EXTENDED)
+  for (uint32_t i = 0; i < n_columns; i++) {
+    if (!d_columns[i]) { set_error("eval_rows_sharded: column %u is null", i); return ZKHIP_EINVAL; }
+    if (forms[i] > ZKHIP_COL_ROW_SHARDS) { set_error("eval_rows_sharded: column %u has form %u", i, forms[i]); return ZKHIP_EINVAL; }
+    if (forms[i] == ZKHIP_COL_COEFF) coeff_cols.push_back(i);
+    if (forms[i] != ZKHIP_COL_ROW_SHARDS) { n_copied++; continue; }
+    // the reference is a host struct: a device address here is a caller's mistake, refused before anything reads it
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, d_columns[i]) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeArray)) {
+      set_error("eval_rows_sharded: column %u has form ZKHIP_COL_ROW_SHARDS but a device address (a zkhip_row_shard_ref is host memory)", i);
+      return ZKHIP_EINVAL;
+    }
+    (void)hipGetLastError();
+    const zkhip_row_shard_ref ref = *(const zkhip_row_shard_ref*)d_columns[i];
+    const row_shards_t* R = find_row_shards(ref.set, "eval_rows_sharded");
+    if (!R) return ZKHIP_EINVAL;
+    if (ref.col >= R->n_cols || R->ext_k != ext_k || R->halo_lo < halo_lo || R->halo_hi < halo_hi) {
+      set_error("eval_rows_sharded: column %u: set column %u of %u, ext_k %u (call %u), halos %llu / %llu (program %llu / %llu)", i, ref.col, R->n_cols, R->ext_k,
+                ext_k, (unsigned long long)R->halo_lo, (unsigned long long)R->halo_hi, (unsigned long long)halo_lo, (unsigned long long)halo_hi);
+      return ZKHIP_EINVAL;
+    }
+    rs_set[i] = R;
+    rs_col[i] = ref.col;
+  }
+  // device j's window of a ZKHIP_COL_ROW_SHARDS column in the program's halos; the set's event on (j, stream) follows the launch that reads it
+  auto rs_window = [&](int j, uint32_t c) -> const void* { return rs_set[c]->window(j, rs_col[c]) + (rs_set[c]->halo_lo - halo_lo) * 8; };
+  auto rs_touch = [&](int j, hipStream_t st) -> int {
+    for (uint32_t c = 0; c < n_columns; c++)
+      if (rs_set[c]) { int r = touch_row_shards(const_cast<row_shards_t*>(rs_set[c]), j, st); if (r != ZKHIP_OK) return r; }
+    return ZKHIP_OK;
+  };
   hipStream_t s = caller_stream(stream);
   const int S = (int)g_ctx.devs.size();
   const size_t N = (size_t)1 << ext_k, n_in = (size_t)1 << k, nC = coeff_cols.size();
@@ -1834,6 +1994,8 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     // the cosets go to the caller stream's scratch set: calls on other streams have sets of their own, calls on this one are ordered by it
     if ((rc = sc->q_ext.reserve(std::max<size_t>(nC, 1) * N * 32)) != ZKHIP_OK) return rc;
     std::vector<const void*> cols(d_columns, d_columns + n_columns);
+    for (uint32_t c = 0; c < n_columns; c++)
+      if (rs_set[c]) cols[c] = rs_set[c]->window(0, rs_col[c]) + rs_set[c]->halo_lo * 8;   // the whole column sits behind the set's halo_lo
     {
       prof_hold hold;
       for (size_t c = 0; c < nC; c++) {
@@ -1848,6 +2010,7 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     if ((rc = sc->vm.reserve(row_vm_workspace_bytes(prog, n_columns, ext_k))) != ZKHIP_OK) return rc;
     int compiled = 0;
     if ((rc = row_vm_device(prog, cols.data(), n_columns, ext_k, 0, (uint32_t*)d_out, sc->vm.p, sc->vm.cap, s, &sc->vm_stage, &compiled)) != ZKHIP_OK) return rc;
+    if ((rc = rs_touch(0, s)) != ZKHIP_OK) return rc;
     prof_mark(s, compiled ? "rows_compiled" : "rows_interpreted");
     prof_mark(s, "gather");
     return ZKHIP_OK;
@@ -1879,7 +2042,7 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     size_t lo, hi, olo, ohi;
     shard_range(N, j, S, &lo, &hi);
     shard_range(nC, j, S, &olo, &ohi);
-    grows |= D->q_ext.cap < std::max<size_t>(ohi - olo, 1) * N * 32 || D->q_win.cap < std::max<size_t>(n_columns, 1) * (halo_lo + hi - lo + halo_hi) * 32 ||
+    grows |= D->q_ext.cap < std::max<size_t>(ohi - olo, 1) * N * 32 || D->q_win.cap < std::max<size_t>(n_copied, 1) * (halo_lo + hi - lo + halo_hi) * 32 ||
              (j > 0 && D->q_out.cap < std::max<size_t>(hi - lo, 1) * 32);
   }
   // a buffer about to be replaced may still be read by another device's copies of the previous call: the ONE place this call blocks the host
@@ -1905,7 +2068,7 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     own_n[j] -= own_lo[j];
     const size_t W = halo_lo + row_n[j] + halo_hi;
     if ((rc = D->q_ext.reserve(std::max<size_t>(own_n[j], 1) * N * 32)) != ZKHIP_OK) return rc;
-    if ((rc = D->q_win.reserve(std::max<size_t>(n_columns, 1) * W * 32)) != ZKHIP_OK) return rc;
+    if ((rc = D->q_win.reserve(std::max<size_t>(n_copied, 1) * W * 32)) != ZKHIP_OK) return rc;
     if (j > 0 && (rc = D->q_out.reserve(std::max<size_t>(row_n[j], 1) * 32)) != ZKHIP_OK) return rc;
     if ((rc = dsc[j]->vm.reserve(row_vm_workspace_bytes(prog, n_columns, ext_k))) != ZKHIP_OK) return rc;
   }
@@ -1947,7 +2110,9 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
       if (own_n[i]) HIPCHK(hipStreamWaitEvent(st[j], g_ctx.devs[(size_t)i]->q_transformed, 0));
     const size_t W = halo_lo + row_n[j] + halo_hi;
     const size_t start = (size_t)((((int64_t)row_lo[j] - (int64_t)halo_lo) % (int64_t)N + (int64_t)N) % (int64_t)N);
+    uint32_t slot = 0;                                     // this device's window buffers, one per copied column
     for (uint32_t c = 0; c < n_columns; c++) {
+      if (rs_set[c]) { win[c] = rs_window(j, c); continue; }
       const uint32_t* src;
       int src_dev;
       if (forms[c] == ZKHIP_COL_EXTENDED) { src = (const uint32_t*)d_columns[c]; src_dev = P.device; }
@@ -1958,7 +2123,7 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
         src = (const uint32_t*)g_ctx.devs[(size_t)o]->q_ext.p + (ci - own_lo[o]) * N * 8;
         src_dev = g_ctx.devs[(size_t)o]->device;
       }
-      uint32_t* dst = (uint32_t*)D->q_win.p + (size_t)c * W * 8;
+      uint32_t* dst = (uint32_t*)D->q_win.p + (size_t)slot++ * W * 8;
       win[c] = dst;
       for (size_t t = 0, pos = start; t < W;) {              // at most ceil(W / N) + 1 pieces
         const size_t len = std::min(W - t, N - pos);
@@ -1972,6 +2137,7 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     int compiled = 0;
     if ((rc = row_vm_window_device(prog, win.data(), n_columns, ext_k, row_lo[j], row_n[j], 0, out, dsc[j]->vm.p, dsc[j]->vm.cap, st[j], &dsc[j]->vm_stage,
                                    &compiled)) != ZKHIP_OK) return rc;
+    if ((rc = rs_touch(j, st[j])) != ZKHIP_OK) return rc;
     if (j == 0) prof_mark(s, compiled ? "rows_compiled" : "rows_interpreted");
     else HIPCHK(hipMemcpyPeerAsync((uint32_t*)d_out + row_lo[j] * 8, P.device, out, D->device, row_n[j] * 32, st[j]));
     HIPCHK(hipEventRecord(D->q_done, st[j]));
@@ -1983,6 +2149,234 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
   prof_mark(s, "gather");
   drain.armed = false;
   return ZKHIP_OK;
+}
+
+// ---- row-shard sets (include/zkhip.h) -------------------------------------------------------------------------------------
+int zkhip_row_shards_create(uint32_t ext_k, uint32_t n_cols, uint32_t halo_lo, uint32_t halo_hi, zkhip_row_shards** out) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if (!out) { set_error("row_shards_create: null pointer"); return ZKHIP_EINVAL; }
+  *out = nullptr;
+  if (ext_k > 28 || n_cols == 0 || (uint64_t)halo_lo + halo_hi >= ((uint64_t)1 << 31)) {
+    set_error("row_shards_create: ext_k = %u, n_cols = %u, halos %u + %u", ext_k, n_cols, halo_lo, halo_hi);
+    return ZKHIP_EINVAL;
+  }
+  const int S = (int)g_ctx.devs.size();
+  const size_t N = (size_t)1 << ext_k;
+  row_shards_t* R = new row_shards_t();
+  R->ext_k = ext_k; R->n_cols = n_cols; R->halo_lo = halo_lo; R->halo_hi = halo_hi; R->S = S;
+  R->mem.assign((size_t)S, nullptr);
+  R->last.resize((size_t)S);
+  for (int j = 0; j < S; j++) {
+    size_t lo, hi;
+    shard_range(N, j, S, &lo, &hi);
+    R->row0.push_back(lo);
+    R->count.push_back(hi - lo);
+  }
+  for (int j = 0; j < S; j++) {
+    (void)hipSetDevice(g_ctx.devs[(size_t)j]->device);
+    const size_t bytes = (size_t)n_cols * R->W(j) * 32;
+    if (hipMalloc(&R->mem[(size_t)j], std::max<size_t>(bytes, 32)) != hipSuccess) {
+      (void)hipGetLastError();
+      R->mem[(size_t)j] = nullptr;
+      free_row_shards(R);
+      set_error("row_shards_create: hipMalloc(%zu) failed on device %d", bytes, j);
+      return ZKHIP_ENOMEM;
+    }
+  }
+  (void)hipSetDevice(primary().device);
+  const uintptr_t h = g_ctx.next_set;
+  g_ctx.next_set += 0x10;
+  g_ctx.sets[h] = R;
+  *out = (zkhip_row_shards*)h;
+  return ZKHIP_OK;
+}
+
+int zkhip_row_shards_destroy(zkhip_row_shards* set) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  auto it = g_ctx.sets.find((uintptr_t)set);
+  if (!set || it == g_ctx.sets.end()) { set_error("row_shards_destroy: not a live row-shard set"); return ZKHIP_EINVAL; }
+  row_shards_t* R = it->second;
+  g_ctx.sets.erase(it);
+  free_row_shards(R);
+  return ZKHIP_OK;
+}
+
+int zkhip_row_shards_window(const zkhip_row_shards* set, uint32_t shard, uint32_t col, void** d_window, int* device, uint64_t* row0, uint64_t* count) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  row_shards_t* R = find_row_shards(set, "row_shards_window");
+  if (!R) return ZKHIP_EINVAL;
+  if (shard >= (uint32_t)R->S || col >= R->n_cols) { set_error("row_shards_window: shard %u / col %u out of range (%d shards, %u columns)", shard, col, R->S, R->n_cols); return ZKHIP_EINVAL; }
+  if (d_window) *d_window = R->window((int)shard, col);
+  if (device) *device = g_ctx.devs[shard]->device;
+  if (row0) *row0 = R->row0[shard];
+  if (count) *count = R->count[shard];
+  return ZKHIP_OK;
+}
+
+int zkhip_row_shards_scatter_device(zkhip_row_shards* set, uint32_t col, const void* d_src, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  row_shards_t* R = find_row_shards(set, "row_shards_scatter");
+  if (!R) return ZKHIP_EINVAL;
+  if (col >= R->n_cols || !d_src) { set_error("row_shards_scatter: col %u out of range or null source", col); return ZKHIP_EINVAL; }
+  const size_t N = (size_t)1 << R->ext_k;
+  std::unique_lock<std::mutex> fan(g_fanout_mu);
+  fan_call F;
+  if ((rc = F.begin(caller_stream(stream))) != ZKHIP_OK) return rc;
+  for (int j = 0; j < R->S; j++) {
+    if ((rc = F.dev(j)) != ZKHIP_OK) return rc;
+    if ((rc = copy_window(R->window(j, col), g_ctx.devs[(size_t)j]->device, (const uint32_t*)d_src, primary().device, window_start(R->row0[(size_t)j], R->halo_lo, N),
+                          R->W(j), N, F.st[(size_t)j])) != ZKHIP_OK) return rc;
+    if ((rc = touch_row_shards(R, j, F.st[(size_t)j])) != ZKHIP_OK) return rc;
+  }
+  return F.end();
+}
+
+int zkhip_row_shards_gather_device(const zkhip_row_shards* set, uint32_t col, void* d_dst, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  row_shards_t* R = find_row_shards(set, "row_shards_gather");
+  if (!R) return ZKHIP_EINVAL;
+  if (col >= R->n_cols || !d_dst) { set_error("row_shards_gather: col %u out of range or null destination", col); return ZKHIP_EINVAL; }
+  std::unique_lock<std::mutex> fan(g_fanout_mu);
+  fan_call F;
+  if ((rc = F.begin(caller_stream(stream))) != ZKHIP_OK) return rc;
+  for (int j = 0; j < R->S; j++) {
+    if ((rc = F.dev(j)) != ZKHIP_OK) return rc;
+    if (R->count[(size_t)j])
+      HIPCHK(hipMemcpyPeerAsync((uint32_t*)d_dst + R->row0[(size_t)j] * 8, primary().device, R->window(j, col) + R->halo_lo * 8, g_ctx.devs[(size_t)j]->device,
+                                R->count[(size_t)j] * 32, F.st[(size_t)j]));
+    if ((rc = touch_row_shards(R, j, F.st[(size_t)j])) != ZKHIP_OK) return rc;
+  }
+  return F.end();
+}
+
+int zkhip_row_shards_upload(zkhip_row_shards* set, uint32_t col, const void* host_src) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  row_shards_t* R = find_row_shards(set, "row_shards_upload");
+  if (!R) return ZKHIP_EINVAL;
+  if (col >= R->n_cols || !host_src) { set_error("row_shards_upload: col %u out of range or null source", col); return ZKHIP_EINVAL; }
+  const size_t N = (size_t)1 << R->ext_k;
+  wait_row_shards(R);                                      // earlier work on the set (readers included) is done before it is overwritten
+  for (int j = 0; j < R->S; j++) {
+    if (hipSetDevice(g_ctx.devs[(size_t)j]->device) != hipSuccess) { set_error("hipSetDevice failed"); return ZKHIP_ENODEV; }
+    uint32_t* dst = R->window(j, col);
+    const uint32_t* src = (const uint32_t*)host_src;
+    const size_t W = R->W(j);
+    for (size_t t = 0, pos = window_start(R->row0[(size_t)j], R->halo_lo, N); t < W;) {
+      const size_t len = std::min(W - t, N - pos);
+      if (hipMemcpy(dst + t * 8, src + pos * 8, len * 32, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipSetDevice(primary().device); set_error("row_shards_upload: copy to device %d failed", j); return ZKHIP_EHIP;
+      }
+      t += len;
+      pos = 0;
+    }
+  }
+  (void)hipSetDevice(primary().device);
+  return ZKHIP_OK;
+}
+
+int zkhip_coeff_to_extended_row_shards_device(const void* d_coeff, uint32_t k, uint32_t n_polys, size_t coeff_stride, const uint64_t ext_omega[4],
+                                              const uint64_t zeta[4], zkhip_row_shards* set, uint32_t col0, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  row_shards_t* R = find_row_shards(set, "coeff_to_extended_row_shards");
+  if (!R) return ZKHIP_EINVAL;
+  if (!ext_omega || !zeta || (n_polys && !d_coeff)) { set_error("coeff_to_extended_row_shards: null pointer"); return ZKHIP_EINVAL; }
+  if (k > R->ext_k || (uint64_t)col0 + n_polys > R->n_cols || coeff_stride < ((size_t)1 << k) || coeff_stride >= ((size_t)1 << 32)) {
+    set_error("coeff_to_extended_row_shards: k = %u (ext_k %u), columns %u + %u of %u, stride %zu", k, R->ext_k, col0, n_polys, R->n_cols, coeff_stride);
+    return ZKHIP_EINVAL;
+  }
+  if (n_polys == 0) return ZKHIP_OK;
+  const uint32_t ext_k = R->ext_k;
+  const size_t N = (size_t)1 << ext_k, n_in = (size_t)1 << k;
+  uint32_t scales[24];
+  coset_scales(zeta, nullptr, scales);
+  hipStream_t s = caller_stream(stream);
+  std::unique_lock<std::mutex> fan(g_fanout_mu);
+  fan_call F;
+  if ((rc = F.begin(s)) != ZKHIP_OK) return rc;
+  for (int j = 0; j < R->S; j++) {
+    size_t lo, hi;
+    shard_range(n_polys, j, R->S, &lo, &hi);
+    if (lo == hi) continue;
+    device_ctx* D = g_ctx.devs[(size_t)j];
+    if ((rc = F.dev(j)) != ZKHIP_OK) return rc;
+    hipStream_t st = F.st[(size_t)j];
+    scratch* dsc = scratch_for(*D, st);
+    if ((rc = dsc->q_ext.reserve(N * 32)) != ZKHIP_OK) return rc;
+    uint32_t* ext = (uint32_t*)dsc->q_ext.p;
+    for (size_t c = lo; c < hi; c++) {
+      const uint32_t* src = (const uint32_t*)d_coeff + c * coeff_stride * 8;
+      if ((rc = F.dev(j)) != ZKHIP_OK) return rc;
+      if (j == 0) {
+        if ((rc = run_transform(dsc, src, (uint32_t)n_in, (uint32_t)n_in, ext, (uint32_t)N, (uint32_t)N, 1, ext_k, (const uint32_t*)ext_omega, scales, 3, nullptr, 0,
+                                st)) != ZKHIP_OK) return rc;
+      } else {
+        HIPCHK(hipMemcpyPeerAsync(ext, D->device, src, primary().device, n_in * 32, st));
+        if ((rc = run_transform(dsc, ext, (uint32_t)n_in, (uint32_t)N, ext, (uint32_t)N, (uint32_t)N, 1, ext_k, (const uint32_t*)ext_omega, scales, 3, nullptr, 0,
+                                st)) != ZKHIP_OK) return rc;
+      }
+      for (int i = 0; i < R->S; i++)
+        if ((rc = copy_window(R->window(i, col0 + (uint32_t)c), g_ctx.devs[(size_t)i]->device, ext, D->device, window_start(R->row0[(size_t)i], R->halo_lo, N),
+                              R->W(i), N, st)) != ZKHIP_OK) return rc;
+    }
+    if ((rc = touch_row_shards(R, j, st)) != ZKHIP_OK) return rc;
+  }
+  return F.end();
+}
+
+int zkhip_lagrange_cosets_row_shards_device(uint32_t k, uint64_t usable_rows, const uint64_t omega[4], const uint64_t ext_omega[4], const uint64_t zeta[4],
+                                            zkhip_row_shards* set, uint32_t col0, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  row_shards_t* R = find_row_shards(set, "lagrange_cosets_row_shards");
+  if (!R) return ZKHIP_EINVAL;
+  if (!omega || !ext_omega || !zeta) { set_error("lagrange_cosets_row_shards: null pointer"); return ZKHIP_EINVAL; }
+  const uint64_t n = (uint64_t)1 << (k > 28 ? 0 : k);
+  if (k > R->ext_k || usable_rows < 1 || usable_rows >= n || (uint64_t)col0 + 3 > R->n_cols) {
+    set_error("lagrange_cosets_row_shards: k = %u (ext_k %u), u = %llu, columns %u + 3 of %u", k, R->ext_k, (unsigned long long)usable_rows, col0, R->n_cols);
+    return ZKHIP_EINVAL;
+  }
+  namespace hd = zkhip::halo2::detail;
+  typedef zkhip::halo2::Fr fr;
+  const uint64_t N = (uint64_t)1 << R->ext_k, u = usable_rows;
+  const bool sum_below = u <= n - u;                         // l_active over the shorter side of the active rows
+  const uint64_t a0 = sum_below ? 0 : u, n_terms = sum_below ? u : n - u;
+  fr z, we, w;
+  memcpy(z.l, zeta, 32); memcpy(we.l, ext_omega, 32); memcpy(w.l, omega, 32);
+  const fr step = hd::pow_u64(we, 64 % N), step_inv = hd::pow_u64(we, (N - 64 % N) % N);
+  const fr c[10] = {z, we, step, step_inv, hd::pow_u64(step, n), hd::pow_u64(step_inv, n), hd::invert(hd::from_u64(n)), w, hd::pow_u64(w, u), hd::pow_u64(w, a0)};
+  uint32_t consts[10][8];
+  for (int i = 0; i < 10; i++) memcpy(consts[i], c[i].l, 32);
+  std::unique_lock<std::mutex> fan(g_fanout_mu);
+  fan_call F;
+  if ((rc = F.begin(caller_stream(stream))) != ZKHIP_OK) return rc;
+  for (int j = 0; j < R->S; j++) {
+    if ((rc = F.dev(j)) != ZKHIP_OK) return rc;
+    if ((rc = fr_lagrange_cosets_window_device(R->window(j, col0), R->window(j, col0 + 1), R->window(j, col0 + 2), R->W(j), window_start(R->row0[(size_t)j], R->halo_lo, N),
+                                               k, R->ext_k, (uint32_t)n_terms, sum_below ? 1 : 0, consts, F.st[(size_t)j])) != ZKHIP_OK) return rc;
+    if ((rc = touch_row_shards(R, j, F.st[(size_t)j])) != ZKHIP_OK) return rc;
+  }
+  return F.end();
 }
 
 // The straight-line HIP source rowvm_jit.hip generates for `prog` (buf may be NULL: *len receives the size needed, NUL included), and a

@@ -596,4 +596,92 @@ int fr_batch_invert_device(uint32_t* d_a, size_t n, void* ws, size_t ws_bytes, h
   return ZKHIP_OK;
 }
 
+// ---- the proving key's Lagrange cosets in closed form (zkhip_lagrange_cosets_row_shards_device) -------------------------------------------
+// At X = zeta ext_omega^g:  l_i(X) = omega^i (X^n - 1) / (n (X - omega^i)), so
+//   l0 = Zn / d0,  l_last = Zn omega^u / d1,  sum_{i in A} l_i = Zn Nm / D       (Zn = (X^n - 1) / n, d0 = X - 1, d1 = X - omega^u)
+// with D = prod_{i in A} (X - omega^i) and Nm / D = sum_{i in A} omega^i / (X - omega^i) built up one term at a time.  A is the shorter side
+// of the active rows: {0 .. u-1} (l_active = the sum) or {u .. n-1} (l_active = 1 - the sum).  The zeta coset misses the subgroup, so no
+// denominator vanishes.  One inversion per lane, the interleaved-lane layout of k_batch_invert: lane l takes window elements l, l + 64, ...
+// of its tile.  The forward pass parks the prefix products of den = d0 d1 D, and D and Nm, in the three output slots themselves (internal
+// form, canonical); the backward pass steps X back, recomputes d0, d1, and overwrites each slot with its external-form result.
+// Window element t is global row g = (start + t) mod 2^ext_k; X and X^n advance by ext_omega^64 and ext_omega^(64 n) per element of a lane.
+struct lagrange_consts {
+  fe_arg zeta, ext_omega, step, step_inv, step_n, step_n_inv, n_inv, omega, omega_u, omega_a0;
+};
+
+__global__ void __launch_bounds__(64) k_lagrange_cosets(uint32_t* __restrict__ out_l0, uint32_t* __restrict__ out_last, uint32_t* __restrict__ out_active,
+                                                        size_t W, uint64_t start, uint32_t k, uint32_t ext_k, uint32_t ch, uint32_t n_terms, int active_is_sum,
+                                                        lagrange_consts c) {
+  const size_t first = (size_t)blockIdx.x * 64 * ch + threadIdx.x;
+  if (first >= W) return;
+  const uint64_t mask = ((uint64_t)1 << ext_k) - 1;
+  const fe one = fe_one<Fr>();
+  const fe w = fr_const_internal(c.omega), w_u = fr_const_internal(c.omega_u), w_a0 = fr_const_internal(c.omega_a0);
+  const fe step = fr_const_internal(c.step), step_n = fr_const_internal(c.step_n);
+  // the lane's first X = zeta ext_omega^g and X^n (k squarings)
+  fe x = fe_mul<Fr>(fr_const_internal(c.zeta), fr_pow_u32(fr_const_internal(c.ext_omega), (uint32_t)((start + first) & mask)));
+  fe xn = x;
+  for (uint32_t s = 0; s < k; s++) xn = fe_sqr<Fr>(xn);
+  fe pref = one;
+  uint32_t cnt = 0;
+  for (size_t i = first; cnt < ch && i < W; i += 64, cnt++) {
+    const fe d0 = fe_norm(fe_sub_red(x, one, Fr::P4_S1)), d1 = fe_norm(fe_sub_red(x, w_u, Fr::P4_S1));   // < 6p, N
+    fe D = one, nm = fe_zero(), wi = w_a0;
+    for (uint32_t a = 0; a < n_terms; a++) {
+      const fe d = fe_norm(fe_sub_red(x, wi, Fr::P4_S1));
+      nm = fe_norm(fe_add(fe_mul<Fr>(nm, d), fe_mul<Fr>(wi, D)));      // < 4p, N
+      D = fe_mul<Fr>(D, d);
+      wi = fe_mul<Fr>(wi, w);
+    }
+    uint32_t wv[8];
+    fe_pack(fe_canon_lt2p<Fr>(pref), wv); store_words(out_l0 + i * 8, wv);
+    fe_pack(fe_canon_lt2p<Fr>(D), wv); store_words(out_last + i * 8, wv);
+    fe_pack(fe_canon_lt3p<Fr>(fe_reduce_soft<Fr>(nm)), wv); store_words(out_active + i * 8, wv);
+    pref = fe_mul<Fr>(pref, fe_mul<Fr>(fe_mul<Fr>(d0, d1), D));
+    x = fe_mul<Fr>(x, step);
+    xn = fe_mul<Fr>(xn, step_n);
+  }
+  fe inv = fe_inverse<Fr>(pref);
+  const fe step_inv = fr_const_internal(c.step_inv), step_n_inv = fr_const_internal(c.step_n_inv), n_inv = fr_const_internal(c.n_inv);
+  for (uint32_t j = cnt; j-- > 0;) {
+    const size_t i = first + (size_t)j * 64;
+    x = fe_mul<Fr>(x, step_inv);
+    xn = fe_mul<Fr>(xn, step_n_inv);
+    const fe d0 = fe_norm(fe_sub_red(x, one, Fr::P4_S1)), d1 = fe_norm(fe_sub_red(x, w_u, Fr::P4_S1));
+    const fe zn = fe_mul<Fr>(fe_norm(fe_sub_red(xn, one, Fr::P4_S1)), n_inv);
+    uint32_t wv[8];
+    load_words(out_l0 + i * 8, wv);
+    const fe pre = fe_unpack<0>(wv);
+    load_words(out_last + i * 8, wv);
+    const fe D = fe_unpack<0>(wv);
+    load_words(out_active + i * 8, wv);
+    const fe nm = fe_unpack<0>(wv);
+    const fe d01 = fe_mul<Fr>(d0, d1);
+    const fe inv_den = fe_mul<Fr>(inv, pre);                       // 1 / (d0 d1 D)
+    inv = fe_mul<Fr>(inv, fe_mul<Fr>(d01, D));
+    const fe zi = fe_mul<Fr>(zn, inv_den);
+    const fe l0 = fe_mul<Fr>(zi, fe_mul<Fr>(d1, D));
+    const fe ll = fe_mul<Fr>(fe_mul<Fr>(zi, w_u), fe_mul<Fr>(d0, D));
+    fe la = fe_mul<Fr>(fe_mul<Fr>(zi, nm), d01);
+    if (!active_is_sum) la = fe_norm(fe_sub_red(one, la, Fr::P4_S1));
+    fe_to_ext<Fr>(l0, wv); store_words(out_l0 + i * 8, wv);
+    fe_to_ext<Fr>(ll, wv); store_words(out_last + i * 8, wv);
+    fe_to_ext<Fr>(la, wv); store_words(out_active + i * 8, wv);
+  }
+}
+
+int fr_lagrange_cosets_window_device(uint32_t* out_l0, uint32_t* out_last, uint32_t* out_active, size_t W, uint64_t start, uint32_t k, uint32_t ext_k,
+                                     uint32_t n_terms, int active_is_sum, const uint32_t consts[10][8], hipStream_t stream) {
+  if (W == 0) return ZKHIP_OK;
+  lagrange_consts c;
+  memcpy(&c, consts, sizeof(c));
+  static_assert(sizeof(lagrange_consts) == 10 * 32, "ten constants");
+  uint32_t ch = INV_CH_MAX;
+  while (ch > 4 && W / ch < 65536) ch >>= 1;
+  hipLaunchKernelGGL(k_lagrange_cosets, grid_for((W + ch - 1) / ch, 64), dim3(64), 0, stream, out_l0, out_last, out_active, W, start, k, ext_k, ch, n_terms,
+                     active_is_sum, c);
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
+}
+
 }  // namespace zkhip

@@ -140,6 +140,10 @@ int fr_eval_polynomial_batch_device(const void* const* d_polys_host, size_t coun
 int fr_kate_division_device(const uint32_t* d_a, size_t n, const uint32_t b_host[8], uint32_t* d_q, void* ws, size_t ws_bytes, hipStream_t stream);
 int fr_prefix_product_device(const uint32_t* d_v, size_t n, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream);
 int fr_batch_invert_device(uint32_t* d_a, size_t n, void* ws, size_t ws_bytes, hipStream_t stream);
+// the l0 / l_last / l_active_row cosets of the proving key over a window of W elements (global rows start, start + 1, ... mod 2^ext_k), closed form.
+// consts: zeta, ext_omega, ext_omega^64, ext_omega^-64, ext_omega^(64 n), ext_omega^(-64 n), 1 / n, omega, omega^u, omega^(first index of A)
+int fr_lagrange_cosets_window_device(uint32_t* out_l0, uint32_t* out_last, uint32_t* out_active, size_t W, uint64_t start, uint32_t k, uint32_t ext_k,
+                                     uint32_t n_terms, int active_is_sum, const uint32_t consts[10][8], hipStream_t stream);
 size_t lincomb_workspace_bytes(size_t count, size_t n);
 int fr_linear_combination_device(const void* const* d_cols_host, const uint32_t* coeffs_host, size_t count, size_t n, uint32_t* d_out, void* ws, size_t ws_bytes,
                                  hipStream_t stream, arg_ring* ring = nullptr);

@@ -463,13 +463,108 @@ def run_programs_sum_device(progs: Sequence[RowProgram], weights: Sequence[int],
     _lib.check(lib.zkhip_fr_eval_rows_sum_device(arr, w.ctypes.data, len(progs), ptrs, len(columns), log_rows, C.c_void_p(out), C.c_void_p(stream)))
 
 
-COL_COEFF, COL_EXTENDED = 0, 1          # column forms of zkhip_fr_eval_rows_sharded_device
+COL_COEFF, COL_EXTENDED, COL_ROW_SHARDS = 0, 1, 2          # column forms of zkhip_fr_eval_rows_sharded_device
+
+
+class _ShardRef(C.Structure):              # zkhip_row_shard_ref
+    _fields_ = [("set", C.c_void_p), ("col", C.c_uint32)]
+
+
+class RowShards:
+    """A row-shard set (zkhip_row_shards_create): `n_cols` columns of a 2^ext_k domain cut by rows over the devices of zkhip_init, device j
+    holding each column's window (halo_lo + its rows + halo_hi elements, wrapping mod 2^ext_k) in HBM of its own.  `ref(col)` is what
+    `evaluate_rows_sharded_device` takes with COL_ROW_SHARDS.  Freed by `destroy()` (or the context manager) and by zkhip_shutdown."""
+
+    def __init__(self, ext_k: int, n_cols: int, halo_lo: int, halo_hi: int):
+        self.lib = _lib.load()
+        self.ext_k, self.n_cols, self.halo_lo, self.halo_hi = ext_k, n_cols, halo_lo, halo_hi
+        self.handle = C.c_void_p()
+        _lib.check(self.lib.zkhip_row_shards_create(ext_k, n_cols, halo_lo, halo_hi, C.byref(self.handle)))
+        self._refs: Dict[int, _ShardRef] = {}
+
+    def ref(self, col: int) -> int:
+        """host address of a zkhip_row_shard_ref for column `col` (kept alive by this object)"""
+        if col not in self._refs:
+            self._refs[col] = _ShardRef(self.handle.value, col)
+        return C.addressof(self._refs[col])
+
+    def window(self, shard: int, col: int) -> Tuple[int, int, int, int]:
+        """(device address, device ordinal, row0, count) of shard `shard`'s window of column `col`"""
+        ptr, dev, row0, count = C.c_void_p(), C.c_int(), C.c_uint64(), C.c_uint64()
+        _lib.check(self.lib.zkhip_row_shards_window(self.handle, shard, col, C.byref(ptr), C.byref(dev), C.byref(row0), C.byref(count)))
+        return ptr.value, dev.value, row0.value, count.value
+
+    def scatter_device(self, col: int, d_src: int, stream: int = 0) -> None:
+        _lib.check(self.lib.zkhip_row_shards_scatter_device(self.handle, col, d_src, stream))
+
+    def gather_device(self, col: int, d_dst: int, stream: int = 0) -> None:
+        _lib.check(self.lib.zkhip_row_shards_gather_device(self.handle, col, d_dst, stream))
+
+    def upload(self, col: int, a: np.ndarray) -> None:
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        assert a.shape == (1 << self.ext_k, 4), a.shape
+        _lib.check(self.lib.zkhip_row_shards_upload(self.handle, col, a.ctypes.data))
+
+    def download(self, col: int) -> np.ndarray:
+        """the whole column (2^ext_k elements) gathered to the primary and copied to the host"""
+        n = 1 << self.ext_k
+        d = C.c_void_p()
+        _lib.check(self.lib.zkhip_alloc(n * 32, C.byref(d)))
+        try:
+            self.gather_device(col, d.value)
+            _lib.check(self.lib.zkhip_stream_sync(None))
+            out = np.empty((n, 4), dtype=np.uint64)
+            _lib.check(self.lib.zkhip_download(out.ctypes.data, d, out.nbytes))
+        finally:
+            self.lib.zkhip_free(d)
+        return out
+
+    def destroy(self) -> None:
+        if self.handle:
+            _lib.check(self.lib.zkhip_row_shards_destroy(self.handle))
+            self.handle = C.c_void_p()
+
+    def __enter__(self) -> "RowShards":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.destroy()
+
+
+def quotient_halos(cs: ConstraintSystem, k: int, ext_k: int) -> Tuple[int, int]:
+    """(halo_lo, halo_hi) the quotient program of `cs` needs over a 2^ext_k window (RowProgram.halos of evaluate_h_program): every rotation
+    the gates and lookups query, the permutation's next row and, with more than one set, its -(blinding_factors + 1), the lookups' +1 / -1,
+    times rot_scale = 2^(ext_k - k).  A row-shard set made with these halos serves the program."""
+    rots = {0}
+
+    def walk(e):
+        if e.kind in ("fixed", "advice", "instance"):
+            rots.add(int(e.b or 0))
+        elif e.kind in ("neg", "scaled"):
+            walk(e.a)
+        elif e.kind in ("sum", "product"):
+            walk(e.a)
+            walk(e.b)
+
+    for polys in cs.gates:
+        for poly in polys:
+            walk(poly)
+    if cs.permutation_columns:
+        rots.add(1)
+        if cs.num_permutation_sets > 1:
+            rots.add(-(cs.blinding_factors + 1))
+    for lk in cs.lookups:
+        rots.update((1, -1))
+        for e in list(lk.input_expressions) + list(lk.table_expressions):
+            walk(e)
+    scale = 1 << (ext_k - k)
+    return max(0, -min(rots) * scale), max(0, max(rots) * scale)
 
 
 def evaluate_rows_sharded_device(prog: RowProgram, columns: Sequence[Tuple[int, int]], k: int, ext_k: int, dom, d_out: int, stream: int = 0) -> None:
     """The quotient numerator sharded by rows over the devices of zkhip_init (zkhip_fr_eval_rows_sharded_device).  `columns`: (device
     address, form) per column -- COL_COEFF: 2^k coefficients, taken to the extended coset of `dom` (its extended_omega, g_coset) on the
-    device that owns the column; COL_EXTENDED: 2^ext_k coset values.  d_out receives the 2^ext_k values zkhip_fr_eval_rows_device would
+    device that owns the column; COL_EXTENDED: 2^ext_k coset values; COL_ROW_SHARDS: `RowShards.ref(col)`, read where it lies.  d_out receives the 2^ext_k values zkhip_fr_eval_rows_device would
     write over the extended columns."""
     assert len(columns) >= prog.n_columns, "program reads more columns than were passed"
     ptrs = (C.c_void_p * max(len(columns), 1))(*[c[0] for c in columns])

@@ -377,16 +377,27 @@ class DeviceProvingKey:
     """`ProvingKey` whose polynomials live in HBM, as the prover's device-resident pipeline wants them: two
     allocations -- extended cosets [l0 | l_last | l_active_row | fixed... | sigma...] and n-element columns
     [fixed values | sigma values | fixed polys | sigma polys] -- addressed through the accessors.  `to_host()` downloads a `ProvingKey`
-    (for `write`), `from_host(pk)` uploads one (after `ProvingKey.read`)."""
+    (for `write`), `from_host(pk)` uploads one (after `ProvingKey.read`).
 
-    def __init__(self, vk: VerifyingKey, cs: E.ConstraintSystem, ext: _DeviceBuffer, base: _DeviceBuffer):
+    With `row_shards` the extended cosets are one `evaluation.RowShards` set instead (columns in the same order, halos from
+    `evaluation.quotient_halos`): each device of zkhip_init holds its rows of every coset, and the coset accessors return
+    `RowShards.ref` addresses for COL_ROW_SHARDS.  The n-element columns stay on the primary either way."""
+
+    def __init__(self, vk: VerifyingKey, cs: E.ConstraintSystem, ext: Optional[_DeviceBuffer], base: _DeviceBuffer,
+                 shards: Optional[E.RowShards] = None):
         self.vk, self.cs, self.k, self.n = vk, cs, vk.k, 1 << vk.k
         self.en = EvaluationDomain(cs.degree, vk.k).extended_len()
         self.nf, self.np = cs.num_fixed, len(cs.permutation_columns)
-        self._ext, self._base = ext, base
+        self._ext, self._base, self.shards = ext, base, shards
+
+    @property
+    def row_shards(self) -> bool:
+        return self.shards is not None
 
     # ---- addresses -----------------------------------------------------------------------------------------------------------------
     def _e(self, i: int) -> int:
+        if self.shards is not None:
+            return self.shards.ref(i)
         return self._ext.ptr.value + i * self.en * 32
 
     def _b(self, i: int) -> int:
@@ -403,31 +414,45 @@ class DeviceProvingKey:
     def permutation_poly(self, i: int) -> int: return self._b(2 * self.nf + self.np + i)
 
     @staticmethod
-    def allocate(vk: VerifyingKey, cs: E.ConstraintSystem) -> "DeviceProvingKey":
+    def allocate(vk: VerifyingKey, cs: E.ConstraintSystem, row_shards: bool = False) -> "DeviceProvingKey":
         n = 1 << vk.k
-        en = EvaluationDomain(cs.degree, vk.k).extended_len()
+        ek = EvaluationDomain(cs.degree, vk.k).extended_k
         cols = cs.num_fixed + len(cs.permutation_columns)
-        ext = _DeviceBuffer(max(1, (3 + cols) * en * 32))
+        ext = shards = None
+        if row_shards:
+            shards = E.RowShards(ek, 3 + cols, *E.quotient_halos(cs, vk.k, ek))
+        else:
+            ext = _DeviceBuffer(max(1, (3 + cols) * (1 << ek) * 32))
         try:
             base = _DeviceBuffer(max(1, 2 * cols * n * 32))
         except Exception:
-            ext.free()
+            if ext is not None:
+                ext.free()
+            if shards is not None:
+                shards.destroy()
             raise
-        return DeviceProvingKey(vk, cs, ext, base)
+        return DeviceProvingKey(vk, cs, ext, base, shards)
 
     def to_host(self) -> ProvingKey:
         n, en, nf, npc = self.n, self.en, self.nf, self.np
-        e = self._ext.download((3 + nf + npc, en, 4))
+        if self.shards is not None:
+            e = np.stack([self.shards.download(i) for i in range(3 + nf + npc)])
+        else:
+            e = self._ext.download((3 + nf + npc, en, 4))
         b = self._base.download((2 * (nf + npc), n, 4))
         return ProvingKey(self.vk, e[0], e[1], e[2], [b[i] for i in range(nf)], [b[nf + npc + i] for i in range(nf)], [e[3 + i] for i in range(nf)],
                           [b[nf + i] for i in range(npc)], [b[2 * nf + npc + i] for i in range(npc)], [e[3 + nf + i] for i in range(npc)])
 
     @staticmethod
-    def from_host(pk: ProvingKey, cs: E.ConstraintSystem) -> "DeviceProvingKey":
-        d = DeviceProvingKey.allocate(pk.vk, cs)
+    def from_host(pk: ProvingKey, cs: E.ConstraintSystem, row_shards: bool = False) -> "DeviceProvingKey":
+        """row_shards: each device's windows of every coset go straight from host memory to that device (zkhip_row_shards_upload)"""
+        d = DeviceProvingKey.allocate(pk.vk, cs, row_shards)
         try:
             for i, a in enumerate([pk.l0, pk.l_last, pk.l_active_row] + list(pk.fixed_cosets) + list(pk.permutation_cosets)):
-                d._ext.upload(np.ascontiguousarray(a, dtype=np.uint64), i * d.en * 32)
+                if d.shards is not None:
+                    d.shards.upload(i, np.ascontiguousarray(a, dtype=np.uint64).reshape(d.en, 4))
+                else:
+                    d._ext.upload(np.ascontiguousarray(a, dtype=np.uint64), i * d.en * 32)
             for i, a in enumerate(list(pk.fixed_values) + list(pk.permutations) + list(pk.fixed_polys) + list(pk.permutation_polys)):
                 d._base.upload(np.ascontiguousarray(a, dtype=np.uint64), i * d.n * 32)
         except Exception:
@@ -436,7 +461,10 @@ class DeviceProvingKey:
         return d
 
     def free(self) -> None:
-        self._ext.free()
+        if self._ext is not None:
+            self._ext.free()
+        if self.shards is not None:
+            self.shards.destroy()
         self._base.free()
 
     def __enter__(self) -> "DeviceProvingKey":
@@ -496,10 +524,15 @@ def _commit_lagrange_device(params, d_columns: int, count: int) -> np.ndarray:
         return d_out.download((count, 8), count * 96)
 
 
-def keygen_device(params, cs: E.ConstraintSystem, fixed: Sequence[np.ndarray], assembly: Assembly, selectors: Sequence[np.ndarray] = ()) -> DeviceProvingKey:
+def keygen_device(params, cs: E.ConstraintSystem, fixed: Sequence[np.ndarray], assembly: Assembly, selectors: Sequence[np.ndarray] = (),
+                  row_shards: bool = False) -> DeviceProvingKey:
     """`keygen_vk` + `keygen_pk` with everything but the fixed columns' upload and the 64-byte commitments staying on the device: sigma
     columns by gather, commitments against the registered g_lagrange, polys / cosets by the batched transforms.  The result equals
-    `keygen_pk(params, keygen_vk(...), ...)` element for element (`DeviceProvingKey.to_host()`)."""
+    `keygen_pk(params, keygen_vk(...), ...)` element for element (`DeviceProvingKey.to_host()`).
+
+    row_shards: the 3 + fixed + sigma cosets go into one row-shard set over the devices of zkhip_init (DeviceProvingKey): fixed and sigma
+    through zkhip_coeff_to_extended_row_shards_device (each owner transforms and sends every device its rows), l0 / l_last / l_active_row
+    from their closed form on every device (zkhip_lagrange_cosets_row_shards_device).  No coset is ever whole on the primary."""
     lib = _lib.load()
     k, n = params.k, 1 << params.k
     if len(fixed) != cs.num_fixed or assembly.n_columns != len(cs.permutation_columns) or assembly.n != n:
@@ -510,7 +543,8 @@ def keygen_device(params, cs: E.ConstraintSystem, fixed: Sequence[np.ndarray], a
     en = dom.extended_len()
     nf, npc = cs.num_fixed, len(cs.permutation_columns)
     cols = nf + npc
-    pk = DeviceProvingKey.allocate(VerifyingKey(k, np.zeros((0, 8), dtype=np.uint64), np.zeros((0, 8), dtype=np.uint64), [np.asarray(s, dtype=bool) for s in selectors], cs), cs)
+    pk = DeviceProvingKey.allocate(VerifyingKey(k, np.zeros((0, 8), dtype=np.uint64), np.zeros((0, 8), dtype=np.uint64), [np.asarray(s, dtype=bool) for s in selectors], cs), cs,
+                                   row_shards)
     try:
         for i, c in enumerate(fixed):
             pk._base.upload(np.ascontiguousarray(c, dtype=np.uint64).reshape(n, 4), i * n * 32)
@@ -519,12 +553,21 @@ def keygen_device(params, cs: E.ConstraintSystem, fixed: Sequence[np.ndarray], a
         pk.vk.fixed_commitments, pk.vk.permutation_commitments = commits[:nf], commits[nf:]
         # values -> coefficients (copy, then the batched inverse transform in place) -> extended cosets
         _copy_device_range(pk._b(cols), pk._b(0), cols * n)
+        u = n - (cs.blinding_factors + 1)
         if cols:
             _lib.check(lib.zkhip_ifft_scaled_batch_device(C.c_void_p(pk._b(cols)), dom.omega_inv.ctypes.data, k, dom.ifft_divisor.ctypes.data, cols, n, None))
+        if row_shards:
+            if cols:
+                _lib.check(lib.zkhip_coeff_to_extended_row_shards_device(C.c_void_p(pk._b(cols)), k, cols, n, dom.extended_omega.ctypes.data,
+                                                                         dom.g_coset.ctypes.data, pk.shards.handle, 3, None))
+            _lib.check(lib.zkhip_lagrange_cosets_row_shards_device(k, u, dom.omega.ctypes.data, dom.extended_omega.ctypes.data, dom.g_coset.ctypes.data,
+                                                                   pk.shards.handle, 0, None))
+            _lib.check(lib.zkhip_sync())
+            return pk
+        if cols:
             _lib.check(lib.zkhip_coeff_to_extended_device(C.c_void_p(pk._b(cols)), n, k, C.c_void_p(pk._e(3)), en, dom.extended_k, cols, dom.extended_omega.ctypes.data,
                                                           dom.g_coset.ctypes.data, None))
         # l0, l_last, l_active_row: indicator columns, transformed like the others
-        u = n - (cs.blinding_factors + 1)
         one = fr_encode([1])[0]
         ind = np.zeros((3, n, 4), dtype=np.uint64)
         ind[0, 0] = one

@@ -136,6 +136,15 @@ int zkhip_fr_batch_invert(uint64_t *a, size_t n);
 int zkhip_fr_prefix_product(const uint64_t *v, size_t n, uint64_t *out);
 int zkhip_fr_eval_polynomial_device(const void *d_poly, size_t n, const uint64_t point[4], void *d_out, void *stream);
 int zkhip_fr_kate_division_device(const void *d_a, size_t n, const uint64_t b[4], void *d_q, void *stream);
+/* `div_by_vanishing(a, roots)` [DEP poly/kzg/multiopen/shplonk/prover.rs]: quotient of a(X) by Z(X) = prod_i (X - roots[i]) for 1 <= m <=
+ * ZKHIP_MAX_ROOTS pairwise distinct canonical roots, remainder dropped -- the same bytes as m successive `kate_division`s in any order, in
+ * one pass structure (a read twice, q written once, whatever m).  q has n elements: n - m coefficients followed by m zeros (all zeros when
+ * n <= m).  evals (nullable) receives a(roots[i]), i < m: with the roots these are the remainder.  `roots` is host memory ([m][4]) in both
+ * forms.  d_q must not overlap d_a.  ZKHIP_EINVAL (nothing enqueued): m = 0, m > ZKHIP_MAX_ROOTS, null roots, null a / q with n > 0, a root
+ * >= r, two equal roots.  n = 0 is ZKHIP_OK (evals, if asked for, are zeros). */
+#define ZKHIP_MAX_ROOTS 8
+int zkhip_fr_divide_by_roots(const uint64_t *a, size_t n, const uint64_t *roots, uint32_t m, uint64_t *q, uint64_t *evals);
+int zkhip_fr_divide_by_roots_device(const void *d_a, size_t n, const uint64_t *roots, uint32_t m, void *d_q, void *d_evals, void *stream);
 /* multiopen: `count` device-resident polynomials of n coefficients each (d_polys: host array of device pointers), all evaluated at
  * `point`; d_out receives count results (32 bytes each).  One launch per recursion level for the whole batch. */
 int zkhip_fr_eval_polynomial_batch_device(const void *const *d_polys, size_t count, size_t n, const uint64_t point[4], void *d_out, void *stream);

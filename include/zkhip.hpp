@@ -334,6 +334,16 @@ inline std::vector<Fr> kate_division(const std::vector<Fr>& a, const Fr& b) {
   if (a.size() > 1) check(zkhip_fr_kate_division(a.data()->l, a.size(), b.l, q.data()->l), "kate_division");
   return q;
 }
+// `div_by_vanishing`: quotient of a(X) by prod_i (X - roots[i]) (1 .. ZKHIP_MAX_ROOTS distinct roots), remainder dropped; a.len() elements, the top
+// roots.len() of them zero.  evals (optional) receives a(roots[i]).
+inline std::vector<Fr> divide_by_roots(const std::vector<Fr>& a, const std::vector<Fr>& roots, std::vector<Fr>* evals = nullptr) {
+  std::vector<Fr> q(a.size());
+  if (evals) evals->assign(roots.size(), Fr{});
+  static const Fr dummy{};
+  check(zkhip_fr_divide_by_roots(a.empty() ? dummy.l : a.data()->l, a.size(), roots.empty() ? nullptr : roots.data()->l, (uint32_t)roots.size(),
+                                 a.empty() ? nullptr : q.data()->l, evals && !roots.empty() ? evals->data()->l : nullptr), "divide_by_roots");
+  return q;
+}
 
 // ---- the prover's other Fr-vector steps ---------------------------
 // ff::BatchInvert: in place, zeros stay zero
@@ -1061,7 +1071,8 @@ inline ProvingKey keygen_pk(const ParamsKZG& params, const VerifyingKey& vk, con
 // ---- poly::kzg::multiopen: ProverGWC (the gen_snark path) and ProverSHPLONK (the benches' gen_proof path) -------------------------
 // [DEP halo2-axiom poly/kzg/multiopen/{gwc.rs, gwc/prover.rs, shplonk.rs, shplonk/prover.rs]; reached from
 // /root/reference/aggregator/src/wrapper.rs:59-60, 127-137 (GWC) and /root/reference/aggregator/benches/wrapper_circuit.rs:140 (SHPLONK).
-// Polynomials stay on the device: combinations are fused row programs, quotients zkhip_fr_kate_division_device, commitments a prepared MSM.
+// Polynomials stay on the device: combinations are fused row programs, quotients zkhip_fr_kate_division_device (one point) or
+// zkhip_fr_divide_by_roots_device (a rotation set), commitments a prepared MSM.
 // The transcript is the host's: challenges come in as arguments, commitments go out.  Restated from the published algorithms (unpinned).
 
 // the SRS pinned for device-resident commits (`params.commit(&poly)` on a polynomial that lives in HBM)
@@ -1136,6 +1147,19 @@ inline void zero_at(DeviceVec& poly, size_t index) {
 inline void divide_by_root(const DeviceVec& in, const Fr& root, DeviceVec& out) {
   check(zkhip_fr_kate_division_device(in.data(), in.size(), root.l, out.data(), nullptr), "kate_division");
   zero_at(out, in.size() - 1);
+}
+// `div_by_vanishing` keeping n coefficients (the top points.size() zero): out = in / prod_i (X - points[i]), one pass whatever the number of points
+inline void divide_by_roots(const DeviceVec& in, const std::vector<Fr>& points, DeviceVec& out) {
+  if (out.size() < in.size()) throw std::invalid_argument("divide_by_roots: output shorter than input");
+  if (points.size() > ZKHIP_MAX_ROOTS) {                  // larger than any rotation set of halo2: the fold, through a temporary
+    DeviceVec tmp(in.size());
+    const DeviceVec* src = &in;
+    DeviceVec* dst = points.size() % 2 ? &out : &tmp;     // the last division lands in `out`
+    for (const Fr& z : points) { divide_by_root(*src, z, *dst); src = dst; dst = dst == &out ? &tmp : &out; }
+    return;
+  }
+  check(zkhip_fr_divide_by_roots_device(in.data(), in.size(), points.empty() ? nullptr : points.data()->l, (uint32_t)points.size(), out.data(), nullptr, nullptr),
+        "divide_by_roots");
 }
 // evaluations the queries lack: one batched eval_polynomial per distinct point
 inline void evaluate_queries(std::vector<ProverQuery>& queries, size_t n) {
@@ -1294,15 +1318,10 @@ class ShplonkProver {
       DeviceVec* acc = fresh();
       DeviceVec* tmp = fresh();
       detail::linear_combination(ypow, rs.polys, k_, *acc);
-      // sum_j y^j R_j with R_j = sum_i evals[j][i] basis[i]: first the weights w_i = sum_j y^j evals[j][i], then m basis polynomials
-      std::vector<Fr> low(rs.points.size(), Fr{}), weight(rs.points.size(), Fr{});
-      for (size_t j = 0; j < rs.polys.size(); j++)
-        for (size_t i = 0; i < weight.size(); i++) weight[i] = detail::add_fr(weight[i], detail::mul(ypow[j], rs.evals[j][i]));
-      for (size_t i = 0; i < weight.size(); i++)
-        for (size_t t = 0; t < low.size(); t++) low[t] = detail::add_fr(low[t], detail::mul(weight[i], rs.basis[i][t]));
-      for (size_t t = 0; t < low.size(); t++) detail::sub_const_at(*acc, t, low[t]);
-      DeviceVec *src = acc, *dst = tmp;
-      for (const Fr& z : rs.points) { detail::divide_by_root(*src, z, *dst); std::swap(src, dst); }
+      // the quotient by Z_S is the same polynomial whether or not the interpolant sum_j y^j R_j (degree < |S|) is subtracted first: one division
+      // by the whole point set, no patching of the low coefficients
+      detail::divide_by_roots(*acc, rs.points, *tmp);
+      DeviceVec* src = tmp;
       quotients.push_back(src);
     }
     Fr vp = detail::one();

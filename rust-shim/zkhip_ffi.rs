@@ -60,6 +60,8 @@ extern "C" {
     fn zkhip_fr_eval_rows_sum_device(progs: *const VmProgram, weights: *const u64, n_progs: u32, d_columns: *const *const c_void, n_columns: u32, log_rows: u32,
                                      d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn zkhip_fr_linear_combination_device(d_cols: *const *const c_void, coeffs: *const u64, count: usize, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn zkhip_fr_divide_by_roots_device(d_a: *const c_void, n: usize, roots: *const u64, m: u32, d_q: *mut c_void, d_evals: *mut c_void,
+                                       stream: *mut c_void) -> c_int;
     fn zkhip_multiopen_gwc_device(bases: *const u64, k: u32, queries: *const ProverQueryC, n_queries: usize, v: *const u64, out_points: *mut u64,
                                   capacity: usize, n_out: *mut usize) -> c_int;
     fn zkhip_multiopen_shplonk_begin_device(bases: *const u64, k: u32, queries: *const ProverQueryC, n_queries: usize, y: *const u64, v: *const u64,

@@ -1691,6 +1691,35 @@ int zkhip_fr_kate_division_device(const void* d_a, size_t n, const uint64_t b[4]
   return fr_kate_division_device((const uint32_t*)d_a, n, (const uint32_t*)b, (uint32_t*)d_q, sc->ws.p, sc->ws.cap, s);
 }
 
+// the argument checks of both forms of divide_by_roots: nothing is enqueued before they pass
+static int check_roots(const uint64_t* roots, uint32_t m) {
+  static const uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};   // the modulus of Fr
+  if (m == 0 || m > ZKHIP_MAX_ROOTS) { set_error("divide_by_roots: %u roots (1 .. %d)", m, ZKHIP_MAX_ROOTS); return ZKHIP_EINVAL; }
+  if (!roots) { set_error("divide_by_roots: null pointer"); return ZKHIP_EINVAL; }
+  for (uint32_t i = 0; i < m; i++) {
+    bool below = false;
+    for (int w = 3; w >= 0; w--)
+      if (roots[i * 4 + w] != R[w]) { below = roots[i * 4 + w] < R[w]; break; }
+    if (!below) { set_error("divide_by_roots: root %u is not canonical (>= r)", i); return ZKHIP_EINVAL; }
+    for (uint32_t j = 0; j < i; j++)
+      if (memcmp(roots + i * 4, roots + j * 4, 32) == 0) { set_error("divide_by_roots: roots %u and %u are equal", j, i); return ZKHIP_EINVAL; }
+  }
+  return ZKHIP_OK;
+}
+
+int zkhip_fr_divide_by_roots_device(const void* d_a, size_t n, const uint64_t* roots, uint32_t m, void* d_q, void* d_evals, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if ((rc = check_roots(roots, m)) != ZKHIP_OK) return rc;
+  if (n && (!d_a || !d_q)) { set_error("divide_by_roots: null pointer"); return ZKHIP_EINVAL; }
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->ws.reserve(poly_roots_workspace_bytes(n, m))) != ZKHIP_OK) return rc;
+  return fr_divide_by_roots_device((const uint32_t*)d_a, n, (const uint32_t(*)[8])roots, m, (uint32_t*)d_q, (uint32_t*)d_evals, sc->ws.p, sc->ws.cap, s);
+}
+
 int zkhip_fr_batch_invert_device(void* d_a, size_t n, void* stream) {
   ZK_API_RANGE();
   guard_t g(g_mu);
@@ -1753,6 +1782,35 @@ int zkhip_fr_kate_division(const uint64_t* a, size_t n, const uint64_t b[4], uin
   if (!b || (n > 1 && (!a || !q))) { set_error("kate_division: null pointer"); return ZKHIP_EINVAL; }
   if (n < 2) return ZKHIP_OK;
   return host_vec_op(1, a, n, b, q, n - 1);
+}
+
+int zkhip_fr_divide_by_roots(const uint64_t* a, size_t n, const uint64_t* roots, uint32_t m, uint64_t* q, uint64_t* evals) {
+  ZK_API_RANGE();
+  int rc = check_roots(roots, m);
+  if (rc != ZKHIP_OK) return rc;
+  if (n && (!a || !q)) { set_error("divide_by_roots: null pointer"); return ZKHIP_EINVAL; }
+  if (n == 0) {
+    if (evals) memset(evals, 0, (size_t)m * 32);
+    return ZKHIP_OK;
+  }
+  lane_hold H;
+  if (H.rc != ZKHIP_OK) return H.rc;
+  hipStream_t s = H.s;
+  // on an error after something was enqueued: wait for the lane's stream, so that nothing outlives the caller's buffers or runs into the lane's next user
+  struct drain_t {
+    hipStream_t s; bool armed = true;
+    ~drain_t() { if (armed) { (void)hipStreamSynchronize(s); (void)hipGetLastError(); } }
+  } drain{s};
+  if ((rc = H.sc->poly.reserve(n * 32)) != ZKHIP_OK) return rc;
+  if ((rc = H.sc->poly2.reserve((n + ZKHIP_MAX_ROOTS) * 32)) != ZKHIP_OK) return rc;
+  char* d_ev = (char*)H.sc->poly2.p + n * 32;
+  HIPCHK(hipMemcpyAsync(H.sc->poly.p, a, n * 32, hipMemcpyHostToDevice, s));
+  if ((rc = zkhip_fr_divide_by_roots_device(H.sc->poly.p, n, roots, m, H.sc->poly2.p, evals ? d_ev : nullptr, s)) != ZKHIP_OK) return rc;
+  HIPCHK(hipMemcpyAsync(q, H.sc->poly2.p, n * 32, hipMemcpyDeviceToHost, s));
+  if (evals) HIPCHK(hipMemcpyAsync(evals, d_ev, (size_t)m * 32, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  drain.armed = false;
+  return ZKHIP_OK;
 }
 
 int zkhip_fr_batch_invert(uint64_t* a, size_t n) {

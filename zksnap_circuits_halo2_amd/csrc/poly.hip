@@ -356,6 +356,307 @@ int fr_kate_division_device(const uint32_t* d_a, size_t n, const uint32_t b_host
   return horner_scan(d_a, n, b, d_q, 1, nullptr, (char*)ws, stream);
 }
 
+// ---- division by the vanishing polynomial of a point set (multi-open: `div_by_vanishing`) ---------------------------------------
+// q = floor(a / Z), Z(X) = prod_{i < M} (X - z_i) = X^M + sum_j c_j X^j, in ONE pass structure whatever M: a is read twice and q written once,
+// where the fold of M kate_divisions reads 2 M times and writes M times.
+//   Division from the top is a linear recurrence whose state is the running remainder R_t = (sum_{j >= t} a_j X^(j - t)) mod Z, M
+//   coefficients r_0 .. r_(M-1):   q[t] = r_(M-1) of R_(t+1);   R_t = a[t] + X R_(t+1) - q[t] Z, i.e. r_j <- r_(j-1) - q[t] c_j, r_0 <- a[t] - q[t] c_0.
+//   M independent multiplications per element (the fold spends 2 M), and R_t is the interpolant of the M suffix Horner values
+//   S_i[t] = sum_{j >= t} a_j z_i^(j - t) over the points -- so the carries of the chunked scheme stay M independent scalars:
+//   pass A   per chunk the M Horner aggregates from one load of the chunk (k_roots_agg);
+//   levels   the M aggregate arrays scanned as kate_division scans its one, blockIdx.y = root (k_roots_agg_level up, k_roots_apply_level down);
+//   pass B   each thread turns its M carries S_i[hi] into R_hi with the M x M matrix V[j][i] = [X^j] Z(X) / ((X - z_i) Z'(z_i)) (Lagrange basis
+//            coefficients: host arithmetic on a handful of points, one inversion) and steps the recurrence, one store per element.
+// The zero tail q[n - M .. n) needs no code: R_t has degree < n - t, so its top coefficient is zero there.  a(z_i) is the scanned level-1
+// aggregate at index 0.  Every multiplier -- z_i^(CH^level), -c_j, V -- is computed on the host (fp29.hpp compiles there) in the internal form
+// and travels as a kernel argument: nothing is staged on the device, the constants sit in scalar registers.
+struct roots_k { uint32_t l[ZKHIP_MAX_ROOTS][NL]; };                                     // one internal-form canonical constant per root
+struct roots_div_k { uint32_t nc[ZKHIP_MAX_ROOTS][NL]; uint32_t v[ZKHIP_MAX_ROOTS][ZKHIP_MAX_ROOTS][NL]; };   // -c_j; V[j][i]
+
+__device__ __forceinline__ fe fe_from_limbs(const uint32_t (&l)[NL]) {
+  fe r;
+#pragma unroll
+  for (int i = 0; i < NL; i++) r.l[i] = l[i];
+  return r;
+}
+
+// pass A for M roots: agg[i * stride + t] = sum_{e in chunk t} a[e] z_i^(e - lo).  M x 9 registers of state per lane, the chunk loaded once.
+template <int M>
+__global__ void __launch_bounds__(256) k_roots_agg(const uint32_t* __restrict__ a, size_t n, const roots_k zk, uint32_t* __restrict__ agg, size_t stride) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t lo = t * POLY_CH;
+  if (lo >= n) return;
+  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  fe q[M];
+#pragma unroll
+  for (int r = 0; r < M; r++) q[r] = fe_zero();
+  // static_for, not `#pragma unroll`: the body is M multiplications long and the unroller gives up on it, which sends q[] to scratch memory
+  auto step = [&](const fe& x) {
+    static_for<0, M>([&](auto r) { q[r] = fe_norm(fe_add(x, fe_mul<Fr>(fe_from_limbs(zk.l[r]), q[r]))); });   // < 3p, N (as k_horner_agg)
+  };
+  size_t i = hi;
+  for (; i >= lo + 4 && ((i & 3) == 0); i -= 4) {               // four elements = one 128-byte line per lane, loaded together (see k_horner_agg)
+    uint32_t w[4][8];
+    static_for<0, 4>([&](auto e) { load_words(a + (i - 4 + e) * 8, w[e]); });
+    static_for<0, 4>([&](auto e) { step(fe_unpack<0>(w[3 - e])); });
+  }
+  for (; i-- > lo;) step(load_ext(a, i));
+  static_for<0, M>([&](auto r) { store_canon(agg + (size_t)r * stride * 8, t, q[r]); });
+}
+
+// the recursion levels: blockIdx.y = root, dense [m][n] arrays, the level's multipliers z_i^(CH^level) in zk
+__global__ void __launch_bounds__(256) k_roots_agg_level(const uint32_t* __restrict__ base, size_t n, const roots_k zk, uint32_t* __restrict__ agg, size_t m) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t lo = t * POLY_CH;
+  if (lo >= n) return;
+  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  const uint32_t* a = base + (size_t)blockIdx.y * n * 8;
+  const fe b = fe_from_limbs(zk.l[blockIdx.y]);
+  fe q = fe_zero();
+  for (size_t i = hi; i-- > lo;) q = fe_norm(fe_add(load_ext(a, i), fe_mul<Fr>(b, q)));
+  store_canon(agg + (size_t)blockIdx.y * m * 8, t, q);
+}
+// in place: arr[i] <- arr[i] + b * arr[i + 1] (suffix scan) with carry-in carry[t + 1]; a thread reads and writes its own chunk only, top down
+__global__ void __launch_bounds__(256) k_roots_apply_level(uint32_t* base, size_t n, const roots_k zk, const uint32_t* carry_base, size_t ncarry) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t lo = t * POLY_CH;
+  if (lo >= n) return;
+  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  uint32_t* a = base + (size_t)blockIdx.y * n * 8;
+  const fe b = fe_from_limbs(zk.l[blockIdx.y]);
+  fe q = (carry_base != nullptr && t + 1 < ncarry) ? load_ext(carry_base + (size_t)blockIdx.y * ncarry * 8, t + 1) : fe_zero();
+  for (size_t i = hi; i-- > lo;) {
+    q = fe_norm(fe_add(load_ext(a, i), fe_mul<Fr>(b, q)));
+    store_canon(a, i, q);
+  }
+}
+
+// pass B.  Magnitudes: V, nc canonical (< p); a carry is canonical, so each product of the conversion is < p (p^2 / (p 2^261) + 1) < 1.01 p and
+// r_j < 1.01 M p.  In the loop q is soft-reduced (< 2p + 2^233 < 3p, N) before it is stored and multiplied: q nc_j < 1.02 p, and an r_j
+// collects at most M - 1 such products on top of its start (or M and one a[t] < p) before it becomes q: value < 2.03 M p < 17 p < 2^261 for M = 8,
+// the bound of fe_reduce_soft.  Limbs: every term is N-limbed (< 2^29), r_j is a plain sum of at most M + 1 of them: < 2^32 up to M = 7; M = 8 carries
+// once per step.  Only q, normalised, is ever a multiplication operand.
+template <int M>
+__global__ void __launch_bounds__(256) k_roots_div(const uint32_t* __restrict__ a, size_t n, const roots_div_k k, const uint32_t* __restrict__ carry,
+                                                   size_t ncarry, uint32_t* __restrict__ out, uint32_t* __restrict__ evals) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t lo = t * POLY_CH;
+  if (lo >= n) return;
+  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  fe r[M];
+#pragma unroll
+  for (int j = 0; j < M; j++) r[j] = fe_zero();
+  if (carry != nullptr && t + 1 < ncarry) {
+    fe s[M];
+    static_for<0, M>([&](auto i) { s[i] = load_ext(carry + (size_t)i * ncarry * 8, t + 1); });
+    static_for<0, M>([&](auto j) {
+      fe acc = fe_zero();
+      static_for<0, M / 2>([&](auto h) {                        // two products per reduction: 9 * 2 * 2^58 + 9 * 2^58 + 2^35 < 2^64 (fe_mul_add), all limbs < 2^29
+        constexpr int i = 2 * h;
+        acc = fe_add(acc, fe_mul_add<Fr>(fe_from_limbs(k.v[j][i]), s[i], fe_from_limbs(k.v[j][i + 1]), s[i + 1]));
+      });
+      if (M & 1) acc = fe_add(acc, fe_mul<Fr>(fe_from_limbs(k.v[j][M - 1]), s[M - 1]));
+      r[j] = fe_norm(acc);
+    });
+  }
+  if (evals != nullptr && t == 0 && carry != nullptr) {        // a(z_i): the scan of the level-1 aggregates at index 0 (canonical already)
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+      uint32_t w[8];
+      load_words(carry + (size_t)i * ncarry * 8, w);
+      store_words(evals + i * 8, w);
+    }
+  }
+  auto step = [&](const fe& x, size_t idx) {                  // static_for: see k_roots_agg
+    const fe q = fe_reduce_soft<Fr>(fe_norm(r[M - 1]));
+    store_canon(out, idx, q);
+    static_for<1, M>([&](auto jj) {
+      constexpr int j = M - jj;                                 // M - 1 .. 1: r[j - 1] is read before it is replaced
+      r[j] = fe_add(r[j - 1], fe_mul<Fr>(fe_from_limbs(k.nc[j]), q));
+      if (M > 7) r[j] = fe_norm(r[j]);
+    });
+    r[0] = fe_add(x, fe_mul<Fr>(fe_from_limbs(k.nc[0]), q));
+  };
+  size_t i = hi;
+  for (; i >= lo + 4 && ((i & 3) == 0); i -= 4) {               // four elements = one 128-byte line per lane, loaded together (see k_horner_agg)
+    uint32_t w[4][8];
+    static_for<0, 4>([&](auto e) { load_words(a + (i - 4 + e) * 8, w[e]); });
+    static_for<0, 4>([&](auto e) { step(fe_unpack<0>(w[3 - e]), i - 1 - e); });
+  }
+  for (; i-- > lo;) step(load_ext(a, i), i);
+}
+
+// host arithmetic on the points (internal form, canonical values)
+static fe h_mul(const fe& a, const fe& b) { return fe_canon_lt2p<Fr>(fe_mul<Fr>(a, b)); }
+static fe h_add(const fe& a, const fe& b) { return fe_canon_lt2p<Fr>(fe_norm(fe_add(a, b))); }
+static fe h_neg(const fe& a) {
+  if (fe_is_zero_limbs(a)) return a;
+  fe r;
+  int32_t borrow = 0;
+  for (int i = 0; i < NL; i++) {
+    int32_t t = (int32_t)Fr::P[i] - (int32_t)a.l[i] + borrow;
+    borrow = t >> 31;
+    r.l[i] = i < NL - 1 ? ((uint32_t)t & LMASK) : (uint32_t)t;
+  }
+  return r;
+}
+static fe h_sub(const fe& a, const fe& b) { return h_add(a, h_neg(b)); }
+static fe h_from_ext(const uint32_t w[8]) {
+  uint32_t ww[8];
+  memcpy(ww, w, 32);
+  return h_mul(fe_const<Fr>(Fr::FROM_EXT), fe_unpack<0>(ww));
+}
+static fe h_inverse(const fe& a) {                            // a^(r - 2): the bits of r - 2 from the limbs of r
+  uint32_t e[NL];
+  for (int i = 0; i < NL; i++) e[i] = Fr::P[i];
+  e[0] -= 2;                                                   // the low limb of r is 0x10000001: no borrow
+  fe acc = fe_one<Fr>();
+  for (int bit = LB * NL - 1; bit >= 0; bit--) {
+    acc = h_mul(acc, acc);
+    if ((e[bit / LB] >> (bit % LB)) & 1) acc = h_mul(acc, a);
+  }
+  return acc;
+}
+static void h_store(const fe& a, uint32_t (&l)[NL]) { for (int i = 0; i < NL; i++) l[i] = a.l[i]; }
+
+size_t poly_roots_workspace_bytes(size_t n, uint32_t m) {     // the m aggregate arrays of every level
+  size_t total = 256, c = n;
+  while (c > 1) { c = chunks_of(c); total += (((size_t)m * c * 32 + 255) / 256) * 256; }
+  const size_t single = poly_workspace_bytes(n);              // m = 1 without evaluations runs kate_division's kernels
+  return total > single ? total : single;
+}
+
+template <int M>
+static void launch_roots_agg(const uint32_t* d_a, size_t n, const roots_k& zk, uint32_t* agg, size_t stride, hipStream_t stream) {
+  hipLaunchKernelGGL(k_roots_agg<M>, grid_for(chunks_of(n), 256), dim3(256), 0, stream, d_a, n, zk, agg, stride);
+}
+template <int M>
+static void launch_roots_div(const uint32_t* d_a, size_t n, const roots_div_k& k, const uint32_t* carry, size_t ncarry, uint32_t* d_q, uint32_t* d_evals,
+                             hipStream_t stream) {
+  hipLaunchKernelGGL(k_roots_div<M>, grid_for(chunks_of(n), 256), dim3(256), 0, stream, d_a, n, k, carry, ncarry, d_q, d_evals);
+}
+
+int fr_divide_by_roots_device(const uint32_t* d_a, size_t n, const uint32_t (*roots_host)[8], uint32_t m, uint32_t* d_q, uint32_t* d_evals, void* ws,
+                              size_t ws_bytes, hipStream_t stream) {
+  if (m == 0 || m > ZKHIP_MAX_ROOTS) { set_error("divide_by_roots: %u roots (1 .. %d)", m, ZKHIP_MAX_ROOTS); return ZKHIP_EINVAL; }
+  if (n == 0) {
+    if (d_evals) HIPCHK(hipMemsetAsync(d_evals, 0, (size_t)m * 32, stream));
+    return ZKHIP_OK;
+  }
+  if (ws_bytes < poly_roots_workspace_bytes(n, m)) { set_error("divide_by_roots: workspace too small"); return ZKHIP_EINVAL; }
+  if (m == 1 && !d_evals) {                                   // one root, no evaluation wanted: kate_division as it is, and its one missing element
+    int rc = fr_kate_division_device(d_a, n, roots_host[0], d_q, ws, ws_bytes, stream);
+    if (rc != ZKHIP_OK) return rc;
+    HIPCHK(hipMemsetAsync(d_q + (n - 1) * 8, 0, 32, stream));
+    return ZKHIP_OK;
+  }
+  // constants.  z[i]; Z's coefficients c (monic, degree m); V[j][i] = w_i [X^j] Z / (X - z_i) with w_i = 1 / prod_{j != i} (z_i - z_j)
+  fe z[ZKHIP_MAX_ROOTS], c[ZKHIP_MAX_ROOTS + 1], w[ZKHIP_MAX_ROOTS];
+  for (uint32_t i = 0; i < m; i++) z[i] = h_from_ext(roots_host[i]);
+  c[0] = fe_one<Fr>();
+  for (uint32_t i = 0; i < m; i++) {                          // c <- c * (X - z_i)
+    c[i + 1] = c[i];
+    for (uint32_t j = i; j >= 1; j--) c[j] = h_sub(c[j - 1], h_mul(z[i], c[j]));
+    c[0] = h_neg(h_mul(z[i], c[0]));
+  }
+  fe den = fe_one<Fr>();                                      // one inversion: 1 / prod_i Z'(z_i), then w_i = that times the other derivatives
+  fe dz[ZKHIP_MAX_ROOTS];
+  for (uint32_t i = 0; i < m; i++) {
+    dz[i] = fe_one<Fr>();
+    for (uint32_t j = 0; j < m; j++) if (j != i) dz[i] = h_mul(dz[i], h_sub(z[i], z[j]));
+    den = h_mul(den, dz[i]);
+  }
+  if (fe_is_zero_limbs(den)) { set_error("divide_by_roots: two equal roots"); return ZKHIP_EINVAL; }
+  const fe den_inv = h_inverse(den);
+  for (uint32_t i = 0; i < m; i++) {
+    w[i] = den_inv;
+    for (uint32_t j = 0; j < m; j++) if (j != i) w[i] = h_mul(w[i], dz[j]);
+  }
+  roots_div_k dk;
+  memset(&dk, 0, sizeof dk);
+  for (uint32_t j = 0; j < m; j++) h_store(h_neg(c[j]), dk.nc[j]);
+  for (uint32_t i = 0; i < m; i++) {                          // Z / (X - z_i) by synthetic division from the top: d_(m-1) = 1, d_(j-1) = c_j + z_i d_j
+    fe d = fe_one<Fr>();
+    for (uint32_t j = m; j-- > 0;) {
+      h_store(h_mul(w[i], d), dk.v[j][i]);
+      d = h_add(c[j], h_mul(z[i], d));
+    }
+  }
+  roots_k zk;
+  memset(&zk, 0, sizeof zk);
+  for (uint32_t i = 0; i < m; i++) h_store(z[i], zk.l[i]);
+  auto next_level = [&]() {                                   // z_i <- z_i^CH
+    static_assert(POLY_CH == 16, "z^CH below is four squarings");
+    for (uint32_t i = 0; i < m; i++) { for (int s = 0; s < 4; s++) z[i] = h_mul(z[i], z[i]); h_store(z[i], zk.l[i]); }
+  };
+
+  const size_t n1 = chunks_of(n);
+  uint32_t* level[16];
+  size_t level_n[16];
+  int levels = 0;
+  if (n1 == 1) {                                              // one chunk: no carries; the aggregates are the evaluations
+    if (d_evals) {
+      switch (m) {
+        case 1: launch_roots_agg<1>(d_a, n, zk, d_evals, 1, stream); break;
+        case 2: launch_roots_agg<2>(d_a, n, zk, d_evals, 1, stream); break;
+        case 3: launch_roots_agg<3>(d_a, n, zk, d_evals, 1, stream); break;
+        case 4: launch_roots_agg<4>(d_a, n, zk, d_evals, 1, stream); break;
+        case 5: launch_roots_agg<5>(d_a, n, zk, d_evals, 1, stream); break;
+        case 6: launch_roots_agg<6>(d_a, n, zk, d_evals, 1, stream); break;
+        case 7: launch_roots_agg<7>(d_a, n, zk, d_evals, 1, stream); break;
+        default: launch_roots_agg<8>(d_a, n, zk, d_evals, 1, stream); break;
+      }
+    }
+  } else {
+    char* p = (char*)ws;
+    level[0] = (uint32_t*)p;
+    level_n[0] = n1;
+    levels = 1;
+    switch (m) {
+      case 1: launch_roots_agg<1>(d_a, n, zk, level[0], n1, stream); break;
+      case 2: launch_roots_agg<2>(d_a, n, zk, level[0], n1, stream); break;
+      case 3: launch_roots_agg<3>(d_a, n, zk, level[0], n1, stream); break;
+      case 4: launch_roots_agg<4>(d_a, n, zk, level[0], n1, stream); break;
+      case 5: launch_roots_agg<5>(d_a, n, zk, level[0], n1, stream); break;
+      case 6: launch_roots_agg<6>(d_a, n, zk, level[0], n1, stream); break;
+      case 7: launch_roots_agg<7>(d_a, n, zk, level[0], n1, stream); break;
+      default: launch_roots_agg<8>(d_a, n, zk, level[0], n1, stream); break;
+    }
+    roots_k zks[16];                                          // the multipliers of level l: z^(CH^(l + 1))
+    while (true) {
+      next_level();
+      zks[levels - 1] = zk;
+      const size_t cn = level_n[levels - 1];
+      if (cn <= POLY_CH) break;
+      p += (((size_t)m * cn * 32 + 255) / 256) * 256;
+      const size_t nn = chunks_of(cn);
+      level[levels] = (uint32_t*)p;
+      level_n[levels] = nn;
+      hipLaunchKernelGGL(k_roots_agg_level, dim3((unsigned)((nn + 255) / 256), m), dim3(256), 0, stream, (const uint32_t*)level[levels - 1], cn, zk, level[levels], nn);
+      levels++;
+    }
+    for (int l = levels - 1; l >= 0; l--) {                   // down: scan every level in place with the scanned level above as carries
+      const size_t cn = level_n[l];
+      const uint32_t* carry = l + 1 < levels ? level[l + 1] : nullptr;
+      hipLaunchKernelGGL(k_roots_apply_level, dim3((unsigned)((chunks_of(cn) + 255) / 256), m), dim3(256), 0, stream, level[l], cn, zks[l], carry,
+                         l + 1 < levels ? level_n[l + 1] : (size_t)0);
+    }
+  }
+  const uint32_t* carry = levels ? level[0] : nullptr;
+  switch (m) {
+    case 1: launch_roots_div<1>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
+    case 2: launch_roots_div<2>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
+    case 3: launch_roots_div<3>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
+    case 4: launch_roots_div<4>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
+    case 5: launch_roots_div<5>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
+    case 6: launch_roots_div<6>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
+    case 7: launch_roots_div<7>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
+    default: launch_roots_div<8>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
+  }
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
+}
+
 static int prefix_product_rec(const uint32_t* d_v, size_t n, const uint32_t* carry, uint32_t* d_out, char* ws, hipStream_t stream);
 
 // exclusive prefix product: out[0] = 1, out[i] = v[0] ... v[i-1]   (out may alias v)

@@ -138,6 +138,11 @@ size_t poly_batch_workspace_bytes(size_t n, size_t count);
 int fr_eval_polynomial_batch_device(const void* const* d_polys_host, size_t count, size_t n, const uint32_t x_host[8], uint32_t* d_results,
                                     void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
 int fr_kate_division_device(const uint32_t* d_a, size_t n, const uint32_t b_host[8], uint32_t* d_q, void* ws, size_t ws_bytes, hipStream_t stream);
+// quotient of a(X) by prod_i (X - roots[i]) (m <= ZKHIP_MAX_ROOTS distinct canonical roots, external words, host memory): d_q gets n elements (n - m
+// coefficients, m zeros), d_evals (nullable) a(roots[i]).  d_q must not overlap d_a.
+size_t poly_roots_workspace_bytes(size_t n, uint32_t m);
+int fr_divide_by_roots_device(const uint32_t* d_a, size_t n, const uint32_t (*roots_host)[8], uint32_t m, uint32_t* d_q, uint32_t* d_evals, void* ws,
+                              size_t ws_bytes, hipStream_t stream);
 int fr_prefix_product_device(const uint32_t* d_v, size_t n, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream);
 int fr_batch_invert_device(uint32_t* d_a, size_t n, void* ws, size_t ws_bytes, hipStream_t stream);
 // the l0 / l_last / l_active_row cosets of the proving key over a window of W elements (global rows start, start + 1, ... mod 2^ext_k), closed form.

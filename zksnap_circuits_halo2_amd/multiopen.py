@@ -152,8 +152,8 @@ class ProverGWC:
 #   L(X)  = sum_i v^i Z_{T \ S_i}(u) sum_j y^j (P_ij(X) - R_ij(u))  -  Z_T(u) h(X),     T = all points;   L(u) = 0
 #   h'(X) = L(X) / (X - u) / Z_{T \ S_0}(u)                                                                              -> commit: H'
 #
-# Device work: the y- and v-combinations are fused row programs over the device-resident polynomials, the divisions
-# `zkhip_fr_kate_division_device`, the two commitments prepared MSMs; the interpolations are host arithmetic on a handful of points.
+# Device work: the y- and v-combinations are fused row programs over the device-resident polynomials, the divisions one
+# `zkhip_fr_divide_by_roots_device` per rotation set, the two commitments prepared MSMs; the interpolations are host arithmetic on a handful of points.
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _interpolate(points: Sequence[int], evals: Sequence[int]) -> List[int]:
     """`lagrange_interpolate`: coefficients (low to high) of the polynomial of degree < len(points) through (points[i], evals[i])"""
@@ -231,15 +231,20 @@ class ProverSHPLONK:
                 _sub_const_at(d_poly, t, val, stream)
 
     def _divide(self, d_poly: int, d_tmp: int, roots: Sequence[int], stream: int) -> int:
-        """`div_by_vanishing`: successive `kate_division`s, the quotient kept at n coefficients (zero-padded); returns the buffer that holds it"""
+        """`div_by_vanishing`: one `zkhip_fr_divide_by_roots_device` for the whole point set, the quotient kept at n coefficients (the top
+        len(roots) zero); returns the buffer that holds it.  More points than ZKHIP_MAX_ROOTS (no rotation set of halo2): the fold."""
         lib = _lib.load()
-        src, dst = d_poly, d_tmp
-        for z in roots:
-            zw = fr_encode([z])[0]
-            _lib.check(lib.zkhip_fr_kate_division_device(C.c_void_p(src), self.n, zw.ctypes.data, C.c_void_p(dst), stream))
-            _zero_at(dst, self.n - 1, stream)
-            src, dst = dst, src
-        return src
+        if len(roots) > _lib.ZKHIP_MAX_ROOTS:
+            src, dst = d_poly, d_tmp
+            for z in roots:
+                zw = fr_encode([z])[0]
+                _lib.check(lib.zkhip_fr_kate_division_device(C.c_void_p(src), self.n, zw.ctypes.data, C.c_void_p(dst), stream))
+                _zero_at(dst, self.n - 1, stream)
+                src, dst = dst, src
+            return src
+        zw = fr_encode(list(roots))
+        _lib.check(lib.zkhip_fr_divide_by_roots_device(C.c_void_p(d_poly), self.n, zw.ctypes.data, len(roots), C.c_void_p(d_tmp), None, stream))
+        return d_tmp
 
     def create_proof(self, queries: Sequence[ProverQuery], y: int, v: int, u: int, stream: int = 0):
         """-> (H, H') as 12-limb Jacobian commitments.  In the reference y and v are squeezed before h is committed and u after h has been
@@ -259,10 +264,9 @@ class ProverSHPLONK:
             quotients = []
             for rs in sets:
                 ypow = [pow(y, j, R_MOD) for j in range(len(rs.polys))]
-                low = [_interpolate(rs.points, ev) for ev in rs.evals]                         # R_ij, len(points) coefficients each
                 acc, tmp = alloc(), alloc()
                 E.linear_combination_program(ypow).run_device(rs.polys, self.k, acc, stream=stream)
-                self._patch_low(acc, [sum(yp * lo[t] for yp, lo in zip(ypow, low)) % R_MOD for t in range(len(rs.points))], stream)
+                # the quotient by Z_i is the same polynomial whether or not sum_j y^j R_ij (degree < the number of points) is subtracted first
                 quotients.append(self._divide(acc, tmp, rs.points, stream))
             vpow = [pow(v, i, R_MOD) for i in range(len(sets))]
             h_x = alloc()

@@ -341,6 +341,21 @@ int zkhip_permutation_products_device(const void *const *d_values, const void *c
 int zkhip_lookup_permute(const uint64_t *input, const uint64_t *table, size_t usable_rows, uint64_t *permuted_input, uint64_t *permuted_table);
 int zkhip_lookup_permute_device(const void *d_input, const void *d_table, size_t usable_rows, void *d_permuted_input, void *d_permuted_table,
                                 void *stream);
+/* The lookup argument of EVERY lookup of a circuit, one call per transcript phase (A' and S' are committed before beta and gamma exist).  The
+ * launches of a call do not grow with n_lookups, and the call waits for the stream once, for its status.
+ * permute_expression_pair of n_lookups lookups at once. d_inputs[l] / d_tables[l]: the compressed input / table expression of lookup l
+ * (device, >= usable_rows elements; equal table addresses are one table and are sorted once). d_permuted_inputs / d_permuted_tables:
+ * [n_lookups][2^log_n] dense; rows < usable_rows of every column are written, rows >= usable_rows are not touched.  An input value missing
+ * from its table: ZKHIP_EINVAL, zkhip_last_error names the lowest failing lookup index and the outputs are unspecified.  n_lookups == 0 or
+ * usable_rows == 0: ZKHIP_OK, nothing written. */
+int zkhip_lookup_permute_many_device(const void *const *d_inputs, const void *const *d_tables, uint32_t n_lookups, uint32_t log_n, size_t usable_rows,
+                                     void *d_permuted_inputs, void *d_permuted_tables, void *stream);
+/* z[l][0] = 1, z[l][i+1] = z[l][i] (a_l[i] + beta)(s_l[i] + gamma) / ((a'_l[i] + beta)(s'_l[i] + gamma)) for i < usable_rows; the rows after
+ * usable_rows repeat z[l][usable_rows] (the caller overwrites them, as with zkhip_permutation_products). Zero denominators count as zero.
+ * d_permuted_inputs / d_permuted_tables / d_z: [n_lookups][2^log_n] dense; rows >= usable_rows of the permuted columns are not read. */
+int zkhip_lookup_products_device(const void *const *d_inputs, const void *const *d_tables, const void *d_permuted_inputs, const void *d_permuted_tables,
+                                 uint32_t n_lookups, uint32_t log_n, size_t usable_rows, const uint64_t beta[4], const uint64_t gamma[4], void *d_z,
+                                 void *stream);
 
 /* ---- device buffers for a host that does not link HIP itself (handles instead of host slices) ---- */
 /* The `_device` entry points below take HIP device pointers so that polynomials stay in HBM from iNTT through commit, extended

@@ -1127,6 +1127,44 @@ inline void linear_combination(const std::vector<Fr>& coeffs, const std::vector<
   if (out.size() < n) throw std::invalid_argument("linear_combination: output shorter than 2^k");
   check(zkhip_fr_linear_combination_device(ptrs.data(), coeffs.empty() ? nullptr : coeffs.data()->l, coeffs.size(), n, out.data(), nullptr), "linear_combination");
 }
+// plonk::lookup::prover::permute_expression_pair of EVERY lookup of a circuit in one call: inputs[l] / tables[l] = the compressed input / table
+// expression of lookup l in HBM (the same DeviceVec given as several lookups' table is sorted once); permuted_inputs / permuted_tables hold
+// [lookups][2^k] elements, rows < usable_rows of every column are written, the blinding rows behind them are the caller's.  Throws (like the
+// reference's ConstraintSystemFailure) when an input value is missing from its table; the message names the lowest such lookup.
+inline void permute_expression_pairs_device(const std::vector<const DeviceVec*>& inputs, const std::vector<const DeviceVec*>& tables, uint32_t k, size_t usable_rows,
+                                            DeviceVec& permuted_inputs, DeviceVec& permuted_tables) {
+  if (inputs.size() != tables.size()) throw std::invalid_argument("permute_expression_pairs_device: inputs.len() != tables.len()");
+  const size_t n = (size_t)1 << k;
+  std::vector<const void*> in, tab;
+  for (size_t l = 0; l < inputs.size(); l++) {
+    if (inputs[l]->size() < usable_rows || tables[l]->size() < usable_rows) throw std::invalid_argument("permute_expression_pairs_device: usable_rows > len");
+    in.push_back(inputs[l]->data());
+    tab.push_back(tables[l]->data());
+  }
+  if (permuted_inputs.size() < inputs.size() * n || permuted_tables.size() < inputs.size() * n) throw std::invalid_argument("permute_expression_pairs_device: output too short");
+  if (in.size() == 1 && usable_rows >= (size_t(1) << 20)) {   // one lookup over 2^20 rows or more: the single call's two sorts beat a search per row (same bytes)
+    check(zkhip_lookup_permute_device(in[0], tab[0], usable_rows, permuted_inputs.data(), permuted_tables.data(), nullptr), "permute_expression_pairs_device");
+    return;
+  }
+  check(zkhip_lookup_permute_many_device(in.data(), tab.data(), (uint32_t)in.size(), k, usable_rows, permuted_inputs.data(), permuted_tables.data(), nullptr),
+        "permute_expression_pairs_device");
+}
+// plonk::lookup::prover::commit_product of every lookup in one call: z = [lookups][2^k], z[l][0] = 1, the rows after usable_rows repeat
+// z[l][usable_rows] (the caller writes its blinding scalars there)
+inline void lookup_products_device(const std::vector<const DeviceVec*>& inputs, const std::vector<const DeviceVec*>& tables, const DeviceVec& permuted_inputs,
+                                   const DeviceVec& permuted_tables, uint32_t k, size_t usable_rows, const Fr& beta, const Fr& gamma, DeviceVec& z) {
+  if (inputs.size() != tables.size()) throw std::invalid_argument("lookup_products_device: inputs.len() != tables.len()");
+  const size_t n = (size_t)1 << k;
+  std::vector<const void*> in, tab;
+  for (size_t l = 0; l < inputs.size(); l++) {
+    if (inputs[l]->size() < usable_rows || tables[l]->size() < usable_rows) throw std::invalid_argument("lookup_products_device: usable_rows > len");
+    in.push_back(inputs[l]->data());
+    tab.push_back(tables[l]->data());
+  }
+  if (permuted_inputs.size() < in.size() * n || permuted_tables.size() < in.size() * n || z.size() < in.size() * n) throw std::invalid_argument("lookup_products_device: column block too short");
+  check(zkhip_lookup_products_device(in.data(), tab.data(), permuted_inputs.data(), permuted_tables.data(), (uint32_t)in.size(), k, usable_rows, beta.l, gamma.l, z.data(), nullptr),
+        "lookup_products_device");
+}
 // d_poly[index] -= value / d_poly[index] = 0: one-row programs on the element itself (no host round trip)
 inline void sub_const_at(DeviceVec& poly, size_t index, const Fr& value) {
   zkhip_vm_insn insn{ZKHIP_OP_SUB, 0, 0, RowProgram::column(0, 0), RowProgram::constant(0), zkhip_vm_operand{}};

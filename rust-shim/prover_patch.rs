@@ -126,14 +126,16 @@ pub(crate) struct DeviceProof {
 //   advice (per phase)     base.upload(col, 0, &advice_values[i]) for the phase's columns; commitments = base.commit_many(first, count, n,
 //                          &params.g_lagrange, identity) -> batch_normalize -> transcript (unchanged from here)
 //   lookups, theta         compressed input / table expressions = DevCols::eval_rows(&lower_expression(..)) over base columns (a lookup of plain
-//                          columns needs no program); base.lookup_permute(..) writes the permuted pair; blinding rows:
-//                          base.upload(col, usable_rows, &random_rows); commit_many of the pair
+//                          columns needs no program); base.lookup_permute_many(&input_addresses, &table_addresses, k, usable_rows, first_permuted_input,
+//                          first_permuted_table) writes the permuted pair of EVERY lookup in one call (no input column is sorted, the table once per
+//                          distinct address, one wait for the status); blinding rows: base.upload(col, usable_rows, &random_rows); commit_many of the pairs
 //   permutation, beta/gamma  base.permutation_products(first_perm_product, &value_addresses, &sigma_addresses, chunk_len, k, usable_rows, &beta, &gamma,
 //                          &F::DELTA, &omega): every chunk's z, chained through z[usable_rows], in one call (a handful of launches whatever the
 //                          number of chunks: hundreds at the voter / state-transition column counts); blinding rows uploaded; commit_many over
 //                          all chunks.  (Before this entry point existed: per chunk a numerator and a denominator program,
 //                          base.grand_product, a 32-byte download and a scaling program.)
-//   lookup products        (a' + beta)(s' + gamma) denominators, (compressed input + beta)(compressed table + gamma) numerators, grand_product
+//   lookup products        base.lookup_products(first_lookup_product, &input_addresses, &table_addresses, first_permuted_input, first_permuted_table, k,
+//                          usable_rows, &beta, &gamma): every lookup's z in one call; blinding rows uploaded; commit_many over all lookups
 //   vanishing random poly  generated on the host as upstream, committed through best_multiexp (one column; stays on the host path)
 //   y                      base.ifft_scaled_many(first_advice, all witness-dependent columns, ..): lagrange_to_coeff in place, one call
 //   quotient               base.coeff_to_extended_many(.., &ext, ..) for the witness-dependent columns; DevCols::eval_rows(&quotient_program, all

@@ -73,6 +73,11 @@ extern "C" {
                                          stream: *mut c_void) -> c_int;
     fn zkhip_lookup_permute_device(d_input: *const c_void, d_table: *const c_void, usable_rows: usize, d_permuted_input: *mut c_void,
                                    d_permuted_table: *mut c_void, stream: *mut c_void) -> c_int;
+    fn zkhip_lookup_permute_many_device(d_inputs: *const *const c_void, d_tables: *const *const c_void, n_lookups: u32, log_n: u32, usable_rows: usize,
+                                        d_permuted_inputs: *mut c_void, d_permuted_tables: *mut c_void, stream: *mut c_void) -> c_int;
+    fn zkhip_lookup_products_device(d_inputs: *const *const c_void, d_tables: *const *const c_void, d_permuted_inputs: *const c_void,
+                                    d_permuted_tables: *const c_void, n_lookups: u32, log_n: u32, usable_rows: usize, beta: *const u64, gamma: *const u64,
+                                    d_z: *mut c_void, stream: *mut c_void) -> c_int;
     fn zkhip_fr_eval_polynomial_batch_device(d_polys: *const *const c_void, count: usize, n: usize, point: *const u64, d_out: *mut c_void,
                                              stream: *mut c_void) -> c_int;
 }
@@ -516,6 +521,39 @@ impl DevCols {
         // SAFETY: outputs do not alias the inputs (different blocks or different columns)
         let rc = unsafe { zkhip_lookup_permute_device(self.at(input, 0), self.at(table, 0), usable_rows, out.at(pin, 0), out.at(ptab, 0), std::ptr::null_mut()) };
         if rc != 0 { warn_once("zkhip_lookup_permute_device", rc); }   // ZKHIP_EINVAL = an input value missing from the table (Error::ConstraintSystemFailure upstream)
+        rc == 0
+    }
+    /// `permute_expression_pair` of EVERY lookup in one call: `inputs[l]` / `tables[l]` = device addresses of lookup l's compressed input / table
+    /// expression (equal table addresses are sorted once); columns [pin_first, pin_first + lookups) of self receive A', columns [ptab_first, ..) S',
+    /// first `usable_rows` rows each.  false = ZKHIP_EINVAL: an input value missing from its table (Error::ConstraintSystemFailure upstream)
+    pub(crate) fn lookup_permute_many(&self, inputs: &[*const c_void], tables: &[*const c_void], log_n: u32, usable_rows: usize, pin_first: usize,
+                                      ptab_first: usize) -> bool {
+        let l = inputs.len();
+        if l != tables.len() || self.len != 1usize << log_n.min(28) || pin_first + l > self.count || ptab_first + l > self.count { return false; }
+        if l == 1 && usable_rows >= 1usize << 20 {
+            // one lookup over 2^20 rows or more: the single call's two sorts beat a search per row (same bytes)
+            // SAFETY: outputs do not alias the inputs
+            let rc = unsafe { zkhip_lookup_permute_device(inputs[0], tables[0], usable_rows, self.at(pin_first, 0), self.at(ptab_first, 0), std::ptr::null_mut()) };
+            if rc != 0 { warn_once("zkhip_lookup_permute_device", rc); }
+            return rc == 0;
+        }
+        // SAFETY: the output columns are adjacent in this block (stride = len = 2^log_n elements: the dense [lookups][n] layout the C ABI writes)
+        let rc = unsafe { zkhip_lookup_permute_many_device(inputs.as_ptr(), tables.as_ptr(), l as u32, log_n, usable_rows, self.at(pin_first, 0),
+                                                           self.at(ptab_first, 0), std::ptr::null_mut()) };
+        if rc != 0 { warn_once("zkhip_lookup_permute_many_device", rc); }
+        rc == 0
+    }
+    /// every lookup's product column in one call (`lookup::prover::commit_product`): columns [z_first, z_first + lookups) of self receive z from the
+    /// permuted pairs in columns [pin_first, ..) / [ptab_first, ..); the caller then uploads its blinding rows behind usable_rows
+    pub(crate) fn lookup_products<F: 'static>(&self, z_first: usize, inputs: &[*const c_void], tables: &[*const c_void], pin_first: usize, ptab_first: usize,
+                                              log_n: u32, usable_rows: usize, beta: &F, gamma: &F) -> bool {
+        let l = inputs.len();
+        if !is::<F, Fr>() || l != tables.len() || self.len != 1usize << log_n.min(28) || z_first + l > self.count || pin_first + l > self.count
+            || ptab_first + l > self.count { return false; }
+        // SAFETY: dense [lookups][n] column runs of this block; z does not overlap the permuted pairs
+        let rc = unsafe { zkhip_lookup_products_device(inputs.as_ptr(), tables.as_ptr(), self.at(pin_first, 0), self.at(ptab_first, 0), l as u32, log_n, usable_rows,
+                                                       beta as *const F as *const u64, gamma as *const F as *const u64, self.at(z_first, 0), std::ptr::null_mut()) };
+        if rc != 0 { warn_once("zkhip_lookup_products_device", rc); }
         rc == 0
     }
     /// h(X) (X^n - 1) evaluations in column `col` -> divided by the vanishing polynomial -> `out_len` coefficients in column `out_col` of `out`

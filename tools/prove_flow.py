@@ -36,8 +36,11 @@ _SIDE_STREAM = None
 
 
 def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False,
-        sharded_key=False):
-    """sharded_quotient: the single-program quotient goes through zkhip_fr_eval_rows_sharded_device (rows cut over the devices of zkhip_init; the
+        sharded_key=False, lookups_one_call=True):
+    """lookups_one_call: the lookup argument of every lookup through zkhip_lookup_permute_many_device + zkhip_lookup_products_device (two calls per
+    proof); False: one lookup at a time (the single-lookup call, two row programs and a grand product each).  The same bytes either way.
+    corrupt: "gate" / "copy" break the witness; "lookup" puts a value outside the table into lookup column 1 (ZkhipError from the lookup phase).
+    sharded_quotient: the single-program quotient goes through zkhip_fr_eval_rows_sharded_device (rows cut over the devices of zkhip_init; the
     key's cosets EXTENDED, the proof's columns COEFF, transformed inside the call) instead of coeff_to_extended + the whole-domain launch.
     sharded_key (needs sharded_quotient): the device key keeps its cosets as a row-shard set (keygen_device / from_host with row_shards) and the
     quotient reads them as COL_ROW_SHARDS, where they lie -- nothing of the key crosses between devices during the proof.
@@ -169,6 +172,8 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             advice[0][7] = advice[0][8].clone()
         if corrupt == "copy":
             advice[0][21] = advice[0][22].clone()
+        if corrupt == "lookup":
+            lks[1][3] = small_ints(torch.full((n,), 1 << lookup_bits, dtype=torch.int64, device=dev))[3]      # one value outside the table
         lap("witness_columns")
         adv_commit = commit_all(h_gl, advice)                                       # advice is committed in the Lagrange basis
         lap("commit_advice")
@@ -234,17 +239,31 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
         lap("permutation_products")
 
         # ---- lookup argument ---------------------------------------------------------------------------------------------------
-        pn, pd = E.lookup_product_programs(1, 1, beta, gamma, theta)
         lookup_cols, lookup_closes = [], True
-        for lk in lks:
-            pa, ps = rand_fr(n), rand_fr(n)                                         # rows >= u stay random (blinding)
-            _lib.check(lib.zkhip_lookup_permute_device(lk.data_ptr(), table.data_ptr(), u, pa.data_ptr(), ps.data_ptr(), None))
-            zl = run_prog(pn, [lk, table], k)
-            den = run_prog(pd, [pa, ps], k)
-            _lib.check(lib.zkhip_fr_grand_product_device(zl.data_ptr(), den.data_ptr(), n, zl.data_ptr(), None))
-            lookup_closes = lookup_closes and F.fr_decode(zl[u].cpu().numpy().view(np.uint64))[0] == 1
-            zl[u + 1:] = rand_fr(n - u - 1)
-            lookup_cols += [zl, pa, ps]
+        if lookups_one_call and NL and not (NL == 1 and k >= 20):            # a single lookup over 2^20 rows or more stays with the loop
+            # both phases of every lookup in one call each; the blinding rows are drawn in the per-lookup order of the loop below (pa, ps, z tail)
+            pa_all, ps_all = torch.empty((NL, n, 4), dtype=torch.int64, device=dev), torch.empty((NL, n, 4), dtype=torch.int64, device=dev)
+            tails = []
+            for j in range(NL):
+                pa_all[j], ps_all[j] = rand_fr(n), rand_fr(n)                      # rows >= u stay random (blinding)
+                tails.append(rand_fr(n - u - 1))
+            E.permute_expression_pairs_device(lks, [table] * NL, u, k, pa_all, ps_all)
+            z_lk = E.lookup_products_device(lks, [table] * NL, pa_all, ps_all, u, k, beta, gamma)
+            lookup_closes = all(v_ == 1 for v_ in F.fr_decode(z_lk[:, u].contiguous().cpu().numpy().view(np.uint64)))
+            for j in range(NL):
+                z_lk[j, u + 1:] = tails[j]
+                lookup_cols += [z_lk[j], pa_all[j], ps_all[j]]
+        else:
+            pn, pd = E.lookup_product_programs(1, 1, beta, gamma, theta)
+            for lk in lks:
+                pa, ps = rand_fr(n), rand_fr(n)                                     # rows >= u stay random (blinding)
+                _lib.check(lib.zkhip_lookup_permute_device(lk.data_ptr(), table.data_ptr(), u, pa.data_ptr(), ps.data_ptr(), None))
+                zl = run_prog(pn, [lk, table], k)
+                den = run_prog(pd, [pa, ps], k)
+                _lib.check(lib.zkhip_fr_grand_product_device(zl.data_ptr(), den.data_ptr(), n, zl.data_ptr(), None))
+                lookup_closes = lookup_closes and F.fr_decode(zl[u].cpu().numpy().view(np.uint64))[0] == 1
+                zl[u + 1:] = rand_fr(n - u - 1)
+                lookup_cols += [zl, pa, ps]
         lap("lookup_permute_and_product")
 
         # ---- Lagrange -> coefficients, commitments, extended coset ---------------------------------------------------------------

@@ -1843,6 +1843,47 @@ int zkhip_lookup_permute_device(const void* d_input, const void* d_table, size_t
                                (uint32_t*)d_permuted_table, sc->vm.p, sc->vm.cap, s);
 }
 
+// every argument error of the two many-lookup calls; nothing has been enqueued when it fails
+static int lookup_many_args_ok(const char* what, const void* const* d_inputs, const void* const* d_tables, uint32_t n_lookups, uint32_t log_n, size_t usable_rows,
+                               bool others_ok) {
+  if (!d_inputs || !d_tables || !others_ok) { set_error("%s: null pointer", what); return ZKHIP_EINVAL; }
+  if (log_n > 28 || usable_rows > ((size_t)1 << log_n)) { set_error("%s: bad shape (log_n %u, usable_rows %zu)", what, log_n, usable_rows); return ZKHIP_EINVAL; }
+  for (uint32_t l = 0; l < n_lookups; l++)
+    if (!d_inputs[l] || !d_tables[l]) { set_error("%s: a column of lookup %u is null", what, l); return ZKHIP_EINVAL; }
+  return ZKHIP_OK;
+}
+
+int zkhip_lookup_permute_many_device(const void* const* d_inputs, const void* const* d_tables, uint32_t n_lookups, uint32_t log_n, size_t usable_rows,
+                                     void* d_permuted_inputs, void* d_permuted_tables, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if (n_lookups == 0 || usable_rows == 0) return ZKHIP_OK;
+  if ((rc = lookup_many_args_ok("lookup_permute_many", d_inputs, d_tables, n_lookups, log_n, usable_rows, d_permuted_inputs && d_permuted_tables)) != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->vm.reserve(lookup_permute_many_workspace_bytes(n_lookups, usable_rows))) != ZKHIP_OK) return rc;
+  return lookup_permute_many_device(d_inputs, d_tables, n_lookups, (size_t)1 << log_n, usable_rows, (uint32_t*)d_permuted_inputs, (uint32_t*)d_permuted_tables,
+                                    sc->vm.p, sc->vm.cap, s, &sc->args);
+}
+
+int zkhip_lookup_products_device(const void* const* d_inputs, const void* const* d_tables, const void* d_permuted_inputs, const void* d_permuted_tables,
+                                 uint32_t n_lookups, uint32_t log_n, size_t usable_rows, const uint64_t beta[4], const uint64_t gamma[4], void* d_z, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if (n_lookups == 0 || usable_rows == 0) return ZKHIP_OK;
+  if ((rc = lookup_many_args_ok("lookup_products", d_inputs, d_tables, n_lookups, log_n, usable_rows, d_permuted_inputs && d_permuted_tables && beta && gamma && d_z)) !=
+      ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->ws.reserve(lookup_products_workspace_bytes(n_lookups, log_n))) != ZKHIP_OK) return rc;
+  return fr_lookup_products_device(d_inputs, d_tables, (const uint32_t*)d_permuted_inputs, (const uint32_t*)d_permuted_tables, n_lookups, log_n, usable_rows,
+                                   (const uint32_t*)beta, (const uint32_t*)gamma, (uint32_t*)d_z, sc->ws.p, sc->ws.cap, s, &sc->args);
+}
+
 int zkhip_lookup_permute(const uint64_t* input, const uint64_t* table, size_t usable_rows, uint64_t* permuted_input, uint64_t* permuted_table) {
   ZK_API_RANGE();
   if (usable_rows && (!input || !table || !permuted_input || !permuted_table)) { set_error("lookup_permute: null pointer"); return ZKHIP_EINVAL; }

@@ -107,8 +107,7 @@ __global__ void __launch_bounds__(256) k_horner_agg_batch(const uint32_t* const*
 }
 
 // ---- prefix product --------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_prod_agg(const uint32_t* __restrict__ v, size_t n, uint32_t* __restrict__ agg) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void prod_agg_chunk(const uint32_t* __restrict__ v, size_t n, uint32_t* __restrict__ agg, size_t t) {
   const size_t lo = t * POLY_CH;
   if (lo >= n) return;
   const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
@@ -134,10 +133,17 @@ __global__ void __launch_bounds__(256) k_prod_agg(const uint32_t* __restrict__ v
   store_canon(agg, t, acc);
 }
 
+__global__ void __launch_bounds__(256) k_prod_agg(const uint32_t* __restrict__ v, size_t n, uint32_t* __restrict__ agg) {
+  prod_agg_chunk(v, n, agg, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+// blockIdx.y = one of many independent arrays of n elements, dense; m = chunks of one array
+__global__ void __launch_bounds__(256) k_prod_agg_batch(const uint32_t* __restrict__ v, size_t n, uint32_t* __restrict__ agg, size_t m) {
+  prod_agg_chunk(v + (size_t)blockIdx.y * n * 8, n, agg + (size_t)blockIdx.y * m * 8, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 // out[i] = carry[t] * prod_{lo <= j < i} v[j]   (exclusive); carry == nullptr: carry is 1
-__global__ void __launch_bounds__(256) k_prod_apply(const uint32_t* __restrict__ v, size_t n, const uint32_t* __restrict__ carry,
-                                                    uint32_t* __restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void prod_apply_chunk(const uint32_t* __restrict__ v, size_t n, const uint32_t* __restrict__ carry, uint32_t* __restrict__ out,
+                                                 size_t t) {
   const size_t lo = t * POLY_CH;
   if (lo >= n) return;
   const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
@@ -165,6 +171,16 @@ __global__ void __launch_bounds__(256) k_prod_apply(const uint32_t* __restrict__
     store_canon(out, i, cur);
     cur = fe_mul<Fr>(cur, f);
   }
+}
+
+__global__ void __launch_bounds__(256) k_prod_apply(const uint32_t* __restrict__ v, size_t n, const uint32_t* __restrict__ carry,
+                                                    uint32_t* __restrict__ out) {
+  prod_apply_chunk(v, n, carry, out, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void __launch_bounds__(256) k_prod_apply_batch(const uint32_t* __restrict__ v, size_t n, const uint32_t* __restrict__ carry, size_t m,
+                                                          uint32_t* __restrict__ out) {
+  prod_apply_chunk(v + (size_t)blockIdx.y * n * 8, n, carry ? carry + (size_t)blockIdx.y * m * 8 : nullptr, out + (size_t)blockIdx.y * n * 8,
+                   (size_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // ---- batch inversion (zeros stay zero, like ff::BatchInvert) ------------------------------------------
@@ -805,6 +821,109 @@ int fr_permutation_products_device(const void* const* d_values_host, const void*
   rc = fr_prefix_product_device(d_z, nsets * n, d_z, p, rest, stream);
   prof_mark(stream, "perm_scan");
   return rc;
+}
+
+// ---- lookup argument: every lookup's grand product in one call ------------------------------------------------------------------------------
+// [DEP] halo2-axiom plonk/lookup/prover.rs `commit_product`: z[0] = 1, z[i + 1] = z[i] (a[i] + beta)(s[i] + gamma) / ((a'[i] + beta)(s'[i] + gamma)) over
+// the usable rows.  As with the permutation sets: denominators of all lookups, ONE batch inversion, numerators, one exclusive prefix product with
+// the ratio of the rows >= usable forced to 1 (those rows of A' / S' are the caller's blinding rows, or not written yet: they are not read).  Lookups
+// do not chain, so the scan restarts at every lookup: its kernels take the lookup as blockIdx.y (a chained scan would need every column divided by
+// its own row 0 afterwards: an inversion and a multiply per element more).
+__global__ void __launch_bounds__(256) k_lookup_den(const uint32_t* __restrict__ pa, const uint32_t* __restrict__ ps, size_t n, size_t usable, fe_arg beta,
+                                                    fe_arg gamma, uint32_t* __restrict__ z) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t off = (size_t)blockIdx.y * n;
+  fe acc;
+  if (i >= usable) {                                                                  // 1 in the external domain = 2^256 mod r
+#pragma unroll
+    for (int k = 0; k < NL; k++) acc.l[k] = Fr::TO_EXT[k];
+  } else {
+    uint32_t ws[8];
+    load_words(ps + (off + i) * 8, ws);
+    const fe a = fe_add(load_ext(pa, off + i), fe_unpack<0>(beta.w));                 // external, < 2p
+    const fe t = fe_add(fe_unpack<5>(ws), fr_const_internal(gamma));                  // internal, < 34p
+    acc = fe_mul<Fr>(fe_norm(a), t);                                                  // external x internal: external, < 2p
+  }
+  store_canon(z, off + i, acc);
+}
+
+// z[l][i] <- z[l][i] (a_l[i] + beta)(s_l[i] + gamma) for i < usable; the rows from `usable` on keep their 1
+__global__ void __launch_bounds__(256) k_lookup_num_mul(const uint32_t* const* __restrict__ cols, uint32_t n_lookups, size_t n, size_t usable, fe_arg beta,
+                                                        fe_arg gamma, uint32_t* __restrict__ z) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= usable) return;
+  const uint32_t l = blockIdx.y;
+  uint32_t wa[8], ws[8];
+  load_words(cols[l] + i * 8, wa);
+  load_words(cols[n_lookups + l] + i * 8, ws);
+  const fe a = fe_add(fe_unpack<5>(wa), fr_const_internal(beta));                     // internal, < 34p
+  const fe t = fe_add(fe_unpack<5>(ws), fr_const_internal(gamma));
+  const fe num = fe_mul<Fr>(fe_norm(a), t);                                           // 34 * 34 / 169 + 1 < 8p, then < 2p below
+  uint32_t* zl = z + (size_t)l * n * 8;
+  store_canon(zl, i, fe_mul<Fr>(load_ext(zl, i), fe_norm(num)));                      // external (1 / den) x internal: external
+}
+
+static size_t prefix_product_batch_workspace_bytes(size_t n, size_t batch) {
+  size_t total = 256, m = n;
+  while (m > POLY_CH) { m = chunks_of(m); total += ((batch * m * 32 + 255) / 256) * 256; }
+  return total;
+}
+
+// exclusive prefix products of `batch` dense arrays of n elements each, in place: out[b][0] = 1
+static int prefix_product_batch(uint32_t* d_v, size_t n, uint32_t batch, char* ws, hipStream_t stream) {
+  uint32_t* level[16];
+  size_t level_n[16];
+  int levels = 1;
+  level[0] = d_v;
+  level_n[0] = n;
+  while (level_n[levels - 1] > POLY_CH) {                      // up: the chunk products of every level
+    const size_t cn = level_n[levels - 1], m = chunks_of(cn);
+    level[levels] = (uint32_t*)ws;
+    level_n[levels] = m;
+    ws += (((size_t)batch * m * 32 + 255) / 256) * 256;
+    hipLaunchKernelGGL(k_prod_agg_batch, dim3((unsigned)((m + 255) / 256), batch), dim3(256), 0, stream, (const uint32_t*)level[levels - 1], cn, level[levels], m);
+    levels++;
+  }
+  for (int l = levels - 1; l >= 0; l--) {                      // down: every level in place, with the scanned level above as carries
+    const size_t cn = level_n[l], m = chunks_of(cn);
+    hipLaunchKernelGGL(k_prod_apply_batch, dim3((unsigned)((m + 255) / 256), batch), dim3(256), 0, stream, (const uint32_t*)level[l], cn,
+                       l + 1 < levels ? (const uint32_t*)level[l + 1] : (const uint32_t*)nullptr, m, level[l]);
+  }
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
+}
+
+size_t lookup_products_workspace_bytes(uint32_t n_lookups, uint32_t log_n) {
+  const size_t n = (size_t)1 << log_n;
+  return (((size_t)n_lookups * 16 + 255) / 256) * 256 + prefix_product_batch_workspace_bytes(n, n_lookups) + poly_workspace_bytes((size_t)n_lookups * n);
+}
+
+int fr_lookup_products_device(const void* const* d_inputs_host, const void* const* d_tables_host, const uint32_t* d_permuted_inputs, const uint32_t* d_permuted_tables,
+                              uint32_t n_lookups, uint32_t log_n, size_t usable, const uint32_t beta[8], const uint32_t gamma[8], uint32_t* d_z, void* ws,
+                              size_t ws_bytes, hipStream_t stream, arg_ring* ring) {
+  if (n_lookups == 0) return ZKHIP_OK;
+  const size_t n = (size_t)1 << log_n;
+  if (n_lookups > 65535) { set_error("lookup_products: more than 65535 lookups"); return ZKHIP_EINVAL; }
+  if (ws_bytes < lookup_products_workspace_bytes(n_lookups, log_n)) { set_error("lookup_products: workspace too small"); return ZKHIP_EINVAL; }
+  char* p = (char*)ws;
+  const uint32_t** d_ptrs = (const uint32_t**)p;                  // [inputs ..., tables ...]
+  p += (((size_t)n_lookups * 16 + 255) / 256) * 256;
+  const size_t rest = ws_bytes - (size_t)(p - (char*)ws);
+  int rc = upload_args(ring, d_ptrs, d_inputs_host, (size_t)n_lookups * 8, stream);
+  if (rc == ZKHIP_OK) rc = upload_args(ring, d_ptrs + n_lookups, d_tables_host, (size_t)n_lookups * 8, stream);
+  if (rc != ZKHIP_OK) return rc;
+  fe_arg b, g;
+  memcpy(b.w, beta, 32); memcpy(g.w, gamma, 32);
+  const dim3 grid((unsigned)((n + 255) / 256), n_lookups);
+  hipLaunchKernelGGL(k_lookup_den, grid, dim3(256), 0, stream, d_permuted_inputs, d_permuted_tables, n, usable, b, g, d_z);
+  HIPCHK(hipGetLastError());
+  rc = fr_batch_invert_device(d_z, (size_t)n_lookups * n, p, rest, stream);
+  if (rc != ZKHIP_OK) return rc;
+  if (usable) hipLaunchKernelGGL(k_lookup_num_mul, dim3((unsigned)((usable + 255) / 256), n_lookups), dim3(256), 0, stream, (const uint32_t* const*)d_ptrs, n_lookups, n,
+                                 usable, b, g, d_z);
+  HIPCHK(hipGetLastError());
+  return prefix_product_batch(d_z, n, n_lookups, p, stream);
 }
 
 // ---- linear combination of many columns: out[i] = sum_j c_j col_j[i] -------------------------------------------------------------------

@@ -156,6 +156,10 @@ size_t perm_workspace_bytes(uint32_t nperm, uint32_t chunk, uint32_t log_n);
 int fr_permutation_products_device(const void* const* d_values_host, const void* const* d_sigmas_host, uint32_t nperm, uint32_t chunk, uint32_t log_n,
                                    size_t usable, const uint32_t beta[8], const uint32_t gamma[8], const uint32_t delta[8], const uint32_t omega[8],
                                    uint32_t* d_z, void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
+size_t lookup_products_workspace_bytes(uint32_t n_lookups, uint32_t log_n);
+int fr_lookup_products_device(const void* const* d_inputs_host, const void* const* d_tables_host, const uint32_t* d_permuted_inputs, const uint32_t* d_permuted_tables,
+                              uint32_t n_lookups, uint32_t log_n, size_t usable, const uint32_t beta[8], const uint32_t gamma[8], uint32_t* d_z, void* ws,
+                              size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
 
 // rowvm.hip
 int row_vm_validate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, int accumulate);
@@ -198,6 +202,10 @@ int fr_gather_mul_device(const uint32_t* d_a, uint32_t a_len, const uint32_t* d_
 size_t lookup_permute_workspace_bytes(size_t usable_rows);
 int lookup_permute_device(const uint32_t* d_input, const uint32_t* d_table, size_t usable_rows, uint32_t* d_out_input, uint32_t* d_out_table,
                           void* ws, size_t ws_bytes, hipStream_t stream);
+// every lookup of a circuit at once: n_lookups device addresses each in host memory; outputs [n_lookups][n] dense, rows < usable_rows written
+size_t lookup_permute_many_workspace_bytes(uint32_t n_lookups, size_t usable_rows);
+int lookup_permute_many_device(const void* const* d_inputs_host, const void* const* d_tables_host, uint32_t n_lookups, size_t n, size_t usable_rows,
+                               uint32_t* d_out_input, uint32_t* d_out_table, void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
 
 // serde.hip
 int g1_compress_device(const uint32_t* d_points, size_t n, uint32_t* d_out, int layout, hipStream_t stream);

@@ -637,6 +637,67 @@ def permute_expression_pair(input_expression: np.ndarray, table_expression: np.n
     return pa, ps
 
 
+# A single lookup over this many usable rows or more goes to zkhip_lookup_permute_device (the same bytes): measured at k = 22 the many-lookup
+# call's search per row loses to the single call's two radix sorts.
+SINGLE_LOOKUP_ROWS = 1 << 20
+
+
+def _lookup_column_addresses(inputs, tables, rows: int):
+    import ctypes as C
+
+    if len(inputs) != len(tables):
+        raise ValueError("as many tables as inputs")
+    for c in list(inputs) + list(tables):
+        if not c.is_cuda or not c.is_contiguous() or c.numel() < 4 * rows:
+            raise ValueError("lookup columns are contiguous device tensors of at least usable_rows elements")
+    count = len(inputs)
+    return (C.c_void_p * count)(*[c.data_ptr() for c in inputs]), (C.c_void_p * count)(*[c.data_ptr() for c in tables])
+
+
+def permute_expression_pairs_device(inputs, tables, usable_rows: int, log_n: int, permuted_inputs=None, permuted_tables=None, stream=None):
+    """`permute_expression_pair` of every lookup of a circuit in ONE call (zkhip_lookup_permute_many_device).  inputs[l] / tables[l]: the
+    compressed input / table expression of lookup l, (rows, 4) int64 device tensors; the same tensor given as the table of several lookups
+    is sorted once.  Returns (permuted_inputs, permuted_tables), each (lookups, 2^log_n, 4) int64: rows < usable_rows of every column are
+    written, the rows behind them (the blinding rows) are left as they are -- pass the tensors in to keep what they hold.  Raises ZkhipError
+    when an input value is missing from its table; the message names the lowest such lookup."""
+    import torch
+
+    n, count = 1 << log_n, len(inputs)
+    iptr, tptr = _lookup_column_addresses(inputs, tables, usable_rows)
+    dev = inputs[0].device if count else None
+    if permuted_inputs is None:
+        permuted_inputs = torch.zeros((count, n, 4), dtype=torch.int64, device=dev)
+    if permuted_tables is None:
+        permuted_tables = torch.zeros((count, n, 4), dtype=torch.int64, device=dev)
+    for o in (permuted_inputs, permuted_tables):
+        if not o.is_contiguous() or o.numel() < count * n * 4:
+            raise ValueError("the permuted columns are dense (lookups, 2^log_n, 4) tensors")
+    if count == 1 and usable_rows >= SINGLE_LOOKUP_ROWS:                # one lookup over 2^20 rows or more: two sorts beat a 20-step search per row
+        _lib.check(_lib.load().zkhip_lookup_permute_device(iptr[0], tptr[0], usable_rows, permuted_inputs.data_ptr(), permuted_tables.data_ptr(), stream))
+        return permuted_inputs, permuted_tables
+    _lib.check(_lib.load().zkhip_lookup_permute_many_device(iptr, tptr, count, log_n, usable_rows, permuted_inputs.data_ptr(), permuted_tables.data_ptr(), stream))
+    return permuted_inputs, permuted_tables
+
+
+def lookup_products_device(inputs, tables, permuted_inputs, permuted_tables, usable_rows: int, log_n: int, beta: int, gamma: int, z=None, stream=None):
+    """`lookup::prover::commit_product` of every lookup in ONE call (zkhip_lookup_products_device): z (lookups, 2^log_n, 4) with z[l][0] = 1,
+    z[l][i + 1] = z[l][i] (a + beta)(s + gamma) / ((a' + beta)(s' + gamma)) over the usable rows; the rows after usable_rows repeat
+    z[l][usable_rows] (the caller writes its blinding scalars there)."""
+    import torch
+
+    n, count = 1 << log_n, len(inputs)
+    iptr, tptr = _lookup_column_addresses(inputs, tables, usable_rows)
+    if z is None:
+        z = torch.empty((count, n, 4), dtype=torch.int64, device=permuted_inputs.device)
+    for o in (permuted_inputs, permuted_tables, z):
+        if not o.is_contiguous() or o.numel() < count * n * 4:
+            raise ValueError("the permuted columns and z are dense (lookups, 2^log_n, 4) tensors")
+    b, g = F.fr_encode([beta])[0], F.fr_encode([gamma])[0]
+    _lib.check(_lib.load().zkhip_lookup_products_device(iptr, tptr, permuted_inputs.data_ptr(), permuted_tables.data_ptr(), count, log_n, usable_rows,
+                                                        b.ctypes.data, g.ctypes.data, z.data_ptr(), stream))
+    return z
+
+
 # ---------------------------------------------------------------------------------------------------
 # the row programs of one proof, written out for a host that is not Python (rust-shim/prover_patch.rs, tests/cpp/prover_sequence.c)
 # ---------------------------------------------------------------------------------------------------

@@ -506,6 +506,67 @@ def test_permutation_products_reject_bad_arguments(lib):
     assert lib.zkhip_permutation_products(ptrs, ptrs, 0, 2, 2, 3, *args, None) == 0                    # no columns: nothing to do
 
 
+def _pinned_fr(values):
+    """(len(values), 4) uint64 view of page-locked host memory holding the encoded values (and the tensor that owns it)"""
+    import torch
+
+    t = torch.empty((len(values), 4), dtype=torch.int64, pin_memory=True)
+    a = t.numpy().view(np.uint64)
+    a[:] = enc(values)
+    return a, t
+
+
+def test_permutation_products_null_last_column_then_a_correct_call(lib):
+    """a null column -- the last one, behind columns an upload could already have started on -- is refused with nothing enqueued, and a correct
+    call from the same thread right after it (same lane, pinned inputs) is bit-exact"""
+    k, nperm, chunk = 6, 3, 2
+    rng = random.Random(77)
+    n, usable = 1 << k, (1 << k) - 6
+    beta, gamma = rng.randrange(R), rng.randrange(R)
+    vals = [[rng.randrange(R) for _ in range(n)] for _ in range(nperm)]
+    sig = [[rng.randrange(R) for _ in range(n)] for _ in range(nperm)]
+    V, S = [_pinned_fr(c) for c in vals], [_pinned_fr(c) for c in sig]
+    consts = [F.fr_encode([x])[0] for x in (beta, gamma, O.FR_DELTA, O.omega_for(k))]
+    args = [c.ctypes.data for c in consts]
+    nsets = -(-nperm // chunk)
+    z = np.zeros((nsets * n, 4), dtype=np.uint64)
+    vp = (C.c_void_p * nperm)(*[a.ctypes.data for a, _ in V])
+    sp = (C.c_void_p * nperm)(*[a.ctypes.data for a, _ in S])
+    sp_null = (C.c_void_p * nperm)(*([a.ctypes.data for a, _ in S[:-1]] + [None]))
+    assert lib.zkhip_permutation_products(vp, sp_null, nperm, chunk, k, usable, *args, z.ctypes.data) == -1
+    assert lib.zkhip_last_error().decode() == f"permutation_products: column {nperm - 1} is null"
+    assert not z.any()
+    _lib.check(lib.zkhip_permutation_products(vp, sp, nperm, chunk, k, usable, *args, z.ctypes.data))
+    exp = _permutation_products_expected(vals, sig, chunk, k, usable, beta, gamma)
+    got = F.fr_decode(z)
+    for s in range(nsets):
+        assert got[s * n:(s + 1) * n] == exp[s], f"set {s}"
+
+
+def test_eval_rows_null_last_column_then_a_correct_call(lib):
+    """zkhip_fr_eval_rows checks every column before its first copy: a null LAST column is ZKHIP_EINVAL with the message it always had and nothing
+    enqueued (the output is untouched), and a correct call from the same thread right after it (pinned inputs) equals the oracle"""
+    log_rows, n_cols = 10, 3
+    rows = 1 << log_rows
+    rng = random.Random(78)
+    cols = [[rng.randrange(R) for _ in range(rows)] for _ in range(n_cols)]
+    p = E.RowProgram()
+    p.emit(E.OP_MAD, 0, p.column(0, 1), p.column(1, -1), p.column(2, 0))
+    p.emit(E.OP_ADD, 1, E.RowProgram.reg(0), p.constant(R - 1))
+    p.result_reg = 1
+    P = [_pinned_fr(c) for c in cols]
+    out, _keep = _pinned_fr([0] * rows)
+    prog, keep = p._marshal()
+    ptrs = (C.c_void_p * n_cols)(*[a.ctypes.data for a, _ in P])
+    ptrs_null = (C.c_void_p * n_cols)(*([a.ctypes.data for a, _ in P[:-1]] + [None]))
+    assert lib.zkhip_fr_eval_rows(C.byref(prog), ptrs_null, n_cols, log_rows, 0, out.ctypes.data) == -1
+    assert lib.zkhip_last_error().decode() == f"eval_rows: column {n_cols - 1} is null"
+    assert not out.any()
+    _lib.check(lib.zkhip_fr_eval_rows(C.byref(prog), ptrs, n_cols, log_rows, 0, out.ctypes.data))
+    del keep
+    assert F.fr_decode(out) == oracle_run(p, cols, log_rows)
+
+
 @pytest.mark.parametrize("log_n,count", [(0, 1), (3, 2), (7, 33), (9, 70), (10, 1), (6, 0), (5, 2100)])
 def test_linear_combination_of_many_columns(lib, log_n, count):
     """zkhip_fr_linear_combination_device == sum_j c_j col_j with big integers (one group, several groups, an odd column left over, more than

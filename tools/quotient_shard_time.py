@@ -16,7 +16,9 @@ process.  Prints
   (g) the closed-form Lagrange kernel (zkhip_lagrange_cosets_row_shards_device) against the ifft + coeff_to_extended of the three
       indicator columns it replaces, at ext_k = 24.
 `quotient_shard_time.py` (everything) | `quotient_shard_time.py windows` (only (c), the executor the environment selects) |
-`quotient_shard_time.py rowshards` (only (f) and (g)) | `quotient_shard_time.py keygen` (keygen_device at k = 22 with and without row_shards)."""
+`quotient_shard_time.py rowshards` (only (f) and (g)) | `quotient_shard_time.py keygen` (keygen_device at k = 22 with and without row_shards) |
+`quotient_shard_time.py contexts 1 2 8` (the sharded quotient with both key forms and the row-shard scatter / gather on that many contexts of
+one card, one line per count: wall time, for comparing two builds of the library, not a speed claim)."""
 import ctypes as C
 import os
 import random
@@ -333,8 +335,41 @@ def keygen_timing():
     print(f"keygen_device k={k} (6 fixed + 7 sigma columns), warm: default {res[False]:.1f} ms, row_shards {res[True]:.1f} ms (one device)", flush=True)
 
 
+def contexts_timing(counts):
+    k, ek = 22, 24
+    prog = E.evaluate_h_program(cs, k, ek, *CH)
+    lo, hi = prog.halos(ek)
+    dom = Z.EvaluationDomain(4, k)
+    torch.manual_seed(3)
+    cols = [rand(1 << (ek if f == E.COL_EXTENDED else k)) for f in FORMS]
+    key_idx = [i for i, f in enumerate(FORMS) if f == E.COL_EXTENDED]
+    extended_cols = [(c.data_ptr(), f) for c, f in zip(cols, FORMS)]
+    out = torch.zeros((1 << ek, 4), dtype=torch.int64, device="cuda")
+    back = torch.zeros_like(out)
+    for S in counts:
+        init(S)
+        rs = E.RowShards(ek, len(key_idx), lo, hi)
+
+        def scatter():
+            for c, i in enumerate(key_idx):
+                rs.scatter_device(c, cols[i].data_ptr())
+
+        ts = timed(scatter)
+        tg = timed(lambda: rs.gather_device(0, back.data_ptr()))
+        assert torch.equal(back, cols[key_idx[0]]), S
+        rs_cols = [(rs.ref(key_idx.index(i)), E.COL_ROW_SHARDS) if i in key_idx else (cols[i].data_ptr(), E.COL_COEFF) for i in range(qc.total)]
+        te = timed(lambda: E.evaluate_rows_sharded_device(prog, extended_cols, k, ek, dom, out.data_ptr()))
+        tr = timed(lambda: E.evaluate_rows_sharded_device(prog, rs_cols, k, ek, dom, out.data_ptr()))
+        rs.destroy()
+        print(f"contexts S = {S}: quotient EXTENDED key {te:8.3f} ms, row-shard key {tr:8.3f} ms, scatter of {len(key_idx)} columns {ts:8.3f} ms, "
+              f"gather of one {tg:8.3f} ms", flush=True)
+    init(1)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["windows"]:
+    if sys.argv[1:2] == ["contexts"]:
+        contexts_timing([int(a) for a in sys.argv[2:]] or [1, 2, 8])
+    elif sys.argv[1:] == ["windows"]:
         prog = E.evaluate_h_program(cs, 22, 24, *CH)
         tw, tn = whole_vs_windows(prog, 24)
         print(f"(c) compiled     : whole-domain 2^24 {tw:8.3f} ms   8 windows of 2^21 in sequence {tn:8.3f} ms   ratio {tn / tw:.4f}")

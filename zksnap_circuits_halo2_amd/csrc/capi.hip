@@ -98,8 +98,6 @@ struct prof_hold {
   ~prof_hold() { g_prof_hold = false; }
 };
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s failed: %s", #x, hipGetErrorString(e_)); return ZKHIP_EHIP; } } while (0)
-
 // roctx ranges, one per C-ABI call, so that `rocprofv3 --marker-trace --kernel-trace` attributes kernels to entry points (the tracing
 // counterpart of the reference's per-phase `start_timer!` lines).  OPT-IN: the ranges are live when a marker library is
 // ALREADY loaded in the process (a profiler brought it: found with RTLD_NOLOAD, nothing is loaded on the library's own initiative) or when
@@ -230,9 +228,9 @@ struct device_ctx {
   hipStream_t side = nullptr;          // primary: second stream of a batch of large MSMs (high priority: never the caller's hardware queue)
   hipEvent_t side_fork = nullptr, side_join = nullptr;
   worker* w = nullptr;                 // secondary devices only
-  // device-resident sharded commits (zkhip_msm_g1_registered_device over several shards): a secondary device runs its shards on `fan`, a
-  // stream of its own (not the lane its worker thread drives for host-buffer calls), behind `fan_ready` of the primary device (recorded on
-  // the caller's stream: the scalars are complete) and records `fan_done` for the caller's stream to wait on before the fold
+  // multi-device `_device` calls (fan_call below, their only user): a secondary device runs its share on `fan`, a stream of its own (not the
+  // lane its worker thread drives for host-buffer calls), behind `fan_ready` of the primary device (recorded on the caller's stream: the
+  // inputs are complete) and records `fan_done` for the caller's stream to wait on
   hipStream_t fan = nullptr;
   hipEvent_t fan_ready = nullptr, fan_done = nullptr;
   // the sharded quotient numerator (zkhip_fr_eval_rows_sharded_device): the extended cosets of the COEFF columns this device owns, its window
@@ -342,13 +340,18 @@ static scratch* scratch_for(device_ctx& d, hipStream_t stream) {
 static inline hipStream_t caller_stream(void* stream) { return (hipStream_t)stream; }
 
 // ---- lanes -----------------------------------------------------------------------------------------------------------
-// RAII: borrows a free lane of the primary device (waits for one), resolves its scratch set.  Construct WITHOUT holding g_mu.
+// RAII: one user's turn on a lane, with the lane's stream and scratch set resolved.  Construct WITHOUT holding g_mu.
+// The rule for work on a lane: a call gives the lane up with nothing of its own still queued.  A call that succeeds ends in
+// finish(), its one wait for the stream.  A hold that goes away without it -- any error return after the first enqueue -- waits in its destructor for
+// the lane's stream and copy stream first: the caller's buffers may be pinned memory that an upload is still reading, and the lane's scratch goes to
+// the next user.
 struct lane_hold {
   lane* L = nullptr;
   scratch* sc = nullptr;
   hipStream_t s = nullptr;
   int rc = ZKHIP_OK;
-  lane_hold() {
+  bool borrowed = false, clean = false;
+  lane_hold() {                        // borrows a free lane of the primary device (waits for one)
     std::unique_lock<std::recursive_mutex> lk(g_mu);
     rc = ensure_init();
     if (rc != ZKHIP_OK) return;
@@ -358,12 +361,28 @@ struct lane_hold {
       g_lane_cv.wait(lk);
       if (!g_ctx.ready) { rc = ZKHIP_ENODEV; set_error("library shut down while a call was waiting"); return; }
     }
-    L->busy = true;
+    L->busy = borrowed = true;
     s = L->stream;
     sc = scratch_for(primary(), s);
   }
+  explicit lane_hold(device_ctx& D) : L(&D.lanes[0]), s(D.lanes[0].stream) {   // the one lane of a secondary device (its users take turns under g_fanout_mu)
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    sc = scratch_for(D, s);
+  }
+  int finish() {
+    HIPCHK(hipStreamSynchronize(s));
+    clean = true;
+    return ZKHIP_OK;
+  }
+  void reopen() { clean = false; }     // a call of several rounds (chunks, vectors of a batch) enqueues again after a finish()
   ~lane_hold() {
     if (!L) return;
+    if (!clean) {
+      (void)hipStreamSynchronize(s);
+      if (L->copy) (void)hipStreamSynchronize(L->copy);
+      (void)hipGetLastError();
+    }
+    if (!borrowed) return;
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     L->busy = false;
     g_lane_cv.notify_one();
@@ -486,58 +505,53 @@ static inline size_t window_start(uint64_t row0, uint64_t halo_lo, size_t N) {
   return (size_t)((((int64_t)row0 - (int64_t)halo_lo) % (int64_t)N + (int64_t)N) % (int64_t)N);
 }
 
-// One multi-device `_device` call over a set (g_fanout_mu and g_mu held): st[j] is the caller's stream on the primary and device j's fan
-// stream elsewhere; every secondary starts behind an entry event on the caller's stream, and `end` makes the caller's stream wait for them.
-// On an error after something was enqueued the destructor waits for those streams, so that nothing outlives the call's buffers.
+// One multi-device `_device` call (g_mu held by the caller): `begin` records the entry event on the caller's stream s; dev(j) makes device j current and, the first time, gives it its stream st[j] -- s on the primary, elsewhere the device's fan
+// stream behind the entry event (a device the call never names gets no work); `end` makes s wait for every secondary that was named.
+// The rule for work on these streams is the lanes' (DESIGN.md section 8): a call that does not reach `end` -- any error return after `begin` -- waits
+// in the destructor for every stream it named, so that nothing of it outlives the call's buffers.
 struct fan_call {
-  std::vector<hipStream_t> st;
-  std::vector<bool> used;
+  std::vector<hipStream_t> st;         // st[j] is null until dev(j)
+  hipStream_t s = nullptr;
   bool armed = true;
-  int begin(hipStream_t s) {
-    const int S = (int)g_ctx.devs.size();
-    st.assign((size_t)S, nullptr);
-    used.assign((size_t)S, false);
-    st[0] = s;
-    if (S == 1) return ZKHIP_OK;
+  int begin(hipStream_t caller) {
+    s = caller;
+    st.assign(g_ctx.devs.size(), nullptr);
+    if (st.size() == 1) return ZKHIP_OK;
     device_ctx& P = primary();
     if (!P.fan_ready) HIPCHK(hipEventCreateWithFlags(&P.fan_ready, hipEventDisableTiming));
     HIPCHK(hipEventRecord(P.fan_ready, s));
-    for (int j = 1; j < S; j++) {
-      device_ctx* D = g_ctx.devs[(size_t)j];
-      if (hipSetDevice(D->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", D->device); return ZKHIP_ENODEV; }
-      if (!D->fan) {
-        HIPCHK(hipStreamCreateWithFlags(&D->fan, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&D->fan_done, hipEventDisableTiming));
-      }
-      st[(size_t)j] = D->fan;
-      HIPCHK(hipStreamWaitEvent(D->fan, P.fan_ready, 0));
-    }
-    (void)hipSetDevice(P.device);
     return ZKHIP_OK;
   }
   int dev(int j) {
-    used[(size_t)j] = true;
-    if (hipSetDevice(g_ctx.devs[(size_t)j]->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", g_ctx.devs[(size_t)j]->device); return ZKHIP_ENODEV; }
+    device_ctx* D = g_ctx.devs[(size_t)j];
+    if (hipSetDevice(D->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", D->device); return ZKHIP_ENODEV; }
+    if (st[(size_t)j]) return ZKHIP_OK;
+    if (j == 0) { st[0] = s; return ZKHIP_OK; }
+    if (!D->fan) {
+      HIPCHK(hipStreamCreateWithFlags(&D->fan, hipStreamNonBlocking));
+      HIPCHK(hipEventCreateWithFlags(&D->fan_done, hipEventDisableTiming));
+    }
+    st[(size_t)j] = D->fan;
+    HIPCHK(hipStreamWaitEvent(D->fan, primary().fan_ready, 0));
     return ZKHIP_OK;
   }
   int end() {
-    const int S = (int)st.size();
-    for (int j = 1; j < S; j++) {
-      if (!used[(size_t)j]) continue;
-      device_ctx* D = g_ctx.devs[(size_t)j];
+    for (size_t j = 1; j < st.size(); j++) {
+      if (!st[j]) continue;
+      device_ctx* D = g_ctx.devs[j];
       if (hipSetDevice(D->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", D->device); return ZKHIP_ENODEV; }
       HIPCHK(hipEventRecord(D->fan_done, D->fan));
     }
     if (hipSetDevice(primary().device) != hipSuccess) { set_error("hipSetDevice(%d) failed", primary().device); return ZKHIP_ENODEV; }
-    for (int j = 1; j < S; j++)
-      if (used[(size_t)j]) HIPCHK(hipStreamWaitEvent(st[0], g_ctx.devs[(size_t)j]->fan_done, 0));
+    for (size_t j = 1; j < st.size(); j++)
+      if (st[j]) HIPCHK(hipStreamWaitEvent(s, g_ctx.devs[j]->fan_done, 0));
     armed = false;
     return ZKHIP_OK;
   }
   ~fan_call() {
     if (!armed) return;
     for (size_t j = 0; j < st.size(); j++)
-      if (used[j]) { (void)hipSetDevice(g_ctx.devs[j]->device); (void)hipStreamSynchronize(st[j]); }
+      if (st[j]) { (void)hipSetDevice(g_ctx.devs[j]->device); (void)hipStreamSynchronize(st[j]); }
     if (!g_ctx.devs.empty()) (void)hipSetDevice(primary().device);
     (void)hipGetLastError();
   }
@@ -699,9 +713,8 @@ int zkhip_msm_g1_device(const void* d_scalars, const void* d_bases, size_t n, vo
 
 namespace zkhip {
 
-// One shard's share of a host-buffer MSM on device `d` (current device = d.device, stream / scratch of its lane 0 or the borrowed
-// lane): uploads the scalar slice (and the base slice when there is no prepared table), runs the MSM, leaves the 96-byte partial at
-// d_partial (memory of device d).
+// One shard's share of a host-buffer MSM on the held lane U (its device is the current one): uploads the scalar slice (and the base slice
+// when there is no prepared table), runs the MSM, leaves the 96-byte partial at d_partial (memory of that device).
 // Chunked upload (round 4).  A host-buffer MSM used to upload all its scalars with one copy and only then start its first kernel (2^22 points:
 // 2.4 ms of PCIe + 4.9 ms of kernels, nothing overlapped).  With a prepared table of wide windows and at least two pieces of 2^20 scalars the
 // upload is cut into J even pieces on the lane's copy stream; piece j is sorted and accumulated into the shared bucket set (msm.hip:
@@ -714,21 +727,18 @@ static size_t msm_stream_pieces(size_t n, const prepared_bases* pb) {
   return J < 2 ? 1 : std::min<size_t>(J, (size_t)STREAM_PIECES_MAX);
 }
 
-static int msm_shard_enqueue_chunked(lane* L, scratch* sc, hipStream_t s, const uint64_t* scalars, size_t n, const prepared_bases* pb, size_t pb_off,
-                                     uint32_t* d_partial, size_t J, size_t region) {
+static int msm_shard_enqueue_chunked(lane_hold& U, const uint64_t* scalars, size_t n, const prepared_bases* pb, size_t pb_off, uint32_t* d_partial, size_t J,
+                                     size_t region) {
   int rc;
+  lane* const L = U.L;
+  scratch* const sc = U.sc;
+  hipStream_t s = U.s;
   if (!L->copy) HIPCHK(hipStreamCreateWithFlags(&L->copy, hipStreamNonBlocking));
   const size_t cap = (n + J - 1) / J;
   const size_t ws_bytes = msm_chunk_workspace_bytes(cap, pb->c);
   if ((rc = sc->scalars.reserve((region + n) * 32)) != ZKHIP_OK) return rc;      // (a no-op inside a fan-out: reserve_for_pieces sized the buffer for all pieces)
   if ((rc = sc->ws.reserve(ws_bytes)) != ZKHIP_OK) return rc;
-  // (round 4 advice) every non-OK exit below waits for the copy stream and for `s`: the caller's scalars may be pinned host memory, in which case an
-  // earlier piece could still be crossing PCIe from the caller's buffer into the lane's after this call has returned its error and released the lane
-  struct drain_t {
-    hipStream_t a, b;
-    bool armed = true;
-    ~drain_t() { if (armed) { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } }
-  } drain{L->copy, s};
+  // (a non-OK exit below leaves pieces crossing PCIe from the caller's buffer on the copy stream: the hold waits for that stream too)
   // Every piece of a call has its own region of the lane's scalar buffer (`region`, in scalars), so the copy stream may run ahead of the kernels:
   // while shard k is being accumulated on `s`, the pieces of shard k + 1 are already crossing PCIe (virtual shards on one lane).  A call ends with
   // hipStreamSynchronize(s), and `s` waits for every copy it used, so nothing of an earlier call is in flight here.
@@ -743,21 +753,19 @@ static int msm_shard_enqueue_chunked(lane* L, scratch* sc, hipStream_t s, const 
     if ((rc = msm_chunk_add((const uint32_t*)(dst + lo * 32), len, pb, pb_off + lo, cap, j == 0, sc->ws.p, sc->ws.cap, s)) != ZKHIP_OK) return rc;
     lo += len;
   }
-  if ((rc = msm_chunk_finish(pb, cap, d_partial, sc->ws.p, sc->ws.cap, s)) != ZKHIP_OK) return rc;
-  drain.armed = false;
-  return ZKHIP_OK;
+  return msm_chunk_finish(pb, cap, d_partial, sc->ws.p, sc->ws.cap, s);
 }
 
 // region: offset (in scalars) of this piece inside the lane's scalar buffer -- the pieces one lane runs back to back (virtual shards) do not share
 // upload space, so one piece's upload never waits for the previous piece's kernels
-static int msm_shard_enqueue(scratch* sc, hipStream_t s, const uint64_t* scalars, const uint64_t* bases, size_t n, const prepared_bases* pb,
-                             size_t pb_off, uint32_t* d_partial, lane* L = nullptr, size_t region = 0) {
+static int msm_shard_enqueue(lane_hold& U, const uint64_t* scalars, const uint64_t* bases, size_t n, const prepared_bases* pb, size_t pb_off, uint32_t* d_partial,
+                             size_t region = 0) {
   int rc;
+  scratch* const sc = U.sc;
+  hipStream_t s = U.s;
   if (n == 0) return msm_g1_device(nullptr, nullptr, 0, d_partial, nullptr, 0, 0, s);
-  if (L) {
-    const size_t J = msm_stream_pieces(n, pb);
-    if (J > 1) return msm_shard_enqueue_chunked(L, sc, s, scalars, n, pb, pb_off, d_partial, J, region);
-  }
+  const size_t J = msm_stream_pieces(n, pb);
+  if (J > 1) return msm_shard_enqueue_chunked(U, scalars, n, pb, pb_off, d_partial, J, region);
   if ((rc = sc->scalars.reserve((region + n) * 32)) != ZKHIP_OK) return rc;
   char* const d_sc = (char*)sc->scalars.p + region * 32;
   HIPCHK(hipMemcpyAsync(d_sc, scalars, n * 32, hipMemcpyHostToDevice, s));
@@ -799,6 +807,7 @@ static int reserve_for_pieces(scratch* sc, const std::vector<piece_t>& pieces, c
 static int host_msm(lane_hold& H, const uint64_t* scalars, const uint64_t* bases, size_t n, const std::shared_ptr<registered_t>& reg, size_t off,
                     uint64_t* out_xyz) {
   int rc;
+  H.reopen();                                           // (zkhip_msm_g1_batch runs its vectors through here one after the other)
   std::vector<piece_t> pieces;
   if (reg) {
     for (auto& sh : reg->shards) {
@@ -819,7 +828,7 @@ static int host_msm(lane_hold& H, const uint64_t* scalars, const uint64_t* bases
   if ((rc = sc->small.reserve(4096)) != ZKHIP_OK) return rc;
   if (pieces.size() == 1 && pieces[0].dev == 0) {
     const piece_t& p = pieces[0];
-    if ((rc = msm_shard_enqueue(sc, s, scalars + p.lo * 4, bases + p.lo * 8, p.n, p.pb, p.pb_off, (uint32_t*)sc->small.p, H.L)) != ZKHIP_OK) return rc;
+    if ((rc = msm_shard_enqueue(H, scalars + p.lo * 4, bases + p.lo * 8, p.n, p.pb, p.pb_off, (uint32_t*)sc->small.p)) != ZKHIP_OK) return rc;
   } else {
     // fan out: the primary device's pieces run on this thread's lane, one after another (virtual shards) -- the other devices'
     // pieces on their worker threads, each device over its own PCIe link
@@ -840,9 +849,8 @@ static int host_msm(lane_hold& H, const uint64_t* scalars, const uint64_t* bases
       const std::vector<size_t> mine = by_dev[d];
       const int primary_dev = P.device;
       D->w->submit([D, mine, &pieces, scalars, bases, gather, primary_dev]() -> int {
-        hipStream_t ds = D->lanes[0].stream;
-        scratch* dsc;
-        { guard_t g(g_mu); dsc = scratch_for(*D, ds); }
+        lane_hold U(*D);                                  // a failed job has drained the lane before wait() hands its error to the caller
+        scratch* dsc = U.sc;
         int r;
         if ((r = dsc->small.reserve(4096 + mine.size() * 96)) != ZKHIP_OK) return r;
         if ((r = reserve_for_pieces(dsc, pieces, mine)) != ZKHIP_OK) return r;
@@ -850,19 +858,18 @@ static int host_msm(lane_hold& H, const uint64_t* scalars, const uint64_t* bases
         for (size_t k = 0; k < mine.size(); k++) {
           const piece_t& p = pieces[mine[k]];
           uint32_t* part = (uint32_t*)((char*)dsc->small.p + 4096 + k * 96);
-          if ((r = msm_shard_enqueue(dsc, ds, scalars + p.lo * 4, bases + p.lo * 8, p.n, p.pb, p.pb_off, part, &D->lanes[0], region)) != ZKHIP_OK) return r;
+          if ((r = msm_shard_enqueue(U, scalars + p.lo * 4, bases + p.lo * 8, p.n, p.pb, p.pb_off, part, region)) != ZKHIP_OK) return r;
           region += p.n;
-          HIPCHK(hipMemcpyPeerAsync(gather + mine[k] * 24, primary_dev, part, D->device, 96, ds));
+          HIPCHK(hipMemcpyPeerAsync(gather + mine[k] * 24, primary_dev, part, D->device, 96, U.s));
         }
-        HIPCHK(hipStreamSynchronize(ds));                 // the partials have landed on the primary device
-        return ZKHIP_OK;
+        return U.finish();                                // the partials have landed on the primary device
       });
     }
     int rc_local = ZKHIP_OK;
     size_t region0 = 0;
     for (size_t i : by_dev[0]) {
       const piece_t& p = pieces[i];
-      if ((rc_local = msm_shard_enqueue(sc, s, scalars + p.lo * 4, bases + p.lo * 8, p.n, p.pb, p.pb_off, gather + i * 24, H.L, region0)) != ZKHIP_OK) break;
+      if ((rc_local = msm_shard_enqueue(H, scalars + p.lo * 4, bases + p.lo * 8, p.n, p.pb, p.pb_off, gather + i * 24, region0)) != ZKHIP_OK) break;
       region0 += p.n;
     }
     int rc_remote = ZKHIP_OK;
@@ -878,7 +885,7 @@ static int host_msm(lane_hold& H, const uint64_t* scalars, const uint64_t* bases
     if ((rc = sum_jacobian_device(gather, (int)pieces.size(), (uint32_t*)sc->small.p, s)) != ZKHIP_OK) return rc;
   }
   HIPCHK(hipMemcpyAsync(H.L->pinned, sc->small.p, 96, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  if ((rc = H.finish()) != ZKHIP_OK) return rc;
   memcpy(out_xyz, H.L->pinned, 96);
   return ZKHIP_OK;
 }
@@ -933,7 +940,7 @@ int zkhip_msm_g1_batch(const uint64_t* scalars, const uint64_t* bases, size_t n,
   }
   if (rc != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(H.L->pinned, sc->small.p, batch * 96, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  if ((rc = H.finish()) != ZKHIP_OK) return rc;
   memcpy(out_xyz, H.L->pinned, batch * 96);
   return ZKHIP_OK;
 }
@@ -970,17 +977,17 @@ int zkhip_register_bases(const uint64_t* bases, size_t n) {
     if (lo >= hi) continue;
     const int di = s % ndev;
     device_ctx* D = g_ctx.devs[(size_t)di];
-    hipStream_t ds = di == 0 ? H.s : D->lanes[0].stream;
-    scratch* dsc;
-    { guard_t g(g_mu); dsc = di == 0 ? H.sc : scratch_for(*D, ds); }
+    std::unique_ptr<lane_hold> far(di == 0 ? nullptr : new lane_hold(*D));   // a secondary's lane for this shard (drained while its device is current)
+    lane_hold& U = di == 0 ? H : *far;
+    U.reopen();
     if (hipSetDevice(D->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", D->device); rc = ZKHIP_ENODEV; break; }
     shard_t sh;
     sh.dev = di; sh.lo = lo; sh.n = hi - lo;
-    if ((rc = dsc->bases.reserve(sh.n * 64)) == ZKHIP_OK) {
-      if (hipMemcpyAsync(dsc->bases.p, bases + lo * 8, sh.n * 64, hipMemcpyHostToDevice, ds) != hipSuccess) { set_error("register_bases: upload failed"); rc = ZKHIP_EHIP; }
-      else rc = prepare_bases_device((const uint32_t*)dsc->bases.p, sh.n, ds, &sh.pb, 0, /* direct table only for arrays that are small as a whole: */ n);
+    if ((rc = U.sc->bases.reserve(sh.n * 64)) == ZKHIP_OK) {
+      if (hipMemcpyAsync(U.sc->bases.p, bases + lo * 8, sh.n * 64, hipMemcpyHostToDevice, U.s) != hipSuccess) { set_error("register_bases: upload failed"); rc = ZKHIP_EHIP; }
+      else rc = prepare_bases_device((const uint32_t*)U.sc->bases.p, sh.n, U.s, &sh.pb, 0, /* direct table only for arrays that are small as a whole: */ n);
     }
-    if (rc == ZKHIP_OK) reg->shards.push_back(sh);
+    if (rc == ZKHIP_OK) { reg->shards.push_back(sh); rc = U.finish(); }   // (the stream is idle: prepare_bases_device has waited for it)
   }
   (void)hipSetDevice(primary().device);
   if (rc != ZKHIP_OK) return rc;                      // ~registered_t frees the shards built so far
@@ -1086,8 +1093,8 @@ static int prepared_batch_enqueue(scratch* sc, hipStream_t s, const prepared_bas
 // its device.  The primary device's pieces run on s.  A secondary device waits for the scalars (event on s), pulls its slice of every
 // vector from the primary's HBM over xGMI (hipMemcpyPeerAsync: 32 B x n / S per vector -- 64 MiB per GPU for configs[4], about a
 // millisecond beside a 2.9 ms shard MSM), runs its pieces on its own stream and sends each 96-byte partial back into the gather buffer of
-// the caller's stream; s waits for the secondaries' events and folds: out[k] = sum over pieces of partial[piece][k].  Asynchronous like
-// every `_device` call: nothing here waits for a device.  g_mu held by the caller.
+// the caller's stream; s waits for the secondaries' events (fan_call) and folds: out[k] = sum over pieces of partial[piece][k].  Asynchronous like
+// every `_device` call: nothing here waits for a device unless the call fails half-way.  g_mu held by the caller.
 static int registered_device_msm(const std::shared_ptr<registered_t>& reg, size_t off, const uint32_t* d_scalars, size_t n, size_t batch, size_t stride,
                                  uint32_t* d_out, hipStream_t s) {
   int rc;
@@ -1103,65 +1110,43 @@ static int registered_device_msm(const std::shared_ptr<registered_t>& reg, size_
   const size_t np = pieces.size();
   if ((rc = sc->gather.reserve(np * batch * 96)) != ZKHIP_OK) return rc;
   uint32_t* gather = (uint32_t*)sc->gather.p;                     // [piece][vector] 96-byte slots
-  bool remote = false;
-  for (auto& p : pieces) remote |= p.dev != 0;
-  if (remote) {
-    if (!P.fan_ready) HIPCHK(hipEventCreateWithFlags(&P.fan_ready, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(P.fan_ready, s));
-  }
+  fan_call F;
+  if ((rc = F.begin(s)) != ZKHIP_OK) return rc;
   // the secondaries first: their copies and kernels start while this thread is still enqueueing the primary's pieces
-  int rc_remote = ZKHIP_OK;
-  std::vector<size_t> waited;
-  for (size_t d = 1; d < g_ctx.devs.size() && rc_remote == ZKHIP_OK; d++) {
+  for (size_t d = 1; d < g_ctx.devs.size(); d++) {
     std::vector<size_t> mine;
     for (size_t i = 0; i < np; i++) if ((size_t)pieces[i].dev == d) mine.push_back(i);
     if (mine.empty()) continue;
     device_ctx* D = g_ctx.devs[d];
-    if (hipSetDevice(D->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", D->device); rc_remote = ZKHIP_ENODEV; break; }
-    auto body = [&]() -> int {
-      if (!D->fan) {
-        HIPCHK(hipStreamCreateWithFlags(&D->fan, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&D->fan_done, hipEventDisableTiming));
-      }
-      scratch* dsc = scratch_for(*D, D->fan);
-      size_t sc_elems = 0;
-      for (size_t i : mine) sc_elems = std::max(sc_elems, pieces[i].n);
-      int r;
-      if ((r = dsc->scalars.reserve(sc_elems * batch * 32)) != ZKHIP_OK) return r;
-      if ((r = dsc->small.reserve(4096 + batch * 96)) != ZKHIP_OK) return r;
-      size_t ws_bytes = 0;                                        // sized once for the largest piece (growing it later would free it under queued work)
-      for (size_t i : mine) ws_bytes = std::max(ws_bytes, msm_workspace_bytes(pieces[i].n, pieces[i].pb->c, true, batch_group(pieces[i].pb, pieces[i].n, batch)));
-      if ((r = dsc->ws.reserve(ws_bytes)) != ZKHIP_OK) return r;
-      HIPCHK(hipStreamWaitEvent(D->fan, P.fan_ready, 0));
-      for (size_t i : mine) {
-        const piece_t& p = pieces[i];
-        uint32_t* slice = (uint32_t*)dsc->scalars.p;              // vector k of this piece at slice + k * p.n * 8 words
-        for (size_t k = 0; k < batch; k++)
-          HIPCHK(hipMemcpyPeerAsync(slice + k * p.n * 8, D->device, d_scalars + (k * stride + p.lo) * 8, P.device, p.n * 32, D->fan));
-        uint32_t* part = (uint32_t*)((char*)dsc->small.p + 4096);
-        if ((r = prepared_batch_enqueue(dsc, D->fan, p.pb, p.pb_off, slice, p.n, batch, p.n, part)) != ZKHIP_OK) return r;
-        HIPCHK(hipMemcpyPeerAsync(gather + i * batch * 24, P.device, part, D->device, batch * 96, D->fan));
-      }
-      return ZKHIP_OK;
-    };
-    rc_remote = body();
-    if (D->fan_done && D->fan) { (void)hipEventRecord(D->fan_done, D->fan); waited.push_back(d); }   // also after an error: s must not run ahead of work already queued
+    if ((rc = F.dev((int)d)) != ZKHIP_OK) return rc;
+    hipStream_t fs = F.st[d];
+    scratch* dsc = scratch_for(*D, fs);
+    size_t sc_elems = 0;
+    for (size_t i : mine) sc_elems = std::max(sc_elems, pieces[i].n);
+    if ((rc = dsc->scalars.reserve(sc_elems * batch * 32)) != ZKHIP_OK) return rc;
+    if ((rc = dsc->small.reserve(4096 + batch * 96)) != ZKHIP_OK) return rc;
+    size_t ws_bytes = 0;                                          // sized once for the largest piece (growing it later would free it under queued work)
+    for (size_t i : mine) ws_bytes = std::max(ws_bytes, msm_workspace_bytes(pieces[i].n, pieces[i].pb->c, true, batch_group(pieces[i].pb, pieces[i].n, batch)));
+    if ((rc = dsc->ws.reserve(ws_bytes)) != ZKHIP_OK) return rc;
+    for (size_t i : mine) {
+      const piece_t& p = pieces[i];
+      uint32_t* slice = (uint32_t*)dsc->scalars.p;                // vector k of this piece at slice + k * p.n * 8 words
+      for (size_t k = 0; k < batch; k++)
+        HIPCHK(hipMemcpyPeerAsync(slice + k * p.n * 8, D->device, d_scalars + (k * stride + p.lo) * 8, P.device, p.n * 32, fs));
+      uint32_t* part = (uint32_t*)((char*)dsc->small.p + 4096);
+      if ((rc = prepared_batch_enqueue(dsc, fs, p.pb, p.pb_off, slice, p.n, batch, p.n, part)) != ZKHIP_OK) return rc;
+      HIPCHK(hipMemcpyPeerAsync(gather + i * batch * 24, P.device, part, D->device, batch * 96, fs));
+    }
   }
-  if (hipSetDevice(P.device) != hipSuccess) { set_error("hipSetDevice(%d) failed", P.device); return ZKHIP_ENODEV; }
-  int rc_local = ZKHIP_OK;
-  {
-    size_t ws_bytes = 0;
-    for (auto& p : pieces) if (p.dev == 0) ws_bytes = std::max(ws_bytes, msm_workspace_bytes(p.n, p.pb->c, true, batch_group(p.pb, p.n, batch)));
-    rc_local = sc->ws.reserve(ws_bytes);
-  }
-  for (size_t i = 0; i < np && rc_local == ZKHIP_OK && rc_remote == ZKHIP_OK; i++) {
+  if ((rc = F.dev(0)) != ZKHIP_OK) return rc;
+  size_t ws_bytes = 0;
+  for (auto& p : pieces) if (p.dev == 0) ws_bytes = std::max(ws_bytes, msm_workspace_bytes(p.n, p.pb->c, true, batch_group(p.pb, p.n, batch)));
+  if ((rc = sc->ws.reserve(ws_bytes)) != ZKHIP_OK) return rc;
+  for (size_t i = 0; i < np; i++) {
     const piece_t& p = pieces[i];
-    if (p.dev != 0) continue;
-    rc_local = prepared_batch_enqueue(sc, s, p.pb, p.pb_off, d_scalars + p.lo * 8, p.n, batch, stride, gather + i * batch * 24);
+    if (p.dev == 0 && (rc = prepared_batch_enqueue(sc, s, p.pb, p.pb_off, d_scalars + p.lo * 8, p.n, batch, stride, gather + i * batch * 24)) != ZKHIP_OK) return rc;
   }
-  for (size_t d : waited) HIPCHK(hipStreamWaitEvent(s, g_ctx.devs[d]->fan_done, 0));
-  if (rc_remote != ZKHIP_OK) return rc_remote;
-  if (rc_local != ZKHIP_OK) return rc_local;
+  if ((rc = F.end()) != ZKHIP_OK) return rc;
   return sum_jacobian_device(gather, (int)np, d_out, s, batch);
 }
 
@@ -1269,7 +1254,7 @@ int zkhip_g1_sum(const uint64_t* points_xyz, int m, uint64_t out_xyz[12]) {
   if (m) HIPCHK(hipMemcpyAsync(d + 4096, points_xyz, (size_t)m * 96, hipMemcpyHostToDevice, H.s));
   if ((rc = sum_jacobian_device((const uint32_t*)(d + 4096), m, (uint32_t*)d, H.s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(H.L->pinned, d, 96, hipMemcpyDeviceToHost, H.s));
-  HIPCHK(hipStreamSynchronize(H.s));
+  if ((rc = H.finish()) != ZKHIP_OK) return rc;
   memcpy(out_xyz, H.L->pinned, 96);
   return ZKHIP_OK;
 }
@@ -1316,9 +1301,9 @@ static int device_transform_one(const void* d_in, uint32_t in_len, size_t in_str
 
 // Round 5 (second split): the polynomials of a batch are independent units, so a batched transform may be spread over the
 // devices of zkhip_init -- every transform still runs on ONE device.  Polynomials [lo_d, hi_d) (shard_range over the batch) go to device d.
-// `_device` form (this function, fan-out mode 2 only): device d > 0 waits for the caller's stream (fan_ready), pulls its polynomials from the
-// primary's HBM over xGMI (hipMemcpyPeerAsync) into its own scratch, transforms them on its `fan` stream with its own twiddle plan, pushes the
-// results back into d_out and records fan_done, which the caller's stream waits for.  Asynchronous like every `_device` call.
+// `_device` form (this function, fan-out mode 2 only; the protocol is fan_call's): device d > 0 waits for the caller's stream, pulls its polynomials
+// from the primary's HBM over xGMI (hipMemcpyPeerAsync) into its own scratch, transforms them on its own stream with its own twiddle plan and pushes
+// the results back into d_out; the caller's stream waits for it.  Asynchronous like every `_device` call.
 // Off by default: a 2^24 result is 512 MiB over one xGMI link (about 8 ms at 65 GB/s) against a 1.8 ms transform, so copying out and back
 // only pays where the links are idle and the batch is deep; the host-buffer forms below (mode 1, default) are the ones that win outright --
 // each device moves its own polynomials over its own PCIe link.  Results are identical either way (one device per transform).
@@ -1330,49 +1315,33 @@ static int device_transform(const void* d_in, uint32_t in_len, size_t in_stride,
     return device_transform_one(d_in, in_len, in_stride, d_out, out_len, out_stride, batch, L, omega, in_scale, in_period, out_scale, out_period, s);
   device_ctx& P = primary();
   const size_t N = (size_t)1 << L;
-  if (!P.fan_ready) HIPCHK(hipEventCreateWithFlags(&P.fan_ready, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(P.fan_ready, s));
-  int rc_remote = ZKHIP_OK;
-  std::vector<int> waited;
-  for (int d = 1; d < S && rc_remote == ZKHIP_OK; d++) {
+  int rc;
+  fan_call F;
+  if ((rc = F.begin(s)) != ZKHIP_OK) return rc;
+  for (int d = 1; d < S; d++) {
     size_t lo, hi;
     shard_range(batch, d, S, &lo, &hi);
     if (lo >= hi) continue;
     device_ctx* D = g_ctx.devs[(size_t)d];
-    if (hipSetDevice(D->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", D->device); rc_remote = ZKHIP_ENODEV; break; }
-    auto body = [&]() -> int {
-      if (!D->fan) {
-        HIPCHK(hipStreamCreateWithFlags(&D->fan, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&D->fan_done, hipEventDisableTiming));
-      }
-      scratch* dsc = scratch_for(*D, D->fan);
-      const size_t cnt = hi - lo;
-      int r;
-      if ((r = dsc->poly.reserve(cnt * N * 32)) != ZKHIP_OK) return r;
-      HIPCHK(hipStreamWaitEvent(D->fan, P.fan_ready, 0));
-      uint32_t* buf = (uint32_t*)dsc->poly.p;                 // polynomial b of this device at buf + b * N elements, transformed in place
-      for (size_t b = 0; b < cnt; b++)
-        HIPCHK(hipMemcpyPeerAsync(buf + b * N * 8, D->device, (const uint32_t*)d_in + (lo + b) * in_stride * 8, P.device, (size_t)in_len * 32, D->fan));
-      if ((r = run_transform(dsc, buf, in_len, (uint32_t)N, buf, out_len, (uint32_t)N, (uint32_t)cnt, L, (const uint32_t*)omega, in_scale, in_period,
-                             out_scale, out_period, D->fan)) != ZKHIP_OK) return r;
-      for (size_t b = 0; b < cnt; b++)
-        HIPCHK(hipMemcpyPeerAsync((uint32_t*)d_out + (lo + b) * out_stride * 8, P.device, buf + b * N * 8, D->device, (size_t)out_len * 32, D->fan));
-      return ZKHIP_OK;
-    };
-    rc_remote = body();
-    if (D->fan_done && D->fan) { (void)hipEventRecord(D->fan_done, D->fan); waited.push_back(d); }   // also after an error: s must not run ahead of work already queued
+    if ((rc = F.dev(d)) != ZKHIP_OK) return rc;
+    hipStream_t fs = F.st[(size_t)d];
+    scratch* dsc = scratch_for(*D, fs);
+    const size_t cnt = hi - lo;
+    if ((rc = dsc->poly.reserve(cnt * N * 32)) != ZKHIP_OK) return rc;
+    uint32_t* buf = (uint32_t*)dsc->poly.p;                   // polynomial b of this device at buf + b * N elements, transformed in place
+    for (size_t b = 0; b < cnt; b++)
+      HIPCHK(hipMemcpyPeerAsync(buf + b * N * 8, D->device, (const uint32_t*)d_in + (lo + b) * in_stride * 8, P.device, (size_t)in_len * 32, fs));
+    if ((rc = run_transform(dsc, buf, in_len, (uint32_t)N, buf, out_len, (uint32_t)N, (uint32_t)cnt, L, (const uint32_t*)omega, in_scale, in_period, out_scale,
+                            out_period, fs)) != ZKHIP_OK) return rc;
+    for (size_t b = 0; b < cnt; b++)
+      HIPCHK(hipMemcpyPeerAsync((uint32_t*)d_out + (lo + b) * out_stride * 8, P.device, buf + b * N * 8, D->device, (size_t)out_len * 32, fs));
   }
-  if (hipSetDevice(P.device) != hipSuccess) { set_error("hipSetDevice(%d) failed", P.device); return ZKHIP_ENODEV; }
-  int rc_local = ZKHIP_OK;
-  {
-    size_t lo, hi;
-    shard_range(batch, 0, S, &lo, &hi);
-    if (lo < hi && rc_remote == ZKHIP_OK)
-      rc_local = device_transform_one((const uint32_t*)d_in + lo * in_stride * 8, in_len, in_stride, (uint32_t*)d_out + lo * out_stride * 8, out_len, out_stride,
-                                      (uint32_t)(hi - lo), L, omega, in_scale, in_period, out_scale, out_period, s);
-  }
-  for (int d : waited) HIPCHK(hipStreamWaitEvent(s, g_ctx.devs[(size_t)d]->fan_done, 0));
-  return rc_remote != ZKHIP_OK ? rc_remote : rc_local;
+  if ((rc = F.dev(0)) != ZKHIP_OK) return rc;
+  size_t lo, hi;
+  shard_range(batch, 0, S, &lo, &hi);
+  if (lo < hi && (rc = device_transform_one((const uint32_t*)d_in + lo * in_stride * 8, in_len, in_stride, (uint32_t*)d_out + lo * out_stride * 8, out_len, out_stride,
+                                            (uint32_t)(hi - lo), L, omega, in_scale, in_period, out_scale, out_period, s)) != ZKHIP_OK) return rc;
+  return F.end();
 }
 
 }  // namespace zkhip
@@ -1435,13 +1404,15 @@ int zkhip_mul_periodic_device(void* d_a, size_t n, const void* d_table, uint32_t
 
 namespace zkhip {
 
-// One device's share of a host-buffer batch: `cnt` polynomials (polynomial b at in + b * in_stride elements) cross this device's PCIe link
-// into its scratch, are transformed in place (polynomial b at b * N elements) and go back to out + b * out_stride.  Runs on the calling
-// thread for the primary device and on the device's worker thread for a secondary (the current device is per host thread).
-static int host_transform_share(scratch* sc, hipStream_t s, const uint64_t* in, size_t in_len, size_t in_stride, uint64_t* out, size_t out_len, size_t out_stride,
+// One device's share of a host-buffer batch on the held lane H: `cnt` polynomials (polynomial b at in + b * in_stride elements) cross this
+// device's PCIe link into its scratch, are transformed in place (polynomial b at b * N elements) and go back to out + b * out_stride.  Runs on the
+// calling thread for the primary device and on the device's worker thread for a secondary (the current device is per host thread).
+static int host_transform_share(lane_hold& H, const uint64_t* in, size_t in_len, size_t in_stride, uint64_t* out, size_t out_len, size_t out_stride,
                                 size_t cnt, uint32_t log_n, const uint64_t* omega, const uint32_t* in_scale, uint32_t in_period, const uint32_t* out_scale,
                                 uint32_t out_period) {
   int rc;
+  scratch* const sc = H.sc;
+  hipStream_t s = H.s;
   const size_t N = (size_t)1 << log_n;
   if ((rc = sc->poly.reserve(cnt * N * 32)) != ZKHIP_OK) return rc;
   if (cnt == 1) HIPCHK(hipMemcpyAsync(sc->poly.p, in, in_len * 32, hipMemcpyHostToDevice, s));
@@ -1453,8 +1424,7 @@ static int host_transform_share(scratch* sc, hipStream_t s, const uint64_t* in, 
   if (cnt == 1) HIPCHK(hipMemcpyAsync(out, sc->poly.p, out_len * 32, hipMemcpyDeviceToHost, s));
   else if (out_len == N && out_stride == N) HIPCHK(hipMemcpyAsync(out, sc->poly.p, cnt * N * 32, hipMemcpyDeviceToHost, s));
   else HIPCHK(hipMemcpy2DAsync(out, out_stride * 32, sc->poly.p, N * 32, out_len * 32, cnt, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 // Host-buffer transforms, `batch` polynomials.  With several devices (fan-out mode >= 1) the batch is cut by shard_range: the primary's share
@@ -1472,7 +1442,7 @@ static int host_transform(const uint64_t* in, size_t in_len, size_t in_stride, u
   int S, mode;
   { guard_t g(g_mu); S = (int)g_ctx.devs.size(); mode = g_ctx.ntt_fanout; }
   if (S < 2 || batch < 2 || mode < 1)
-    return host_transform_share(H.sc, H.s, in, in_len, in_stride, out, out_len, out_stride, batch, log_n, omega, in_scale, in_period, out_scale, out_period);
+    return host_transform_share(H, in, in_len, in_stride, out, out_len, out_stride, batch, log_n, omega, in_scale, in_period, out_scale, out_period);
   std::unique_lock<std::mutex> fan(g_fanout_mu);              // the secondary devices have one lane each
   for (int d = 1; d < S; d++) {
     size_t lo, hi;
@@ -1480,10 +1450,8 @@ static int host_transform(const uint64_t* in, size_t in_len, size_t in_stride, u
     if (lo >= hi) continue;
     device_ctx* D = g_ctx.devs[(size_t)d];
     D->w->submit([=]() -> int {
-      hipStream_t ds = D->lanes[0].stream;
-      scratch* dsc;
-      { guard_t g(g_mu); dsc = scratch_for(*D, ds); }
-      return host_transform_share(dsc, ds, in + lo * in_stride * 4, in_len, in_stride, out + lo * out_stride * 4, out_len, out_stride, hi - lo, log_n, omega,
+      lane_hold U(*D);                                     // a failed job has drained the lane before wait() hands its error to the caller
+      return host_transform_share(U, in + lo * in_stride * 4, in_len, in_stride, out + lo * out_stride * 4, out_len, out_stride, hi - lo, log_n, omega,
                                   in_scale, in_period, out_scale, out_period);
     });
   }
@@ -1492,7 +1460,7 @@ static int host_transform(const uint64_t* in, size_t in_len, size_t in_stride, u
     size_t lo, hi;
     shard_range(batch, 0, S, &lo, &hi);
     if (lo < hi)
-      rc_local = host_transform_share(H.sc, H.s, in + lo * in_stride * 4, in_len, in_stride, out + lo * out_stride * 4, out_len, out_stride, hi - lo, log_n, omega,
+      rc_local = host_transform_share(H, in + lo * in_stride * 4, in_len, in_stride, out + lo * out_stride * 4, out_len, out_stride, hi - lo, log_n, omega,
                                       in_scale, in_period, out_scale, out_period);
   }
   int rc_remote = ZKHIP_OK;
@@ -1648,8 +1616,7 @@ int zkhip_mul_periodic(uint64_t* a, size_t n, const uint64_t* table, uint32_t pe
   HIPCHK(hipMemcpyAsync(H.sc->poly2.p, table, (size_t)period * 32, hipMemcpyHostToDevice, s));
   if ((rc = fr_mul_periodic_device((uint32_t*)H.sc->poly.p, n, (const uint32_t*)H.sc->poly2.p, period, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(a, H.sc->poly.p, n * 32, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 // ---- row a7: Fr-vector primitives ---------------------------------------------------------------------
@@ -1748,7 +1715,9 @@ int zkhip_fr_prefix_product_device(const void* d_v, size_t n, void* d_out, void*
 
 namespace zkhip {
 // host-buffer wrappers: upload to the lane's poly scratch, run on the lane's stream, download
-static int host_vec_op(int op, const uint64_t* in, size_t n_in, const uint64_t* c, uint64_t* out, size_t n_out) {
+// (`op(d_in, d_out, stream)` is the `_device` call; `in_place`: its result replaces d_in)
+template <class Op>
+static int host_vec_op(const uint64_t* in, size_t n_in, uint64_t* out, size_t n_out, bool in_place, Op op) {
   lane_hold H;
   if (H.rc != ZKHIP_OK) return H.rc;
   int rc;
@@ -1756,16 +1725,9 @@ static int host_vec_op(int op, const uint64_t* in, size_t n_in, const uint64_t* 
   if ((rc = H.sc->poly.reserve((n_in + 1) * 32)) != ZKHIP_OK) return rc;
   if ((rc = H.sc->poly2.reserve((n_out + 1) * 32)) != ZKHIP_OK) return rc;
   if (n_in) HIPCHK(hipMemcpyAsync(H.sc->poly.p, in, n_in * 32, hipMemcpyHostToDevice, s));
-  switch (op) {
-    case 0: rc = zkhip_fr_eval_polynomial_device(H.sc->poly.p, n_in, c, H.sc->poly2.p, s); break;
-    case 1: rc = zkhip_fr_kate_division_device(H.sc->poly.p, n_in, c, H.sc->poly2.p, s); break;
-    case 2: rc = zkhip_fr_batch_invert_device(H.sc->poly.p, n_in, s); break;
-    default: rc = zkhip_fr_prefix_product_device(H.sc->poly.p, n_in, H.sc->poly2.p, s); break;
-  }
-  if (rc != ZKHIP_OK) return rc;
-  if (n_out) HIPCHK(hipMemcpyAsync(out, op == 2 ? H.sc->poly.p : H.sc->poly2.p, n_out * 32, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  if ((rc = op(H.sc->poly.p, H.sc->poly2.p, s)) != ZKHIP_OK) return rc;
+  if (n_out) HIPCHK(hipMemcpyAsync(out, in_place ? H.sc->poly.p : H.sc->poly2.p, n_out * 32, hipMemcpyDeviceToHost, s));
+  return H.finish();
 }
 }  // namespace zkhip
 
@@ -1774,14 +1736,14 @@ extern "C" {
 int zkhip_fr_eval_polynomial(const uint64_t* poly, size_t n, const uint64_t point[4], uint64_t out[4]) {
   ZK_API_RANGE();
   if (!point || !out || (n && !poly)) { set_error("eval_polynomial: null pointer"); return ZKHIP_EINVAL; }
-  return host_vec_op(0, poly, n, point, out, 1);
+  return host_vec_op(poly, n, out, 1, false, [&](void* d_a, void* d_r, void* s) { return zkhip_fr_eval_polynomial_device(d_a, n, point, d_r, s); });
 }
 
 int zkhip_fr_kate_division(const uint64_t* a, size_t n, const uint64_t b[4], uint64_t* q) {
   ZK_API_RANGE();
   if (!b || (n > 1 && (!a || !q))) { set_error("kate_division: null pointer"); return ZKHIP_EINVAL; }
   if (n < 2) return ZKHIP_OK;
-  return host_vec_op(1, a, n, b, q, n - 1);
+  return host_vec_op(a, n, q, n - 1, false, [&](void* d_a, void* d_q, void* s) { return zkhip_fr_kate_division_device(d_a, n, b, d_q, s); });
 }
 
 int zkhip_fr_divide_by_roots(const uint64_t* a, size_t n, const uint64_t* roots, uint32_t m, uint64_t* q, uint64_t* evals) {
@@ -1796,11 +1758,6 @@ int zkhip_fr_divide_by_roots(const uint64_t* a, size_t n, const uint64_t* roots,
   lane_hold H;
   if (H.rc != ZKHIP_OK) return H.rc;
   hipStream_t s = H.s;
-  // on an error after something was enqueued: wait for the lane's stream, so that nothing outlives the caller's buffers or runs into the lane's next user
-  struct drain_t {
-    hipStream_t s; bool armed = true;
-    ~drain_t() { if (armed) { (void)hipStreamSynchronize(s); (void)hipGetLastError(); } }
-  } drain{s};
   if ((rc = H.sc->poly.reserve(n * 32)) != ZKHIP_OK) return rc;
   if ((rc = H.sc->poly2.reserve((n + ZKHIP_MAX_ROOTS) * 32)) != ZKHIP_OK) return rc;
   char* d_ev = (char*)H.sc->poly2.p + n * 32;
@@ -1808,23 +1765,21 @@ int zkhip_fr_divide_by_roots(const uint64_t* a, size_t n, const uint64_t* roots,
   if ((rc = zkhip_fr_divide_by_roots_device(H.sc->poly.p, n, roots, m, H.sc->poly2.p, evals ? d_ev : nullptr, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(q, H.sc->poly2.p, n * 32, hipMemcpyDeviceToHost, s));
   if (evals) HIPCHK(hipMemcpyAsync(evals, d_ev, (size_t)m * 32, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  drain.armed = false;
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 int zkhip_fr_batch_invert(uint64_t* a, size_t n) {
   ZK_API_RANGE();
   if (n && !a) { set_error("batch_invert: null pointer"); return ZKHIP_EINVAL; }
   if (n == 0) return ZKHIP_OK;
-  return host_vec_op(2, a, n, nullptr, a, n);
+  return host_vec_op(a, n, a, n, true, [&](void* d_a, void*, void* s) { return zkhip_fr_batch_invert_device(d_a, n, s); });
 }
 
 int zkhip_fr_prefix_product(const uint64_t* v, size_t n, uint64_t* out) {
   ZK_API_RANGE();
   if (n && (!v || !out)) { set_error("prefix_product: null pointer"); return ZKHIP_EINVAL; }
   if (n == 0) return ZKHIP_OK;
-  return host_vec_op(3, v, n, nullptr, out, n);
+  return host_vec_op(v, n, out, n, false, [&](void* d_v, void* d_out, void* s) { return zkhip_fr_prefix_product_device(d_v, n, d_out, s); });
 }
 
 // ---- lookup argument: permute_expression_pair ----------------------------------------------------------------------
@@ -1902,8 +1857,7 @@ int zkhip_lookup_permute(const uint64_t* input, const uint64_t* table, size_t us
   if ((rc = zkhip_lookup_permute_device(in, in + bytes, usable_rows, out, out + bytes, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(permuted_input, out, bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(permuted_table, out + bytes, bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 // ---- device buffers for hosts that do not link HIP -------------------------------------------------------------
@@ -2027,7 +1981,7 @@ int zkhip_fr_eval_rows_window_device(const zkhip_vm_program* prog, const void* c
 
 // The quotient numerator re-cut by rows over the devices of zkhip_init.  Device j of S: rows shard_range(2^ext_k, j, S),
 // COEFF columns shard_range(n_coeff, j, S) in argument order.  Steps, all enqueued from this thread (nothing here waits for a device):
-//   A  every device's stream waits for the caller's stream (entry event) and for the previous call's last steps on every device
+//   A  every device's stream waits for the caller's stream (fan_call's entry event) and for the previous call's last steps on every device
 //      (its transforms overwrite q_ext, which the previous call's window copies read);
 //   B  each owner pulls its COEFF columns from the primary and runs coeff_to_extended into q_ext (its own twiddle plan), records q_transformed;
 //   C  device j waits for every owner's q_transformed, fills its window buffers with peer copies (COEFF columns from their owner's q_ext,
@@ -2115,25 +2069,8 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     return ZKHIP_OK;
   }
   std::unique_lock<std::mutex> fan(g_fanout_mu);
-  std::vector<hipStream_t> st(S, nullptr);                  // the stream device j works on: the caller's for the primary, its fan stream otherwise
   std::vector<scratch*> dsc(S, nullptr);
   std::vector<size_t> row_lo(S), row_n(S), own_lo(S), own_n(S);
-  std::vector<bool> used(S, false);                        // streams that hold enqueued work (drained on an error)
-  // on an error after something was enqueued: wait for every stream that holds this call's work, so that nothing outlives the call's buffers
-  struct drain_t {
-    std::vector<hipStream_t>* st; std::vector<bool>* used; std::vector<device_ctx*>* devs; bool armed = true;
-    ~drain_t() {
-      if (!armed) return;
-      for (size_t j = 0; j < st->size(); j++)
-        if ((*used)[j]) { (void)hipSetDevice((*devs)[j]->device); (void)hipStreamSynchronize((*st)[j]); }
-      (void)hipSetDevice((*devs)[0]->device);
-      (void)hipGetLastError();
-    }
-  } drain{&st, &used, &g_ctx.devs};
-  auto set_dev = [&](int j) -> int {
-    if (hipSetDevice(g_ctx.devs[(size_t)j]->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", g_ctx.devs[(size_t)j]->device); return ZKHIP_ENODEV; }
-    return ZKHIP_OK;
-  };
   // A: streams, scratch, events; every device's first step waits for the entry event and for the previous call's last steps
   bool grows = false;
   for (int j = 0; j < S; j++) {
@@ -2148,19 +2085,15 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
   // thread, and only when a shape needs more scratch than any earlier call (a second call of the same shape allocates nothing and never waits)
   if (grows)
     for (auto* D : g_ctx.devs) if (D->q_done_live) HIPCHK(hipEventSynchronize(D->q_done));
-  if (!P.fan_ready) HIPCHK(hipEventCreateWithFlags(&P.fan_ready, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(P.fan_ready, s));
+  fan_call F;                                              // an error return from here on waits for every device's stream
+  if ((rc = F.begin(s)) != ZKHIP_OK) return rc;
+  const std::vector<hipStream_t>& st = F.st;               // the stream device j works on: the caller's for the primary, its fan stream otherwise
   for (int j = 0; j < S; j++) {
     device_ctx* D = g_ctx.devs[(size_t)j];
-    if ((rc = set_dev(j)) != ZKHIP_OK) return rc;
-    if (j > 0 && !D->fan) {
-      HIPCHK(hipStreamCreateWithFlags(&D->fan, hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&D->fan_done, hipEventDisableTiming));
-    }
+    if ((rc = F.dev(j)) != ZKHIP_OK) return rc;
     if (!D->q_transformed) HIPCHK(hipEventCreateWithFlags(&D->q_transformed, hipEventDisableTiming));
     if (!D->q_done) HIPCHK(hipEventCreateWithFlags(&D->q_done, hipEventDisableTiming));
-    st[j] = j == 0 ? s : D->fan;
-    dsc[j] = j == 0 ? sc : scratch_for(*D, D->fan);
+    dsc[j] = scratch_for(*D, st[j]);
     shard_range(N, j, S, &row_lo[j], &row_n[j]);
     row_n[j] -= row_lo[j];
     shard_range(nC, j, S, &own_lo[j], &own_n[j]);
@@ -2172,16 +2105,14 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     if ((rc = dsc[j]->vm.reserve(row_vm_workspace_bytes(prog, n_columns, ext_k))) != ZKHIP_OK) return rc;
   }
   for (int j = 0; j < S; j++) {
-    if ((rc = set_dev(j)) != ZKHIP_OK) return rc;
-    if (j > 0) HIPCHK(hipStreamWaitEvent(st[j], P.fan_ready, 0));
+    if ((rc = F.dev(j)) != ZKHIP_OK) return rc;
     for (int i = 0; i < S; i++)
       if (g_ctx.devs[(size_t)i]->q_done_live) HIPCHK(hipStreamWaitEvent(st[j], g_ctx.devs[(size_t)i]->q_done, 0));
   }
   // B: the transforms, each on its owner
   for (int j = 0; j < S; j++) {
     device_ctx* D = g_ctx.devs[(size_t)j];
-    if ((rc = set_dev(j)) != ZKHIP_OK) return rc;
-    used[j] = true;
+    if ((rc = F.dev(j)) != ZKHIP_OK) return rc;
     prof_hold hold;
     uint32_t* ext = (uint32_t*)D->q_ext.p;
     for (size_t c = 0; c < own_n[j]; c++) {
@@ -2198,17 +2129,16 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
                             nullptr, 0, st[j])) != ZKHIP_OK) return rc;
     HIPCHK(hipEventRecord(D->q_transformed, st[j]));
   }
-  if ((rc = set_dev(0)) != ZKHIP_OK) return rc;
+  if ((rc = F.dev(0)) != ZKHIP_OK) return rc;
   prof_mark(s, "transform");
   // C: windows, the window kernel, the results into d_out
   std::vector<const void*> win(n_columns ? n_columns : 1);
   for (int j = 0; j < S; j++) {
     device_ctx* D = g_ctx.devs[(size_t)j];
-    if ((rc = set_dev(j)) != ZKHIP_OK) return rc;
+    if ((rc = F.dev(j)) != ZKHIP_OK) return rc;
     for (int i = 0; i < S; i++)
       if (own_n[i]) HIPCHK(hipStreamWaitEvent(st[j], g_ctx.devs[(size_t)i]->q_transformed, 0));
     const size_t W = halo_lo + row_n[j] + halo_hi;
-    const size_t start = (size_t)((((int64_t)row_lo[j] - (int64_t)halo_lo) % (int64_t)N + (int64_t)N) % (int64_t)N);
     uint32_t slot = 0;                                     // this device's window buffers, one per copied column
     for (uint32_t c = 0; c < n_columns; c++) {
       if (rs_set[c]) { win[c] = rs_window(j, c); continue; }
@@ -2224,12 +2154,7 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
       }
       uint32_t* dst = (uint32_t*)D->q_win.p + (size_t)slot++ * W * 8;
       win[c] = dst;
-      for (size_t t = 0, pos = start; t < W;) {              // at most ceil(W / N) + 1 pieces
-        const size_t len = std::min(W - t, N - pos);
-        HIPCHK(hipMemcpyPeerAsync(dst + t * 8, D->device, src + pos * 8, src_dev, len * 32, st[j]));
-        t += len;
-        pos = 0;
-      }
+      if ((rc = copy_window(dst, D->device, src, src_dev, window_start(row_lo[j], halo_lo, N), W, N, st[j])) != ZKHIP_OK) return rc;
     }
     if (j == 0) prof_mark(s, "exchange");
     uint32_t* out = j == 0 ? (uint32_t*)d_out + row_lo[0] * 8 : (uint32_t*)D->q_out.p;
@@ -2242,11 +2167,11 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     HIPCHK(hipEventRecord(D->q_done, st[j]));
     D->q_done_live = true;
   }
-  // D: the caller's stream waits for every device
-  if ((rc = set_dev(0)) != ZKHIP_OK) return rc;
+  // D: the caller's stream waits for every device (their q_done events are what F.end() would record: this call is complete without it)
+  if ((rc = F.dev(0)) != ZKHIP_OK) return rc;
   for (int j = 1; j < S; j++) HIPCHK(hipStreamWaitEvent(s, g_ctx.devs[(size_t)j]->q_done, 0));
   prof_mark(s, "gather");
-  drain.armed = false;
+  F.armed = false;
   return ZKHIP_OK;
 }
 
@@ -2504,6 +2429,8 @@ int zkhip_fr_eval_rows(const zkhip_vm_program* prog, const uint64_t* const* colu
   int rc;
   if ((rc = row_vm_validate(prog, n_columns, log_rows, accumulate)) != ZKHIP_OK) return rc;
   if (!out || (n_columns && !columns)) { set_error("eval_rows: null pointer"); return ZKHIP_EINVAL; }
+  for (uint32_t i = 0; i < n_columns; i++)
+    if (!columns[i]) { set_error("eval_rows: column %u is null", i); return ZKHIP_EINVAL; }
   lane_hold H;
   if (H.rc != ZKHIP_OK) return H.rc;
   const size_t rows = (size_t)1 << log_rows, bytes = rows * 32;
@@ -2512,15 +2439,13 @@ int zkhip_fr_eval_rows(const zkhip_vm_program* prog, const uint64_t* const* colu
   if ((rc = H.sc->poly2.reserve(bytes)) != ZKHIP_OK) return rc;
   std::vector<const void*> d_cols(n_columns);
   for (uint32_t i = 0; i < n_columns; i++) {
-    if (!columns[i]) { set_error("eval_rows: column %u is null", i); return ZKHIP_EINVAL; }
     d_cols[i] = (char*)H.sc->poly.p + (size_t)i * bytes;
     HIPCHK(hipMemcpyAsync((void*)d_cols[i], columns[i], bytes, hipMemcpyHostToDevice, s));
   }
   if (accumulate) HIPCHK(hipMemcpyAsync(H.sc->poly2.p, out, bytes, hipMemcpyHostToDevice, s));
   if ((rc = zkhip_fr_eval_rows_device(prog, d_cols.data(), n_columns, log_rows, accumulate, H.sc->poly2.p, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(out, H.sc->poly2.p, bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 int zkhip_fr_gather_mul_device(const void* d_a, size_t a_len, const void* d_index_a, const void* d_b, size_t b_len, const void* d_index_b, size_t n,
@@ -2564,8 +2489,7 @@ int zkhip_fr_grand_product(const uint64_t* num, const uint64_t* den, size_t n, u
   HIPCHK(hipMemcpyAsync(H.sc->poly2.p, den, n * 32, hipMemcpyHostToDevice, s));
   if ((rc = zkhip_fr_grand_product_device(H.sc->poly.p, H.sc->poly2.p, n, H.sc->poly.p, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(z, H.sc->poly.p, n * 32, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 int zkhip_fr_linear_combination_device(const void* const* d_cols, const uint64_t* coeffs, size_t count, size_t n, void* d_out, void* stream) {
@@ -2636,8 +2560,7 @@ int zkhip_permutation_products(const uint64_t* const* values, const uint64_t* co
   if ((rc = zkhip_permutation_products_device(d_cols.data(), d_cols.data() + n_columns, n_columns, chunk_len, log_n, usable_rows, beta, gamma, delta, omega,
                                               H.sc->poly2.p, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(z, H.sc->poly2.p, nsets * bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 int zkhip_profile_enable(int on) {
@@ -2760,8 +2683,7 @@ int zkhip_g_to_lagrange(const uint64_t* g_xyz, uint32_t k, uint64_t* g_lagrange)
   const Hh::Fr omega_inv = Hh::detail::invert(omega), n_inv = Hh::detail::invert(Hh::detail::from_u64((uint64_t)n));
   if ((rc = g1_fft_device((const uint32_t*)sc->bases.p, 1, (uint32_t*)sc->poly.p, 0, k, (const uint32_t*)omega_inv.l, (const uint32_t*)n_inv.l, sc->ws.p, sc->ws.cap, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(g_lagrange, sc->poly.p, n * 64, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 int zkhip_g1_gen_walk_device(const uint64_t t0[4], const uint64_t d[4], size_t n, void* d_out, void* stream) {
@@ -2804,8 +2726,7 @@ int zkhip_g1_batch_normalize(const uint64_t* points_xyz, size_t n, uint64_t* out
   HIPCHK(hipMemcpyAsync(d, points_xyz, n * 96, hipMemcpyHostToDevice, s));
   if ((rc = g1_batch_normalize_device((const uint32_t*)d, n, (uint32_t*)(d + n * 96), H.sc->ws.p, H.sc->ws.cap, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(out_affine, d + n * 96, n * 64, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 // ---- G2 MSM: best_multiexp::<G2Affine> -------------------------------------------------------------------------------
@@ -2838,7 +2759,7 @@ int zkhip_msm_g2(const uint64_t* scalars, const uint64_t* bases, size_t n, uint6
   }
   if ((rc = msm_g2_device((const uint32_t*)H.sc->scalars.p, (const uint32_t*)H.sc->bases.p, n, (uint32_t*)H.sc->small.p, H.sc->ws.p, H.sc->ws.cap, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(H.L->pinned, H.sc->small.p, 192, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  if ((rc = H.finish()) != ZKHIP_OK) return rc;
   memcpy(out_xyz, H.L->pinned, 192);
   return ZKHIP_OK;
 }
@@ -2873,10 +2794,11 @@ int zkhip_g1_check_points(const uint64_t* points, size_t n, uint64_t* first_bad)
   if ((rc = H.sc->small.reserve(4096)) != ZKHIP_OK) return rc;
   for (size_t lo = 0; lo < n; lo += chunk) {
     const size_t m = std::min(chunk, n - lo);
+    H.reopen();
     HIPCHK(hipMemcpyAsync(H.sc->bases.p, points + lo * 8, m * 64, hipMemcpyHostToDevice, H.s));
     if ((rc = g1_check_points_device((const uint32_t*)H.sc->bases.p, m, (unsigned long long*)H.sc->small.p, H.s)) != ZKHIP_OK) return rc;
     HIPCHK(hipMemcpyAsync(H.L->pinned, H.sc->small.p, 8, hipMemcpyDeviceToHost, H.s));
-    HIPCHK(hipStreamSynchronize(H.s));
+    if ((rc = H.finish()) != ZKHIP_OK) return rc;
     const unsigned long long v = *(const unsigned long long*)H.L->pinned;
     if (v < m) { *first_bad = lo + (size_t)v; return ZKHIP_OK; }
   }
@@ -2924,10 +2846,11 @@ int zkhip_g1_compress(const uint64_t* points, size_t n, uint8_t* out32, int flag
   if ((rc = H.sc->poly.reserve(std::min(n, chunk) * 32)) != ZKHIP_OK) return rc;
   for (size_t lo = 0; lo < n; lo += chunk) {
     const size_t m = std::min(chunk, n - lo);
+    H.reopen();
     HIPCHK(hipMemcpyAsync(H.sc->bases.p, points + lo * 8, m * 64, hipMemcpyHostToDevice, H.s));
     if ((rc = g1_compress_device((const uint32_t*)H.sc->bases.p, m, (uint32_t*)H.sc->poly.p, flag_layout, H.s)) != ZKHIP_OK) return rc;
     HIPCHK(hipMemcpyAsync(out32 + lo * 32, H.sc->poly.p, m * 32, hipMemcpyDeviceToHost, H.s));
-    HIPCHK(hipStreamSynchronize(H.s));
+    if ((rc = H.finish()) != ZKHIP_OK) return rc;
   }
   return ZKHIP_OK;
 }
@@ -2946,13 +2869,14 @@ int zkhip_g1_decompress(const uint8_t* in32, size_t n, uint64_t* points, int fla
   if ((rc = H.sc->small.reserve(4096)) != ZKHIP_OK) return rc;
   for (size_t lo = 0; lo < n; lo += chunk) {
     const size_t m = std::min(chunk, n - lo);
+    H.reopen();
     *(unsigned long long*)H.L->pinned = (unsigned long long)m;
     HIPCHK(hipMemcpyAsync(H.sc->small.p, H.L->pinned, 8, hipMemcpyHostToDevice, H.s));
     HIPCHK(hipMemcpyAsync(H.sc->poly.p, in32 + lo * 32, m * 32, hipMemcpyHostToDevice, H.s));
     if ((rc = g1_decompress_device((const uint32_t*)H.sc->poly.p, m, (uint32_t*)H.sc->bases.p, flag_layout, (unsigned long long*)H.sc->small.p, H.s)) != ZKHIP_OK) return rc;
     HIPCHK(hipMemcpyAsync(points + lo * 8, H.sc->bases.p, m * 64, hipMemcpyDeviceToHost, H.s));
     HIPCHK(hipMemcpyAsync(H.L->pinned, H.sc->small.p, 8, hipMemcpyDeviceToHost, H.s));
-    HIPCHK(hipStreamSynchronize(H.s));
+    if ((rc = H.finish()) != ZKHIP_OK) return rc;
     const unsigned long long v = *(const unsigned long long*)H.L->pinned;
     if (v < m) { *first_bad = lo + (size_t)v; return ZKHIP_OK; }
   }
@@ -2974,8 +2898,7 @@ int zkhip_test_field_op(int field, int op, const uint64_t* a, const uint64_t* b,
   HIPCHK(hipMemcpyAsync(d + n * 32, b, n * 32, hipMemcpyHostToDevice, s));
   if ((rc = test_field_op(field, op, (uint32_t*)d, (uint32_t*)(d + n * 32), (uint32_t*)(d + n * 64), n, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(out, d + n * 64, n * 32, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 int zkhip_test_g1_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out_xyz, size_t n) {
@@ -2992,8 +2915,7 @@ int zkhip_test_g1_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out
   HIPCHK(hipMemcpyAsync(d + n * 64, b, n * 64, hipMemcpyHostToDevice, s));
   if ((rc = test_g1_op(op, (uint32_t*)d, (uint32_t*)(d + n * 64), (uint32_t*)(d + n * 128), n, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(out_xyz, d + n * 128, n * 96, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 int zkhip_test_g2_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out_xyz, size_t n) {
@@ -3010,8 +2932,7 @@ int zkhip_test_g2_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out
   HIPCHK(hipMemcpyAsync(d + n * 128, b, n * 128, hipMemcpyHostToDevice, s));
   if ((rc = test_g2_op(op, (uint32_t*)d, (uint32_t*)(d + n * 128), (uint32_t*)(d + n * 256), n, s)) != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(out_xyz, d + n * 256, n * 192, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKHIP_OK;
+  return H.finish();
 }
 
 }  // extern "C"

@@ -130,8 +130,6 @@ __global__ void __launch_bounds__(256) k_lookup_assign(const key256* __restrict_
   store_key_as_fr(repeated[i] ? leftover[n_repeated - 1 - repeated_rank[i]] : v, out_table, i);
 }
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s failed: %s", #x, hipGetErrorString(e_)); return ZKHIP_EHIP; } } while (0)
-
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static size_t sort_temp_bytes(size_t u) {

@@ -1623,8 +1623,6 @@ size_t msm_workspace_bytes(size_t n_one, int c, bool prepared, size_t batch, siz
   return b;
 }
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s failed: %s", #x, hipGetErrorString(e_)); return ZKHIP_EHIP; } } while (0)
-
 // Steps 1 - 5 (digits, bucket sort, tasks, execution order): everything that depends on the scalars only, shared by the curves.
 // `shared_buckets`: one bucket set per MSM of the batch for all windows (prepared G1 tables) instead of one per window.
 // ref_base / ref_stride: point reference of entry i of window w = ref_base + w * ref_stride + i.

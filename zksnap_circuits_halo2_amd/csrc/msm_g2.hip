@@ -25,8 +25,6 @@ struct task_t {
   uint32_t bucket, start, len;
 };
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s failed: %s", #x, hipGetErrorString(e_)); return ZKHIP_EHIP; } } while (0)
-
 // beta^2 (Montgomery-256 words): the cube root of unity in Fq with (beta^2 x, y) = lambda (x, y) on G2 for the lambda of msm.hip's GLV split
 __device__ constexpr uint32_t BETA2_EXT[8] = {0x13e80b9cu, 0x3350c88eu, 0xdb5e56b9u, 0x7dce557cu, 0xb615564au, 0x6001b4b8u, 0x020217e0u, 0x2682e617u};
 

@@ -410,8 +410,6 @@ struct ntt_plan {
 static std::mutex g_plan_mu;
 static std::map<std::array<uint32_t, 10>, std::shared_ptr<ntt_plan>> g_plans;   // a transform in flight keeps its plan alive past an eviction
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s failed: %s", #x, hipGetErrorString(e_)); return ZKHIP_EHIP; } } while (0)
-
 static int plan_alloc(ntt_plan* p, uint32_t** out, size_t bytes) {
   void* d = nullptr;
   if (hipMalloc(&d, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("ntt: hipMalloc(%zu) failed", bytes); return ZKHIP_ENOMEM; }

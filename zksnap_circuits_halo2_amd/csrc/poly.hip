@@ -232,8 +232,6 @@ __global__ void __launch_bounds__(64) k_batch_invert(uint32_t* __restrict__ a, s
 }
 
 // ---- host orchestration ------------------------------------------------------------------------------
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s failed: %s", #x, hipGetErrorString(e_)); return ZKHIP_EHIP; } } while (0)
-
 static inline size_t chunks_of(size_t n) { return (n + POLY_CH - 1) / POLY_CH; }
 static inline dim3 grid_for(size_t threads, int block) { return dim3((unsigned)((threads + block - 1) / block)); }
 

@@ -365,8 +365,6 @@ __global__ void __launch_bounds__(256) k_fr_gather_mul(const uint32_t* __restric
   store_words(out + j * 8, w);
 }
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s failed: %s", #x, hipGetErrorString(e_)); return ZKHIP_EHIP; } } while (0)
-
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static bool fr_is_canonical(const uint64_t* w) {

@@ -11,6 +11,9 @@ namespace zkhip {
 
 void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 
+// a failed HIP call ends the function it is in: its text and HIP's message become the thread's error, ZKHIP_EHIP the return value
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ::zkhip::set_error("%s failed: %s", #x, hipGetErrorString(e_)); return ZKHIP_EHIP; } } while (0)
+
 // profiler (capi.hip): when enabled, device paths drop named HIP events on their stream between phases
 void prof_begin(hipStream_t stream);
 void prof_mark(hipStream_t stream, const char* name);

@@ -357,6 +357,33 @@ int zkhip_lookup_products_device(const void *const *d_inputs, const void *const 
                                  uint32_t n_lookups, uint32_t log_n, size_t usable_rows, const uint64_t beta[4], const uint64_t gamma[4], void *d_z,
                                  void *stream);
 
+/* ---- random field elements: blinding rows and the vanishing argument's random polynomial, drawn in HBM ---------------------------
+ * A cryptographic, reproducible stream of Fr elements addressed by index.  THE STREAM (normative): element i of stream (seed, stream_id) is
+ *   1. one ChaCha20 block of 20 rounds in the original layout with a 64-bit block counter: words 0..3 are "expand 32-byte k" (0x61707865,
+ *      0x3320646e, 0x79622d32, 0x6b206574); words 4..11 are the 32 seed bytes as little-endian u32; word 12 is the low half of i, word 13
+ *      its high half; word 14 is the low half of stream_id, word 15 its high half;
+ *   2. its 64 output bytes (the 16 output words, little-endian, word 0 first) read as a little-endian 512-bit integer;
+ *   3. that integer mod r,
+ * stored in the external format (4 x u64 Montgomery-256, canonical).  One block gives exactly one element, so an element depends on (seed,
+ * stream_id, i) alone: every launch geometry, every split of a range into calls and every device produce the same column, and a host can
+ * restate it.  (Design intent, not pinned by any test: the i-th `Fr::random` of a `ChaCha20Rng::from_seed(seed)` after `set_stream(stream_id)`.)
+ * Pin: seed bytes 00 01 .. 1f, stream_id 0x4a000000, i = 0x0900000000000001 is the block of RFC 8439 section 2.3.2; its element is
+ * 0x099d737c79bea952e4c9671a82baa6de853af4f7694e36c4e5577d4ae6d300c5, stored as the 256-bit number
+ * 0x25312d9be543d4c7a1d921e13f01589a414c389165c4cad2b5e970bf8f628f64.
+ * CONTRACT: the library holds no entropy -- the caller draws the seed from its own generator; blinding is exactly as secret as the seed; a
+ * (seed, stream_id, index) triple is never reused across proofs.
+ * zkhip_fr_random_device writes elements first .. first + n - 1 to d_out.  zkhip_fr_random is its host-buffer form.
+ * zkhip_fr_random_rows_device writes element first + c * count + j to row row0 + j of column c (d_cols: host array of n_cols device pointers,
+ * every column holding at least row0 + count elements) in one launch whatever n_cols is, and touches no other row: the blinding tails of all
+ * columns of a phase in one call.  n_cols * count is at most 2^30.
+ * Both `_device` forms are asynchronous on `stream`; the seed and the pointer array are consumed before the call returns.  n == 0, n_cols == 0
+ * and count == 0 are ZKHIP_OK and do nothing.  ZKHIP_EINVAL with nothing written: a null pointer (a null column included), first + the number
+ * of elements above 2^64, more than 2^30 elements in the rows form. */
+int zkhip_fr_random_device(const uint8_t seed[32], uint64_t stream_id, uint64_t first, size_t n, void *d_out, void *stream);
+int zkhip_fr_random(const uint8_t seed[32], uint64_t stream_id, uint64_t first, size_t n, uint64_t *out);
+int zkhip_fr_random_rows_device(const uint8_t seed[32], uint64_t stream_id, uint64_t first, const void *const *d_cols,
+                                uint32_t n_cols, size_t row0, size_t count, void *stream);
+
 /* ---- device buffers for a host that does not link HIP itself (handles instead of host slices) ---- */
 /* The `_device` entry points below take HIP device pointers so that polynomials stay in HBM from iNTT through commit, extended
  * NTT, quotient and back (PCIe is 8x slower than the NTT kernel: DESIGN.md section 5).  A Rust / C host obtains such pointers

@@ -387,6 +387,13 @@ inline std::pair<std::vector<Fr>, std::vector<Fr>> permute_expression_pair(const
   if (usable_rows) check(zkhip_lookup_permute(input.data()->l, table.data()->l, usable_rows, pi.data()->l, pt.data()->l), "permute_expression_pair");
   return {std::move(pi), std::move(pt)};
 }
+// elements first .. first + n - 1 of the library's random stream (zkhip.h, "random field elements"), brought to the host: what a verifier of
+// the stream, or a host without device-resident columns, compares against
+inline std::vector<Fr> random_fr(const std::array<uint8_t, 32>& seed, size_t n, uint64_t first = 0, uint64_t stream_id = 0) {
+  std::vector<Fr> out(n);
+  if (n) check(zkhip_fr_random(seed.data(), stream_id, first, n, out.data()->l), "random_fr");
+  return out;
+}
 
 // A polynomial / column that lives in HBM between calls (zkhip_alloc / upload / download): what a host passes to the `_device`
 // entry points so that iNTT -> commit -> extended NTT -> quotient never cross PCIe.
@@ -1164,6 +1171,22 @@ inline void lookup_products_device(const std::vector<const DeviceVec*>& inputs, 
   if (permuted_inputs.size() < in.size() * n || permuted_tables.size() < in.size() * n || z.size() < in.size() * n) throw std::invalid_argument("lookup_products_device: column block too short");
   check(zkhip_lookup_products_device(in.data(), tab.data(), permuted_inputs.data(), permuted_tables.data(), (uint32_t)in.size(), k, usable_rows, beta.l, gamma.l, z.data(), nullptr),
         "lookup_products_device");
+}
+// Random field elements drawn in HBM (zkhip.h, "random field elements": element i of stream (seed, stream_id) is one ChaCha20 block reduced mod r).
+// The library holds no entropy: `seed` comes from the caller's generator, and a (seed, stream_id, index) triple is never reused across proofs.
+// out[j] = element first + j for every j < out.size(): the vanishing argument's random polynomial, never on the host
+inline void random_fr_device(const std::array<uint8_t, 32>& seed, uint64_t stream_id, uint64_t first, DeviceVec& out) {
+  check(zkhip_fr_random_device(seed.data(), stream_id, first, out.size(), out.data(), nullptr), "random_fr_device");
+}
+// the blinding tails of all `columns` in one call: row row0 + j of column c = element first + c * count + j, j < count; no other row is touched
+inline void blind_rows_device(const std::vector<DeviceVec*>& columns, size_t row0, size_t count, const std::array<uint8_t, 32>& seed, uint64_t stream_id = 0,
+                              uint64_t first = 0) {
+  std::vector<const void*> ptrs;
+  for (DeviceVec* c : columns) {
+    if (c->size() < row0 + count) throw std::invalid_argument("blind_rows_device: column shorter than row0 + count");
+    ptrs.push_back(c->data());
+  }
+  check(zkhip_fr_random_rows_device(seed.data(), stream_id, first, ptrs.data(), (uint32_t)ptrs.size(), row0, count, nullptr), "blind_rows_device");
 }
 // d_poly[index] -= value / d_poly[index] = 0: one-row programs on the element itself (no host round trip)
 inline void sub_const_at(DeviceVec& poly, size_t index, const Fr& value) {

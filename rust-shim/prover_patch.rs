@@ -119,24 +119,33 @@ pub(crate) struct DeviceProof {
     pub first_advice: usize,
     pub first_perm_product: usize,
     pub first_lookup: usize,
+    /// the vanishing argument's random polynomial (coefficients; drawn on the device, never on the host)
+    pub random_poly: usize,
 }
 
-// The order of `create_proof` is unchanged; each step that used host `Polynomial`s uses the handle instead:
+// The order of `create_proof` is unchanged; each step that used host `Polynomial`s uses the handle instead.  Randomness is drawn in HBM from
+// `let seed = zkhip_ffi::random_seed(&mut rng);` (once per proof, from the prover's own generator): `next` counts the stream indices handed
+// out so far, and every call below takes its elements from `next` on and advances it by columns * blinding_factors (an index is used once).
 //
 //   advice (per phase)     base.upload(col, 0, &advice_values[i]) for the phase's columns; commitments = base.commit_many(first, count, n,
-//                          &params.g_lagrange, identity) -> batch_normalize -> transcript (unchanged from here)
+//                          &params.g_lagrange, identity) -> batch_normalize -> transcript (unchanged from here).  The host leaves the unusable
+//                          rows of the witness alone: base.blind_rows(first, count, usable_rows, n - usable_rows, &seed, 0, next) draws the
+//                          blinding rows of all the phase's columns in one call, after the upload and before the commit
 //   lookups, theta         compressed input / table expressions = DevCols::eval_rows(&lower_expression(..)) over base columns (a lookup of plain
 //                          columns needs no program); base.lookup_permute_many(&input_addresses, &table_addresses, k, usable_rows, first_permuted_input,
 //                          first_permuted_table) writes the permuted pair of EVERY lookup in one call (no input column is sorted, the table once per
-//                          distinct address, one wait for the status); blinding rows: base.upload(col, usable_rows, &random_rows); commit_many of the pairs
+//                          distinct address, one wait for the status); blinding rows: base.blind_rows(first_permuted_input, lookups, usable_rows, n - usable_rows, &seed, 0, next) and
+//                          the same for first_permuted_table (one call where the two runs of columns are adjacent); commit_many of the pairs
 //   permutation, beta/gamma  base.permutation_products(first_perm_product, &value_addresses, &sigma_addresses, chunk_len, k, usable_rows, &beta, &gamma,
 //                          &F::DELTA, &omega): every chunk's z, chained through z[usable_rows], in one call (a handful of launches whatever the
-//                          number of chunks: hundreds at the voter / state-transition column counts); blinding rows uploaded; commit_many over
-//                          all chunks.  (Before this entry point existed: per chunk a numerator and a denominator program,
+//                          number of chunks: hundreds at the voter / state-transition column counts); blinding rows: base.blind_rows(first_perm_product,
+//                          chunks, usable_rows + 1, n - usable_rows - 1, &seed, 0, next); commit_many over all chunks.  (Before this entry point existed: per chunk a numerator and a denominator program,
 //                          base.grand_product, a 32-byte download and a scaling program.)
 //   lookup products        base.lookup_products(first_lookup_product, &input_addresses, &table_addresses, first_permuted_input, first_permuted_table, k,
-//                          usable_rows, &beta, &gamma): every lookup's z in one call; blinding rows uploaded; commit_many over all lookups
-//   vanishing random poly  generated on the host as upstream, committed through best_multiexp (one column; stays on the host path)
+//                          usable_rows, &beta, &gamma): every lookup's z in one call; blinding rows: base.blind_rows(first_lookup_product, lookups,
+//                          usable_rows + 1, n - usable_rows - 1, &seed, 0, next); commit_many over all lookups
+//   vanishing random poly  base.fill_random(random_poly, n, &seed, 1, 0): n coefficients of stream 1, written where the multi-open reads them;
+//                          commitment = base.commit_many(random_poly, 1, n, &params.g, identity)
 //   y                      base.ifft_scaled_many(first_advice, all witness-dependent columns, ..): lagrange_to_coeff in place, one call
 //   quotient               base.coeff_to_extended_many(.., &ext, ..) for the witness-dependent columns; DevCols::eval_rows(&quotient_program, all
 //                          columns of ext, extended_k, &h, 0); h.quotient_to_coeff(..) (divide_by_vanishing_poly + extended_to_coeff);

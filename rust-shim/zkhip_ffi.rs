@@ -80,6 +80,11 @@ extern "C" {
                                     d_z: *mut c_void, stream: *mut c_void) -> c_int;
     fn zkhip_fr_eval_polynomial_batch_device(d_polys: *const *const c_void, count: usize, n: usize, point: *const u64, d_out: *mut c_void,
                                              stream: *mut c_void) -> c_int;
+    // ---- random field elements drawn in HBM (zkhip.h "random field elements": one ChaCha20 block per element, addressed by index) ----------
+    fn zkhip_fr_random_device(seed: *const u8, stream_id: u64, first: u64, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn zkhip_fr_random(seed: *const u8, stream_id: u64, first: u64, n: usize, out: *mut u64) -> c_int;
+    fn zkhip_fr_random_rows_device(seed: *const u8, stream_id: u64, first: u64, d_cols: *const *const c_void,
+                                   n_cols: u32, row0: usize, count: usize, stream: *mut c_void) -> c_int;
 }
 
 /// `zkhip_vm_operand` / `zkhip_vm_insn` / `zkhip_vm_program` of include/zkhip.h (field order and widths checked by tests/test_rust_shim.py).
@@ -394,6 +399,14 @@ pub(crate) fn try_coeff_to_extended_many<F: 'static + Clone>(columns: &[&[F]], k
     }).collect())
 }
 
+/// The seed of one proof's device-side randomness: 32 bytes from the prover's OWN generator (`create_proof`'s `rng`).  The library holds no
+/// entropy; blinding is as secret as these bytes, and a (seed, stream_id, index) triple is never used for two proofs -- draw a fresh seed per proof.
+pub(crate) fn random_seed<R: rand_core::RngCore>(rng: &mut R) -> [u8; 32] {
+    let mut seed = [0u8; 32];
+    rng.fill_bytes(&mut seed);
+    seed
+}
+
 // ======================================================================================================================================
 // prover_patch.rs, mode (b): device-resident columns.  A `DevCols` is `count` columns of `len` field elements in ONE zkhip_alloc'd block
 // (column i at element offset i * len): what `Vec<Polynomial<Fr, _>>` becomes while a proof is in flight.  Only commitments (96 bytes) and
@@ -419,7 +432,7 @@ impl DevCols {
         debug_assert!(col < self.count && row <= self.len);
         (self.ptr as usize + (col * self.len + row) * 32) as *mut c_void
     }
-    /// host slice -> rows [row, row + src.len()) of column `col` (the witness going up; the blinding rows of a product)
+    /// host slice -> rows [row, row + src.len()) of column `col` (the witness going up)
     pub(crate) fn upload<F: 'static>(&self, col: usize, row: usize, src: &[F]) -> bool {
         if !is::<F, Fr>() || row + src.len() > self.len { return false; }
         // SAFETY: src = &[Fr]; the destination range was checked
@@ -504,7 +517,7 @@ impl DevCols {
     /// every set's product column of the permutation argument in ONE call (`permutation::Argument::commit`'s loop over
     /// `columns.chunks(chunk_len)`): `values[c]` / `sigmas[c]` = device addresses of permutation column c and of its sigma column in the
     /// Lagrange basis; columns [z_first, z_first + ceil(columns / chunk_len)) of self receive z, chained through z[usable_rows]; the
-    /// caller then uploads its blinding rows behind usable_rows as upstream does
+    /// caller then draws its blinding rows behind usable_rows with `blind_rows`
     pub(crate) fn permutation_products<F: 'static>(&self, z_first: usize, values: &[*const c_void], sigmas: &[*const c_void], chunk_len: usize, log_n: u32,
                                                    usable_rows: usize, beta: &F, gamma: &F, delta: &F, omega: &F) -> bool {
         let sets = (values.len() + chunk_len.max(1) - 1) / chunk_len.max(1);
@@ -544,7 +557,7 @@ impl DevCols {
         rc == 0
     }
     /// every lookup's product column in one call (`lookup::prover::commit_product`): columns [z_first, z_first + lookups) of self receive z from the
-    /// permuted pairs in columns [pin_first, ..) / [ptab_first, ..); the caller then uploads its blinding rows behind usable_rows
+    /// permuted pairs in columns [pin_first, ..) / [ptab_first, ..); the caller then draws its blinding rows behind usable_rows (`blind_rows`)
     pub(crate) fn lookup_products<F: 'static>(&self, z_first: usize, inputs: &[*const c_void], tables: &[*const c_void], pin_first: usize, ptab_first: usize,
                                               log_n: u32, usable_rows: usize, beta: &F, gamma: &F) -> bool {
         let l = inputs.len();
@@ -554,6 +567,26 @@ impl DevCols {
         let rc = unsafe { zkhip_lookup_products_device(inputs.as_ptr(), tables.as_ptr(), self.at(pin_first, 0), self.at(ptab_first, 0), l as u32, log_n, usable_rows,
                                                        beta as *const F as *const u64, gamma as *const F as *const u64, self.at(z_first, 0), std::ptr::null_mut()) };
         if rc != 0 { warn_once("zkhip_lookup_products_device", rc); }
+        rc == 0
+    }
+    /// rows [0, n) of column `col` = elements first .. first + n - 1 of stream (seed, stream_id) (zkhip.h "random field elements"): the vanishing
+    /// argument's random polynomial, drawn where it is committed and opened.  `seed` = `random_seed(&mut rng)`, once per proof
+    pub(crate) fn fill_random(&self, col: usize, n: usize, seed: &[u8; 32], stream_id: u64, first: u64) -> bool {
+        if col >= self.count || n > self.len { return false; }
+        // SAFETY: n elements of a column this handle owns; the seed is read before the call returns
+        let rc = unsafe { zkhip_fr_random_device(seed.as_ptr(), stream_id, first, n, self.at(col, 0), std::ptr::null_mut()) };
+        if rc != 0 { warn_once("zkhip_fr_random_device", rc); }
+        rc == 0
+    }
+    /// the blinding tails of columns [first_col, first_col + n_cols) in ONE call: row row0 + j of the c-th of them = element
+    /// first + c * count + j of stream (seed, stream_id); no other row is touched.  The caller advances `first` by n_cols * count from one
+    /// call of a proof to the next (or gives every call a stream_id of its own): an index is used once
+    pub(crate) fn blind_rows(&self, first_col: usize, n_cols: usize, row0: usize, count: usize, seed: &[u8; 32], stream_id: u64, first: u64) -> bool {
+        if first_col + n_cols > self.count || row0 + count > self.len { return false; }
+        let cols: Vec<*const c_void> = (0..n_cols).map(|c| self.at(first_col + c, 0) as *const c_void).collect();
+        // SAFETY: every column holds row0 + count rows (checked); the seed and the address array are read before the call returns
+        let rc = unsafe { zkhip_fr_random_rows_device(seed.as_ptr(), stream_id, first, cols.as_ptr(), n_cols as u32, row0, count, std::ptr::null_mut()) };
+        if rc != 0 { warn_once("zkhip_fr_random_rows_device", rc); }
         rc == 0
     }
     /// h(X) (X^n - 1) evaluations in column `col` -> divided by the vanishing polynomial -> `out_len` coefficients in column `out_col` of `out`

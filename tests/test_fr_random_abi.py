@@ -1,0 +1,110 @@
+"""CPU: `zkhip_fr_random_device` / `zkhip_fr_random` / `zkhip_fr_random_rows_device` are declared the same way everywhere they are declared -- the
+header, the ctypes table, the C++ mirror and the Rust shim -- libzkhip.so exports all three, and the prover's step list draws its blinding rows
+and the vanishing argument's random polynomial through them."""
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("zkhip_fr_random_device", "zkhip_fr_random", "zkhip_fr_random_rows_device")
+HEADER = {
+    NAMES[0]: ["const uint8_t seed[32]", "uint64_t stream_id", "uint64_t first", "size_t n", "void *d_out", "void *stream"],
+    NAMES[1]: ["const uint8_t seed[32]", "uint64_t stream_id", "uint64_t first", "size_t n", "uint64_t *out"],
+    NAMES[2]: ["const uint8_t seed[32]", "uint64_t stream_id", "uint64_t first", "const void *const *d_cols", "uint32_t n_cols", "size_t row0", "size_t count",
+               "void *stream"],
+}
+RUST = {
+    NAMES[0]: ["seed: *const u8", "stream_id: u64", "first: u64", "n: usize", "d_out: *mut c_void", "stream: *mut c_void"],
+    NAMES[1]: ["seed: *const u8", "stream_id: u64", "first: u64", "n: usize", "out: *mut u64"],
+    NAMES[2]: ["seed: *const u8", "stream_id: u64", "first: u64", "d_cols: *const *const c_void", "n_cols: u32", "row0: usize", "count: usize", "stream: *mut c_void"],
+}
+MIRRORS = {NAMES[0]: "random_fr_device", NAMES[1]: "random_fr", NAMES[2]: "blind_rows_device"}
+
+
+def _header():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zkhip.h")).read(), flags=re.S)
+
+
+def _header_params(name):
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^;{]*?)\)\s*;", _header(), flags=re.S)
+    assert m, f"include/zkhip.h does not declare {name}"
+    return [" ".join(p.split()) for p in m.group(1).split(",")]
+
+
+def test_header_declares_the_three_calls():
+    for name in NAMES:
+        assert _header_params(name) == HEADER[name]
+
+
+def test_header_states_the_stream():
+    """the definition of the stream is the contract: the header carries the layout, the reduction, the storage format and the first pin"""
+    text = " ".join(open(os.path.join(ROOT, "include", "zkhip.h")).read().replace("\n *", " ").split())
+    for needle in ("expand 32-byte k", "64-bit block counter", "little-endian 512-bit integer", "mod r", "Montgomery-256", "RFC 8439",
+                   "25312d9be543d4c7a1d921e13f01589a414c389165c4cad2b5e970bf8f628f64", "holds no entropy", "never reused"):
+        assert needle in text, needle
+
+
+def test_ctypes_table_agrees_with_the_header():
+    import ctypes as C
+
+    from zksnap_circuits_halo2_amd import _lib
+
+    for name in NAMES:
+        res, args = _lib._SIGS[name]
+        params = _header_params(name)
+        assert res is C.c_int and len(args) == len(params), name
+        for ty, p in zip(args, params):
+            want = C.c_void_p if ("*" in p or "[" in p) else {"size_t": C.c_size_t, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}[p.split()[0]]
+            assert ty is want, (name, p)
+
+
+def test_cpp_mirror_and_rust_shim_agree_with_the_header():
+    hpp = open(os.path.join(ROOT, "include", "zkhip.hpp")).read()
+    for name in NAMES:
+        assert re.search(r"inline [\w:<> ]+ " + MIRRORS[name] + r"\(", hpp), f"include/zkhip.hpp has no {MIRRORS[name]}"
+        calls = list(re.finditer(r"\b" + name + r"\(", hpp))
+        assert calls, f"include/zkhip.hpp never calls {name}"
+        for m in calls:                      # the calls of the mirror pass as many arguments as the header declares
+            depth, i, args = 1, m.end(), 1
+            while depth:
+                ch = hpp[i]
+                depth += ch in "([{"
+                depth -= ch in ")]}"
+                args += ch == "," and depth == 1
+                i += 1
+            assert args == len(_header_params(name)), (name, args)
+    ffi = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "rust-shim", "zkhip_ffi.rs")).read())
+    for name in NAMES:
+        m = re.search(r"fn\s+" + name + r"\s*\((.*?)\)\s*->\s*c_int\s*;", ffi, flags=re.S)
+        assert m, f"rust-shim/zkhip_ffi.rs does not declare {name}"
+        assert [" ".join(p.split()) for p in m.group(1).split(",")] == RUST[name]
+    methods = set(re.findall(r"pub\(crate\) fn (\w+)", re.search(r"impl DevCols \{.*?\n\}", ffi, flags=re.S).group(0)))
+    assert {"fill_random", "blind_rows"} <= methods
+    assert re.search(r"pub\(crate\) fn random_seed<R: rand_core::RngCore>\(rng: &mut R\) -> \[u8; 32\]", ffi)      # the seed comes from the prover's own rng
+    from zksnap_circuits_halo2_amd import arithmetic as A
+    from zksnap_circuits_halo2_amd import evaluation as E
+
+    assert callable(A.random_fr) and callable(E.random_fr_device) and callable(E.blind_rows_device)
+
+
+def test_prover_step_list_draws_its_randomness_on_the_device():
+    patch = open(os.path.join(ROOT, "rust-shim", "prover_patch.rs")).read()
+    assert "base.blind_rows(" in patch and "base.fill_random(" in patch
+    assert "zkhip_ffi::random_seed(&mut rng)" in patch
+    steps = patch[patch.index("// The order of `create_proof` is unchanged"):patch.index("pub(crate) enum OpenWith")]
+    vanishing = steps[steps.index("vanishing random poly"):steps.index("//   y  ")]
+    assert "base.fill_random(" in vanishing and "commit_many(" in vanishing and "&params.g," in vanishing
+    assert "host" not in vanishing                                              # no host copy remains
+    assert "blinding rows uploaded" not in steps and "random_rows" not in steps
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    assert patch.rstrip() in doc
+
+
+def test_library_exports_the_three_calls(lib):
+    for name in NAMES:
+        assert hasattr(lib, name), f"libzkhip.so does not export {name}"
+    from zksnap_circuits_halo2_amd import _lib
+
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.split()}
+    assert set(NAMES) <= exported

@@ -14,7 +14,10 @@ with `calculate_params(Some(20))` (/root/reference/voter/benches/voter_circuit.r
 /root/reference/voter/frontend/app/worker.js:95-102): `run(13, 256, lookups=8)` and `run(15, 64, lookups=8)` are those shapes, with all
 the columns of a phase committed through ONE batched call (`zkhip_msm_g1_registered_batch_device`) as a Rust host would have to.  Checks (the prover's own invariants): both
 grand products close, the quotient is a polynomial (coefficients of degree >= 3n vanish), commit_lagrange(column) = commit(coefficients).
-There is no transcript: challenges are seeded.  Usage: prove_flow.py [k] [gate_cols] [lookups]   (default 16 4 1)."""
+There is no transcript: challenges are seeded.  Usage: prove_flow.py [k] [gate_cols] [lookups] [--device-randomness]   (default 16 4 1).
+--device-randomness (run(device_randomness=True)): every blinding tail is drawn by zkhip_fr_random_rows_device, all columns of a step in one
+call, and the vanishing argument's random polynomial is filled by zkhip_fr_random_device and committed (lap `vanishing_random_poly`); the
+default flow draws its blinding rows with torch and has no such lap."""
 import ctypes as C
 import os
 import random
@@ -36,8 +39,10 @@ _SIDE_STREAM = None
 
 
 def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False,
-        sharded_key=False, lookups_one_call=True):
-    """lookups_one_call: the lookup argument of every lookup through zkhip_lookup_permute_many_device + zkhip_lookup_products_device (two calls per
+        sharded_key=False, lookups_one_call=True, device_randomness=False):
+    """device_randomness: blinding tails through E.blind_rows_device (one call per step, whatever the number of columns) and the vanishing argument's
+    random polynomial through E.random_fr_device + a commit against params.g (lap vanishing_random_poly); the seed of the stream comes from `seed`.
+    lookups_one_call: the lookup argument of every lookup through zkhip_lookup_permute_many_device + zkhip_lookup_products_device (two calls per
     proof); False: one lookup at a time (the single-lookup call, two row programs and a grand product each).  The same bytes either way.
     corrupt: "gate" / "copy" break the witness; "lookup" puts a value outside the table into lookup column 1 (ZkhipError from the lookup phase).
     sharded_quotient: the single-program quotient goes through zkhip_fr_eval_rows_sharded_device (rows cut over the devices of zkhip_init; the
@@ -81,6 +86,13 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
         a = torch.randint(-(1 << 63), (1 << 63) - 1, (m, 4), dtype=torch.int64, device=dev)
         a[:, 3] = torch.randint(0, 1 << 61, (m,), dtype=torch.int64, device=dev)
         return a
+
+    dr_seed = random.Random(seed ^ 0xB11D).randbytes(32)      # a real prover takes these 32 bytes from its own generator, once per proof
+    dr_next = [0]                                            # stream indices handed out so far: an index is used once
+
+    def blind(cols, row0):               # device_randomness: rows row0 .. n - 1 of every column in one call
+        E.blind_rows_device(cols, row0, n - row0, dr_seed, first=dr_next[0])
+        dr_next[0] += len(cols) * (n - row0)
 
     def run_prog(prog, cols, log_rows, out=None):
         if out is None:
@@ -146,7 +158,8 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
         lks = []
         for _ in range(NL):
             lk = small_ints(torch.randint(0, 1 << lookup_bits, (n,), dtype=torch.int64, device=dev))
-            lk[u:] = rand_fr(n - u)
+            if not device_randomness:
+                lk[u:] = rand_fr(n - u)
             lks.append(lk)
             advice.append(lk)
         FC = G + NL                                                                # index of the constants column among the permutation columns
@@ -174,6 +187,8 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             advice[0][21] = advice[0][22].clone()
         if corrupt == "lookup":
             lks[1][3] = small_ints(torch.full((n,), 1 << lookup_bits, dtype=torch.int64, device=dev))[3]      # one value outside the table
+        if device_randomness:
+            blind(advice, u)
         lap("witness_columns")
         adv_commit = commit_all(h_gl, advice)                                       # advice is committed in the Lagrange basis
         lap("commit_advice")
@@ -234,8 +249,11 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
         _lib.check(lib.zkhip_permutation_products_device(vptr, sptr, npc, cs.chunk_len, k, u, *[c_.ctypes.data for c_ in pconsts], z_all.data_ptr(), None))
         z_sets = [z_all[si] for si in range(nsets_)]
         perm_closes = F.fr_decode(z_all[nsets_ - 1, u:u + 1].cpu().numpy().view(np.uint64))[0] == 1
-        for z in z_sets:
-            z[u + 1:] = rand_fr(n - u - 1)                                         # blinding rows
+        if device_randomness:
+            blind(z_sets, u + 1)
+        else:
+            for z in z_sets:
+                z[u + 1:] = rand_fr(n - u - 1)                                     # blinding rows
         lap("permutation_products")
 
         # ---- lookup argument ---------------------------------------------------------------------------------------------------
@@ -244,27 +262,45 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             # both phases of every lookup in one call each; the blinding rows are drawn in the per-lookup order of the loop below (pa, ps, z tail)
             pa_all, ps_all = torch.empty((NL, n, 4), dtype=torch.int64, device=dev), torch.empty((NL, n, 4), dtype=torch.int64, device=dev)
             tails = []
-            for j in range(NL):
-                pa_all[j], ps_all[j] = rand_fr(n), rand_fr(n)                      # rows >= u stay random (blinding)
-                tails.append(rand_fr(n - u - 1))
+            if device_randomness:
+                blind([pa_all[j] for j in range(NL)] + [ps_all[j] for j in range(NL)], u)
+            else:
+                for j in range(NL):
+                    pa_all[j], ps_all[j] = rand_fr(n), rand_fr(n)                  # rows >= u stay random (blinding)
+                    tails.append(rand_fr(n - u - 1))
             E.permute_expression_pairs_device(lks, [table] * NL, u, k, pa_all, ps_all)
             z_lk = E.lookup_products_device(lks, [table] * NL, pa_all, ps_all, u, k, beta, gamma)
             lookup_closes = all(v_ == 1 for v_ in F.fr_decode(z_lk[:, u].contiguous().cpu().numpy().view(np.uint64)))
+            if device_randomness:
+                blind([z_lk[j] for j in range(NL)], u + 1)
             for j in range(NL):
-                z_lk[j, u + 1:] = tails[j]
+                if not device_randomness:
+                    z_lk[j, u + 1:] = tails[j]
                 lookup_cols += [z_lk[j], pa_all[j], ps_all[j]]
         else:
             pn, pd = E.lookup_product_programs(1, 1, beta, gamma, theta)
             for lk in lks:
-                pa, ps = rand_fr(n), rand_fr(n)                                     # rows >= u stay random (blinding)
+                if device_randomness:
+                    pa, ps = (torch.empty((n, 4), dtype=torch.int64, device=dev) for _ in range(2))
+                    blind([pa, ps], u)
+                else:
+                    pa, ps = rand_fr(n), rand_fr(n)                                 # rows >= u stay random (blinding)
                 _lib.check(lib.zkhip_lookup_permute_device(lk.data_ptr(), table.data_ptr(), u, pa.data_ptr(), ps.data_ptr(), None))
                 zl = run_prog(pn, [lk, table], k)
                 den = run_prog(pd, [pa, ps], k)
                 _lib.check(lib.zkhip_fr_grand_product_device(zl.data_ptr(), den.data_ptr(), n, zl.data_ptr(), None))
                 lookup_closes = lookup_closes and F.fr_decode(zl[u].cpu().numpy().view(np.uint64))[0] == 1
-                zl[u + 1:] = rand_fr(n - u - 1)
+                if device_randomness:
+                    blind([zl], u + 1)
+                else:
+                    zl[u + 1:] = rand_fr(n - u - 1)
                 lookup_cols += [zl, pa, ps]
         lap("lookup_permute_and_product")
+        if device_randomness:
+            # the vanishing argument's random polynomial: n coefficients of stream 1, drawn where they are committed (and later opened)
+            random_poly = E.random_fr_device(dr_seed, n, stream_id=1)
+            random_poly_commit = commit(h_g, random_poly)
+            lap("vanishing_random_poly")
 
         # ---- Lagrange -> coefficients, commitments, extended coset ---------------------------------------------------------------
         l0 = torch.zeros((n, 4), dtype=torch.int64, device=dev); l0[0] = ONE
@@ -422,7 +458,8 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             print("  checks:", checks)
         return {"timings_ms": t, "prove_ms": prove_ms, "checks": checks, "columns": ncol, "proof_columns": n_proof_cols, "msms": n_msm, "queries": len(queries),
                 "program_insns": n_insns, "program_registers": n_regs, "h_commitments": [affine(c) for c in h_commit],
-                "keygen_ms": t.get("keygen_vk", 0.0) + t.get("keygen_pk", 0.0) + t.get("keygen_device", 0.0), "pk_file_bytes": pk_bytes}
+                "keygen_ms": t.get("keygen_vk", 0.0) + t.get("keygen_pk", 0.0) + t.get("keygen_device", 0.0), "pk_file_bytes": pk_bytes,
+                "vanishing_random_commitment": affine(random_poly_commit) if device_randomness else None}
     finally:
         torch.cuda.synchronize()
         if dpk is not None:
@@ -431,8 +468,10 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
 
 
 if __name__ == "__main__":
+    dr = "--device-randomness" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--device-randomness"]
     kk = int(sys.argv[1]) if len(sys.argv) > 1 else 16
     gg = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     ll = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-    res = run(kk, gg, lookups=ll)
+    res = run(kk, gg, lookups=ll, device_randomness=dr)
     sys.exit(0 if all(res["checks"].values()) else 1)

@@ -57,6 +57,9 @@ _SIGS = {
     "zkhip_lookup_permute_many_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_lookup_products_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p]),
+    "zkhip_fr_random_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zkhip_fr_random": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]),
+    "zkhip_fr_random_rows_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_size_t, C.c_size_t, C.c_void_p]),
     "zkhip_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "zkhip_free": (C.c_int, [C.c_void_p]),
     "zkhip_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

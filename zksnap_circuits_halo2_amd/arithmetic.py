@@ -75,3 +75,20 @@ def prefix_product(v: np.ndarray) -> np.ndarray:
     out = np.zeros_like(v)
     _lib.check(_lib.load().zkhip_fr_prefix_product(_ptr(v), v.shape[0], _ptr(out)))
     return out
+
+
+def _seed_bytes(seed) -> bytes:
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("the seed is 32 bytes")
+    return seed
+
+
+def random_fr(seed, n: int, first: int = 0, stream_id: int = 0) -> np.ndarray:
+    """Elements first .. first + n - 1 of the library's random stream (include/zkhip.h, "random field elements": one ChaCha20 block per
+    element, reduced mod r) -> (n,4) uint64 Fr.  `seed`: 32 bytes from the caller's own generator -- the library holds no entropy, and a
+    (seed, stream_id, index) triple is never reused across proofs."""
+    seed = _seed_bytes(seed)
+    out = np.zeros((n, 4), dtype=np.uint64)
+    _lib.check(_lib.load().zkhip_fr_random(seed, stream_id, first, n, _ptr(out)))
+    return out

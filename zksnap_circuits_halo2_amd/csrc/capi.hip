@@ -1860,6 +1860,46 @@ int zkhip_lookup_permute(const uint64_t* input, const uint64_t* table, size_t us
   return H.finish();
 }
 
+// ---- random field elements (fr_random.hpp, random.hip) ---------------------------------------------------------------
+// first + count > 2^64: the stream has no such index
+static inline bool random_range_ok(uint64_t first, uint64_t count) { return first == 0 || count <= (uint64_t)0 - first; }
+
+int zkhip_fr_random_device(const uint8_t seed[32], uint64_t stream_id, uint64_t first, size_t n, void* d_out, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if (n == 0) return ZKHIP_OK;
+  if (!seed || !d_out) { set_error("fr_random: null pointer"); return ZKHIP_EINVAL; }
+  if (!random_range_ok(first, n)) { set_error("fr_random: first + n exceeds 2^64"); return ZKHIP_EINVAL; }
+  return fr_random_device(seed, stream_id, first, n, (uint32_t*)d_out, caller_stream(stream));
+}
+
+int zkhip_fr_random_rows_device(const uint8_t seed[32], uint64_t stream_id, uint64_t first, const void* const* d_cols, uint32_t n_cols, size_t row0, size_t count,
+                                void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if (n_cols == 0 || count == 0) return ZKHIP_OK;
+  if (!seed || !d_cols) { set_error("fr_random_rows: null pointer"); return ZKHIP_EINVAL; }
+  for (uint32_t c = 0; c < n_cols; c++)
+    if (!d_cols[c]) { set_error("fr_random_rows: column %u is null", c); return ZKHIP_EINVAL; }
+  if (count > ((size_t)1 << 30) / n_cols) { set_error("fr_random_rows: %u columns x %zu rows exceed 2^30 elements", n_cols, count); return ZKHIP_EINVAL; }
+  if (!random_range_ok(first, (uint64_t)n_cols * count)) { set_error("fr_random_rows: first + n_cols * count exceeds 2^64"); return ZKHIP_EINVAL; }
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->ws.reserve(fr_random_rows_workspace_bytes(n_cols))) != ZKHIP_OK) return rc;
+  return fr_random_rows_device(seed, stream_id, first, d_cols, n_cols, row0, count, sc->ws.p, sc->ws.cap, s, &sc->args);
+}
+
+int zkhip_fr_random(const uint8_t seed[32], uint64_t stream_id, uint64_t first, size_t n, uint64_t* out) {
+  ZK_API_RANGE();
+  if (n == 0) return ZKHIP_OK;
+  if (!seed || !out) { set_error("fr_random: null pointer"); return ZKHIP_EINVAL; }
+  return host_vec_op(nullptr, 0, out, n, false, [&](void*, void* d_out, void* s) { return zkhip_fr_random_device(seed, stream_id, first, n, d_out, s); });
+}
+
 // ---- device buffers for hosts that do not link HIP -------------------------------------------------------------
 int zkhip_alloc(size_t bytes, void** d_ptr) {
   ZK_API_RANGE();

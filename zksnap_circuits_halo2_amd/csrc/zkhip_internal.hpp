@@ -210,6 +210,13 @@ size_t lookup_permute_many_workspace_bytes(uint32_t n_lookups, size_t usable_row
 int lookup_permute_many_device(const void* const* d_inputs_host, const void* const* d_tables_host, uint32_t n_lookups, size_t n, size_t usable_rows,
                                uint32_t* d_out_input, uint32_t* d_out_table, void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
 
+// random.hip: the random Fr stream of fr_random.hpp (include/zkhip.h, "random field elements").  `seed`: 32 bytes of host memory, read before the call returns
+int fr_random_device(const uint8_t seed[32], uint64_t stream_id, uint64_t first, size_t n, uint32_t* d_out, hipStream_t stream);
+// element first + c * count + j to row row0 + j of column c (n_cols device addresses in host memory), one launch; n_cols * count <= 2^30
+size_t fr_random_rows_workspace_bytes(uint32_t n_cols);
+int fr_random_rows_device(const uint8_t seed[32], uint64_t stream_id, uint64_t first, const void* const* d_cols_host, uint32_t n_cols, size_t row0, size_t count,
+                          void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
+
 // serde.hip
 int g1_compress_device(const uint32_t* d_points, size_t n, uint32_t* d_out, int layout, hipStream_t stream);
 int g1_decompress_device(const uint32_t* d_in, size_t n, uint32_t* d_points, int layout, unsigned long long* d_first_bad, hipStream_t stream);

@@ -698,6 +698,37 @@ def lookup_products_device(inputs, tables, permuted_inputs, permuted_tables, usa
     return z
 
 
+def random_fr_device(seed, n: int, first: int = 0, stream_id: int = 0, out=None, stream=None):
+    """Elements first .. first + n - 1 of the library's random stream (include/zkhip.h, "random field elements") written in HBM
+    (zkhip_fr_random_device): an (n, 4) int64 device tensor -- the vanishing argument's random polynomial without a host copy.  Asynchronous
+    on `stream`.  `seed`: 32 bytes from the caller's own generator; a (seed, stream_id, index) triple is never reused across proofs."""
+    import torch
+
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("the seed is 32 bytes")
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.int64, device="cuda")
+    if not out.is_cuda or not out.is_contiguous() or out.numel() < 4 * n:
+        raise ValueError("the output is a contiguous device tensor of at least n elements")
+    _lib.check(_lib.load().zkhip_fr_random_device(seed, stream_id, first, n, out.data_ptr(), stream))
+    return out
+
+
+def blind_rows_device(columns, row0: int, count: int, seed, first: int = 0, stream_id: int = 0, stream=None) -> None:
+    """The blinding tails of all `columns` in ONE call (zkhip_fr_random_rows_device): row row0 + j of columns[c] becomes element
+    first + c * count + j of the stream, j < count; no other row is touched.  columns: contiguous (rows, 4) int64 device tensors of at
+    least row0 + count rows.  Asynchronous on `stream`."""
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("the seed is 32 bytes")
+    for c in columns:
+        if not c.is_cuda or not c.is_contiguous() or c.numel() < 4 * (row0 + count):
+            raise ValueError("blinded columns are contiguous device tensors of at least row0 + count elements")
+    ptrs = (C.c_void_p * len(columns))(*[c.data_ptr() for c in columns])
+    _lib.check(_lib.load().zkhip_fr_random_rows_device(seed, stream_id, first, ptrs, len(columns), row0, count, stream))
+
+
 # ---------------------------------------------------------------------------------------------------
 # the row programs of one proof, written out for a host that is not Python (rust-shim/prover_patch.rs, tests/cpp/prover_sequence.c)
 # ---------------------------------------------------------------------------------------------------

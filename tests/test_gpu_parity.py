@@ -522,7 +522,7 @@ def test_sharded_msm_single_rank_gpu_path(cref):
 
 
 # ---------------------------------------------------------------- row a7: eval_polynomial, kate_division, batch_invert, grand product
-@pytest.mark.parametrize("n", [1, 2, 31, 32, 33, 1000, 1025, 32 * 32 + 1, 70000, 1 << 20])
+@pytest.mark.parametrize("n", [1, 2, 31, 32, 33, 1000, 1025, 32 * 32 + 1, 70000, 1 << 20, 17, 257, 65537])
 def test_row_a7_vs_reference_algorithm(cref, n):
     from zksnap_circuits_halo2_amd import arithmetic as A
 

@@ -219,7 +219,7 @@ def test_linear_combination_and_accumulate(lib):
     assert run_host(p, cols[:1], log_rows, prev) == [(a * x + b) % R for a, b in zip(prev, cols[0])]
 
 
-@pytest.mark.parametrize("n", [1, 2, 33, 1000, 4097, 1 << 16])
+@pytest.mark.parametrize("n", [1, 2, 33, 1000, 4097, 1 << 16, 17, 257, 65537])
 def test_grand_product_vs_reference_algorithm(lib, cref, n):
     num = cref.gen_scalars(900 + n, n, 0)
     den = cref.gen_scalars(901 + n, n, 0)

@@ -320,7 +320,7 @@ int fr_eval_polynomial_device(const uint32_t* d_a, size_t n, const uint32_t x_ho
 }
 
 // `count` polynomials of n coefficients each, all evaluated at x: d_results[p] = sum_i poly_p[i] x^i.  One launch per recursion
-// level for the whole batch (ceil(log_32 n) levels) instead of one recursion per polynomial.
+// level for the whole batch (ceil(log_16 n) levels) instead of one recursion per polynomial.
 size_t poly_batch_workspace_bytes(size_t n, size_t count) {
   size_t total = 8192 + ((count * 8 + 255) / 256) * 256, m = n;
   while (m > 1) { m = chunks_of(m); total += ((count * m * 32 + 255) / 256) * 256 + 256; }

@@ -357,6 +357,39 @@ int zkhip_lookup_products_device(const void *const *d_inputs, const void *const 
                                  uint32_t n_lookups, uint32_t log_n, size_t usable_rows, const uint64_t beta[4], const uint64_t gamma[4], void *d_z,
                                  void *stream);
 
+/* ---- witness checks: does this witness satisfy its circuit, and if not, where (MockProver) -----------------------------------------
+ * The reference never proves an unchecked witness: `gen_proof` runs `MockProver::run(k, &circuit, instances).assert_satisfied()` first
+ * (/root/reference/aggregator/src/wrapper.rs:117-123).  These three calls answer the same three questions -- every gate polynomial is zero
+ * on every usable row, every copy constraint holds, every lookup input occurs in its table -- as read-only passes over columns that are
+ * already in HBM for the proof.  Each question is reduced on the device to one record per item list:
+ *   failures  the number of failing items
+ *   first     the lowest failing index, UINT64_MAX when there is none
+ * a count and a minimum, so both are exact and do not depend on the launch geometry.  All three calls are asynchronous on `stream`,
+ * initialise their records themselves, read their columns only, wait for nothing on the host and return ZKHIP_OK when the check RAN,
+ * whatever it found: the caller reads the records back (zkhip_stream_sync + zkhip_download).  A satisfied witness costs no atomic.
+ * Argument errors are ZKHIP_EINVAL with nothing enqueued and the records untouched.  Records are 8-byte aligned device memory.
+ * Not covered: halo2's unassigned-cell (`Poison`) diagnostics, selector / region bookkeeping, row-shard sets, devices other than the stream's. */
+typedef struct zkhip_check_report { uint64_t failures; uint64_t first; } zkhip_check_report;   /* 16 bytes */
+/* Gates.  `n_progs` row programs (1 .. 65535), one per gate polynomial, rot_scale = 1, over the same whole-domain columns (2^log_rows
+ * elements each), side by side in ONE launch of the interpreter (one grid row per program; never the run-time compiler).  d_reports[p]
+ * counts the rows r in [row0, row0 + count) where program p's result is not zero; `first` is the lowest such row of the domain.  Rotations
+ * wrap modulo 2^log_rows as in the evaluator, ZKHIP_SRC_PREV reads 0, ZKHIP_SRC_ROWPOW is omega^r (programs that read it name one omega).
+ * ZKHIP_EINVAL: count == 0, row0 + count > 2^log_rows, n_progs == 0 or > 65535, a null pointer, a program zkhip_fr_eval_rows_device rejects. */
+int zkhip_check_rows_device(const zkhip_vm_program *progs, uint32_t n_progs, const void *const *d_columns, uint32_t n_columns,
+                            uint32_t log_rows, uint64_t row0, uint64_t count, void *d_reports, void *stream);
+/* Copy constraints.  d_map_col / d_map_row: [n_columns][2^log_n] u32 each (device), the permutation as `Assembly` keeps it: cell (c, r)
+ * maps to cell (map_col[c][r], map_row[c][r]).  A cell fails when its 32 bytes differ from those of the cell it maps to; item index
+ * c 2^log_n + r.  Map entries are reduced modulo n_columns / 2^log_n, not trusted (as in zkhip_fr_gather_mul_device).  One record.
+ * ZKHIP_EINVAL: n_columns == 0 or > 4096, log_n > 28, n_columns 2^log_n >= 2^39, a null pointer. */
+int zkhip_check_copies_device(const void *const *d_columns, uint32_t n_columns, uint32_t log_n, const void *d_map_col, const void *d_map_row,
+                              void *d_report, void *stream);
+/* Lookup membership, arguments as zkhip_lookup_permute_many_device: compressed input / table columns, equal table addresses are one table
+ * and are sorted once, only rows < usable_rows of either side count.  Row i of lookup l fails when input_l[i] equals no table_l[j],
+ * j < usable_rows; d_reports[l].  n_lookups == 0 or usable_rows == 0: ZKHIP_OK, the n_lookups records say "no failure".
+ * ZKHIP_EINVAL: n_lookups > 1365, log_n > 28, usable_rows > 2^log_n, a null pointer. */
+int zkhip_check_lookups_device(const void *const *d_inputs, const void *const *d_tables, uint32_t n_lookups, uint32_t log_n,
+                               size_t usable_rows, void *d_reports, void *stream);
+
 /* ---- random field elements: blinding rows and the vanishing argument's random polynomial, drawn in HBM ---------------------------
  * A cryptographic, reproducible stream of Fr elements addressed by index.  THE STREAM (normative): element i of stream (seed, stream_id) is
  *   1. one ChaCha20 block of 20 rounds in the original layout with a 64-bit block counter: words 0..3 are "expand 32-byte k" (0x61707865,

@@ -1172,6 +1172,66 @@ inline void lookup_products_device(const std::vector<const DeviceVec*>& inputs, 
   check(zkhip_lookup_products_device(in.data(), tab.data(), permuted_inputs.data(), permuted_tables.data(), (uint32_t)in.size(), k, usable_rows, beta.l, gamma.l, z.data(), nullptr),
         "lookup_products_device");
 }
+// The witness checks (zkhip.h, "witness checks"): MockProver's three questions over columns that are already in HBM.  Each returns the
+// records read back: failures = the number of failing items, first = the lowest failing index (UINT64_MAX: none).  They throw only when the
+// check could not run.
+inline std::vector<zkhip_check_report> read_check_reports(const std::function<int(void*)>& enqueue, size_t count, const char* what) {
+  std::vector<zkhip_check_report> out(count);
+  if (count == 0) return out;
+  void* d = nullptr;
+  check(zkhip_alloc(count * sizeof(zkhip_check_report), &d), what);
+  int rc = enqueue(d);
+  if (rc == ZKHIP_OK) rc = zkhip_stream_sync(nullptr);
+  if (rc == ZKHIP_OK) rc = zkhip_download(out.data(), d, count * sizeof(zkhip_check_report));
+  (void)zkhip_free(d);
+  check(rc, what);
+  return out;
+}
+inline zkhip_vm_program vm_program_of(const RowProgram& r) {
+  zkhip_vm_program p{};
+  p.insns = r.insns.data(); p.n_insns = (uint32_t)r.insns.size();
+  p.constants = r.constants.empty() ? nullptr : r.constants.data()->l; p.n_constants = (uint32_t)r.constants.size();
+  p.rotations = r.rotations.data(); p.n_rotations = (uint32_t)r.rotations.size();
+  p.rot_scale = r.rot_scale; p.result_reg = r.result_reg;
+  p.omega = r.uses_omega ? r.omega.l : nullptr;
+  return p;
+}
+// gates: one program per gate polynomial over whole-domain columns; report p counts the rows of [row0, row0 + count) where program p is not zero
+inline std::vector<zkhip_check_report> check_rows_device(const std::vector<RowProgram>& gates, const std::vector<const DeviceVec*>& columns, uint32_t k, uint64_t row0,
+                                                         uint64_t count) {
+  std::vector<zkhip_vm_program> progs;
+  for (const RowProgram& g : gates) progs.push_back(vm_program_of(g));
+  std::vector<const void*> ptrs;
+  for (const DeviceVec* c : columns) {
+    if (c->size() < ((size_t)1 << k)) throw std::invalid_argument("check_rows_device: column shorter than 2^k");
+    ptrs.push_back(c->data());
+  }
+  return read_check_reports([&](void* d) {
+    return zkhip_check_rows_device(progs.data(), (uint32_t)progs.size(), ptrs.data(), (uint32_t)ptrs.size(), k, row0, count, d, nullptr); }, progs.size(), "check_rows_device");
+}
+// copy constraints: d_map_col / d_map_row are [columns][2^k] u32 in HBM (permutation::keygen::Assembly's mapping); item index = column 2^k + row
+inline zkhip_check_report check_copies_device(const std::vector<const DeviceVec*>& columns, uint32_t k, const void* d_map_col, const void* d_map_row) {
+  std::vector<const void*> ptrs;
+  for (const DeviceVec* c : columns) {
+    if (c->size() < ((size_t)1 << k)) throw std::invalid_argument("check_copies_device: column shorter than 2^k");
+    ptrs.push_back(c->data());
+  }
+  return read_check_reports([&](void* d) {
+    return zkhip_check_copies_device(ptrs.data(), (uint32_t)ptrs.size(), k, d_map_col, d_map_row, d, nullptr); }, 1, "check_copies_device")[0];
+}
+// lookup membership over the usable rows, arguments as permute_expression_pairs_device (compressed columns; a shared table is sorted once)
+inline std::vector<zkhip_check_report> check_lookups_device(const std::vector<const DeviceVec*>& inputs, const std::vector<const DeviceVec*>& tables, uint32_t k,
+                                                            size_t usable_rows) {
+  if (inputs.size() != tables.size()) throw std::invalid_argument("check_lookups_device: inputs.len() != tables.len()");
+  std::vector<const void*> in, tab;
+  for (size_t l = 0; l < inputs.size(); l++) {
+    if (inputs[l]->size() < usable_rows || tables[l]->size() < usable_rows) throw std::invalid_argument("check_lookups_device: usable_rows > len");
+    in.push_back(inputs[l]->data());
+    tab.push_back(tables[l]->data());
+  }
+  return read_check_reports([&](void* d) {
+    return zkhip_check_lookups_device(in.data(), tab.data(), (uint32_t)in.size(), k, usable_rows, d, nullptr); }, in.size(), "check_lookups_device");
+}
 // Random field elements drawn in HBM (zkhip.h, "random field elements": element i of stream (seed, stream_id) is one ChaCha20 block reduced mod r).
 // The library holds no entropy: `seed` comes from the caller's generator, and a (seed, stream_id, index) triple is never reused across proofs.
 // out[j] = element first + j for every j < out.size(): the vanishing argument's random polynomial, never on the host

@@ -25,7 +25,8 @@
 //! include/zkhip.h, the `repr(C)` program structs agree with the header's structs field by field, and the call sequence of both modes
 //! runs on the GPU from C99 with every commitment compared (tests/cpp/prover_sequence.c, tests/test_gpu_prover_sequence.py).
 
-use crate::zkhip_ffi::{self, DevCols, VmInsn, VmOperand, VmProgramOwned};
+use crate::zkhip_ffi::{self, CheckReport, DevCols, VmInsn, VmOperand, VmProgramOwned};
+use std::os::raw::c_void;
 
 // ======================================================================================================================================
 // (a) one call per phase, host buffers
@@ -273,3 +274,56 @@ pub(crate) fn lower_graph(calcs: &[Calc], constants: Vec<[u64; 4]>, rotations: V
 //         // the caller (vanishing::Committed::construct) then calls dp.h.quotient_to_coeff(..) instead of
 //         // domain.divide_by_vanishing_poly + domain.extended_to_coeff
 //     }
+
+// ======================================================================================================================================
+// MockProver on the device (opt-in)
+// ======================================================================================================================================
+//
+// The reference checks every witness before it proves it: `gen_proof` runs `MockProver::run(k, &circuit, instances).assert_satisfied()`
+// whenever k > 3 (/root/reference/aggregator/src/wrapper.rs:117-123), a walk over every gate, copy constraint and lookup of 2^k rows on CPU
+// threads, after which the same columns are uploaded and proven.  A host on mode (b) can ask the three questions of the columns where they
+// already lie -- opt-in, `std::env::var_os("ZKHIP_MOCK_ON_DEVICE").is_some()`, at the place of that `MockProver::run` (or, inside
+// `create_proof`, right after `base.upload(..)` of the last advice phase and before the first commitment):
+//
+//     if let Some(failures) = mock_on_device(&gate_programs, &columns, &perm_columns, map.at(0, 0), map.at(1, 0), &lookup_inputs, &lookup_tables,
+//                                            k, usable_rows) {
+//         assert!(failures.is_empty(), "circuit was not satisfied: {:?}", failures);     // what assert_satisfied() does
+//     }                                                                                   // None: the device path declined, run MockProver
+//
+//   gate_programs   one `lower_graph(.., rot_scale = 1, ..)` per polynomial of every gate over the base domain (no y-fold, no Horner over gates:
+//                   a failure is located by its polynomial), sources mapped to `columns` = fixed | advice | instance of `base`
+//   perm_columns    the permutation's columns in `cs.permutation.columns` order; `map` = a DevCols of 2 columns holding `Assembly::mapping` split
+//                   into [column][row] u32 arrays of target columns and target rows (uploaded once per proving key, next to sigma)
+//   lookups         the compressed input / table expressions the lookup phase needs anyway (theta must exist: inside create_proof the check of the
+//                   lookups runs after theta is squeezed; a lookup of one plain column per side needs no theta and is exact)
+// Gates are checked on rows [0, usable_rows), copies on all rows, lookups on the usable rows.  Not covered: MockProver's unassigned-cell
+// (`Poison`) diagnostics, selector / region bookkeeping in the failure's location, row-shard sets and devices other than the stream's.
+#[derive(Debug)]
+pub(crate) enum MockFailure {
+    /// program `index` of `gate_programs` is not zero on `failures` rows, the first of them `row`
+    Gate { index: usize, row: u64, failures: u64 },
+    /// `failures` cells differ from the cell they are constrained to equal, the lowest of them (`column` of the permutation, `row`)
+    Copy { column: u64, row: u64, failures: u64 },
+    /// `failures` rows of lookup `index` hold a value its table does not, the first of them `row`
+    Lookup { index: usize, row: u64, failures: u64 },
+}
+
+pub(crate) fn mock_on_device(gate_programs: &[VmProgramOwned], columns: &[*const c_void], perm_columns: &[*const c_void], map_col: *const c_void,
+                             map_row: *const c_void, lookup_inputs: &[*const c_void], lookup_tables: &[*const c_void], k: u32, usable_rows: usize)
+                             -> Option<Vec<MockFailure>> {
+    let mut out = Vec::new();
+    let failing = |r: &CheckReport| r.failures != 0;
+    if !gate_programs.is_empty() {
+        for (index, r) in DevCols::check_rows(gate_programs, columns, k, 0, usable_rows as u64)?.iter().enumerate() {
+            if failing(r) { out.push(MockFailure::Gate { index, row: r.first, failures: r.failures }); }
+        }
+    }
+    if !perm_columns.is_empty() {
+        let r = DevCols::check_copies(perm_columns, k, map_col, map_row)?;
+        if failing(&r) { out.push(MockFailure::Copy { column: r.first >> k, row: r.first & ((1u64 << k) - 1), failures: r.failures }); }
+    }
+    for (index, r) in DevCols::check_lookups(lookup_inputs, lookup_tables, k, usable_rows)?.iter().enumerate() {
+        if failing(r) { out.push(MockFailure::Lookup { index, row: r.first, failures: r.failures }); }
+    }
+    Some(out)
+}

@@ -78,6 +78,14 @@ extern "C" {
     fn zkhip_lookup_products_device(d_inputs: *const *const c_void, d_tables: *const *const c_void, d_permuted_inputs: *const c_void,
                                     d_permuted_tables: *const c_void, n_lookups: u32, log_n: u32, usable_rows: usize, beta: *const u64, gamma: *const u64,
                                     d_z: *mut c_void, stream: *mut c_void) -> c_int;
+    // ---- witness checks (zkhip.h "witness checks"): MockProver's three questions over columns that are already in HBM ----------------------
+    fn zkhip_check_rows_device(progs: *const VmProgram, n_progs: u32, d_columns: *const *const c_void, n_columns: u32, log_rows: u32, row0: u64, count: u64,
+                               d_reports: *mut c_void, stream: *mut c_void) -> c_int;
+    fn zkhip_check_copies_device(d_columns: *const *const c_void, n_columns: u32, log_n: u32, d_map_col: *const c_void, d_map_row: *const c_void,
+                                 d_report: *mut c_void, stream: *mut c_void) -> c_int;
+    fn zkhip_check_lookups_device(d_inputs: *const *const c_void, d_tables: *const *const c_void, n_lookups: u32, log_n: u32, usable_rows: usize,
+                                  d_reports: *mut c_void, stream: *mut c_void) -> c_int;
+    fn zkhip_stream_sync(stream: *mut c_void) -> c_int;
     fn zkhip_fr_eval_polynomial_batch_device(d_polys: *const *const c_void, count: usize, n: usize, point: *const u64, d_out: *mut c_void,
                                              stream: *mut c_void) -> c_int;
     // ---- random field elements drawn in HBM (zkhip.h "random field elements": one ChaCha20 block per element, addressed by index) ----------
@@ -108,6 +116,10 @@ pub(crate) struct VmProgram {
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub(crate) struct ProverQueryC { pub point: [u64; 4], pub d_poly: *const c_void, pub eval: [u64; 4], pub has_eval: u32, pub reserved: u32 }
+/// `zkhip_check_report`: what a witness check leaves per item list -- the number of failing items and the lowest failing index (u64::MAX: none)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub(crate) struct CheckReport { pub failures: u64, pub first: u64 }
 /// `zkhip_shplonk`: the state between the two steps of the SHPLONK prover (opaque)
 #[repr(C)]
 pub(crate) struct ShplonkState { _opaque: [u8; 0] }
@@ -568,6 +580,41 @@ impl DevCols {
                                                        beta as *const F as *const u64, gamma as *const F as *const u64, self.at(z_first, 0), std::ptr::null_mut()) };
         if rc != 0 { warn_once("zkhip_lookup_products_device", rc); }
         rc == 0
+    }
+    /// the records of a witness check, read back: `enqueue` gets the device address of `count` records, the stream is waited for once
+    fn check_reports(count: usize, what: &'static str, enqueue: impl FnOnce(*mut c_void) -> c_int) -> Option<Vec<CheckReport>> {
+        let mut out = vec![CheckReport { failures: 0, first: u64::MAX }; count];
+        if count == 0 { return Some(out); }
+        let recs = DevCols::alloc(1, (count + 1) / 2)?;          // 16 bytes per record
+        let mut rc = enqueue(recs.ptr);
+        // SAFETY: the default stream; out = Vec<CheckReport> of `count` records of 16 bytes
+        if rc == 0 { rc = unsafe { zkhip_stream_sync(std::ptr::null_mut()) }; }
+        if rc == 0 { rc = unsafe { zkhip_download(out.as_mut_ptr() as *mut c_void, recs.ptr, count * 16) }; }
+        if rc != 0 { warn_once(what, rc); return None; }
+        Some(out)
+    }
+    /// gates (`MockProver::verify`'s loop over `cs.gates`): one program per gate polynomial (rot_scale 1) over whole-domain `columns`; record p
+    /// counts the rows of [row0, row0 + count) where program p is not zero and names the first.  None = the check could not run
+    pub(crate) fn check_rows(progs: &[VmProgramOwned], columns: &[*const c_void], log_rows: u32, row0: u64, count: u64) -> Option<Vec<CheckReport>> {
+        let ffi: Vec<VmProgram> = progs.iter().map(|p| p.as_ffi()).collect();
+        // SAFETY: `ffi` borrows the Vecs of `progs`, alive for the call; columns are device addresses of 2^log_rows rows; `d` holds ffi.len() records
+        DevCols::check_reports(ffi.len(), "zkhip_check_rows_device", |d| unsafe {
+            zkhip_check_rows_device(ffi.as_ptr(), ffi.len() as u32, columns.as_ptr(), columns.len() as u32, log_rows, row0, count, d, std::ptr::null_mut()) })
+    }
+    /// copy constraints: `map_col` / `map_row` = device addresses of the permutation's mapping, [columns][2^log_n] u32 each (`Assembly::mapping`
+    /// split in two); the record counts the cells that differ from the cell they map to, `first` = column * 2^log_n + row of the lowest
+    pub(crate) fn check_copies(columns: &[*const c_void], log_n: u32, map_col: *const c_void, map_row: *const c_void) -> Option<CheckReport> {
+        // SAFETY: columns are device addresses of 2^log_n rows, the maps hold columns.len() * 2^log_n u32 each; `d` holds one record
+        DevCols::check_reports(1, "zkhip_check_copies_device", |d| unsafe {
+            zkhip_check_copies_device(columns.as_ptr(), columns.len() as u32, log_n, map_col, map_row, d, std::ptr::null_mut()) }).map(|v| v[0])
+    }
+    /// lookup membership over the usable rows: `inputs[l]` / `tables[l]` as for `lookup_permute_many` (compressed columns, a shared table is
+    /// sorted once); record l counts the rows whose input value the table does not hold
+    pub(crate) fn check_lookups(inputs: &[*const c_void], tables: &[*const c_void], log_n: u32, usable_rows: usize) -> Option<Vec<CheckReport>> {
+        if inputs.len() != tables.len() { return None; }
+        // SAFETY: device addresses of >= usable_rows rows each; `d` holds inputs.len() records
+        DevCols::check_reports(inputs.len(), "zkhip_check_lookups_device", |d| unsafe {
+            zkhip_check_lookups_device(inputs.as_ptr(), tables.as_ptr(), inputs.len() as u32, log_n, usable_rows, d, std::ptr::null_mut()) })
     }
     /// rows [0, n) of column `col` = elements first .. first + n - 1 of stream (seed, stream_id) (zkhip.h "random field elements"): the vanishing
     /// argument's random polynomial, drawn where it is committed and opened.  `seed` = `random_seed(&mut rng)`, once per proof

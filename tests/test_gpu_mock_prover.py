@@ -1,0 +1,137 @@
+"""GPU: `mock.MockProver` over device-resident columns against `mock.verify_host` (Python integers) on witnesses of the halo2-lib shape built
+the way tools/prove_flow.py builds them -- vertical gates on rows 0, 4, 8, ..., range-lookup columns against one table, copy cycles across
+advice columns and the constants column -- and the `mock=` step of the flow itself."""
+import random
+
+import numpy as np
+import pytest
+
+from zksnap_circuits_halo2_amd import evaluation as E, fields as F, mock as M
+from zksnap_circuits_halo2_amd.keygen import Assembly
+
+pytestmark = pytest.mark.gpu
+R = F.R_MOD
+BLIND = 5
+G, NL, BITS = 5, 2, 6
+
+
+def _torch():
+    import torch
+
+    return torch, torch.device("cuda", 0)
+
+
+def words(vals):
+    torch, dev = _torch()
+    return torch.from_numpy(F.fr_encode(vals).view(np.int64)).to(dev)
+
+
+def build_witness(k, seed):
+    """(cs, fixed, advice, assembly) in Python integers: prove_flow's circuit and witness"""
+    n, u = 1 << k, (1 << k) - (BLIND + 1)
+    rng = random.Random(seed)
+    cs = E.halo2_lib_shape(G, NL, BLIND)
+    gate_rows = [r for r in range(n) if r % 4 == 0 and r + 3 < u]
+    sel = [1 if r % 4 == 0 and r + 3 < u else 0 for r in range(n)]
+    fixed = [list(sel) for _ in range(G)] + [[rng.randrange(R) for _ in range(n)], [r % (1 << BITS) for r in range(n)]]      # q_0.., constants, table
+    advice = [[rng.randrange(R) for _ in range(n)] for _ in range(G)]
+    advice += [[rng.randrange(1 << BITS) for _ in range(u)] + [rng.randrange(R) for _ in range(n - u)] for _ in range(NL)]   # blinding rows are random
+    FC = G + NL
+    pcol = lambda c: advice[c] if c < FC else fixed[G]
+    cycles = [[(0, 1), (FC, 2)], [(G, 10), (G, 20)], [(0, 13), (G, 30)], [(0, 17), (0, 21), (FC, 5)]]
+    cycles += [[(G + j, 40 + j), (G, 60 + j)] for j in range(1, NL)]
+    cycles += [[(G - 1, 5), (FC, 7)], [(G // 2, 9), (G - 1, 25)]]
+    for cyc in cycles:                               # a cycle through a lookup column carries a table value
+        src = next(((c, r) for c, r in cyc if G <= c < FC), cyc[0])
+        v = pcol(src[0])[src[1]]
+        for c, r in cyc:
+            pcol(c)[r] = v
+    for i in range(G):
+        for r in gate_rows:
+            advice[i][r + 3] = (advice[i][r] + advice[i][r + 1] * advice[i][r + 2]) % R
+    asm = Assembly(n, len(cs.permutation_columns))
+    for cyc in cycles:
+        for (c1, r1), (c2, r2) in zip(cyc, cyc[1:]):
+            asm.copy(c1, r1, c2, r2)
+    return cs, fixed, advice, asm
+
+
+def device_verify(cs, k, fixed, advice, asm):
+    with M.MockProver(cs, k, [words(c) for c in fixed], [words(c) for c in advice], (), asm) as mp:
+        first = mp.verify()
+        assert mp.verify() == first                  # the records are initialised by every call
+        return first
+
+
+@pytest.mark.parametrize("k", [8, 10])
+def test_mock_prover_equals_verify_host(k):
+    n, u = 1 << k, (1 << k) - (BLIND + 1)
+    cs, fixed, advice, asm = build_witness(k, 40 + k)
+    assert M.verify_host(cs, k, fixed, advice, (), asm) == []
+    assert device_verify(cs, k, fixed, advice, asm) == []
+    last_gate_row = max(r for r in range(n) if r % 4 == 0 and r + 3 < u)
+    for c in (0, G // 2, G - 1):                     # "gate": one output cell of the first, a middle and the last gate column
+        bad = [list(a) for a in advice]
+        bad[c][7] = bad[c][8]
+        want = M.verify_host(cs, k, fixed, bad, (), asm)
+        assert want == [("gate", c, 0, 4, 1)]
+        assert device_verify(cs, k, fixed, bad, asm) == want
+        bad[c][last_gate_row + 3] = (bad[c][last_gate_row + 3] + 1) % R
+        want = M.verify_host(cs, k, fixed, bad, (), asm)
+        assert want == [("gate", c, 0, 4, 2)]
+        assert device_verify(cs, k, fixed, bad, asm) == want
+    bad = [list(a) for a in advice]                  # "copy": a cell of the 3-cycle (0, 17) (0, 21) (constants, 5)
+    bad[0][21] = bad[0][22]
+    want = M.verify_host(cs, k, fixed, bad, (), asm)
+    assert [w[0] for w in want] == ["copy", "gate"] and want[0][3] == 2 and want[1] == ("gate", 0, 0, 20, 1)      # row 21 is also an operand of the gate at row 20
+    assert device_verify(cs, k, fixed, bad, asm) == want
+    bad = [list(a) for a in advice]                  # "lookup": a value outside the table in lookup column 1
+    bad[G + 1][3] = 1 << BITS
+    want = M.verify_host(cs, k, fixed, bad, (), asm)
+    assert want == [("lookup", 1, 3, 1)]
+    assert device_verify(cs, k, fixed, bad, asm) == want
+    bad[G + 1][u] = 1 << BITS                        # behind the usable rows: not looked up
+    bad[G][u - 1] = R - 1                            # the last usable row of lookup 0
+    bad[G - 1][7] = 0                                # ... and a gate and a copy at the same time
+    bad[0][1] = (bad[0][1] + 1) % R
+    want = M.verify_host(cs, k, fixed, bad, (), asm)
+    assert [w[0] for w in want] == ["copy", "gate", "gate", "lookup", "lookup"]      # (0, 1) is also an operand of gate 0 at row 0
+    assert device_verify(cs, k, fixed, bad, asm) == want
+
+
+def test_multi_column_lookup_is_compressed_with_theta():
+    """two input and two table expressions, one of them not a plain column: the compressed columns are evaluated on the device"""
+    k, n = 8, 256
+    u = n - (BLIND + 1)
+    rng = random.Random(9)
+    cs = E.ConstraintSystem(num_fixed=2, num_advice=2, lookups=[E.Lookup([E.Advice(0), E.Advice(1) * E.Advice(0)], [E.Fixed(0), E.Fixed(1)]),
+                                                                E.Lookup([E.Advice(1)], [E.Fixed(0)])], blinding_factors=BLIND)
+    t0 = [rng.randrange(1, 50) for _ in range(n)]
+    t1 = [rng.randrange(R) for _ in range(n)]
+    pick = [rng.randrange(u) for _ in range(n)]
+    a0 = [t0[j] for j in pick]
+    a1 = [t1[j] * pow(t0[j], -1, R) % R for j in pick]          # a0 = t0[j], a1 a0 = t1[j]: the pair is row j of the table
+    fixed, advice = [t0, t1], [a0, a1]
+    want = M.verify_host(cs, k, fixed, advice, (), None)
+    assert [w[:2] for w in want] == [("lookup", 1)]             # the pairs are all there; a1 alone is not a column of t0's values
+    assert device_verify(cs, k, fixed, advice, None) == want
+    advice[1][17] = (advice[1][17] + 1) % R
+    want = M.verify_host(cs, k, fixed, advice, (), None)
+    assert want[0] == ("lookup", 0, 17, 1)
+    assert device_verify(cs, k, fixed, advice, None) == want
+
+
+def test_prove_flow_with_the_mock_step(lib):
+    from tools import prove_flow
+
+    plain = prove_flow.run(10, 4, seed=15, verbose=False)
+    assert all(plain["checks"].values()) and "mock_prover" not in plain["timings_ms"]
+    res = prove_flow.run(10, 4, seed=15, verbose=False, mock=True)
+    assert all(res["checks"].values()) and res["timings_ms"]["mock_prover"] > 0
+    assert res["h_commitments"] == plain["h_commitments"]       # the step reads, nothing else: the same proof with and without it
+    with pytest.raises(AssertionError, match=r"\('gate', 0, 0, 4, 1\)"):
+        prove_flow.run(10, 4, seed=15, verbose=False, mock=True, corrupt="gate")
+    with pytest.raises(AssertionError, match=r"\('copy', 0, 17, 2\)|\('copy', 0, 21, 2\)"):
+        prove_flow.run(10, 4, seed=15, verbose=False, mock=True, corrupt="copy")
+    with pytest.raises(AssertionError, match=r"\('lookup', 1, 3, 1\)"):
+        prove_flow.run(10, 4, seed=15, verbose=False, mock=True, corrupt="lookup", lookups=2)

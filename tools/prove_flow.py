@@ -14,7 +14,8 @@ with `calculate_params(Some(20))` (/root/reference/voter/benches/voter_circuit.r
 /root/reference/voter/frontend/app/worker.js:95-102): `run(13, 256, lookups=8)` and `run(15, 64, lookups=8)` are those shapes, with all
 the columns of a phase committed through ONE batched call (`zkhip_msm_g1_registered_batch_device`) as a Rust host would have to.  Checks (the prover's own invariants): both
 grand products close, the quotient is a polynomial (coefficients of degree >= 3n vanish), commit_lagrange(column) = commit(coefficients).
-There is no transcript: challenges are seeded.  Usage: prove_flow.py [k] [gate_cols] [lookups] [--device-randomness]   (default 16 4 1).
+There is no transcript: challenges are seeded.  Usage: prove_flow.py [k] [gate_cols] [lookups] [--device-randomness] [--mock]   (default 16 4 1).
+--mock (run(mock=True)): the witness is checked against the circuit on the device before keygen and the arguments run (lap `mock_prover`).
 --device-randomness (run(device_randomness=True)): every blinding tail is drawn by zkhip_fr_random_rows_device, all columns of a step in one
 call, and the vanishing argument's random polynomial is filled by zkhip_fr_random_device and committed (lap `vanishing_random_poly`); the
 default flow draws its blinding rows with torch and has no such lap."""
@@ -39,8 +40,15 @@ _SIDE_STREAM = None
 
 
 def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False,
-        sharded_key=False, lookups_one_call=True, device_randomness=False):
-    """device_randomness: blinding tails through E.blind_rows_device (one call per step, whatever the number of columns) and the vanishing argument's
+        sharded_key=False, lookups_one_call=True, device_randomness=False, mock=False, on_witness=None):
+    """mock: what the reference's `gen_proof` does before it proves (`MockProver::run(..).assert_satisfied()`,
+    /root/reference/aggregator/src/wrapper.rs:117-123), over the columns where they lie: `mock.MockProver(..).assert_satisfied()` once the
+    witness columns and the copy constraints exist, as lap `mock_prover` (not part of `prove_ms`).  A witness broken with `corrupt=` then raises
+    an AssertionError that says where -- ("gate", gate, polynomial, row, rows) / ("copy", column, row, cells) / ("lookup", lookup, row, rows) --
+    instead of the proof going on until a product does not close or the quotient is no polynomial.
+    on_witness: a callable handed (cs, k, fixed, advice, assembly, theta) at that same point, the columns being device tensors (tools/mock_time.py
+    measures the checks there, on the flow's own witness).
+    device_randomness: blinding tails through E.blind_rows_device (one call per step, whatever the number of columns) and the vanishing argument's
     random polynomial through E.random_fr_device + a commit against params.g (lap vanishing_random_poly); the seed of the stream comes from `seed`.
     lookups_one_call: the lookup argument of every lookup through zkhip_lookup_permute_many_device + zkhip_lookup_products_device (two calls per
     proof); False: one lookup at a time (the single-lookup call, two row programs and a grand product each).  The same bytes either way.
@@ -205,6 +213,15 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
                 assembly.copy(c1, r1, c2, r2)
         host = lambda tns: tns.cpu().numpy().view(np.uint64).reshape(-1, 4)
         lap("witness_columns")
+        if mock:
+            from zksnap_circuits_halo2_amd import mock as MK
+
+            with MK.MockProver(cs, k, fixed, advice, (), assembly, theta=theta) as mock_prover:
+                mock_prover.assert_satisfied()
+            lap("mock_prover")
+        if on_witness is not None:
+            on_witness(cs, k, fixed, advice, assembly, theta)
+            lap("witness_columns")
         pk_bytes = None
         if pk_file is None:
             # the key is produced in HBM and stays there (keygen.keygen_device): sigma columns by gather, commitments against the
@@ -447,7 +464,7 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
         checks = {"permutation_product_closes": perm_closes, "lookup_product_closes": lookup_closes, "quotient_is_a_polynomial": top_is_zero and low_nonzero,
                   "commit_lagrange_equals_commit_coeff": commit_agrees, "multiopen_linearisation_vanishes": mo_ok}
         n_msm = len(adv_commit) + len(prod_commit) + 1 + len(h_commit) + 2
-        prove_ms = sum(v for kk, v in t.items() if kk not in ("setup_srs", "witness_columns", "stack_columns", "pk_file_round_trip", "pk_upload") and not kk.startswith("keygen_"))
+        prove_ms = sum(v for kk, v in t.items() if kk not in ("setup_srs", "witness_columns", "mock_prover", "stack_columns", "pk_file_round_trip", "pk_upload") and not kk.startswith("keygen_"))
         n_proof_cols = sum(hi - lo for lo, hi in proof_ranges)
         if verbose:
             print(f"k={k} gate_cols={G} lookups={NL}{' (batched commits)' if batched else ''}: {ncol} columns ({n_proof_cols} witness-dependent, {ncol - n_proof_cols} of the proving key), {n_msm} MSMs of 2^{k}, "
@@ -468,10 +485,10 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
 
 
 if __name__ == "__main__":
-    dr = "--device-randomness" in sys.argv
-    sys.argv = [a for a in sys.argv if a != "--device-randomness"]
+    dr, mk = "--device-randomness" in sys.argv, "--mock" in sys.argv
+    sys.argv = [a for a in sys.argv if a not in ("--device-randomness", "--mock")]
     kk = int(sys.argv[1]) if len(sys.argv) > 1 else 16
     gg = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     ll = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-    res = run(kk, gg, lookups=ll, device_randomness=dr)
+    res = run(kk, gg, lookups=ll, device_randomness=dr, mock=mk)
     sys.exit(0 if all(res["checks"].values()) else 1)

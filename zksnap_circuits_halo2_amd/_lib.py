@@ -57,6 +57,9 @@ _SIGS = {
     "zkhip_lookup_permute_many_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_lookup_products_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p]),
+    "zkhip_check_rows_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "zkhip_check_copies_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkhip_check_lookups_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zkhip_fr_random_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zkhip_fr_random": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]),
     "zkhip_fr_random_rows_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_size_t, C.c_size_t, C.c_void_p]),
@@ -133,6 +136,10 @@ _SIGS = {
 
 class ProverQueryC(C.Structure):   # zkhip_prover_query (80 bytes)
     _fields_ = [("point", C.c_uint64 * 4), ("d_poly", C.c_void_p), ("eval", C.c_uint64 * 4), ("has_eval", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CheckReport(C.Structure):     # zkhip_check_report (16 bytes)
+    _fields_ = [("failures", C.c_uint64), ("first", C.c_uint64)]
 
 
 class VmOperand(C.Structure):      # zkhip_vm_operand

@@ -1839,6 +1839,69 @@ int zkhip_lookup_products_device(const void* const* d_inputs, const void* const*
                                    (const uint32_t*)beta, (const uint32_t*)gamma, (uint32_t*)d_z, sc->ws.p, sc->ws.cap, s, &sc->args);
 }
 
+// ---- witness checks (include/zkhip.h): gates, copy constraints, lookup membership -----------------------------------------------------------
+// Every argument is looked at before anything is enqueued; after that nothing waits for the stream.
+static inline bool report_ptr_ok(const void* p) { return p && ((uintptr_t)p & 7u) == 0; }
+
+int zkhip_check_rows_device(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint64_t row0,
+                            uint64_t count, void* d_reports, void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if (!progs || n_progs == 0 || n_progs > 65535 || !report_ptr_ok(d_reports) || (n_columns && !d_columns)) { set_error("check_rows: bad argument"); return ZKHIP_EINVAL; }
+  for (uint32_t p = 0; p < n_progs; p++)
+    if ((rc = row_vm_validate(&progs[p], n_columns, log_rows, 0)) != ZKHIP_OK) return rc;
+  const uint64_t rows = (uint64_t)1 << log_rows;
+  if (count == 0 || count > rows || row0 > rows - count) {
+    set_error("check_rows: rows [%llu, +%llu) outside a domain of 2^%u rows", (unsigned long long)row0, (unsigned long long)count, log_rows);
+    return ZKHIP_EINVAL;
+  }
+  for (uint32_t i = 0; i < n_columns; i++)
+    if (!d_columns[i]) { set_error("check_rows: column %u is null", i); return ZKHIP_EINVAL; }
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->vm.reserve(row_vm_multi_workspace_bytes(progs, n_progs, n_columns, log_rows))) != ZKHIP_OK) return rc;
+  return row_vm_check_device(progs, n_progs, d_columns, n_columns, log_rows, row0, count, d_reports, sc->vm.p, sc->vm.cap, s, &sc->vm_stage);
+}
+
+int zkhip_check_copies_device(const void* const* d_columns, uint32_t n_columns, uint32_t log_n, const void* d_map_col, const void* d_map_row, void* d_report,
+                              void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if (!d_columns || !d_map_col || !d_map_row || !report_ptr_ok(d_report)) { set_error("check_copies: null pointer"); return ZKHIP_EINVAL; }
+  // the column addresses travel through one slot of the argument ring (no wait for the stream), the grid has one lane per cell
+  if (n_columns == 0 || (size_t)n_columns * 8 > arg_ring::SLOT_BYTES || log_n > 28 || ((uint64_t)n_columns << log_n) >= (1ull << 39)) {
+    set_error("check_copies: bad shape (%u columns of 2^%u rows)", n_columns, log_n);
+    return ZKHIP_EINVAL;
+  }
+  for (uint32_t i = 0; i < n_columns; i++)
+    if (!d_columns[i]) { set_error("check_copies: column %u is null", i); return ZKHIP_EINVAL; }
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->ws.reserve((size_t)n_columns * 8)) != ZKHIP_OK) return rc;
+  if ((rc = upload_args(&sc->args, sc->ws.p, d_columns, (size_t)n_columns * 8, s)) != ZKHIP_OK) return rc;
+  return check_copies_device(sc->ws.p, n_columns, log_n, (const uint32_t*)d_map_col, (const uint32_t*)d_map_row, d_report, s);
+}
+
+int zkhip_check_lookups_device(const void* const* d_inputs, const void* const* d_tables, uint32_t n_lookups, uint32_t log_n, size_t usable_rows, void* d_reports,
+                               void* stream) {
+  ZK_API_RANGE();
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  if (n_lookups == 0) return ZKHIP_OK;
+  // the argument block travels through one slot of the argument ring: no wait for the stream
+  if (3 * (size_t)n_lookups * 8 > arg_ring::SLOT_BYTES) { set_error("check_lookups: more than %zu lookups", arg_ring::SLOT_BYTES / 24); return ZKHIP_EINVAL; }
+  if ((rc = lookup_many_args_ok("check_lookups", d_inputs, d_tables, n_lookups, log_n, usable_rows, report_ptr_ok(d_reports))) != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if (usable_rows && (rc = sc->vm.reserve(lookup_check_workspace_bytes(n_lookups, usable_rows))) != ZKHIP_OK) return rc;
+  return lookup_check_device(d_inputs, d_tables, n_lookups, usable_rows, d_reports, sc->vm.p, sc->vm.cap, s, &sc->args);
+}
+
 int zkhip_lookup_permute(const uint64_t* input, const uint64_t* table, size_t usable_rows, uint64_t* permuted_input, uint64_t* permuted_table) {
   ZK_API_RANGE();
   if (usable_rows && (!input || !table || !permuted_input || !permuted_table)) { set_error("lookup_permute: null pointer"); return ZKHIP_EINVAL; }

@@ -19,6 +19,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <cstdint>
 #include <vector>
+#include "check_report.hpp"
 #include "fp29.hpp"
 #include "fr_vec.hpp"
 #include "zkhip_internal.hpp"
@@ -242,6 +243,18 @@ __global__ void __launch_bounds__(256) k_lookup_table_keys(const uint64_t* __res
   keys[(size_t)blockIdx.y * u + i] = canonical_key(table, i);
 }
 
+// the key search the histogram and the membership check share: the lower bound of v among the u ascending keys t; true when v is there
+__device__ __forceinline__ bool lookup_find(const key256* __restrict__ t, uint32_t u, const key256& v, uint32_t* slot) {
+  uint32_t lo = 0, hi = u;
+  const key256_less less;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (less(t[mid], v)) lo = mid + 1; else hi = mid;
+  }
+  *slot = lo;
+  return lo < u && key_eq(t[lo], v);
+}
+
 // One thread per (lookup, input row): the row's key in registers, its lower bound in the lookup's sorted table, one count.  Padding rows make
 // real columns skewed (one slot can take most of a column) and the compiler folds atomicAdd(p, 1) into one add per wavefront only for a uniform
 // p: the lanes that share the slot of the first pending lane are counted with one atomic, four rounds at the most (the heavy slots), and what
@@ -256,13 +269,7 @@ __global__ void __launch_bounds__(256) k_lookup_hist(const uint64_t* __restrict_
   uint32_t slot = 0;
   if (i < u) {
     const key256 v = canonical_key((const uint32_t*)args[l], i);
-    uint32_t lo = 0, hi = u;
-    const key256_less less;
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (less(t[mid], v)) lo = mid + 1; else hi = mid;
-    }
-    if (lo < u && key_eq(t[lo], v)) { pending = true; slot = lo; }
+    if (lookup_find(t, u, v, &slot)) pending = true;
     else atomicMin(status, l);                                       // the lowest failing lookup
   }
   uint32_t* c = cnt + (size_t)l * (u + 1);
@@ -278,6 +285,20 @@ __global__ void __launch_bounds__(256) k_lookup_hist(const uint64_t* __restrict_
     if (same) pending = false;
   }
   if (pending) atomicAdd(c + slot, 1u);
+}
+
+// Membership only (zkhip_check_lookups_device): one thread per (lookup, input row), the same search, no counters -- the rows whose value the
+// table does not hold go to the lookup's report record, item index = row
+__global__ void __launch_bounds__(256) k_lookup_member(const uint64_t* __restrict__ args, uint32_t n_lookups, uint32_t n_tables, uint32_t u,
+                                                       const key256* __restrict__ sorted, unsigned long long* __restrict__ reports) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
+  const key256* t = sorted + (size_t)(uint32_t)args[n_lookups + n_tables + l] * u;
+  bool failing = false;
+  if (i < u) {
+    uint32_t slot;
+    failing = !lookup_find(t, u, canonical_key((const uint32_t*)args[l], i), &slot);
+  }
+  check_report_wave(failing, i, reports + 2 * (size_t)l);
 }
 
 // exclusive scan of 256 values, one per thread of the workgroup; *total: their sum
@@ -379,14 +400,9 @@ size_t lookup_permute_many_workspace_bytes(uint32_t n_lookups, size_t u) {
   return al256(3 * L * 8) + 2 * al256(L * u * sizeof(key256)) + al256(sort_temp_bytes(u)) + al256(L * (u + 1) * 4) + al256(L * (u + 1) * 8) + sums + 256;
 }
 
-// d_inputs_host / d_tables_host: n_lookups device addresses each, in host memory.  out_input / out_table: [n_lookups][n] dense.
-int lookup_permute_many_device(const void* const* d_inputs_host, const void* const* d_tables_host, uint32_t n_lookups, size_t n, size_t u,
-                               uint32_t* d_out_input, uint32_t* d_out_table, void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring) {
-  if (n_lookups == 0 || u == 0) return ZKHIP_OK;
-  if (n_lookups > 65535) { set_error("lookup_permute_many: more than 65535 lookups"); return ZKHIP_EINVAL; }
-  if (ws_bytes < lookup_permute_many_workspace_bytes(n_lookups, u)) { set_error("lookup_permute_many: workspace too small"); return ZKHIP_EINVAL; }
-  const uint32_t L = n_lookups, un = (uint32_t)u;
-  std::vector<uint64_t> tables, index(L);                              // equal table addresses are one table
+// the argument block of a many-lookup call: [inputs L][distinct tables T][table index of every lookup L]; equal table addresses are one table
+static std::vector<uint64_t> lookup_args(const void* const* d_inputs_host, const void* const* d_tables_host, uint32_t L) {
+  std::vector<uint64_t> tables, index(L);
   for (uint32_t l = 0; l < L; l++) {
     const uint64_t addr = (uint64_t)(uintptr_t)d_tables_host[l];
     size_t t = 0;
@@ -394,11 +410,33 @@ int lookup_permute_many_device(const void* const* d_inputs_host, const void* con
     if (t == tables.size()) tables.push_back(addr);
     index[l] = t;
   }
-  const uint32_t T = (uint32_t)tables.size();
-  std::vector<uint64_t> host;                                          // [inputs L][distinct tables T][table index of every lookup L]
+  std::vector<uint64_t> host;
   for (uint32_t l = 0; l < L; l++) host.push_back((uint64_t)(uintptr_t)d_inputs_host[l]);
   host.insert(host.end(), tables.begin(), tables.end());
   host.insert(host.end(), index.begin(), index.end());
+  return host;
+}
+
+// the block uploaded to `args`, then the keys of every distinct table and their ascending order (sorted[t * u ..]): what both many-lookup calls start with
+static int lookup_sort_tables(const std::vector<uint64_t>& host, uint32_t L, uint32_t T, size_t u, uint64_t* args, key256* keys, key256* sorted, void* sort_tmp,
+                              size_t sort_bytes, hipStream_t stream, arg_ring* ring) {
+  int rc = upload_args(ring, args, host.data(), host.size() * 8, stream);
+  if (rc != ZKHIP_OK) return rc;
+  hipLaunchKernelGGL(k_lookup_table_keys, dim3((unsigned)((u + 255) / 256), T), dim3(256), 0, stream, (const uint64_t*)args, L, (uint32_t)u, keys);
+  for (uint32_t t = 0; t < T; t++)                                      // a library sort, once per distinct table: 256-bit comparison, no dispatch on the width
+    HIPCHK(rocprim::merge_sort(sort_tmp, sort_bytes, keys + (size_t)t * u, sorted + (size_t)t * u, u, key256_less{}, stream));
+  return ZKHIP_OK;
+}
+
+// d_inputs_host / d_tables_host: n_lookups device addresses each, in host memory.  out_input / out_table: [n_lookups][n] dense.
+int lookup_permute_many_device(const void* const* d_inputs_host, const void* const* d_tables_host, uint32_t n_lookups, size_t n, size_t u,
+                               uint32_t* d_out_input, uint32_t* d_out_table, void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring) {
+  if (n_lookups == 0 || u == 0) return ZKHIP_OK;
+  if (n_lookups > 65535) { set_error("lookup_permute_many: more than 65535 lookups"); return ZKHIP_EINVAL; }
+  if (ws_bytes < lookup_permute_many_workspace_bytes(n_lookups, u)) { set_error("lookup_permute_many: workspace too small"); return ZKHIP_EINVAL; }
+  const uint32_t L = n_lookups, un = (uint32_t)u;
+  const std::vector<uint64_t> host = lookup_args(d_inputs_host, d_tables_host, L);
+  const uint32_t T = (uint32_t)host.size() - 2 * L;
   char* p = (char*)ws;
   auto carve = [&](size_t bytes) { void* r = p; p += al256(bytes); return r; };
   uint64_t* args = (uint64_t*)carve(3 * (size_t)L * 8);
@@ -413,14 +451,11 @@ int lookup_permute_many_device(const void* const* d_inputs_host, const void* con
   level[0] = (unsigned long long*)carve((size_t)L * (u + 1) * 8);
   for (uint32_t k = 1; k < levels; k++) level[k] = (unsigned long long*)carve((size_t)L * counts[k] * 8);
   uint32_t* status = (uint32_t*)carve(256);
-  int rc = upload_args(ring, args, host.data(), host.size() * 8, stream);
-  if (rc != ZKHIP_OK) return rc;
   HIPCHK(hipMemsetAsync(status, 0xFF, 4, stream));
   HIPCHK(hipMemsetAsync(cnt, 0, (size_t)L * (u + 1) * 4, stream));
   const dim3 block(256), rows((unsigned)((u + 255) / 256), L);
-  hipLaunchKernelGGL(k_lookup_table_keys, dim3(rows.x, T), block, 0, stream, (const uint64_t*)args, L, un, keys);
-  for (uint32_t t = 0; t < T; t++)                                      // a library sort, once per distinct table: 256-bit comparison, no dispatch on the width
-    HIPCHK(rocprim::merge_sort(sort_tmp, sort_bytes, keys + (size_t)t * u, sorted + (size_t)t * u, u, key256_less{}, stream));
+  int rc = lookup_sort_tables(host, L, T, u, args, keys, sorted, sort_tmp, sort_bytes, stream, ring);
+  if (rc != ZKHIP_OK) return rc;
   hipLaunchKernelGGL(k_lookup_hist, rows, block, 0, stream, (const uint64_t*)args, L, T, un, (const key256*)sorted, cnt, status);
   for (uint32_t k = 0; k < levels; k++) {                               // up: tiles of every level, their sums are the level above
     const uint32_t tiles = (uint32_t)((counts[k] + SCAN_TILE - 1) / SCAN_TILE);
@@ -440,6 +475,37 @@ int lookup_permute_many_device(const void* const* d_inputs_host, const void* con
     set_error("lookup_permute_many: lookup %u: an input value is missing from the table (the reference returns Error::ConstraintSystemFailure)", failed);
     return ZKHIP_EINVAL;
   }
+  return ZKHIP_OK;
+}
+
+// ---- lookup membership: the witness check -------------------------------------------------------------------------------------------------
+size_t lookup_check_workspace_bytes(uint32_t n_lookups, size_t u) {
+  const size_t L = n_lookups;
+  return al256(3 * L * 8) + 2 * al256(L * u * sizeof(key256)) + al256(sort_temp_bytes(u)) + 256;
+}
+
+// Nothing here waits for the stream: the argument block goes through the ring, the sort is enqueued, the verdicts stay in d_reports.
+int lookup_check_device(const void* const* d_inputs_host, const void* const* d_tables_host, uint32_t n_lookups, size_t u, void* d_reports, void* ws, size_t ws_bytes,
+                        hipStream_t stream, arg_ring* ring) {
+  if (n_lookups == 0) return ZKHIP_OK;
+  if (u >= (1ull << 31)) { set_error("check_lookups: %zu rows is too many", u); return ZKHIP_EINVAL; }
+  if (u && ws_bytes < lookup_check_workspace_bytes(n_lookups, u)) { set_error("check_lookups: workspace too small"); return ZKHIP_EINVAL; }
+  int rc = check_reports_init_device(d_reports, n_lookups, stream);
+  if (rc != ZKHIP_OK || u == 0) return rc;
+  const uint32_t L = n_lookups;
+  const std::vector<uint64_t> host = lookup_args(d_inputs_host, d_tables_host, L);
+  const uint32_t T = (uint32_t)host.size() - 2 * L;
+  char* p = (char*)ws;
+  auto carve = [&](size_t bytes) { void* r = p; p += al256(bytes); return r; };
+  uint64_t* args = (uint64_t*)carve(3 * (size_t)L * 8);
+  key256* keys = (key256*)carve((size_t)L * u * sizeof(key256));
+  key256* sorted = (key256*)carve((size_t)L * u * sizeof(key256));
+  const size_t sort_bytes = sort_temp_bytes(u);
+  void* sort_tmp = carve(sort_bytes);
+  if ((rc = lookup_sort_tables(host, L, T, u, args, keys, sorted, sort_tmp, sort_bytes, stream, ring)) != ZKHIP_OK) return rc;
+  hipLaunchKernelGGL(k_lookup_member, dim3((unsigned)((u + 255) / 256), L), dim3(256), 0, stream, (const uint64_t*)args, L, T, (uint32_t)u, (const key256*)sorted,
+                     (unsigned long long*)d_reports);
+  HIPCHK(hipGetLastError());
   return ZKHIP_OK;
 }
 

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "check_report.hpp"
 #include "fp29.hpp"
 #include "fr_vec.hpp"
 #include "zkhip_internal.hpp"
@@ -37,12 +38,12 @@ struct vm_launch {
   const uint32_t* rot_off;      // per rotation slot: (rotation * rot_scale) mod rows
   const uint32_t* pow_lo;       // omega^j, j < 2^POW_LO_BITS (nullptr: ROWPOW unused)
   const uint32_t* pow_hi;       // omega^(j << POW_LO_BITS)
-  uint32_t* out;
-  uint64_t rows;                // rows this launch computes: the domain, or a window's `count`
+  uint32_t* out;                // CHECK: the program's report record instead
+  uint64_t rows;                // rows this launch computes: the domain, a window's `count`, or a check's `count`
   uint32_t accumulate;
   const struct vm_part* parts;  // nullptr, or one record per blockIdx.y: several programs over the same columns in ONE launch (row_vm_device_multi)
   uint64_t wrap;                // column index mask: domain - 1 for whole columns, all ones for window buffers (offsets include halo_lo)
-  uint64_t row0;                // global row of local row 0 (0 for whole columns)
+  uint64_t row0;                // global row of local row 0 (0 for whole columns; CHECK: whole columns read from this row on)
   uint64_t dom_mask;            // domain - 1: ROWPOW is omega^((row0 + row) & dom_mask)
 };
 // what differs between the programs of a multi-program launch (the column table, the power tables and the rows are shared)
@@ -255,7 +256,18 @@ __device__ __forceinline__ void vm_prefetch(const vm_launch& L, const vm_decoded
   vm_load_resolved(d.base_b, d.off_b, d.mask_b, row, L.wrap, wb);
 }
 
-template <int R>
+// the end of a row: the result register in canonical words.  The evaluator stores them; the check variant (CHECK) stores nothing -- a lane whose
+// eight words are not all zero is failing, and the wavefront's verdicts go to the program's report record (check_report.hpp)
+template <bool CHECK, int R>
+__device__ __forceinline__ void vm_finish(const vm_launch& L, const fe (&r)[R], uint64_t row) {
+  uint32_t w[8];
+  fe_pack(fe_canon_lt2p<Fr>(vm_reg_get(r, L.result_reg)), w);
+  if constexpr (CHECK) check_report_wave((w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) != 0u, row, (unsigned long long*)L.out);
+  else store_words(L.out + row * 8, w);
+}
+
+// CHECK (zkhip_check_rows_device): lane i of the grid runs global row row0 + i of whole-domain columns, i < rows, and reports instead of storing
+template <int R, bool CHECK = false>
 __global__ void __launch_bounds__(VM_THREADS) k_row_vm(const vm_launch L0) {
   __shared__ uint32_t s_prev[NL * VM_THREADS], s_pow[NL * VM_THREADS];
   vm_launch L = L0;
@@ -269,14 +281,16 @@ __global__ void __launch_bounds__(VM_THREADS) k_row_vm(const vm_launch L0) {
     L.n_insns = (uint32_t)w4;
     L.result_reg = (uint32_t)(w4 >> 32);
   }
-  const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= L.rows) return;
+  const uint64_t lane_row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane_row >= L.rows) return;
+  const uint64_t row = CHECK ? L.row0 + lane_row : lane_row;
   fe r[R];
 #pragma unroll
   for (int i = 0; i < R; i++) r[i] = fe_zero();
-  vm_lds_put(s_prev, L.accumulate ? load_ext(L.out, row) : fe_zero());      // (a lane reads back only what it wrote: no barrier)
+  if constexpr (CHECK) vm_lds_put(s_prev, fe_zero());                       // there is no previous value
+  else vm_lds_put(s_prev, L.accumulate ? load_ext(L.out, row) : fe_zero());      // (a lane reads back only what it wrote: no barrier)
   if (L.pow_lo) {
-    const uint64_t prow = (L.row0 + row) & L.dom_mask;       // the global row (a window's rows wrap past the domain's end)
+    const uint64_t prow = (CHECK ? row : L.row0 + row) & L.dom_mask;       // the global row (a window's rows wrap past the domain's end)
     uint32_t w[8];
     load_words(L.pow_lo + (prow & ((1u << POW_LO_BITS) - 1)) * 8, w);
     vm_lds_put(s_pow, fe_mul<Fr>(load_ext(L.pow_hi, prow >> POW_LO_BITS), fe_unpack<5>(w)));
@@ -292,9 +306,7 @@ __global__ void __launch_bounds__(VM_THREADS) k_row_vm(const vm_launch L0) {
       vm_prefetch(L, d, row, wa, wb);
       vm_execute<R>(L, d.head, d.oa, d.ob, d.oc, wa, wb, row, r, s_prev, s_pow);
     }
-    uint32_t w[8];
-    fe_pack(fe_canon_lt2p<Fr>(vm_reg_get(r, L.result_reg)), w);
-    store_words(L.out + row * 8, w);
+    vm_finish<CHECK>(L, r, row);
     return;
   }
   // Software pipeline, two word-buffer pairs alternated by a loop unrolled twice (no register copies):
@@ -317,9 +329,7 @@ __global__ void __launch_bounds__(VM_THREADS) k_row_vm(const vm_launch L0) {
     vm_execute<R>(L, nxt.head, nxt.oa, nxt.ob, nxt.oc, wa1, wb1, row, r, s_prev, s_pow);
     nxt = n3;
   }
-  uint32_t w[8];
-  fe_pack(fe_canon_lt2p<Fr>(vm_reg_get(r, L.result_reg)), w);
-  store_words(L.out + row * 8, w);
+  vm_finish<CHECK>(L, r, row);
 }
 
 // table[i] = omega^(i << shift), i < count, external words
@@ -363,6 +373,34 @@ __global__ void __launch_bounds__(256) k_fr_gather_mul(const uint32_t* __restric
   uint32_t w[8];
   fe_pack(fe_canon_lt2p<Fr>(p), w);
   store_words(out + j * 8, w);
+}
+
+// Copy constraints (zkhip_check_copies_device): one lane per cell (c, r) of the permutation's columns, item index c 2^log_n + r.  The cell fails
+// when its 32 bytes differ from those of the cell the mapping sends it to; map entries are reduced, not trusted (k_fr_gather_mul).  A cell that
+// maps to itself -- most of a circuit's cells -- is read not at all.
+__global__ void __launch_bounds__(256) k_check_copies(const uint64_t* __restrict__ cols, uint32_t n_columns, uint32_t log_n, const uint32_t* __restrict__ map_col,
+                                                      const uint32_t* __restrict__ map_row, unsigned long long* __restrict__ report) {
+  const uint64_t cell = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, n = (uint64_t)1 << log_n;
+  bool failing = false;
+  if (cell < (uint64_t)n_columns << log_n) {
+    const uint32_t c = (uint32_t)(cell >> log_n), to_c = map_col[cell] % n_columns;
+    const uint64_t r = cell & (n - 1), to_r = (uint64_t)map_row[cell] & (n - 1);
+    if (to_c != c || to_r != r) {
+      uint32_t a[8], b[8];
+      load_words((const uint32_t*)cols[c] + r * 8, a);
+      load_words((const uint32_t*)cols[to_c] + to_r * 8, b);
+#pragma unroll
+      for (int i = 0; i < 8; i++) failing |= a[i] != b[i];
+    }
+  }
+  check_report_wave(failing, cell, report);
+}
+
+__global__ void __launch_bounds__(256) k_check_report_init(unsigned long long* __restrict__ reports, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  reports[2 * (size_t)i] = 0;
+  reports[2 * (size_t)i + 1] = CHECK_NONE;
 }
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -477,9 +515,15 @@ static uint32_t vm_top_register(const zkhip_vm_program* p) {
   return top;
 }
 
-static int vm_launch_kernel(const vm_launch& L, uint32_t top, uint32_t n_parts, hipStream_t stream) {
+static int vm_launch_kernel(const vm_launch& L, uint32_t top, uint32_t n_parts, hipStream_t stream, bool check = false) {
   const dim3 grid((unsigned)((L.rows + VM_THREADS - 1) / VM_THREADS), n_parts);
-  if (top < 6) hipLaunchKernelGGL(k_row_vm<6>, grid, dim3(VM_THREADS), 0, stream, L);
+  if (check) {
+    if (top < 6) hipLaunchKernelGGL((k_row_vm<6, true>), grid, dim3(VM_THREADS), 0, stream, L);
+    else if (top < 8) hipLaunchKernelGGL((k_row_vm<8, true>), grid, dim3(VM_THREADS), 0, stream, L);
+    else if (top < 12) hipLaunchKernelGGL((k_row_vm<12, true>), grid, dim3(VM_THREADS), 0, stream, L);
+    else hipLaunchKernelGGL((k_row_vm<16, true>), grid, dim3(VM_THREADS), 0, stream, L);
+  }
+  else if (top < 6) hipLaunchKernelGGL(k_row_vm<6>, grid, dim3(VM_THREADS), 0, stream, L);
   else if (top < 8) hipLaunchKernelGGL(k_row_vm<8>, grid, dim3(VM_THREADS), 0, stream, L);
   else if (top < 12) hipLaunchKernelGGL(k_row_vm<12>, grid, dim3(VM_THREADS), 0, stream, L);
   else hipLaunchKernelGGL(k_row_vm<16>, grid, dim3(VM_THREADS), 0, stream, L);
@@ -517,8 +561,9 @@ static unsigned char* vm_staging_acquire(vm_staging* staging, size_t bytes, int*
   return (unsigned char*)staging->host[slot];
 }
 
-int row_vm_device_multi(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint32_t* const* d_outs,
-                        void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging) {
+// check: the check variant over rows [row0, row0 + count), d_outs[p] = program p's report record (initialised here, behind every argument check)
+static int row_vm_multi_run(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint32_t* const* d_outs,
+                            void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, bool check, uint64_t row0, uint64_t count) {
   const uint64_t rows = (uint64_t)1 << log_rows;
   if (n_progs == 0 || n_progs > 65535) { set_error("eval_rows: %u programs in one launch", n_progs); return ZKHIP_EINVAL; }
   if (ws_bytes < row_vm_multi_workspace_bytes(progs, n_progs, n_columns, log_rows)) { set_error("eval_rows: workspace too small"); return ZKHIP_EINVAL; }
@@ -556,6 +601,7 @@ int row_vm_device_multi(const zkhip_vm_program* progs, uint32_t n_progs, const v
     blob.p = local.data();
   }
   char* d = (char*)ws;
+  if (check) { const int rc = check_reports_init_device(d_outs[0], n_progs, stream); if (rc != ZKHIP_OK) return rc; }
   for (uint32_t i = 0; i < n_columns; i++) std::memcpy(blob.data() + o_cols + (size_t)i * 8, &d_columns[i], 8);
   if (omega) std::memcpy(blob.data() + o_omega, omega, 32);
   vm_part* parts = (vm_part*)(blob.data() + o_parts);
@@ -577,10 +623,10 @@ int row_vm_device_multi(const zkhip_vm_program* progs, uint32_t n_progs, const v
   L.consts = parts[0].consts; L.rot_off = parts[0].rot_off;
   L.pow_lo = nullptr; L.pow_hi = nullptr;
   L.out = d_outs[0];
-  L.rows = rows;
+  L.rows = check ? count : rows;
   L.accumulate = 0;
   L.parts = (const vm_part*)(d + o_parts);
-  L.wrap = rows - 1; L.row0 = 0; L.dom_mask = rows - 1;
+  L.wrap = rows - 1; L.row0 = check ? row0 : 0; L.dom_mask = rows - 1;
   if (omega) {
     const uint32_t n_lo = 1u << POW_LO_BITS, n_hi = (uint32_t)((rows >> POW_LO_BITS) ? (rows >> POW_LO_BITS) : 1);
     hipLaunchKernelGGL(k_vm_pow_table, dim3((n_lo + 255) / 256), dim3(256), 0, stream, (const fe_arg*)(d + o_omega), 0u, n_lo, (uint32_t*)(d + o_lo));
@@ -588,7 +634,42 @@ int row_vm_device_multi(const zkhip_vm_program* progs, uint32_t n_progs, const v
     L.pow_lo = (const uint32_t*)(d + o_lo);
     L.pow_hi = (const uint32_t*)(d + o_hi);
   }
-  return vm_launch_kernel(L, top, n_progs, stream);
+  return vm_launch_kernel(L, top, n_progs, stream, check);
+}
+
+int row_vm_device_multi(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint32_t* const* d_outs,
+                        void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging) {
+  return row_vm_multi_run(progs, n_progs, d_columns, n_columns, log_rows, d_outs, ws, ws_bytes, stream, staging, false, 0, (uint64_t)1 << log_rows);
+}
+
+int check_reports_init_device(void* d_reports, uint32_t n, hipStream_t stream) {
+  if (n == 0) return ZKHIP_OK;
+  hipLaunchKernelGGL(k_check_report_init, dim3((n + 255) / 256), dim3(256), 0, stream, (unsigned long long*)d_reports, n);
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
+}
+
+int row_vm_check_device(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint64_t row0,
+                        uint64_t count, void* d_reports, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging) {
+  const uint64_t rows = (uint64_t)1 << log_rows;
+  if (count == 0 || count > rows || row0 > rows - count) {
+    set_error("check_rows: rows [%llu, +%llu) outside a domain of 2^%u rows", (unsigned long long)row0, (unsigned long long)count, log_rows);
+    return ZKHIP_EINVAL;
+  }
+  std::vector<uint32_t*> records(n_progs);
+  for (uint32_t p = 0; p < n_progs; p++) records[p] = (uint32_t*)((zkhip_check_report*)d_reports + p);
+  return row_vm_multi_run(progs, n_progs, d_columns, n_columns, log_rows, records.data(), ws, ws_bytes, stream, staging, true, row0, count);
+}
+
+int check_copies_device(const void* d_columns_dev, uint32_t n_columns, uint32_t log_n, const uint32_t* d_map_col, const uint32_t* d_map_row, void* d_report,
+                        hipStream_t stream) {
+  int rc = check_reports_init_device(d_report, 1, stream);
+  if (rc != ZKHIP_OK) return rc;
+  const uint64_t cells = (uint64_t)n_columns << log_n;
+  hipLaunchKernelGGL(k_check_copies, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, (const uint64_t*)d_columns_dev, n_columns, log_n, d_map_col, d_map_row,
+                     (unsigned long long*)d_report);
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
 }
 
 void row_vm_halos(const zkhip_vm_program* p, uint64_t* lo, uint64_t* hi) {

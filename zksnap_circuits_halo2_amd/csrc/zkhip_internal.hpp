@@ -200,6 +200,16 @@ int row_vm_window_device(const zkhip_vm_program* p, const void* const* d_windows
 int fr_pointwise_mul_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t* d_out, hipStream_t stream);
 int fr_gather_mul_device(const uint32_t* d_a, uint32_t a_len, const uint32_t* d_ia, const uint32_t* d_b, uint32_t b_len, const uint32_t* d_ib, size_t n,
                          uint32_t* d_out, hipStream_t stream);
+// The witness checks (include/zkhip.h, "witness checks"; check_report.hpp).  d_reports: zkhip_check_report records, initialised by the call.
+// reports[i] = (0, none) for i < n, on `stream`
+int check_reports_init_device(void* d_reports, uint32_t n, hipStream_t stream);
+// gates: the programs side by side in one launch of the check variant of the interpreter, rows [row0, row0 + count) of whole-domain columns;
+// workspace as row_vm_device_multi
+int row_vm_check_device(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint64_t row0,
+                        uint64_t count, void* d_reports, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging = nullptr);
+// copy constraints: d_columns_dev is the DEVICE array of the n_columns column addresses
+int check_copies_device(const void* d_columns_dev, uint32_t n_columns, uint32_t log_n, const uint32_t* d_map_col, const uint32_t* d_map_row, void* d_report,
+                        hipStream_t stream);
 
 // lookup.hip
 size_t lookup_permute_workspace_bytes(size_t usable_rows);
@@ -209,6 +219,10 @@ int lookup_permute_device(const uint32_t* d_input, const uint32_t* d_table, size
 size_t lookup_permute_many_workspace_bytes(uint32_t n_lookups, size_t usable_rows);
 int lookup_permute_many_device(const void* const* d_inputs_host, const void* const* d_tables_host, uint32_t n_lookups, size_t n, size_t usable_rows,
                                uint32_t* d_out_input, uint32_t* d_out_table, void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
+// lookup membership (the witness check): report l counts the rows i < usable_rows whose input_l[i] is no table_l[j], j < usable_rows
+size_t lookup_check_workspace_bytes(uint32_t n_lookups, size_t usable_rows);
+int lookup_check_device(const void* const* d_inputs_host, const void* const* d_tables_host, uint32_t n_lookups, size_t usable_rows, void* d_reports, void* ws,
+                        size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
 
 // random.hip: the random Fr stream of fr_random.hpp (include/zkhip.h, "random field elements").  `seed`: 32 bytes of host memory, read before the call returns
 int fr_random_device(const uint8_t seed[32], uint64_t stream_id, uint64_t first, size_t n, uint32_t* d_out, hipStream_t stream);

@@ -552,6 +552,25 @@ int zkhip_test_g1_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out
  * a, b: n G2Affine points, out: n G2 Jacobian points */
 int zkhip_test_g2_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out_xyz, size_t n);
 
+/* ---- pairing check (`multi_miller_loop` + `final_exponentiation` + `is_identity` [DEP halo2curves bn256], under `verify_proof` and the decider) ---- */
+#define ZKHIP_MAX_PAIRS 64
+/* *ok = 1 when prod_i e(g1[i], g2[i]) is the identity of Gt, else 0.  g1: n x 8 words (G1Affine, Montgomery, (0,0) = identity),
+   g2: n x 16 words (G2Affine as zkhip_msm_g2 takes it).  A pair with either point the identity contributes 1; n = 0 gives 1.
+   Points are NOT checked to be on the curve or in the subgroup (as halo2curves' multi_miller_loop does not): callers that
+   read them from a file check them first.  n > ZKHIP_MAX_PAIRS or a null pointer with n > 0: ZKHIP_EINVAL, nothing enqueued.
+   The Gt value itself is not an interface: only the verdict leaves the device.  `_device`: asynchronous on `stream`, no host wait;
+   d_g1 and d_g2 must be 16-byte aligned (the pairs are read with vector loads; any zkhip_alloc'd block is) and d_ok 4-byte aligned, else ZKHIP_EINVAL. */
+int zkhip_pairing_check(const uint64_t *g1, const uint64_t *g2, size_t n, int *ok);
+int zkhip_pairing_check_device(const void *d_g1, const void *d_g2, size_t n, void *d_ok /* one uint32 */, void *stream);
+/* One operation of the Fq12 tower (csrc/pairing.hpp) on the device, so that a wrong verdict can be located.  a, b: 48 words each (the 12 Fq
+ * coefficients c0.c0.c0, c0.c0.c1, c0.c1.c0 .. c1.c2.c1, Montgomery); out: 2 x 48 words, canonical: first through the quad policy in one quad,
+ * then through the single-lane policy in one lane.  op: 0 mul, 1 sqr, 2 inverse, 3 / 4 / 5 Frobenius q / q^2 / q^3, 6 cyclotomic square (a in
+ * the cyclotomic subgroup), 7 a times the sparse line x + y w + z w^3 with (x, y, z) the first three Fq2 of b, 8 the Miller value of the one
+ * pair a = G1Affine (8 words) | G2Affine (16 words), 9 the final exponentiation, 10 conjugation, 11 the verdict (out word 0) of the two pairs
+ * a = 2 G1Affine | 2 G2Affine run as one serial chain.  op + 256: quad policy only, op + 512: single-lane policy only (the other half of out
+ * is left as it was). */
+int zkhip_test_fq12_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

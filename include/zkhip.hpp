@@ -1520,5 +1520,191 @@ inline std::pair<G1, G1> shplonk_create_proof(const DeviceCommitter& params, uin
   return shplonk_create_proof(commit_with(params), k, std::move(queries), y, v, u);
 }
 
+// ---- the verifiers: `verify_proof`'s pairing and the two multi-open verifiers (zksnap_circuits_halo2_amd/multiopen.py, second half) ---------------
+// `multi_miller_loop(..).final_exponentiation().is_identity()` [DEP halo2curves]: is prod_i e(g1[i], g2[i]) one?  At most ZKHIP_MAX_PAIRS pairs;
+// a pair with an identity contributes 1; the points are not checked.  Only the verdict leaves the device.
+inline bool pairing_check(const std::vector<G1Affine>& g1, const std::vector<G2Affine>& g2) {
+  if (g1.size() != g2.size()) throw std::invalid_argument("pairing_check: g1.len() != g2.len()");
+  int ok = 0;
+  check(zkhip_pairing_check(g1.empty() ? nullptr : g1.data()->x, g2.empty() ? nullptr : g2.data()->x, g1.size(), &ok), "pairing_check");
+  return ok != 0;
+}
+
+// `poly_id`: two DIFFERENT polynomials of a proof may have EQUAL commitments (two selector columns with the same rows); halo2 tells them apart by
+// the address of the commitment (`CommitmentReference` compares pointers), here any non-null pointer, one per polynomial, does -- given for every
+// query or for none.  Without it a polynomial is known by its commitment's bytes.
+struct VerifierQuery {
+  Fr point;
+  G1 commitment;
+  Fr eval;
+  const void* poly_id = nullptr;
+};
+
+namespace detail {
+inline bool same_point(const G1& a, const G1& b) { return std::memcmp(&a, &b, sizeof(G1)) == 0; }
+inline bool same_poly(const VerifierQuery& a, const VerifierQuery& b) { return a.poly_id ? a.poly_id == b.poly_id : same_point(a.commitment, b.commitment); }
+// What the set construction would otherwise hide (it keeps the first evaluation of a (polynomial, point) pair, as the prover's repeated queries agree
+// by construction): false when one polynomial has two different evaluations at one point or two different commitments -- the verifiers then reject.
+// poly_id on some queries and not on others throws: the keys would not be comparable.
+inline bool queries_consistent(const std::vector<VerifierQuery>& queries) {
+  size_t with_id = 0;
+  for (const auto& q : queries) with_id += q.poly_id != nullptr;
+  if (with_id != 0 && with_id != queries.size()) throw std::invalid_argument("VerifierQuery::poly_id: give it for every query or for none");
+  for (size_t i = 0; i < queries.size(); i++)
+    for (size_t j = 0; j < i; j++) {
+      if (!same_poly(queries[i], queries[j])) continue;
+      if (!same_point(queries[i].commitment, queries[j].commitment)) return false;
+      if (queries[i].point == queries[j].point && !(queries[i].eval == queries[j].eval)) return false;
+    }
+  return true;
+}
+// sum_i scalars[i] * points[i] as an affine point: the points normalised, one small MSM, the result normalised
+inline G1Affine g1_combination(const std::vector<Fr>& scalars, const std::vector<G1>& points) {
+  if (scalars.size() != points.size() || points.empty()) throw std::invalid_argument("g1_combination: lengths");
+  std::vector<G1Affine> aff(points.size());
+  check(zkhip_g1_batch_normalize(points.data()->x, points.size(), aff.data()->x), "batch_normalize");
+  const G1 acc = best_multiexp(scalars, aff);
+  G1Affine out;
+  check(zkhip_g1_batch_normalize(acc.x, 1, out.x), "batch_normalize");
+  return out;
+}
+inline G1 to_g1(const G1Affine& a) {
+  G1 p;
+  std::memcpy(p.x, a.x, 32);
+  std::memcpy(p.y, a.y, 32);
+  const Fq one_q = fq_one();
+  std::memcpy(p.z, one_q.l, 32);
+  return p;
+}
+inline G2Affine g2_point(const std::array<uint64_t, 16>& w) { G2Affine p; std::memcpy(&p, w.data(), 128); return p; }
+// e(left, g2) e(right_negated, [s]_2) = 1
+inline bool final_pairing(const ParamsKZG& params, const G1Affine& left, const G1Affine& right_negated) {
+  return pairing_check({left, right_negated}, {g2_point(params.g2()), g2_point(params.s_g2())});
+}
+}  // namespace detail
+
+// `ParamsKZG::verify_opening` of the Python mirror: e(C - value G + z W, g2) e(-W, [s]_2) = 1, W a commitment to (p(X) - value) / (X - z)
+inline bool verify_opening(const ParamsKZG& params, const G1& commitment, const Fr& z, const Fr& value, const G1& witness) {
+  const G1Affine left = detail::g1_combination({detail::one(), detail::neg_fr(value), z}, {commitment, detail::to_g1(params.get_g()[0]), witness});
+  const G1Affine right_neg = detail::g1_combination({detail::neg_fr(detail::one())}, {witness});
+  return detail::final_pairing(params, left, right_neg);
+}
+
+// `VerifierGWC::verify_proof`: e(sum_i u^i W_i, [s]_2) = e(sum_i u^i (z_i W_i + sum_j v^j C_ij - (sum_j v^j e_ij) G), g2); sets as gwc_create_proof
+class VerifierGWC {
+ public:
+  explicit VerifierGWC(const ParamsKZG& params) : params_(params) {}
+  bool verify_proof(const std::vector<VerifierQuery>& queries, const std::vector<G1>& witnesses, const Fr& v, const Fr& u) const {
+    if (!detail::queries_consistent(queries)) return false;
+    std::vector<Fr> points;
+    for (const auto& q : queries) {
+      bool seen = false;
+      for (const Fr& p : points) seen = seen || p == q.point;
+      if (!seen) points.push_back(q.point);
+    }
+    if (points.size() != witnesses.size()) throw std::invalid_argument("VerifierGWC: one witness per distinct point");
+    std::vector<Fr> left, right;
+    std::vector<G1> right_points = witnesses;
+    Fr ui = detail::one(), g_scalar{};
+    for (const Fr& z : points) {
+      left.push_back(detail::neg_fr(ui));
+      right.push_back(detail::mul(ui, z));
+      ui = detail::mul(ui, u);
+    }
+    ui = detail::one();
+    for (const Fr& z : points) {
+      Fr vj = detail::one();
+      for (const auto& q : queries) {
+        if (!(q.point == z)) continue;
+        const Fr c = detail::mul(ui, vj);
+        right.push_back(c);
+        right_points.push_back(q.commitment);
+        g_scalar = detail::sub_fr(g_scalar, detail::mul(c, q.eval));
+        vj = detail::mul(vj, v);
+      }
+      ui = detail::mul(ui, u);
+    }
+    right.push_back(g_scalar);
+    right_points.push_back(detail::to_g1(params_.get_g()[0]));
+    return detail::final_pairing(params_, detail::g1_combination(right, right_points), detail::g1_combination(left, witnesses));
+  }
+
+ private:
+  const ParamsKZG& params_;
+};
+
+// `VerifierSHPLONK::verify_proof`: e(Lc + u H', g2) e(-H', [s]_2) = 1 with Lc = sum_ij c_ij (C_ij - R_ij(u) G) - Z_T(u) / Z_{T \ S_0}(u) H and
+// c_ij = v^i Z_{T \ S_i}(u) y^j / Z_{T \ S_0}(u); rotation sets as ShplonkProver::begin builds them, keyed by commitment
+class VerifierSHPLONK {
+ public:
+  explicit VerifierSHPLONK(const ParamsKZG& params) : params_(params) {}
+  bool verify_proof(const std::vector<VerifierQuery>& queries, const G1& H, const G1& Hp, const Fr& y, const Fr& v, const Fr& u) const {
+    if (!detail::queries_consistent(queries)) return false;
+    struct poly_pts { const VerifierQuery* poly; std::vector<Fr> pts; };       // a polynomial is named by its first query
+    struct rotation_set { std::vector<Fr> points; std::vector<const VerifierQuery*> polys; std::vector<std::vector<Fr>> evals; };
+    std::vector<poly_pts> by_poly;
+    std::vector<Fr> super;
+    auto insert_sorted = [](std::vector<Fr>& vset, const Fr& p) {
+      for (const Fr& e : vset) if (e == p) return;
+      auto it = vset.begin();
+      while (it != vset.end() && detail::less_fr(*it, p)) ++it;
+      vset.insert(it, p);
+    };
+    for (const auto& q : queries) {
+      insert_sorted(super, q.point);
+      bool found = false;
+      for (auto& pp : by_poly) if (detail::same_poly(*pp.poly, q)) { insert_sorted(pp.pts, q.point); found = true; break; }
+      if (!found) by_poly.push_back({&q, {q.point}});
+    }
+    auto same = [](const std::vector<Fr>& a, const std::vector<Fr>& b) {
+      if (a.size() != b.size()) return false;
+      for (size_t i = 0; i < a.size(); i++) if (!(a[i] == b[i])) return false;
+      return true;
+    };
+    std::vector<rotation_set> sets;
+    for (const auto& pp : by_poly) {
+      rotation_set* rs = nullptr;
+      for (auto& s_ : sets) if (same(s_.points, pp.pts)) rs = &s_;
+      if (!rs) { sets.push_back({pp.pts, {}, {}}); rs = &sets.back(); }
+      std::vector<Fr> ev;
+      for (const Fr& z : pp.pts)
+        for (const auto& q : queries) if (detail::same_poly(q, *pp.poly) && q.point == z) { ev.push_back(q.eval); break; }
+      rs->polys.push_back(pp.poly);
+      rs->evals.push_back(std::move(ev));
+    }
+    std::vector<Fr> z_diffs;
+    for (const auto& rs : sets) {
+      std::vector<Fr> diff;
+      for (const Fr& p : super) { bool in = false; for (const Fr& q : rs.points) in = in || q == p; if (!in) diff.push_back(p); }
+      z_diffs.push_back(detail::vanishing_at(diff, u));
+    }
+    const Fr norm = detail::invert(z_diffs[0]);
+    std::vector<Fr> scalars;
+    std::vector<G1> points;
+    Fr g_scalar{}, vi = detail::one();
+    for (size_t i = 0; i < sets.size(); i++) {
+      Fr yj = detail::one();
+      for (size_t j = 0; j < sets[i].polys.size(); j++) {
+        const Fr c = detail::mul(detail::mul(detail::mul(vi, z_diffs[i]), yj), norm);
+        scalars.push_back(c);
+        points.push_back(sets[i].polys[j]->commitment);
+        g_scalar = detail::sub_fr(g_scalar, detail::mul(c, detail::eval_small(detail::lagrange_interpolate(sets[i].points, sets[i].evals[j]), u)));
+        yj = detail::mul(yj, y);
+      }
+      vi = detail::mul(vi, v);
+    }
+    scalars.push_back(g_scalar);
+    points.push_back(detail::to_g1(params_.get_g()[0]));
+    scalars.push_back(detail::neg_fr(detail::mul(detail::vanishing_at(super, u), norm)));
+    points.push_back(H);
+    scalars.push_back(u);
+    points.push_back(Hp);
+    return detail::final_pairing(params_, detail::g1_combination(scalars, points), detail::g1_combination({detail::neg_fr(detail::one())}, {Hp}));
+  }
+
+ private:
+  const ParamsKZG& params_;
+};
+
 }  // namespace halo2
 }  // namespace zkhip

@@ -327,3 +327,23 @@ pub(crate) fn mock_on_device(gate_programs: &[VmProgramOwned], columns: &[*const
     }
     Some(out)
 }
+
+// ======================================================================================================================================
+// verify_proof's pairing on the device (opt-in)
+// ======================================================================================================================================
+//
+// The reference verifies every proof it makes: `gen_proof` ends in `assert!(verify_proof(..))` (/root/reference/aggregator/src/wrapper.rs:140-155)
+// and the IVC test in the decider's pairing check on (g[0], g2, s_g2) (wrapper.rs:1140-1158).  Both end in ONE product of two pairings: the
+// verifier's strategy (`SingleStrategy` / `AccumulatorStrategy` [DEP poly/kzg/strategy.rs]) folds every equation of the proof into a
+// `DualMSM { left, right }` with random linear combinations, evaluates the two multi-exponentiations (a few hundred points: the crate's CPU
+// body, see MIN_GPU_MSM) and asks `e(left, [s]_2) e(right, -g2) = 1`.  That accumulation stays the crate's; a host can hand the last step to the
+// device -- opt-in, `std::env::var_os("ZKHIP_VERIFY_ON_DEVICE").is_some()`, in `DualMSM::check` at the place of its `multi_miller_loop`:
+//
+//     let (left, right) = (self.left.eval().to_affine(), self.right.eval().to_affine());
+//     if let Some(accept) = verify_on_device(left, right, params.s_g2(), -params.g2()) { return accept; }     // None: the crate's own pairing
+//
+// Not covered: the scalar half of `verify_proof` (the expected quotient evaluation from the gate, permutation and lookup expressions at x) and the
+// transcript, which are host arithmetic on a few hundred field elements.
+pub(crate) fn verify_on_device<A: 'static + Copy, B: 'static + Copy>(left: A, right: A, s_g2: B, minus_g2: B) -> Option<bool> {
+    zkhip_ffi::pairing_check(&[left, right], &[s_g2, minus_g2])
+}

@@ -93,6 +93,9 @@ extern "C" {
     fn zkhip_fr_random(seed: *const u8, stream_id: u64, first: u64, n: usize, out: *mut u64) -> c_int;
     fn zkhip_fr_random_rows_device(seed: *const u8, stream_id: u64, first: u64, d_cols: *const *const c_void,
                                    n_cols: u32, row0: usize, count: usize, stream: *mut c_void) -> c_int;
+    // ---- pairing check (zkhip.h "pairing check"): is prod_i e(g1[i], g2[i]) the identity of Gt?  Only the verdict leaves the device ----------
+    fn zkhip_pairing_check(g1: *const u64, g2: *const u64, n: usize, ok: *mut c_int) -> c_int;
+    fn zkhip_pairing_check_device(d_g1: *const c_void, d_g2: *const c_void, n: usize, d_ok: *mut c_void, stream: *mut c_void) -> c_int;
 }
 
 /// `zkhip_vm_operand` / `zkhip_vm_insn` / `zkhip_vm_program` of include/zkhip.h (field order and widths checked by tests/test_rust_shim.py).
@@ -123,6 +126,8 @@ pub(crate) struct CheckReport { pub failures: u64, pub first: u64 }
 /// `zkhip_shplonk`: the state between the two steps of the SHPLONK prover (opaque)
 #[repr(C)]
 pub(crate) struct ShplonkState { _opaque: [u8; 0] }
+/// `ZKHIP_MAX_PAIRS`: the most pairs of one zkhip_pairing_check call
+pub(crate) const MAX_PAIRS: usize = 64;
 pub(crate) const VM_REGS: usize = 16;
 pub(crate) const SRC_CONST: u8 = 0;
 pub(crate) const SRC_REG: u8 = 1;
@@ -417,6 +422,24 @@ pub(crate) fn random_seed<R: rand_core::RngCore>(rng: &mut R) -> [u8; 32] {
     let mut seed = [0u8; 32];
     rng.fill_bytes(&mut seed);
     seed
+}
+
+/// `multi_miller_loop(&[(&g1[i], &G2Prepared::from(g2[i]))]).final_exponentiation().is_identity()` [DEP halo2curves bn256]: Some(verdict) when
+/// A = bn256::G1Affine, B = bn256::G2Affine (64 / 128 bytes: x | y, Montgomery limbs, the identity all zero) and the GPU call succeeded, None
+/// otherwise (the caller runs the crate's own pairing).  The points are not checked, as `multi_miller_loop` does not check them.
+pub(crate) fn pairing_check<A: 'static, B: 'static>(g1: &[A], g2: &[B]) -> Option<bool> {
+    if !(is::<A, G1Affine>() && is::<B, halo2curves::bn256::G2Affine>()) || std::mem::size_of::<B>() != 128 || g1.len() != g2.len() || g1.len() > MAX_PAIRS
+        || !usable() {
+        return None;
+    }
+    let mut ok: c_int = 0;
+    // SAFETY: the TypeId / size checks make &[A] = &[G1Affine] (64-byte elements) and &[B] = &[G2Affine] (128); the library borrows both for the call
+    let rc = unsafe { zkhip_pairing_check(g1.as_ptr() as *const u64, g2.as_ptr() as *const u64, g1.len(), &mut ok) };
+    if rc != 0 {
+        warn_once("zkhip_pairing_check", rc);
+        return None;
+    }
+    Some(ok != 0)
 }
 
 // ======================================================================================================================================

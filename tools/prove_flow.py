@@ -40,12 +40,19 @@ _SIDE_STREAM = None
 
 
 def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False,
-        sharded_key=False, lookups_one_call=True, device_randomness=False, mock=False, on_witness=None):
+        sharded_key=False, lookups_one_call=True, device_randomness=False, mock=False, on_witness=None, verify=False, corrupt_proof=None, on_proof=None):
     """mock: what the reference's `gen_proof` does before it proves (`MockProver::run(..).assert_satisfied()`,
     /root/reference/aggregator/src/wrapper.rs:117-123), over the columns where they lie: `mock.MockProver(..).assert_satisfied()` once the
     witness columns and the copy constraints exist, as lap `mock_prover` (not part of `prove_ms`).  A witness broken with `corrupt=` then raises
     an AssertionError that says where -- ("gate", gate, polynomial, row, rows) / ("copy", column, row, cells) / ("lookup", lookup, row, rows) --
     instead of the proof going on until a product does not close or the quotient is no polynomial.
+    verify: the third step of the reference's `gen_proof` (`assert!(verify_proof(..))`, wrapper.rs:140-155): a `VerifierQuery` for every `ProverQuery`
+    of the multi-open -- the commitments the flow has (advice, products, quotient pieces, the verifying key's fixed and sigma commitments), the
+    evaluations of its `evals` buffer and of the rotated openings -- through `VerifierSHPLONK`, ending in one pairing check on the device: check
+    "proof_verifies", lap `verify` (not part of `prove_ms`).  corrupt_proof: "eval" / "commitment" / "witness" change one evaluation, one
+    commitment or H' AFTER the prover has run: "proof_verifies" is then false and every other check stays true.
+    on_proof (with verify): a callable handed (params, k, queries, verifier queries, commit, (H, H'), (y, v, u)) after the verdict, while the
+    polynomials are still in HBM (tools/verify_time.py measures the verifiers there, on the flow's own plan); its time goes to the lap `verify`.
     on_witness: a callable handed (cs, k, fixed, advice, assembly, theta) at that same point, the columns being device tensors (tools/mock_time.py
     measures the checks there, on the flow's own witness).
     device_randomness: blinding tails through E.blind_rows_device (one call per step, whatever the number of columns) and the vanishing argument's
@@ -63,6 +70,8 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
 
     if sharded_key and not sharded_quotient:
         raise ValueError("sharded_key needs sharded_quotient")
+    if corrupt_proof not in (None, "eval", "commitment", "witness"):
+        raise ValueError("corrupt_proof: eval, commitment or witness")
     lib = _lib.load()
     dev = torch.device("cuda", 0)
     n, u = 1 << k, (1 << k) - (BLIND + 1)
@@ -449,22 +458,60 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             return out.cpu().numpy().view(np.uint64)
 
         y_mo, v_mo, u_mo = (rng.randrange(1, R) for _ in range(3))
-        mo_ok = True
+        mo_ok, mo_proof = True, None
         mo_prover = MO.ProverSHPLONK(k, commit_ptr)
         try:
-            mo_prover.create_proof(queries, y_mo, v_mo, u_mo)      # raises if L(u) != 0: an evaluation that does not belong to its polynomial
+            mo_proof = mo_prover.create_proof(queries, y_mo, v_mo, u_mo)      # raises if L(u) != 0: an evaluation that does not belong to its polynomial
         except ArithmeticError:
             mo_ok = False
         lap("multiopen_shplonk")
         mo_prover.close()
+
+        # ---- verify: what a verifier holds -- commitments, evaluations, H and H' -- and one pairing check --------------------------------------
+        proof_verifies = None
+        if verify:
+            jac = lambda t_: t_.cpu().numpy().view(np.uint64).reshape(12).copy()
+            commitment_of = {}
+            for i in range(qc.fixed, qc.advice):
+                commitment_of[coeff[i].data_ptr()] = MO._affine_to_xyz(vk.fixed_commitments[i - qc.fixed])
+            for i in range(len(advice)):
+                commitment_of[coeff[qc.advice + i].data_ptr()] = jac(adv_commit[i])
+            for i in range(len(perm_cols)):
+                commitment_of[coeff[qc.sigma + i].data_ptr()] = MO._affine_to_xyz(vk.permutation_commitments[i])
+            for j, c_ in enumerate(prod_commit):
+                commitment_of[coeff[first_prover_poly + j].data_ptr()] = jac(c_)
+            for i in range(3):
+                commitment_of[h_coeff[i * n:].data_ptr()] = jac(h_commit[i])
+            at_x = dict(zip([int(p_) for p_ in ptrs], F.fr_decode(evals.cpu().numpy().view(np.uint64))))      # the evaluations at x of the `evals` buffer
+            # (poly_id: the G selector columns are equal, and so are their commitments -- a verifier tells them apart as the prover does)
+            vqueries = [MO.VerifierQuery(q.point, commitment_of[q.poly], at_x[q.poly] if q.point == rot(0) else q.eval, poly_id=q.poly) for q in queries]
+            proof_verifies = False
+            if mo_proof is not None:
+                H_mo, Hp_mo = mo_proof
+                if corrupt_proof == "eval":
+                    vqueries[len(vqueries) // 2].eval = (vqueries[len(vqueries) // 2].eval + 1) % R
+                elif corrupt_proof == "commitment":
+                    vqueries[0].commitment = vqueries[-1].commitment                  # the first fixed column's opening names a quotient piece's commitment
+                elif corrupt_proof == "witness":
+                    moved = np.zeros(12, dtype=np.uint64)
+                    both = np.stack([Hp_mo, MO._generator_xyz(params)])
+                    _lib.check(lib.zkhip_g1_sum(both.ctypes.data, 2, moved.ctypes.data))     # H' + G: another curve point
+                    Hp_mo = moved
+                proof_verifies = MO.VerifierSHPLONK(params).verify_proof(vqueries, H_mo, Hp_mo, y_mo, v_mo, u_mo)
+            lap("verify")
+            if on_proof is not None and mo_proof is not None:
+                on_proof(params, k, queries, vqueries, commit_ptr, mo_proof, (y_mo, v_mo, u_mo))
+                lap("on_proof")
 
         top_is_zero = not bool(h_coeff[3 * n:].any().item())
         low_nonzero = bool(h_coeff[:3 * n].any().item())
         commit_agrees = affine(adv_commit[0]) == affine(a0_coeff_commit)
         checks = {"permutation_product_closes": perm_closes, "lookup_product_closes": lookup_closes, "quotient_is_a_polynomial": top_is_zero and low_nonzero,
                   "commit_lagrange_equals_commit_coeff": commit_agrees, "multiopen_linearisation_vanishes": mo_ok}
+        if verify:
+            checks["proof_verifies"] = proof_verifies
         n_msm = len(adv_commit) + len(prod_commit) + 1 + len(h_commit) + 2
-        prove_ms = sum(v for kk, v in t.items() if kk not in ("setup_srs", "witness_columns", "mock_prover", "stack_columns", "pk_file_round_trip", "pk_upload") and not kk.startswith("keygen_"))
+        prove_ms = sum(v for kk, v in t.items() if kk not in ("setup_srs", "witness_columns", "mock_prover", "stack_columns", "pk_file_round_trip", "pk_upload", "verify", "on_proof") and not kk.startswith("keygen_"))
         n_proof_cols = sum(hi - lo for lo, hi in proof_ranges)
         if verbose:
             print(f"k={k} gate_cols={G} lookups={NL}{' (batched commits)' if batched else ''}: {ncol} columns ({n_proof_cols} witness-dependent, {ncol - n_proof_cols} of the proving key), {n_msm} MSMs of 2^{k}, "
@@ -485,10 +532,10 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
 
 
 if __name__ == "__main__":
-    dr, mk = "--device-randomness" in sys.argv, "--mock" in sys.argv
-    sys.argv = [a for a in sys.argv if a not in ("--device-randomness", "--mock")]
+    dr, mk, vf = "--device-randomness" in sys.argv, "--mock" in sys.argv, "--verify" in sys.argv
+    sys.argv = [a for a in sys.argv if a not in ("--device-randomness", "--mock", "--verify")]
     kk = int(sys.argv[1]) if len(sys.argv) > 1 else 16
     gg = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     ll = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-    res = run(kk, gg, lookups=ll, device_randomness=dr, mock=mk)
+    res = run(kk, gg, lookups=ll, device_randomness=dr, mock=mk, verify=vf)
     sys.exit(0 if all(res["checks"].values()) else 1)

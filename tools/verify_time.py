@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""The pairing check and the verifiers built on it, timed on one MI355X: one process, clocks warmed first, 9 repetitions, wall ms, medians; every
+timed region ends with the verdict on the host.
+
+  zkhip_pairing_check at n = 2 and n = 64 (host form: upload, kernel, verdict back)
+  the check of two pairs as ONE serial chain through the quad policy and through the single-lane policy (hook operation 11 of
+      zkhip_test_fq12_op): the measured gain of sharing every Fq2 product among four lanes
+  VerifierSHPLONK / VerifierGWC on the plans tools/prove_flow.py opens at (k, gate columns, lookups) = (22, 4, 1), (13, 256, 8), (15, 64, 8), split
+      into the G1 side (normalisation + small MSMs) and the pairing
+  ParamsKZG.verify at k = 22
+  the `verify` lap of prove_flow.run(verify=True) beside prove_ms, three warm proofs per shape
+    python tools/verify_time.py [--reps 9] [--shapes 22:4:1,13:256:8,15:64:8] [--no-flow] [--no-srs]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, os.path.dirname(__file__))
+import numpy as np
+import torch
+
+from oracle import bn254 as O
+from zksnap_circuits_halo2_amd import _lib, arithmetic as A, fields as F, kzg, multiopen as MO, srs
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=9)
+ap.add_argument("--shapes", default="22:4:1,13:256:8,15:64:8")
+ap.add_argument("--no-flow", action="store_true")
+ap.add_argument("--no-srs", action="store_true")
+ap.add_argument("--srs-k", type=int, default=22)
+args = ap.parse_args()
+lib = _lib.load()
+R = O.R_MOD
+
+
+def fmt(ts):
+    return f"min {min(ts):.3f} median {statistics.median(ts):.3f} max {max(ts):.3f}"
+
+
+def timed(fn, reps=None, warm_s=0.5):
+    t_end = time.perf_counter() + warm_s
+    while True:
+        fn()
+        if time.perf_counter() >= t_end:
+            break
+    out = []
+    for _ in range(reps or args.reps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t) * 1e3)
+    return out
+
+
+# ---- the check itself ------------------------------------------------------------------------------------------------------------------------
+def pairs(n):
+    """n pairs (a_i G, b_i H) with sum a_i b_i = 0: 4 distinct points on either side"""
+    a = [3 + i for i in range(4)]
+    b = [11 + i for i in range(4)]
+    ab = [(a[i % 4], b[(i // 4) % 4]) for i in range(n - 1)]
+    s = sum(x * y for x, y in ab) % R
+    ab.append((R - s, 1))
+    g1 = F.g1_encode([O.scalar_mul(x % R, O.G1_GEN) for x, _ in ab])
+    g2 = np.stack([srs.g2_encode(srs.g2_mul(y % R)) for _, y in ab])
+    return g1, g2
+
+
+print(f"zkhip_pairing_check, host form ({args.reps} repetitions, wall ms, the verdict on the host)")
+for n in (2, 64):
+    g1, g2 = pairs(n)
+    assert A.pairing_check(g1, g2)
+    print(f"    n = {n:2d}                                                  {fmt(timed(lambda: A.pairing_check(g1, g2)))}")
+g1, g2 = pairs(2)
+operand = np.concatenate([g1.reshape(-1), g2.reshape(-1)]).astype(np.uint64)
+out = np.zeros(96, dtype=np.uint64)
+med = {}
+for name, flag in (("quad policy", 256), ("single-lane policy", 512)):
+    def run(flag=flag):
+        _lib.check(lib.zkhip_test_fq12_op(11 + flag, operand.ctypes.data, operand.ctypes.data, out.ctypes.data))
+    run()
+    assert out[0 if flag == 256 else 48] == 1
+    ts = timed(run)
+    med[name] = statistics.median(ts)
+    print(f"    two pairs as one serial chain, {name:20s}        {fmt(ts)}")
+print(f"    single-lane / quad = {med['single-lane policy'] / med['quad policy']:.2f}")
+
+# ---- ParamsKZG.verify ------------------------------------------------------------------------------------------------------------------------
+if not args.no_srs:
+    t0 = time.perf_counter()
+    with kzg.ParamsKZG.setup(args.srs_k, 0x1122334455667788) as params:
+        print(f"ParamsKZG.verify at k = {args.srs_k} (setup {time.perf_counter() - t0:.1f} s, not timed)")
+        seed = bytes(range(32))
+        assert params.verify(seed)
+        print(f"    verify                                                  {fmt(timed(lambda: params.verify(seed), reps=3, warm_s=0.0))}")
+
+# ---- the verifiers on the flow's plans, and the flow's own lap ---------------------------------------------------------------------------------
+if not args.no_flow:
+    import prove_flow
+
+    for shape in args.shapes.split(","):
+        k, g, l = (int(x) for x in shape.split(":"))
+        print(f"==== prove_flow shape k = {k}, {g} gate columns, {l} lookups ====")
+
+        def measure(params, k_, queries, vqueries, commit, proof, challenges):
+            H, Hp = proof
+            y, v, u = challenges
+            Gx = MO._generator_xyz(params)
+            pair = lambda left, right_neg: A.pairing_check(np.stack([left, right_neg]), np.stack([params.g2, params.s_g2]))
+            # SHPLONK
+            def g1_side():
+                scalars, commitments = MO.shplonk_accumulate(vqueries, y, v, u)
+                left = A.g1_combination(scalars, np.stack(MO.commitment_points(vqueries, commitments) + [Gx, H, Hp]))
+                return left, A.g1_combination([-1], Hp.reshape(1, 12))
+            left, right_neg = g1_side()
+            assert pair(left, right_neg)
+            print(f"    VerifierSHPLONK: {len(vqueries)} queries, {len(MO.shplonk_accumulate(vqueries, y, v, u)[1]) + 3} points")
+            print(f"      G1 side (scalars, normalisation, MSM)                 {fmt(timed(g1_side))}")
+            print(f"      pairing check                                         {fmt(timed(lambda: pair(left, right_neg)))}")
+            print(f"      verify_proof                                          {fmt(timed(lambda: MO.VerifierSHPLONK(params).verify_proof(vqueries, H, Hp, y, v, u)))}")
+            # GWC on the same plan
+            gwc = MO.ProverGWC(k_, commit)
+            fresh = [MO.ProverQuery(q.point, q.poly, q.eval) for q in queries]
+            W = gwc.create_proof(fresh, v)
+            gwc.close()
+            def g1_side_gwc():
+                lft, rgt, commitments = MO.gwc_accumulate(vqueries, len(W), v, u)
+                Wl = [np.ascontiguousarray(w, dtype=np.uint64).reshape(12) for w in W]
+                return A.g1_combination(rgt, np.stack(Wl + MO.commitment_points(vqueries, commitments) + [Gx])), A.g1_combination([-s for s in lft], np.stack(Wl))
+            left_g, right_g = g1_side_gwc()
+            assert pair(left_g, right_g)
+            print(f"    VerifierGWC: {len(W)} witnesses")
+            print(f"      G1 side (scalars, normalisation, MSM)                 {fmt(timed(g1_side_gwc))}")
+            print(f"      pairing check                                         {fmt(timed(lambda: pair(left_g, right_g)))}")
+            print(f"      verify_proof                                          {fmt(timed(lambda: MO.VerifierGWC(params).verify_proof(vqueries, W, v, u)))}")
+
+        prove_flow.run(k, g, lookups=l, verbose=False, verify=True, on_proof=measure)
+        laps = []
+        for _ in range(3):
+            res = prove_flow.run(k, g, lookups=l, verbose=False, verify=True)
+            assert all(res["checks"].values())
+            laps.append((res["timings_ms"]["verify"], res["prove_ms"]))
+        print("    flow, three warm proofs: verify lap / prove_ms = " + ", ".join(f"{a:.1f} / {b:.1f}" for a, b in laps))

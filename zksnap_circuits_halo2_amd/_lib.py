@@ -8,6 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libzkhip.so")
 ZKHIP_MAX_ROOTS = 8          # include/zkhip.h: the most roots of one zkhip_fr_divide_by_roots call
+ZKHIP_MAX_PAIRS = 64         # include/zkhip.h: the most pairs of one zkhip_pairing_check call
 
 # every symbol include/zkhip.h declares (tests check the export list against the header)
 _SIGS = {
@@ -130,6 +131,9 @@ _SIGS = {
     "zkhip_profile_read_calls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "zkhip_test_field_op": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "zkhip_test_g1_op": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "zkhip_pairing_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
+    "zkhip_pairing_check_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zkhip_test_fq12_op": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

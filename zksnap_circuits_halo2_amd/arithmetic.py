@@ -36,6 +36,35 @@ def best_multiexp_g2(coeffs: np.ndarray, bases: np.ndarray) -> np.ndarray:
     return out
 
 
+def pairing_check(g1: np.ndarray, g2: np.ndarray) -> bool:
+    """Is prod_i e(g1[i], g2[i]) the identity of Gt?  (`multi_miller_loop(..).final_exponentiation().is_identity()` [DEP halo2curves].)
+    g1: (n,8) uint64 G1Affine, g2: (n,16) uint64 G2Affine, n <= 64; a pair with an identity contributes 1.  The points are not checked."""
+    import ctypes as C
+
+    g1 = np.ascontiguousarray(g1, dtype=np.uint64).reshape(-1, 8)
+    g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(-1, 16)
+    assert g1.shape[0] == g2.shape[0], "g1.len() != g2.len()"
+    ok = C.c_int(0)
+    _lib.check(_lib.load().zkhip_pairing_check(_ptr(g1), _ptr(g2), g1.shape[0], C.byref(ok)))
+    return bool(ok.value)
+
+
+def g1_combination(scalars, points_xyz: np.ndarray) -> np.ndarray:
+    """sum_i scalars[i] * points[i] for Python-integer scalars and Jacobian points ((n,12) uint64) -> (8,) uint64 G1Affine: the points are
+    normalised (`batch_normalize`), then one small MSM, then the result is normalised -- the G1 side of the verifiers"""
+    from .fields import R_MOD, fr_encode
+
+    pts = np.ascontiguousarray(points_xyz, dtype=np.uint64).reshape(-1, 12)
+    assert len(scalars) == pts.shape[0]
+    lib = _lib.load()
+    aff = np.zeros((pts.shape[0], 8), dtype=np.uint64)
+    _lib.check(lib.zkhip_g1_batch_normalize(_ptr(pts), pts.shape[0], _ptr(aff)))
+    acc = best_multiexp(fr_encode([s % R_MOD for s in scalars]), aff)
+    out = np.zeros(8, dtype=np.uint64)
+    _lib.check(lib.zkhip_g1_batch_normalize(_ptr(acc), 1, _ptr(out)))
+    return out
+
+
 def best_fft(a: np.ndarray, omega: np.ndarray, log_n: int) -> None:
     """In-place NTT of a ((2^log_n, 4) uint64 Fr) with the (4,) uint64 root `omega`."""
     assert a.dtype == np.uint64 and a.flags.c_contiguous

@@ -3038,4 +3038,55 @@ int zkhip_test_g2_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out
   return H.finish();
 }
 
+// ---- pairing check (pairing.hip) ------------------------------------------------------------------------------------------------------
+int zkhip_pairing_check_device(const void* d_g1, const void* d_g2, size_t n, void* d_ok, void* stream) {
+  ZK_API_RANGE();
+  if (!d_ok || n > ZKHIP_MAX_PAIRS || (n && (!d_g1 || !d_g2))) { set_error("pairing_check: null pointer or more than %d pairs", ZKHIP_MAX_PAIRS); return ZKHIP_EINVAL; }
+  // the kernel reads the pairs with 16-byte vector loads and stores the verdict as one 32-bit word
+  if ((n && (((uintptr_t)d_g1 | (uintptr_t)d_g2) & 15)) || ((uintptr_t)d_ok & 3)) { set_error("pairing_check: d_g1 / d_g2 must be 16-byte aligned, d_ok 4-byte aligned"); return ZKHIP_EINVAL; }
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  return pairing_check_device((const uint32_t*)d_g1, (const uint32_t*)d_g2, n, (uint32_t*)d_ok, caller_stream(stream));
+}
+
+int zkhip_pairing_check(const uint64_t* g1, const uint64_t* g2, size_t n, int* ok) {
+  ZK_API_RANGE();
+  if (!ok || n > ZKHIP_MAX_PAIRS || (n && (!g1 || !g2))) { set_error("pairing_check: null pointer or more than %d pairs", ZKHIP_MAX_PAIRS); return ZKHIP_EINVAL; }
+  lane_hold H;
+  if (H.rc != ZKHIP_OK) return H.rc;
+  int rc;
+  hipStream_t s = H.s;
+  if ((rc = H.sc->poly.reserve(ZKHIP_MAX_PAIRS * (64 + 128) + 64)) != ZKHIP_OK) return rc;
+  char* d = (char*)H.sc->poly.p;                             // g1 | g2 | verdict
+  if (n) {
+    HIPCHK(hipMemcpyAsync(d, g1, n * 64, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d + ZKHIP_MAX_PAIRS * 64, g2, n * 128, hipMemcpyHostToDevice, s));
+  }
+  uint32_t* d_ok = (uint32_t*)(d + ZKHIP_MAX_PAIRS * (64 + 128));
+  if ((rc = pairing_check_device((const uint32_t*)d, (const uint32_t*)(d + ZKHIP_MAX_PAIRS * 64), n, d_ok, s)) != ZKHIP_OK) return rc;
+  HIPCHK(hipMemcpyAsync(H.L->pinned, d_ok, 4, hipMemcpyDeviceToHost, s));
+  if ((rc = H.finish()) != ZKHIP_OK) return rc;
+  *ok = *(const uint32_t*)H.L->pinned ? 1 : 0;
+  return ZKHIP_OK;
+}
+
+int zkhip_test_fq12_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out) {
+  ZK_API_RANGE();
+  const int which = (op & 256) ? 1 : ((op & 512) ? 2 : 3), base_op = op & 255;
+  if (op < 0 || (op & ~(255 | 256 | 512)) || base_op > 11 || !a || !b || !out) { set_error("test_fq12_op: bad argument"); return ZKHIP_EINVAL; }
+  lane_hold H;
+  if (H.rc != ZKHIP_OK) return H.rc;
+  int rc;
+  hipStream_t s = H.s;
+  if ((rc = H.sc->poly.reserve(4 * 384)) != ZKHIP_OK) return rc;
+  char* d = (char*)H.sc->poly.p;
+  HIPCHK(hipMemcpyAsync(d, a, 384, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d + 384, b, 384, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d + 768, out, 768, hipMemcpyHostToDevice, s));       // the half that is not computed stays as the caller had it
+  if ((rc = test_fq12_op(base_op, which, (const uint32_t*)d, (const uint32_t*)(d + 384), (uint32_t*)(d + 768), s)) != ZKHIP_OK) return rc;
+  HIPCHK(hipMemcpyAsync(out, d + 768, 768, hipMemcpyDeviceToHost, s));
+  return H.finish();
+}
+
 }  // extern "C"

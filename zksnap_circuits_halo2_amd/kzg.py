@@ -200,6 +200,77 @@ class ParamsKZG:
         _lib.check(_lib.load().zkhip_msm_g1_batch(polys.ctypes.data, bases.ctypes.data, polys.shape[1], polys.shape[0], out.ctypes.data))
         return out
 
+    # ---- verification (the pairing check: zkhip_pairing_check) ------------------------------------------------------------------------
+    def _g_xyz(self) -> np.ndarray:
+        from .multiopen import _generator_xyz
+
+        return _generator_xyz(self)
+
+    def verify_opening(self, commitment: np.ndarray, z: int, value: int, witness: np.ndarray) -> bool:
+        """The single-point KZG check e(C - value G + z W, g2) e(-W, [s]_2) = 1: `witness` commits to (p(X) - value) / (X - z).
+        commitment, witness: 12-limb Jacobian points."""
+        from .arithmetic import g1_combination, pairing_check
+
+        if self.g2 is None or self.s_g2 is None:
+            raise ValueError("verify_opening needs g2 and s_g2")
+        C_ = np.ascontiguousarray(commitment, dtype=np.uint64).reshape(12)
+        W = np.ascontiguousarray(witness, dtype=np.uint64).reshape(12)
+        left = g1_combination([1, -value, z], np.stack([C_, self._g_xyz(), W]))
+        right_neg = g1_combination([-1], W.reshape(1, 12))
+        return pairing_check(np.stack([left, right_neg]), np.stack([self.g2, self.s_g2]))
+
+    def verify(self, seed: bytes) -> bool:
+        """Is this a powers-of-tau string with its Lagrange table?  What `read` / `read_custom` can be followed by: a file's points are checked
+        to be on the curve when it is read, but only a pairing can tell whether g[i] = [s^i] G for the s of s_g2 (nobody knows s for a real file).
+        (a) every point of g and g_lagrange on the curve; g2 and s_g2 on the twist and of order r (msm_g2([r - 1], [Q]) = -Q: an Fr scalar cannot hold r);
+        (b) with rho drawn from `seed`: e(sum rho_i g[i + 1], g2) = e(sum rho_i g[i], [s]_2) -- one false g[i] passes with probability 1 / r;
+        (c) g[0] and g2 are not the identity;
+        (d) with a second vector rho': commit_lagrange(rho') = commit(lagrange_to_coeff(rho')).
+        `seed`: 32 bytes of the caller's own randomness."""
+        import ctypes as C
+
+        from . import srs
+        from .arithmetic import best_multiexp, best_multiexp_g2, g1_combination, pairing_check, random_fr
+        from .domain import EvaluationDomain
+        from .fields import R_MOD, fr_encode
+
+        if self.g_lagrange is None or self.g2 is None or self.s_g2 is None:
+            return False
+        lib = _lib.load()
+        n = self.n
+        # (a), (c)
+        for table in (self.g, self.g_lagrange):
+            bad = C.c_uint64(0)
+            _lib.check(lib.zkhip_g1_check_points(table.ctypes.data, n, C.byref(bad)))
+            if bad.value != n:
+                return False
+        if not self.g[0].any() or not self.g2.any():
+            return False
+        minus_one = fr_encode([R_MOD - 1])
+        for q2 in (self.g2, self.s_g2):
+            try:
+                P = srs.g2_decode(q2)
+            except Exception:   # noqa: BLE001  (not canonical)
+                return False
+            if P is None or not srs.g2_is_on_curve(P):
+                return False
+            if _g2_jacobian_to_affine(best_multiexp_g2(minus_one, q2.reshape(1, 16))) != (P[0], srs._f2sub((0, 0), P[1])):
+                return False
+        # (b)
+        if n > 1:
+            rho = random_fr(seed, n - 1, stream_id=0x5352535F52484F31)
+            left = g1_combination([1], best_multiexp(rho, self.g[1:]).reshape(1, 12))
+            right_neg = g1_combination([-1], best_multiexp(rho, self.g[: n - 1]).reshape(1, 12))
+            if not pairing_check(np.stack([left, right_neg]), np.stack([self.g2, self.s_g2])):
+                return False
+        # (d)
+        rho2 = random_fr(seed, n, stream_id=0x5352535F52484F32)
+        dom = EvaluationDomain(2, self.k)
+        coeffs = dom.lagrange_to_coeff(rho2.copy())
+        lhs = g1_combination([1], self.commit_lagrange(rho2).reshape(1, 12))
+        rhs = g1_combination([1], self.commit(coeffs).reshape(1, 12))
+        return bool(np.array_equal(lhs, rhs))
+
     def close(self) -> None:
         """end the residency of g / g_lagrange (idempotent); also runs when the object is garbage-collected"""
         self._finalizer()
@@ -224,3 +295,18 @@ def _unregister_arrays(arrays, was_writeable=()) -> None:
                 a.flags.writeable = True
             except ValueError:   # a view of a read-only base
                 pass
+
+
+def _g2_jacobian_to_affine(xyz: np.ndarray):
+    """24 limbs (x | y | z over Fq2, Montgomery) -> ((x0, x1), (y0, y1)) as integers, None for the identity"""
+    from . import srs
+    from .fields import Q_MOD
+
+    inv_r = pow(1 << 256, -1, Q_MOD)
+    v = [sum(int(w) << (64 * j) for j, w in enumerate(xyz[4 * c:4 * c + 4])) * inv_r % Q_MOD for c in range(6)]
+    X, Y, Zc = (v[0], v[1]), (v[2], v[3]), (v[4], v[5])
+    if Zc == (0, 0):
+        return None
+    zi = srs._f2inv(Zc)
+    zi2 = srs._f2mul(zi, zi)
+    return srs._f2mul(X, zi2), srs._f2mul(Y, srs._f2mul(zi2, zi))

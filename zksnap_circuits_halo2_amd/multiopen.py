@@ -307,3 +307,160 @@ class ProverSHPLONK:
         finally:
             _lib.check(lib.zkhip_sync())
             self.pool.give_back(bufs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The verifiers: `VerifierGWC::verify_proof` / `VerifierSHPLONK::verify_proof` [DEP poly/kzg/multiopen/{gwc,shplonk}/verifier.rs], the third
+# step of the reference's `gen_proof` (`assert!(verify_proof(..))`, /root/reference/aggregator/src/wrapper.rs:140-155).  They accept exactly
+# what the provers above emit and use the same set construction, keyed by commitment instead of device address (see VerifierQuery.poly_id for
+# polynomials whose commitments are equal).  The scalars are Python integers, the G1 side is one small MSM through zkhip_msm_g1 per
+# accumulated point, and the end is one zkhip_pairing_check of two pairs: e(L, g2) e(-R, [s]_2) = 1.  The transcript is the host's business.
+# ---------------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class VerifierQuery:
+    """`VerifierQuery { point, commitment, eval }`: `commitment` is a 12-limb Jacobian point (what `commit` returns).  The set construction
+    groups queries by polynomial; a verifier knows a polynomial by its commitment's bytes.  Two DIFFERENT polynomials of a proof may have EQUAL
+    commitments (two selector columns with the same rows): halo2 tells them apart by the address of the commitment (`CommitmentReference`
+    compares pointers), here `poly_id` -- any hashable value, one per polynomial -- does, and must then be given for every query
+    (`check_queries` refuses a mixture)."""
+    point: int
+    commitment: np.ndarray
+    eval: int
+    poly_id: object = None
+
+    @property
+    def poly(self):                   # the key the set construction groups by
+        if self.poly_id is not None:
+            return self.poly_id
+        return np.ascontiguousarray(self.commitment, dtype=np.uint64).reshape(12).tobytes()
+
+
+class InconsistentQueries(ValueError):
+    """the queries contradict each other: a verifier rejects"""
+
+
+def check_queries(queries: Sequence[VerifierQuery]) -> None:
+    """What the set construction would otherwise hide.  It was written for the prover, whose repeated queries agree by construction: it keeps the
+    FIRST evaluation of a (polynomial, point) pair and one commitment per key.  A verifier's queries are claims: two different evaluations of one
+    polynomial at one point, or two different commitments under one `poly_id`, raise InconsistentQueries (the verifiers answer False), so that a
+    changed claim cannot hide behind a repeated query.  `poly_id` on some queries and not on others is a ValueError: the keys would not be comparable."""
+    with_id = sum(q.poly_id is not None for q in queries)
+    if with_id not in (0, len(queries)):
+        raise ValueError("VerifierQuery.poly_id: give it for every query or for none")
+    commitment_of, eval_at = {}, {}
+    for q in queries:
+        key = q.poly
+        c = np.ascontiguousarray(q.commitment, dtype=np.uint64).reshape(12).tobytes()
+        if commitment_of.setdefault(key, c) != c:
+            raise InconsistentQueries("two commitments for one polynomial")
+        if eval_at.setdefault((key, q.point % R_MOD), q.eval % R_MOD) != q.eval % R_MOD:
+            raise InconsistentQueries("two evaluations of one polynomial at one point")
+
+
+def commitment_points(queries, keys) -> List[np.ndarray]:
+    """the commitments (12 limbs each) of the polynomial keys that an accumulation returned"""
+    by_key = {q.poly: np.ascontiguousarray(q.commitment, dtype=np.uint64).reshape(12) for q in queries}
+    return [by_key[k] for k in keys]
+
+
+def _affine_to_xyz(point: np.ndarray) -> np.ndarray:
+    """G1Affine (8 limbs, not the identity) -> Jacobian (12 limbs) with z = 1"""
+    out = np.zeros(12, dtype=np.uint64)
+    out[:8] = np.asarray(point, dtype=np.uint64).reshape(8)
+    out[8:] = _FQ_ONE
+    return out
+
+
+def _generator_xyz(params) -> np.ndarray:
+    """g[0] as a Jacobian point"""
+    return _affine_to_xyz(params.g[0])
+
+
+_FQ_ONE = np.array([0xd35d438dc58f0d9d, 0x0a78eb28f5c70b3d, 0x666ea36f7879462c, 0x0e0a77c19a07df2f], dtype=np.uint64)      # 2^256 mod q: 1 in Fq's Montgomery form
+
+
+def gwc_accumulate(queries: Sequence[VerifierQuery], n_witnesses: int, v: int, u: int):
+    """-> (scalars of the left point over the witnesses, scalars of the right point over [witnesses | commitments | G], the commitments in order):
+    left = sum_i u^i W_i, right = sum_i u^i (z_i W_i + sum_j v^j C_ij - (sum_j v^j e_ij) G)"""
+    check_queries(queries)
+    sets = construct_intermediate_sets(queries)
+    if len(sets) != n_witnesses:
+        raise ValueError("GWC: one witness per distinct point")
+    left, right_w, commitments, right_c, g_scalar = [], [], [], [], 0
+    for i, (z, qs) in enumerate(sets):
+        ui = pow(u, i, R_MOD)
+        left.append(ui)
+        right_w.append(ui * z % R_MOD)
+        for j, q in enumerate(qs):
+            vj = pow(v, j, R_MOD)
+            commitments.append(q.poly)
+            right_c.append(ui * vj % R_MOD)
+            g_scalar = (g_scalar - ui * vj % R_MOD * q.eval) % R_MOD
+    return left, right_w + right_c + [g_scalar], commitments
+
+
+def shplonk_accumulate(queries: Sequence[VerifierQuery], y: int, v: int, u: int):
+    """-> (scalars over [commitments | G | H | H'], the commitments in order) of the left point Lc + u H' with
+    Lc = sum_ij c_ij (C_ij - R_ij(u) G) - Z_T(u) / Z_{T \\ S_0}(u) H, c_ij = v^i Z_{T \\ S_i}(u) y^j / Z_{T \\ S_0}(u) (the comment block above
+    ProverSHPLONK); the right point is H'"""
+    check_queries(queries)
+    sets, super_points = construct_rotation_sets(queries)
+    z_diffs = [_vanishing_at([p for p in super_points if p not in rs.points], u) for rs in sets]
+    norm = pow(z_diffs[0], -1, R_MOD)
+    commitments, coeffs, g_scalar = [], [], 0
+    for i, rs in enumerate(sets):
+        for j, key in enumerate(rs.polys):
+            c = pow(v, i, R_MOD) * z_diffs[i] % R_MOD * pow(y, j, R_MOD) % R_MOD * norm % R_MOD
+            commitments.append(key)
+            coeffs.append(c)
+            g_scalar = (g_scalar - c * _eval_small(_interpolate(rs.points, rs.evals[j]), u)) % R_MOD
+    h_scalar = (-_vanishing_at(super_points, u) * norm) % R_MOD
+    return coeffs + [g_scalar, h_scalar, u % R_MOD], commitments
+
+
+def _final_check(params, left_affine: np.ndarray, right_affine_negated: np.ndarray) -> bool:
+    from .arithmetic import pairing_check
+
+    if params.g2 is None or params.s_g2 is None:
+        raise ValueError("the verifier needs g2 and s_g2")
+    return pairing_check(np.stack([left_affine, right_affine_negated]), np.stack([params.g2, params.s_g2]))
+
+
+class VerifierGWC:
+    """`VerifierGWC::new(params)` / `verify_proof`: e(sum_i u^i W_i, [s]_2) = e(sum_i u^i (z_i W_i + sum_j v^j C_ij - (sum_j v^j e_ij) G), g2).
+    `witnesses`: what `ProverGWC.create_proof` returned; v the prover's challenge, u the verifier's own."""
+
+    def __init__(self, params):
+        self.params = params
+
+    def verify_proof(self, queries: Sequence[VerifierQuery], witnesses: Sequence[np.ndarray], v: int, u: int) -> bool:
+        from .arithmetic import g1_combination
+
+        try:
+            left, right, commitments = gwc_accumulate(queries, len(witnesses), v, u)
+        except InconsistentQueries:
+            return False
+        W = [np.ascontiguousarray(w, dtype=np.uint64).reshape(12) for w in witnesses]
+        R_pt = g1_combination(right, np.stack(W + commitment_points(queries, commitments) + [_generator_xyz(self.params)]))
+        L_neg = g1_combination([-s for s in left], np.stack(W))
+        return _final_check(self.params, R_pt, L_neg)
+
+
+class VerifierSHPLONK:
+    """`VerifierSHPLONK::new(params)` / `verify_proof`: e(Lc + u H', g2) e(-H', [s]_2) = 1.  H, Hp: what `ProverSHPLONK.create_proof` returned."""
+
+    def __init__(self, params):
+        self.params = params
+
+    def verify_proof(self, queries: Sequence[VerifierQuery], H: np.ndarray, Hp: np.ndarray, y: int, v: int, u: int) -> bool:
+        from .arithmetic import g1_combination
+
+        try:
+            scalars, commitments = shplonk_accumulate(queries, y, v, u)
+        except InconsistentQueries:
+            return False
+        H = np.ascontiguousarray(H, dtype=np.uint64).reshape(12)
+        Hp = np.ascontiguousarray(Hp, dtype=np.uint64).reshape(12)
+        left = g1_combination(scalars, np.stack(commitment_points(queries, commitments) + [_generator_xyz(self.params), H, Hp]))
+        right_neg = g1_combination([-1], Hp.reshape(1, 12))
+        return _final_check(self.params, left, right_neg)

@@ -198,6 +198,9 @@ int zkhip_fr_eval_rows_device(const zkhip_vm_program *prog, const void *const *d
  * launching anything (no device needed), e.g. at keygen, so that the first proof does not pay the seconds of compilation. */
 int zkhip_vm_jit_source(const zkhip_vm_program *prog, uint32_t n_columns, uint32_t log_rows, char *buf, size_t cap, size_t *len);
 int zkhip_vm_jit_compile(const zkhip_vm_program *prog, uint32_t n_columns, uint32_t log_rows, size_t *code_bytes);
+/* Test hook: how many row-program launches of this process went through a compiled kernel (every entry point: whole-domain, window, sharded;
+ * never reset).  The interpreter takes over silently with the same results, so this is the only way to tell which executor a call ran. */
+uint64_t zkhip_test_rows_compiled_count(void);
 /* Window form: `count` rows starting at global row `row0` of a 2^log_rows domain, e.g. one device's share of the rows.  With
  * o_i = rotations[i] * rot_scale (signed, not reduced), halo_lo = max(0, max_i(-o_i)) and halo_hi = max(0, max_i(o_i)), each d_windows[c]
  * is a WINDOW BUFFER of W = halo_lo + count + halo_hi elements: element t = column_c[(row0 - halo_lo + t) mod 2^log_rows] (valid for W >

@@ -47,10 +47,14 @@ out = torch.zeros((1 << ek) * 4, dtype=torch.int64, device="cuda")
 prog.run_device([t.data_ptr() for t in cols], ek, out.data_ptr())
 torch.cuda.synchronize()
 print("DIGEST", hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest())
+print("COMPILED", _lib.load().zkhip_test_rows_compiled_count())
 ''' % ROOT
-    digests = []
+    digests, compiled = [], []
     for mode in ("0", "1"):
         res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, ZKHIP_VM_JIT=mode, ZKHIP_VM_JIT_LOG="1"))
         assert res.returncode == 0 and "compilation failed" not in res.stderr, res.stdout + res.stderr[-2000:]
         digests.append([l for l in res.stdout.splitlines() if l.startswith("DIGEST")][0])
+        compiled.append(int([l for l in res.stdout.splitlines() if l.startswith("COMPILED")][0].split()[1]))
     assert digests[0] == digests[1]
+    # the interpreter takes over silently when there is no compiled kernel: the two runs must really be the two executors
+    assert compiled[0] == 0 and compiled[1] > 0, compiled

@@ -29,6 +29,7 @@ _SIGS = {
     "zkhip_coeff_to_extended_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "zkhip_vm_jit_source": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "zkhip_vm_jit_compile": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "zkhip_test_rows_compiled_count": (C.c_uint64, []),
     "zkhip_set_ntt_fanout": (C.c_int, [C.c_int]),
     "zkhip_ntt_fanout": (C.c_int, []),
     "zkhip_register_bases": (C.c_int, [C.c_void_p, C.c_size_t]),

@@ -2526,6 +2526,10 @@ int zkhip_vm_jit_compile(const zkhip_vm_program* prog, uint32_t n_columns, uint3
   return row_vm_jit_compile_only(prog, n_columns, log_rows, code_bytes);
 }
 
+// Which executor ran: the interpreter takes every call the compiled one does not (hiprtc missing, a failed compilation, a program outside
+// the limits) with the same results, so a test that compares the two reads this before and after a call.
+uint64_t zkhip_test_rows_compiled_count(void) { return row_vm_jit_launches(); }
+
 int zkhip_fr_eval_rows(const zkhip_vm_program* prog, const uint64_t* const* columns, uint32_t n_columns, uint32_t log_rows,
                        int accumulate, uint64_t* out) {
   ZK_API_RANGE();

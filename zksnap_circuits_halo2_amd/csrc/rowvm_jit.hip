@@ -15,6 +15,7 @@
 // at most 256 instructions (tests).
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -75,9 +76,11 @@ int jit_mode() {
 
 // ---- code generation ---------------------------------------------------------------------------------------------------------------------
 // Bounds are in units of r.  Every named value is in N form (fp29.hpp): a load gives < 1, a product of operands <= 2 gives
-// 2 * 32 * 2 / 169.3 + 1 < 1.76 (the second factor is scaled by 2^5), a sum adds the bounds, a difference a - b adds K with K r the smallest
-// borrow-proof constant of FrParams above b's bound.  Before a product an operand above 2 is brought back: one conditional subtraction of 2r
-// up to 4, the quotient-estimate reduction (fe_reduce_soft, < 2r + 2^233) above that.
+// 2 * 32 * 2 / 169.28 + 1 < 1.76 (the second factor is scaled by 2^5; 2^261 / r = 169.2848..., rounded DOWN so that no bound is understated),
+// a sum adds the bounds, a difference a - b adds K with K r the smallest borrow-proof constant of FrParams above b's bound.  Before a product
+// an operand above 2 is brought back: one conditional subtraction of 2r up to 4, the quotient-estimate reduction (fe_reduce_soft, < 2r +
+// 2^233) above that.  A bound is ATTAINED, not only approached (K r - 0 is exactly K r): every comparison against a strict precondition
+// is inclusive.
 const int RED_K[] = {2, 3, 4, 6, 8, 10, 12, 16, 32, 64};
 
 struct gen {
@@ -141,7 +144,7 @@ struct gen {
   }
   static bool is_mem(const zkhip_vm_operand& o) { return o.kind == ZKHIP_SRC_COLUMN || o.kind == ZKHIP_SRC_CONST; }
 
-  // product a * b as an expression; *out_bound = Ba * 32 Bb / 169.3 + 1 (the Montgomery product's lazy bound, radix 2^261 = 169.3 r), kept at or
+  // product a * b as an expression; *out_bound = Ba * 32 Bb / 169.28 + 1 (the Montgomery product's lazy bound, radix 2^261 = 169.2848... r), kept at or
   // below 2 by reducing a register operand first when Ba * Bb > 5.29 (a memory operand is canonical: bound 1; the repack of a register that
   // becomes the second factor needs it below 2^256 = 5.29 r)
   std::string product(zkhip_vm_operand a, zkhip_vm_operand b, double* out_bound) {
@@ -158,7 +161,7 @@ struct gen {
     double bb;
     if (b.kind == ZKHIP_SRC_REG) { vb = "times32(" + reg(b.index) + ")"; bb = bound[b.index]; }
     else { const val v = operand(b, true); vb = v.expr; bb = v.bound; }
-    *out_bound = va.bound * bb * 32.0 / 169.3 + 1.0;
+    *out_bound = va.bound * bb * 32.0 / 169.28 + 1.0;
     return "fe_mul<Fr, false>(" + va.expr + ", " + vb + ")";
   }
 
@@ -175,7 +178,7 @@ struct gen {
         if (in.a.kind == ZKHIP_SRC_REG && bound[in.a.index] > 2.3) reduce(reg(in.a.index), bound[in.a.index]);     // 2.3^2 = 5.29
         val a = operand(in.a, false);
         if (!a.is_reg) { const std::string t = fresh(); line("const fe " + t + " = " + a.expr + ";"); a.expr = t; }
-        set(in.dst, "fe_mul<Fr, false>(" + a.expr + ", times32(" + a.expr + "))", a.bound * a.bound * 32.0 / 169.3 + 1.0);
+        set(in.dst, "fe_mul<Fr, false>(" + a.expr + ", times32(" + a.expr + "))", a.bound * a.bound * 32.0 / 169.28 + 1.0);
         break;
       }
       case ZKHIP_OP_MAD: {
@@ -308,7 +311,9 @@ std::string generate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log
   {
     const std::string r = g.reg(p->result_reg);
     double& b = g.bound[p->result_reg];
-    if (b > 3.0) g.reduce(r, b);                 // condsub -> < 2r; the soft reduction -> < 2r + 2^233 < 3r
+    // fe_canon_lt3p needs a value STRICTLY below 3r, and 3r - 0 is exactly 3r (it would be stored as r, not 0): from 3 inclusive,
+    // condsub2 -> at most 2r; the soft reduction -> < 2r + 2^233 < 3r
+    if (b >= 3.0) g.reduce(r, b);
     g.line("{ uint32_t w[8]; fe_pack(fe_canon_lt3p<Fr>(" + r + "), w); store_words(A.out + row * 8, w); }");
   }
   std::string src = JIT_PRELUDE_TYPES;
@@ -340,6 +345,7 @@ std::string generate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log
 // ---- cache ---------------------------------------------------------------------------------------------------------------------------------
 struct compiled { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; bool failed = false; };
 std::mutex g_jit_mu;
+std::atomic<uint64_t> g_jit_launches{0};           // launches that went through a compiled kernel, in this process (zkhip_test_rows_compiled_count)
 std::map<std::string, compiled> g_jit_cache;       // key: device | rows | window flag | columns | the instruction bytes | scaled rotations | result register
 
 std::string cache_key(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, int device, bool window) {
@@ -434,8 +440,11 @@ int row_vm_jit_launch(const zkhip_vm_program* p, const void* const* d_columns, u
     set_error("eval_rows: launch of the compiled kernel failed");
     return ZKHIP_EHIP;
   }
+  g_jit_launches.fetch_add(1, std::memory_order_relaxed);
   return ZKHIP_OK;
 }
+
+uint64_t row_vm_jit_launches() { return g_jit_launches.load(std::memory_order_relaxed); }
 
 // the generated source / a compile-only run of it (hiprtc cross-compiles for gfx950 without a device): the CPU-side test of the generator
 int row_vm_jit_source(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, std::string* out) {

@@ -190,6 +190,7 @@ bool row_vm_jit_wanted_window(const zkhip_vm_program* p, uint32_t n_columns, uin
 int row_vm_jit_launch(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, bool window, uint64_t row0, uint64_t count,
                       int accumulate, const uint32_t* d_consts, const uint32_t* d_pow_lo, const uint32_t* d_pow_hi, uint32_t* d_out, hipStream_t stream);
 void row_vm_jit_clear();
+uint64_t row_vm_jit_launches();        // how many launches of this process went through a compiled kernel (never reset)
 int row_vm_jit_source(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, std::string* out);
 int row_vm_jit_compile_only(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, size_t* code_bytes);
 int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, int accumulate,

@@ -533,6 +533,54 @@ int zkhip_g1_compress(const uint64_t *points, size_t n, uint8_t *out32, int flag
 int zkhip_g1_compress_device(const void *d_points, size_t n, void *d_out32, int flag_layout, void *stream);
 int zkhip_g1_decompress(const uint8_t *in32, size_t n, uint64_t *points, int flag_layout, uint64_t *first_bad);
 int zkhip_g1_decompress_device(const void *d_in32, size_t n, void *d_points, int flag_layout, uint64_t *first_bad, void *stream);
+/* ---- transcript: halo2's `Blake2bWrite` / `Blake2bRead` with `Challenge255` -- a proof written and read as bytes ------------------------
+ * [DEP halo2-axiom transcript.rs; the benches prove with create_proof(SHPLONK, Blake2b): halo2-base `gen_proof`,
+ * /root/reference/aggregator/benches/wrapper_circuit.rs:140.]  Restated from the published format, unpinned like everything at this boundary.
+ * THE FORMAT (normative):
+ *   state          Blake2b-512 (RFC 7693), no key, personalisation "Halo2-Transcript" (16 bytes), plus the proof byte stream: grown by a
+ *                  writer, walked by a reader's cursor.
+ *   common_point   absorb the byte 0x01, then x and y as 32-byte little-endian canonical integers.  The identity is ZKHIP_EINVAL (halo2:
+ *                  "cannot write points at infinity to the transcript") and leaves the transcript untouched.
+ *   common_scalar  absorb the byte 0x02, then the 32-byte little-endian canonical scalar.
+ *   write_*        the common_* call, then 32 bytes appended to the proof: the point's GroupEncoding exactly as zkhip_g1_compress writes it
+ *                  (flag_layout is fixed when the transcript is made) or the scalar's canonical repr.
+ *   read_*         32 bytes from the proof, decoded STRICTLY, then the common_* call.  ZKHIP_EINVAL: x not canonical, x^3 + 3 not a square,
+ *                  an identity encoding, a scalar >= r, fewer than 32 n bytes left.  zkhip_last_error() names the index of the first bad
+ *                  element; the hash state and the cursor are as before the call.
+ *   squeeze        absorb the byte 0x00; finalise A COPY of the state to 64 bytes (the running state goes on, the 0x00 included); the
+ *                  challenge is those 64 bytes as a little-endian 512-bit integer mod r (`from_uniform_bytes`), returned as 4 Montgomery
+ *                  words like every other Fr here.
+ * Pin: the first squeeze of a fresh transcript is 0x0e89c2c9ef365f095ec7aa36500bb0ba58bf7d5e17194055afb5a1c746f1786a (canonical).
+ * Batches: a call over n elements is n calls over one, in order; a failing call absorbs and appends NOTHING (all n are checked first).
+ * Where things run.  The hash runs on the host, inside the library (a serial chain of 128-byte blocks).  The calls marked "host" touch no
+ * GPU and work in a process that never initialises HIP: Montgomery <-> canonical and the 512-bit reduction are host arithmetic.  The
+ * `_device` calls take what the prover has in HBM: write_points_device takes n Jacobian commitments exactly as the MSM calls leave them (12
+ * words each) and costs ONE launch (shared inversion of the z's, canonical x and y, the encoding: 96 bytes per point) behind a 4-byte upload that
+ * clears the call's identity count, one copy into a pinned block the transcript owns and one wait on `stream`; write_scalars_device the same for n Montgomery Fr (e.g. the buffer
+ * zkhip_fr_eval_polynomial_batch_device filled).  read_points_device uploads n encodings, decompresses them (zkhip_g1_decompress's kernel)
+ * and leaves the n affine Montgomery points (8 words each) at d_affine for the verifier's MSMs.  The forms without `_device` take / fill host
+ * buffers and borrow a lane like every host-buffer call.  Device pointers must be 16-byte aligned.  After a failed `_device` call nothing of
+ * it is left queued on `stream`.
+ * A transcript object is used by one thread at a time; different objects may be used concurrently: no library lock is held while a call
+ * waits for its stream or hashes.  A writer refuses read_*, a reader
+ * refuses write_*; common_* and squeeze work on both. */
+typedef struct zkhip_transcript zkhip_transcript;
+zkhip_transcript *zkhip_transcript_new(int flag_layout);                                                /* a writer; NULL on a bad layout */
+zkhip_transcript *zkhip_transcript_new_reader(const uint8_t *proof, size_t len, int flag_layout);       /* the bytes are copied */
+void zkhip_transcript_free(zkhip_transcript *t);
+int zkhip_transcript_common_scalars(zkhip_transcript *t, const uint64_t *fr_mont, size_t n);            /* host */
+int zkhip_transcript_common_points(zkhip_transcript *t, const uint64_t *affine_mont, size_t n);         /* host; 8 words per point */
+int zkhip_transcript_squeeze(zkhip_transcript *t, uint64_t out_fr_mont[4]);                             /* host */
+int zkhip_transcript_write_scalars(zkhip_transcript *t, const uint64_t *fr_mont, size_t n);             /* host */
+int zkhip_transcript_write_points_device(zkhip_transcript *t, const void *d_points_xyz, size_t n, void *stream);
+int zkhip_transcript_write_scalars_device(zkhip_transcript *t, const void *d_fr, size_t n, void *stream);
+int zkhip_transcript_write_points(zkhip_transcript *t, const uint64_t *points_xyz, size_t n);           /* host buffer: upload, then the device form */
+int zkhip_transcript_read_scalars(zkhip_transcript *t, size_t n, uint64_t *fr_mont);                    /* host */
+int zkhip_transcript_read_points_device(zkhip_transcript *t, size_t n, void *d_affine, void *stream);
+int zkhip_transcript_read_points(zkhip_transcript *t, size_t n, uint64_t *affine_mont);                 /* host buffer */
+/* the proof: everything written so far (a writer) or the bytes given (a reader).  *len = its length; buf may be NULL to ask for the length,
+ * otherwise cap must be at least that (ZKHIP_EINVAL, *len still set). */
+int zkhip_transcript_proof(const zkhip_transcript *t, uint8_t *buf, size_t cap, size_t *len);
 /* Per-phase timing with HIP events on the stream the kernels run on.  enable(1), run one call, then
  * zkhip_profile_read synchronises and returns the number of phases of the last profiled call, writing up to
  * `max` durations (milliseconds) and names (63 chars + NUL each). */
@@ -554,6 +602,11 @@ int zkhip_test_g1_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out
  * latency-bound end: 3 = 2 a[i] + b[i], 4 = 4 a[i]; with their lazy forms chained as in the window fold: 5 = 4 a[i] + b[i], 6 = 16 a[i].
  * a, b: n G2Affine points, out: n G2 Jacobian points */
 int zkhip_test_g2_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out_xyz, size_t n);
+
+/* the transcript's challenge reduction on its own: 64 bytes as a little-endian 512-bit integer mod r, 4 Montgomery words (host, no GPU) */
+int zkhip_test_reduce512(const uint8_t in64[64], uint64_t out_fr_mont[4]);
+/* how many points share one inversion when zkhip_transcript_write_points_device runs over n points (the kernel's launch shape; host, no GPU) */
+uint32_t zkhip_test_transcript_chunk(size_t n);
 
 /* ---- pairing check (`multi_miller_loop` + `final_exponentiation` + `is_identity` [DEP halo2curves bn256], under `verify_proof` and the decider) ---- */
 #define ZKHIP_MAX_PAIRS 64

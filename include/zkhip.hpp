@@ -429,6 +429,59 @@ class DeviceVec {
   bool owned_ = true;
 };
 
+// `Blake2bWrite` / `Blake2bRead` with `Challenge255` [DEP transcript.rs] over zkhip_transcript_* (zkhip.h, "transcript"): the hash and the framing
+// run on the host inside the library, the `_device` forms take commitments / evaluations where they lie in HBM.  One thread at a time per object.
+class Transcript {
+ public:
+  static Transcript writer(int flag_layout = 0) { return Transcript(zkhip_transcript_new(flag_layout)); }                       // Blake2bWrite::init(vec![])
+  static Transcript reader(const std::vector<uint8_t>& proof, int flag_layout = 0) {                                              // Blake2bRead::init(proof)
+    return Transcript(zkhip_transcript_new_reader(proof.data(), proof.size(), flag_layout));
+  }
+  Transcript(const Transcript&) = delete;
+  Transcript& operator=(const Transcript&) = delete;
+  Transcript(Transcript&& o) noexcept : t_(o.t_) { o.t_ = nullptr; }
+  ~Transcript() { zkhip_transcript_free(t_); }
+  void common_scalar(const Fr& s) { check(zkhip_transcript_common_scalars(t_, s.l, 1), "Transcript::common_scalar"); }
+  void common_point(const G1Affine& p) { check(zkhip_transcript_common_points(t_, p.x, 1), "Transcript::common_point"); }
+  Fr squeeze_challenge() {
+    Fr c;
+    check(zkhip_transcript_squeeze(t_, c.l), "Transcript::squeeze_challenge");
+    return c;
+  }
+  void write_scalars(const std::vector<Fr>& s) { if (!s.empty()) check(zkhip_transcript_write_scalars(t_, s[0].l, s.size()), "Transcript::write_scalars"); }
+  void write_scalars(const DeviceVec& s, void* stream = nullptr) { check(zkhip_transcript_write_scalars_device(t_, s.data(), s.size(), stream), "Transcript::write_scalars"); }
+  void write_points(const std::vector<G1>& p) { if (!p.empty()) check(zkhip_transcript_write_points(t_, p[0].x, p.size()), "Transcript::write_points"); }
+  // n Jacobian commitments (96 bytes each) in device memory, e.g. the output of zkhip_msm_g1_registered_batch_device
+  void write_points_device(const void* d_points_xyz, size_t n, void* stream = nullptr) {
+    check(zkhip_transcript_write_points_device(t_, d_points_xyz, n, stream), "Transcript::write_points_device");
+  }
+  std::vector<Fr> read_scalars(size_t n) {
+    std::vector<Fr> out(n);
+    if (n) check(zkhip_transcript_read_scalars(t_, n, out[0].l), "Transcript::read_scalars");
+    return out;
+  }
+  std::vector<G1Affine> read_points(size_t n) {
+    std::vector<G1Affine> out(n);
+    if (n) check(zkhip_transcript_read_points(t_, n, out[0].x), "Transcript::read_points");
+    return out;
+  }
+  // n affine points (64 bytes each) left at d_affine for the verifier's MSMs
+  void read_points_device(size_t n, void* d_affine, void* stream = nullptr) {
+    check(zkhip_transcript_read_points_device(t_, n, d_affine, stream), "Transcript::read_points_device");
+  }
+  std::vector<uint8_t> finalize() const {                                                                                         // the proof written (or given) so far
+    size_t len = 0;
+    check(zkhip_transcript_proof(t_, nullptr, 0, &len), "Transcript::finalize");
+    std::vector<uint8_t> out(len);
+    if (len) check(zkhip_transcript_proof(t_, out.data(), len, &len), "Transcript::finalize");
+    return out;
+  }
+
+ private:
+  explicit Transcript(zkhip_transcript* t) : t_(t) { if (!t_) throw std::runtime_error(std::string("Transcript: ") + zkhip_last_error()); }
+  zkhip_transcript* t_;
+};
+
 // A row program (plonk::evaluation::GraphEvaluator lowered to include/zkhip.h's instruction set) over device-resident columns.
 struct RowProgram {
   std::vector<zkhip_vm_insn> insns;

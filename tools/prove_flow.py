@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A transcript-less `create_proof` for a *satisfied* circuit of the halo2-lib shape, device-resident from witness columns to
+"""A `create_proof` (seeded challenges; with `transcript=True` a Blake2b transcript and a proof as bytes) for a *satisfied* circuit of the halo2-lib shape, device-resident from witness columns to
 quotient commitments -- the steps of [DEP] halo2-axiom plonk/prover.rs in the order the reference's prover runs them
 (/root/reference/aggregator/src/wrapper.rs:129), composed from this repo's entry points only:
 
@@ -14,7 +14,8 @@ with `calculate_params(Some(20))` (/root/reference/voter/benches/voter_circuit.r
 /root/reference/voter/frontend/app/worker.js:95-102): `run(13, 256, lookups=8)` and `run(15, 64, lookups=8)` are those shapes, with all
 the columns of a phase committed through ONE batched call (`zkhip_msm_g1_registered_batch_device`) as a Rust host would have to.  Checks (the prover's own invariants): both
 grand products close, the quotient is a polynomial (coefficients of degree >= 3n vanish), commit_lagrange(column) = commit(coefficients).
-There is no transcript: challenges are seeded.  Usage: prove_flow.py [k] [gate_cols] [lookups] [--device-randomness] [--mock]   (default 16 4 1).
+By default there is no transcript: challenges are seeded.  --transcript (run(transcript=True)): Fiat-Shamir challenges from a Blake2b transcript, and
+the proof as bytes.  Usage: prove_flow.py [k] [gate_cols] [lookups] [--device-randomness] [--mock] [--verify] [--transcript]   (default 16 4 1).
 --mock (run(mock=True)): the witness is checked against the circuit on the device before keygen and the arguments run (lap `mock_prover`).
 --device-randomness (run(device_randomness=True)): every blinding tail is drawn by zkhip_fr_random_rows_device, all columns of a step in one
 call, and the vanishing argument's random polynomial is filled by zkhip_fr_random_device and committed (lap `vanishing_random_poly`); the
@@ -39,8 +40,56 @@ BLIND = 5
 _SIDE_STREAM = None
 
 
+def verify_transcript_proof(params, vk, k, proof, shape, plan):
+    """The verifier of `run(transcript=True)`: it is handed the parameters, the verifying key, the proof BYTES, and what a verifier knows of the
+    circuit -- `shape` (how many advice columns, lookups, permutation sets, whether a random polynomial is committed) and `plan` (the opened
+    (kind, index, rotation) triples, in the order their evaluations were written).  It replays the prover's order with reads -- commitments land
+    on the device as affine points, evaluations as integers --, derives every challenge itself and ends in `VerifierSHPLONK.verify_proof_transcript`.
+    The verifier's scalar half (the gates' identity at x) is out of scope.  Bytes that do not decode reject."""
+    import io
+
+    from zksnap_circuits_halo2_amd import keygen as KG, multiopen as MO
+    from zksnap_circuits_halo2_amd.transcript import Blake2bRead, vk_transcript_repr
+
+    def xyz(points):                                       # device affine points -> Jacobian limbs with z = 1 for the host-side accumulation
+        return [MO._affine_to_xyz(p_) for p_ in points.cpu().numpy().view(np.uint64).reshape(-1, 8)]
+
+    vk_io = io.BytesIO()
+    vk.write(vk_io, KG.RAW_BYTES)
+    n_adv, n_lk, n_sets = shape["advice"], shape["lookups"], shape["permutation_sets"]
+    with Blake2bRead(bytes(proof)) as r:
+        try:
+            r.common_scalar(vk_transcript_repr(vk_io.getvalue()))
+            com = {("advice", i): c_ for i, c_ in enumerate(xyz(r.read_points(n_adv)))}
+            r.squeeze_challenge()                          # theta
+            if n_lk:
+                for j, c_ in enumerate(xyz(r.read_points(2 * n_lk))):
+                    com[("lookup_pa" if j % 2 == 0 else "lookup_ps", j // 2)] = c_
+            r.squeeze_challenge(), r.squeeze_challenge()   # beta, gamma
+            for j, c_ in enumerate(xyz(r.read_points(n_sets + n_lk))):
+                com[("perm", j) if j < n_sets else ("lookup_z", j - n_sets)] = c_
+            if shape["random_poly"]:
+                com[("random", 0)] = xyz(r.read_points(1))[0]
+            r.squeeze_challenge()                          # y
+            for i, c_ in enumerate(xyz(r.read_points(3))):
+                com[("h", i)] = c_
+            x = r.squeeze_challenge()
+            evals = r.read_scalars(len(plan))
+        except _lib.ZkhipError as e:
+            if e.code == -1:
+                return False
+            raise
+        for i in range(len(vk.fixed_commitments)):
+            com[("fixed", i)] = MO._affine_to_xyz(vk.fixed_commitments[i])
+        for i in range(len(vk.permutation_commitments)):
+            com[("sigma", i)] = MO._affine_to_xyz(vk.permutation_commitments[i])
+        w_ = F.omega_for(k)
+        vqueries = [MO.VerifierQuery(x * pow(w_, r_, R) % R, com[(kind, idx)], e, poly_id=(kind, idx)) for (kind, idx, r_), e in zip(plan, evals)]
+        return MO.VerifierSHPLONK(params).verify_proof_transcript(vqueries, r)
+
+
 def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False,
-        sharded_key=False, lookups_one_call=True, device_randomness=False, mock=False, on_witness=None, verify=False, corrupt_proof=None, on_proof=None):
+        sharded_key=False, lookups_one_call=True, device_randomness=False, mock=False, on_witness=None, verify=False, corrupt_proof=None, on_proof=None, transcript=False):
     """mock: what the reference's `gen_proof` does before it proves (`MockProver::run(..).assert_satisfied()`,
     /root/reference/aggregator/src/wrapper.rs:117-123), over the columns where they lie: `mock.MockProver(..).assert_satisfied()` once the
     witness columns and the copy constraints exist, as lap `mock_prover` (not part of `prove_ms`).  A witness broken with `corrupt=` then raises
@@ -51,6 +100,13 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
     evaluations of its `evals` buffer and of the rotated openings -- through `VerifierSHPLONK`, ending in one pairing check on the device: check
     "proof_verifies", lap `verify` (not part of `prove_ms`).  corrupt_proof: "eval" / "commitment" / "witness" change one evaluation, one
     commitment or H' AFTER the prover has run: "proof_verifies" is then false and every other check stays true.
+    transcript: the challenges are not seeded but squeezed from a Blake2b transcript (zksnap_circuits_halo2_amd/transcript.py) in halo2
+    `create_proof`'s order -- vk repr; advice commitments, theta; the lookups' permuted commitments, beta, gamma; permutation then lookup product
+    commitments, the random polynomial's commitment (device_randomness), y; the quotient pieces, x; the evaluations in halo2's order, written from
+    the device buffer they were computed into; the SHPLONK multi-open through `create_proof_transcript` -- and the result gains `proof` (bytes),
+    `proof_bytes`, `proof_plan` and `proof_shape`; lap `transcript` (part of `prove_ms`).  With verify as well, `verify_transcript_proof` gets
+    (params, vk, the proof bytes, shape and plan) after the prover's tensors are dropped.  corrupt_proof=("byte", i) flips bit 0 of proof byte i
+    before that; the three named values belong to the seeded flow.  The mock step keeps the seeded theta.
     on_proof (with verify): a callable handed (params, k, queries, verifier queries, commit, (H, H'), (y, v, u)) after the verdict, while the
     polynomials are still in HBM (tools/verify_time.py measures the verifiers there, on the flow's own plan); its time goes to the lap `verify`.
     on_witness: a callable handed (cs, k, fixed, advice, assembly, theta) at that same point, the columns being device tensors (tools/mock_time.py
@@ -70,8 +126,15 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
 
     if sharded_key and not sharded_quotient:
         raise ValueError("sharded_key needs sharded_quotient")
-    if corrupt_proof not in (None, "eval", "commitment", "witness"):
-        raise ValueError("corrupt_proof: eval, commitment or witness")
+    byte_flip = isinstance(corrupt_proof, tuple) and len(corrupt_proof) == 2 and corrupt_proof[0] == "byte"
+    if corrupt_proof not in (None, "eval", "commitment", "witness") and not byte_flip:
+        raise ValueError("corrupt_proof: eval, commitment, witness or (\"byte\", i)")
+    if transcript and corrupt_proof is not None and not byte_flip:
+        raise ValueError("transcript: the proof is bytes, corrupt it with corrupt_proof=(\"byte\", i)")
+    if byte_flip and not (transcript and verify):
+        raise ValueError("corrupt_proof=(\"byte\", i) needs transcript=True and verify=True")
+    if transcript and lookups and not lookups_one_call:
+        raise ValueError("transcript: the lookup argument is split at its challenges only in the one-call form")
     lib = _lib.load()
     dev = torch.device("cuda", 0)
     n, u = 1 << k, (1 << k) - (BLIND + 1)
@@ -79,6 +142,8 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
     rng = random.Random(seed)
     torch.manual_seed(seed)
     beta, gamma, theta, y, x, s = (rng.randrange(1, R) for _ in range(6))
+    theta_mock = theta                   # transcript: the mock step keeps a seeded theta of its own, every other challenge is squeezed below
+    tr = None
     dom = Z.EvaluationDomain(4, k)
     ek, en = dom.extended_k, dom.extended_len()
     G, NL = gate_cols, lookups
@@ -225,11 +290,11 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
         if mock:
             from zksnap_circuits_halo2_amd import mock as MK
 
-            with MK.MockProver(cs, k, fixed, advice, (), assembly, theta=theta) as mock_prover:
+            with MK.MockProver(cs, k, fixed, advice, (), assembly, theta=theta_mock) as mock_prover:
                 mock_prover.assert_satisfied()
             lap("mock_prover")
         if on_witness is not None:
-            on_witness(cs, k, fixed, advice, assembly, theta)
+            on_witness(cs, k, fixed, advice, assembly, theta_mock)
             lap("witness_columns")
         pk_bytes = None
         if pk_file is None:
@@ -264,27 +329,48 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             KG._copy_device(t_.data_ptr(), ptr, log_rows)
             return t_
 
+        if transcript:
+            # ---- the transcript opens: halo2 `create_proof`'s order.  The advice commitments exist already (they are
+            # what the flow times first); nothing has been squeezed before they are absorbed.
+            import io
+            from zksnap_circuits_halo2_amd.transcript import Blake2bWrite, vk_transcript_repr
+
+            vk_io = io.BytesIO()
+            vk.write(vk_io, KG.RAW_BYTES)
+            vk_bytes = vk_io.getvalue()
+            tr = Blake2bWrite()
+            tr.common_scalar(vk_transcript_repr(vk_bytes))           # a stand-in for halo2's vk.transcript_repr (transcript.py)
+            tr.write_points(torch.stack(adv_commit).contiguous())    # no instance columns: nothing between the key and the advice commitments
+            theta = tr.squeeze_challenge()
+            lap("transcript")
+
         sigma = [from_key(dpk.permutation_values(i), k) for i in range(len(perm_cols))]
-        # every set's product column in ONE call (zkhip_permutation_products_device: the sets are chained on the device through z[u]); one
-        # read-back of the last set's z[u] says whether the argument closes
         nsets_, npc = cs.num_permutation_sets, len(perm_cols)
-        z_all = torch.empty((nsets_, n, 4), dtype=torch.int64, device=dev)
-        vptr = (C.c_void_p * npc)(*[pcol(c).data_ptr() for c in range(npc)])
-        sptr = (C.c_void_p * npc)(*[sg.data_ptr() for sg in sigma])
-        pconsts = [F.fr_encode([v_])[0] for v_ in (beta, gamma, E.DELTA, F.omega_for(k))]
-        _lib.check(lib.zkhip_permutation_products_device(vptr, sptr, npc, cs.chunk_len, k, u, *[c_.ctypes.data for c_ in pconsts], z_all.data_ptr(), None))
-        z_sets = [z_all[si] for si in range(nsets_)]
-        perm_closes = F.fr_decode(z_all[nsets_ - 1, u:u + 1].cpu().numpy().view(np.uint64))[0] == 1
-        if device_randomness:
-            blind(z_sets, u + 1)
-        else:
-            for z in z_sets:
-                z[u + 1:] = rand_fr(n - u - 1)                                     # blinding rows
-        lap("permutation_products")
+
+        def permutation_products():
+            # every set's product column in ONE call (zkhip_permutation_products_device: the sets are chained on the device through z[u]); one
+            # read-back of the last set's z[u] says whether the argument closes
+            z_all = torch.empty((nsets_, n, 4), dtype=torch.int64, device=dev)
+            vptr = (C.c_void_p * npc)(*[pcol(c).data_ptr() for c in range(npc)])
+            sptr = (C.c_void_p * npc)(*[sg.data_ptr() for sg in sigma])
+            pconsts = [F.fr_encode([v_])[0] for v_ in (beta, gamma, E.DELTA, F.omega_for(k))]
+            _lib.check(lib.zkhip_permutation_products_device(vptr, sptr, npc, cs.chunk_len, k, u, *[c_.ctypes.data for c_ in pconsts], z_all.data_ptr(), None))
+            z_sets = [z_all[si] for si in range(nsets_)]
+            closes = F.fr_decode(z_all[nsets_ - 1, u:u + 1].cpu().numpy().view(np.uint64))[0] == 1
+            if device_randomness:
+                blind(z_sets, u + 1)
+            else:
+                for z in z_sets:
+                    z[u + 1:] = rand_fr(n - u - 1)                                 # blinding rows
+            lap("permutation_products")
+            return z_all, z_sets, closes
+
+        if not transcript:
+            z_all, z_sets, perm_closes = permutation_products()
 
         # ---- lookup argument ---------------------------------------------------------------------------------------------------
         lookup_cols, lookup_closes = [], True
-        if lookups_one_call and NL and not (NL == 1 and k >= 20):            # a single lookup over 2^20 rows or more stays with the loop
+        if lookups_one_call and NL and (transcript or not (NL == 1 and k >= 20)):   # a single lookup over 2^20 rows or more stays with the loop
             # both phases of every lookup in one call each; the blinding rows are drawn in the per-lookup order of the loop below (pa, ps, z tail)
             pa_all, ps_all = torch.empty((NL, n, 4), dtype=torch.int64, device=dev), torch.empty((NL, n, 4), dtype=torch.int64, device=dev)
             tails = []
@@ -295,6 +381,15 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
                     pa_all[j], ps_all[j] = rand_fr(n), rand_fr(n)                  # rows >= u stay random (blinding)
                     tails.append(rand_fr(n - u - 1))
             E.permute_expression_pairs_device(lks, [table] * NL, u, k, pa_all, ps_all)
+            if transcript:
+                # each lookup's permuted input and table commitments, then beta and gamma; only now can the products be formed
+                lap("lookup_permute_and_product")
+                permuted_commit = commit_all(h_gl, [c_ for j in range(NL) for c_ in (pa_all[j], ps_all[j])])
+                lap("commit_products")
+                tr.write_points(torch.stack(permuted_commit).contiguous())
+                beta, gamma = tr.squeeze_challenge(), tr.squeeze_challenge()
+                lap("transcript")
+                z_all, z_sets, perm_closes = permutation_products()
             z_lk = E.lookup_products_device(lks, [table] * NL, pa_all, ps_all, u, k, beta, gamma)
             lookup_closes = all(v_ == 1 for v_ in F.fr_decode(z_lk[:, u].contiguous().cpu().numpy().view(np.uint64)))
             if device_randomness:
@@ -322,11 +417,24 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
                     zl[u + 1:] = rand_fr(n - u - 1)
                 lookup_cols += [zl, pa, ps]
         lap("lookup_permute_and_product")
+        if transcript and not NL:
+            beta, gamma = tr.squeeze_challenge(), tr.squeeze_challenge()
+            z_all, z_sets, perm_closes = permutation_products()
         if device_randomness:
             # the vanishing argument's random polynomial: n coefficients of stream 1, drawn where they are committed (and later opened)
             random_poly = E.random_fr_device(dr_seed, n, stream_id=1)
             random_poly_commit = commit(h_g, random_poly)
             lap("vanishing_random_poly")
+        if transcript:
+            # permutation product commitments, then lookup product commitments (Lagrange basis: the same group elements as the commitments to
+            # their coefficients), the random polynomial's commitment, then y
+            product_commit = commit_all(h_gl, z_sets + [lookup_cols[3 * j] for j in range(NL)])
+            lap("commit_products")
+            tr.write_points(torch.stack(product_commit).contiguous())
+            if device_randomness:
+                tr.write_points(random_poly_commit)
+            y = tr.squeeze_challenge()
+            lap("transcript")
 
         # ---- Lagrange -> coefficients, commitments, extended coset ---------------------------------------------------------------
         l0 = torch.zeros((n, 4), dtype=torch.int64, device=dev); l0[0] = ONE
@@ -364,8 +472,12 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             ifft_range(lo, hi)
         lap("lagrange_to_coeff")
         first_prover_poly = qc.sigma + len(perm_cols)                               # z sets, lookup product, permuted pair
-        prod_commit = commit_all(h_g, [coeff[i] for i in range(first_prover_poly, ncol)] + [coeff[qc.advice]])
-        a0_coeff_commit = prod_commit.pop()
+        if transcript:
+            prod_commit = product_commit + permuted_commit if NL else product_commit
+            a0_coeff_commit = commit(h_g, coeff[qc.advice])
+        else:
+            prod_commit = commit_all(h_g, [coeff[i] for i in range(first_prover_poly, ncol)] + [coeff[qc.advice]])
+            a0_coeff_commit = prod_commit.pop()
         lap("commit_products")
         ext = torch.empty((ncol, en, 4), dtype=torch.int64, device=dev)
 
@@ -418,11 +530,16 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
         lap("extended_to_coeff")
         h_commit = commit_all(h_g, [h_coeff[i * n:(i + 1) * n] for i in range(3)])
         lap("commit_h")
+        if transcript:
+            tr.write_points(torch.stack(h_commit).contiguous())
+            x = tr.squeeze_challenge()
+            lap("transcript")
 
         # ---- evaluations at x ----------------------------------------------------------------------------------------------------------
         evals = torch.zeros((ncol + 3, 4), dtype=torch.int64, device=dev)
         ptrs = (C.c_void_p * (ncol + 3))(*([coeff[i].data_ptr() for i in range(ncol)] + [h_coeff[i * n:].data_ptr() for i in range(3)]))
-        _lib.check(lib.zkhip_fr_eval_polynomial_batch_device(ptrs, ncol + 3, n, F.fr_encode([x])[0].ctypes.data, evals.data_ptr(), None))
+        if not transcript:                                         # transcript: every opened (polynomial, rotation) is evaluated below, in the plan's order
+            _lib.check(lib.zkhip_fr_eval_polynomial_batch_device(ptrs, ncol + 3, n, F.fr_encode([x])[0].ctypes.data, evals.data_ptr(), None))
         lap("evaluations")
 
         # ---- multiopen (SHPLONK, the benches' `gen_proof` path): every opened (polynomial, rotation) of the halo2 prover's query plan -----
@@ -431,25 +548,73 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
         w_ = F.omega_for(k)
         rot = lambda r: x * pow(w_, r, R) % R
         queries = []
-        for i in range(qc.fixed, qc.advice):                       # fixed columns (selectors, constants, table): at x
+        plan = []                                                  # transcript: (kind, index, rotation) per query -- what a verifier knows of the circuit
+        if transcript:
+            # halo2's order of evaluations: advice; fixed; the random polynomial; sigma; per permutation set z(x), z(omega x) and z(omega^last x)
+            # for all but the last set; per lookup product, product-next, permuted input, permuted input at omega^-1 x, permuted table.  The three
+            # quotient pieces follow: this flow opens them one by one (halo2 opens their combination, whose value its verifier computes).
+            def opened(kind, idx, r, ptr):
+                plan.append((kind, idx, r))
+                queries.append(MO.ProverQuery(rot(r), ptr))
+
+            for i in range(G):
+                for r in range(4):
+                    opened("advice", i, r, coeff[qc.advice + i].data_ptr())
+            for j in range(NL):
+                opened("advice", G + j, 0, coeff[qc.advice + G + j].data_ptr())
+            for i in range(qc.fixed, qc.advice):
+                opened("fixed", i - qc.fixed, 0, coeff[i].data_ptr())
+            if device_randomness:
+                opened("random", 0, 0, random_poly.data_ptr())
+            for i in range(len(perm_cols)):
+                opened("sigma", i, 0, coeff[qc.sigma + i].data_ptr())
+            for si in range(cs.num_permutation_sets):
+                for r in (0, 1) + ((u,) if si + 1 < cs.num_permutation_sets else ()):
+                    opened("perm", si, r, coeff[qc.perm_product + si].data_ptr())
+            for j in range(NL):
+                for kind, t_, r in (("lookup_z", 0, 0), ("lookup_z", 0, 1), ("lookup_pa", 1, 0), ("lookup_pa", 1, -1), ("lookup_ps", 2, 0)):
+                    opened(kind, j, r, coeff[qc.lookup + 3 * j + t_].data_ptr())
+            for i in range(3):
+                opened("h", i, 0, h_coeff[i * n:].data_ptr())
+            # one batched evaluation per rotation into one device buffer, put into the plan's order there, and written from there
+            by_rot = {}
+            for qi, (_, _, r) in enumerate(plan):
+                by_rot.setdefault(r, []).append(qi)
+            grouped = torch.zeros((len(queries), 4), dtype=torch.int64, device=dev)
+            where, off = [0] * len(queries), 0
+            for r, qis in by_rot.items():
+                ptrs_r = (C.c_void_p * len(qis))(*[queries[qi].poly for qi in qis])
+                point = F.fr_encode([rot(r)])[0]
+                _lib.check(lib.zkhip_fr_eval_polynomial_batch_device(ptrs_r, len(qis), n, point.ctypes.data, grouped[off:].data_ptr(), None))
+                for t_, qi in enumerate(qis):
+                    where[qi] = off + t_
+                off += len(qis)
+            evals_plan = grouped[torch.tensor(where, dtype=torch.int64, device=dev)].contiguous()
+            lap("evaluations")
+            tr.write_scalars(evals_plan)
+            for q_, e_ in zip(queries, F.fr_decode(evals_plan.cpu().numpy().view(np.uint64))):
+                q_.eval = e_                                        # the multi-open's R_ij need them as integers
+            lap("transcript")
+        for i in range(qc.fixed, qc.advice) if not transcript else ():   # fixed columns (selectors, constants, table): at x
             queries.append(MO.ProverQuery(rot(0), coeff[i].data_ptr()))
-        for i in range(G):                                         # gate advice columns: the vertical gate reads rows 0 .. 3
+        seeded = not transcript                                    # the seeded flow's plan, as it always was
+        for i in range(G) if seeded else ():                       # gate advice columns: the vertical gate reads rows 0 .. 3
             for r in range(4):
                 queries.append(MO.ProverQuery(rot(r), coeff[qc.advice + i].data_ptr()))
-        for j in range(NL):                                        # lookup advice
+        for j in range(NL) if seeded else ():                      # lookup advice
             queries.append(MO.ProverQuery(rot(0), coeff[qc.advice + G + j].data_ptr()))
-        for i in range(qc.sigma, qc.sigma + len(perm_cols)):       # permutation polynomials (proving key)
+        for i in range(qc.sigma, qc.sigma + len(perm_cols)) if seeded else ():       # permutation polynomials (proving key)
             queries.append(MO.ProverQuery(rot(0), coeff[i].data_ptr()))
-        for si in range(cs.num_permutation_sets):                  # permutation products: x, omega x, and the last usable row for chaining
+        for si in range(cs.num_permutation_sets) if seeded else ():                  # permutation products: x, omega x, and the last usable row for chaining
             zi = coeff[qc.perm_product + si].data_ptr()
             queries += [MO.ProverQuery(rot(0), zi), MO.ProverQuery(rot(1), zi)]
             if si + 1 < cs.num_permutation_sets:
                 queries.append(MO.ProverQuery(rot(u), zi))
-        for j in range(NL):
+        for j in range(NL) if seeded else ():
             zl_i, pa_i, ps_i = (coeff[qc.lookup + 3 * j + t].data_ptr() for t in range(3))
             queries += [MO.ProverQuery(rot(0), zl_i), MO.ProverQuery(rot(1), zl_i), MO.ProverQuery(rot(0), pa_i), MO.ProverQuery(rot(-1), pa_i),
                         MO.ProverQuery(rot(0), ps_i)]
-        for i in range(3):                                         # the quotient's pieces
+        for i in range(3) if seeded else ():                       # the quotient's pieces
             queries.append(MO.ProverQuery(rot(0), h_coeff[i * n:].data_ptr()))
 
         def commit_ptr(ptr):
@@ -461,15 +626,23 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
         mo_ok, mo_proof = True, None
         mo_prover = MO.ProverSHPLONK(k, commit_ptr)
         try:
-            mo_proof = mo_prover.create_proof(queries, y_mo, v_mo, u_mo)      # raises if L(u) != 0: an evaluation that does not belong to its polynomial
+            if transcript:                                         # y, v and u are squeezed, H and H' written
+                mo_proof = mo_prover.create_proof_transcript(queries, tr)
+            else:
+                mo_proof = mo_prover.create_proof(queries, y_mo, v_mo, u_mo)      # raises if L(u) != 0: an evaluation that does not belong to its polynomial
         except ArithmeticError:
             mo_ok = False
         lap("multiopen_shplonk")
         mo_prover.close()
+        proof = None
+        if transcript:
+            proof = tr.finalize()
+            tr.close()
+            lap("transcript")
 
         # ---- verify: what a verifier holds -- commitments, evaluations, H and H' -- and one pairing check --------------------------------------
         proof_verifies = None
-        if verify:
+        if verify and not transcript:
             jac = lambda t_: t_.cpu().numpy().view(np.uint64).reshape(12).copy()
             commitment_of = {}
             for i in range(qc.fixed, qc.advice):
@@ -503,14 +676,31 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
                 on_proof(params, k, queries, vqueries, commit_ptr, mo_proof, (y_mo, v_mo, u_mo))
                 lap("on_proof")
 
+        n_queries = len(queries)
         top_is_zero = not bool(h_coeff[3 * n:].any().item())
         low_nonzero = bool(h_coeff[:3 * n].any().item())
         commit_agrees = affine(adv_commit[0]) == affine(a0_coeff_commit)
+        h_affine = [affine(c) for c in h_commit]
+        n_msm = len(adv_commit) + len(prod_commit) + 1 + len(h_commit) + 2
+        shape = {"advice": G + NL, "lookups": NL, "permutation_sets": cs.num_permutation_sets, "random_poly": bool(device_randomness)}
+        if verify and transcript:
+            # the verifier gets (params, vk, proof bytes, the query plan) and nothing else: the prover's polynomials, commitments and evaluations
+            # are dropped first, so that a verdict cannot lean on them
+            torch.cuda.synchronize()
+            clock[0] = time.perf_counter()                         # the lap `verify` starts here
+            proof_verifies = False
+            if mo_proof is not None:
+                del coeff, ext, h_ext, h_coeff, evals, lagrange, advice, adv_commit, prod_commit, h_commit, queries, mo_proof, z_all, z_sets, lookup_cols
+                del evals_plan, grouped
+                checked = bytearray(proof)
+                if byte_flip:
+                    checked[corrupt_proof[1]] ^= 1
+                proof_verifies = verify_transcript_proof(params, vk, k, bytes(checked), dict(shape), list(plan))
+            lap("verify")
         checks = {"permutation_product_closes": perm_closes, "lookup_product_closes": lookup_closes, "quotient_is_a_polynomial": top_is_zero and low_nonzero,
                   "commit_lagrange_equals_commit_coeff": commit_agrees, "multiopen_linearisation_vanishes": mo_ok}
         if verify:
             checks["proof_verifies"] = proof_verifies
-        n_msm = len(adv_commit) + len(prod_commit) + 1 + len(h_commit) + 2
         prove_ms = sum(v for kk, v in t.items() if kk not in ("setup_srs", "witness_columns", "mock_prover", "stack_columns", "pk_file_round_trip", "pk_upload", "verify", "on_proof") and not kk.startswith("keygen_"))
         n_proof_cols = sum(hi - lo for lo, hi in proof_ranges)
         if verbose:
@@ -520,10 +710,13 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
                 print(f"  {name:28s} {ms:9.3f} ms")
             print(f"  {'prover steps (no setup/witness)':28s} {prove_ms:9.3f} ms")
             print("  checks:", checks)
-        return {"timings_ms": t, "prove_ms": prove_ms, "checks": checks, "columns": ncol, "proof_columns": n_proof_cols, "msms": n_msm, "queries": len(queries),
-                "program_insns": n_insns, "program_registers": n_regs, "h_commitments": [affine(c) for c in h_commit],
-                "keygen_ms": t.get("keygen_vk", 0.0) + t.get("keygen_pk", 0.0) + t.get("keygen_device", 0.0), "pk_file_bytes": pk_bytes,
-                "vanishing_random_commitment": affine(random_poly_commit) if device_randomness else None}
+        res = {"timings_ms": t, "prove_ms": prove_ms, "checks": checks, "columns": ncol, "proof_columns": n_proof_cols, "msms": n_msm, "queries": n_queries,
+               "program_insns": n_insns, "program_registers": n_regs, "h_commitments": h_affine,
+               "keygen_ms": t.get("keygen_vk", 0.0) + t.get("keygen_pk", 0.0) + t.get("keygen_device", 0.0), "pk_file_bytes": pk_bytes,
+               "vanishing_random_commitment": affine(random_poly_commit) if device_randomness else None}
+        if transcript:
+            res.update(proof=proof, proof_bytes=len(proof), proof_plan=plan, proof_shape=shape)
+        return res
     finally:
         torch.cuda.synchronize()
         if dpk is not None:
@@ -532,10 +725,10 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
 
 
 if __name__ == "__main__":
-    dr, mk, vf = "--device-randomness" in sys.argv, "--mock" in sys.argv, "--verify" in sys.argv
-    sys.argv = [a for a in sys.argv if a not in ("--device-randomness", "--mock", "--verify")]
+    dr, mk, vf, tp = "--device-randomness" in sys.argv, "--mock" in sys.argv, "--verify" in sys.argv, "--transcript" in sys.argv
+    sys.argv = [a for a in sys.argv if a not in ("--device-randomness", "--mock", "--verify", "--transcript")]
     kk = int(sys.argv[1]) if len(sys.argv) > 1 else 16
     gg = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     ll = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-    res = run(kk, gg, lookups=ll, device_randomness=dr, mock=mk, verify=vf)
+    res = run(kk, gg, lookups=ll, device_randomness=dr, mock=mk, verify=vf, transcript=tp)
     sys.exit(0 if all(res["checks"].values()) else 1)

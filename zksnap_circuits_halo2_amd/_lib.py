@@ -127,6 +127,22 @@ _SIGS = {
     "zkhip_multiopen_shplonk_begin_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "zkhip_multiopen_shplonk_finish_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_multiopen_shplonk_abort": (C.c_int, [C.c_void_p]),
+    "zkhip_transcript_new": (C.c_void_p, [C.c_int]),
+    "zkhip_transcript_new_reader": (C.c_void_p, [C.c_char_p, C.c_size_t, C.c_int]),
+    "zkhip_transcript_free": (None, [C.c_void_p]),
+    "zkhip_transcript_common_scalars": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "zkhip_transcript_common_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "zkhip_transcript_squeeze": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "zkhip_transcript_write_scalars": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "zkhip_transcript_write_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "zkhip_transcript_write_scalars_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "zkhip_transcript_write_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "zkhip_transcript_read_scalars": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "zkhip_transcript_read_points_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zkhip_transcript_read_points": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "zkhip_transcript_proof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "zkhip_test_reduce512": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "zkhip_test_transcript_chunk": (C.c_uint32, [C.c_size_t]),
     "zkhip_profile_enable": (C.c_int, [C.c_int]),
     "zkhip_profile_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "zkhip_profile_read_calls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),

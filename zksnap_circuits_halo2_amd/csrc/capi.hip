@@ -28,6 +28,7 @@
 #include <thread>
 #include <vector>
 #include "zkhip_internal.hpp"
+#include "blake2b.hpp"
 #include "../../include/zkhip.hpp"   // host-side 4 x 64 Montgomery arithmetic for domain constants (zkhip::halo2::detail)
 
 namespace zkhip {
@@ -159,8 +160,10 @@ struct scratch {       // one user at a time: the calls of one stream
   dev_buf q_ext;                       // zkhip_fr_eval_rows_sharded_device on one device: the extended cosets of the COEFF columns
   vm_staging vm_stage;                 // pinned host staging of the row programs' blobs (rowvm.hip)
   arg_ring args;                       // pinned slots for the small host arrays of `_device` calls (lists of column addresses, coefficients)
+  dev_buf transcript;                  // the transcript calls' records: a head (TR_HEAD bytes, word 0 = the call's count of identity inputs) + the payload
+  int pins = 0;                        // `_device` calls that wait on this set's stream WITHOUT g_mu (the transcript's): a pinned set is not evicted
   uint64_t last_use = 0;
-  void release() { ws.release(); scalars.release(); bases.release(); poly.release(); poly2.release(); small.release(); ntt_tmp.release(); vm.release(); gather.release(); q_ext.release(); vm_stage.release(); args.release(); }
+  void release() { transcript.release(); ws.release(); scalars.release(); bases.release(); poly.release(); poly2.release(); small.release(); ntt_tmp.release(); vm.release(); gather.release(); q_ext.release(); vm_stage.release(); args.release(); }
 };
 
 constexpr int STREAM_PIECES_MAX = 64;      // pieces of one chunked host-buffer MSM
@@ -318,7 +321,7 @@ static scratch* scratch_for(device_ctx& d, hipStream_t stream) {
     for (auto jt = d.scratch_by_stream.begin(); jt != d.scratch_by_stream.end(); ++jt) {
       bool is_lane = (jt->first == d.side && d.side != nullptr) || (jt->first == d.fan && d.fan != nullptr);
       for (auto& L : d.lanes) is_lane |= (L.stream == jt->first);
-      if (is_lane) continue;
+      if (is_lane || jt->second->pins) continue;
       if (victim == d.scratch_by_stream.end() || jt->second->last_use < victim->second->last_use) victim = jt;
     }
     if (victim != d.scratch_by_stream.end()) {
@@ -637,6 +640,7 @@ void zkhip_shutdown(void) {
   for (;;) {
     bool busy = false;
     for (auto& L : primary().lanes) busy |= L.busy;
+    for (auto& kv : primary().scratch_by_stream) busy |= kv.second->pins != 0;      // a transcript `_device` call is waiting on its stream
     if (!busy) break;
     g_lane_cv.wait(lk);
   }
@@ -3092,5 +3096,363 @@ int zkhip_test_fq12_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* o
   HIPCHK(hipMemcpyAsync(out, d + 768, 768, hipMemcpyDeviceToHost, s));
   return H.finish();
 }
+
+}  // extern "C"
+
+// ---- transcript (include/zkhip.h, "transcript"): Blake2bWrite / Blake2bRead with Challenge255 ------------------------------------------------
+// The object is host state: the hash, the proof bytes, a cursor, and a pinned staging block for the `_device` calls.  The calls marked "host" in
+// the header never reach ensure_init(): their field arithmetic is zkhip::halo2::detail's 4 x 64 Montgomery product.
+struct zkhip_transcript {
+  zkhip::blake2b st;
+  std::vector<uint8_t> proof;
+  size_t cursor = 0;
+  bool reader = false;
+  int layout = 0;
+  void* pinned = nullptr;              // hipHostMalloc, grown on demand by the `_device` calls
+  size_t pinned_cap = 0;
+};
+
+namespace zkhip {
+namespace hd = halo2::detail;
+
+constexpr size_t TR_HEAD = 256;        // bytes in front of the payload in scratch::transcript
+constexpr size_t TR_MAX = (size_t)1 << 24;
+
+static const uint64_t RAW_ONE_64[4] = {1, 0, 0, 0};
+// host byte order is little-endian (as everywhere in this library: the external formats are memcpy'd limbs)
+static void fr_mont_to_repr(const uint64_t m[4], uint8_t out[32]) { uint64_t c[4]; hd::mont_mul(c, m, RAW_ONE_64, hd::R_MOD, hd::R_INV); memcpy(out, c, 32); }
+static void fq_mont_to_repr(const uint64_t m[4], uint8_t out[32]) { uint64_t c[4]; hd::mont_mul(c, m, RAW_ONE_64, hd::Q_MOD, hd::Q_INV); memcpy(out, c, 32); }
+static bool fr_repr_to_mont(const uint8_t in[32], uint64_t out[4]) {
+  uint64_t v[4];
+  memcpy(v, in, 32);
+  if (hd::geq(v, hd::R_MOD)) return false;
+  hd::mont_mul(out, v, hd::R_R2, hd::R_MOD, hd::R_INV);
+  return true;
+}
+// 64 bytes as a little-endian integer lo + 2^256 hi, mod r, in Montgomery form: lo R + hi R^2 = mont(lo, R^2) + mont(hi, R^3)
+// (the Montgomery product accepts one factor below 2^256 when the other is below r: the result is below 2r before its one subtraction)
+static void fr_reduce512(const uint8_t in[64], uint64_t out[4]) {
+  uint64_t lo[4], hi[4], r3[4];
+  memcpy(lo, in, 32);
+  memcpy(hi, in + 32, 32);
+  hd::mont_mul(r3, hd::R_R2, hd::R_R2, hd::R_MOD, hd::R_INV);
+  halo2::Fr a, b;
+  hd::mont_mul(a.l, lo, hd::R_R2, hd::R_MOD, hd::R_INV);
+  hd::mont_mul(b.l, hi, r3, hd::R_MOD, hd::R_INV);
+  const halo2::Fr sum = hd::add_fr(a, b);
+  memcpy(out, sum.l, 32);
+}
+
+static void tr_absorb_scalar(zkhip_transcript* t, const uint8_t repr[32]) {
+  uint8_t b[33];
+  b[0] = 0x02;
+  memcpy(b + 1, repr, 32);
+  t->st.update(b, 33);
+}
+static void tr_absorb_point(zkhip_transcript* t, const uint8_t xy[64]) {
+  uint8_t b[65];
+  b[0] = 0x01;
+  memcpy(b + 1, xy, 64);
+  t->st.update(b, 65);
+}
+static bool bytes_zero(const uint8_t* p, size_t n) { for (size_t i = 0; i < n; i++) if (p[i]) return false; return true; }
+
+static int tr_pinned(zkhip_transcript* t, size_t bytes) {
+  if (bytes <= t->pinned_cap) return ZKHIP_OK;
+  if (t->pinned) (void)hipHostFree(t->pinned);
+  t->pinned = nullptr; t->pinned_cap = 0;
+  const size_t want = bytes + bytes / 2 + 4096;
+  if (hipHostMalloc(&t->pinned, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); t->pinned = nullptr; set_error("transcript: hipHostMalloc(%zu) failed", want); return ZKHIP_ENOMEM; }
+  t->pinned_cap = want;
+  return ZKHIP_OK;
+}
+// the scratch set's record buffer with room for `payload` bytes behind the head
+static int tr_reserve(scratch* sc, size_t payload) { return sc->transcript.reserve(TR_HEAD + payload); }
+// A scratch set resolved under g_mu and then used WITHOUT it: the transcript's `_device` calls wait for the caller's stream -- all of the
+// caller's earlier work, the MSMs that made the commitments included -- and hash on the host, and no other thread's call should stand
+// behind that.  While pinned the set is not evicted (scratch_for) and zkhip_shutdown waits for it.  One stream, one enqueuing thread at a
+// time (include/zkhip.h), so the set has one user.
+struct scratch_pin {
+  scratch* sc = nullptr;
+  int rc = ZKHIP_OK;
+  explicit scratch_pin(hipStream_t s) {
+    std::lock_guard<std::recursive_mutex> g(g_mu);
+    if ((rc = ensure_init()) != ZKHIP_OK) return;
+    sc = scratch_for(primary(), s);
+    sc->pins++;
+  }
+  ~scratch_pin() {
+    if (!sc) return;
+    std::lock_guard<std::recursive_mutex> g(g_mu);
+    sc->pins--;
+    g_lane_cv.notify_all();
+  }
+  scratch_pin(const scratch_pin&) = delete;
+  scratch_pin& operator=(const scratch_pin&) = delete;
+};
+// The failure guard of the `_device` transcript calls, the lanes' rule on a caller's stream: a call that returns without
+// done() -- any error after its first enqueue -- waits for the stream first, so that no copy into the transcript's pinned block is left queued.
+struct stream_drain {
+  hipStream_t s;
+  bool armed = true;
+  explicit stream_drain(hipStream_t st) : s(st) {}
+  void done() { armed = false; }
+  ~stream_drain() { if (armed) { (void)hipStreamSynchronize(s); (void)hipGetLastError(); } }
+};
+
+// one launch, one copy into the pinned block, one wait; then the host absorbs and appends.  The caller drains `s` on a non-OK return.
+static int tr_write_points_core(zkhip_transcript* t, scratch* sc, hipStream_t s, const void* d_points, size_t n) {
+  int rc;
+  if ((rc = tr_reserve(sc, n * 96)) != ZKHIP_OK) return rc;
+  if ((rc = tr_pinned(t, TR_HEAD + n * 96)) != ZKHIP_OK) return rc;
+  char* d = (char*)sc->transcript.p;
+  *(uint32_t*)t->pinned = 0;                               // the call's identity count starts at zero: no state is carried between calls
+  HIPCHK(hipMemcpyAsync(d, t->pinned, 4, hipMemcpyHostToDevice, s));
+  if ((rc = transcript_points_device((const uint32_t*)d_points, n, (uint32_t*)(d + TR_HEAD), t->layout, (uint32_t*)d, s)) != ZKHIP_OK) return rc;
+  HIPCHK(hipMemcpyAsync(t->pinned, d, TR_HEAD + n * 96, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const uint8_t* rec = (const uint8_t*)t->pinned + TR_HEAD;
+  const uint32_t identities = *(const uint32_t*)t->pinned;
+  if (identities) {
+    size_t first = 0;
+    while (first < n && !bytes_zero(rec + first * 96, 64)) first++;      // an identity input's record is zeros; no curve point has x = y = 0
+    set_error("transcript: cannot write points at infinity to the transcript (point %zu of %zu; %u in all)", first, n, identities);
+    return ZKHIP_EINVAL;
+  }
+  t->proof.reserve(t->proof.size() + n * 32);
+  for (size_t i = 0; i < n; i++) {
+    tr_absorb_point(t, rec + i * 96);
+    t->proof.insert(t->proof.end(), rec + i * 96 + 64, rec + i * 96 + 96);
+  }
+  return ZKHIP_OK;
+}
+
+static int tr_write_scalars_core(zkhip_transcript* t, scratch* sc, hipStream_t s, const void* d_fr, size_t n) {
+  int rc;
+  if ((rc = tr_reserve(sc, n * 32)) != ZKHIP_OK) return rc;
+  if ((rc = tr_pinned(t, n * 32)) != ZKHIP_OK) return rc;
+  char* d = (char*)sc->transcript.p + TR_HEAD;
+  if ((rc = transcript_scalars_device((const uint32_t*)d_fr, n, (uint32_t*)d, s)) != ZKHIP_OK) return rc;
+  HIPCHK(hipMemcpyAsync(t->pinned, d, n * 32, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const uint8_t* rec = (const uint8_t*)t->pinned;
+  for (size_t i = 0; i < n; i++) tr_absorb_scalar(t, rec + i * 32);
+  t->proof.insert(t->proof.end(), rec, rec + n * 32);
+  return ZKHIP_OK;
+}
+
+// payload: encodings (32 n) | first_bad (64 bytes) | canonical x | y records (64 n).  host_out (nullable): the affine points, downloaded
+// before anything is absorbed.
+static int tr_read_points_core(zkhip_transcript* t, scratch* sc, hipStream_t s, size_t n, void* d_affine, uint64_t* host_out) {
+  int rc;
+  const size_t enc = n * 32, payload = enc + 64 + n * 64;
+  if ((rc = tr_reserve(sc, payload)) != ZKHIP_OK) return rc;
+  if ((rc = tr_pinned(t, payload)) != ZKHIP_OK) return rc;
+  char* d = (char*)sc->transcript.p + TR_HEAD;
+  uint8_t* pin = (uint8_t*)t->pinned;
+  memcpy(pin, t->proof.data() + t->cursor, enc);
+  memset(pin + enc, 0, 64);
+  *(unsigned long long*)(pin + enc) = (unsigned long long)n;
+  HIPCHK(hipMemcpyAsync(d, pin, enc + 64, hipMemcpyHostToDevice, s));
+  unsigned long long* d_bad = (unsigned long long*)(d + enc);
+  if ((rc = g1_decompress_device((const uint32_t*)d, n, (uint32_t*)d_affine, t->layout, d_bad, s)) != ZKHIP_OK) return rc;
+  if ((rc = transcript_affine_device((const uint32_t*)d_affine, n, (uint32_t*)(d + enc + 64), d_bad, s)) != ZKHIP_OK) return rc;
+  HIPCHK(hipMemcpyAsync(pin + enc, d + enc, 64 + n * 64, hipMemcpyDeviceToHost, s));
+  if (host_out) HIPCHK(hipMemcpyAsync(host_out, d_affine, n * 64, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const unsigned long long bad = *(const unsigned long long*)(pin + enc);
+  if (bad < n) {
+    set_error("transcript: read_points: encoding %llu of %zu (proof byte %zu) is not a point a transcript accepts (x not canonical, not on the curve, or the identity)",
+              bad, n, t->cursor + (size_t)bad * 32);
+    return ZKHIP_EINVAL;
+  }
+  for (size_t i = 0; i < n; i++) tr_absorb_point(t, pin + enc + 64 + i * 64);
+  t->cursor += enc;
+  return ZKHIP_OK;
+}
+
+static int tr_check_write(const zkhip_transcript* t, const void* p, size_t n, const char* who) {
+  if (!t || (n && !p)) { set_error("%s: null pointer", who); return ZKHIP_EINVAL; }
+  if (t->reader) { set_error("%s: this transcript reads a proof", who); return ZKHIP_EINVAL; }
+  if (n > TR_MAX) { set_error("%s: more than 2^24 elements in one call", who); return ZKHIP_EINVAL; }
+  return ZKHIP_OK;
+}
+static int tr_check_read(const zkhip_transcript* t, const void* p, size_t n, const char* who) {
+  if (!t || (n && !p)) { set_error("%s: null pointer", who); return ZKHIP_EINVAL; }
+  if (!t->reader) { set_error("%s: this transcript writes a proof", who); return ZKHIP_EINVAL; }
+  if (n > TR_MAX || n * 32 > t->proof.size() - t->cursor) { set_error("%s: %zu elements asked for, %zu bytes of proof left", who, n, t->proof.size() - t->cursor); return ZKHIP_EINVAL; }
+  return ZKHIP_OK;
+}
+
+}  // namespace zkhip
+
+extern "C" {
+
+zkhip_transcript* zkhip_transcript_new(int flag_layout) {
+  if (flag_layout < 0 || flag_layout > 1) { set_error("transcript_new: flag_layout %d", flag_layout); return nullptr; }
+  zkhip_transcript* t = new (std::nothrow) zkhip_transcript();
+  if (!t) { set_error("transcript_new: out of memory"); return nullptr; }
+  t->layout = flag_layout;
+  t->st.init(64, (const uint8_t*)"Halo2-Transcript");
+  return t;
+}
+
+zkhip_transcript* zkhip_transcript_new_reader(const uint8_t* proof, size_t len, int flag_layout) {
+  if (len && !proof) { set_error("transcript_new_reader: null pointer"); return nullptr; }
+  zkhip_transcript* t = zkhip_transcript_new(flag_layout);
+  if (!t) return nullptr;
+  t->reader = true;
+  t->proof.assign(proof, proof + len);
+  return t;
+}
+
+void zkhip_transcript_free(zkhip_transcript* t) {
+  if (!t) return;
+  if (t->pinned) { (void)hipHostFree(t->pinned); (void)hipGetLastError(); }
+  delete t;
+}
+
+int zkhip_transcript_common_scalars(zkhip_transcript* t, const uint64_t* fr_mont, size_t n) {
+  if (!t || (n && !fr_mont)) { set_error("transcript_common_scalars: null pointer"); return ZKHIP_EINVAL; }
+  for (size_t i = 0; i < n; i++) {
+    uint8_t repr[32];
+    fr_mont_to_repr(fr_mont + i * 4, repr);
+    tr_absorb_scalar(t, repr);
+  }
+  return ZKHIP_OK;
+}
+
+int zkhip_transcript_common_points(zkhip_transcript* t, const uint64_t* affine_mont, size_t n) {
+  if (!t || (n && !affine_mont)) { set_error("transcript_common_points: null pointer"); return ZKHIP_EINVAL; }
+  for (size_t i = 0; i < n; i++)
+    if (bytes_zero((const uint8_t*)(affine_mont + i * 8), 64)) { set_error("transcript: cannot write points at infinity to the transcript (point %zu of %zu)", i, n); return ZKHIP_EINVAL; }
+  for (size_t i = 0; i < n; i++) {
+    uint8_t xy[64];
+    fq_mont_to_repr(affine_mont + i * 8, xy);
+    fq_mont_to_repr(affine_mont + i * 8 + 4, xy + 32);
+    tr_absorb_point(t, xy);
+  }
+  return ZKHIP_OK;
+}
+
+int zkhip_transcript_squeeze(zkhip_transcript* t, uint64_t out_fr_mont[4]) {
+  if (!t || !out_fr_mont) { set_error("transcript_squeeze: null pointer"); return ZKHIP_EINVAL; }
+  const uint8_t prefix = 0x00;
+  t->st.update(&prefix, 1);
+  uint8_t digest[64];
+  t->st.digest(digest, 64);
+  fr_reduce512(digest, out_fr_mont);
+  return ZKHIP_OK;
+}
+
+int zkhip_transcript_write_scalars(zkhip_transcript* t, const uint64_t* fr_mont, size_t n) {
+  int rc = tr_check_write(t, fr_mont, n, "transcript_write_scalars");
+  if (rc != ZKHIP_OK) return rc;
+  for (size_t i = 0; i < n; i++) {
+    uint8_t repr[32];
+    fr_mont_to_repr(fr_mont + i * 4, repr);
+    tr_absorb_scalar(t, repr);
+    t->proof.insert(t->proof.end(), repr, repr + 32);
+  }
+  return ZKHIP_OK;
+}
+
+int zkhip_transcript_write_points_device(zkhip_transcript* t, const void* d_points_xyz, size_t n, void* stream) {
+  ZK_API_RANGE();
+  int rc = tr_check_write(t, d_points_xyz, n, "transcript_write_points_device");
+  if (rc != ZKHIP_OK) return rc;
+  if ((uintptr_t)d_points_xyz & 15) { set_error("transcript_write_points_device: d_points_xyz must be 16-byte aligned"); return ZKHIP_EINVAL; }
+  if (n == 0) return ZKHIP_OK;
+  hipStream_t s = caller_stream(stream);
+  scratch_pin P(s);                                        // g_mu is not held while the call waits for the stream and hashes
+  if (P.rc != ZKHIP_OK) return P.rc;
+  stream_drain drain(s);
+  if ((rc = tr_write_points_core(t, P.sc, s, d_points_xyz, n)) != ZKHIP_OK) return rc;
+  drain.done();
+  return ZKHIP_OK;
+}
+
+int zkhip_transcript_write_scalars_device(zkhip_transcript* t, const void* d_fr, size_t n, void* stream) {
+  ZK_API_RANGE();
+  int rc = tr_check_write(t, d_fr, n, "transcript_write_scalars_device");
+  if (rc != ZKHIP_OK) return rc;
+  if ((uintptr_t)d_fr & 15) { set_error("transcript_write_scalars_device: d_fr must be 16-byte aligned"); return ZKHIP_EINVAL; }
+  if (n == 0) return ZKHIP_OK;
+  hipStream_t s = caller_stream(stream);
+  scratch_pin P(s);                                        // g_mu is not held while the call waits for the stream and hashes
+  if (P.rc != ZKHIP_OK) return P.rc;
+  stream_drain drain(s);
+  if ((rc = tr_write_scalars_core(t, P.sc, s, d_fr, n)) != ZKHIP_OK) return rc;
+  drain.done();
+  return ZKHIP_OK;
+}
+
+int zkhip_transcript_write_points(zkhip_transcript* t, const uint64_t* points_xyz, size_t n) {
+  ZK_API_RANGE();
+  int rc = tr_check_write(t, points_xyz, n, "transcript_write_points");
+  if (rc != ZKHIP_OK) return rc;
+  if (n == 0) return ZKHIP_OK;
+  lane_hold H;                                             // drains its stream when the call leaves without finish()
+  if (H.rc != ZKHIP_OK) return H.rc;
+  if ((rc = H.sc->poly.reserve(n * 96)) != ZKHIP_OK) return rc;
+  HIPCHK(hipMemcpyAsync(H.sc->poly.p, points_xyz, n * 96, hipMemcpyHostToDevice, H.s));
+  if ((rc = tr_write_points_core(t, H.sc, H.s, H.sc->poly.p, n)) != ZKHIP_OK) return rc;
+  return H.finish();
+}
+
+int zkhip_transcript_read_scalars(zkhip_transcript* t, size_t n, uint64_t* fr_mont) {
+  int rc = tr_check_read(t, fr_mont, n, "transcript_read_scalars");
+  if (rc != ZKHIP_OK) return rc;
+  const uint8_t* src = t->proof.data() + t->cursor;
+  for (size_t i = 0; i < n; i++)
+    if (!fr_repr_to_mont(src + i * 32, fr_mont + i * 4)) { set_error("transcript: read_scalars: scalar %zu of %zu (proof byte %zu) is not below r", i, n, t->cursor + i * 32); return ZKHIP_EINVAL; }
+  for (size_t i = 0; i < n; i++) tr_absorb_scalar(t, src + i * 32);
+  t->cursor += n * 32;
+  return ZKHIP_OK;
+}
+
+int zkhip_transcript_read_points_device(zkhip_transcript* t, size_t n, void* d_affine, void* stream) {
+  ZK_API_RANGE();
+  int rc = tr_check_read(t, d_affine, n, "transcript_read_points_device");
+  if (rc != ZKHIP_OK) return rc;
+  if ((uintptr_t)d_affine & 15) { set_error("transcript_read_points_device: d_affine must be 16-byte aligned"); return ZKHIP_EINVAL; }
+  if (n == 0) return ZKHIP_OK;
+  hipStream_t s = caller_stream(stream);
+  scratch_pin P(s);                                        // g_mu is not held while the call waits for the stream and hashes
+  if (P.rc != ZKHIP_OK) return P.rc;
+  stream_drain drain(s);
+  if ((rc = tr_read_points_core(t, P.sc, s, n, d_affine, nullptr)) != ZKHIP_OK) return rc;
+  drain.done();
+  return ZKHIP_OK;
+}
+
+int zkhip_transcript_read_points(zkhip_transcript* t, size_t n, uint64_t* affine_mont) {
+  ZK_API_RANGE();
+  int rc = tr_check_read(t, affine_mont, n, "transcript_read_points");
+  if (rc != ZKHIP_OK) return rc;
+  if (n == 0) return ZKHIP_OK;
+  lane_hold H;
+  if (H.rc != ZKHIP_OK) return H.rc;
+  if ((rc = H.sc->bases.reserve(n * 64)) != ZKHIP_OK) return rc;
+  if ((rc = tr_read_points_core(t, H.sc, H.s, n, H.sc->bases.p, affine_mont)) != ZKHIP_OK) return rc;
+  return H.finish();
+}
+
+int zkhip_transcript_proof(const zkhip_transcript* t, uint8_t* buf, size_t cap, size_t* len) {
+  if (!t || !len) { set_error("transcript_proof: null pointer"); return ZKHIP_EINVAL; }
+  *len = t->proof.size();
+  if (!buf) return ZKHIP_OK;
+  if (cap < t->proof.size()) { set_error("transcript_proof: %zu bytes of room, %zu needed", cap, t->proof.size()); return ZKHIP_EINVAL; }
+  if (!t->proof.empty()) memcpy(buf, t->proof.data(), t->proof.size());
+  return ZKHIP_OK;
+}
+
+int zkhip_test_reduce512(const uint8_t in64[64], uint64_t out_fr_mont[4]) {
+  if (!in64 || !out_fr_mont) { set_error("test_reduce512: null pointer"); return ZKHIP_EINVAL; }
+  fr_reduce512(in64, out_fr_mont);
+  return ZKHIP_OK;
+}
+
+uint32_t zkhip_test_transcript_chunk(size_t n) { return transcript_chunk(n); }
 
 }  // extern "C"

@@ -170,6 +170,17 @@ ZK_D bool affine_is_identity(const affine_words& a) {
   return o == 0;
 }
 
+ZK_D bool words_zero(const uint32_t (&w)[8]) { return (w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0; }
+
+// internal form (any multiply output) -> the canonical integer's limbs
+ZK_D fe fq_plain(const fe& a) { return fe_canon_lt2p<Fq>(fe_mul<Fq>(fe_const<Fq>(Fq::RAW_ONE), a)); }
+
+// `GroupEncoding` of a point that is not the identity (serde.hip has the layouts): the canonical x words with the sign of canonical y in the flag bit
+ZK_D void g1_encoding_words(const fe& x_plain, const fe& y_plain, int layout, uint32_t (&w)[8]) {
+  fe_pack(x_plain, w);
+  w[7] |= (y_plain.l[0] & 1u) << (layout == 0 ? 30 : 31);
+}
+
 // XYZZ -> G1 Jacobian memory (x||y||z, 24 u32 words, canonical Montgomery-256; identity = (0, 1, 0)
 // like halo2curves `G1::identity()` [DEP]).  (X, Y, ZZ, ZZZ) -> (X ZZ^2, Y ZZZ^2, ZZZ).
 ZK_D void store_jacobian(const xyzz& a, uint32_t* out) {

@@ -37,9 +37,6 @@ __device__ __forceinline__ bool raw_below_q(const fe& v) {      // v = limbs of 
   return lt;
 }
 
-// internal form (any multiply output) -> the canonical integer's limbs
-__device__ __forceinline__ fe fq_plain(const fe& a) { return fe_canon_lt2p<Fq>(fe_mul<Fq>(fq_const(Fq::RAW_ONE), a)); }
-
 __global__ void __launch_bounds__(256) k_g1_compress(const uint32_t* __restrict__ pts, size_t n, uint32_t* __restrict__ out, int layout) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -51,8 +48,7 @@ __global__ void __launch_bounds__(256) k_g1_compress(const uint32_t* __restrict_
     const fe from_ext = fq_const(Fq::FROM_EXT_CANON);
     const fe x = fe_canon_lt2p<Fq>(fe_mul<Fq>(from_ext, fe_unpack<0>(p.x)));     // x * 2^256 -> x
     const fe y = fe_canon_lt2p<Fq>(fe_mul<Fq>(from_ext, fe_unpack<0>(p.y)));
-    fe_pack(x, w);
-    w[7] |= (y.l[0] & 1u) << (layout == 0 ? 30 : 31);
+    g1_encoding_words(x, y, layout, w);
   }
   store_words(out + i * 8, w);
 }

@@ -239,6 +239,14 @@ int fr_random_rows_device(const uint8_t seed[32], uint64_t stream_id, uint64_t f
 int g1_compress_device(const uint32_t* d_points, size_t n, uint32_t* d_out, int layout, hipStream_t stream);
 int g1_decompress_device(const uint32_t* d_in, size_t n, uint32_t* d_points, int layout, unsigned long long* d_first_bad, hipStream_t stream);
 
+// transcript.hip: the conversions that feed the transcript's hash (include/zkhip.h, "transcript").  All pointers 16-byte aligned.
+uint32_t transcript_chunk(size_t n);      // points that share one inversion in a launch over n points
+// n Jacobian points -> n x 96 bytes (canonical x | canonical y | GroupEncoding); the number of identity inputs is added to *d_ident (zero before the launch)
+int transcript_points_device(const uint32_t* d_in, size_t n, uint32_t* d_out, int layout, uint32_t* d_ident, hipStream_t stream);
+int transcript_scalars_device(const uint32_t* d_in, size_t n, uint32_t* d_out, hipStream_t stream);
+// n affine points -> n x 64 bytes (canonical x | y); atomicMin of the indices of (0, 0) points into *d_first_bad
+int transcript_affine_device(const uint32_t* d_points, size_t n, uint32_t* d_out, unsigned long long* d_first_bad, hipStream_t stream);
+
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);
 int g1_check_points_device(const uint32_t* d_points, size_t n, unsigned long long* d_first_bad, hipStream_t stream);

@@ -139,6 +139,14 @@ class ProverGWC:
             self.pool.give_back([batch, quot])
         return witnesses
 
+    def create_proof_transcript(self, queries: Sequence[ProverQuery], tr, stream: int = 0) -> List[np.ndarray]:
+        """`create_proof(transcript, queries)` with the transcript (transcript.Blake2bWrite): v is squeezed, every witness commitment written"""
+        v = tr.squeeze_challenge()
+        witnesses = self.create_proof(queries, v, stream)
+        if witnesses:
+            tr.write_points(np.stack(witnesses))
+        return witnesses
+
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # SHPLONK: `ProverSHPLONK::create_proof` [DEP poly/kzg/multiopen/shplonk.rs + shplonk/prover.rs] -- the multi-open of the reference's
@@ -246,9 +254,27 @@ class ProverSHPLONK:
         _lib.check(lib.zkhip_fr_divide_by_roots_device(C.c_void_p(d_poly), self.n, zw.ctypes.data, len(roots), C.c_void_p(d_tmp), None, stream))
         return d_tmp
 
+    def create_proof_transcript(self, queries: Sequence[ProverQuery], tr, stream: int = 0):
+        """`create_proof(transcript, queries)` with the transcript (transcript.Blake2bWrite), in the reference's order: squeeze y, squeeze v,
+        commit and write H, squeeze u, write H'.  -> (H, H')"""
+        y = tr.squeeze_challenge()
+        v = tr.squeeze_challenge()
+
+        def u_after(H):
+            tr.write_points(H.reshape(1, 12))
+            return tr.squeeze_challenge()
+
+        H, Hp = self._create_proof(queries, y, v, u_after, stream)
+        tr.write_points(Hp.reshape(1, 12))
+        return H, Hp
+
     def create_proof(self, queries: Sequence[ProverQuery], y: int, v: int, u: int, stream: int = 0):
         """-> (H, H') as 12-limb Jacobian commitments.  In the reference y and v are squeezed before h is committed and u after h has been
         written to the transcript; here all three are arguments."""
+        return self._create_proof(queries, y, v, lambda H: u, stream)
+
+    def _create_proof(self, queries: Sequence[ProverQuery], y: int, v: int, u_of_H, stream: int = 0):
+        """the prover with u asked for once H exists (`u_of_H(H) -> u`): the one place where the transcript reaches into the argument"""
         lib = _lib.load()
         n = self.n
         evaluate_queries(queries, self.k, stream)
@@ -273,6 +299,7 @@ class ProverSHPLONK:
             E.linear_combination_program(vpow).run_device(quotients, self.k, h_x, stream=stream)
             _lib.check(lib.zkhip_stream_sync(stream))         # `commit` runs on a stream of its own choosing: hand it finished coefficients
             H = np.array(self.commit(h_x), dtype=np.uint64).reshape(12)
+            u = u_of_H(H)
             # ---- L(X) and the final quotient ----------------------------------------------------------------------------------------------
             z_diffs = [_vanishing_at([p for p in super_points if p not in rs.points], u) for rs in sets]
             zt_eval = _vanishing_at(super_points, u)
@@ -371,6 +398,11 @@ def _affine_to_xyz(point: np.ndarray) -> np.ndarray:
     return out
 
 
+def _read_xyz(tr, n: int) -> List[np.ndarray]:
+    """n points read from a transcript, as Jacobian points with z = 1 (a transcript holds no identity)"""
+    return [_affine_to_xyz(p) for p in tr.read_points(n, device=False)]
+
+
 def _generator_xyz(params) -> np.ndarray:
     """g[0] as a Jacobian point"""
     return _affine_to_xyz(params.g[0])
@@ -445,6 +477,19 @@ class VerifierGWC:
         L_neg = g1_combination([-s for s in left], np.stack(W))
         return _final_check(self.params, R_pt, L_neg)
 
+    def verify_proof_transcript(self, queries: Sequence[VerifierQuery], tr) -> bool:
+        """`verify_proof(transcript, queries, ..)` with the transcript (transcript.Blake2bRead): v is squeezed, one witness per distinct point
+        read, then u squeezed.  Proof bytes that do not decode reject."""
+        v = tr.squeeze_challenge()
+        try:
+            W = _read_xyz(tr, len(construct_intermediate_sets(queries)))
+        except _lib.ZkhipError as e:
+            if e.code == -1:
+                return False
+            raise
+        u = tr.squeeze_challenge()
+        return self.verify_proof(queries, W, v, u)
+
 
 class VerifierSHPLONK:
     """`VerifierSHPLONK::new(params)` / `verify_proof`: e(Lc + u H', g2) e(-H', [s]_2) = 1.  H, Hp: what `ProverSHPLONK.create_proof` returned."""
@@ -464,3 +509,18 @@ class VerifierSHPLONK:
         left = g1_combination(scalars, np.stack(commitment_points(queries, commitments) + [_generator_xyz(self.params), H, Hp]))
         right_neg = g1_combination([-1], Hp.reshape(1, 12))
         return _final_check(self.params, left, right_neg)
+
+    def verify_proof_transcript(self, queries: Sequence[VerifierQuery], tr) -> bool:
+        """`verify_proof(transcript, queries, ..)` with the transcript (transcript.Blake2bRead): squeeze y, squeeze v, read H, squeeze u, read
+        H'.  Proof bytes that do not decode reject."""
+        y = tr.squeeze_challenge()
+        v = tr.squeeze_challenge()
+        try:
+            H = _read_xyz(tr, 1)[0]
+            u = tr.squeeze_challenge()
+            Hp = _read_xyz(tr, 1)[0]
+        except _lib.ZkhipError as e:
+            if e.code == -1:
+                return False
+            raise
+        return self.verify_proof(queries, H, Hp, y, v, u)

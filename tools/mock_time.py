@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The three witness checks (zkhip_check_rows_device / _copies_ / _lookups_) against what the library offered for the same questions before
-they existed, on the witnesses tools/prove_flow.py builds: (k, gate columns, lookups) = (22, 4, 1), (13, 256, 8), (15, 64, 8).
+they existed, on the witnesses tools/prove_flow.py proves (prover.halo2_lib_witness): (k, gate columns, lookups) = (22, 4, 1), (13, 256, 8), (15, 64, 8).
 
   gates     zkhip_check_rows_device, every gate polynomial in one launch    against  one zkhip_fr_eval_rows_device per polynomial into a scratch
                                                                                       column, a download and a host scan for a non-zero word
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 import prove_flow
-from zksnap_circuits_halo2_amd import _lib, evaluation as E, fields as F, mock as M
+from zksnap_circuits_halo2_amd import _lib, evaluation as E, fields as F, mock as M, prover
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=9)
@@ -176,7 +176,10 @@ def measure(cs, k, fixed, advice, assembly, theta):
 for shape in args.shapes.split(","):
     k, g, l = (int(x) for x in shape.split(":"))
     print(f"==== prove_flow shape k = {k}, {g} gate columns, {l} lookups ====", flush=True)
-    prove_flow.run(k, g, lookups=l, verbose=False, on_witness=measure)
+    torch.manual_seed(1)
+    w = prover.halo2_lib_witness(k, g, l, prover.TorchBlinding())
+    measure(w.cs, k, w.fixed, w.advice, w.assembly, prover.SeededChallenges(1).theta())
+    del w
     if args.no_flow:
         continue
     prove_flow.run(k, g, lookups=l, verbose=False, mock=True)                                # warm: code objects, plans, scratch

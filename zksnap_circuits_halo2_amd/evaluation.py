@@ -156,6 +156,10 @@ class RowProgram:
         z = (SRC_CONST, 0, 0)
         self.insns.append((op, dst, a, b or z, c or z))
 
+    def registers_used(self) -> int:
+        """one more than the highest register an instruction writes or reads"""
+        return 1 + max([ins[1] for ins in self.insns] + [o[1] for ins in self.insns for o in ins[2:5] if o[0] == SRC_REG])
+
     # ---- marshalling -------------------------------------------------------------------------------
     def _marshal(self):
         n = len(self.insns)
@@ -744,6 +748,13 @@ def halo2_lib_shape(gate_cols: int, lookups: int, blinding: int = 5) -> Constrai
         permutation_columns=[("advice", i) for i in range(G + NL)] + [("fixed", G)], blinding_factors=blinding, degree=4)
 
 
+def to_mont_program() -> RowProgram:
+    """column 0 times R: raw integer words are the Montgomery form of a / R"""
+    prog = RowProgram()
+    prog.emit(OP_MUL, 0, prog.column(0), prog.constant(pow(2, 256, F.R_MOD)))
+    return prog
+
+
 def export_prover_programs(k: int, gate_cols: int, lookups: int, seed: int = 1) -> bytes:
     """Everything tests/cpp/prover_sequence.c needs for one proof of the halo2-lib shape at 2^k rows: the domain constants and the row
     programs (challenges seeded -- there is no transcript on this side), in the order the C program reads them."""
@@ -768,9 +779,7 @@ def export_prover_programs(k: int, gate_cols: int, lookups: int, seed: int = 1) 
            w(F.fr_encode([x])[0]), w(F.fr_encode([F.omega_for(k)])[0]), w(F.fr_encode([DELTA])[0]), w(F.fr_encode([beta])[0]), w(F.fr_encode([gamma])[0]),
            w(F.fr_encode(rot_points)), w(F.fr_encode([y_mo, v_mo, u_mo])),
            struct.pack("<I", dom.t_evaluations.shape[0]), w(dom.t_evaluations)]      # (version 2: omega, delta, beta, gamma; version 3: x omega^r for r = 0, 1, 2, 3, -1, u and the multi-open challenges)
-    to_mont = RowProgram()                # raw integer words are the Montgomery form of a / R: multiply by R
-    to_mont.emit(OP_MUL, 0, to_mont.column(0), to_mont.constant(pow(2, 256, F.R_MOD)))
-    progs = [to_mont]
+    progs = [to_mont_program()]
     for si in range(cs.num_permutation_sets):
         lo, hi = si * cs.chunk_len, min((si + 1) * cs.chunk_len, len(cs.permutation_columns))
         progs.append(permutation_numerator_program(hi - lo, lo, beta, gamma, k))

@@ -581,6 +581,22 @@ int zkhip_transcript_read_points(zkhip_transcript *t, size_t n, uint64_t *affine
 /* the proof: everything written so far (a writer) or the bytes given (a reader).  *len = its length; buf may be NULL to ask for the length,
  * otherwise cap must be at least that (ZKHIP_EINVAL, *len still set). */
 int zkhip_transcript_proof(const zkhip_transcript *t, uint8_t *buf, size_t cap, size_t *len);
+/* The same object over the Poseidon sponge of the section "Poseidon" below: snark-verifier's halo2 `PoseidonTranscript<G1Affine, NativeLoader, _>`,
+ * the transcript of the reference's `gen_snark` (/root/reference/aggregator/src/wrapper.rs:111-158).  Every zkhip_transcript_* call above works on
+ * it and dispatches on the object's hash; what differs (normative):
+ *   no prefix bytes anywhere.
+ *   common_scalar  appends the scalar to the sponge's buffer.
+ *   common_point   appends x mod r, then y mod r: the canonical Fq coordinates read as integers (q < 2 r: one conditional subtraction).  The
+ *                  identity is ZKHIP_EINVAL and leaves the transcript untouched.
+ *   squeeze        the sponge's squeeze; the challenge is that full Fr value.
+ *   write_*        the common_* call, then the SAME 32 bytes the Blake2b transcript appends: a proof's bytes do not depend on the hash, only
+ *                  its challenges do.  read_*: the same strict decoding, then the common_* call.  Atomicity and batches as above.
+ * The `_device` calls launch the same kernels and move the same 96 / 32 / 64-byte records; only what the host does with a record differs.
+ * The chain of permutations is serial and runs on the host inside the library: one permutation, 13 microseconds, per two absorbed elements
+ * (profiles/r15_poseidon.txt).  Pins: the first squeeze of a fresh Poseidon transcript is the fresh-sponge pin below; after common_point((1, 2))
+ * it is hash(1, 2). */
+zkhip_transcript *zkhip_transcript_new_poseidon(int flag_layout);                                       /* a writer; NULL on a bad layout */
+zkhip_transcript *zkhip_transcript_new_poseidon_reader(const uint8_t *proof, size_t len, int flag_layout);
 /* Per-phase timing with HIP events on the stream the kernels run on.  enable(1), run one call, then
  * zkhip_profile_read synchronises and returns the number of phases of the last profiled call, writing up to
  * `max` durations (milliseconds) and names (63 chars + NUL each). */
@@ -590,6 +606,50 @@ int zkhip_profile_read(double *ms, char (*names)[64], int max);
  * unprofiled); zkhip_profile_read_calls then synchronises and returns all recorded phases in call order, call_of[i] = index of the
  * call phase i belongs to.  The pool holds 2048 events (about 100 MSM calls); calls beyond it record nothing. */
 int zkhip_profile_read_calls(double *ms, char (*names)[64], int *call_of, int max);
+
+/* ---- Poseidon over Fr: T = 3, RATE = 2, R_F = 8, R_P = 57, x^5 (`SECURE_MDS = 0`) -- Merkle trees and the sponge of the Poseidon transcript ----
+ * [DEP pse_poseidon / snark-verifier `hash::Poseidon`; the reference's trees: /root/reference/voter/src/merkletree/native.rs:30-49, its
+ * `gen_snark` transcript: aggregator/src/wrapper.rs:111-158.]  Restated from the Poseidon paper.  The PERMUTATION is pinned by the published
+ * `poseidonperm_x5_254_3` vector and circomlib's poseidon([1, 2]); the FRAMING (sponge, tree, transcript) is pinned only as these lines word
+ * it, not against the crates: its parity with them is unpinned like the rest of this boundary.
+ * THE DEFINITION (normative):
+ *   Grain        an 80-bit state, initialised most-significant bit first from: field = 1 (2 bits), sbox = 0 (4), n = 254 (12), t = 3 (12),
+ *                R_F = 8 (10), R_P = 57 (10), thirty 1 bits.  A step: new = b62 ^ b51 ^ b38 ^ b23 ^ b13 ^ b0; b0 leaves, `new` is appended.
+ *                The first 160 new bits are discarded.  Output bits come from PAIRS of new bits: first = 1 emits the second, else nothing.
+ *   constants    round constants: (R_F + R_P) T = 195 elements in round order, then word order; each is 254 output bits as a big-endian
+ *                integer, redrawn while it is >= r.  Then 2 T more elements, 254 bits each reduced mod r WITHOUT rejection: xs the first T,
+ *                ys the next T, M[i][j] = (xs[i] + ys[j])^-1.  The library runs Grain itself, once per process; nothing is a pasted table.
+ *   permutation  65 rounds, each: add the round's three constants; x^5 on all three words in rounds 0-3 and 61-64, on word 0 only in
+ *                rounds 4-60; state'[i] = sum_j M[i][j] state[j].
+ *   sponge       a fresh state is (2^64, 0, 0) with an empty buffer; update appends to the buffer; squeeze takes the buffer and (1) for each
+ *                full chunk of 2 adds the chunk into words 1 and 2 and permutes, (2) adds the remaining 0 or 1 elements followed by a single
+ *                1 into words 1.. and permutes, (3) returns word 1.  The state carries on after a squeeze; the buffer is empty.
+ *   hash         a fresh sponge, one update, one squeeze.
+ *   Merkle tree  a power of two of leaves >= 1; node = hash(left, right); level 0 is the leaves; one leaf: the root is the leaf.
+ * Pins (canonical integers):
+ *   permute(0, 1, 2) = (0x115cc0f5e7d690413df64c6b9662e9cf2a3617f2743245519e19607a4417189a,
+ *                       0x0fca49b798923ab0239de1c9e7a4a9a2210312b6a2f616d18b5a87f9b628ae29,
+ *                       0x0e7ae82e40091e63cbd4f16a6d16310b3729d4b6e138fcf54110e2867045a30c)
+ *   constant [0][0] = 0x0ee9a592ba9a9518d05986d656f40c2114c4993c11bb29938d21d47304cd8e6e, M[0][0] = 0x109b7f411ba0e4c9b2b70caf5c36a7b194be7c11ad24378bfedb68592ba8118b
+ *   squeeze of a fresh sponge = 0x14b2e5484b232721d64f405caa487febbce835dd07c5de940f2a775dc9aa0da6
+ *   hash(1, 2) = 0x305df2f9f9f1c0b591427aa9fd8ff8b8b8ad8a16953065fca066cb6a69deff53
+ *   root of the leaves (1, 2, 3, 4) = 0x2c01ebd821c7ffc51531dc18169a856bfa0e54c4f5ff99b94f328a38d57d2194
+ * Elements are 4 Montgomery words like every other Fr here.  The calls marked "host" touch no GPU and work in a process that never initialises
+ * HIP.  The kernels run one lane per message or node (csrc/poseidon.hip). */
+#define ZKHIP_POSEIDON_MAX_WIDTH 16   /* the most elements of one message of zkhip_poseidon_hash_many_device */
+#define ZKHIP_POSEIDON_SUBTREE 256    /* elements of a level one workgroup of zkhip_poseidon_merkle_device folds: tree sizes around it take different paths */
+int zkhip_poseidon_permute(uint64_t *states, size_t n);                                                 /* host; n states of 12 words, in place */
+int zkhip_poseidon_hash(const uint64_t *fr, size_t n, uint64_t out[4]);                                 /* host; a fresh sponge over n elements */
+/* the table the permutation runs on, canonical integers (not Montgomery): 195 round constants, then the 9 matrix entries row-major (host) */
+int zkhip_poseidon_constants(uint64_t out[204 * 4]);
+/* n messages of `width` elements each, row-major at d_in; d_out[i] = hash of message i (a fresh sponge each).  1 <= width <=
+ * ZKHIP_POSEIDON_MAX_WIDTH, else ZKHIP_EINVAL.  One launch, no host wait (the FIRST Poseidon `_device` call of a process uploads the table and
+ * waits for that).  d_in and d_out 16-byte aligned; they must not overlap. */
+int zkhip_poseidon_hash_many_device(const void *d_in, size_t n, uint32_t width, void *d_out, void *stream);
+/* The n_leaves - 1 inner nodes of the tree over d_leaves, level 1 (n_leaves / 2 nodes) first, the root last: level L starts at node
+ * n_leaves - (n_leaves >> (L - 1)).  One launch behind one small memset, no host wait.  n_leaves = 1 writes nothing (the root is the leaf).
+ * ZKHIP_EINVAL, nothing enqueued: n_leaves not a power of two, 0, or above 2^30; a null or misaligned pointer.  d_nodes must not overlap d_leaves. */
+int zkhip_poseidon_merkle_device(const void *d_leaves, size_t n_leaves, void *d_nodes, void *stream);
 
 /* ---- parity hooks for the field / curve layer (rows a1/a2 of SURVEY.md section 8) ------------------ */
 /* field: 0 = Fq, 1 = Fr.  op: 0 mul, 1 add, 2 sub, 3 square (b ignored).  Elementwise on n elements. */

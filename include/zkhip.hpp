@@ -429,6 +429,29 @@ class DeviceVec {
   bool owned_ = true;
 };
 
+// Poseidon over Fr, T = 3, RATE = 2, R_F = 8, R_P = 57 (zkhip.h, "Poseidon"): `pse_poseidon::Poseidon` as far as the reference uses it -- `update`,
+// `squeeze_and_reset` (host, no GPU) -- and the trees of `MerkleTree::new` over leaves that lie in HBM.
+struct Poseidon {
+  std::vector<Fr> buf;
+  void update(const std::vector<Fr>& values) { buf.insert(buf.end(), values.begin(), values.end()); }
+  Fr squeeze_and_reset() {
+    Fr out;
+    check(zkhip_poseidon_hash(buf.empty() ? nullptr : buf[0].l, buf.size(), out.l), "Poseidon::squeeze_and_reset");
+    buf.clear();
+    return out;
+  }
+  static Fr hash(const std::vector<Fr>& values) { Poseidon p; p.update(values); return p.squeeze_and_reset(); }
+  static void permute(Fr (&state)[3]) { check(zkhip_poseidon_permute(state[0].l, 1), "Poseidon::permute"); }
+  // n messages of `width` elements at d_in -> n digests at d_out; one launch on `stream`
+  static void hash_many_device(const void* d_in, size_t n, uint32_t width, void* d_out, void* stream = nullptr) {
+    check(zkhip_poseidon_hash_many_device(d_in, n, width, d_out, stream), "Poseidon::hash_many_device");
+  }
+  // the n_leaves - 1 inner nodes, level 1 first, the root last; no host wait
+  static void merkle_device(const void* d_leaves, size_t n_leaves, void* d_nodes, void* stream = nullptr) {
+    check(zkhip_poseidon_merkle_device(d_leaves, n_leaves, d_nodes, stream), "Poseidon::merkle_device");
+  }
+};
+
 // `Blake2bWrite` / `Blake2bRead` with `Challenge255` [DEP transcript.rs] over zkhip_transcript_* (zkhip.h, "transcript"): the hash and the framing
 // run on the host inside the library, the `_device` forms take commitments / evaluations where they lie in HBM.  One thread at a time per object.
 class Transcript {
@@ -436,6 +459,11 @@ class Transcript {
   static Transcript writer(int flag_layout = 0) { return Transcript(zkhip_transcript_new(flag_layout)); }                       // Blake2bWrite::init(vec![])
   static Transcript reader(const std::vector<uint8_t>& proof, int flag_layout = 0) {                                              // Blake2bRead::init(proof)
     return Transcript(zkhip_transcript_new_reader(proof.data(), proof.size(), flag_layout));
+  }
+  // the same object over the Poseidon sponge (zkhip.h, "Poseidon"): snark-verifier's `PoseidonTranscript` with the native loader
+  static Transcript poseidon_writer(int flag_layout = 0) { return Transcript(zkhip_transcript_new_poseidon(flag_layout)); }
+  static Transcript poseidon_reader(const std::vector<uint8_t>& proof, int flag_layout = 0) {
+    return Transcript(zkhip_transcript_new_poseidon_reader(proof.data(), proof.size(), flag_layout));
   }
   Transcript(const Transcript&) = delete;
   Transcript& operator=(const Transcript&) = delete;

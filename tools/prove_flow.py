@@ -17,7 +17,8 @@ with `calculate_params(Some(20))` (/root/reference/voter/benches/voter_circuit.r
 the columns of a phase committed through ONE batched call (`zkhip_msm_g1_registered_batch_device`) as a Rust host would have to.  Checks (the prover's own invariants): both
 grand products close, the quotient is a polynomial (coefficients of degree >= 3n vanish), commit_lagrange(column) = commit(coefficients).
 By default there is no transcript: challenges are seeded.  --transcript (run(transcript=True)): Fiat-Shamir challenges from a Blake2b transcript, and
-the proof as bytes.  Usage: prove_flow.py [k] [gate_cols] [lookups] [--device-randomness] [--mock] [--verify] [--transcript]   (default 16 4 1).
+the proof as bytes; --poseidon --gwc: the Poseidon transcript and the GWC multi-open, `gen_snark`'s pair.
+Usage: prove_flow.py [k] [gate_cols] [lookups] [--device-randomness] [--mock] [--verify] [--transcript] [--poseidon] [--gwc]   (default 16 4 1).
 --mock (run(mock=True)): the witness is checked against the circuit on the device before keygen and the arguments run (lap `mock_prover`).
 --device-randomness (run(device_randomness=True)): every blinding tail is drawn by zkhip_fr_random_rows_device, all columns of a step in one
 call, and the vanishing argument's random polynomial is filled by zkhip_fr_random_device and committed (lap `vanishing_random_poly`); the
@@ -106,7 +107,7 @@ def _verify_seeded(pv, params, corrupt_proof, on_proof, lap):
 
 
 def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False,
-        sharded_key=False, lookups_one_call=True, device_randomness=False, mock=False, on_witness=None, verify=False, corrupt_proof=None, on_proof=None, transcript=False):
+        sharded_key=False, lookups_one_call=True, device_randomness=False, mock=False, on_witness=None, verify=False, corrupt_proof=None, on_proof=None, transcript=False, multiopen="shplonk"):
     """mock: what the reference's `gen_proof` does before it proves (`MockProver::run(..).assert_satisfied()`,
     /root/reference/aggregator/src/wrapper.rs:117-123), over the columns where they lie: `mock.MockProver(..).assert_satisfied()` once the
     witness columns and the copy constraints exist, as lap `mock_prover` (not part of `prove_ms`).  A witness broken with `corrupt=` then raises
@@ -121,7 +122,10 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
     `create_proof`'s order -- vk repr; advice commitments, theta; the lookups' permuted commitments, beta, gamma; permutation then lookup product
     commitments, the random polynomial's commitment (device_randomness), y; the quotient pieces, x; the evaluations in halo2's order, written from
     the device buffer they were computed into; the SHPLONK multi-open through `create_proof_transcript` -- and the result gains `proof` (bytes),
-    `proof_bytes`, `proof_plan` and `proof_shape`; lap `transcript` (part of `prove_ms`).  With verify as well, `verify_transcript_proof` gets
+    `proof_bytes`, `proof_plan` and `proof_shape`; lap `transcript` (part of `prove_ms`).  transcript="poseidon": the same flow under the
+    Poseidon transcript (transcript.PoseidonWrite; True and "blake2b" are Blake2b); multiopen="gwc" (transcript flows only): the GWC multi-open
+    instead of SHPLONK, lap `multiopen_gwc`.  run(transcript="poseidon", multiopen="gwc") is the pair the reference's `gen_snark` proves under
+    (/root/reference/aggregator/src/wrapper.rs:111-158).  With verify as well, `verify_transcript_proof` gets
     (params, vk, the proof bytes, shape and plan) after the prover's tensors are dropped.  corrupt_proof=("byte", i) flips bit 0 of proof byte i
     before that; the three named values belong to the seeded flow.  The mock step keeps the seeded theta.
     on_proof (with verify): a callable handed (params, k, queries, verifier queries, commit, (H, H'), (y, v, u)) after the verdict, while the
@@ -140,6 +144,12 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
     pk_file: path -- the proving key is written there (`ProvingKey::write`, RawBytesUnchecked), read back, and the READ key is what the
     prover uses (the reference's wrapper does the same through build/*_pk.bin: /root/reference/aggregator/src/wrapper.rs:967-989, :1007-1034)"""
     P.check_options(transcript, lookups, lookups_one_call, sharded_quotient, sharded_key)
+    tr_hash = "blake2b" if transcript is True else transcript      # False: seeded
+    if transcript:
+        P.transcript_classes(tr_hash)
+    P.multiopen_classes(multiopen)
+    if multiopen != "shplonk" and not transcript:
+        raise ValueError("multiopen=\"gwc\" needs a transcript: the seeded flow opens with SHPLONK")
     byte_flip = isinstance(corrupt_proof, tuple) and len(corrupt_proof) == 2 and corrupt_proof[0] == "byte"
     if corrupt_proof not in (None, "eval", "commitment", "witness") and not byte_flip:
         raise ValueError("corrupt_proof: eval, commitment, witness or (\"byte\", i)")
@@ -158,7 +168,7 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
     lap("setup_srs")
     try:
         w = P.halo2_lib_witness(k, gate_cols, lookups, blinding, lookup_bits, corrupt)
-        pv = P.Prover(params, w, blinding, batched, lap)
+        pv = P.Prover(params, w, blinding, batched, lap, multiopen)
         lap("witness_columns")
         pv.commit_advice()
         if mock:
@@ -172,7 +182,7 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
             lap("witness_columns")
         dpk, pk_bytes = _keygen(params, w, lap, pk_file, sharded_key)
         vk = dpk.vk
-        pv.prove(dpk, P.TranscriptChallenges(vk) if transcript else seeded, lookups_one_call, sharded_quotient, sharded_key)
+        pv.prove(dpk, P.TranscriptChallenges(vk, tr_hash) if transcript else seeded, lookups_one_call, sharded_quotient, sharded_key)
 
         proof_verifies = _verify_seeded(pv, params, corrupt_proof, on_proof, lap) if verify and not transcript else None
         n, ncol = pv.n, pv.qc.total
@@ -200,7 +210,8 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
                 checked = bytearray(res["proof"])
                 if byte_flip:
                     checked[corrupt_proof[1]] ^= 1
-                proof_verifies = verify_transcript_proof(params, vk, k, bytes(checked), dict(shape), list(res["proof_plan"]))
+                how = () if (tr_hash, multiopen) == ("blake2b", "shplonk") else (tr_hash, multiopen)      # the verifier's defaults
+                proof_verifies = verify_transcript_proof(params, vk, k, bytes(checked), dict(shape), list(res["proof_plan"]), *how)
             lap("verify")
         if verify:
             checks["proof_verifies"] = proof_verifies
@@ -224,9 +235,12 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
 
 if __name__ == "__main__":
     dr, mk, vf, tp = "--device-randomness" in sys.argv, "--mock" in sys.argv, "--verify" in sys.argv, "--transcript" in sys.argv
-    sys.argv = [a for a in sys.argv if a not in ("--device-randomness", "--mock", "--verify", "--transcript")]
+    if "--poseidon" in sys.argv:
+        tp = "poseidon"
+    mo = "gwc" if "--gwc" in sys.argv else "shplonk"
+    sys.argv = [a for a in sys.argv if a not in ("--device-randomness", "--mock", "--verify", "--transcript", "--poseidon", "--gwc")]
     kk = int(sys.argv[1]) if len(sys.argv) > 1 else 16
     gg = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     ll = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-    res = run(kk, gg, lookups=ll, device_randomness=dr, mock=mk, verify=vf, transcript=tp)
+    res = run(kk, gg, lookups=ll, device_randomness=dr, mock=mk, verify=vf, transcript=tp, multiopen=mo)
     sys.exit(0 if all(res["checks"].values()) else 1)

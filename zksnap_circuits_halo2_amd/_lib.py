@@ -9,6 +9,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libzkhip.so")
 ZKHIP_MAX_ROOTS = 8          # include/zkhip.h: the most roots of one zkhip_fr_divide_by_roots call
 ZKHIP_MAX_PAIRS = 64         # include/zkhip.h: the most pairs of one zkhip_pairing_check call
+ZKHIP_POSEIDON_MAX_WIDTH = 16   # include/zkhip.h: the most elements of one message of zkhip_poseidon_hash_many_device
+ZKHIP_POSEIDON_SUBTREE = 256    # include/zkhip.h: elements of a level one workgroup of zkhip_poseidon_merkle_device folds
 
 # every symbol include/zkhip.h declares (tests check the export list against the header)
 _SIGS = {
@@ -141,6 +143,13 @@ _SIGS = {
     "zkhip_transcript_read_points_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zkhip_transcript_read_points": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "zkhip_transcript_proof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "zkhip_transcript_new_poseidon": (C.c_void_p, [C.c_int]),
+    "zkhip_transcript_new_poseidon_reader": (C.c_void_p, [C.c_char_p, C.c_size_t, C.c_int]),
+    "zkhip_poseidon_permute": (C.c_int, [C.c_void_p, C.c_size_t]),
+    "zkhip_poseidon_hash": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "zkhip_poseidon_constants": (C.c_int, [C.c_void_p]),
+    "zkhip_poseidon_hash_many_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "zkhip_poseidon_merkle_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zkhip_test_reduce512": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zkhip_test_transcript_chunk": (C.c_uint32, [C.c_size_t]),
     "zkhip_profile_enable": (C.c_int, [C.c_int]),

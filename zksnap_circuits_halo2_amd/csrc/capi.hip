@@ -29,6 +29,7 @@
 #include <vector>
 #include "zkhip_internal.hpp"
 #include "blake2b.hpp"
+#include "poseidon.hpp"
 #include "../../include/zkhip.hpp"   // host-side 4 x 64 Montgomery arithmetic for domain constants (zkhip::halo2::detail)
 
 namespace zkhip {
@@ -226,6 +227,8 @@ struct device_ctx {
   uint64_t use_clock = 0;
   dev_buf fixed_table;                 // multiples of the generator for zkhip_g1_fixed_base_mul_device (primary only)
   bool fixed_table_ready = false;
+  dev_buf poseidon_table;              // poseidon.hpp's table in the kernels' limbs (primary only), uploaded by the first Poseidon `_device` call
+  bool poseidon_table_ready = false;
   dev_buf gather;                      // primary: the shards' 96-byte partials, one 96-byte slot per shard
   std::vector<hipEvent_t> shard_events;
   hipStream_t side = nullptr;          // primary: second stream of a batch of large MSMs (high priority: never the caller's hardware queue)
@@ -447,6 +450,7 @@ static void destroy_device_ctx(device_ctx* d) {
   if (d->q_done) (void)hipEventDestroy(d->q_done);
   d->q_ext.release(); d->q_win.release(); d->q_out.release();
   d->fixed_table.release();
+  d->poseidon_table.release();
   d->gather.release();
   delete d;
 }
@@ -3099,10 +3103,96 @@ int zkhip_test_fq12_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* o
 
 }  // extern "C"
 
-// ---- transcript (include/zkhip.h, "transcript"): Blake2bWrite / Blake2bRead with Challenge255 ------------------------------------------------
+// ---- Poseidon (include/zkhip.h, "Poseidon") ------------------------------------------------------------------------------------------------
+namespace zkhip {
+// the kernels' table on the primary device (g_mu held): uploaded once, on `s`, and waited for -- the source is host memory of this call
+static int poseidon_device_table(hipStream_t s, const uint32_t** d_tab) {
+  device_ctx& P = primary();
+  if (!P.poseidon_table_ready) {
+    const poseidon_tables& T = poseidon_tab();
+    int rc;
+    if ((rc = P.poseidon_table.reserve(sizeof(T.dev))) != ZKHIP_OK) return rc;
+    HIPCHK(hipMemcpyAsync(P.poseidon_table.p, T.dev, sizeof(T.dev), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    P.poseidon_table_ready = true;
+  }
+  *d_tab = (const uint32_t*)P.poseidon_table.p;
+  return ZKHIP_OK;
+}
+}  // namespace zkhip
+
+extern "C" {
+
+int zkhip_poseidon_permute(uint64_t* states, size_t n) {
+  if (n && !states) { set_error("poseidon_permute: null pointer"); return ZKHIP_EINVAL; }
+  for (size_t i = 0; i < n; i++) {
+    halo2::Fr st[3];
+    memcpy(st, states + i * 12, 96);
+    poseidon_host_permute(st);
+    memcpy(states + i * 12, st, 96);
+  }
+  return ZKHIP_OK;
+}
+
+int zkhip_poseidon_hash(const uint64_t* fr, size_t n, uint64_t out[4]) {
+  if (!out || (n && !fr)) { set_error("poseidon_hash: null pointer"); return ZKHIP_EINVAL; }
+  if (n > 0xffffffffu) { set_error("poseidon_hash: more than 2^32 - 1 elements"); return ZKHIP_EINVAL; }
+  const halo2::Fr h = poseidon_host_hash((const halo2::Fr*)fr, n);
+  memcpy(out, h.l, 32);
+  return ZKHIP_OK;
+}
+
+int zkhip_poseidon_constants(uint64_t out[204 * 4]) {
+  if (!out) { set_error("poseidon_constants: null pointer"); return ZKHIP_EINVAL; }
+  static_assert(POSEIDON_TAB_INIT == 204, "the header's count");
+  memcpy(out, poseidon_tab().canon, (size_t)POSEIDON_TAB_INIT * 32);
+  return ZKHIP_OK;
+}
+
+int zkhip_poseidon_hash_many_device(const void* d_in, size_t n, uint32_t width, void* d_out, void* stream) {
+  ZK_API_RANGE();
+  if (width < 1 || width > ZKHIP_POSEIDON_MAX_WIDTH) { set_error("poseidon_hash_many: width %u is not in 1..%d", width, ZKHIP_POSEIDON_MAX_WIDTH); return ZKHIP_EINVAL; }
+  if (n && (!d_in || !d_out)) { set_error("poseidon_hash_many: null pointer"); return ZKHIP_EINVAL; }
+  if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) { set_error("poseidon_hash_many: d_in and d_out must be 16-byte aligned"); return ZKHIP_EINVAL; }
+  if (n > ((size_t)1 << 30)) { set_error("poseidon_hash_many: more than 2^30 messages in one call"); return ZKHIP_EINVAL; }
+  if (n == 0) return ZKHIP_OK;
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  const uint32_t* d_tab = nullptr;
+  if ((rc = poseidon_device_table(s, &d_tab)) != ZKHIP_OK) return rc;
+  return poseidon_hash_many_device((const uint32_t*)d_in, n, width, (uint32_t*)d_out, d_tab, s);
+}
+
+int zkhip_poseidon_merkle_device(const void* d_leaves, size_t n_leaves, void* d_nodes, void* stream) {
+  ZK_API_RANGE();
+  if (n_leaves == 0 || (n_leaves & (n_leaves - 1)) || n_leaves > ((size_t)1 << 30)) {
+    set_error("poseidon_merkle: %zu leaves: not a power of two in 1..2^30", n_leaves);
+    return ZKHIP_EINVAL;
+  }
+  if (!d_leaves || (n_leaves > 1 && !d_nodes)) { set_error("poseidon_merkle: null pointer"); return ZKHIP_EINVAL; }
+  if (((uintptr_t)d_leaves | (uintptr_t)d_nodes) & 15) { set_error("poseidon_merkle: d_leaves and d_nodes must be 16-byte aligned"); return ZKHIP_EINVAL; }
+  if (n_leaves == 1) return ZKHIP_OK;
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  const uint32_t* d_tab = nullptr;
+  if ((rc = poseidon_device_table(s, &d_tab)) != ZKHIP_OK) return rc;
+  if ((rc = sc->small.reserve(poseidon_merkle_workspace(n_leaves))) != ZKHIP_OK) return rc;
+  return poseidon_merkle_device((const uint32_t*)d_leaves, n_leaves, (uint32_t*)d_nodes, d_tab, sc->small.p, sc->small.cap, s);
+}
+
+}  // extern "C"
+
+// ---- transcript (include/zkhip.h, "transcript"): Blake2bWrite / Blake2bRead with Challenge255, or the Poseidon transcript ------------------------
 // The object is host state: the hash, the proof bytes, a cursor, and a pinned staging block for the `_device` calls.  The calls marked "host" in
 // the header never reach ensure_init(): their field arithmetic is zkhip::halo2::detail's 4 x 64 Montgomery product.
 struct zkhip_transcript {
+  bool poseidon = false;               // which hash absorbs: `st` (Blake2b) or `sponge`; everything else is common to both
+  zkhip::poseidon_sponge* sponge = nullptr;
   zkhip::blake2b st;
   std::vector<uint8_t> proof;
   size_t cursor = 0;
@@ -3143,13 +3233,22 @@ static void fr_reduce512(const uint8_t in[64], uint64_t out[4]) {
   memcpy(out, sum.l, 32);
 }
 
+// Poseidon: a canonical 32-byte integer below 2 r (a scalar, or an Fq coordinate: q < 2 r) into the sponge's buffer, mod r
+static void tr_sponge_absorb(zkhip_transcript* t, const uint8_t repr[32]) {
+  uint64_t v[4];
+  memcpy(v, repr, 32);
+  if (hd::geq(v, hd::R_MOD)) hd::sub(v, v, hd::R_MOD);
+  t->sponge->update(hd::from_raw(v));
+}
 static void tr_absorb_scalar(zkhip_transcript* t, const uint8_t repr[32]) {
+  if (t->poseidon) { tr_sponge_absorb(t, repr); return; }
   uint8_t b[33];
   b[0] = 0x02;
   memcpy(b + 1, repr, 32);
   t->st.update(b, 33);
 }
 static void tr_absorb_point(zkhip_transcript* t, const uint8_t xy[64]) {
+  if (t->poseidon) { tr_sponge_absorb(t, xy); tr_sponge_absorb(t, xy + 32); return; }
   uint8_t b[65];
   b[0] = 0x01;
   memcpy(b + 1, xy, 64);
@@ -3306,8 +3405,28 @@ zkhip_transcript* zkhip_transcript_new_reader(const uint8_t* proof, size_t len, 
   return t;
 }
 
+zkhip_transcript* zkhip_transcript_new_poseidon(int flag_layout) {
+  if (flag_layout < 0 || flag_layout > 1) { set_error("transcript_new_poseidon: flag_layout %d", flag_layout); return nullptr; }
+  zkhip_transcript* t = new (std::nothrow) zkhip_transcript();
+  if (t) t->sponge = new (std::nothrow) zkhip::poseidon_sponge();
+  if (!t || !t->sponge) { delete t; set_error("transcript_new_poseidon: out of memory"); return nullptr; }
+  t->layout = flag_layout;
+  t->poseidon = true;
+  return t;
+}
+
+zkhip_transcript* zkhip_transcript_new_poseidon_reader(const uint8_t* proof, size_t len, int flag_layout) {
+  if (len && !proof) { set_error("transcript_new_poseidon_reader: null pointer"); return nullptr; }
+  zkhip_transcript* t = zkhip_transcript_new_poseidon(flag_layout);
+  if (!t) return nullptr;
+  t->reader = true;
+  t->proof.assign(proof, proof + len);
+  return t;
+}
+
 void zkhip_transcript_free(zkhip_transcript* t) {
   if (!t) return;
+  delete t->sponge;
   if (t->pinned) { (void)hipHostFree(t->pinned); (void)hipGetLastError(); }
   delete t;
 }
@@ -3337,6 +3456,11 @@ int zkhip_transcript_common_points(zkhip_transcript* t, const uint64_t* affine_m
 
 int zkhip_transcript_squeeze(zkhip_transcript* t, uint64_t out_fr_mont[4]) {
   if (!t || !out_fr_mont) { set_error("transcript_squeeze: null pointer"); return ZKHIP_EINVAL; }
+  if (t->poseidon) {
+    const halo2::Fr c = t->sponge->squeeze();
+    memcpy(out_fr_mont, c.l, 32);
+    return ZKHIP_OK;
+  }
   const uint8_t prefix = 0x00;
   t->st.update(&prefix, 1);
   uint8_t digest[64];

@@ -247,6 +247,11 @@ int transcript_scalars_device(const uint32_t* d_in, size_t n, uint32_t* d_out, h
 // n affine points -> n x 64 bytes (canonical x | y); atomicMin of the indices of (0, 0) points into *d_first_bad
 int transcript_affine_device(const uint32_t* d_points, size_t n, uint32_t* d_out, unsigned long long* d_first_bad, hipStream_t stream);
 
+// poseidon.hip (include/zkhip.h, "Poseidon").  d_tab: poseidon.hpp's table in the kernels' limbs (POSEIDON_TAB_LEN x 9 words)
+int poseidon_hash_many_device(const uint32_t* d_in, size_t n, uint32_t width, uint32_t* d_out, const uint32_t* d_tab, hipStream_t stream);
+size_t poseidon_merkle_workspace(size_t n);
+int poseidon_merkle_device(const uint32_t* d_leaves, size_t n, uint32_t* d_nodes, const uint32_t* d_tab, void* ws, size_t ws_bytes, hipStream_t stream);
+
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);
 int g1_check_points_device(const uint32_t* d_points, size_t n, unsigned long long* d_first_bad, hipStream_t stream);

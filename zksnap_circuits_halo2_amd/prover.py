@@ -23,7 +23,7 @@ import torch
 
 from . import _lib, evaluation as E, fields as F, keygen as KG, multiopen as MO
 from .domain import EvaluationDomain
-from .transcript import Blake2bRead, Blake2bWrite, vk_transcript_repr
+from .transcript import transcript_classes, vk_transcript_repr
 
 R = F.R_MOD
 BLIND = 5
@@ -141,13 +141,14 @@ class SeededChallenges:
 
 
 class TranscriptChallenges:
-    """Fiat-Shamir: a Blake2b transcript opened with the verifying key; each challenge is squeezed after the commitments handed in (Jacobian
-    points on the device) have been written.  `finish()` returns the proof bytes."""
+    """Fiat-Shamir: a transcript opened with the verifying key; each challenge is squeezed after the commitments handed in (Jacobian
+    points on the device) have been written.  `finish()` returns the proof bytes.  hash: "blake2b" (the benches' `gen_proof`) or "poseidon"
+    (`gen_snark`'s `PoseidonTranscript`): the same calls and the same proof layout, other challenges."""
 
-    def __init__(self, vk):
+    def __init__(self, vk, hash="blake2b"):
         vk_io = io.BytesIO()
         vk.write(vk_io, KG.RAW_BYTES)
-        self.transcript = Blake2bWrite()
+        self.transcript = transcript_classes(hash)[0]()
         self.transcript.common_scalar(vk_transcript_repr(vk_io.getvalue()))      # a stand-in for halo2's vk.transcript_repr (transcript.py)
 
     def _after(self, points):
@@ -207,12 +208,23 @@ def _key_commitments(vk):
     return com
 
 
-def verify_transcript_proof(params, vk, k, proof, shape, plan):
+MULTIOPEN = {"shplonk": (MO.ProverSHPLONK, MO.VerifierSHPLONK), "gwc": (MO.ProverGWC, MO.VerifierGWC)}
+
+
+def multiopen_classes(multiopen):
+    """(prover, verifier) of a multi-open's name; ValueError on any other name"""
+    if multiopen not in MULTIOPEN:
+        raise ValueError(f"multiopen {multiopen!r}: 'shplonk' or 'gwc'")
+    return MULTIOPEN[multiopen]
+
+
+def verify_transcript_proof(params, vk, k, proof, shape, plan, hash="blake2b", multiopen="shplonk"):
     """The verifier of a proof written through TranscriptChallenges: it is handed the parameters, the verifying key, the proof BYTES, and what a
     verifier knows of the circuit -- `shape` (how many advice columns, lookups, permutation sets, whether a random polynomial is committed) and
     `plan` (the opened (kind, index, rotation) triples, in the order their evaluations were written).  It replays the prover's order with reads
     -- commitments land on the device as affine points, evaluations as integers --, derives every challenge itself and ends in
-    `VerifierSHPLONK.verify_proof_transcript`.  The verifier's scalar half (the gates' identity at x) is out of scope.
+    `VerifierSHPLONK.verify_proof_transcript` (multiopen="gwc": `VerifierGWC.verify_proof_transcript`); hash: the transcript the proof was
+    written under ("blake2b" or "poseidon").  The verifier's scalar half (the gates' identity at x) is out of scope.
     Bytes that do not decode reject."""
     def xyz(points):                                       # device affine points -> Jacobian limbs with z = 1 for the host-side accumulation
         return [MO._affine_to_xyz(p_) for p_ in points.cpu().numpy().view(np.uint64).reshape(-1, 8)]
@@ -220,7 +232,8 @@ def verify_transcript_proof(params, vk, k, proof, shape, plan):
     vk_io = io.BytesIO()
     vk.write(vk_io, KG.RAW_BYTES)
     n_adv, n_lk, n_sets = shape["advice"], shape["lookups"], shape["permutation_sets"]
-    with Blake2bRead(bytes(proof)) as r:
+    verifier = multiopen_classes(multiopen)[1]
+    with transcript_classes(hash)[1](bytes(proof)) as r:
         try:
             r.common_scalar(vk_transcript_repr(vk_io.getvalue()))
             com = {("advice", i): c_ for i, c_ in enumerate(xyz(r.read_points(n_adv)))}
@@ -243,7 +256,7 @@ def verify_transcript_proof(params, vk, k, proof, shape, plan):
                 return False
             raise
         com.update(_key_commitments(vk))
-        return MO.VerifierSHPLONK(params).verify_proof_transcript(verifier_queries(plan, com, evals, x, k), r)
+        return verifier(params).verify_proof_transcript(verifier_queries(plan, com, evals, x, k), r)
 
 
 # ---- the witness -------------------------------------------------------------------------------------------------------------------------------
@@ -328,8 +341,9 @@ class Prover:
     before the key exists.  Afterwards the object holds what the proof consists of (`commitments`, `plan`, `queries`, `multiopen_proof`, with a
     transcript `proof`) and what the prover's own invariants are read from (`*_closes`, `h_coeff`, `a0_coeff_commit`, `multiopen_ok`)."""
 
-    def __init__(self, params, witness, blinding, batched=None, lap=None):
+    def __init__(self, params, witness, blinding, batched=None, lap=None, multiopen="shplonk"):
         self.params, self.w, self.blinding = params, witness, blinding
+        self.multiopen_name, self.multiopen_prover = multiopen, multiopen_classes(multiopen)[0]
         self.cs, self.qc = witness.cs, E.quotient_columns(witness.cs)
         self.k, self.n, self.u = witness.k, 1 << witness.k, (1 << witness.k) - (BLIND + 1)
         self.dom = EvaluationDomain(4, self.k)
@@ -380,6 +394,8 @@ class Prover:
     def prove(self, dpk, challenges, lookups_one_call=True, sharded_quotient=False, sharded_key=False):
         NL, with_transcript = self.w.lookups, challenges.transcript is not None
         check_options(with_transcript, NL, lookups_one_call, sharded_quotient, sharded_key)
+        if self.multiopen_name != "shplonk" and not with_transcript:
+            raise ValueError("multiopen=\"gwc\" writes its witnesses to a transcript: the seeded flow opens with SHPLONK")
         self.dpk, self.ch, self.sharded_quotient, self.sharded_key = dpk, challenges, sharded_quotient, sharded_key
         # a single lookup over 2^20 rows or more stays with the loop
         self.one_call = bool(lookups_one_call and NL and (with_transcript or not (NL == 1 and self.k >= 20)))
@@ -668,14 +684,15 @@ class Prover:
             q_.eval = e_                                        # the multi-open's R_ij need them as integers
 
     def multiopen(self):
-        """SHPLONK (the benches' `gen_proof` path) over the plan's queries; with a transcript the proof bytes are complete after it"""
+        """SHPLONK (the benches' `gen_proof` path; `gen_snark` opens with GWC: multiopen="gwc") over the plan's queries; with a transcript the
+        proof bytes are complete after it"""
         self.multiopen_ok, self.multiopen_proof = True, None
-        mo_prover = MO.ProverSHPLONK(self.k, self.commit_ptr)
+        mo_prover = self.multiopen_prover(self.k, self.commit_ptr)
         try:
             self.multiopen_proof = self.ch.multiopen(mo_prover, self.queries)
         except ArithmeticError:
             self.multiopen_ok = False
-        self.lap("multiopen_shplonk")
+        self.lap("multiopen_" + self.multiopen_name)
         mo_prover.close()
         self.proof = self.ch.finish()
 
@@ -691,6 +708,6 @@ class Prover:
         return verifier_queries(self.plan, com, evals, self.x, self.k)
 
 
-def create_proof(params, dpk, witness, challenges, blinding, batched=None, lap=None, **how):
+def create_proof(params, dpk, witness, challenges, blinding, batched=None, lap=None, multiopen="shplonk", **how):
     """one proof, start to end, with no synchronisation added for timing when `lap` is None; `how`: lookups_one_call, sharded_quotient, sharded_key (Prover.prove).  Returns the Prover."""
-    return Prover(params, witness, blinding, batched, lap).prove(dpk, challenges, **how)
+    return Prover(params, witness, blinding, batched, lap, multiopen).prove(dpk, challenges, **how)

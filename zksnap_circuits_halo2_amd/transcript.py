@@ -77,11 +77,8 @@ class _Transcript:
         return buf.raw[:n.value]
 
 
-class Blake2bWrite(_Transcript):
-    """`Blake2bWrite::<_, G1Affine, Challenge255<_>>::init(vec![])`; `finalize()` returns the proof"""
-
-    def __init__(self, flag_layout: int = 0):
-        super().__init__(_lib.load().zkhip_transcript_new(flag_layout))
+class _Write(_Transcript):
+    """the writing calls: the library dispatches on the object's hash, the proof bytes are the same under either"""
 
     def write_points(self, points, stream=None) -> None:
         """Jacobian commitments, 12 limbs each: a torch tensor on the device (one launch, one copy, one wait on `stream`) or host limbs"""
@@ -107,13 +104,7 @@ class Blake2bWrite(_Transcript):
         return self.proof()
 
 
-class Blake2bRead(_Transcript):
-    """`Blake2bRead::<_, G1Affine, Challenge255<_>>::init(proof)`"""
-
-    def __init__(self, proof: bytes, flag_layout: int = 0):
-        proof = bytes(proof)
-        super().__init__(_lib.load().zkhip_transcript_new_reader(proof, len(proof), flag_layout))
-
+class _Read(_Transcript):
     def read_points(self, n: int, device: bool = True, stream=None):
         """n points -> affine Montgomery limbs: an (n, 8) int64 torch tensor on the device, or with device=False an (n, 8) uint64 array.  A bad
         encoding raises ZkhipError (ZKHIP_EINVAL) and leaves the transcript where it was."""
@@ -134,6 +125,46 @@ class Blake2bRead(_Transcript):
 
     def read_scalar(self) -> int:
         return self.read_scalars(1)[0]
+
+
+class Blake2bWrite(_Write):
+    """`Blake2bWrite::<_, G1Affine, Challenge255<_>>::init(vec![])`; `finalize()` returns the proof"""
+
+    def __init__(self, flag_layout: int = 0):
+        super().__init__(_lib.load().zkhip_transcript_new(flag_layout))
+
+
+class Blake2bRead(_Read):
+    """`Blake2bRead::<_, G1Affine, Challenge255<_>>::init(proof)`"""
+
+    def __init__(self, proof: bytes, flag_layout: int = 0):
+        proof = bytes(proof)
+        super().__init__(_lib.load().zkhip_transcript_new_reader(proof, len(proof), flag_layout))
+
+
+class PoseidonWrite(_Write):
+    """snark-verifier's `PoseidonTranscript::<G1Affine, NativeLoader, _>::new(vec![])`, the transcript of the reference's `gen_snark`
+    (include/zkhip.h, "Poseidon"): the same calls and the same proof bytes as `Blake2bWrite`, other challenges"""
+
+    def __init__(self, flag_layout: int = 0):
+        super().__init__(_lib.load().zkhip_transcript_new_poseidon(flag_layout))
+
+
+class PoseidonRead(_Read):
+    def __init__(self, proof: bytes, flag_layout: int = 0):
+        proof = bytes(proof)
+        super().__init__(_lib.load().zkhip_transcript_new_poseidon_reader(proof, len(proof), flag_layout))
+
+
+WRITERS = {"blake2b": Blake2bWrite, "poseidon": PoseidonWrite}
+READERS = {"blake2b": Blake2bRead, "poseidon": PoseidonRead}
+
+
+def transcript_classes(hash: str):
+    """(writer, reader) of a hash name; ValueError on any other name"""
+    if hash not in WRITERS:
+        raise ValueError(f"transcript hash {hash!r}: 'blake2b' or 'poseidon'")
+    return WRITERS[hash], READERS[hash]
 
 
 

@@ -651,6 +651,68 @@ int zkhip_poseidon_hash_many_device(const void *d_in, size_t n, uint32_t width, 
  * ZKHIP_EINVAL, nothing enqueued: n_leaves not a power of two, 0, or above 2^30; a null or misaligned pointer.  d_nodes must not overlap d_leaves. */
 int zkhip_poseidon_merkle_device(const void *d_leaves, size_t n_leaves, void *d_nodes, void *stream);
 
+/* ---- indexed Merkle tree: the nullifier tree of the state-transition circuit, a BATCH of insertions in one device call ----
+ * [DEP indexed_merkle_tree_halo2 `IndexedMerkleTree` / `IMTLeaf`; the reference: `generate_state_transition_circuit_inputs` and `update_idx_leaf`,
+ * /root/reference/aggregator/src/utils.rs:101-197, which scans for the low leaf and rebuilds the whole tree twice per vote; the witness is the
+ * argument list of `IndexedMerkleTreeInput::new`, aggregator/src/state_transition.rs:44-70.]  The hash is the Poseidon of the section above.
+ * The FRAMING below is pinned only as these lines word it: the `indexed_merkle_tree_halo2` crate is not vendored with the reference and could
+ * not be built, so parity with it is unpinned, like the Poseidon framing.
+ * THE DEFINITION (normative):
+ *   tree        2^depth leaves.  A leaf has a preimage (val, next_val, next_idx) of three Fr; its value in the tree is hash(val, next_val,
+ *               next_idx), the width-3 sponge (two permutations); an inner node is hash(left, right).
+ *   empty tree  every preimage is (0, 0, 0).  Leaf 0 is the permanent head of the sorted list; the first free index is 1 (the reference
+ *               inserts round r at index r, rounds counted from 1).  `used` counts the head: it is the first free index.
+ *   insert v    at the first free index j, values compared as canonical integers: the low leaf l is the used leaf with the greatest val < v
+ *               (it exists, and next_val[l] == 0 or next_val[l] > v).  The new leaf becomes (v, next_val[l], next_idx[l]); the low leaf becomes
+ *               (val[l], v, j), next_idx held as the field element j.  (`update_idx_leaf`, whose special case for the first insertion is
+ *               this rule.)
+ *   refusals    v == 0; v equal to a val already in the tree; v equal to an earlier value of the same batch; a value that finds no free
+ *               leaf; four words that are not a reduced Montgomery element.  The call returns ZKHIP_EINVAL, *first_bad = the index of the
+ *               first such value, nothing is enqueued and the tree is unchanged.  (*first_bad = (size_t)-1 on every other outcome.)
+ *   witness of insertion i of a batch:
+ *     old_root = roots[i], the root before the insertion; new_root = roots[i + 1], the root after both leaf updates;
+ *     low_leaf = the low leaf's preimage BEFORE the insertion, low index = l;
+ *     low_leaf_proof = the siblings of the low leaf's path in the tree before the insertion, from the leaf level up;
+ *     new_leaf = the new leaf's preimage, new_leaf_index = used-before-the-batch + i;
+ *     new_leaf_proof = the siblings of the new leaf's path AFTER the low leaf's update (and before its own);
+ *     is_new_leaf_largest = (new_leaf.next_val == 0); the proof helpers are 1 where the path node is a left child (bit L of the index clear).
+ * How it runs: the host links the batch over an ordered index of the used values (no scan); the device computes all 2 n_new leaf updates level
+ * by level, one lane per update and depth + 2 launches per batch (csrc/imt.hip).  One insertion alone is better served by
+ * the host hash: see DESIGN.md section 9 for the batch size from which the device wins.  Not built: removal of leaves, trees sharded over
+ * devices.
+ * The object lives on the primary device and owns the leaves, inner nodes and preimages in device memory and the host index.  Calls on one
+ * object come from one thread at a time and are ordered by the caller on ONE stream; the host index advances at call time.  Destroy it before
+ * zkhip_shutdown. */
+#define ZKHIP_IMT_MAX_DEPTH 24        /* 160 bytes of device memory per leaf: 2.5 GiB at the cap */
+typedef struct zkhip_imt zkhip_imt;
+/* where zkhip_imt_insert leaves the witnesses: device pointers the caller owns, 16-byte aligned (d_low_indices: 4-byte), 4 words per element */
+typedef struct zkhip_imt_witness {
+  void *d_roots;        /* (n_new + 1) x 4 words: entry i the old_root of insertion i, entry i + 1 its new_root */
+  void *d_low_leaves;   /* n_new x 12 words */
+  void *d_new_leaves;   /* n_new x 12 words */
+  void *d_low_indices;  /* n_new uint32 */
+  void *d_low_proofs;   /* n_new x depth x 4 words */
+  void *d_new_proofs;   /* n_new x depth x 4 words */
+} zkhip_imt_witness;
+int zkhip_imt_create(uint32_t depth, zkhip_imt **t);             /* 1 <= depth <= ZKHIP_IMT_MAX_DEPTH; the empty tree from depth + 1 host hashes and fills; waits */
+int zkhip_imt_destroy(zkhip_imt *t);                              /* NULL is ZKHIP_OK */
+/* values: n_new x 4 Montgomery words on the HOST, in insertion order (the linking is host work).  out may be NULL: the call only updates the
+ * tree.  No host wait after the uploads.  n_new == 0 is ZKHIP_OK and does nothing.  A null or misaligned pointer is ZKHIP_EINVAL, nothing enqueued. */
+int zkhip_imt_insert(zkhip_imt *t, const uint64_t *values, size_t n_new, const zkhip_imt_witness *out, size_t *first_bad, void *stream);
+/* host results, read behind the stream of the object's last insert, which they wait for: the root; leaf `index`'s preimage; the depth siblings
+ * of its path from the leaf level up.  index >= 2^depth is ZKHIP_EINVAL. */
+int zkhip_imt_root(zkhip_imt *t, uint64_t out[4]);
+int zkhip_imt_leaf(zkhip_imt *t, uint32_t index, uint64_t out[12]);
+int zkhip_imt_proof(zkhip_imt *t, uint32_t index, uint64_t *out /* depth x 4 words */);
+int zkhip_imt_size(const zkhip_imt *t, uint32_t *depth, uint32_t *used);                                /* host; either pointer may be NULL */
+/* device-to-device copies on `stream`, no host wait: 2^depth leaves, the 2^depth - 1 inner nodes in zkhip_poseidon_merkle_device's order,
+ * 2^depth preimages of 12 words */
+int zkhip_imt_export_device(zkhip_imt *t, void *d_leaves, void *d_nodes, void *d_preimages, void *stream);
+/* The linking alone (host; touches no GPU and works in a process that never initialises HIP; the code the object runs).  used_vals: the vals of
+ * leaves 0 .. n_used - 1 in index order, leaf 0 the head with val 0 (n_used == 0 stands for the empty tree).  low_index_out[i] = the low leaf of
+ * new value i, inserted at leaf max(n_used, 1) + i.  Refusals as above, except that any number of leaves is free. */
+int zkhip_imt_link(const uint64_t *used_vals, size_t n_used, const uint64_t *new_vals, size_t n_new, uint32_t *low_index_out, size_t *first_bad);
+
 /* ---- parity hooks for the field / curve layer (rows a1/a2 of SURVEY.md section 8) ------------------ */
 /* field: 0 = Fq, 1 = Fr.  op: 0 mul, 1 add, 2 sub, 3 square (b ignored).  Elementwise on n elements. */
 int zkhip_test_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);

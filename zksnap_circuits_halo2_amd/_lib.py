@@ -11,6 +11,7 @@ ZKHIP_MAX_ROOTS = 8          # include/zkhip.h: the most roots of one zkhip_fr_d
 ZKHIP_MAX_PAIRS = 64         # include/zkhip.h: the most pairs of one zkhip_pairing_check call
 ZKHIP_POSEIDON_MAX_WIDTH = 16   # include/zkhip.h: the most elements of one message of zkhip_poseidon_hash_many_device
 ZKHIP_POSEIDON_SUBTREE = 256    # include/zkhip.h: elements of a level one workgroup of zkhip_poseidon_merkle_device folds
+ZKHIP_IMT_MAX_DEPTH = 24        # include/zkhip.h: the deepest indexed Merkle tree zkhip_imt_create makes
 
 # every symbol include/zkhip.h declares (tests check the export list against the header)
 _SIGS = {
@@ -150,6 +151,15 @@ _SIGS = {
     "zkhip_poseidon_constants": (C.c_int, [C.c_void_p]),
     "zkhip_poseidon_hash_many_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "zkhip_poseidon_merkle_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zkhip_imt_create": (C.c_int, [C.c_uint32, C.POINTER(C.c_void_p)]),
+    "zkhip_imt_destroy": (C.c_int, [C.c_void_p]),
+    "zkhip_imt_insert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]),
+    "zkhip_imt_root": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "zkhip_imt_leaf": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "zkhip_imt_proof": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "zkhip_imt_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "zkhip_imt_export_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkhip_imt_link": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
     "zkhip_test_reduce512": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zkhip_test_transcript_chunk": (C.c_uint32, [C.c_size_t]),
     "zkhip_profile_enable": (C.c_int, [C.c_int]),
@@ -166,6 +176,11 @@ _SIGS = {
 
 class ProverQueryC(C.Structure):   # zkhip_prover_query (80 bytes)
     _fields_ = [("point", C.c_uint64 * 4), ("d_poly", C.c_void_p), ("eval", C.c_uint64 * 4), ("has_eval", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ImtWitness(C.Structure):      # zkhip_imt_witness: six device pointers
+    _fields_ = [("d_roots", C.c_void_p), ("d_low_leaves", C.c_void_p), ("d_new_leaves", C.c_void_p), ("d_low_indices", C.c_void_p),
+                ("d_low_proofs", C.c_void_p), ("d_new_proofs", C.c_void_p)]
 
 
 class CheckReport(C.Structure):     # zkhip_check_report (16 bytes)
@@ -192,6 +207,8 @@ _lib = None
 
 
 class ZkhipError(RuntimeError):
+    index = None                       # the first refused value of a batch, where a call reports one (the indexed Merkle tree's)
+
     def __init__(self, code: int, msg: str):
         super().__init__(f"libzkhip error {code}: {msg}")
         self.code = code

@@ -30,6 +30,7 @@
 #include "zkhip_internal.hpp"
 #include "blake2b.hpp"
 #include "poseidon.hpp"
+#include "imt.hpp"
 #include "../../include/zkhip.hpp"   // host-side 4 x 64 Montgomery arithmetic for domain constants (zkhip::halo2::detail)
 
 namespace zkhip {
@@ -3183,6 +3184,242 @@ int zkhip_poseidon_merkle_device(const void* d_leaves, size_t n_leaves, void* d_
   if ((rc = poseidon_device_table(s, &d_tab)) != ZKHIP_OK) return rc;
   if ((rc = sc->small.reserve(poseidon_merkle_workspace(n_leaves))) != ZKHIP_OK) return rc;
   return poseidon_merkle_device((const uint32_t*)d_leaves, n_leaves, (uint32_t*)d_nodes, d_tab, sc->small.p, sc->small.cap, s);
+}
+
+}  // extern "C"
+
+// ---- indexed Merkle tree (include/zkhip.h, "indexed Merkle tree") -----------------------------------------------------------------------------
+// The object owns the tree in device memory (primary device), the ordered index of the used values (imt.hpp, host), a grow-only workspace and
+// a pinned staging block for what a batch uploads; `staged` says when the last batch's uploads have left the block.
+struct zkhip_imt {
+  uint32_t depth = 0;
+  zkhip::imt_index index;
+  uint32_t *leaves = nullptr, *nodes = nullptr, *preimages = nullptr;
+  zkhip::dev_buf ws;
+  void* stage = nullptr;
+  size_t stage_cap = 0;
+  hipEvent_t staged = nullptr;
+  bool staged_live = false;
+  hipStream_t last = nullptr;          // the stream of the last insert: the read-backs run behind it
+  size_t n_leaves() const { return (size_t)1 << depth; }
+};
+
+namespace zkhip {
+static void imt_release(zkhip_imt* t) {
+  if (t->staged) { if (t->staged_live) (void)hipEventSynchronize(t->staged); (void)hipEventDestroy(t->staged); }
+  if (t->stage) (void)hipHostFree(t->stage);
+  t->ws.release();
+  if (t->leaves) (void)hipFree(t->leaves);
+  if (t->nodes) (void)hipFree(t->nodes);
+  if (t->preimages) (void)hipFree(t->preimages);
+  delete t;
+}
+static inline halo2::Fr imt_fr_of_index(uint32_t j) { return halo2::detail::from_u64(j); }
+}  // namespace zkhip
+
+extern "C" {
+
+int zkhip_imt_link(const uint64_t* used_vals, size_t n_used, const uint64_t* new_vals, size_t n_new, uint32_t* low_index_out, size_t* first_bad) {
+  if (first_bad) *first_bad = (size_t)-1;
+  if ((n_used && !used_vals) || (n_new && (!new_vals || !low_index_out))) { set_error("imt_link: null pointer"); return ZKHIP_EINVAL; }
+  if (n_used > 0xffffffffu || n_new > 0xffffffffu - (n_used ? n_used : 1)) { set_error("imt_link: more than 2^32 - 1 leaves"); return ZKHIP_EINVAL; }
+  if (n_used && (used_vals[0] | used_vals[1] | used_vals[2] | used_vals[3])) { set_error("imt_link: leaf 0 is the head: its value is 0"); return ZKHIP_EINVAL; }
+  imt_index index;
+  const char* why = nullptr;
+  size_t bad = 0;
+  if (n_used > 1 && !index.link(used_vals + 4, n_used - 1, (size_t)-1, nullptr, &bad, &why)) {
+    set_error("imt_link: used value %zu: %s", bad + 1, why);
+    return ZKHIP_EINVAL;
+  }
+  std::vector<imt_link> links(n_new);
+  if (!index.link(new_vals, n_new, (size_t)-1, links.data(), &bad, &why)) {
+    if (first_bad) *first_bad = bad;
+    set_error("imt_link: new value %zu: %s", bad, why);
+    return ZKHIP_EINVAL;
+  }
+  for (size_t i = 0; i < n_new; i++) low_index_out[i] = links[i].low;
+  return ZKHIP_OK;
+}
+
+int zkhip_imt_create(uint32_t depth, zkhip_imt** out) {
+  ZK_API_RANGE();
+  if (!out) { set_error("imt_create: null pointer"); return ZKHIP_EINVAL; }
+  *out = nullptr;
+  if (depth < 1 || depth > ZKHIP_IMT_MAX_DEPTH) { set_error("imt_create: depth %u is not in 1..%d", depth, ZKHIP_IMT_MAX_DEPTH); return ZKHIP_EINVAL; }
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  zkhip_imt* t = new (std::nothrow) zkhip_imt();
+  if (!t) { set_error("imt_create: out of memory"); return ZKHIP_ENOMEM; }
+  t->depth = depth;
+  const size_t n = t->n_leaves();
+  if (hipMalloc((void**)&t->leaves, n * 32) != hipSuccess || hipMalloc((void**)&t->nodes, (n - 1) * 32) != hipSuccess ||
+      hipMalloc((void**)&t->preimages, n * 96) != hipSuccess || hipEventCreateWithFlags(&t->staged, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    imt_release(t);
+    set_error("imt_create: no device memory for a tree of depth %u", depth);
+    return ZKHIP_ENOMEM;
+  }
+  // the empty tree: every level one repeated value, depth + 1 host hashes
+  const uint32_t* d_tab = nullptr;
+  rc = poseidon_device_table(nullptr, &d_tab);
+  halo2::Fr h = poseidon_host_hash(std::vector<halo2::Fr>(3, halo2::Fr{{0, 0, 0, 0}}).data(), 3);
+  if (rc == ZKHIP_OK && hipMemsetAsync(t->preimages, 0, n * 96, nullptr) != hipSuccess) { set_error("imt_create: memset failed"); rc = ZKHIP_EHIP; }
+  for (uint32_t L = 0; L <= depth && rc == ZKHIP_OK; L++) {
+    uint32_t w[8];
+    memcpy(w, h.l, 32);
+    rc = imt_fill_device(L == 0 ? t->leaves : t->nodes + (n - (n >> (L - 1))) * 8, n >> L, w, nullptr);
+    const halo2::Fr two[2] = {h, h};
+    h = poseidon_host_hash(two, 2);
+  }
+  if (rc == ZKHIP_OK && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("imt_create: the fills failed"); rc = ZKHIP_EHIP; }
+  if (rc != ZKHIP_OK) { imt_release(t); return rc; }
+  *out = t;
+  return ZKHIP_OK;
+}
+
+int zkhip_imt_destroy(zkhip_imt* t) {
+  ZK_API_RANGE();
+  if (!t) return ZKHIP_OK;
+  guard_t g(g_mu);
+  if (g_ctx.ready) (void)ensure_init();
+  imt_release(t);                      // hipFree waits for the device: nothing queued still reads the tree
+  return ZKHIP_OK;
+}
+
+int zkhip_imt_size(const zkhip_imt* t, uint32_t* depth, uint32_t* used) {
+  if (!t) { set_error("imt_size: null tree"); return ZKHIP_EINVAL; }
+  if (depth) *depth = t->depth;
+  if (used) *used = (uint32_t)t->index.used();
+  return ZKHIP_OK;
+}
+
+int zkhip_imt_insert(zkhip_imt* t, const uint64_t* values, size_t n_new, const zkhip_imt_witness* out, size_t* first_bad, void* stream) {
+  ZK_API_RANGE();
+  if (first_bad) *first_bad = (size_t)-1;
+  if (!t || (n_new && !values)) { set_error("imt_insert: null pointer"); return ZKHIP_EINVAL; }
+  if (out) {
+    if (n_new && (!out->d_roots || !out->d_low_leaves || !out->d_new_leaves || !out->d_low_indices || !out->d_low_proofs || !out->d_new_proofs)) {
+      set_error("imt_insert: a null pointer in the witness buffers");
+      return ZKHIP_EINVAL;
+    }
+    if ((((uintptr_t)out->d_roots | (uintptr_t)out->d_low_leaves | (uintptr_t)out->d_new_leaves | (uintptr_t)out->d_low_proofs | (uintptr_t)out->d_new_proofs) & 15) ||
+        ((uintptr_t)out->d_low_indices & 3)) {
+      set_error("imt_insert: the witness buffers must be 16-byte aligned (d_low_indices: 4-byte)");
+      return ZKHIP_EINVAL;
+    }
+  }
+  if (n_new == 0) return ZKHIP_OK;
+  const size_t used0 = t->index.used(), n = t->n_leaves();
+  std::vector<imt_link> links(n_new);
+  const char* why = nullptr;
+  size_t bad = 0;
+  if (!t->index.link(values, n_new, n, links.data(), &bad, &why)) {
+    if (first_bad) *first_bad = bad;
+    set_error("imt_insert: value %zu: %s", bad, why);
+    return ZKHIP_EINVAL;
+  }
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  hipStream_t s = caller_stream(stream);
+  const uint32_t* d_tab = nullptr;
+  if (rc == ZKHIP_OK) rc = poseidon_device_table(s, &d_tab);
+  const size_t n_ev = 2 * n_new, up_bytes = n_ev * (8 + 96), stage_bytes = up_bytes + n_new * (96 + 4);
+  if (rc == ZKHIP_OK) rc = t->ws.reserve(imt_workspace_bytes(n_new));
+  if (rc == ZKHIP_OK && t->staged_live && hipEventSynchronize(t->staged) != hipSuccess) { set_error("imt_insert: the last batch's uploads failed"); rc = ZKHIP_EHIP; }
+  if (rc == ZKHIP_OK && stage_bytes > t->stage_cap) {
+    if (t->stage) (void)hipHostFree(t->stage);
+    t->stage = nullptr; t->stage_cap = 0;
+    if (hipHostMalloc(&t->stage, stage_bytes + stage_bytes / 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); t->stage = nullptr; set_error("imt_insert: no pinned memory (%zu bytes)", stage_bytes); rc = ZKHIP_ENOMEM; }
+    else t->stage_cap = stage_bytes + stage_bytes / 8;
+  }
+  if (rc != ZKHIP_OK) { t->index.unlink(n_new); return rc; }
+  // the events: time 2 i the low leaf as insertion i leaves it, time 2 i + 1 the new leaf; keys ordered by (leaf, time) for level 0
+  uint64_t* keys = (uint64_t*)t->stage;
+  halo2::Fr* pre = (halo2::Fr*)((char*)t->stage + n_ev * 8);
+  halo2::Fr* low_before = (halo2::Fr*)((char*)t->stage + up_bytes);
+  uint32_t* low_idx = (uint32_t*)((char*)t->stage + up_bytes + n_new * 96);
+  for (size_t i = 0; i < n_new; i++) {
+    const imt_link& k = links[i];
+    const uint32_t j = (uint32_t)(used0 + i);
+    const halo2::Fr next_idx = imt_fr_of_index(k.next_idx);
+    halo2::Fr v;
+    memcpy(v.l, values + 4 * i, 32);
+    low_before[3 * i] = k.low_val; low_before[3 * i + 1] = k.next_val; low_before[3 * i + 2] = next_idx;
+    pre[6 * i] = k.low_val; pre[6 * i + 1] = v; pre[6 * i + 2] = imt_fr_of_index(j);
+    pre[6 * i + 3] = v; pre[6 * i + 4] = k.next_val; pre[6 * i + 5] = next_idx;
+    low_idx[i] = k.low;
+    keys[2 * i] = ((uint64_t)k.low << 32) | (uint64_t)(2 * i);
+    keys[2 * i + 1] = ((uint64_t)j << 32) | (uint64_t)(2 * i + 1);
+  }
+  std::sort(keys, keys + n_ev);
+  // from here on a failure leaves the stream and the tree in an unknown state (ZKHIP_EHIP): the index stays advanced, as the stream's work is
+  HIPCHK(hipMemcpyAsync(t->ws.p, t->stage, up_bytes, hipMemcpyHostToDevice, s));
+  if (out) {
+    HIPCHK(hipMemcpyAsync(out->d_low_leaves, low_before, n_new * 96, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(out->d_low_indices, low_idx, n_new * 4, hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(hipEventRecord(t->staged, s));
+  t->staged_live = true;
+  t->last = s;
+  return imt_insert_device(t->depth, n_new, t->ws.p, t->leaves, t->nodes, t->preimages, out ? (uint32_t*)out->d_roots : nullptr, out ? (uint32_t*)out->d_new_leaves : nullptr,
+                           out ? (uint32_t*)out->d_low_proofs : nullptr, out ? (uint32_t*)out->d_new_proofs : nullptr, d_tab, s);
+}
+
+// a handful of cells to the host behind the last insert: `cells` (pointer, bytes) pairs, copied in order into `out`
+static int imt_read_back(zkhip_imt* t, const std::vector<std::pair<const void*, size_t>>& cells, uint64_t* out) {
+  hipStream_t s;
+  {
+    guard_t g(g_mu);
+    int rc = ensure_init();
+    if (rc != ZKHIP_OK) return rc;
+    s = t->last;
+    char* at = (char*)out;
+    for (auto& c : cells) { HIPCHK(hipMemcpyAsync(at, c.first, c.second, hipMemcpyDeviceToHost, s)); at += c.second; }
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return ZKHIP_OK;
+}
+
+int zkhip_imt_root(zkhip_imt* t, uint64_t out[4]) {
+  ZK_API_RANGE();
+  if (!t || !out) { set_error("imt_root: null pointer"); return ZKHIP_EINVAL; }
+  return imt_read_back(t, {{t->nodes + (t->n_leaves() - 2) * 8, 32}}, out);
+}
+
+int zkhip_imt_leaf(zkhip_imt* t, uint32_t index, uint64_t out[12]) {
+  ZK_API_RANGE();
+  if (!t || !out) { set_error("imt_leaf: null pointer"); return ZKHIP_EINVAL; }
+  if (index >= t->n_leaves()) { set_error("imt_leaf: leaf %u of a tree of depth %u", index, t->depth); return ZKHIP_EINVAL; }
+  return imt_read_back(t, {{t->preimages + (size_t)index * 24, 96}}, out);
+}
+
+int zkhip_imt_proof(zkhip_imt* t, uint32_t index, uint64_t* out) {
+  ZK_API_RANGE();
+  if (!t || !out) { set_error("imt_proof: null pointer"); return ZKHIP_EINVAL; }
+  const size_t n = t->n_leaves();
+  if (index >= n) { set_error("imt_proof: leaf %u of a tree of depth %u", index, t->depth); return ZKHIP_EINVAL; }
+  std::vector<std::pair<const void*, size_t>> cells;
+  for (uint32_t L = 0; L < t->depth; L++) {
+    const uint32_t* level = L == 0 ? t->leaves : t->nodes + (n - (n >> (L - 1))) * 8;
+    cells.push_back({level + (size_t)((index >> L) ^ 1u) * 8, 32});
+  }
+  return imt_read_back(t, cells, out);
+}
+
+int zkhip_imt_export_device(zkhip_imt* t, void* d_leaves, void* d_nodes, void* d_preimages, void* stream) {
+  ZK_API_RANGE();
+  if (!t || !d_leaves || !d_nodes || !d_preimages) { set_error("imt_export: null pointer"); return ZKHIP_EINVAL; }
+  if (((uintptr_t)d_leaves | (uintptr_t)d_nodes | (uintptr_t)d_preimages) & 15) { set_error("imt_export: the buffers must be 16-byte aligned"); return ZKHIP_EINVAL; }
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  const size_t n = t->n_leaves();
+  HIPCHK(hipMemcpyAsync(d_leaves, t->leaves, n * 32, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_nodes, t->nodes, (n - 1) * 32, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_preimages, t->preimages, n * 96, hipMemcpyDeviceToDevice, s));
+  return ZKHIP_OK;
 }
 
 }  // extern "C"

@@ -252,6 +252,14 @@ int poseidon_hash_many_device(const uint32_t* d_in, size_t n, uint32_t width, ui
 size_t poseidon_merkle_workspace(size_t n);
 int poseidon_merkle_device(const uint32_t* d_leaves, size_t n, uint32_t* d_nodes, const uint32_t* d_tab, void* ws, size_t ws_bytes, hipStream_t stream);
 
+// imt.hip (include/zkhip.h, "indexed Merkle tree").  A batch of n_new insertions is 2 n_new events; the workspace holds, per event, the level-0
+// key (8 bytes, uploaded), the preimage the event leaves behind (96 bytes, by time, uploaded) and three sets of (key, value) used level by level.
+constexpr size_t IMT_WS_EVENT_BYTES = 8 + 96 + 32 + 2 * (8 + 32);          // the keys first, the preimages behind them: one upload
+size_t imt_workspace_bytes(size_t n_new);
+int imt_fill_device(uint32_t* d_dst, size_t n, const uint32_t value[8], hipStream_t stream);
+int imt_insert_device(uint32_t depth, size_t n_new, void* ws, uint32_t* d_leaves, uint32_t* d_nodes, uint32_t* d_preimages, uint32_t* out_roots,
+                      uint32_t* out_new_leaves, uint32_t* out_low_proofs, uint32_t* out_new_proofs, const uint32_t* d_tab, hipStream_t stream);
+
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);
 int g1_check_points_device(const uint32_t* d_points, size_t n, unsigned long long* d_first_bad, hipStream_t stream);

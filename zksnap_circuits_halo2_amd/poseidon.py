@@ -2,7 +2,9 @@
 (`MerkleTree`, /root/reference/voter/src/merkletree/native.rs) and of its `gen_snark` transcript (transcript.PoseidonWrite).
 
 `permute` and `hash` are the library's host form (Python integers in and out, no GPU touched); `hash_many_device` and `MerkleTree` run the
-kernels over device tensors of Montgomery limbs.  Nothing here computes: there is no CPU fallback for the device calls.
+kernels over device tensors of Montgomery limbs.  `IndexedMerkleTree` is the nullifier tree of the state-transition circuit
+(`generate_state_transition_circuit_inputs`, /root/reference/aggregator/src/utils.rs): a whole batch of insertions and their witnesses in one
+device call; `imt_link` is its host half alone.  Nothing here computes: there is no CPU fallback for the device calls.
 """
 from __future__ import annotations
 
@@ -119,3 +121,156 @@ class MerkleTree:
             acc = hash([acc, sibling]) if index % 2 == 0 else hash([sibling, acc])
             index //= 2
         return acc == int(root)
+
+
+IMT_MAX_DEPTH = _lib.ZKHIP_IMT_MAX_DEPTH
+
+
+def _ints(t) -> List[int]:
+    return fr_decode(np.ascontiguousarray(t.cpu().numpy()).view(np.uint64).reshape(-1, 4))
+
+
+def _helper(index: int, depth: int) -> List[int]:
+    return [1 - ((index >> L) & 1) for L in range(depth)]
+
+
+def imt_link(used_vals: Sequence[int], new_vals: Sequence[int]) -> List[int]:
+    """the low leaf of every new value (include/zkhip.h, zkhip_imt_link): host only, no GPU touched.  used_vals: the vals of leaves 0, 1, ..
+    in index order, leaf 0 the head with val 0 ([] stands for the empty tree).  ZkhipError with `.index` on a refusal."""
+    used, new = fr_encode([int(v) for v in used_vals]), fr_encode([int(v) for v in new_vals])
+    low = np.zeros(max(len(new), 1), dtype=np.uint32)
+    bad = _lib.C.c_size_t(0)
+    rc = _lib.load().zkhip_imt_link(used.ctypes.data if len(used) else None, len(used), new.ctypes.data if len(new) else None, len(new), low.ctypes.data,
+                                    _lib.C.byref(bad))
+    _check_index(rc, bad)
+    return [int(x) for x in low[:len(new)]]
+
+
+def _check_index(rc: int, bad) -> None:
+    if rc != 0:
+        err = _lib.ZkhipError(rc, _lib.load().zkhip_last_error().decode(errors="replace"))
+        err.index = None if bad.value == _lib.C.c_size_t(-1).value else int(bad.value)      # the first refused value of the batch
+        raise err
+
+
+class ImtBatch:
+    """the witnesses of one `insert_batch`, device tensors of Montgomery limbs: `roots` (n + 1, 4), `low_leaves` and `new_leaves` (n, 3, 4),
+    `low_indices` (n,) int32, `low_proofs` and `new_proofs` (n, depth, 4); insertion i went to leaf `first_index + i`"""
+
+    def __init__(self, n: int, depth: int, first_index: int, device):
+        import torch
+
+        def fr(*shape):
+            return torch.empty(shape + (4,), dtype=torch.int64, device=device)
+
+        self.n, self.depth, self.first_index = n, depth, first_index
+        self.roots, self.low_leaves, self.new_leaves = fr(n + 1), fr(n, 3), fr(n, 3)
+        self.low_indices = torch.empty((n,), dtype=torch.int32, device=device)
+        self.low_proofs, self.new_proofs = fr(n, depth), fr(n, depth)
+
+    def _c(self):
+        return _lib.ImtWitness(*(t.data_ptr() for t in (self.roots, self.low_leaves, self.new_leaves, self.low_indices, self.low_proofs, self.new_proofs)))
+
+    def round(self, i: int):
+        """the arguments of `IndexedMerkleTreeInput::new` for insertion i, Python integers: (old_root, low_leaf, low_leaf_proof,
+        low_leaf_proof_helper, new_root, new_leaf, new_leaf_index, new_leaf_proof, new_leaf_proof_helper, is_new_leaf_largest); a leaf is
+        (val, next_val, next_idx)"""
+        if not 0 <= i < self.n:
+            raise IndexError("round: no such insertion")
+        old_root, new_root = _ints(self.roots[i:i + 2])
+        low_leaf, new_leaf = tuple(_ints(self.low_leaves[i])), tuple(_ints(self.new_leaves[i]))
+        low, index = int(self.low_indices[i].item()), self.first_index + i
+        return (old_root, low_leaf, _ints(self.low_proofs[i]), _helper(low, self.depth), new_root, new_leaf, index, _ints(self.new_proofs[i]),
+                _helper(index, self.depth), 1 if new_leaf[1] == 0 else 0)
+
+
+class IndexedMerkleTree:
+    """the nullifier tree of the state-transition circuit (include/zkhip.h, "indexed Merkle tree"): leaves (val, next_val, next_idx), leaf 0 the
+    head, values inserted at the first free index.  `insert_batch` computes the witnesses of a whole batch on the device; a single insertion is
+    better served by the host hash."""
+
+    def __init__(self, depth: int):
+        h = _lib.C.c_void_p()
+        _lib.check(_lib.load().zkhip_imt_create(int(depth), _lib.C.byref(h)))
+        self._h, self.depth, self.n = h, int(depth), 1 << int(depth)
+
+    def close(self) -> None:
+        if self._h is not None:
+            _lib.load().zkhip_imt_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def used(self) -> int:
+        """used leaves, the head included: the index the next insertion goes to"""
+        u = _lib.C.c_uint32()
+        _lib.check(_lib.load().zkhip_imt_size(self._h, None, _lib.C.byref(u)))
+        return u.value
+
+    def insert_batch(self, values: Sequence[int], witness: bool = True, stream=None):
+        """values in insertion order -- integers, or an (n, 4) uint64 array of Montgomery limbs -- -> an ImtBatch (None with witness=False: the
+        tree alone is updated); no host wait"""
+        import torch
+
+        if isinstance(values, np.ndarray) and values.dtype == np.uint64 and values.ndim == 2 and values.shape[1] == 4:
+            w = np.ascontiguousarray(values)
+        else:
+            w = fr_encode([int(v) for v in values])
+        first = self.used
+        out = ImtBatch(len(w), self.depth, first, torch.device("cuda", torch.cuda.current_device())) if witness else None
+        c = out._c() if out is not None else None
+        bad = _lib.C.c_size_t(0)
+        rc = _lib.load().zkhip_imt_insert(self._h, w.ctypes.data if len(w) else None, len(w), _lib.C.byref(c) if c is not None else None, _lib.C.byref(bad),
+                                          _stream_of(stream))
+        _check_index(rc, bad)
+        if out is not None and len(w) == 0:
+            out.roots[0] = self.export()[1][-1]
+        return out
+
+    def get_root(self) -> int:
+        out = np.zeros((1, 4), dtype=np.uint64)
+        _lib.check(_lib.load().zkhip_imt_root(self._h, out.ctypes.data))
+        return fr_decode(out)[0]
+
+    def leaf(self, index: int) -> Tuple[int, int, int]:
+        """(val, next_val, next_idx) of leaf `index`"""
+        if not 0 <= index < self.n:
+            raise IndexError("leaf: no such leaf")
+        out = np.zeros((3, 4), dtype=np.uint64)
+        _lib.check(_lib.load().zkhip_imt_leaf(self._h, index, out.ctypes.data))
+        return tuple(fr_decode(out))
+
+    def get_proof(self, index: int) -> Tuple[List[int], List[int]]:
+        """(siblings from the leaf's level up, 1 where the node on the path is a left child else 0), as MerkleTree.get_proof"""
+        if not 0 <= index < self.n:
+            raise IndexError("get_proof: no such leaf")
+        out = np.zeros((self.depth, 4), dtype=np.uint64)
+        _lib.check(_lib.load().zkhip_imt_proof(self._h, index, out.ctypes.data))
+        return fr_decode(out), _helper(index, self.depth)
+
+    @staticmethod
+    def verify_proof(leaf: Sequence[int], index: int, root: int, proof: Sequence[int]) -> bool:
+        """the path from hash(val, next_val, next_idx) up, recomputed with the library's host hash"""
+        return MerkleTree.verify_proof(hash(list(leaf)), index, root, proof)
+
+    def export(self, stream=None):
+        """(leaves (n, 4), inner nodes (n - 1, 4) in merkle_device's order, preimages (n, 3, 4)): device copies of the tree as it stands"""
+        import torch
+
+        dev = torch.device("cuda", torch.cuda.current_device())
+        leaves = torch.empty((self.n, 4), dtype=torch.int64, device=dev)
+        nodes = torch.empty((self.n - 1, 4), dtype=torch.int64, device=dev)
+        pre = torch.empty((self.n, 3, 4), dtype=torch.int64, device=dev)
+        _lib.check(_lib.load().zkhip_imt_export_device(self._h, leaves.data_ptr(), nodes.data_ptr(), pre.data_ptr(), _stream_of(stream)))
+        return leaves, nodes, pre

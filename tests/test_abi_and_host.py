@@ -1,11 +1,11 @@
 """CPU: the C-ABI library loads and exports every symbol include/zkhip.h declares; host-side logic (formats, domain
 constants, sharding) is right; without a GPU every compute entry point fails loudly (no CPU fallback)."""
 import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header as AH
 from oracle import bn254 as O
 from zksnap_circuits_halo2_amd import _lib, fields as F
 from zksnap_circuits_halo2_amd.domain import EvaluationDomain
@@ -14,15 +14,10 @@ from zksnap_circuits_halo2_amd.multi_gpu import shard_range
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def header_functions():
-    text = open(os.path.join(ROOT, "include", "zkhip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(zkhip_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_library_exports_every_header_symbol(lib):
-    names = header_functions()
-    assert len(names) >= 20
+    names = sorted(AH.functions())
+    assert len(names) >= 150
+    assert set(names) <= AH.exported(), f"declared in include/zkhip.h but not exported by libzkhip.so: {sorted(set(names) - AH.exported())}"
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/zkhip.h but not exported by libzkhip.so"
     assert names == _lib.exported_symbols(), "ctypes signature table out of sync with include/zkhip.h"

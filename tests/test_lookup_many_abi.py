@@ -4,10 +4,10 @@ over the sorted table instead of a sort of the input column) is `permute_express
 import os
 import random
 import re
-import subprocess
 
 import pytest
 
+import abi_header as AH
 from oracle import bn254 as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,55 +26,19 @@ RUST = {
 }
 
 
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "zkhip.h")).read(), flags=re.S)
-
-
-def _header_params(name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;{]*?)\)\s*;", _header(), flags=re.S)
-    assert m, f"include/zkhip.h does not declare {name}"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
 def test_header_declares_both_calls():
     for name in NAMES:
-        assert _header_params(name) == HEADER[name]
-
-
-def test_ctypes_table_agrees_with_the_header():
-    import ctypes as C
-
-    from zksnap_circuits_halo2_amd import _lib
-
-    for name in NAMES:
-        res, args = _lib._SIGS[name]
-        params = _header_params(name)
-        assert res is C.c_int and len(args) == len(params), name
-        for ty, p in zip(args, params):
-            want = C.c_void_p if ("*" in p or "[" in p) else {"size_t": C.c_size_t, "uint32_t": C.c_uint32}[p.split()[0]]
-            assert ty is want, (name, p)
+        assert AH.params(name) == HEADER[name]
 
 
 def test_cpp_mirror_and_rust_shim_agree_with_the_header():
     hpp = open(os.path.join(ROOT, "include", "zkhip.hpp")).read()
     for name, mirror in zip(NAMES, ("permute_expression_pairs_device", "lookup_products_device")):
         assert re.search(r"inline void " + mirror + r"\(", hpp), f"include/zkhip.hpp has no {mirror}"
-        calls = list(re.finditer(r"\b" + name + r"\(", hpp))
-        assert calls, f"include/zkhip.hpp never calls {name}"
-        for m in calls:                      # the calls of the mirror pass as many arguments as the header declares
-            depth, i, args = 1, m.end(), 1
-            while depth:
-                ch = hpp[i]
-                depth += ch in "([{"
-                depth -= ch in ")]}"
-                args += ch == "," and depth == 1
-                i += 1
-            assert args == len(_header_params(name)), (name, args)
+        assert AH.hpp_call_arities(name), f"include/zkhip.hpp never calls {name}"
     ffi = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "rust-shim", "zkhip_ffi.rs")).read())
     for name in NAMES:
-        m = re.search(r"fn\s+" + name + r"\s*\((.*?)\)\s*->\s*c_int\s*;", ffi, flags=re.S)
-        assert m, f"rust-shim/zkhip_ffi.rs does not declare {name}"
-        assert [" ".join(p.split()) for p in m.group(1).split(",")] == RUST[name]
+        assert AH.rust_functions().get(name) == ("c_int", RUST[name]), f"rust-shim/zkhip_ffi.rs does not declare {name} this way"
     methods = set(re.findall(r"pub\(crate\) fn (\w+)", ffi))
     assert {"lookup_permute_many", "lookup_products"} <= methods
     patch = open(os.path.join(ROOT, "rust-shim", "prover_patch.rs")).read()
@@ -87,11 +51,6 @@ def test_cpp_mirror_and_rust_shim_agree_with_the_header():
 def test_library_exports_both_calls(lib):
     for name in NAMES:
         assert hasattr(lib, name), f"libzkhip.so does not export {name}"
-    from zksnap_circuits_halo2_amd import _lib
-
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.split()}
-    assert set(NAMES) <= exported
 
 
 # ---- the algorithm, in plain Python ---------------------------------------------------------------------------------------------------------

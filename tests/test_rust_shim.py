@@ -11,6 +11,8 @@ import re
 
 import pytest
 
+import abi_header as AH
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "rust-shim")
 
@@ -25,10 +27,6 @@ RUST_TYPES = {
     "c_char": ("int", 8), "c_void": ("void", 0), "VmProgram": ("struct zkhip_vm_program", 0), "u16": ("uint", 16),
     "ProverQueryC": ("struct zkhip_prover_query", 0), "ShplonkState": ("struct zkhip_shplonk", 0),
 }
-
-
-def strip_c_comments(text):
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
 
 
 def c_param(p):
@@ -52,18 +50,12 @@ def c_param(p):
 
 
 def c_prototypes():
-    text = strip_c_comments(open(os.path.join(ROOT, "include", "zkhip.h")).read())
     protos = {}
-    for m in re.finditer(r"\b(int|void|const char \*|size_t)\s*(zkhip_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        ret, name, params = m.group(1).strip(), m.group(2), " ".join(m.group(3).split())
-        if "(*" in params:                       # array-of-array parameters (zkhip_profile_read): not bound by the shim
+    for name, (ret, _) in AH.functions().items():
+        try:                                     # array-of-array, pointer-to-pointer / struct parameters (device-pipeline entry points): not bound by the shim
+            protos[name] = (ret, None if any("(*" in p for p in AH.params(name)) else [c_param(p) for p in AH.params(name)])
+        except AssertionError:
             protos[name] = (ret, None)
-            continue
-        try:
-            plist = [] if params in ("void", "") else [c_param(p) for p in params.split(",")]
-        except AssertionError:                   # pointer-to-pointer / struct parameters (device-pipeline entry points): not bound by the shim
-            plist = None
-        protos[name] = (ret, plist)
     return protos
 
 
@@ -82,15 +74,8 @@ def rust_param(p):
 
 
 def rust_externs():
-    text = open(os.path.join(SHIM, "zkhip_ffi.rs")).read()
-    text = re.sub(r"//[^\n]*", "", text)
-    block = re.search(r'extern\s+"C"\s*\{(.*?)\n\}', text, flags=re.S)
-    assert block, 'no extern "C" block in rust-shim/zkhip_ffi.rs'
-    out = {}
-    for m in re.finditer(r"fn\s+(zkhip_[a-z0-9_]+)\s*\((.*?)\)\s*(?:->\s*([^;]+?))?\s*;", block.group(1), flags=re.S):
-        params = " ".join(m.group(2).split())
-        out[m.group(1)] = ((m.group(3) or "()").strip(), [rust_param(p) for p in params.split(",") if p.strip()])
-    return out, text
+    text = re.sub(r"//[^\n]*", "", open(os.path.join(SHIM, "zkhip_ffi.rs")).read())
+    return {name: (ret or "()", [rust_param(p) for p in params]) for name, (ret, params) in AH.rust_functions().items()}, text
 
 
 def test_extern_block_matches_the_header():
@@ -169,17 +154,13 @@ def test_srs_arrays_unregister_in_their_own_drop_and_pin_in_every_constructor():
 def test_program_structs_match_the_header_field_by_field():
     """`#[repr(C)]` VmOperand / VmInsn / VmProgram of zkhip_ffi.rs against zkhip_vm_operand / zkhip_vm_insn / zkhip_vm_program of the header:
     the same fields, in the same order, of the same class and width; the opcode / source constants carry the header's values"""
-    hdr = strip_c_comments(open(os.path.join(ROOT, "include", "zkhip.h")).read())
     ffi = re.sub(r"//[^\n]*", "", open(os.path.join(SHIM, "zkhip_ffi.rs")).read())
     names = {"zkhip_vm_operand": "VmOperand", "zkhip_vm_insn": "VmInsn", "zkhip_vm_program": "VmProgram"}
     for cname, rname in names.items():
-        cbody = re.search(r"typedef struct " + cname + r"\s*\{(.*?)\}\s*" + cname + r"\s*;", hdr, flags=re.S).group(1)
         cfields = []
-        for decl in [d.strip() for d in cbody.split(";") if d.strip()]:
-            m = re.fullmatch(r"(const\s+)?(\w+)\s*(\*?)\s*(.+)", decl)
-            base, ptr = m.group(2), bool(m.group(3))
-            for nm in [x.strip() for x in m.group(4).split(",")]:
-                cfields.append((nm, ("ptr" if ptr else "val", names.get(base, None) or C_TYPES[base])))
+        for ty, nm in AH.structs()[cname]:
+            base = ty.replace("const ", "").replace("*", "").strip()
+            cfields.append((nm, ("ptr" if "*" in ty else "val", names.get(base, None) or C_TYPES[base])))
         rbody = re.search(r"pub\(crate\) struct " + rname + r"\s*\{(.*?)\}", ffi, flags=re.S).group(1)
         rfields = []
         for decl in [d.strip() for d in rbody.replace("\n", " ").split(",") if d.strip()]:
@@ -189,10 +170,10 @@ def test_program_structs_match_the_header_field_by_field():
             cls = base if base in names.values() else RUST_TYPES[base]
             rfields.append((nm, ("ptr" if m else "val", cls)))
         assert rfields == cfields, f"{rname} != {cname}: {rfields} vs {cfields}"
-    for group in (("ZKHIP_SRC_", "SRC_"), ("ZKHIP_OP_", "OP_")):
-        for nm, val in re.findall(group[0] + r"(\w+)\s*=\s*(\d+)", hdr):
-            assert re.search(r"pub\(crate\) const " + group[1] + nm + r": u8 = " + val + r";", ffi), f"{group[1]}{nm} != {val}"
-    assert re.search(r"#define ZKHIP_VM_REGS (\d+)", hdr).group(1) == re.search(r"pub\(crate\) const VM_REGS: usize = (\d+);", ffi).group(1)
+    assert len(AH.enums()) >= 13
+    for nm, val in AH.enums().items():
+        assert re.search(r"pub\(crate\) const " + nm[len("ZKHIP_"):] + r": u8 = " + str(val) + r";", ffi), f"{nm} != {val}"
+    assert str(AH.defines()["ZKHIP_VM_REGS"]) == re.search(r"pub\(crate\) const VM_REGS: usize = (\d+);", ffi).group(1)
 
 
 def test_prover_query_struct_matches_the_header():
@@ -202,10 +183,8 @@ def test_prover_query_struct_matches_the_header():
 
     from zksnap_circuits_halo2_amd import _lib
 
-    hdr = strip_c_comments(open(os.path.join(ROOT, "include", "zkhip.h")).read())
-    body = re.search(r"typedef struct zkhip_prover_query\s*\{(.*?)\}\s*zkhip_prover_query\s*;", hdr, flags=re.S).group(1)
-    cfields = [" ".join(d.split()) for d in body.split(";") if d.strip()]
-    assert cfields == ["uint64_t point[4]", "const void *d_poly", "uint64_t eval[4]", "uint32_t has_eval", "uint32_t reserved"]
+    assert AH.structs()["zkhip_prover_query"] == [("uint64_t[4]", "point"), ("const void *", "d_poly"), ("uint64_t[4]", "eval"), ("uint32_t", "has_eval"),
+                                                  ("uint32_t", "reserved")]
     ffi = re.sub(r"//[^\n]*", "", open(os.path.join(SHIM, "zkhip_ffi.rs")).read())
     rbody = re.search(r"pub\(crate\) struct ProverQueryC\s*\{(.*?)\}", ffi, flags=re.S).group(1)
     rfields = [" ".join(d.replace("pub ", "").split()) for d in rbody.split(",") if d.strip()]

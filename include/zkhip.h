@@ -713,6 +713,40 @@ int zkhip_imt_export_device(zkhip_imt *t, void *d_leaves, void *d_nodes, void *d
  * new value i, inserted at leaf max(n_used, 1) + i.  Refusals as above, except that any number of leaves is free. */
 int zkhip_imt_link(const uint64_t *used_vals, size_t n_used, const uint64_t *new_vals, size_t n_new, uint32_t *low_index_out, size_t *first_bad);
 
+/* ---- Paillier tally: the running homomorphic sum of a batch of ballots in one device call ----
+ * [DEP paillier_chip `paillier_enc_native` / `paillier_add_native`; the reference: `generate_wrapper_circuit_input`,
+ * /root/reference/aggregator/src/utils.rs:298-341, which encrypts every vote and folds the ballots one at a time into `prev_vote`, the argument
+ * of `StateTransitionInput::new`, aggregator/src/state_transition.rs:81.]  The `paillier_chip` crate is not vendored with the reference and
+ * could not be built, so parity with it is unpinned; only the two textbook formulas are restated here.
+ * THE DEFINITION (normative), over non-negative integers, N = n^2:
+ *   enc(n, g, m, r) = g^m * r^n mod N                 (`paillier_enc_native`)
+ *   add(n, a, b)    = a * b mod N                     (`paillier_add_native`: the product of two ciphertexts encrypts the sum of their votes)
+ *   pinned   n = 0x1ef95 (293 * 433), g = n + 1:  enc(m = 42, r = 23) = 0x13a7c1d25,  enc(m = 58, r = 101) = 0x32a4da219,  their add = 0x1b5145505
+ *   pinned   n = 2^175 + 2^88 + 1, g = n + 1:  enc(m = 2^253 + 5, r = 2^100 + 7) =
+ *            0xd46573adf90cb6f703909e88c21470d8d54038324d18ed3723a3b62fae6bca752ac6bc47b0d61531e9c8199,
+ *            enc(m = 1, r = n - 1) = 0x400000000000000000000100000000000000000000018000000000000000000000ffffffffffffffffffffff,
+ *            their add = 0x695b9b430ba3fb1445f14b6f5912adac3d5d33a7d5d0877d0cb74a94285556ccd43275cac8214d40c0c624a   (Python `pow`)
+ * Formats: a ciphertext is ZKHIP_PAILLIER_WORDS little-endian 64-bit words holding the canonical integer -- NOT Montgomery: the modulus is the
+ * caller's, and the Montgomery form mod N is internal to a call.  n is 3 words (at most ZKHIP_PAILLIER_MAX_N_BITS bits), on the HOST, read
+ * before the call returns; the modulus is always n^2.  An input >= N is taken mod N, as `BigUint %` would; every output is < N.
+ * Every call is asynchronous on `stream` with no host wait; scratch is the stream's workspace; at most 2^32 ciphertexts per call.
+ * ZKHIP_EINVAL, nothing enqueued (decided before the device is touched): n even (the arithmetic is Montgomery's and needs an odd modulus;
+ * every n = p q of a real key is odd) or n < 3; a null or non-8-byte-aligned pointer with a non-zero count; n_cols == 0; the overlaps named
+ * below.  Not built: moduli wider than 384 bits, decryption, a tally sharded over devices. */
+#define ZKHIP_PAILLIER_WORDS 6        /* 64-bit words of a ciphertext: an integer below n^2 < 2^384 */
+#define ZKHIP_PAILLIER_MAX_N_BITS 192 /* n fits three 64-bit words */
+/* d_out[i] = d_a[i] * d_b[i] mod n^2, i < count: `paillier_add_native` over arrays.  d_out may be d_a or d_b; any other overlap is refused. */
+int zkhip_paillier_mul_device(const uint64_t n[3], const void *d_a, const void *d_b, size_t count, void *d_out, void *stream);
+/* d_ballots: [n_ballots][n_cols] ciphertexts, ballot-major (one ballot contiguous, as it arrives).  d_init: n_cols ciphertexts, the
+ * reference's prev_vote at round 0; NULL starts every column from 1.  d_running: [n_ballots + 1][n_cols]: row 0 = init mod n^2, row i + 1 =
+ * row i * ballot i mod n^2 column by column -- row i is the prev_vote of round i, the last row the tally.  n_ballots == 0 writes row 0 only.
+ * A chunked scan per column, 2 ceil(log_16 n_ballots) - 1 launches above 16 ballots and one below (csrc/paillier.hip).  d_running must not overlap d_ballots or d_init. */
+int zkhip_paillier_tally_device(const uint64_t n[3], const void *d_ballots, size_t n_ballots, uint32_t n_cols, const void *d_init, void *d_running, void *stream);
+/* d_out[i] = g^m[i] * r[i]^n mod n^2, i < count.  g: 6 words on the host; d_m: 4 words per ciphertext (a vote is `fe_to_biguint` of an Fr);
+ * d_r: 3 words per ciphertext (any value; r >= n is not refused).  m = 0 gives g^0 = 1 whatever g is.  One lane per ciphertext, both powers by
+ * the plain left-to-right ladder.  d_out must not overlap d_m or d_r. */
+int zkhip_paillier_encrypt_device(const uint64_t n[3], const uint64_t g[6], const void *d_m, const void *d_r, size_t count, void *d_out, void *stream);
+
 /* ---- parity hooks for the field / curve layer (rows a1/a2 of SURVEY.md section 8) ------------------ */
 /* field: 0 = Fq, 1 = Fr.  op: 0 mul, 1 add, 2 sub, 3 square (b ignored).  Elementwise on n elements. */
 int zkhip_test_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);

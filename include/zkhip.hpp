@@ -452,6 +452,24 @@ struct Poseidon {
   }
 };
 
+// `paillier_add_native` / `paillier_enc_native` over arrays in HBM (zkhip.h, "Paillier tally"): ciphertexts are ZKHIP_PAILLIER_WORDS canonical
+// little-endian words, n is three words on the host and odd; every call is asynchronous on `stream`.
+struct Paillier {
+  uint64_t n[3];
+  // d_out[i] = d_a[i] d_b[i] mod n^2; d_out may be d_a or d_b
+  void mul_device(const void* d_a, const void* d_b, size_t count, void* d_out, void* stream = nullptr) const {
+    check(zkhip_paillier_mul_device(n, d_a, d_b, count, d_out, stream), "Paillier::mul_device");
+  }
+  // d_running[n_ballots + 1][n_cols]: row i the prev_vote of round i, the last row the tally; d_init null: every column starts from 1
+  void tally_device(const void* d_ballots, size_t n_ballots, uint32_t n_cols, const void* d_init, void* d_running, void* stream = nullptr) const {
+    check(zkhip_paillier_tally_device(n, d_ballots, n_ballots, n_cols, d_init, d_running, stream), "Paillier::tally_device");
+  }
+  // d_out[i] = g^m[i] r[i]^n mod n^2; m: 4 words each, r: 3 words each
+  void encrypt_device(const uint64_t g[6], const void* d_m, const void* d_r, size_t count, void* d_out, void* stream = nullptr) const {
+    check(zkhip_paillier_encrypt_device(n, g, d_m, d_r, count, d_out, stream), "Paillier::encrypt_device");
+  }
+};
+
 // `Blake2bWrite` / `Blake2bRead` with `Challenge255` [DEP transcript.rs] over zkhip_transcript_* (zkhip.h, "transcript"): the hash and the framing
 // run on the host inside the library, the `_device` forms take commitments / evaluations where they lie in HBM.  One thread at a time per object.
 class Transcript {

@@ -1,0 +1,157 @@
+"""GPU (-m gpu): the Paillier kernels (csrc/paillier.hip over csrc/modn.hpp) against Python integers -- `pow`, `*`, `%` -- exactly and on every
+element.  The tally's batch sizes sit on the scan's structure: 16 ballots per lane, so 16^l and 16^l + 1 switch the number of recursion levels
+(0, 1, 15 | 16, 17 | 255, 256, 257 | 4096, 4097: none to three levels).  The moduli are n = 3, a 176-bit n, n = 2^192 - 237 (n^2 just under
+2^384) and n = 2^32 k + 1; the ballots hold 0 (absorbing: its column is 0 from there on, and only its column), 1, n^2 - 1 and unreduced values
+up to 2^384 - 1."""
+import pytest
+import torch
+
+import paillier_cases as PC
+from zksnap_circuits_halo2_amd import paillier as P, poseidon
+
+pytestmark = pytest.mark.gpu
+
+BATCHES = [0, 1, 15, 16, 17, 255, 256, 257, 4096, 4097]
+
+
+def _ballots(rng, n, B, C, zero_at):
+    N = n * n
+    edges = [1, N - 1, PC.FULL, N + 1, (1 << 383) + 1]
+    rows = []
+    for b in range(B):
+        row = []
+        for c in range(C):
+            k = rng.randrange(8)
+            row.append(edges[rng.randrange(len(edges))] if k == 0 else rng.randrange(1, N) if k < 4 else rng.getrandbits(384))
+        rows.append(row)
+    if zero_at is not None:
+        rows[zero_at[0]][zero_at[1]] = 0
+    return rows
+
+
+def _running(n, ballots, init, C):
+    N = n * n
+    rows = [[v % N for v in init] if init is not None else [1 % N] * C]
+    for ballot in ballots:
+        rows.append([x * y % N for x, y in zip(rows[-1], ballot)])
+    return rows
+
+
+@pytest.mark.parametrize("C", [1, 5])
+@pytest.mark.parametrize("name", sorted(PC.MODULI))
+def test_tally_at_the_chunk_switches(lib, name, C):
+    n = PC.MODULI[name]
+    N = n * n
+    rng = PC.rng(f"tally-{name}-{C}")
+    for B in BATCHES:
+        zero_at = (B // 3, C // 2) if B >= 2 else None
+        ballots = _ballots(rng, n, B, C, zero_at)
+        given = [PC.FULL if c == 0 else rng.randrange(1, N) for c in range(C)]            # an unreduced init too
+        d_ballots = P.encode(ballots).reshape(B, C, 6)
+        for init in (None, given):
+            tally = P.tally_device(n, d_ballots, None if init is None else P.encode(init))
+            want = _running(n, ballots, init, C)
+            got = P.decode(tally.running)
+            assert tuple(tally.running.shape) == (B + 1, C, 6)
+            assert got == want, (name, C, B, init is not None, next(i for i in range(B + 1) if got[i] != want[i]))
+            assert tally.total() == want[-1]
+            if zero_at is not None:
+                assert all(got[i][zero_at[1]] == 0 for i in range(zero_at[0] + 1, B + 1))
+        if name != "n3" and C > 1 and zero_at is not None:
+            assert all(v != 0 for i in range(B + 1) for c, v in enumerate(got[i]) if c != zero_at[1])      # only that column
+
+
+def test_tally_rounds_are_the_arguments_of_the_state_transition(lib):
+    n = PC.N_176
+    rng = PC.rng("rounds")
+    ballots = _ballots(rng, n, 20, 5, None)
+    tally = P.tally_device(n, P.encode(ballots))
+    want = _running(n, ballots, None, 5)
+    for i in (0, 1, 16, 19):
+        assert tally.round(i) == ([v % (n * n) for v in ballots[i]], want[i])
+    with pytest.raises(IndexError):
+        tally.round(20)
+
+
+@pytest.mark.parametrize("name", sorted(PC.MODULI))
+def test_mul_device(lib, name):
+    n = PC.MODULI[name]
+    N = n * n
+    rng = PC.rng(f"mul-{name}")
+    for count in (1, 63, 64, 65, 1000):
+        edges = PC.edge_operands(n)
+        a = [edges[i % 5] if i < 25 else rng.getrandbits(384) for i in range(count)]
+        b = [edges[(i // 5) % 5] if i < 25 else rng.getrandbits(384) for i in range(count)]
+        want = [x * y % N for x, y in zip(a, b)]
+        ta, tb = P.encode(a), P.encode(b)
+        assert P.decode(P.mul_device(n, ta, tb)) == want, (name, count)
+        assert P.decode(ta) == a and P.decode(tb) == b
+        assert P.mul_device(n, ta, tb, out=ta) is ta and P.decode(ta) == want, (name, count, "d_out is d_a")
+        tc = P.encode(a)
+        assert P.mul_device(n, tc, tb, out=tb) is tb and P.decode(tb) == want, (name, count, "d_out is d_b")
+
+
+@pytest.mark.parametrize("g_kind", ["n_plus_1", "random352"])
+@pytest.mark.parametrize("name", ["n176", "ntop"])
+def test_encrypt_many(lib, name, g_kind):
+    n = PC.MODULI[name]
+    N = n * n
+    rng = PC.rng(f"enc-{name}-{g_kind}")
+    g = n + 1 if g_kind == "n_plus_1" else rng.getrandbits(352) | (1 << 351)
+    m_edges, r_edges = [0, 1, (1 << 256) - 1], [0, 1, n - 1, n, (1 << 192) - 1]
+    for count in (1, 64, 65, 300):
+        m = [m_edges[i % 3] if i < 15 else rng.getrandbits(256) for i in range(count)]
+        r = [r_edges[(i // 3) % 5] if i < 15 else rng.getrandbits(192) if i % 4 == 0 else rng.randrange(1, n) for i in range(count)]
+        if count == 1:
+            m, r = [rng.getrandbits(256)], [rng.randrange(n, 1 << 192)]
+        got = P.decode(P.encrypt_many_device(n, g, P.encode_exponents(m), P.encode_randomness(r)))
+        want = [pow(g, x, N) * pow(y, n, N) % N for x, y in zip(m, r)]
+        assert got == want, (name, g_kind, count, next(i for i in range(count) if got[i] != want[i]))
+        assert want == [P.enc_native(n, g, x, y) for x, y in zip(m, r)]
+
+
+def test_a_batch_of_rounds_end_to_end(lib):
+    """the loop of `generate_wrapper_circuit_input` restated: per ballot 5 one-hot votes encrypted, prev_vote folded with add_native"""
+    n = PC.N_176
+    g = n + 1
+    rng = PC.rng("e2e")
+    B = 33
+    votes, r_enc = [], []
+    for i in range(B):
+        vote = [0] * 5
+        vote[rng.randrange(5)] = 1
+        votes.append(vote)
+        r_enc.append([rng.getrandbits(176) for _ in range(5)])
+    prev_vote = [P.enc_native(n, g, 0, r_enc[0][0]) for _ in range(5)]              # round 0's prev_vote: encryptions of 0
+    expected = []
+    for i in range(B):
+        vote_enc = [P.enc_native(n, g, votes[i][c], r_enc[i][c]) for c in range(5)]
+        expected.append((vote_enc, prev_vote))
+        prev_vote = [P.add_native(n, x, y) for x, y in zip(prev_vote, vote_enc)]
+    init = P.encrypt_many_device(n, g, [0] * 5, [r_enc[0][0]] * 5)
+    ballots = P.encrypt_many_device(n, g, [v for vote in votes for v in vote], [r for row in r_enc for r in row]).reshape(B, 5, 6)
+    tally = P.tally_device(n, ballots, init)
+    for i in range(B):
+        assert tally.round(i) == expected[i], i
+    assert tally.total() == prev_vote
+
+
+def test_an_even_n_gives_the_same_tensors_from_the_host(lib):
+    n = PC.N_176 + 1
+    rng = PC.rng("even-gpu")
+    ballots = _ballots(rng, n, 17, 5, (4, 1))
+    tally = P.tally_device(n, P.encode(ballots))
+    assert tally.running.is_cuda and P.decode(tally.running) == _running(n, ballots, None, 5)
+
+
+def test_nullifier_values(lib):
+    rng = PC.rng("nullifier-gpu")
+    points = [(0, 0), (1, 1), ((1 << 256) - 1, (1 << 256) - 1)] + [(rng.getrandbits(256), rng.getrandbits(256)) for _ in range(62)]
+    assert len(points) == 65
+    got = poseidon.nullifier_values(points)
+    assert got.is_cuda and tuple(got.shape) == (65, 4) and got.dtype == torch.int64
+    want = []
+    for x, y in points:
+        raw = x.to_bytes(32, "little")
+        want.append(poseidon.hash([3 if y % 2 else 2] + [int.from_bytes(raw[at:at + 11], "little") for at in (0, 11, 22)]))
+    assert poseidon._ints(got) == want

@@ -12,6 +12,8 @@ ZKHIP_MAX_PAIRS = 64         # include/zkhip.h: the most pairs of one zkhip_pair
 ZKHIP_POSEIDON_MAX_WIDTH = 16   # include/zkhip.h: the most elements of one message of zkhip_poseidon_hash_many_device
 ZKHIP_POSEIDON_SUBTREE = 256    # include/zkhip.h: elements of a level one workgroup of zkhip_poseidon_merkle_device folds
 ZKHIP_IMT_MAX_DEPTH = 24        # include/zkhip.h: the deepest indexed Merkle tree zkhip_imt_create makes
+ZKHIP_PAILLIER_WORDS = 6        # include/zkhip.h: 64-bit words of a Paillier ciphertext (an integer below n^2)
+ZKHIP_PAILLIER_MAX_N_BITS = 192 # include/zkhip.h: the widest Paillier n
 
 # every symbol include/zkhip.h declares (tests check the export list against the header)
 _SIGS = {
@@ -160,6 +162,9 @@ _SIGS = {
     "zkhip_imt_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "zkhip_imt_export_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_imt_link": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "zkhip_paillier_mul_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zkhip_paillier_tally_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkhip_paillier_encrypt_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zkhip_test_reduce512": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zkhip_test_transcript_chunk": (C.c_uint32, [C.c_size_t]),
     "zkhip_profile_enable": (C.c_int, [C.c_int]),

@@ -31,6 +31,7 @@
 #include "blake2b.hpp"
 #include "poseidon.hpp"
 #include "imt.hpp"
+#include "modn.hpp"
 #include "../../include/zkhip.hpp"   // host-side 4 x 64 Montgomery arithmetic for domain constants (zkhip::halo2::detail)
 
 namespace zkhip {
@@ -3184,6 +3185,81 @@ int zkhip_poseidon_merkle_device(const void* d_leaves, size_t n_leaves, void* d_
   if ((rc = poseidon_device_table(s, &d_tab)) != ZKHIP_OK) return rc;
   if ((rc = sc->small.reserve(poseidon_merkle_workspace(n_leaves))) != ZKHIP_OK) return rc;
   return poseidon_merkle_device((const uint32_t*)d_leaves, n_leaves, (uint32_t*)d_nodes, d_tab, sc->small.p, sc->small.cap, s);
+}
+
+}  // extern "C"
+
+// ---- Paillier tally (include/zkhip.h, "Paillier tally") ------------------------------------------------------------------------------------------
+// Every refusal is decided on the host before HIP is touched: a refused call enqueues nothing and works in a process that has no device.
+namespace zkhip {
+static bool pl_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
+}
+static int pl_context(const char* who, const uint64_t* n, modn_ctx* ctx) {
+  if (!n) { set_error("%s: null modulus", who); return ZKHIP_EINVAL; }
+  if (!paillier_context(n, ctx)) { set_error("%s: n must be odd and at least 3 (Montgomery arithmetic mod n^2)", who); return ZKHIP_EINVAL; }
+  return ZKHIP_OK;
+}
+constexpr size_t PL_MAX_COUNT = (size_t)1 << 32;          // ciphertexts of one call
+constexpr size_t PL_BYTES = ZKHIP_PAILLIER_WORDS * 8;
+}  // namespace zkhip
+
+extern "C" {
+
+int zkhip_paillier_mul_device(const uint64_t n[3], const void* d_a, const void* d_b, size_t count, void* d_out, void* stream) {
+  ZK_API_RANGE();
+  modn_ctx ctx;
+  int rc = pl_context("paillier_mul", n, &ctx);
+  if (rc != ZKHIP_OK) return rc;
+  if (count > PL_MAX_COUNT) { set_error("paillier_mul: more than 2^32 ciphertexts in one call"); return ZKHIP_EINVAL; }
+  if (count && (!d_a || !d_b || !d_out)) { set_error("paillier_mul: null pointer"); return ZKHIP_EINVAL; }
+  if (count && (((uintptr_t)d_a | (uintptr_t)d_b | (uintptr_t)d_out) & 7)) { set_error("paillier_mul: pointers must be 8-byte aligned"); return ZKHIP_EINVAL; }
+  if (count == 0) return ZKHIP_OK;
+  // d_out may BE an input; a partial overlap would let one lane's store reach another lane's load
+  for (const void* in : {d_a, d_b})
+    if (in != d_out && pl_overlap(in, count * PL_BYTES, d_out, count * PL_BYTES)) { set_error("paillier_mul: d_out overlaps an input without being it"); return ZKHIP_EINVAL; }
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  return paillier_mul_device(ctx, (const uint64_t*)d_a, (const uint64_t*)d_b, count, (uint64_t*)d_out, caller_stream(stream));
+}
+
+int zkhip_paillier_tally_device(const uint64_t n[3], const void* d_ballots, size_t n_ballots, uint32_t n_cols, const void* d_init, void* d_running, void* stream) {
+  ZK_API_RANGE();
+  modn_ctx ctx;
+  int rc = pl_context("paillier_tally", n, &ctx);
+  if (rc != ZKHIP_OK) return rc;
+  if (n_cols == 0) { set_error("paillier_tally: n_cols is 0"); return ZKHIP_EINVAL; }
+  if (n_ballots >= PL_MAX_COUNT || (n_ballots + 1) * (size_t)n_cols > PL_MAX_COUNT) { set_error("paillier_tally: more than 2^32 ciphertexts in one call"); return ZKHIP_EINVAL; }
+  if (!d_running || (n_ballots && !d_ballots)) { set_error("paillier_tally: null pointer"); return ZKHIP_EINVAL; }
+  if (((uintptr_t)d_running | (uintptr_t)d_init | (n_ballots ? (uintptr_t)d_ballots : 0)) & 7) { set_error("paillier_tally: pointers must be 8-byte aligned"); return ZKHIP_EINVAL; }
+  const size_t row = (size_t)n_cols * PL_BYTES;
+  if (pl_overlap(d_running, (n_ballots + 1) * row, d_ballots, n_ballots * row) || (d_init && pl_overlap(d_running, (n_ballots + 1) * row, d_init, row))) {
+    set_error("paillier_tally: d_running overlaps an input");
+    return ZKHIP_EINVAL;
+  }
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->ws.reserve(paillier_tally_workspace_bytes(n_ballots, n_cols))) != ZKHIP_OK) return rc;
+  return paillier_tally_device(ctx, (const uint64_t*)d_ballots, n_ballots, n_cols, (const uint64_t*)d_init, (uint64_t*)d_running, sc->ws.p, sc->ws.cap, s);
+}
+
+int zkhip_paillier_encrypt_device(const uint64_t n[3], const uint64_t g[6], const void* d_m, const void* d_r, size_t count, void* d_out, void* stream) {
+  ZK_API_RANGE();
+  modn_ctx ctx;
+  int rc = pl_context("paillier_encrypt", n, &ctx);
+  if (rc != ZKHIP_OK) return rc;
+  if (!g) { set_error("paillier_encrypt: null base"); return ZKHIP_EINVAL; }
+  if (count > PL_MAX_COUNT) { set_error("paillier_encrypt: more than 2^32 ciphertexts in one call"); return ZKHIP_EINVAL; }
+  if (count && (!d_m || !d_r || !d_out)) { set_error("paillier_encrypt: null pointer"); return ZKHIP_EINVAL; }
+  if (count && (((uintptr_t)d_m | (uintptr_t)d_r | (uintptr_t)d_out) & 7)) { set_error("paillier_encrypt: pointers must be 8-byte aligned"); return ZKHIP_EINVAL; }
+  if (count == 0) return ZKHIP_OK;
+  if (pl_overlap(d_out, count * PL_BYTES, d_m, count * 32) || pl_overlap(d_out, count * PL_BYTES, d_r, count * 24)) { set_error("paillier_encrypt: d_out overlaps an input"); return ZKHIP_EINVAL; }
+  guard_t gd(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  return paillier_encrypt_device(ctx, n, g, (const uint64_t*)d_m, (const uint64_t*)d_r, count, (uint64_t*)d_out, caller_stream(stream));
 }
 
 }  // extern "C"

@@ -260,6 +260,16 @@ int imt_fill_device(uint32_t* d_dst, size_t n, const uint32_t value[8], hipStrea
 int imt_insert_device(uint32_t depth, size_t n_new, void* ws, uint32_t* d_leaves, uint32_t* d_nodes, uint32_t* d_preimages, uint32_t* out_roots,
                       uint32_t* out_new_leaves, uint32_t* out_low_proofs, uint32_t* out_new_proofs, const uint32_t* d_tab, hipStream_t stream);
 
+// paillier.hip (include/zkhip.h, "Paillier tally").  The context of n^2 is built on the host per call (modn.hpp) and handed to the kernels by value.
+struct modn_ctx;
+bool paillier_context(const uint64_t n[3], modn_ctx* ctx);      // false: n even or n < 3
+size_t paillier_tally_workspace_bytes(size_t n_ballots, uint32_t n_cols);
+int paillier_mul_device(const modn_ctx& ctx, const uint64_t* d_a, const uint64_t* d_b, size_t count, uint64_t* d_out, hipStream_t stream);
+int paillier_tally_device(const modn_ctx& ctx, const uint64_t* d_ballots, size_t n_ballots, uint32_t n_cols, const uint64_t* d_init, uint64_t* d_running, void* ws,
+                          size_t ws_bytes, hipStream_t stream);
+int paillier_encrypt_device(const modn_ctx& ctx, const uint64_t n[3], const uint64_t g[6], const uint64_t* d_m, const uint64_t* d_r, size_t count, uint64_t* d_out,
+                            hipStream_t stream);
+
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);
 int g1_check_points_device(const uint32_t* d_points, size_t n, unsigned long long* d_first_bad, hipStream_t stream);

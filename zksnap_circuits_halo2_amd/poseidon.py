@@ -64,6 +64,26 @@ def hash_many_device(messages, out=None, stream=None):
     return out
 
 
+def compress_nullifier(point: Tuple[int, int]) -> List[int]:
+    """`compress_native_nullifier` (/root/reference/aggregator/src/utils.rs:355) of a secp256k1 affine point (x, y): the tag -- 2 for an even
+    y, 3 for an odd one -- then the 11-, 11- and 10-byte little-endian chunks of x's 32 bytes.  Host; integers in and out."""
+    x, y = int(point[0]), int(point[1])
+    if not (0 <= x < 1 << 256 and 0 <= y < 1 << 256):
+        raise ValueError("compress_nullifier: a coordinate is 32 bytes")
+    raw = x.to_bytes(32, "little")
+    return [2 + (y & 1)] + [int.from_bytes(raw[at:at + 11], "little") for at in (0, 11, 22)]
+
+
+def nullifier_values(points: Sequence[Tuple[int, int]], stream=None):
+    """secp256k1 affine points (x, y) -> the (n, 4) device tensor of the values the state-transition circuit inserts into the nullifier tree:
+    the width-4 hash of every compressed point, one launch.  `IndexedMerkleTree.insert_batch` takes its host copy."""
+    import torch
+
+    packed = fr_encode([v for P in points for v in compress_nullifier(P)]).reshape(len(points), 4, 4)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    return hash_many_device(torch.from_numpy(packed.view(np.int64)).to(dev), stream=stream)
+
+
 def merkle_device(leaves, stream=None):
     """leaves: (n, 4) int64 device tensor, n a power of two -> the (n - 1, 4) inner nodes, level 1 first, the root last; no host wait"""
     import torch

@@ -124,7 +124,7 @@ def chunks_of(n):
 
 
 def scan_levels(n):
-    """recursion levels below the top one of a scan over n elements (csrc/poly.hip scan_levels): one more at every 16^l + 1"""
+    """stored levels of a scan over n elements (csrc/scan_plan.hpp, scan_plan::L): one more at every 16^l + 1"""
     levels = 0
     while n > CH:
         n, levels = chunks_of(n), levels + 1
@@ -149,8 +149,8 @@ def test_chunk_length_the_sizes_are_chosen_around():
         assert (scan_levels(16 ** l), scan_levels(16 ** l + 1)) == (l - 1, l)
     assert [invert_chunk(n) for n in INVERT_SIZES] == [4, 4, 4, 4, 4, 4, 8]
     # the next change of the chunk length fails here instead of moving the code's switches away from SCAN_SIZES
-    src = os.path.join(os.path.dirname(zksnap_circuits_halo2_amd.__file__), "csrc", "poly.hip")
-    assert "constexpr uint32_t POLY_CH = 16;" in open(src).read()
+    src = os.path.join(os.path.dirname(zksnap_circuits_halo2_amd.__file__), "csrc", "scan_plan.hpp")
+    assert "constexpr uint32_t SCAN_CH = 16;" in open(src).read()
 
 
 # ---------------------------------------------------------------- 2. Horner scans

@@ -1,7 +1,7 @@
 // The Paillier tally (include/zkhip.h, "Paillier tally"): ciphertexts are integers mod n^2, the homomorphic sum of two votes is their product
 // (`paillier_add_native`), and the `prev_vote` of every round of a batch is an exclusive prefix product down a column of ciphertexts.  The
-// reference folds one ballot at a time (/root/reference/aggregator/src/utils.rs:337-341); here the fold is the chunked scan of poly.hip
-// (k_prod_agg, recurse, k_prod_apply, PL_CH = POLY_CH elements per lane) over the ring of modn.hpp, one column per blockIdx.y:
+// reference folds one ballot at a time (/root/reference/aggregator/src/utils.rs:337-341); here the fold is a chunked scan over the ring of
+// modn.hpp, SCAN_CH ballots per lane and one column per blockIdx.y, driven by the level plan of scan_plan.hpp as the scans of poly.hip are:
 //
 //   k_pl_agg<TOP>     lane (t, c) multiplies chunk t of column c into agg[c][t].  TOP: the elements are the caller's ballots (canonical, any
 //                     384-bit integer, ballot-major) and are converted at the load; below the top they are the Montgomery values of the level above.
@@ -18,11 +18,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "modn.hpp"
+#include "scan_plan.hpp"
 #include "zkhip_internal.hpp"
 
 namespace zkhip {
 
-constexpr uint32_t PL_CH = 16;         // ballots per lane of the scan (poly.hip's POLY_CH: same shape, same chunk switches)
 constexpr int PL_BLOCK = 64;           // one wave: a multiplication is ~300 multiply-adds, the lanes are worth spreading over the SIMDs
 constexpr int PL_W = ZKHIP_PAILLIER_WORDS;
 
@@ -64,7 +64,7 @@ template <bool TOP>
 __global__ void __launch_bounds__(PL_BLOCK) k_pl_agg(const modn_ctx ctx, const uint64_t* __restrict__ v, size_t n, uint32_t n_cols, uint64_t* __restrict__ agg, size_t m) {
   const size_t t = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
   if (t >= m) return;
-  const size_t lo = t * PL_CH, hi = lo + PL_CH < n ? lo + PL_CH : n;
+  const size_t lo = t * SCAN_CH, hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   for (uint32_t c = blockIdx.y; c < n_cols; c += gridDim.y) {
     modn acc = pl_elem<TOP>(ctx, v, n, n_cols, c, lo);
     for (size_t i = lo + 1; i < hi; i++) acc = modn_mul(acc, pl_elem<TOP>(ctx, v, n, n_cols, c, i), ctx);
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_agg(const modn_ctx ctx, const u
 __global__ void __launch_bounds__(PL_BLOCK) k_pl_scan(const modn_ctx ctx, uint64_t* __restrict__ v, size_t n, uint32_t n_cols, const uint64_t* __restrict__ carry, size_t m) {
   const size_t t = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
   if (t >= m) return;
-  const size_t lo = t * PL_CH, hi = lo + PL_CH < n ? lo + PL_CH : n;
+  const size_t lo = t * SCAN_CH, hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   for (uint32_t c = blockIdx.y; c < n_cols; c += gridDim.y) {
     modn cur = carry ? pl_load(carry + ((size_t)c * m + t) * PL_W) : modn_one(ctx);
     for (size_t i = lo; i < hi; i++) {
@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_apply(const modn_ctx ctx, const
                                                       const uint64_t* __restrict__ carry, size_t m, uint64_t* __restrict__ running) {
   const size_t t = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
   if (t >= m && t != 0) return;
-  const size_t lo = t * PL_CH, hi = lo + PL_CH < n ? lo + PL_CH : n;
+  const size_t lo = t * SCAN_CH, hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   for (uint32_t c = blockIdx.y; c < n_cols; c += gridDim.y) {
     modn cur = init ? modn_to_mont(pl_load(init + (size_t)c * PL_W), ctx) : modn_one(ctx);
     if (carry) cur = modn_mul(cur, pl_load(carry + ((size_t)c * m + t) * PL_W), ctx);
@@ -118,8 +118,6 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_encrypt(const modn_ctx ctx, con
   pl_store(out + i * PL_W, modn_from_mont(modn_mul(gm, rn, ctx), ctx));
 }
 
-static inline size_t pl_chunks(size_t n) { return (n + PL_CH - 1) / PL_CH; }
-static inline size_t pl_level_bytes(size_t m, uint32_t n_cols) { return ((m * n_cols * PL_W * 8 + 255) / 256) * 256; }
 static inline dim3 pl_grid(size_t lanes, uint32_t n_cols) {
   return dim3((unsigned)((lanes + PL_BLOCK - 1) / PL_BLOCK), n_cols < 65535u ? n_cols : 65535u);
 }
@@ -129,12 +127,6 @@ bool paillier_context(const uint64_t n[3], modn_ctx* ctx) {
   uint32_t N[MODN_L];
   modn_square_words(n, 3, N);
   return modn_ctx_build(N, ctx);
-}
-
-size_t paillier_tally_workspace_bytes(size_t n_ballots, uint32_t n_cols) {
-  size_t total = 256, m = n_ballots;
-  while (m > PL_CH) { m = pl_chunks(m); total += pl_level_bytes(m, n_cols); }
-  return total;
 }
 
 int paillier_mul_device(const modn_ctx& ctx, const uint64_t* d_a, const uint64_t* d_b, size_t count, uint64_t* d_out, hipStream_t stream) {
@@ -147,33 +139,17 @@ int paillier_mul_device(const modn_ctx& ctx, const uint64_t* d_a, const uint64_t
 int paillier_tally_device(const modn_ctx& ctx, const uint64_t* d_ballots, size_t n_ballots, uint32_t n_cols, const uint64_t* d_init, uint64_t* d_running, void* ws,
                           size_t ws_bytes, hipStream_t stream) {
   if (ws_bytes < paillier_tally_workspace_bytes(n_ballots, n_cols)) { set_error("paillier_tally: workspace too small"); return ZKHIP_EINVAL; }
-  // up: the chunk products of every level until one chunk holds a column
-  constexpr int MAX_LEVELS = 16;                              // 16^16 ballots
-  uint64_t* level[MAX_LEVELS];
-  size_t level_n[MAX_LEVELS];
-  int levels = 0;
-  char* at = (char*)ws;
-  size_t n = n_ballots;
-  while (n > PL_CH && levels < MAX_LEVELS) {
-    const size_t m = pl_chunks(n);
-    level[levels] = (uint64_t*)at;
-    level_n[levels] = m;
-    at += pl_level_bytes(m, n_cols);
-    if (levels == 0) hipLaunchKernelGGL(k_pl_agg<true>, pl_grid(m, n_cols), dim3(PL_BLOCK), 0, stream, ctx, d_ballots, n, n_cols, level[0], m);
-    else hipLaunchKernelGGL(k_pl_agg<false>, pl_grid(m, n_cols), dim3(PL_BLOCK), 0, stream, ctx, (const uint64_t*)level[levels - 1], n, n_cols, level[levels], m);
-    HIPCHK(hipGetLastError());
-    n = m;
-    levels++;
+  const scan_plan plan(n_ballots, (size_t)n_cols * PL_W * 8);
+  auto level = [&](int k) { return plan.level<uint64_t>(ws, k); };
+  for (int k = 1; k <= plan.L; k++) {                         // up: the chunk products of every level until one chunk holds a column
+    if (k == 1) hipLaunchKernelGGL(k_pl_agg<true>, pl_grid(plan.n[1], n_cols), dim3(PL_BLOCK), 0, stream, ctx, d_ballots, n_ballots, n_cols, level(1), plan.n[1]);
+    else hipLaunchKernelGGL(k_pl_agg<false>, pl_grid(plan.n[k], n_cols), dim3(PL_BLOCK), 0, stream, ctx, (const uint64_t*)level(k - 1), plan.n[k - 1], n_cols, level(k), plan.n[k]);
   }
-  // down: every level scanned in place from the carries of the level above it
-  for (int l = levels - 1; l >= 0; l--) {
-    const size_t m = pl_chunks(level_n[l]);
-    hipLaunchKernelGGL(k_pl_scan, pl_grid(m, n_cols), dim3(PL_BLOCK), 0, stream, ctx, level[l], level_n[l], n_cols, l + 1 < levels ? (const uint64_t*)level[l + 1] : (const uint64_t*)nullptr, m);
-    HIPCHK(hipGetLastError());
-  }
-  const size_t m = pl_chunks(n_ballots);
-  hipLaunchKernelGGL(k_pl_apply, pl_grid(m ? m : 1, n_cols), dim3(PL_BLOCK), 0, stream, ctx, d_ballots, n_ballots, n_cols, d_init, levels ? (const uint64_t*)level[0] : (const uint64_t*)nullptr, m,
-                     d_running);
+  for (int k = plan.L; k >= 1; k--)                           // down: every level scanned in place from the carries of the level above it
+    hipLaunchKernelGGL(k_pl_scan, pl_grid(plan.n[k + 1], n_cols), dim3(PL_BLOCK), 0, stream, ctx, level(k), plan.n[k], n_cols,
+                       k < plan.L ? (const uint64_t*)level(k + 1) : (const uint64_t*)nullptr, plan.n[k + 1]);
+  hipLaunchKernelGGL(k_pl_apply, pl_grid(plan.n[1] ? plan.n[1] : 1, n_cols), dim3(PL_BLOCK), 0, stream, ctx, d_ballots, n_ballots, n_cols, d_init,
+                     plan.L ? (const uint64_t*)level(1) : (const uint64_t*)nullptr, plan.n[1], d_running);
   HIPCHK(hipGetLastError());
   return ZKHIP_OK;
 }

@@ -4,8 +4,8 @@
 // z[i+1] = z[i] * v[i]); all reached from create_proof, /root/reference/aggregator/src/wrapper.rs:129.
 //
 // All four are chunked linear recurrences: a thread owns CH consecutive elements, a first pass produces one aggregate
-// per chunk, the aggregates are processed recursively (1/CH of the work), a second pass re-runs each chunk with its
-// incoming carry.  2 multiplies per element, O(log_CH n) launches.
+// per chunk, the aggregates are scanned the same way (1/CH of the work), a second pass re-runs each chunk with its
+// incoming carry.  2 multiplies per element, O(log_CH n) launches; the levels of every scan come from scan_plan.hpp.
 //   suffix Horner scan  out[i] = a[i] + b * out[i+1]           (kate_division; eval_polynomial is out[0])
 //   prefix product      out[0] = 1, out[i+1] = out[i] * v[i]
 //   batch inversion     Montgomery's trick per chunk with one inversion (division steps, fe_inverse.hpp) per thread
@@ -18,24 +18,25 @@
 #include "fp29.hpp"
 #include "fe_inverse.hpp"
 #include "fr_vec.hpp"
+#include "scan_plan.hpp"
 #include "zkhip_internal.hpp"
 
 namespace zkhip {
 
-// elements per thread of the scans.  16, not 32 (round 3, same-box A/B in profiles/r03_batch_invert_ab.txt): 2^15 eval / kate / prefix 0.099 / 0.170 /
-// 0.111 -> 0.086 / 0.139 / 0.078 ms, 2^20 0.130 / 0.231 / 0.160 -> 0.117 / 0.196 / 0.120, 2^24 0.367 / 0.980 / 0.854 -> 0.361 / 0.942 / 0.805 (8: the large
-// sizes lose).  The batch inversion picks its own chunk length (INV_CH_MAX).
-constexpr uint32_t POLY_CH = 16;
+// elements per thread of the scans: SCAN_CH (scan_plan.hpp).  16, not 32 (round 3, same-box A/B in profiles/r03_batch_invert_ab.txt): 2^15 eval / kate /
+// prefix 0.099 / 0.170 / 0.111 -> 0.086 / 0.139 / 0.078 ms, 2^20 0.130 / 0.231 / 0.160 -> 0.117 / 0.196 / 0.120, 2^24 0.367 / 0.980 / 0.854 -> 0.361 / 0.942 /
+// 0.805 (8: the large sizes lose).  The batch inversion picks its own chunk length (INV_CH_MAX).
 constexpr uint32_t INV_CH_MAX = 32;
 
 // ---- suffix Horner scan ---------------------------------------------------------------------------
-// pass A: agg[t] = sum_{i in chunk t} a[i] b^(i - lo)          (the chunk's scan value at its first element, carry-in 0)
+// pass A: agg[t] = sum_{i in chunk t} a[i] b^(i - lo)          (the chunk's scan value at its first element, carry-in 0).  One dense array:
+// k_horner_agg_batch with one lane computes the same, 3 % slower per launch (profiles/r18_scan_plan.txt), so the single-array form stays
 __global__ void __launch_bounds__(256) k_horner_agg(const uint32_t* __restrict__ a, size_t n, const fe_arg* __restrict__ b_dev, uint32_t* __restrict__ agg) {
   const fe_arg b_ext = *b_dev;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t lo = t * POLY_CH;
+  const size_t lo = t * SCAN_CH;
   if (lo >= n) return;
-  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  const size_t hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   const fe b = fr_const_internal(b_ext);
   fe q = fe_zero();
   size_t i = hi;
@@ -59,9 +60,9 @@ __global__ void __launch_bounds__(256) k_horner_apply(const uint32_t* __restrict
                                                       size_t out_shift) {
   const fe_arg b_ext = *b_dev;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t lo = t * POLY_CH;
+  const size_t lo = t * SCAN_CH;
   if (lo >= n) return;
-  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  const size_t hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   const fe b = fr_const_internal(b_ext);
   fe q = (carry != nullptr && t + 1 < ncarry) ? load_ext(carry, t + 1) : fe_zero();
   size_t i = hi;
@@ -87,9 +88,9 @@ __global__ void __launch_bounds__(256) k_horner_apply(const uint32_t* __restrict
 __global__ void __launch_bounds__(256) k_horner_agg_batch(const uint32_t* const* __restrict__ ptrs, const uint32_t* __restrict__ base, size_t n,
                                                           const fe_arg* __restrict__ b_dev, uint32_t* __restrict__ agg, size_t m) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t lo = t * POLY_CH;
+  const size_t lo = t * SCAN_CH;
   if (lo >= n) return;
-  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  const size_t hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   const uint32_t* a = ptrs ? ptrs[blockIdx.y] : base + (size_t)blockIdx.y * n * 8;
   const fe_arg b_ext = *b_dev;
   const fe b = fr_const_internal(b_ext);
@@ -108,9 +109,9 @@ __global__ void __launch_bounds__(256) k_horner_agg_batch(const uint32_t* const*
 
 // ---- prefix product --------------------------------------------------------------------------------
 __device__ __forceinline__ void prod_agg_chunk(const uint32_t* __restrict__ v, size_t n, uint32_t* __restrict__ agg, size_t t) {
-  const size_t lo = t * POLY_CH;
+  const size_t lo = t * SCAN_CH;
   if (lo >= n) return;
-  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  const size_t hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   uint32_t w[8];
   load_words(v + lo * 8, w);
   fe acc = fe_unpack<0>(w);                                   // x * 2^256 (external domain)
@@ -133,9 +134,6 @@ __device__ __forceinline__ void prod_agg_chunk(const uint32_t* __restrict__ v, s
   store_canon(agg, t, acc);
 }
 
-__global__ void __launch_bounds__(256) k_prod_agg(const uint32_t* __restrict__ v, size_t n, uint32_t* __restrict__ agg) {
-  prod_agg_chunk(v, n, agg, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
-}
 // blockIdx.y = one of many independent arrays of n elements, dense; m = chunks of one array
 __global__ void __launch_bounds__(256) k_prod_agg_batch(const uint32_t* __restrict__ v, size_t n, uint32_t* __restrict__ agg, size_t m) {
   prod_agg_chunk(v + (size_t)blockIdx.y * n * 8, n, agg + (size_t)blockIdx.y * m * 8, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
@@ -144,9 +142,9 @@ __global__ void __launch_bounds__(256) k_prod_agg_batch(const uint32_t* __restri
 // out[i] = carry[t] * prod_{lo <= j < i} v[j]   (exclusive); carry == nullptr: carry is 1
 __device__ __forceinline__ void prod_apply_chunk(const uint32_t* __restrict__ v, size_t n, const uint32_t* __restrict__ carry, uint32_t* __restrict__ out,
                                                  size_t t) {
-  const size_t lo = t * POLY_CH;
+  const size_t lo = t * SCAN_CH;
   if (lo >= n) return;
-  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  const size_t hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   fe cur;
   if (carry) cur = load_ext(carry, t);
   else {                                                      // 1 in the external domain = 2^256 mod r
@@ -173,10 +171,6 @@ __device__ __forceinline__ void prod_apply_chunk(const uint32_t* __restrict__ v,
   }
 }
 
-__global__ void __launch_bounds__(256) k_prod_apply(const uint32_t* __restrict__ v, size_t n, const uint32_t* __restrict__ carry,
-                                                    uint32_t* __restrict__ out) {
-  prod_apply_chunk(v, n, carry, out, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
-}
 __global__ void __launch_bounds__(256) k_prod_apply_batch(const uint32_t* __restrict__ v, size_t n, const uint32_t* __restrict__ carry, size_t m,
                                                           uint32_t* __restrict__ out) {
   prod_apply_chunk(v + (size_t)blockIdx.y * n * 8, n, carry ? carry + (size_t)blockIdx.y * m * 8 : nullptr, out + (size_t)blockIdx.y * n * 8,
@@ -232,43 +226,15 @@ __global__ void __launch_bounds__(64) k_batch_invert(uint32_t* __restrict__ a, s
 }
 
 // ---- host orchestration ------------------------------------------------------------------------------
-static inline size_t chunks_of(size_t n) { return (n + POLY_CH - 1) / POLY_CH; }
-static inline dim3 grid_for(size_t threads, int block) { return dim3((unsigned)((threads + block - 1) / block)); }
-
-size_t poly_workspace_bytes(size_t n) {   // aggregate arrays of every recursion level + constants + batch-invert scratch
-  size_t total = 8192, m = n;
-  while (m > 1) { m = chunks_of(m); total += ((m * 32 + 255) / 256) * 256 + 256; }
-  return total + ((n * 36 + 255) / 256) * 256;
-}
-
-// out[i - out_shift] = sum_{j >= i} a[j] b^(j-i) for i >= out_shift (out may be nullptr: only the value at index 0 is
-// wanted and is written to d_result).  b: the multiplier in device memory (8 external words).  ws: scratch.
-static int horner_scan(const uint32_t* d_a, size_t n, const fe_arg* b, uint32_t* d_out, size_t out_shift,
-                       uint32_t* d_result, char* ws, hipStream_t stream) {
-  if (n <= POLY_CH) {   // one chunk
-    if (d_out) hipLaunchKernelGGL(k_horner_apply, dim3(1), dim3(256), 0, stream, d_a, n, b, (const uint32_t*)nullptr, (size_t)0, d_out, out_shift);
-    if (d_result) hipLaunchKernelGGL(k_horner_agg, dim3(1), dim3(256), 0, stream, d_a, n, b, d_result);
-    HIPCHK(hipGetLastError());
-    return ZKHIP_OK;
-  }
-  const size_t m = chunks_of(n);
-  uint32_t* agg = (uint32_t*)ws;
-  char* next_ws = ws + ((m * 32 + 255) / 256) * 256;
-  hipLaunchKernelGGL(k_horner_agg, grid_for(m, 256), dim3(256), 0, stream, d_a, n, b, agg);
-  // recursion: scan the aggregates in place with multiplier b^CH -- the next entry of the power array the caller parked (stage_const: b,
-  // b^CH, b^(CH^2), ... computed by ONE thread up front; a launch per level for one power each cost 11 us apiece in the dependent chain);
-  // the scan's value at index 0 is the overall result
-  int rc = horner_scan(agg, m, b + 1, d_out ? agg : nullptr, 0, d_result, next_ws, stream);
-  if (rc != ZKHIP_OK) return rc;
-  if (d_out) hipLaunchKernelGGL(k_horner_apply, grid_for(m, 256), dim3(256), 0, stream, d_a, n, b, (const uint32_t*)agg, m, d_out, out_shift);
-  HIPCHK(hipGetLastError());
-  return ZKHIP_OK;
-}
+// Every scan walks one scan_plan (scan_plan.hpp) of its workspace: up, level k - 1 is reduced into level k for k = 1 .. L; down, level k is
+// scanned in place from the carries in level k + 1 for k = L .. 1, and level 0 -- the caller's array -- last, into the caller's output.
+// plan.n[k + 1] is the number of chunks of level k; one launch per step, `lanes` independent arrays as blockIdx.y.
+static inline dim3 grid_for(size_t threads, int block, size_t lanes = 1) { return dim3((unsigned)((threads + block - 1) / block), (unsigned)lanes); }
 
 // a constant that arrives from the host travels as a kernel argument (by value: the caller's memory is free when the launch returns, and
 // nothing waits for the stream -- a copy from the caller's memory would need a synchronisation) and is parked in device memory by one thread
-// out[0] = v, out[l] = out[l - 1]^CH for l <= levels: the multipliers of every recursion level of a scan
-constexpr uint32_t POW_LEVELS = 7;        // 16^7 = 2^28 elements; 8 constants = the 256 bytes the scans reserve
+// out[0] = v, out[l] = out[l - 1]^CH for l <= levels: the multipliers of every level of a scan
+constexpr int POW_LEVELS = 7;             // 16^7 = 2^28 elements; 8 constants = the 256 bytes the scans reserve
 __global__ void k_store_const(fe_arg v, fe_arg* __restrict__ out, uint32_t levels) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   out[0] = v;
@@ -279,7 +245,7 @@ __global__ void k_store_const(fe_arg v, fe_arg* __restrict__ out, uint32_t level
   for (int i = 0; i < NL; i++) k.l[i] = Fr::TO_EXT[i];
 #pragma unroll 1
   for (uint32_t l = 1; l <= levels; l++) {
-    static_assert(POLY_CH == 16, "b^CH below is four squarings");
+    static_assert(SCAN_CH == 16, "b^CH below is four squarings");
 #pragma unroll
     for (int q = 0; q < 4; q++) r = fe_sqr<Fr>(r);              // b^16 (products of values < 2p stay < 2p)
     uint32_t w[8];
@@ -288,24 +254,34 @@ __global__ void k_store_const(fe_arg v, fe_arg* __restrict__ out, uint32_t level
     for (int i = 0; i < 8; i++) out[l].w[i] = w[i];
   }
 }
-static int store_const(const uint32_t host[8], fe_arg* d, hipStream_t stream, uint32_t levels = 0) {
+// d[k] = host^(CH^k) for every level k of the plan: level k is scanned with the multiplier d[k].  ONE thread computes them up front (a launch
+// per level for one power each cost 11 us apiece in the dependent chain)
+static int store_const(const uint32_t host[8], fe_arg* d, hipStream_t stream, const scan_plan& plan) {
   fe_arg v;
   memcpy(v.w, host, 32);
-  hipLaunchKernelGGL(k_store_const, dim3(1), dim3(64), 0, stream, v, d, levels);
+  hipLaunchKernelGGL(k_store_const, dim3(1), dim3(64), 0, stream, v, d, (uint32_t)(plan.L < POW_LEVELS ? plan.L : POW_LEVELS));
   HIPCHK(hipGetLastError());
   return ZKHIP_OK;
 }
-// recursion levels below the top one of a scan over n elements (= how many powers of the multiplier it needs)
-static uint32_t scan_levels(size_t n) {
-  uint32_t levels = 0;
-  while (n > POLY_CH) { n = (n + POLY_CH - 1) / POLY_CH; levels++; }
-  return levels < POW_LEVELS ? levels : POW_LEVELS;
-}
-// the multiplier of a scan over n elements and its powers: parked in the last 256 bytes of the workspace
-static int stage_const(const uint32_t host[8], size_t n, char* ws, size_t ws_bytes, hipStream_t stream, fe_arg** out) {
-  fe_arg* d = (fe_arg*)(ws + ws_bytes - 256);
+// the same, parked in the last 256 bytes of the workspace
+static int stage_const(const uint32_t host[8], const scan_plan& plan, void* ws, size_t ws_bytes, hipStream_t stream, const fe_arg** out) {
+  fe_arg* d = (fe_arg*)((char*)ws + ws_bytes - 256);
   *out = d;
-  return store_const(host, d, stream, scan_levels(n));
+  return store_const(host, d, stream, plan);
+}
+
+// the evaluations of `count` polynomials of plan.n[0] coefficients: up through the levels and one step further, where the single aggregate of
+// every polynomial is its evaluation.  Level 0 is read through the pointer table d_ptrs; without one it is the single dense array d_a.
+static int horner_eval(const uint32_t* const* d_ptrs, const uint32_t* d_a, size_t count, const scan_plan& plan, const fe_arg* b, uint32_t* d_results,
+                       void* ws, hipStream_t stream) {
+  for (int k = 1; k <= plan.L + 1; k++) {
+    const uint32_t* src = k == 1 ? d_a : plan.level<const uint32_t>(ws, k - 1);
+    uint32_t* agg = k <= plan.L ? plan.level<uint32_t>(ws, k) : d_results;
+    if (d_ptrs) hipLaunchKernelGGL(k_horner_agg_batch, grid_for(plan.n[k], 256, count), dim3(256), 0, stream, k == 1 ? d_ptrs : nullptr, src, plan.n[k - 1], b + (k - 1), agg, plan.n[k]);
+    else hipLaunchKernelGGL(k_horner_agg, grid_for(plan.n[k], 256), dim3(256), 0, stream, src, plan.n[k - 1], b + (k - 1), agg);
+  }
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
 }
 
 // eval_polynomial: result (8 words, device) = sum a[i] x^i
@@ -313,61 +289,51 @@ int fr_eval_polynomial_device(const uint32_t* d_a, size_t n, const uint32_t x_ho
                               hipStream_t stream) {
   if (n == 0) { HIPCHK(hipMemsetAsync(d_result, 0, 32, stream)); return ZKHIP_OK; }
   if (ws_bytes < poly_workspace_bytes(n)) { set_error("eval_polynomial: workspace too small"); return ZKHIP_EINVAL; }
-  fe_arg* b = nullptr;
-  int rc = stage_const(x_host, n, (char*)ws, ws_bytes, stream, &b);
+  const scan_plan plan(n, 32);
+  const fe_arg* b = nullptr;
+  int rc = stage_const(x_host, plan, ws, ws_bytes, stream, &b);
   if (rc != ZKHIP_OK) return rc;
-  return horner_scan(d_a, n, b, nullptr, 0, d_result, (char*)ws, stream);
+  return horner_eval(nullptr, d_a, 1, plan, b, d_result, ws, stream);
 }
 
-// `count` polynomials of n coefficients each, all evaluated at x: d_results[p] = sum_i poly_p[i] x^i.  One launch per recursion
-// level for the whole batch (ceil(log_16 n) levels) instead of one recursion per polynomial.
-size_t poly_batch_workspace_bytes(size_t n, size_t count) {
-  size_t total = 8192 + ((count * 8 + 255) / 256) * 256, m = n;
-  while (m > 1) { m = chunks_of(m); total += ((count * m * 32 + 255) / 256) * 256 + 256; }
-  return total;
-}
-
+// `count` polynomials of n coefficients each, all evaluated at x: d_results[p] = sum_i poly_p[i] x^i.  One launch per level for the whole
+// batch (ceil(log_16 n) levels) instead of one scan per polynomial.  Workspace: [pointer table][256: the multipliers][levels]
 int fr_eval_polynomial_batch_device(const void* const* d_polys_host, size_t count, size_t n, const uint32_t x_host[8], uint32_t* d_results,
                                     void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring) {
   if (count == 0) return ZKHIP_OK;
   if (n == 0) { HIPCHK(hipMemsetAsync(d_results, 0, count * 32, stream)); return ZKHIP_OK; }
   if (count > 65535) { set_error("eval_polynomial_batch: more than 65535 polynomials"); return ZKHIP_EINVAL; }
   if (ws_bytes < poly_batch_workspace_bytes(n, count)) { set_error("eval_polynomial_batch: workspace too small"); return ZKHIP_EINVAL; }
+  const scan_plan plan(n, 32 * count);
   char* p = (char*)ws;
   const uint32_t** d_ptrs = (const uint32_t**)p;
-  p += ((count * 8 + 255) / 256) * 256;
+  p += scan_align(count * 8);
   fe_arg* b = (fe_arg*)p;
   p += 256;
   int rc = upload_args(ring, d_ptrs, d_polys_host, count * 8, stream);        // caller memory: through the pinned ring, no wait for the stream
-  if (rc == ZKHIP_OK) rc = store_const(x_host, b, stream, scan_levels(n));   // b, b^CH, b^(CH^2), ...: the multiplier of every level, one thread, once
+  if (rc == ZKHIP_OK) rc = store_const(x_host, b, stream, plan);
   if (rc != ZKHIP_OK) return rc;
-  const uint32_t* cur = nullptr;                            // level 0 reads through d_ptrs
-  size_t cur_n = n;
-  while (true) {
-    const size_t m = chunks_of(cur_n);
-    uint32_t* agg = m == 1 ? d_results : (uint32_t*)p;      // the last level's single aggregate per polynomial is the evaluation
-    hipLaunchKernelGGL(k_horner_agg_batch, dim3((unsigned)((m + 255) / 256), (unsigned)count), dim3(256), 0, stream,
-                       cur ? (const uint32_t* const*)nullptr : (const uint32_t* const*)d_ptrs, cur, cur_n, (const fe_arg*)b, agg, m);
-    if (m == 1) break;
-    p += ((count * m * 32 + 255) / 256) * 256 + 256;
-    b = b + 1;
-    cur = agg;
-    cur_n = m;
-  }
-  HIPCHK(hipGetLastError());
-  return ZKHIP_OK;
+  return horner_eval(d_ptrs, nullptr, count, plan, b, d_results, p, stream);
 }
 
-// kate_division: q[i] = a[i+1] + b q[i+1], i < n-1  (quotient of a(X) by (X - b), remainder dropped)
+// kate_division: q[i] = a[i+1] + b q[i+1], i < n-1  (quotient of a(X) by (X - b), remainder dropped).  The suffix Horner scan
+// s[i] = sum_{j >= i} a[j] b^(j-i) at index i+1 is q[i]: scan everything, drop index 0
 int fr_kate_division_device(const uint32_t* d_a, size_t n, const uint32_t b_host[8], uint32_t* d_q, void* ws, size_t ws_bytes,
                             hipStream_t stream) {
   if (n < 2) return ZKHIP_OK;
   if (ws_bytes < poly_workspace_bytes(n)) { set_error("kate_division: workspace too small"); return ZKHIP_EINVAL; }
-  fe_arg* b = nullptr;
-  int rc = stage_const(b_host, n, (char*)ws, ws_bytes, stream, &b);
+  const scan_plan plan(n, 32);
+  const fe_arg* b = nullptr;
+  int rc = stage_const(b_host, plan, ws, ws_bytes, stream, &b);
   if (rc != ZKHIP_OK) return rc;
-  // the suffix Horner scan of a at index i+1 is q[i]: scan everything, drop index 0
-  return horner_scan(d_a, n, b, d_q, 1, nullptr, (char*)ws, stream);
+  auto level = [&](int k) { return plan.level<uint32_t>(ws, k); };
+  for (int k = 1; k <= plan.L; k++)
+    hipLaunchKernelGGL(k_horner_agg, grid_for(plan.n[k], 256), dim3(256), 0, stream, k == 1 ? d_a : (const uint32_t*)level(k - 1), plan.n[k - 1], b + (k - 1), level(k));
+  for (int k = plan.L; k >= 0; k--)
+    hipLaunchKernelGGL(k_horner_apply, grid_for(plan.n[k + 1], 256), dim3(256), 0, stream, k ? (const uint32_t*)level(k) : d_a, plan.n[k], b + k,
+                       k < plan.L ? (const uint32_t*)level(k + 1) : (const uint32_t*)nullptr, plan.n[k + 1], k ? level(k) : d_q, (size_t)(k ? 0 : 1));
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
 }
 
 // ---- division by the vanishing polynomial of a point set (multi-open: `div_by_vanishing`) ---------------------------------------
@@ -398,9 +364,9 @@ __device__ __forceinline__ fe fe_from_limbs(const uint32_t (&l)[NL]) {
 template <int M>
 __global__ void __launch_bounds__(256) k_roots_agg(const uint32_t* __restrict__ a, size_t n, const roots_k zk, uint32_t* __restrict__ agg, size_t stride) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t lo = t * POLY_CH;
+  const size_t lo = t * SCAN_CH;
   if (lo >= n) return;
-  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  const size_t hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   fe q[M];
 #pragma unroll
   for (int r = 0; r < M; r++) q[r] = fe_zero();
@@ -421,9 +387,9 @@ __global__ void __launch_bounds__(256) k_roots_agg(const uint32_t* __restrict__ 
 // the recursion levels: blockIdx.y = root, dense [m][n] arrays, the level's multipliers z_i^(CH^level) in zk
 __global__ void __launch_bounds__(256) k_roots_agg_level(const uint32_t* __restrict__ base, size_t n, const roots_k zk, uint32_t* __restrict__ agg, size_t m) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t lo = t * POLY_CH;
+  const size_t lo = t * SCAN_CH;
   if (lo >= n) return;
-  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  const size_t hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   const uint32_t* a = base + (size_t)blockIdx.y * n * 8;
   const fe b = fe_from_limbs(zk.l[blockIdx.y]);
   fe q = fe_zero();
@@ -433,9 +399,9 @@ __global__ void __launch_bounds__(256) k_roots_agg_level(const uint32_t* __restr
 // in place: arr[i] <- arr[i] + b * arr[i + 1] (suffix scan) with carry-in carry[t + 1]; a thread reads and writes its own chunk only, top down
 __global__ void __launch_bounds__(256) k_roots_apply_level(uint32_t* base, size_t n, const roots_k zk, const uint32_t* carry_base, size_t ncarry) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t lo = t * POLY_CH;
+  const size_t lo = t * SCAN_CH;
   if (lo >= n) return;
-  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  const size_t hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   uint32_t* a = base + (size_t)blockIdx.y * n * 8;
   const fe b = fe_from_limbs(zk.l[blockIdx.y]);
   fe q = (carry_base != nullptr && t + 1 < ncarry) ? load_ext(carry_base + (size_t)blockIdx.y * ncarry * 8, t + 1) : fe_zero();
@@ -454,9 +420,9 @@ template <int M>
 __global__ void __launch_bounds__(256) k_roots_div(const uint32_t* __restrict__ a, size_t n, const roots_div_k k, const uint32_t* __restrict__ carry,
                                                    size_t ncarry, uint32_t* __restrict__ out, uint32_t* __restrict__ evals) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t lo = t * POLY_CH;
+  const size_t lo = t * SCAN_CH;
   if (lo >= n) return;
-  const size_t hi = lo + POLY_CH < n ? lo + POLY_CH : n;
+  const size_t hi = lo + SCAN_CH < n ? lo + SCAN_CH : n;
   fe r[M];
 #pragma unroll
   for (int j = 0; j < M; j++) r[j] = fe_zero();
@@ -533,21 +499,11 @@ static fe h_inverse(const fe& a) {                            // a^(r - 2): the 
 }
 static void h_store(const fe& a, uint32_t (&l)[NL]) { for (int i = 0; i < NL; i++) l[i] = a.l[i]; }
 
-size_t poly_roots_workspace_bytes(size_t n, uint32_t m) {     // the m aggregate arrays of every level
-  size_t total = 256, c = n;
-  while (c > 1) { c = chunks_of(c); total += (((size_t)m * c * 32 + 255) / 256) * 256; }
-  const size_t single = poly_workspace_bytes(n);              // m = 1 without evaluations runs kate_division's kernels
-  return total > single ? total : single;
-}
-
-template <int M>
-static void launch_roots_agg(const uint32_t* d_a, size_t n, const roots_k& zk, uint32_t* agg, size_t stride, hipStream_t stream) {
-  hipLaunchKernelGGL(k_roots_agg<M>, grid_for(chunks_of(n), 256), dim3(256), 0, stream, d_a, n, zk, agg, stride);
-}
-template <int M>
-static void launch_roots_div(const uint32_t* d_a, size_t n, const roots_div_k& k, const uint32_t* carry, size_t ncarry, uint32_t* d_q, uint32_t* d_evals,
-                             hipStream_t stream) {
-  hipLaunchKernelGGL(k_roots_div<M>, grid_for(chunks_of(n), 256), dim3(256), 0, stream, d_a, n, k, carry, ncarry, d_q, d_evals);
+// f(std::integral_constant<int, M>) for the run-time root count m in 1 .. ZKHIP_MAX_ROOTS: the kernels take it as a template argument
+template <int M = 1, class F>
+static void with_root_count(uint32_t m, F&& f) {
+  if (m == M) f(std::integral_constant<int, M>{});
+  else if constexpr (M < ZKHIP_MAX_ROOTS) with_root_count<M + 1>(m, f);
 }
 
 int fr_divide_by_roots_device(const uint32_t* d_a, size_t n, const uint32_t (*roots_host)[8], uint32_t m, uint32_t* d_q, uint32_t* d_evals, void* ws,
@@ -600,102 +556,52 @@ int fr_divide_by_roots_device(const uint32_t* d_a, size_t n, const uint32_t (*ro
   memset(&zk, 0, sizeof zk);
   for (uint32_t i = 0; i < m; i++) h_store(z[i], zk.l[i]);
   auto next_level = [&]() {                                   // z_i <- z_i^CH
-    static_assert(POLY_CH == 16, "z^CH below is four squarings");
+    static_assert(SCAN_CH == 16, "z^CH below is four squarings");
     for (uint32_t i = 0; i < m; i++) { for (int s = 0; s < 4; s++) z[i] = h_mul(z[i], z[i]); h_store(z[i], zk.l[i]); }
   };
 
-  const size_t n1 = chunks_of(n);
-  uint32_t* level[16];
-  size_t level_n[16];
-  int levels = 0;
-  if (n1 == 1) {                                              // one chunk: no carries; the aggregates are the evaluations
-    if (d_evals) {
-      switch (m) {
-        case 1: launch_roots_agg<1>(d_a, n, zk, d_evals, 1, stream); break;
-        case 2: launch_roots_agg<2>(d_a, n, zk, d_evals, 1, stream); break;
-        case 3: launch_roots_agg<3>(d_a, n, zk, d_evals, 1, stream); break;
-        case 4: launch_roots_agg<4>(d_a, n, zk, d_evals, 1, stream); break;
-        case 5: launch_roots_agg<5>(d_a, n, zk, d_evals, 1, stream); break;
-        case 6: launch_roots_agg<6>(d_a, n, zk, d_evals, 1, stream); break;
-        case 7: launch_roots_agg<7>(d_a, n, zk, d_evals, 1, stream); break;
-        default: launch_roots_agg<8>(d_a, n, zk, d_evals, 1, stream); break;
-      }
-    }
-  } else {
-    char* p = (char*)ws;
-    level[0] = (uint32_t*)p;
-    level_n[0] = n1;
-    levels = 1;
-    switch (m) {
-      case 1: launch_roots_agg<1>(d_a, n, zk, level[0], n1, stream); break;
-      case 2: launch_roots_agg<2>(d_a, n, zk, level[0], n1, stream); break;
-      case 3: launch_roots_agg<3>(d_a, n, zk, level[0], n1, stream); break;
-      case 4: launch_roots_agg<4>(d_a, n, zk, level[0], n1, stream); break;
-      case 5: launch_roots_agg<5>(d_a, n, zk, level[0], n1, stream); break;
-      case 6: launch_roots_agg<6>(d_a, n, zk, level[0], n1, stream); break;
-      case 7: launch_roots_agg<7>(d_a, n, zk, level[0], n1, stream); break;
-      default: launch_roots_agg<8>(d_a, n, zk, level[0], n1, stream); break;
-    }
-    roots_k zks[16];                                          // the multipliers of level l: z^(CH^(l + 1))
-    while (true) {
-      next_level();
-      zks[levels - 1] = zk;
-      const size_t cn = level_n[levels - 1];
-      if (cn <= POLY_CH) break;
-      p += (((size_t)m * cn * 32 + 255) / 256) * 256;
-      const size_t nn = chunks_of(cn);
-      level[levels] = (uint32_t*)p;
-      level_n[levels] = nn;
-      hipLaunchKernelGGL(k_roots_agg_level, dim3((unsigned)((nn + 255) / 256), m), dim3(256), 0, stream, (const uint32_t*)level[levels - 1], cn, zk, level[levels], nn);
-      levels++;
-    }
-    for (int l = levels - 1; l >= 0; l--) {                   // down: scan every level in place with the scanned level above as carries
-      const size_t cn = level_n[l];
-      const uint32_t* carry = l + 1 < levels ? level[l + 1] : nullptr;
-      hipLaunchKernelGGL(k_roots_apply_level, dim3((unsigned)((chunks_of(cn) + 255) / 256), m), dim3(256), 0, stream, level[l], cn, zks[l], carry,
-                         l + 1 < levels ? level_n[l + 1] : (size_t)0);
-    }
+  const scan_plan plan(n, 32 * (size_t)m);
+  auto level = [&](int k) { return plan.level<uint32_t>(ws, k); };
+  const uint32_t* carry = plan.L ? level(1) : nullptr;
+  // up.  Level 1 (with one chunk and no carries: the evaluations themselves) takes all m aggregates from one load of a chunk
+  if (plan.L || d_evals)
+    with_root_count(m, [&](auto M) {
+      hipLaunchKernelGGL(k_roots_agg<M>, grid_for(plan.n[1], 256), dim3(256), 0, stream, d_a, n, zk, plan.L ? level(1) : d_evals, plan.n[1]);
+    });
+  roots_k zks[SCAN_MAX_LEVELS + 1];                           // the multipliers of level k: z^(CH^k)
+  for (int k = 1; k <= plan.L; k++) {
+    next_level();
+    zks[k] = zk;
+    if (k < plan.L) hipLaunchKernelGGL(k_roots_agg_level, grid_for(plan.n[k + 1], 256, m), dim3(256), 0, stream, (const uint32_t*)level(k), plan.n[k], zk, level(k + 1), plan.n[k + 1]);
   }
-  const uint32_t* carry = levels ? level[0] : nullptr;
-  switch (m) {
-    case 1: launch_roots_div<1>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
-    case 2: launch_roots_div<2>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
-    case 3: launch_roots_div<3>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
-    case 4: launch_roots_div<4>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
-    case 5: launch_roots_div<5>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
-    case 6: launch_roots_div<6>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
-    case 7: launch_roots_div<7>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
-    default: launch_roots_div<8>(d_a, n, dk, carry, n1, d_q, d_evals, stream); break;
-  }
+  for (int k = plan.L; k >= 1; k--)                           // down: every level in place with the scanned level above as carries
+    hipLaunchKernelGGL(k_roots_apply_level, grid_for(plan.n[k + 1], 256, m), dim3(256), 0, stream, level(k), plan.n[k], zks[k],
+                       k < plan.L ? (const uint32_t*)level(k + 1) : (const uint32_t*)nullptr, plan.n[k + 1]);
+  with_root_count(m, [&](auto M) {
+    hipLaunchKernelGGL(k_roots_div<M>, grid_for(plan.n[1], 256), dim3(256), 0, stream, d_a, n, dk, carry, plan.n[1], d_q, d_evals);
+  });
   HIPCHK(hipGetLastError());
   return ZKHIP_OK;
 }
 
-static int prefix_product_rec(const uint32_t* d_v, size_t n, const uint32_t* carry, uint32_t* d_out, char* ws, hipStream_t stream);
+// exclusive prefix products of `batch` dense arrays of n elements each: out[b][0] = 1.  d_out may be d_v: each lane reads before it writes
+static int prefix_product_batch(const uint32_t* d_v, uint32_t* d_out, size_t n, uint32_t batch, void* ws, hipStream_t stream) {
+  const scan_plan plan(n, 32 * (size_t)batch);
+  auto level = [&](int k) { return plan.level<uint32_t>(ws, k); };
+  for (int k = 1; k <= plan.L; k++)                            // up: the chunk products of every level
+    hipLaunchKernelGGL(k_prod_agg_batch, grid_for(plan.n[k], 256, batch), dim3(256), 0, stream, k == 1 ? d_v : (const uint32_t*)level(k - 1), plan.n[k - 1], level(k), plan.n[k]);
+  for (int k = plan.L; k >= 0; k--)                            // down: every level in place, with the scanned level above as carries
+    hipLaunchKernelGGL(k_prod_apply_batch, grid_for(plan.n[k + 1], 256, batch), dim3(256), 0, stream, k ? (const uint32_t*)level(k) : d_v, plan.n[k],
+                       k < plan.L ? (const uint32_t*)level(k + 1) : (const uint32_t*)nullptr, plan.n[k + 1], k ? level(k) : d_out);
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
+}
 
 // exclusive prefix product: out[0] = 1, out[i] = v[0] ... v[i-1]   (out may alias v)
 int fr_prefix_product_device(const uint32_t* d_v, size_t n, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (n == 0) return ZKHIP_OK;
   if (ws_bytes < poly_workspace_bytes(n)) { set_error("prefix_product: workspace too small"); return ZKHIP_EINVAL; }
-  return prefix_product_rec(d_v, n, nullptr, d_out, (char*)ws, stream);
-}
-
-static int prefix_product_rec(const uint32_t* d_v, size_t n, const uint32_t* carry_unused, uint32_t* d_out, char* ws, hipStream_t stream) {
-  (void)carry_unused;
-  if (n <= POLY_CH) {
-    hipLaunchKernelGGL(k_prod_apply, dim3(1), dim3(256), 0, stream, d_v, n, (const uint32_t*)nullptr, d_out);
-    HIPCHK(hipGetLastError());
-    return ZKHIP_OK;
-  }
-  const size_t m = chunks_of(n);
-  uint32_t* agg = (uint32_t*)ws;
-  char* next_ws = ws + ((m * 32 + 255) / 256) * 256 + 256;
-  hipLaunchKernelGGL(k_prod_agg, grid_for(m, 256), dim3(256), 0, stream, d_v, n, agg);
-  int rc = prefix_product_rec(agg, m, nullptr, agg, next_ws, stream);   // exclusive prefix products of the chunk products, in place
-  if (rc != ZKHIP_OK) return rc;
-  hipLaunchKernelGGL(k_prod_apply, grid_for(m, 256), dim3(256), 0, stream, d_v, n, (const uint32_t*)agg, d_out);
-  HIPCHK(hipGetLastError());
-  return ZKHIP_OK;
+  return prefix_product_batch(d_v, d_out, n, 1, ws, stream);
 }
 
 // ---- permutation argument: every set's grand product in one call ----------------------------------------------------------------
@@ -765,13 +671,6 @@ __global__ void __launch_bounds__(256) k_perm_num_mul(const uint32_t* const* __r
     acc = j == 0 ? t : fe_mul<Fr>(fe_norm(acc), t);                                              // 36 * 36 / 169 + 1 < 9p, then < 3p, < 2p: N
   }
   store_canon(zs, i, fe_mul<Fr>(load_ext(zs, i), fe_norm(acc)));                                 // external (1 / den) x internal: external, < 2p
-}
-
-size_t perm_workspace_bytes(uint32_t nperm, uint32_t chunk, uint32_t log_n) {
-  const size_t n = (size_t)1 << log_n, nsets = chunk ? (nperm + chunk - 1) / chunk : 0;
-  const uint32_t h = (log_n + 1) / 2;
-  const size_t tables = (((size_t)nperm * 16 + 255) / 256) * 256 + (((size_t)nperm * 32 + 255) / 256) * 256 + (((size_t)1 << h) + (n >> h)) * 32 + 768;
-  return tables + poly_workspace_bytes(nsets * n);
 }
 
 int fr_permutation_products_device(const void* const* d_values_host, const void* const* d_sigmas_host, uint32_t nperm, uint32_t chunk, uint32_t log_n,
@@ -862,41 +761,6 @@ __global__ void __launch_bounds__(256) k_lookup_num_mul(const uint32_t* const* _
   store_canon(zl, i, fe_mul<Fr>(load_ext(zl, i), fe_norm(num)));                      // external (1 / den) x internal: external
 }
 
-static size_t prefix_product_batch_workspace_bytes(size_t n, size_t batch) {
-  size_t total = 256, m = n;
-  while (m > POLY_CH) { m = chunks_of(m); total += ((batch * m * 32 + 255) / 256) * 256; }
-  return total;
-}
-
-// exclusive prefix products of `batch` dense arrays of n elements each, in place: out[b][0] = 1
-static int prefix_product_batch(uint32_t* d_v, size_t n, uint32_t batch, char* ws, hipStream_t stream) {
-  uint32_t* level[16];
-  size_t level_n[16];
-  int levels = 1;
-  level[0] = d_v;
-  level_n[0] = n;
-  while (level_n[levels - 1] > POLY_CH) {                      // up: the chunk products of every level
-    const size_t cn = level_n[levels - 1], m = chunks_of(cn);
-    level[levels] = (uint32_t*)ws;
-    level_n[levels] = m;
-    ws += (((size_t)batch * m * 32 + 255) / 256) * 256;
-    hipLaunchKernelGGL(k_prod_agg_batch, dim3((unsigned)((m + 255) / 256), batch), dim3(256), 0, stream, (const uint32_t*)level[levels - 1], cn, level[levels], m);
-    levels++;
-  }
-  for (int l = levels - 1; l >= 0; l--) {                      // down: every level in place, with the scanned level above as carries
-    const size_t cn = level_n[l], m = chunks_of(cn);
-    hipLaunchKernelGGL(k_prod_apply_batch, dim3((unsigned)((m + 255) / 256), batch), dim3(256), 0, stream, (const uint32_t*)level[l], cn,
-                       l + 1 < levels ? (const uint32_t*)level[l + 1] : (const uint32_t*)nullptr, m, level[l]);
-  }
-  HIPCHK(hipGetLastError());
-  return ZKHIP_OK;
-}
-
-size_t lookup_products_workspace_bytes(uint32_t n_lookups, uint32_t log_n) {
-  const size_t n = (size_t)1 << log_n;
-  return (((size_t)n_lookups * 16 + 255) / 256) * 256 + prefix_product_batch_workspace_bytes(n, n_lookups) + poly_workspace_bytes((size_t)n_lookups * n);
-}
-
 int fr_lookup_products_device(const void* const* d_inputs_host, const void* const* d_tables_host, const uint32_t* d_permuted_inputs, const uint32_t* d_permuted_tables,
                               uint32_t n_lookups, uint32_t log_n, size_t usable, const uint32_t beta[8], const uint32_t gamma[8], uint32_t* d_z, void* ws,
                               size_t ws_bytes, hipStream_t stream, arg_ring* ring) {
@@ -921,7 +785,7 @@ int fr_lookup_products_device(const void* const* d_inputs_host, const void* cons
   if (usable) hipLaunchKernelGGL(k_lookup_num_mul, dim3((unsigned)((usable + 255) / 256), n_lookups), dim3(256), 0, stream, (const uint32_t* const*)d_ptrs, n_lookups, n,
                                  usable, b, g, d_z);
   HIPCHK(hipGetLastError());
-  return prefix_product_batch(d_z, n, n_lookups, p, stream);
+  return prefix_product_batch(d_z, d_z, n, n_lookups, p, stream);
 }
 
 // ---- linear combination of many columns: out[i] = sum_j c_j col_j[i] -------------------------------------------------------------------

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstring>
 #include "../../include/zkhip.h"
+#include "scan_plan.hpp"      // defines the *_workspace_bytes of the chunked scans declared below (inline, host-only)
 
 namespace zkhip {
 

@@ -747,6 +747,58 @@ int zkhip_paillier_tally_device(const uint64_t n[3], const void *d_ballots, size
  * the plain left-to-right ladder.  d_out must not overlap d_m or d_r. */
 int zkhip_paillier_encrypt_device(const uint64_t n[3], const uint64_t g[6], const void *d_m, const void *d_r, size_t count, void *d_out, void *stream);
 
+/* ---- PLUME nullifiers on secp256k1: a batch of nullifiers verified in one device call ----
+ * [DEP k256 `hash_from_bytes::<ExpandMsgXmd<Sha256>>`, halo2curves secp256k1; the reference: `verify_nullifier`, `compress_point`, `hash_to_curve`
+ * and `gen_test_nullifier`, voter_tests/src/lib.rs:25-119, called for every round by `generate_wrapper_circuit_input`,
+ * aggregator/src/utils.rs:289-290.]  The crates are not vendored with the reference and could not be built: parity with `k256` / `plume-halo2` is
+ * pinned by the two RFC 9380 vectors below and no further; the PLUME vector pins the next restatement against this one.
+ * THE DEFINITION (normative).
+ *   Curve     secp256k1: y^2 = x^3 + 7 over p = 2^256 - 2^32 - 977, group order
+ *             n = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141, generator G as in SEC 2.
+ *   compress(P) = the 33 bytes 02|03 || x big-endian, 03 for an odd y (`compress_point`).  The identity is the affine pair (0, 0), as
+ *             halo2curves' `to_affine` gives it, and so compresses to 02 || 00..00 (restated, not pinned).
+ *   H(msg, pk) = hash_to_curve(msg || compress(pk)) of RFC 9380, suite secp256k1_XMD:SHA-256_SSWU_RO_, with the DST
+ *             "QUUX-V01-CS02-with-secp256k1_XMD:SHA-256_SSWU_RO_": expand_message_xmd to 96 bytes, two 48-byte big-endian values mod p,
+ *             simplified SWU on E': y^2 = x^3 + A'x + B' with Z = -11 (the exceptional cases of section 6.6.2 included), the 3-isogeny to
+ *             secp256k1 (a zero denominator gives the identity), the sum of the two images.  A', B' and the isogeny's coefficients are those
+ *             of RFC 9380 section 8.7 and appendix E.1 (csrc/secp256k1_h2c.hpp).
+ *   pinned    (RFC 9380 J.8.1) hash_to_curve(""):    x = 0xc1cae290e291aee617ebaef1be6d73861479c48b841eaba9b7b5852ddfeb1346
+ *                                                    y = 0x64fa678e07ae116126f08b022a94af6de15985c996c3a91b64c406a960e51067
+ *                              hash_to_curve("abc"): x = 0x3377e01eab42db296b512293120c6cee72b6ecf9f9205760bd9ff11fb3cb2c4b
+ *                                                    y = 0x7f95890f33efebd1044d382a01b1bee0900fb6116f94688d487c6c7b9c8371f6
+ *   verify(msg, N, pk, s, c) (`verify_nullifier`), with H = H(msg, pk):  A = s G - c pk,  B = s H - c N,
+ *             d = SHA-256(compress(G) || compress(pk) || compress(H) || compress(N) || compress(A) || compress(B))   (198 bytes);
+ *             accept iff the big-endian integer of d equals c.  d is not reduced: the reference's `from_bytes_le` panics on a digest >= n, and
+ *             here such a digest never equals a c < n.
+ *   verdict   0 accepted; 1 well-formed but d != c; 2 malformed: a coordinate >= p, a point off the curve (the pair (0, 0) included), or s or
+ *             c >= n.  A malformed voter is a verdict, never a failed call.
+ *   pinned    msg = 01 00, sk = SHA-256("sk") mod n, r = SHA-256("r") mod n, `gen_test_nullifier` with that r:
+ *             pk = (0x020f475341bdcaa86307f6bc73482e9f97de1eb143c4d377882338e41bd3816c, 0xd9b0bc73ac2ef11aa0d9c7e597a2247fae84397fbcf7c5545ca569c392a43d9d)
+ *             H  = (0xfc8ad938310804a146d15e27c45dd085890d059a4fe75efb792557945cd4e555, 0x5dff9477353e60cd4f45ced0dadf3646df67bc09aacc29b645ff2338763b8509)
+ *             N  = (0x022e80224208f61d2bd0db01ee45f1ad280afed208073f8cadfea796b62ec66e, 0xeb2167a30ea8a02d40c3a86c93961b7f02664aac622d11d34b9f120eed108c73)
+ *             s  = 0x2dd6d3be74b08a383e981dac34dda120b5f0d32f9a1e245ab034d00b4d1149a3, c = 0x31c5e6a7886d3802ee2e0bc16993e6dda5f9992597c67ee4bfb5acba7bf07535
+ *             verify -> 0; with c + 1 -> 1; with msg = 02 00 -> 1.
+ * Formats: a point is 8 little-endian 64-bit words, x then y, each the canonical integer (NOT Montgomery); a scalar is 4 words.  A verdict or
+ * status is a uint32.  msg is on the HOST, read before the call returns, at most ZKHIP_PLUME_MAX_MSG bytes, and shared by the batch (the proposal).
+ * The `_device` calls are asynchronous on `stream` with no host wait; at most 2^30 elements per call.
+ * ZKHIP_EINVAL, nothing enqueued (decided on the host before the device is touched): a null pointer where none is allowed (msg may be null when
+ * msg_len is 0; d_h_out may be null; every array may be null when count is 0, d_report never), msg_len > ZKHIP_PLUME_MAX_MSG, a pointer that is
+ * not 8-byte aligned, an output that overlaps an input or another output.  count == 0 succeeds; the verify call then writes only a zeroed report.
+ * Not built: a fixed-base table for G, batch verification by a random linear combination, signing on the device, sharding over devices,
+ * PLUME v2. */
+#define ZKHIP_PLUME_MAX_MSG 64
+/* d_out[i] = a[i] P[i] + b[i] Q[i], affine, identity as (0, 0); scalars are any 256-bit integers; a malformed P or Q gives status 2 and (0, 0) */
+int zkhip_secp256k1_lincomb_device(const void *d_a, const void *d_p, const void *d_b, const void *d_q, size_t count, void *d_out, void *d_status, void *stream);
+/* d_out[i] = H(msg, pk[i]); msg on the host, shared by the batch (the proposal); a malformed pk gives status 2 and (0, 0) */
+int zkhip_secp256k1_hash_to_curve_device(const uint8_t *msg, size_t msg_len, const void *d_pk, size_t count, void *d_out, void *d_status, void *stream);
+/* d_status[i] (uint32) = the verdict above; d_report: one zkhip_check_report -- voters with a non-zero verdict, lowest such index; d_h_out optional
+ * (NULL or count points): H of every voter, (0, 0) where pk is malformed.  Two lanes per voter (csrc/plume.hip). */
+int zkhip_plume_verify_device(const uint8_t *msg, size_t msg_len, const void *d_pk, const void *d_nullifier, const void *d_s, const void *d_c, size_t count, void *d_status, void *d_report, void *d_h_out, void *stream);
+/* The same for one voter on the host, over the same headers; no GPU is touched.  out = H(msg, pk) and *status 0, or (0, 0) and 2 for a malformed pk. */
+int zkhip_secp256k1_hash_to_curve(const uint8_t *msg, size_t msg_len, const uint64_t pk[8], uint64_t out[8], uint32_t *status);
+/* *verdict as above; h_out optional: H(msg, pk), (0, 0) where pk is malformed */
+int zkhip_plume_verify(const uint8_t *msg, size_t msg_len, const uint64_t pk[8], const uint64_t nullifier[8], const uint64_t s[4], const uint64_t c[4], uint32_t *verdict, uint64_t h_out[8]);
+
 /* ---- parity hooks for the field / curve layer (rows a1/a2 of SURVEY.md section 8) ------------------ */
 /* field: 0 = Fq, 1 = Fr.  op: 0 mul, 1 add, 2 sub, 3 square (b ignored).  Elementwise on n elements. */
 int zkhip_test_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);

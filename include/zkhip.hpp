@@ -470,6 +470,36 @@ struct Paillier {
   }
 };
 
+// The PLUME nullifier check over arrays in HBM (zkhip.h, "PLUME nullifiers on secp256k1"): points are 8 and scalars 4 canonical little-endian
+// words; `msg` is on the host and shared by the batch; every `_device` call is asynchronous on `stream`.
+struct Plume {
+  // d_out[i] = a[i] P[i] + b[i] Q[i]; d_status[i] = 2 and (0, 0) for a malformed point
+  static void lincomb_device(const void* d_a, const void* d_p, const void* d_b, const void* d_q, size_t count, void* d_out, void* d_status, void* stream = nullptr) {
+    check(zkhip_secp256k1_lincomb_device(d_a, d_p, d_b, d_q, count, d_out, d_status, stream), "Plume::lincomb_device");
+  }
+  // d_out[i] = H(msg, pk[i])
+  static void hash_to_curve_device(const uint8_t* msg, size_t msg_len, const void* d_pk, size_t count, void* d_out, void* d_status, void* stream = nullptr) {
+    check(zkhip_secp256k1_hash_to_curve_device(msg, msg_len, d_pk, count, d_out, d_status, stream), "Plume::hash_to_curve_device");
+  }
+  // d_status[i]: 0 accepted, 1 refused, 2 malformed; d_report: one zkhip_check_report; d_h_out null or count points
+  static void verify_device(const uint8_t* msg, size_t msg_len, const void* d_pk, const void* d_nullifier, const void* d_s, const void* d_c, size_t count, void* d_status,
+                            void* d_report, void* d_h_out = nullptr, void* stream = nullptr) {
+    check(zkhip_plume_verify_device(msg, msg_len, d_pk, d_nullifier, d_s, d_c, count, d_status, d_report, d_h_out, stream), "Plume::verify_device");
+  }
+  // one voter on the host
+  static uint32_t hash_to_curve(const uint8_t* msg, size_t msg_len, const uint64_t pk[8], uint64_t out[8]) {
+    uint32_t status = 0;
+    check(zkhip_secp256k1_hash_to_curve(msg, msg_len, pk, out, &status), "Plume::hash_to_curve");
+    return status;
+  }
+  static uint32_t verify(const uint8_t* msg, size_t msg_len, const uint64_t pk[8], const uint64_t nullifier[8], const uint64_t s[4], const uint64_t c[4],
+                         uint64_t h_out[8] = nullptr) {
+    uint32_t verdict = 0;
+    check(zkhip_plume_verify(msg, msg_len, pk, nullifier, s, c, &verdict, h_out), "Plume::verify");
+    return verdict;
+  }
+};
+
 // `Blake2bWrite` / `Blake2bRead` with `Challenge255` [DEP transcript.rs] over zkhip_transcript_* (zkhip.h, "transcript"): the hash and the framing
 // run on the host inside the library, the `_device` forms take commitments / evaluations where they lie in HBM.  One thread at a time per object.
 class Transcript {

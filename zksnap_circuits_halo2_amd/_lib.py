@@ -14,6 +14,7 @@ ZKHIP_POSEIDON_SUBTREE = 256    # include/zkhip.h: elements of a level one workg
 ZKHIP_IMT_MAX_DEPTH = 24        # include/zkhip.h: the deepest indexed Merkle tree zkhip_imt_create makes
 ZKHIP_PAILLIER_WORDS = 6        # include/zkhip.h: 64-bit words of a Paillier ciphertext (an integer below n^2)
 ZKHIP_PAILLIER_MAX_N_BITS = 192 # include/zkhip.h: the widest Paillier n
+ZKHIP_PLUME_MAX_MSG = 64        # include/zkhip.h: the most bytes of the message a batch of PLUME nullifiers shares
 
 # every symbol include/zkhip.h declares (tests check the export list against the header)
 _SIGS = {
@@ -165,6 +166,12 @@ _SIGS = {
     "zkhip_paillier_mul_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zkhip_paillier_tally_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_paillier_encrypt_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zkhip_secp256k1_lincomb_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkhip_secp256k1_hash_to_curve_device": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkhip_plume_verify_device": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "zkhip_secp256k1_hash_to_curve": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkhip_plume_verify": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_test_reduce512": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zkhip_test_transcript_chunk": (C.c_uint32, [C.c_size_t]),
     "zkhip_profile_enable": (C.c_int, [C.c_int]),

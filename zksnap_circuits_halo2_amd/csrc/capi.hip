@@ -32,6 +32,7 @@
 #include "poseidon.hpp"
 #include "imt.hpp"
 #include "modn.hpp"
+#include "secp256k1_h2c.hpp"
 #include "../../include/zkhip.hpp"   // host-side 4 x 64 Montgomery arithmetic for domain constants (zkhip::halo2::detail)
 
 namespace zkhip {
@@ -3260,6 +3261,119 @@ int zkhip_paillier_encrypt_device(const uint64_t n[3], const uint64_t g[6], cons
   guard_t gd(g_mu);
   if ((rc = ensure_init()) != ZKHIP_OK) return rc;
   return paillier_encrypt_device(ctx, n, g, (const uint64_t*)d_m, (const uint64_t*)d_r, count, (uint64_t*)d_out, caller_stream(stream));
+}
+
+}  // extern "C"
+
+// ---- PLUME nullifiers on secp256k1 (include/zkhip.h, "PLUME nullifiers on secp256k1") -----------------------------------------------------------
+// Every refusal is decided on the host before HIP is touched: a refused call enqueues nothing and works in a process that has no device.
+namespace zkhip {
+struct pm_span {
+  const void* p;
+  size_t bytes;
+  bool out;
+};
+constexpr size_t PM_MAX_COUNT = (size_t)1 << 30;
+constexpr size_t PM_POINT = 64, PM_SCALAR = 32;
+static int pm_message(const char* who, const uint8_t* msg, size_t msg_len, h2c_prefix* pre) {
+  if (msg_len > ZKHIP_PLUME_MAX_MSG) { set_error("%s: the message is longer than ZKHIP_PLUME_MAX_MSG bytes", who); return ZKHIP_EINVAL; }
+  if (msg_len && !msg) { set_error("%s: null message", who); return ZKHIP_EINVAL; }
+  h2c_prefix_build(msg, msg_len, pre);
+  return ZKHIP_OK;
+}
+// the arrays of a call: none null (count > 0), all 8-byte aligned, no output overlapping anything else
+static int pm_arrays(const char* who, size_t count, const pm_span* spans, int n) {
+  if (count > PM_MAX_COUNT) { set_error("%s: more than 2^30 elements in one call", who); return ZKHIP_EINVAL; }
+  for (int i = 0; i < n; i++) {
+    if (count && !spans[i].p) { set_error("%s: null pointer", who); return ZKHIP_EINVAL; }
+    if ((uintptr_t)spans[i].p & 7) { set_error("%s: pointers must be 8-byte aligned", who); return ZKHIP_EINVAL; }
+  }
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++)
+      if (i != j && spans[i].out && pl_overlap(spans[i].p, spans[i].bytes, spans[j].p, spans[j].bytes)) { set_error("%s: an output overlaps another array", who); return ZKHIP_EINVAL; }
+  return ZKHIP_OK;
+}
+static sk_aff pm_point(const uint64_t* w) {
+  sk_aff a;
+  a.x = sk_from_words(w);
+  a.y = sk_from_words(w + 4);
+  return a;
+}
+}  // namespace zkhip
+
+extern "C" {
+
+int zkhip_secp256k1_lincomb_device(const void* d_a, const void* d_p, const void* d_b, const void* d_q, size_t count, void* d_out, void* d_status, void* stream) {
+  ZK_API_RANGE();
+  const pm_span spans[] = {{d_a, count * PM_SCALAR, false}, {d_p, count * PM_POINT, false}, {d_b, count * PM_SCALAR, false}, {d_q, count * PM_POINT, false},
+                           {d_out, count * PM_POINT, true}, {d_status, count * 4, true}};
+  int rc = pm_arrays("secp256k1_lincomb", count, spans, 6);
+  if (rc != ZKHIP_OK || count == 0) return rc;
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  return secp256k1_lincomb_device((const uint64_t*)d_a, (const uint64_t*)d_p, (const uint64_t*)d_b, (const uint64_t*)d_q, count, (uint64_t*)d_out, (uint32_t*)d_status,
+                                  caller_stream(stream));
+}
+
+int zkhip_secp256k1_hash_to_curve_device(const uint8_t* msg, size_t msg_len, const void* d_pk, size_t count, void* d_out, void* d_status, void* stream) {
+  ZK_API_RANGE();
+  h2c_prefix pre;
+  int rc = pm_message("secp256k1_hash_to_curve", msg, msg_len, &pre);
+  if (rc != ZKHIP_OK) return rc;
+  const pm_span spans[] = {{d_pk, count * PM_POINT, false}, {d_out, count * PM_POINT, true}, {d_status, count * 4, true}};
+  rc = pm_arrays("secp256k1_hash_to_curve", count, spans, 3);
+  if (rc != ZKHIP_OK || count == 0) return rc;
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  return secp256k1_hash_to_curve_device(pre, (const uint64_t*)d_pk, count, (uint64_t*)d_out, (uint32_t*)d_status, caller_stream(stream));
+}
+
+int zkhip_plume_verify_device(const uint8_t* msg, size_t msg_len, const void* d_pk, const void* d_nullifier, const void* d_s, const void* d_c, size_t count, void* d_status,
+                              void* d_report, void* d_h_out, void* stream) {
+  ZK_API_RANGE();
+  h2c_prefix pre;
+  int rc = pm_message("plume_verify", msg, msg_len, &pre);
+  if (rc != ZKHIP_OK) return rc;
+  if (!d_report) { set_error("plume_verify: null report"); return ZKHIP_EINVAL; }
+  const pm_span spans[] = {{d_pk, count * PM_POINT, false}, {d_nullifier, count * PM_POINT, false}, {d_s, count * PM_SCALAR, false}, {d_c, count * PM_SCALAR, false},
+                           {d_status, count * 4, true}, {d_report, sizeof(zkhip_check_report), true}, {d_h_out, count * PM_POINT, true}};
+  rc = pm_arrays("plume_verify", count, spans, d_h_out ? 7 : 6);
+  if (rc != ZKHIP_OK) return rc;
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  return plume_verify_device(pre, (const uint64_t*)d_pk, (const uint64_t*)d_nullifier, (const uint64_t*)d_s, (const uint64_t*)d_c, count, (uint32_t*)d_status, d_report,
+                             (uint64_t*)d_h_out, caller_stream(stream));
+}
+
+int zkhip_secp256k1_hash_to_curve(const uint8_t* msg, size_t msg_len, const uint64_t pk[8], uint64_t out[8], uint32_t* status) {
+  h2c_prefix pre;
+  const int rc = pm_message("secp256k1_hash_to_curve", msg, msg_len, &pre);
+  if (rc != ZKHIP_OK) return rc;
+  if (!pk || !out || !status) { set_error("secp256k1_hash_to_curve: null pointer"); return ZKHIP_EINVAL; }
+  const sk_aff key = pm_point(pk);
+  const bool ok = sk_on_curve(key);
+  sk_aff h;
+  h.x = h.y = sk_small(0);
+  if (ok) h = h2c_hash(pre, key);
+  sk_to_words(h.x, out);
+  sk_to_words(h.y, out + 4);
+  *status = ok ? PLUME_OK : PLUME_MALFORMED;
+  return ZKHIP_OK;
+}
+
+int zkhip_plume_verify(const uint8_t* msg, size_t msg_len, const uint64_t pk[8], const uint64_t nullifier[8], const uint64_t s[4], const uint64_t c[4], uint32_t* verdict,
+                       uint64_t h_out[8]) {
+  h2c_prefix pre;
+  const int rc = pm_message("plume_verify", msg, msg_len, &pre);
+  if (rc != ZKHIP_OK) return rc;
+  if (!pk || !nullifier || !s || !c || !verdict) { set_error("plume_verify: null pointer"); return ZKHIP_EINVAL; }
+  sk_aff h;
+  *verdict = plume_verdict(pre, pm_point(pk), pm_point(nullifier), sk_from_words(s), sk_from_words(c), &h);
+  if (h_out) {
+    sk_to_words(h.x, h_out);
+    sk_to_words(h.y, h_out + 4);
+  }
+  return ZKHIP_OK;
 }
 
 }  // extern "C"

@@ -271,6 +271,15 @@ int paillier_tally_device(const modn_ctx& ctx, const uint64_t* d_ballots, size_t
 int paillier_encrypt_device(const modn_ctx& ctx, const uint64_t n[3], const uint64_t g[6], const uint64_t* d_m, const uint64_t* d_r, size_t count, uint64_t* d_out,
                             hipStream_t stream);
 
+// plume.hip (include/zkhip.h, "PLUME nullifiers on secp256k1").  The prefix of a batch's message is built on the host per call (secp256k1_h2c.hpp) and handed
+// to the kernels by value.
+struct h2c_prefix;
+int secp256k1_lincomb_device(const uint64_t* d_a, const uint64_t* d_p, const uint64_t* d_b, const uint64_t* d_q, size_t count, uint64_t* d_out, uint32_t* d_status,
+                             hipStream_t stream);
+int secp256k1_hash_to_curve_device(const h2c_prefix& pre, const uint64_t* d_pk, size_t count, uint64_t* d_out, uint32_t* d_status, hipStream_t stream);
+int plume_verify_device(const h2c_prefix& pre, const uint64_t* d_pk, const uint64_t* d_nullifier, const uint64_t* d_s, const uint64_t* d_c, size_t count, uint32_t* d_status,
+                        void* d_report, uint64_t* d_h_out, hipStream_t stream);
+
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);
 int g1_check_points_device(const uint32_t* d_points, size_t n, unsigned long long* d_first_bad, hipStream_t stream);

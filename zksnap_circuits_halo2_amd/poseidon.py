@@ -84,6 +84,27 @@ def nullifier_values(points: Sequence[Tuple[int, int]], stream=None):
     return hash_many_device(torch.from_numpy(packed.view(np.int64)).to(dev), stream=stream)
 
 
+def pack_member(point: Tuple[int, int]) -> List[int]:
+    """the six values behind a leaf of the members tree (reference aggregator/src/utils.rs:224-254): the 11-, 11- and 10-byte little-endian
+    chunks of pk.x's 32 bytes, then those of pk.y's.  Host; integers in and out."""
+    out = []
+    for v in (int(point[0]), int(point[1])):
+        if not 0 <= v < 1 << 256:
+            raise ValueError("pack_member: a coordinate is 32 bytes")
+        raw = v.to_bytes(32, "little")
+        out += [int.from_bytes(raw[at:at + 11], "little") for at in (0, 11, 22)]
+    return out
+
+
+def member_leaves(points: Sequence[Tuple[int, int]], stream=None):
+    """secp256k1 public keys (x, y) -> the (n, 4) device tensor of the members tree's leaves: the width-6 hash of every packed key, one launch"""
+    import torch
+
+    packed = fr_encode([v for P in points for v in pack_member(P)]).reshape(len(points), 6, 4)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    return hash_many_device(torch.from_numpy(packed.view(np.int64)).to(dev), stream=stream)
+
+
 def merkle_device(leaves, stream=None):
     """leaves: (n, 4) int64 device tensor, n a power of two -> the (n - 1, 4) inner nodes, level 1 first, the root last; no host wait"""
     import torch

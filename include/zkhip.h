@@ -646,6 +646,13 @@ int zkhip_poseidon_constants(uint64_t out[204 * 4]);
  * ZKHIP_POSEIDON_MAX_WIDTH, else ZKHIP_EINVAL.  One launch, no host wait (the FIRST Poseidon `_device` call of a process uploads the table and
  * waits for that).  d_in and d_out 16-byte aligned; they must not overlap. */
 int zkhip_poseidon_hash_many_device(const void *d_in, size_t n, uint32_t width, void *d_out, void *stream);
+/* n secp256k1 points as the PLUME calls hold them (8 little-endian 64-bit words, canonical x then y; ANY 256-bit values are taken) packed and
+ * hashed where they lie: d_out[i] = what zkhip_poseidon_hash_many_device gives over the packed message of point i.  layout 0 (nullifier,
+ * `compress_native_nullifier`): (2 + (y & 1), x bytes 0..10, 11..21, 22..31 as little-endian integers), width 4.  layout 1 (member, the
+ * members tree's leaf): the three chunks of x, then those of y, width 6.  One launch, one lane per point, no host wait (the first Poseidon
+ * `_device` call uploads the table).  ZKHIP_EINVAL, nothing enqueued: another layout, a null or non-16-byte-aligned pointer, n above 2^30,
+ * d_out overlapping d_points.  n == 0 succeeds and writes nothing. */
+int zkhip_poseidon_hash_points_device(const void *d_points, size_t n, uint32_t layout, void *d_out, void *stream);
 /* The n_leaves - 1 inner nodes of the tree over d_leaves, level 1 (n_leaves / 2 nodes) first, the root last: level L starts at node
  * n_leaves - (n_leaves >> (L - 1)).  One launch behind one small memset, no host wait.  n_leaves = 1 writes nothing (the root is the leaf).
  * ZKHIP_EINVAL, nothing enqueued: n_leaves not a power of two, 0, or above 2^30; a null or misaligned pointer.  d_nodes must not overlap d_leaves. */
@@ -747,7 +754,7 @@ int zkhip_paillier_tally_device(const uint64_t n[3], const void *d_ballots, size
  * the plain left-to-right ladder.  d_out must not overlap d_m or d_r. */
 int zkhip_paillier_encrypt_device(const uint64_t n[3], const uint64_t g[6], const void *d_m, const void *d_r, size_t count, void *d_out, void *stream);
 
-/* ---- PLUME nullifiers on secp256k1: a batch of nullifiers verified in one device call ----
+/* ---- PLUME nullifiers on secp256k1: a batch of nullifiers verified, or signed, in one device call ----
  * [DEP k256 `hash_from_bytes::<ExpandMsgXmd<Sha256>>`, halo2curves secp256k1; the reference: `verify_nullifier`, `compress_point`, `hash_to_curve`
  * and `gen_test_nullifier`, voter_tests/src/lib.rs:25-119, called for every round by `generate_wrapper_circuit_input`,
  * aggregator/src/utils.rs:289-290.]  The crates are not vendored with the reference and could not be built: parity with `k256` / `plume-halo2` is
@@ -778,14 +785,20 @@ int zkhip_paillier_encrypt_device(const uint64_t n[3], const uint64_t g[6], cons
  *             N  = (0x022e80224208f61d2bd0db01ee45f1ad280afed208073f8cadfea796b62ec66e, 0xeb2167a30ea8a02d40c3a86c93961b7f02664aac622d11d34b9f120eed108c73)
  *             s  = 0x2dd6d3be74b08a383e981dac34dda120b5f0d32f9a1e245ab034d00b4d1149a3, c = 0x31c5e6a7886d3802ee2e0bc16993e6dda5f9992597c67ee4bfb5acba7bf07535
  *             verify -> 0; with c + 1 -> 1; with msg = 02 00 -> 1.
+ *   sign(msg, sk, r) (`gen_test_nullifier`, r in place of `Fq::random`), sk and r in [1, n):  pk = sk G,  H = H(msg, pk),  N = sk H,
+ *             d = SHA-256(compress(G) || compress(pk) || compress(H) || compress(N) || compress(r G) || compress(r H)),
+ *             c = the big-endian integer of d, taken mod n (the reference panics on a digest >= n; probability 2^-128),  s = r + sk c mod n.
+ *             status 0, or 2 and zeros in every output where sk or r is 0 or >= n.  The pinned vector above is sign(01 00, sk, r).
+ *             The ladders are branch-free, but nothing here is audited for side channels: the call is meant for generated populations
+ *             (tests, probes, simulations), not for a voter's wallet.
  * Formats: a point is 8 little-endian 64-bit words, x then y, each the canonical integer (NOT Montgomery); a scalar is 4 words.  A verdict or
  * status is a uint32.  msg is on the HOST, read before the call returns, at most ZKHIP_PLUME_MAX_MSG bytes, and shared by the batch (the proposal).
  * The `_device` calls are asynchronous on `stream` with no host wait; at most 2^30 elements per call.
  * ZKHIP_EINVAL, nothing enqueued (decided on the host before the device is touched): a null pointer where none is allowed (msg may be null when
  * msg_len is 0; d_h_out may be null; every array may be null when count is 0, d_report never), msg_len > ZKHIP_PLUME_MAX_MSG, a pointer that is
  * not 8-byte aligned, an output that overlaps an input or another output.  count == 0 succeeds; the verify call then writes only a zeroed report.
- * Not built: a fixed-base table for G, batch verification by a random linear combination, signing on the device, sharding over devices,
- * PLUME v2. */
+ * Not built: a fixed-base table for G, batch verification by a random linear combination, sharding over devices, PLUME v2, constant-time
+ * guarantees. */
 #define ZKHIP_PLUME_MAX_MSG 64
 /* d_out[i] = a[i] P[i] + b[i] Q[i], affine, identity as (0, 0); scalars are any 256-bit integers; a malformed P or Q gives status 2 and (0, 0) */
 int zkhip_secp256k1_lincomb_device(const void *d_a, const void *d_p, const void *d_b, const void *d_q, size_t count, void *d_out, void *d_status, void *stream);
@@ -794,10 +807,16 @@ int zkhip_secp256k1_hash_to_curve_device(const uint8_t *msg, size_t msg_len, con
 /* d_status[i] (uint32) = the verdict above; d_report: one zkhip_check_report -- voters with a non-zero verdict, lowest such index; d_h_out optional
  * (NULL or count points): H of every voter, (0, 0) where pk is malformed.  Two lanes per voter (csrc/plume.hip). */
 int zkhip_plume_verify_device(const uint8_t *msg, size_t msg_len, const void *d_pk, const void *d_nullifier, const void *d_s, const void *d_c, size_t count, void *d_status, void *d_report, void *d_h_out, void *stream);
+/* sign of every voter: d_sk, d_r count scalars in; d_pk, d_nullifier count points, d_s, d_c count scalars, d_status count uint32 out; d_h_out
+ * optional (NULL or count points): H of every voter.  A malformed sk or r gives status 2 and zeros in every output of that voter.  One launch, two
+ * lanes per voter (csrc/plume_sign.hip); count == 0 succeeds and writes nothing. */
+int zkhip_plume_sign_device(const uint8_t *msg, size_t msg_len, const void *d_sk, const void *d_r, size_t count, void *d_pk, void *d_nullifier, void *d_s, void *d_c, void *d_status, void *d_h_out, void *stream);
 /* The same for one voter on the host, over the same headers; no GPU is touched.  out = H(msg, pk) and *status 0, or (0, 0) and 2 for a malformed pk. */
 int zkhip_secp256k1_hash_to_curve(const uint8_t *msg, size_t msg_len, const uint64_t pk[8], uint64_t out[8], uint32_t *status);
 /* *verdict as above; h_out optional: H(msg, pk), (0, 0) where pk is malformed */
 int zkhip_plume_verify(const uint8_t *msg, size_t msg_len, const uint64_t pk[8], const uint64_t nullifier[8], const uint64_t s[4], const uint64_t c[4], uint32_t *verdict, uint64_t h_out[8]);
+/* *status 0 and the signature, or 2 and zeros; h_out optional: H(msg, pk) */
+int zkhip_plume_sign(const uint8_t *msg, size_t msg_len, const uint64_t sk[4], const uint64_t r[4], uint64_t pk[8], uint64_t nullifier[8], uint64_t s[4], uint64_t c[4], uint32_t *status, uint64_t h_out[8]);
 
 /* ---- parity hooks for the field / curve layer (rows a1/a2 of SURVEY.md section 8) ------------------ */
 /* field: 0 = Fq, 1 = Fr.  op: 0 mul, 1 add, 2 sub, 3 square (b ignored).  Elementwise on n elements. */

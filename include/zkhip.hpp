@@ -446,6 +446,10 @@ struct Poseidon {
   static void hash_many_device(const void* d_in, size_t n, uint32_t width, void* d_out, void* stream = nullptr) {
     check(zkhip_poseidon_hash_many_device(d_in, n, width, d_out, stream), "Poseidon::hash_many_device");
   }
+  // n secp256k1 points (8 canonical words each) packed and hashed in HBM: layout 0 the nullifier tree's values, 1 the members tree's leaves
+  static void hash_points_device(const void* d_points, size_t n, uint32_t layout, void* d_out, void* stream = nullptr) {
+    check(zkhip_poseidon_hash_points_device(d_points, n, layout, d_out, stream), "Poseidon::hash_points_device");
+  }
   // the n_leaves - 1 inner nodes, level 1 first, the root last; no host wait
   static void merkle_device(const void* d_leaves, size_t n_leaves, void* d_nodes, void* stream = nullptr) {
     check(zkhip_poseidon_merkle_device(d_leaves, n_leaves, d_nodes, stream), "Poseidon::merkle_device");
@@ -470,7 +474,7 @@ struct Paillier {
   }
 };
 
-// The PLUME nullifier check over arrays in HBM (zkhip.h, "PLUME nullifiers on secp256k1"): points are 8 and scalars 4 canonical little-endian
+// The PLUME nullifier check, and signing, over arrays in HBM (zkhip.h, "PLUME nullifiers on secp256k1"): points are 8 and scalars 4 canonical little-endian
 // words; `msg` is on the host and shared by the batch; every `_device` call is asynchronous on `stream`.
 struct Plume {
   // d_out[i] = a[i] P[i] + b[i] Q[i]; d_status[i] = 2 and (0, 0) for a malformed point
@@ -486,7 +490,18 @@ struct Plume {
                             void* d_report, void* d_h_out = nullptr, void* stream = nullptr) {
     check(zkhip_plume_verify_device(msg, msg_len, d_pk, d_nullifier, d_s, d_c, count, d_status, d_report, d_h_out, stream), "Plume::verify_device");
   }
+  // `gen_test_nullifier` of every voter from d_sk, d_r; d_status[i]: 0, or 2 and zeros for sk or r outside [1, n); d_h_out null or count points
+  static void sign_device(const uint8_t* msg, size_t msg_len, const void* d_sk, const void* d_r, size_t count, void* d_pk, void* d_nullifier, void* d_s, void* d_c,
+                          void* d_status, void* d_h_out = nullptr, void* stream = nullptr) {
+    check(zkhip_plume_sign_device(msg, msg_len, d_sk, d_r, count, d_pk, d_nullifier, d_s, d_c, d_status, d_h_out, stream), "Plume::sign_device");
+  }
   // one voter on the host
+  static uint32_t sign(const uint8_t* msg, size_t msg_len, const uint64_t sk[4], const uint64_t r[4], uint64_t pk[8], uint64_t nullifier[8], uint64_t s[4],
+                       uint64_t c[4], uint64_t h_out[8] = nullptr) {
+    uint32_t status = 0;
+    check(zkhip_plume_sign(msg, msg_len, sk, r, pk, nullifier, s, c, &status, h_out), "Plume::sign");
+    return status;
+  }
   static uint32_t hash_to_curve(const uint8_t* msg, size_t msg_len, const uint64_t pk[8], uint64_t out[8]) {
     uint32_t status = 0;
     check(zkhip_secp256k1_hash_to_curve(msg, msg_len, pk, out, &status), "Plume::hash_to_curve");

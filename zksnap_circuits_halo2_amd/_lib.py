@@ -153,6 +153,7 @@ _SIGS = {
     "zkhip_poseidon_hash": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "zkhip_poseidon_constants": (C.c_int, [C.c_void_p]),
     "zkhip_poseidon_hash_many_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "zkhip_poseidon_hash_points_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "zkhip_poseidon_merkle_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "zkhip_imt_create": (C.c_int, [C.c_uint32, C.POINTER(C.c_void_p)]),
     "zkhip_imt_destroy": (C.c_int, [C.c_void_p]),
@@ -172,6 +173,9 @@ _SIGS = {
                                             C.c_void_p]),
     "zkhip_secp256k1_hash_to_curve": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_plume_verify": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkhip_plume_sign_device": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "zkhip_plume_sign": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_test_reduce512": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zkhip_test_transcript_chunk": (C.c_uint32, [C.c_size_t]),
     "zkhip_profile_enable": (C.c_int, [C.c_int]),

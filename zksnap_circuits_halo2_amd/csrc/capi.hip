@@ -3168,6 +3168,24 @@ int zkhip_poseidon_hash_many_device(const void* d_in, size_t n, uint32_t width, 
   return poseidon_hash_many_device((const uint32_t*)d_in, n, width, (uint32_t*)d_out, d_tab, s);
 }
 
+int zkhip_poseidon_hash_points_device(const void* d_points, size_t n, uint32_t layout, void* d_out, void* stream) {
+  ZK_API_RANGE();
+  if (layout > 1) { set_error("poseidon_hash_points: layout %u is neither 0 (nullifier) nor 1 (member)", layout); return ZKHIP_EINVAL; }
+  if (n && (!d_points || !d_out)) { set_error("poseidon_hash_points: null pointer"); return ZKHIP_EINVAL; }
+  if (((uintptr_t)d_points | (uintptr_t)d_out) & 15) { set_error("poseidon_hash_points: d_points and d_out must be 16-byte aligned"); return ZKHIP_EINVAL; }
+  if (n > ((size_t)1 << 30)) { set_error("poseidon_hash_points: more than 2^30 points in one call"); return ZKHIP_EINVAL; }
+  if (n == 0) return ZKHIP_OK;
+  const uintptr_t in = (uintptr_t)d_points, out = (uintptr_t)d_out;
+  if (in < out + n * 32 && out < in + n * 64) { set_error("poseidon_hash_points: d_out overlaps d_points"); return ZKHIP_EINVAL; }
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  const uint32_t* d_tab = nullptr;
+  if ((rc = poseidon_device_table(s, &d_tab)) != ZKHIP_OK) return rc;
+  return poseidon_hash_points_device((const uint32_t*)d_points, n, layout, (uint32_t*)d_out, d_tab, s);
+}
+
 int zkhip_poseidon_merkle_device(const void* d_leaves, size_t n_leaves, void* d_nodes, void* stream) {
   ZK_API_RANGE();
   if (n_leaves == 0 || (n_leaves & (n_leaves - 1)) || n_leaves > ((size_t)1 << 30)) {
@@ -3343,6 +3361,43 @@ int zkhip_plume_verify_device(const uint8_t* msg, size_t msg_len, const void* d_
   if ((rc = ensure_init()) != ZKHIP_OK) return rc;
   return plume_verify_device(pre, (const uint64_t*)d_pk, (const uint64_t*)d_nullifier, (const uint64_t*)d_s, (const uint64_t*)d_c, count, (uint32_t*)d_status, d_report,
                              (uint64_t*)d_h_out, caller_stream(stream));
+}
+
+int zkhip_plume_sign_device(const uint8_t* msg, size_t msg_len, const void* d_sk, const void* d_r, size_t count, void* d_pk, void* d_nullifier, void* d_s, void* d_c,
+                            void* d_status, void* d_h_out, void* stream) {
+  ZK_API_RANGE();
+  h2c_prefix pre;
+  int rc = pm_message("plume_sign", msg, msg_len, &pre);
+  if (rc != ZKHIP_OK) return rc;
+  const pm_span spans[] = {{d_sk, count * PM_SCALAR, false}, {d_r, count * PM_SCALAR, false}, {d_pk, count * PM_POINT, true}, {d_nullifier, count * PM_POINT, true},
+                           {d_s, count * PM_SCALAR, true}, {d_c, count * PM_SCALAR, true}, {d_status, count * 4, true}, {d_h_out, count * PM_POINT, true}};
+  rc = pm_arrays("plume_sign", count, spans, d_h_out ? 8 : 7);
+  if (rc != ZKHIP_OK || count == 0) return rc;
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  return plume_sign_device(pre, (const uint64_t*)d_sk, (const uint64_t*)d_r, count, (uint64_t*)d_pk, (uint64_t*)d_nullifier, (uint64_t*)d_s, (uint64_t*)d_c,
+                           (uint32_t*)d_status, (uint64_t*)d_h_out, caller_stream(stream));
+}
+
+int zkhip_plume_sign(const uint8_t* msg, size_t msg_len, const uint64_t sk[4], const uint64_t r[4], uint64_t pk[8], uint64_t nullifier[8], uint64_t s[4], uint64_t c[4],
+                     uint32_t* status, uint64_t h_out[8]) {
+  h2c_prefix pre;
+  const int rc = pm_message("plume_sign", msg, msg_len, &pre);
+  if (rc != ZKHIP_OK) return rc;
+  if (!sk || !r || !pk || !nullifier || !s || !c || !status) { set_error("plume_sign: null pointer"); return ZKHIP_EINVAL; }
+  plume_signature sig;
+  *status = plume_sign(pre, sk_from_words(sk), sk_from_words(r), &sig);
+  sk_to_words(sig.pk.x, pk);
+  sk_to_words(sig.pk.y, pk + 4);
+  sk_to_words(sig.nullifier.x, nullifier);
+  sk_to_words(sig.nullifier.y, nullifier + 4);
+  sk_to_words(sig.s, s);
+  sk_to_words(sig.c, c);
+  if (h_out) {
+    sk_to_words(sig.h.x, h_out);
+    sk_to_words(sig.h.y, h_out + 4);
+  }
+  return ZKHIP_OK;
 }
 
 int zkhip_secp256k1_hash_to_curve(const uint8_t* msg, size_t msg_len, const uint64_t pk[8], uint64_t out[8], uint32_t* status) {

@@ -4,6 +4,8 @@
 // on another.
 //
 //   k_poseidon_hash_many  n messages of `width` Montgomery Fr, row-major -> n digests: a fresh sponge per lane.
+//   k_poseidon_hash_points  n secp256k1 points as the PLUME calls leave them in HBM -> the nullifier tree's values or the members tree's leaves:
+//                         the host packers' byte chunks are cut in registers, so a signed population never returns to the host to be packed.
 //   k_poseidon_merkle     the n - 1 inner nodes of a tree over n leaves in ONE launch.  A workgroup of POSEIDON_SUBTREE / 2 lanes takes a run
 //                         of POSEIDON_SUBTREE neighbouring elements of a level and folds it PM_DEPTH levels up -- level 1 from global
 //                         memory, level 2 through LDS, whole waves busy on both -- and hands its POSEIDON_SUBTREE >> PM_DEPTH nodes on
@@ -44,6 +46,51 @@ __global__ void __launch_bounds__(PH_BLOCK) k_poseidon_hash_many(const uint32_t*
   if (i >= n) return;
   const uint32_t* msg = in + i * width * 8;
   const fe h = poseidon_hash<poseidon_dev_field>(width, tab, [&](uint32_t j) { return ps_load(msg + (size_t)j * 8); });
+  ps_store(out + i * 8, h);
+}
+
+// The 11-, 11- and 10-byte little-endian chunks of a 32-byte coordinate (eight words): bits 0 .. 87, 88 .. 175 and 176 .. 255.  All three are cut
+// with shifts known when the code is compiled and `which` picks one by conditional moves, so that nothing is indexed at run time.
+__device__ __forceinline__ void ps_chunk(const uint32_t (&w)[8], uint32_t which, uint32_t (&out)[3]) {
+  const uint32_t a[3] = {w[0], w[1], w[2] & 0x00ffffffu};
+  const uint32_t b[3] = {(w[2] >> 24) | (w[3] << 8), (w[3] >> 24) | (w[4] << 8), ((w[4] >> 24) | (w[5] << 8)) & 0x00ffffffu};
+  const uint32_t c[3] = {(w[5] >> 16) | (w[6] << 16), (w[6] >> 16) | (w[7] << 16), w[7] >> 16};
+#pragma unroll
+  for (int k = 0; k < 3; k++) out[k] = which == 0 ? a[k] : which == 1 ? b[k] : c[k];
+}
+// a canonical integer below 2^96 -> Montgomery-261, N form: v 2^522 2^-261, the product far below r^2, so the result is < 1.1 r
+__device__ __forceinline__ fe ps_from_small(const uint32_t (&v)[3]) {
+  const uint32_t w[8] = {v[0], v[1], v[2], 0, 0, 0, 0, 0};
+  fe r2;
+#pragma unroll
+  for (int i = 0; i < NL; i++) r2.l[i] = FrParams::R2[i];
+  return fe_mul<FrParams>(r2, fe_unpack<0>(w));
+}
+
+// One lane per secp256k1 point (x then y, eight canonical words each, ANY 256-bit values): the message the host packers build
+// (poseidon.py `compress_nullifier`, `pack_member`) is cut from the point in registers and hashed.  layout 0: (2 + (y & 1), the three chunks
+// of x), width 4; layout 1: the chunks of x, then those of y, width 6.  The layout is uniform over the launch.
+__global__ void __launch_bounds__(PH_BLOCK) k_poseidon_hash_points(const uint32_t* __restrict__ points, size_t n, uint32_t layout, uint32_t* __restrict__ out,
+                                                                   const fe* __restrict__ tab) {
+  const size_t i = (size_t)blockIdx.x * PH_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  uint32_t x[8], y[8];
+  load_words(points + i * 16, x);
+  load_words(points + i * 16 + 8, y);
+  const fe h = poseidon_hash<poseidon_dev_field>(layout ? 6u : 4u, tab, [&](uint32_t j) {
+    // layout 0: element 0 is the tag and element j > 0 chunk j - 1 of x; layout 1: element j is chunk j % 3 of x (j < 3) or y
+    const bool of_y = layout && j >= 3;
+    const uint32_t which = layout ? (of_y ? j - 3 : j) : j - 1;
+    uint32_t w[8], v[3];
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = of_y ? y[k] : x[k];
+    ps_chunk(w, which, v);
+    const bool tag = !layout && j == 0;
+    v[0] = tag ? 2u + (y[0] & 1u) : v[0];
+    v[1] = tag ? 0u : v[1];
+    v[2] = tag ? 0u : v[2];
+    return ps_from_small(v);
+  });
   ps_store(out + i * 8, h);
 }
 
@@ -123,6 +170,13 @@ __global__ void __launch_bounds__(PM_BLOCK) k_poseidon_merkle(const uint32_t* __
 int poseidon_hash_many_device(const uint32_t* d_in, size_t n, uint32_t width, uint32_t* d_out, const uint32_t* d_tab, hipStream_t stream) {
   if (n == 0) return ZKHIP_OK;
   hipLaunchKernelGGL(k_poseidon_hash_many, dim3((unsigned)((n + PH_BLOCK - 1) / PH_BLOCK)), dim3(PH_BLOCK), 0, stream, d_in, n, width, d_out, (const fe*)d_tab);
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
+}
+
+int poseidon_hash_points_device(const uint32_t* d_points, size_t n, uint32_t layout, uint32_t* d_out, const uint32_t* d_tab, hipStream_t stream) {
+  if (n == 0) return ZKHIP_OK;
+  hipLaunchKernelGGL(k_poseidon_hash_points, dim3((unsigned)((n + PH_BLOCK - 1) / PH_BLOCK)), dim3(PH_BLOCK), 0, stream, d_points, n, layout, d_out, (const fe*)d_tab);
   HIPCHK(hipGetLastError());
   return ZKHIP_OK;
 }

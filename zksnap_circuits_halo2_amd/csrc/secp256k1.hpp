@@ -9,6 +9,16 @@
 //   sk_add / sk_sub / sk_neg                        need canonical operands: a + b < 2 p is reduced by one subtraction, a - b by one addition
 //   sk_eq / sk_is_zero / sk_is_odd                  compare limbs, so they need canonical operands too
 //   sk_inv = a^(p - 2) (0 -> 0), sk_sqrt = a^((p + 1) / 4) (a root iff its square is a): fixed addition chains, 255 squarings and 15 / 13 products
+//   sk_scalar_*                                     the same discipline mod the group order n = 2^256 - delta_n, delta_n =
+//                                                   0x14551231950B75FC4402DA1732FC9BEBF (129 bits, 1.271 * 2^128): ANY 256-bit operands (a 512-bit one
+//                                                   for sk_scalar_reduce512), canonical results (< n).  A value T = lo + hi * 2^256 becomes
+//                                                   lo + hi * delta_n, and the bound of every fold is:
+//       (1) T < 2^512:         hi <= 2^256 - 1,   T1 = lo + hi delta_n < 2^256 + (2^256 - 1) delta_n < (delta_n + 1) 2^256: thirteen words, hi1 <= delta_n
+//       (2) T1:                hi1 <= delta_n,    T2 = lo1 + hi1 delta_n < 2^256 + delta_n^2 < 2.62 * 2^256: nine words, hi2 <= 2
+//       (3) T2 (sk_scalar_fold, c < 2^32):        T3 = lo2 + c delta_n < 2^256 + 2^161: the carry is 0 or 1
+//       (4) a carry of 1 leaves words < 2^161:    T4 = lo3 + delta_n does not wrap; T4 < 2^256 < 2 n, so one conditional subtraction finishes
+//                                                   sk_scalar_add's carry (0 or 1) and sk_scalar_from_digest (no carry) enter at (3); sk_scalar_muladd
+//                                                   forms a b + c <= (2^256 - 1)^2 + 2^256 - 1 < 2^512 and enters at (1).
 //
 // THE GROUP.  Points are projective (X : Y : Z), x = X / Z, y = Y / Z, the identity (0 : 1 : 0).  Addition and doubling are the complete formulas
 // for a = 0 of Renes, Costello and Batina (2016), algorithms 7 and 9 with b3 = 21: no branches, correct for P + P, P + (-P), the identity on
@@ -17,8 +27,9 @@
 //
 // sk_lincomb(a, P, b, Q) = a P + b Q by one interleaved ladder (Strauss-Shamir) over the joint table {P, Q, P + Q}: 256 doublings and 256
 // additions, the entry chosen by conditional moves (an array indexed at run time would go to scratch) and the identity added where both bits
-// are zero.  The scalars are ANY 256-bit integers: the group has prime order n, so a counts mod n and n P is the identity.  Nothing here is
-// secret, constant time is not a goal.
+// are zero.  The scalars are ANY 256-bit integers: the group has prime order n, so a counts mod n and n P is the identity.  sk_mul_proj(k, P) is
+// the same ladder over the table {P}, for the signer (plume_sign.hip).  The ladders are branch-free, but nothing here is audited for side
+// channels: the signing call is meant for generated populations (tests, probes, simulations), not for a voter's wallet.
 //
 // Everything is host and device code and compiles with plain g++ (tests/cpp/secp256k1_host_check.cpp).
 #pragma once
@@ -371,6 +382,134 @@ SK_HD sk_pt sk_lincomb_proj(sk_fe a, const sk_aff& P, sk_fe b, const sk_aff& Q) 
   return r;
 }
 SK_HD sk_aff sk_lincomb(const sk_fe& a, const sk_aff& P, const sk_fe& b, const sk_aff& Q) { return sk_to_affine(sk_lincomb_proj(a, P, b, Q)); }
+
+// k P, projective, by the plain left-to-right ladder over the table {P}: 256 doublings and 256 additions, the identity added where the bit is
+// zero.  P affine, (0, 0) the identity; k any 256-bit integer.  A third fewer live words than the joint ladder with b = 0.
+SK_HD sk_pt sk_mul_proj(sk_fe k, const sk_aff& P) {
+  const sk_pt p = sk_from_affine(P);
+  const sk_fe zero = sk_small(0), one = sk_small(1);
+  sk_pt r = sk_identity();
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int i = 0; i < 256; i++) {
+    const bool bit = k.l[7] >> 31;
+#pragma unroll
+    for (int j = 7; j > 0; j--) k.l[j] = (k.l[j] << 1) | (k.l[j - 1] >> 31);
+    k.l[0] <<= 1;
+    sk_pt e;
+    e.X = sk_sel(bit, p.X, zero);
+    e.Y = sk_sel(bit, p.Y, one);
+    e.Z = sk_sel(bit, p.Z, zero);
+    r = sk_padd(sk_pdbl(r), e);
+  }
+  return r;
+}
+
+// ---- scalars mod n ------------------------------------------------------------------------------------------------------------------------
+// r (eight words) + c * 2^256 with c < 2^32 -> canonical mod n: c * delta_n is added (bound (3) above), a wrap adds delta_n once more, and one
+// conditional subtraction finishes: r - n = r + delta_n - 2^256, so the carry of r + delta_n says r >= n.
+SK_HD void sk_scalar_delta(uint32_t d[5]) {
+  d[0] = 0x2FC9BEBFu; d[1] = 0x402DA173u; d[2] = 0x50B75FC4u; d[3] = 0x45512319u; d[4] = 1u;
+}
+// out = a + c * delta_n over eight words; the carry out of 2^256 is returned.  c < 2^32.
+SK_HD uint32_t sk_scalar_add_delta(const sk_fe& a, uint32_t c, sk_fe& out) {
+  uint32_t d[5];
+  sk_scalar_delta(d);
+  uint64_t acc = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint64_t prod = i < 5 ? (uint64_t)c * d[i] : 0u;    // <= (2^32 - 1)^2; with a.l[i] and the carry <= 2^64 - 1
+    acc = (acc >> 32) + a.l[i] + prod;
+    out.l[i] = (uint32_t)acc;
+  }
+  return (uint32_t)(acc >> 32);
+}
+SK_HD sk_fe sk_scalar_fold(const sk_fe& r, uint32_t c) {
+  sk_fe o, t;
+  const uint32_t wrap = sk_scalar_add_delta(r, c, o);         // 0 or 1
+  sk_scalar_add_delta(o, wrap, t);                            // no carry: where wrap is 1, o < 2^161
+  const uint32_t ge = sk_scalar_add_delta(t, 1u, o);
+  return sk_sel(ge != 0, o, t);
+}
+// lo (eight words) + h (NH words) * delta_n -> out (eight words and NH + 5 - 8 more, at least one)
+template <int NH>
+SK_HD void sk_scalar_fold_wide(const uint32_t* lo, const uint32_t* h, uint32_t* out) {
+  constexpr int W = NH + 5 > 9 ? NH + 5 : 9;
+  uint32_t d[5];
+  sk_scalar_delta(d);
+#pragma unroll
+  for (int i = 0; i < W; i++) out[i] = i < 8 ? lo[i] : 0u;
+#pragma unroll
+  for (int i = 0; i < NH; i++) {
+    uint64_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+      const uint64_t acc = (uint64_t)h[i] * d[j] + out[i + j] + carry;   // <= 2^64 - 1, as in sk_mul
+      out[i + j] = (uint32_t)acc;
+      carry = acc >> 32;
+    }
+#pragma unroll
+    for (int k = i + 5; k < W; k++) {                         // the sum stays below 2^(32 W) (bounds (1), (2)): the last carry is zero
+      carry += out[k];
+      out[k] = (uint32_t)carry;
+      carry >>= 32;
+    }
+  }
+}
+// sixteen little-endian words -> the value mod n
+SK_HD sk_fe sk_scalar_reduce512(const uint32_t* t) {
+  uint32_t a[13], b[10];
+  sk_scalar_fold_wide<8>(t, t + 8, a);                        // (1): thirteen words, a[8 .. 12] <= delta_n
+  sk_scalar_fold_wide<5>(a, a + 8, b);                        // (2): b[8] <= 2, b[9] = 0
+  sk_fe r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.l[i] = b[i];
+  return sk_scalar_fold(r, b[8]);                             // (3), (4)
+}
+// any 256-bit a -> a mod n
+SK_HD sk_fe sk_scalar_reduce(const sk_fe& a) { return sk_scalar_fold(a, 0u); }
+SK_HD sk_fe sk_scalar_add(const sk_fe& a, const sk_fe& b) {
+  sk_fe s;
+  uint64_t acc = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    acc = (acc >> 32) + a.l[i] + b.l[i];
+    s.l[i] = (uint32_t)acc;
+  }
+  return sk_scalar_fold(s, (uint32_t)(acc >> 32));
+}
+// a b + c mod n: the 512-bit product, c added into it ((2^256 - 1)^2 + 2^256 - 1 < 2^512: no carry leaves word 15)
+SK_HD sk_fe sk_scalar_muladd(const sk_fe& a, const sk_fe& b, const sk_fe& c) {
+  uint32_t t[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) t[i] = i < 8 ? c.l[i] : 0u;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    uint64_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const uint64_t acc = (uint64_t)a.l[i] * b.l[j] + t[i + j] + carry;
+      t[i + j] = (uint32_t)acc;
+      carry = acc >> 32;
+    }
+#pragma unroll
+    for (int k = i + 8; k < 16; k++) {
+      carry += t[k];
+      t[k] = (uint32_t)carry;
+      carry >>= 32;
+    }
+  }
+  return sk_scalar_reduce512(t);
+}
+SK_HD sk_fe sk_scalar_mul(const sk_fe& a, const sk_fe& b) { return sk_scalar_muladd(a, b, sk_small(0)); }
+// a SHA-256 digest (eight big-endian words) read as a big-endian integer, mod n
+SK_HD sk_fe sk_scalar_from_digest(const uint32_t d[8]) {
+  sk_fe a;
+#pragma unroll
+  for (int i = 0; i < 8; i++) a.l[i] = d[7 - i];
+  return sk_scalar_reduce(a);
+}
 
 // `compress_point`: 33 bytes, 02 | 03 then x big-endian, as nine big-endian words whose last holds one byte at the top
 SK_HD void sk_compress(const sk_aff& a, uint32_t c[9]) {

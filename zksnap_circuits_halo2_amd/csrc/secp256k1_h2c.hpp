@@ -15,6 +15,8 @@
 //   h2c_hash              the sum of the two images, affine: one inversion.
 //   plume_challenge       SHA-256 of the six compressed points, 198 bytes at fixed offsets.
 //   plume_verdict         the whole check of one voter in one thread; the kernel splits the same pieces over two lanes.
+//   plume_sign            `gen_test_nullifier` of one voter in one thread: four single-scalar ladders, H, the challenge mod n, s = r + sk c mod n;
+//                         the kernel (plume_sign.hip) splits the ladders over two lanes and shares plume_sign_finish.
 //
 // Host and device code; plain g++ compiles it (tests/cpp/secp256k1_host_check.cpp).
 #pragma once
@@ -238,6 +240,35 @@ SK_HD uint32_t plume_verdict(const h2c_prefix& pre, const sk_aff& pk, const sk_a
   const sk_aff a = sk_lincomb(s, sk_generator(), c, sk_neg_affine(pk));
   const sk_aff b = sk_lincomb(s, h, c, sk_neg_affine(nullifier));
   return plume_challenge_is(pk, h, nullifier, a, b, c) ? PLUME_OK : PLUME_REFUSED;
+}
+
+// what `gen_test_nullifier` returns, and H(msg, pk) beside it
+struct plume_signature {
+  sk_aff pk, nullifier, h;
+  sk_fe s, c;
+};
+// sk, r in [1, n)
+SK_HD bool plume_secret_ok(const sk_fe& k) { return !sk_is_zero(k) && sk_scalar_ok(k); }
+// the last step, given the four ladder results: c = SHA-256(..) mod n, s = r + sk c mod n
+SK_HD void plume_sign_finish(const sk_fe& sk, const sk_fe& r, const sk_aff& rg, const sk_aff& rh, plume_signature& o) {
+  uint32_t d[8];
+  plume_challenge(o.pk, o.h, o.nullifier, rg, rh, d);
+  o.c = sk_scalar_from_digest(d);
+  o.s = sk_scalar_muladd(sk, o.c, r);
+}
+// `gen_test_nullifier` of one voter in one thread, r in place of `Fq::random`; the kernel splits the same pieces over two lanes.  A malformed
+// sk or r gives PLUME_MALFORMED and zeros.
+SK_HD uint32_t plume_sign(const h2c_prefix& pre, const sk_fe& sk, const sk_fe& r, plume_signature* o) {
+  if (!plume_secret_ok(sk) || !plume_secret_ok(r)) {
+    o->pk.x = o->pk.y = o->nullifier.x = o->nullifier.y = o->h.x = o->h.y = o->s = o->c = sk_small(0);
+    return PLUME_MALFORMED;
+  }
+  const sk_aff g = sk_generator();
+  o->pk = sk_to_affine(sk_mul_proj(sk, g));
+  o->h = h2c_hash(pre, o->pk);
+  o->nullifier = sk_to_affine(sk_mul_proj(sk, o->h));
+  plume_sign_finish(sk, r, sk_to_affine(sk_mul_proj(r, g)), sk_to_affine(sk_mul_proj(r, o->h)), *o);
+  return PLUME_OK;
 }
 
 }  // namespace zkhip

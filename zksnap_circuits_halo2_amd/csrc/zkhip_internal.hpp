@@ -250,6 +250,8 @@ int transcript_affine_device(const uint32_t* d_points, size_t n, uint32_t* d_out
 
 // poseidon.hip (include/zkhip.h, "Poseidon").  d_tab: poseidon.hpp's table in the kernels' limbs (POSEIDON_TAB_LEN x 9 words)
 int poseidon_hash_many_device(const uint32_t* d_in, size_t n, uint32_t width, uint32_t* d_out, const uint32_t* d_tab, hipStream_t stream);
+// n secp256k1 points (16 canonical words each) packed and hashed: layout 0 the nullifier's (width 4), 1 the member's (width 6)
+int poseidon_hash_points_device(const uint32_t* d_points, size_t n, uint32_t layout, uint32_t* d_out, const uint32_t* d_tab, hipStream_t stream);
 size_t poseidon_merkle_workspace(size_t n);
 int poseidon_merkle_device(const uint32_t* d_leaves, size_t n, uint32_t* d_nodes, const uint32_t* d_tab, void* ws, size_t ws_bytes, hipStream_t stream);
 
@@ -279,6 +281,9 @@ int secp256k1_lincomb_device(const uint64_t* d_a, const uint64_t* d_p, const uin
 int secp256k1_hash_to_curve_device(const h2c_prefix& pre, const uint64_t* d_pk, size_t count, uint64_t* d_out, uint32_t* d_status, hipStream_t stream);
 int plume_verify_device(const h2c_prefix& pre, const uint64_t* d_pk, const uint64_t* d_nullifier, const uint64_t* d_s, const uint64_t* d_c, size_t count, uint32_t* d_status,
                         void* d_report, uint64_t* d_h_out, hipStream_t stream);
+// plume_sign.hip: d_h_out may be null
+int plume_sign_device(const h2c_prefix& pre, const uint64_t* d_sk, const uint64_t* d_r, size_t count, uint64_t* d_pk, uint64_t* d_nullifier, uint64_t* d_s, uint64_t* d_c,
+                      uint32_t* d_status, uint64_t* d_h_out, hipStream_t stream);
 
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);

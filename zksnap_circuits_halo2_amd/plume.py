@@ -4,8 +4,8 @@ whole batch in one device call.
 
 `compress_point`, `hash_to_curve`, `verify_native` and `gen_native` are the host forms on Python integers, named after the reference's
 (voter_tests/src/lib.rs:25-119); they are this module's own restatement, and tests compare them with the library's C calls and kernels.
-`hash_to_curve_host` and `verify_host` run one voter through the library's host C calls (the headers the kernels run).  `lincomb_device`,
-`hash_to_curve_many_device` and `verify_many_device` run the kernels over device tensors of canonical integers: a point is `[..., 8]` int64
+`hash_to_curve_host`, `verify_host` and `sign_host` run one voter through the library's host C calls (the headers the kernels run).
+`lincomb_device`, `hash_to_curve_many_device`, `verify_many_device` and `sign_many_device` run the kernels over device tensors of canonical integers: a point is `[..., 8]` int64
 (x then y, four little-endian words each), a scalar `[..., 4]`.  There is no CPU fallback for the device calls.
 
 A point is a pair of integers (x, y); the identity is (0, 0).
@@ -254,6 +254,20 @@ def verify_host(msg: bytes, nullifier: Point, pk: Point, s: int, c: int) -> Tupl
     return verdict.value, (x, y)
 
 
+def sign_host(msg: bytes, sk: int, r: int) -> Tuple[Point, Point, int, int, int, Point]:
+    """zkhip_plume_sign -> (pk, nullifier, s, c, status, H(msg, pk)): `gen_native` through the headers the kernel runs; status 2 and zeros for
+    sk or r outside [1, N).  No GPU is touched."""
+    import ctypes as C
+
+    msg = _msg(msg, "sign_host")
+    skw, rw = _words([sk]), _words([r])
+    pk, nul, h = (np.zeros(8, dtype=np.uint64) for _ in range(3))
+    s, c, status = np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64), C.c_uint32(0)
+    _lib.check(_lib.load().zkhip_plume_sign(msg, len(msg), skw.ctypes.data, rw.ctypes.data, pk.ctypes.data, nul.ctypes.data, s.ctypes.data, c.ctypes.data,
+                                            C.addressof(status), h.ctypes.data))
+    return tuple(_decode(pk, 4)), tuple(_decode(nul, 4)), _decode(s, 4)[0], _decode(c, 4)[0], status.value, tuple(_decode(h, 4))
+
+
 # ---- the device calls ----------------------------------------------------------------------------------------------------------------------------
 def lincomb_device(a, p, b, q, stream=None):
     """a, b: [n, 4] scalars (any 256-bit integers); p, q: [n, 8] points -> ([n, 8] a[i] p[i] + b[i] q[i], [n] int32 status: 2 and (0, 0) where a
@@ -318,3 +332,27 @@ def verify_many_device(msg: bytes, pk, nullifier, s, c, stream=None) -> Verdicts
     _lib.check(_lib.load().zkhip_plume_verify_device(msg, len(msg), _ptr(pk), _ptr(nullifier), _ptr(s), _ptr(c), n, _ptr(status), report.data_ptr(), _ptr(h),
                                                      _stream_of(stream)))
     return Verdicts(status, h, report)
+
+
+class Signatures:
+    """what one `sign_many_device` made, device tensors: `pk`, `nullifier` and `h` (H(msg, pk[i])) are [n, 8], `s` and `c` [n, 4], `status` [n]
+    int32 (0, or 2 with zeros in every other tensor where sk or r is outside [1, N)).  Nothing here waits for the stream."""
+
+    def __init__(self, pk, nullifier, s, c, status, h):
+        self.pk, self.nullifier, self.s, self.c, self.status, self.h = pk, nullifier, s, c, status, h
+
+
+def sign_many_device(msg: bytes, sk, r, stream=None) -> Signatures:
+    """sk, r: [n, 4] scalars in [1, N) -> Signatures: `gen_native` of every voter with its own r; one launch, two lanes per voter, no host wait.
+    Meant for generated populations: nothing here is audited for side channels."""
+    import torch
+
+    msg, sk = _msg(msg, "sign_many_device"), _want(sk, 4, "sign_many_device")
+    n = sk.shape[0]
+    r = _want(r, 4, "sign_many_device", n)
+    pk, nullifier, h = (torch.empty((n, 8), dtype=torch.int64, device=sk.device) for _ in range(3))
+    s, c = (torch.empty((n, 4), dtype=torch.int64, device=sk.device) for _ in range(2))
+    status = torch.empty((n,), dtype=torch.int32, device=sk.device)
+    _lib.check(_lib.load().zkhip_plume_sign_device(msg, len(msg), _ptr(sk), _ptr(r), n, _ptr(pk), _ptr(nullifier), _ptr(s), _ptr(c), _ptr(status), _ptr(h),
+                                                   _stream_of(stream)))
+    return Signatures(pk, nullifier, s, c, status, h)

@@ -74,11 +74,36 @@ def compress_nullifier(point: Tuple[int, int]) -> List[int]:
     return [2 + (y & 1)] + [int.from_bytes(raw[at:at + 11], "little") for at in (0, 11, 22)]
 
 
-def nullifier_values(points: Sequence[Tuple[int, int]], stream=None):
-    """secp256k1 affine points (x, y) -> the (n, 4) device tensor of the values the state-transition circuit inserts into the nullifier tree:
-    the width-4 hash of every compressed point, one launch.  `IndexedMerkleTree.insert_batch` takes its host copy."""
+LAYOUT_NULLIFIER, LAYOUT_MEMBER = 0, 1
+
+
+def _is_point_tensor(points) -> bool:
+    return hasattr(points, "data_ptr") and hasattr(points, "is_cuda")
+
+
+def hash_points_device(points, layout: int, stream=None):
+    """points: an (n, 8) int64 device tensor of secp256k1 points as plume.py holds them (canonical x then y, four little-endian words each; any
+    256-bit values) -> (n, 4): the hash of every point's packed message, LAYOUT_NULLIFIER (`compress_nullifier`) or LAYOUT_MEMBER
+    (`pack_member`); the packing runs in the kernel, one launch, no host round trip"""
     import torch
 
+    if points.dim() != 2 or points.shape[1] != 8 or not points.is_cuda or points.dtype != torch.int64:
+        raise ValueError("hash_points_device: an (n, 8) int64 tensor on the device (there is no CPU fallback)")
+    points = points.contiguous()
+    n = points.shape[0]
+    out = torch.empty((n, 4), dtype=torch.int64, device=points.device)
+    _lib.check(_lib.load().zkhip_poseidon_hash_points_device(points.data_ptr() if n else None, n, int(layout), out.data_ptr() if n else None, _stream_of(stream)))
+    return out
+
+
+def nullifier_values(points, stream=None):
+    """secp256k1 affine points -- a sequence of (x, y) integers, or an (n, 8) int64 device tensor (`plume.sign_many_device(..).nullifier`) -> the
+    (n, 4) device tensor of the values the state-transition circuit inserts into the nullifier tree: the width-4 hash of every compressed
+    point, one launch.  A tensor is packed on the device.  `IndexedMerkleTree.insert_batch` takes its host copy."""
+    import torch
+
+    if _is_point_tensor(points):
+        return hash_points_device(points, LAYOUT_NULLIFIER, stream)
     packed = fr_encode([v for P in points for v in compress_nullifier(P)]).reshape(len(points), 4, 4)
     dev = torch.device("cuda", torch.cuda.current_device())
     return hash_many_device(torch.from_numpy(packed.view(np.int64)).to(dev), stream=stream)
@@ -96,10 +121,13 @@ def pack_member(point: Tuple[int, int]) -> List[int]:
     return out
 
 
-def member_leaves(points: Sequence[Tuple[int, int]], stream=None):
-    """secp256k1 public keys (x, y) -> the (n, 4) device tensor of the members tree's leaves: the width-6 hash of every packed key, one launch"""
+def member_leaves(points, stream=None):
+    """secp256k1 public keys -- a sequence of (x, y) integers, or an (n, 8) int64 device tensor (`plume.sign_many_device(..).pk`) -> the (n, 4)
+    device tensor of the members tree's leaves: the width-6 hash of every packed key, one launch.  A tensor is packed on the device."""
     import torch
 
+    if _is_point_tensor(points):
+        return hash_points_device(points, LAYOUT_MEMBER, stream)
     packed = fr_encode([v for P in points for v in pack_member(P)]).reshape(len(points), 6, 4)
     dev = torch.device("cuda", torch.cuda.current_device())
     return hash_many_device(torch.from_numpy(packed.view(np.int64)).to(dev), stream=stream)

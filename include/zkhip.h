@@ -818,6 +818,39 @@ int zkhip_plume_verify(const uint8_t *msg, size_t msg_len, const uint64_t pk[8],
 /* *status 0 and the signature, or 2 and zeros; h_out optional: H(msg, pk) */
 int zkhip_plume_sign(const uint8_t *msg, size_t msg_len, const uint64_t sk[4], const uint64_t r[4], uint64_t pk[8], uint64_t nullifier[8], uint64_t s[4], uint64_t c[4], uint32_t *status, uint64_t h_out[8]);
 
+/* ---- the quotient identity at x: the scalar half of `verify_proof`, a batch of proofs in one call -------------------------------------
+ * [DEP] halo2-axiom plonk/verifier.rs recomputes the expected quotient evaluation from the gate, permutation and lookup expressions at the
+ * challenge x and compares it with h(x) (x^n - 1); the reference's aggregator does so for the voter proof of every ballot
+ * (/root/reference/aggregator/src/wrapper.rs:140-155).  One proof is a few thousand field products, so the unit of work is the batch: every
+ * proof of one circuit is a ROW of one row program (an ordinary zkhip_vm_program), run by the interpreter of zkhip_fr_eval_rows_device (never
+ * the run-time compiler).  Both calls are asynchronous on `stream`, wait for nothing on the host, take their scratch from the stream's
+ * scratch set and return ZKHIP_OK when the check RAN, whatever it found (as the witness checks above).  All elements are in the external Fr
+ * format (4 x u64 Montgomery-256, canonical); device arrays of elements are 16-byte aligned.  Argument errors are ZKHIP_EINVAL, decided on the
+ * host before the device is touched, with nothing enqueued.
+ *
+ * Domain values.  n = 2^k rows; rows 0 .. usable_rows - 1 are usable, row u = usable_rows carries l_last and the n - u - 1 rows behind it are
+ * blinding rows.  With l_i(x) = omega^i (x^n - 1) / (n (x - omega^i)):  l_last = l_u,  l_active = 1 - l_last - sum_{i > u} l_i.
+ * zkhip_fr_domain_points_device: one lane per point; d_out is [4][n_points]: x^n, l_0(x), l_last(x), l_active(x).  A point OF the domain
+ * (x^n = 1) has no closed form: its four values are written as zero, which no other point produces (x^n = 0 only at x = 0, where l_0 = 1 / n).
+ * ZKHIP_EINVAL unless k <= 28, 1 <= usable_rows < 2^k, 2^k - usable_rows <= 64 (the per-lane loop; halo2 circuits have 5 to 10 blinding
+ * rows), n_points >= 1 (at most 2^30), omega canonical, no null or misaligned pointer.
+ *
+ * zkhip_verify_identity_device.  d_evals: [n_proofs][n_evals], one record per proof as it comes off that proof's transcript; d_challenges:
+ * [n_proofs][5] = theta, beta, gamma, y, x.  COLUMNS OF THE PROGRAM (normative): column j < n_evals is evaluation j of the record;
+ * columns n_evals + 0 .. 4 are theta, beta, gamma, y, x; columns n_evals + 5 .. 8 are x^n, l_0(x), l_last(x), l_active(x).  The program's
+ * result must be zero exactly when the identity holds (evaluation.py identity_program builds it from the terms of the prover's quotient).
+ * d_status: int32[n_proofs] -- 0 the identity holds; 1 it does not; 2 x lies in the domain (x^n = 1), so nothing was divided: a verdict,
+ * never a failed call.  d_report: one zkhip_check_report -- `failures` the number of proofs with a status other than 0, `first` the lowest
+ * such index, UINT64_MAX when there is none.  n_proofs == 0: ZKHIP_OK, the report says "no failure", nothing else is written.
+ * ZKHIP_EINVAL: a program zkhip_fr_eval_rows_device rejects over n_evals + 9 columns (a column >= n_evals + 9 included), or one whose
+ * rotation table holds a non-zero rotation, or that reads ZKHIP_SRC_PREV or ZKHIP_SRC_ROWPOW; n_evals == 0 or n_evals + 9 > 65536;
+ * n_proofs > 2^24; the domain arguments as above; a null pointer, d_evals / d_challenges not 16-byte aligned, d_status not 4-byte or d_report
+ * not 8-byte aligned (with n_proofs == 0 the three arrays may be null, d_report never).
+ * Not built: instance columns, multi-phase challenges, folding a batch's pairing checks into one (halo2's BatchVerifier) -- DESIGN.md section 10. */
+int zkhip_fr_domain_points_device(uint32_t k, uint32_t usable_rows, const uint64_t omega[4], const void *d_x, size_t n_points, void *d_out, void *stream);
+int zkhip_verify_identity_device(const zkhip_vm_program *prog, const void *d_evals, uint32_t n_evals, const void *d_challenges, uint32_t k,
+                                 uint32_t usable_rows, const uint64_t omega[4], size_t n_proofs, void *d_status, void *d_report, void *stream);
+
 /* ---- parity hooks for the field / curve layer (rows a1/a2 of SURVEY.md section 8) ------------------ */
 /* field: 0 = Fq, 1 = Fr.  op: 0 mul, 1 add, 2 sub, 3 square (b ignored).  Elementwise on n elements. */
 int zkhip_test_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);

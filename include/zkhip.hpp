@@ -1376,6 +1376,32 @@ inline std::vector<zkhip_check_report> check_lookups_device(const std::vector<co
   return read_check_reports([&](void* d) {
     return zkhip_check_lookups_device(in.data(), tab.data(), (uint32_t)in.size(), k, usable_rows, d, nullptr); }, in.size(), "check_lookups_device");
 }
+// The quotient identity at x (zkhip.h, "the quotient identity at x"): the scalar half of `verify_proof` for a batch of proofs of one circuit.
+// x^n, l_0, l_last, l_active at every point of `x`: out = [4][x.size()]; a point of the domain gets four zeros
+inline void domain_points_device(uint32_t k, uint32_t usable_rows, const Fr& omega, const DeviceVec& x, DeviceVec& out) {
+  if (out.size() < 4 * x.size()) throw std::invalid_argument("domain_points_device: out shorter than 4 x points");
+  check(zkhip_fr_domain_points_device(k, usable_rows, omega.l, x.data(), x.size(), out.data(), nullptr), "domain_points_device");
+}
+struct IdentityVerdicts {
+  std::vector<int32_t> status;       // per proof: 0 the identity holds, 1 it does not, 2 x lies in the domain
+  zkhip_check_report report;         // proofs with a status other than 0, the lowest such index
+};
+// evals = [n_proofs][n_evals] as the proofs' transcripts yield them, challenges = [n_proofs][5] = theta, beta, gamma, y, x; `identity` reads
+// column j < n_evals as evaluation j, n_evals + 0 .. 4 as the challenges, n_evals + 5 .. 8 as x^n, l_0, l_last, l_active
+inline IdentityVerdicts verify_identity_device(const RowProgram& identity, const DeviceVec& evals, uint32_t n_evals, const DeviceVec& challenges, uint32_t k,
+                                               uint32_t usable_rows, const Fr& omega, size_t n_proofs) {
+  if (evals.size() < n_proofs * n_evals || challenges.size() < n_proofs * 5) throw std::invalid_argument("verify_identity_device: records shorter than the batch");
+  IdentityVerdicts out;
+  out.status.assign(n_proofs, 0);
+  const zkhip_vm_program prog = vm_program_of(identity);
+  void* d_status = nullptr;
+  check(zkhip_alloc(n_proofs * sizeof(int32_t) + 16, &d_status), "verify_identity_device");
+  struct release { void* p; ~release() { (void)zkhip_free(p); } } held{d_status};
+  out.report = read_check_reports([&](void* d) {
+    return zkhip_verify_identity_device(&prog, evals.data(), n_evals, challenges.data(), k, usable_rows, omega.l, n_proofs, d_status, d, nullptr); }, 1, "verify_identity_device")[0];
+  if (n_proofs) check(zkhip_download(out.status.data(), d_status, n_proofs * sizeof(int32_t)), "verify_identity_device");
+  return out;
+}
 // Random field elements drawn in HBM (zkhip.h, "random field elements": element i of stream (seed, stream_id) is one ChaCha20 block reduced mod r).
 // The library holds no entropy: `seed` comes from the caller's generator, and a (seed, stream_id, index) triple is never reused across proofs.
 // out[j] = element first + j for every j < out.size(): the vanishing argument's random polynomial, never on the host

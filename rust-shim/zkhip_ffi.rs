@@ -85,6 +85,10 @@ extern "C" {
                                  d_report: *mut c_void, stream: *mut c_void) -> c_int;
     fn zkhip_check_lookups_device(d_inputs: *const *const c_void, d_tables: *const *const c_void, n_lookups: u32, log_n: u32, usable_rows: usize,
                                   d_reports: *mut c_void, stream: *mut c_void) -> c_int;
+    fn zkhip_fr_domain_points_device(k: u32, usable_rows: u32, omega: *const u64, d_x: *const c_void, n_points: usize, d_out: *mut c_void,
+                                     stream: *mut c_void) -> c_int;
+    fn zkhip_verify_identity_device(prog: *const VmProgram, d_evals: *const c_void, n_evals: u32, d_challenges: *const c_void, k: u32, usable_rows: u32,
+                                    omega: *const u64, n_proofs: usize, d_status: *mut c_void, d_report: *mut c_void, stream: *mut c_void) -> c_int;
     fn zkhip_stream_sync(stream: *mut c_void) -> c_int;
     fn zkhip_fr_eval_polynomial_batch_device(d_polys: *const *const c_void, count: usize, n: usize, point: *const u64, d_out: *mut c_void,
                                              stream: *mut c_void) -> c_int;
@@ -638,6 +642,26 @@ impl DevCols {
         // SAFETY: device addresses of >= usable_rows rows each; `d` holds inputs.len() records
         DevCols::check_reports(inputs.len(), "zkhip_check_lookups_device", |d| unsafe {
             zkhip_check_lookups_device(inputs.as_ptr(), tables.as_ptr(), inputs.len() as u32, log_n, usable_rows, d, std::ptr::null_mut()) })
+    }
+    /// x^n, l_0, l_last, l_active at `n_points` points (zkhip.h "the quotient identity at x"): `out` = device address of [4][n_points] elements
+    pub(crate) fn domain_points<F: 'static>(k: u32, usable_rows: u32, omega: &F, x: *const c_void, n_points: usize, out: *mut c_void) -> bool {
+        if !is::<F, Fr>() { return false; }
+        // SAFETY: x holds n_points elements, out 4 * n_points; omega is four words read before the call returns
+        let rc = unsafe { zkhip_fr_domain_points_device(k, usable_rows, omega as *const F as *const u64, x, n_points, out, std::ptr::null_mut()) };
+        if rc != 0 { warn_once("zkhip_fr_domain_points_device", rc); }
+        rc == 0
+    }
+    /// the quotient identity of `n_proofs` proofs of one circuit in one call: `evals` = [n_proofs][n_evals], `challenges` = [n_proofs][5] = theta,
+    /// beta, gamma, y, x; `status` = device address of n_proofs i32 (0 holds, 1 does not, 2 x lies in the domain).  The record counts the proofs
+    /// with a status other than 0 and names the first.  None = the check could not run
+    pub(crate) fn verify_identity<F: 'static>(prog: &VmProgramOwned, evals: *const c_void, n_evals: u32, challenges: *const c_void, k: u32, usable_rows: u32,
+                                              omega: &F, n_proofs: usize, status: *mut c_void) -> Option<CheckReport> {
+        if !is::<F, Fr>() { return None; }
+        let ffi = prog.as_ffi();
+        // SAFETY: `ffi` borrows the Vecs of `prog`, alive for the call; the arrays hold what the sizes say; `d` holds one record
+        DevCols::check_reports(1, "zkhip_verify_identity_device", |d| unsafe {
+            zkhip_verify_identity_device(&ffi, evals, n_evals, challenges, k, usable_rows, omega as *const F as *const u64, n_proofs, status, d,
+                                         std::ptr::null_mut()) }).map(|v| v[0])
     }
     /// rows [0, n) of column `col` = elements first .. first + n - 1 of stream (seed, stream_id) (zkhip.h "random field elements"): the vanishing
     /// argument's random polynomial, drawn where it is committed and opened.  `seed` = `random_seed(&mut rng)`, once per proof

@@ -9,7 +9,12 @@ timed region ends with the verdict on the host.
       into the G1 side (normalisation + small MSMs) and the pairing
   ParamsKZG.verify at k = 22
   the `verify` lap of prove_flow.run(verify=True) beside prove_ms, three warm proofs per shape
-    python tools/verify_time.py [--reps 9] [--shapes 22:4:1,13:256:8,15:64:8] [--no-flow] [--no-srs]"""
+  zkhip_verify_identity_device (the quotient identity at x, csrc/verify_identity.hip) at B = 1, 64 and 4096 proofs on the same plans: the records are
+      random field elements already in HBM (the time does not depend on the verdicts), the program is compiled and marshalled once (that time is
+      printed beside it), a timed region is the call and the statuses and the report back on the host
+  the `verify` lap of the transcript flow with the identity and without it -- the openings alone are what the verifier was before the identity was
+      added --, the two sides in turn in this one process
+    python tools/verify_time.py [--reps 9] [--shapes 22:4:1,13:256:8,15:64:8] [--no-pairing] [--no-flow] [--no-srs] [--no-identity]"""
 import argparse
 import os
 import statistics
@@ -30,6 +35,9 @@ ap.add_argument("--shapes", default="22:4:1,13:256:8,15:64:8")
 ap.add_argument("--no-flow", action="store_true")
 ap.add_argument("--no-srs", action="store_true")
 ap.add_argument("--srs-k", type=int, default=22)
+ap.add_argument("--no-pairing", action="store_true")
+ap.add_argument("--no-identity", action="store_true")
+ap.add_argument("--batches", default="1,64,4096")
 args = ap.parse_args()
 lib = _lib.load()
 R = O.R_MOD
@@ -67,24 +75,25 @@ def pairs(n):
     return g1, g2
 
 
-print(f"zkhip_pairing_check, host form ({args.reps} repetitions, wall ms, the verdict on the host)")
-for n in (2, 64):
-    g1, g2 = pairs(n)
-    assert A.pairing_check(g1, g2)
-    print(f"    n = {n:2d}                                                  {fmt(timed(lambda: A.pairing_check(g1, g2)))}")
-g1, g2 = pairs(2)
-operand = np.concatenate([g1.reshape(-1), g2.reshape(-1)]).astype(np.uint64)
-out = np.zeros(96, dtype=np.uint64)
-med = {}
-for name, flag in (("quad policy", 256), ("single-lane policy", 512)):
-    def run(flag=flag):
-        _lib.check(lib.zkhip_test_fq12_op(11 + flag, operand.ctypes.data, operand.ctypes.data, out.ctypes.data))
-    run()
-    assert out[0 if flag == 256 else 48] == 1
-    ts = timed(run)
-    med[name] = statistics.median(ts)
-    print(f"    two pairs as one serial chain, {name:20s}        {fmt(ts)}")
-print(f"    single-lane / quad = {med['single-lane policy'] / med['quad policy']:.2f}")
+if not args.no_pairing:
+    print(f"zkhip_pairing_check, host form ({args.reps} repetitions, wall ms, the verdict on the host)")
+    for n in (2, 64):
+        g1, g2 = pairs(n)
+        assert A.pairing_check(g1, g2)
+        print(f"    n = {n:2d}                                                  {fmt(timed(lambda: A.pairing_check(g1, g2)))}")
+    g1, g2 = pairs(2)
+    operand = np.concatenate([g1.reshape(-1), g2.reshape(-1)]).astype(np.uint64)
+    out = np.zeros(96, dtype=np.uint64)
+    med = {}
+    for name, flag in (("quad policy", 256), ("single-lane policy", 512)):
+        def run(flag=flag):
+            _lib.check(lib.zkhip_test_fq12_op(11 + flag, operand.ctypes.data, operand.ctypes.data, out.ctypes.data))
+        run()
+        assert out[0 if flag == 256 else 48] == 1
+        ts = timed(run)
+        med[name] = statistics.median(ts)
+        print(f"    two pairs as one serial chain, {name:20s}        {fmt(ts)}")
+    print(f"    single-lane / quad = {med['single-lane policy'] / med['quad policy']:.2f}")
 
 # ---- ParamsKZG.verify ------------------------------------------------------------------------------------------------------------------------
 if not args.no_srs:
@@ -142,3 +151,48 @@ if not args.no_flow:
             assert all(res["checks"].values())
             laps.append((res["timings_ms"]["verify"], res["prove_ms"]))
         print("    flow, three warm proofs: verify lap / prove_ms = " + ", ".join(f"{a:.1f} / {b:.1f}" for a, b in laps))
+
+# ---- the quotient identity at x: the call on its own, and the flow's verify lap with and without it ------------------------------------------------
+if not args.no_identity:
+    import prove_flow
+    from zksnap_circuits_halo2_amd import evaluation as E, prover as P
+
+    def random_elements(*shape):
+        a = torch.randint(-(1 << 63), (1 << 63) - 1, shape + (4,), dtype=torch.int64, device="cuda")
+        a[..., 3] = torch.randint(0, 1 << 61, shape, dtype=torch.int64, device="cuda")          # below r: canonical words
+        return a
+
+    for shape in args.shapes.split(","):
+        k, g, l = (int(x) for x in shape.split(":"))
+        cs = E.halo2_lib_shape(g, l)
+        u = (1 << k) - (cs.blinding_factors + 1)
+        plan = P.opening_plan(cs, g, l, u, False, "halo2")
+        t0 = time.perf_counter()
+        prog = E.identity_program(cs, plan, k)
+        t1 = time.perf_counter()
+        marshalled = prog._marshal()
+        t2 = time.perf_counter()
+        print(f"==== identity at x, shape k = {k}, {g} gate columns, {l} lookups: {len(plan)} evaluations, {len(prog.insns)} instructions, {prog.registers_used()} registers "
+              f"(compiled in {(t1 - t0) * 1e3:.1f} ms, marshalled in {(t2 - t1) * 1e3:.1f} ms, once per key) ====")
+        for B in (int(b) for b in args.batches.split(",")):
+            evals, challenges = random_elements(B, len(plan)), random_elements(B, 5)
+            status, (failures, first) = E.verify_identity_device(marshalled, evals, challenges, k, u)
+            assert len(status) == B and failures == int((status != 0).sum())
+            ts = timed(lambda: E.verify_identity_device(marshalled, evals, challenges, k, u))
+            print(f"    B = {B:5d}                                               {fmt(ts)}   ({statistics.median(ts) / B * 1e3:.2f} us a proof)")
+            del evals, challenges
+        if not args.no_flow:
+            with_identity = prove_flow.verify_transcript_proof
+            openings_alone = lambda params, vk, k_, proof, shape_, plan_, *how: P.verify_transcript_proofs(params, vk, k_, [proof], shape_, plan_, *how, identity=False)[0]
+            laps = {"openings alone": [], "identity + openings": []}
+            try:
+                for _ in range(3):
+                    for name, verifier in (("openings alone", openings_alone), ("identity + openings", with_identity)):
+                        prove_flow.verify_transcript_proof = verifier
+                        res = prove_flow.run(k, g, lookups=l, verbose=False, transcript=True, verify=True)
+                        assert all(res["checks"].values())
+                        laps[name].append(res["timings_ms"]["verify"])
+            finally:
+                prove_flow.verify_transcript_proof = with_identity
+            for name, ts in laps.items():
+                print(f"    transcript flow, verify lap, {name:22s}      {fmt(ts)}   (three proofs; every run makes its key anew, so every lap compiles and marshals the identity once)")

@@ -1913,6 +1913,44 @@ int zkhip_check_lookups_device(const void* const* d_inputs, const void* const* d
   return lookup_check_device(d_inputs, d_tables, n_lookups, usable_rows, d_reports, sc->vm.p, sc->vm.cap, s, &sc->args);
 }
 
+// ---- the quotient identity at x (include/zkhip.h; verify_identity.hip) ---------------------------------------------------------------------------
+// Every refusal is decided before the device is touched (a host without a GPU gets the same ZKHIP_EINVAL); after that nothing waits for the stream.
+static inline bool elems_ptr_ok(const void* p) { return p && ((uintptr_t)p & 15u) == 0; }
+
+int zkhip_fr_domain_points_device(uint32_t k, uint32_t usable_rows, const uint64_t omega[4], const void* d_x, size_t n_points, void* d_out, void* stream) {
+  ZK_API_RANGE();
+  int rc = identity_domain_validate("fr_domain_points", k, usable_rows, omega);
+  if (rc != ZKHIP_OK) return rc;
+  if (n_points < 1 || n_points > ((size_t)1 << 30)) { set_error("fr_domain_points: %zu points", n_points); return ZKHIP_EINVAL; }
+  if (!elems_ptr_ok(d_x) || !elems_ptr_ok(d_out)) { set_error("fr_domain_points: null or misaligned pointer"); return ZKHIP_EINVAL; }
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  return fr_domain_points_device(k, usable_rows, omega, (const uint32_t*)d_x, n_points, (uint32_t*)d_out, caller_stream(stream));
+}
+
+int zkhip_verify_identity_device(const zkhip_vm_program* prog, const void* d_evals, uint32_t n_evals, const void* d_challenges, uint32_t k, uint32_t usable_rows,
+                                 const uint64_t omega[4], size_t n_proofs, void* d_status, void* d_report, void* stream) {
+  ZK_API_RANGE();
+  if (n_evals == 0) { set_error("verify_identity: no evaluations"); return ZKHIP_EINVAL; }
+  int rc = verify_identity_validate(prog, n_evals);
+  if (rc != ZKHIP_OK) return rc;
+  if ((rc = identity_domain_validate("verify_identity", k, usable_rows, omega)) != ZKHIP_OK) return rc;
+  if (n_proofs > ((size_t)1 << 24)) { set_error("verify_identity: %zu proofs in one call", n_proofs); return ZKHIP_EINVAL; }
+  const bool arrays_ok = elems_ptr_ok(d_evals) && elems_ptr_ok(d_challenges) && d_status && ((uintptr_t)d_status & 3u) == 0;
+  if (!report_ptr_ok(d_report) || (n_proofs && !arrays_ok)) {      // (an empty batch names no array)
+    set_error("verify_identity: null or misaligned pointer");
+    return ZKHIP_EINVAL;
+  }
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if (n_proofs && (rc = sc->poly2.reserve(verify_identity_columns_bytes(n_evals, n_proofs))) != ZKHIP_OK) return rc;
+  if (n_proofs && (rc = sc->vm.reserve(verify_identity_vm_bytes(prog, n_evals))) != ZKHIP_OK) return rc;
+  return verify_identity_device(prog, (const uint32_t*)d_evals, n_evals, (const uint32_t*)d_challenges, k, usable_rows, omega, n_proofs, (int32_t*)d_status, d_report,
+                                sc->poly2.p, sc->vm.p, sc->vm.cap, s, &sc->vm_stage);
+}
+
 int zkhip_lookup_permute(const uint64_t* input, const uint64_t* table, size_t usable_rows, uint64_t* permuted_input, uint64_t* permuted_table) {
   ZK_API_RANGE();
   if (usable_rows && (!input || !table || !permuted_input || !permuted_table)) { set_error("lookup_permute: null pointer"); return ZKHIP_EINVAL; }

@@ -685,9 +685,9 @@ void row_vm_halos(const zkhip_vm_program* p, uint64_t* lo, uint64_t* hi) {
 
 // The whole-domain launch (window = false: row0 = 0, count = 2^log_rows, columns indexed modulo the domain) and the window launch (columns
 // are window buffers of halo_lo + count + halo_hi elements, indexed row + halo_lo + offset without a mask).  *compiled (if given): 1 when
-// the run-time compiled kernel took the call, 0 for the interpreter.
+// the run-time compiled kernel took the call, 0 for the interpreter.  allow_jit = false: the interpreter, whatever the shape.
 static int row_vm_run(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, bool window, uint64_t row0, uint64_t count,
-                      int accumulate, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, int* compiled) {
+                      int accumulate, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, int* compiled, bool allow_jit = true) {
   const uint64_t rows = (uint64_t)1 << log_rows;
   if (compiled) *compiled = 0;
   if (ws_bytes < row_vm_workspace_bytes(p, n_columns, log_rows)) { set_error("eval_rows: workspace too small"); return ZKHIP_EINVAL; }
@@ -756,7 +756,7 @@ static int row_vm_run(const zkhip_vm_program* p, const void* const* d_columns, u
   }
   // a short program over many rows runs as compiled straight-line code when a kernel for its shape exists or can be built (rowvm_jit.hip);
   // any failure there leaves nothing launched and the interpreter below takes the call
-  if ((window ? row_vm_jit_wanted_window(p, n_columns, count) : row_vm_jit_wanted(p, n_columns, log_rows)) &&
+  if (allow_jit && (window ? row_vm_jit_wanted_window(p, n_columns, count) : row_vm_jit_wanted(p, n_columns, log_rows)) &&
       row_vm_jit_launch(p, d_columns, n_columns, log_rows, window, L.row0, L.rows, accumulate, L.consts, L.pow_lo, L.pow_hi, d_out, stream) == ZKHIP_OK) {
     if (compiled) *compiled = 1;
     return ZKHIP_OK;
@@ -773,6 +773,13 @@ int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint3
 int row_vm_window_device(const zkhip_vm_program* p, const void* const* d_windows, uint32_t n_columns, uint32_t log_rows, uint64_t row0, uint64_t count,
                          int accumulate, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, int* compiled) {
   return row_vm_run(p, d_windows, n_columns, log_rows, true, row0, count, accumulate, d_out, ws, ws_bytes, stream, staging, compiled);
+}
+
+// `count` independent rows: a window launch over a domain of one row, so that column i is simply `count` elements and nothing wraps.  The
+// program names no rotation but 0 and neither PREV nor ROWPOW (the caller has checked); workspace as row_vm_device with log_rows = 0.
+int row_vm_rows_device(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint64_t count, uint32_t* d_out, void* ws, size_t ws_bytes,
+                       hipStream_t stream, vm_staging* staging) {
+  return row_vm_run(p, d_columns, n_columns, 0, true, 0, count, 0, d_out, ws, ws_bytes, stream, staging, nullptr, false);
 }
 
 int fr_pointwise_mul_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t* d_out, hipStream_t stream) {

@@ -202,6 +202,10 @@ int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint3
 void row_vm_halos(const zkhip_vm_program* p, uint64_t* lo, uint64_t* hi);
 int row_vm_window_device(const zkhip_vm_program* p, const void* const* d_windows, uint32_t n_columns, uint32_t log_rows, uint64_t row0, uint64_t count,
                          int accumulate, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging = nullptr, int* compiled = nullptr);
+// `count` independent rows through the INTERPRETER (never the run-time compiler): column i holds `count` elements, d_out receives `count`.  For
+// programs whose rotations are all 0 and that read neither PREV nor ROWPOW (verify_identity.hip checks); workspace: row_vm_workspace_bytes(p, n_columns, 0)
+int row_vm_rows_device(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint64_t count, uint32_t* d_out, void* ws, size_t ws_bytes,
+                       hipStream_t stream, vm_staging* staging = nullptr);
 int fr_pointwise_mul_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t* d_out, hipStream_t stream);
 int fr_gather_mul_device(const uint32_t* d_a, uint32_t a_len, const uint32_t* d_ia, const uint32_t* d_b, uint32_t b_len, const uint32_t* d_ib, size_t n,
                          uint32_t* d_out, hipStream_t stream);
@@ -284,6 +288,16 @@ int plume_verify_device(const h2c_prefix& pre, const uint64_t* d_pk, const uint6
 // plume_sign.hip: d_h_out may be null
 int plume_sign_device(const h2c_prefix& pre, const uint64_t* d_sk, const uint64_t* d_r, size_t count, uint64_t* d_pk, uint64_t* d_nullifier, uint64_t* d_s, uint64_t* d_c,
                       uint32_t* d_status, uint64_t* d_h_out, hipStream_t stream);
+
+// verify_identity.hip (include/zkhip.h, "the quotient identity at x").  The two validators touch no device; `who` names the call in the error text.
+int identity_domain_validate(const char* who, uint32_t k, uint64_t usable_rows, const uint64_t* omega);
+int fr_domain_points_device(uint32_t k, uint32_t usable_rows, const uint64_t* omega, const uint32_t* d_x, uint64_t n_points, uint32_t* d_out, hipStream_t stream);
+int verify_identity_validate(const zkhip_vm_program* p, uint32_t n_evals);
+size_t verify_identity_columns_bytes(uint32_t n_evals, uint64_t n_proofs);      // cols_ws: the column-major image, the result column, the in-domain flags
+size_t verify_identity_vm_bytes(const zkhip_vm_program* p, uint32_t n_evals);   // vm_ws: the interpreter's workspace
+int verify_identity_device(const zkhip_vm_program* prog, const uint32_t* d_evals, uint32_t n_evals, const uint32_t* d_challenges, uint32_t k, uint32_t usable_rows,
+                           const uint64_t* omega, uint64_t n_proofs, int32_t* d_status, void* d_report, void* cols_ws, void* vm_ws, size_t vm_ws_bytes,
+                           hipStream_t stream, vm_staging* staging = nullptr);
 
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);

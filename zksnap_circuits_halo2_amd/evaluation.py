@@ -347,10 +347,14 @@ def _add_expression(g: Graph, cs: ConstraintSystem, qc: QuotientColumns, e: Expr
 DELTA = pow(7, 1 << F.S, F.R_MOD)     # `Fr::DELTA` = g^(2^S), generator of the odd-order subgroup cosets
 
 
-def _evaluate_h_terms(cs: ConstraintSystem, beta: int, gamma: int, theta: int, challenges: Sequence[int], zeta: int):
+def _evaluate_h_terms(cs: ConstraintSystem, beta, gamma, theta, challenges: Sequence[int], zeta: int, point=None):
     """The terms `evaluate_h` folds with y, in the order of [DEP] plonk/evaluation.rs `Evaluator::evaluate_h` (custom gates, permutation,
-    lookups), each as a builder `term(g) -> node` so that one graph (the whole quotient numerator) or several (its parts) can be made."""
+    lookups), each as a builder `term(g) -> node` so that one graph (the whole quotient numerator) or several (its parts) can be made.
+    The prover hands in beta, gamma and theta as integers (constants of the program) and evaluates over the extended coset, where the
+    permutation's X is zeta omega^row.  The verifier's restatement (`identity_program`) hands in builders `g -> node` for the three
+    challenges and `point`, a builder of X itself: the same terms at one point, beta X in place of beta zeta omega^row."""
     qc = quotient_columns(cs)
+    value = lambda g, v: v(g) if callable(v) else g.const(v)
     last_rotation = -(cs.blinding_factors + 1)
     terms = []
     for polys in cs.gates:                                              # custom gates: Horner(PreviousValue = 0, all gate polynomials in order, y)
@@ -371,19 +375,19 @@ def _evaluate_h_terms(cs: ConstraintSystem, beta: int, gamma: int, theta: int, c
 
         def perm_set(g, s_):
             # current_delta = beta * zeta * delta^j * extended_omega^row
-            x_term = g.mul(g.rowpow(), g.const(beta * zeta % F.R_MOD))
+            x_term = g.mul(g.rowpow(), g.const(beta * zeta % F.R_MOD)) if point is None else g.mul(value(g, beta), point(g))
             chunk = cs.permutation_columns[s_ * cs.chunk_len:(s_ + 1) * cs.chunk_len]
             left = z(g, s_, 1)
             for j, (kind, idx) in enumerate(chunk):
                 v = g.col(col_of[kind] + idx)
                 sig = g.col(qc.sigma + s_ * cs.chunk_len + j)
-                left = g.mul(left, g.add(g.mad(sig, g.const(beta), v), g.const(gamma)))          # v + beta sigma + gamma
+                left = g.mul(left, g.add(g.mad(sig, value(g, beta), v), value(g, gamma)))        # v + beta sigma + gamma
             right = z(g, s_)
             delta_pow = pow(DELTA, s_ * cs.chunk_len, F.R_MOD)
             for (kind, idx) in chunk:
                 v = g.col(col_of[kind] + idx)
                 cur = x_term if delta_pow == 1 else g.mul(x_term, g.const(delta_pow))
-                right = g.mul(right, g.add(g.add(v, cur), g.const(gamma)))                       # v + delta^j beta X + gamma
+                right = g.mul(right, g.add(g.add(v, cur), value(g, gamma)))                      # v + delta^j beta X + gamma
                 delta_pow = delta_pow * DELTA % F.R_MOD
             return g.mul(g.sub(left, right), l_active(g))
 
@@ -395,16 +399,16 @@ def _evaluate_h_terms(cs: ConstraintSystem, beta: int, gamma: int, theta: int, c
         ptab = lambda g, li=li: g.col(qc.lookup + 3 * li + 2)
 
         def table_value(g, lk=lk):
-            zero, th = g.const(0), g.const(theta)
+            zero, th = g.const(0), value(g, theta)
             cin = g.horner(zero, [_add_expression(g, cs, qc, e, challenges) for e in lk.input_expressions], th)
             ctab = g.horner(zero, [_add_expression(g, cs, qc, e, challenges) for e in lk.table_expressions], th)
-            return g.mul(g.add(cin, g.const(beta)), g.add(ctab, g.const(gamma)))
+            return g.mul(g.add(cin, value(g, beta)), g.add(ctab, value(g, gamma)))
 
         a_minus_s = lambda g, pin=pin, ptab=ptab: g.sub(pin(g), ptab(g))
         terms.append(lambda g, prod=prod: g.mul(g.sub(one(g), prod(g)), l0(g)))
         terms.append(lambda g, prod=prod: g.mul(g.sub(g.mul(prod(g), prod(g)), prod(g)), l_last(g)))
         terms.append(lambda g, prod=prod, pin=pin, ptab=ptab, table_value=table_value: g.mul(
-            g.sub(g.mul(g.mul(prod(g, 1), g.add(pin(g), g.const(beta))), g.add(ptab(g), g.const(gamma))), g.mul(prod(g), table_value(g))), l_active(g)))
+            g.sub(g.mul(g.mul(prod(g, 1), g.add(pin(g), value(g, beta))), g.add(ptab(g), value(g, gamma))), g.mul(prod(g), table_value(g))), l_active(g)))
         terms.append(lambda g, a_minus_s=a_minus_s: g.mul(a_minus_s(g), l0(g)))
         terms.append(lambda g, a_minus_s=a_minus_s, pin=pin: g.mul(g.mul(a_minus_s(g), g.sub(pin(g), pin(g, -1))), l_active(g)))
     return terms
@@ -455,6 +459,121 @@ def evaluate_h_parts(cs: ConstraintSystem, k: int, extended_k: int, beta: int, g
         progs.append(_fold_terms(terms[lo:hi], y, k, extended_k))
         weights.append(pow(y, T - hi, F.R_MOD))
     return progs, weights
+
+
+# ---------------------------------------------------------------------------------------------------
+# the quotient identity at x: the verifier's restatement of the same terms (zkhip_verify_identity_device)
+# ---------------------------------------------------------------------------------------------------
+# columns behind a proof's evaluations, in the order include/zkhip.h fixes
+ID_THETA, ID_BETA, ID_GAMMA, ID_Y, ID_X, ID_XN, ID_L0, ID_L_LAST, ID_L_ACTIVE = range(9)
+IDENTITY_DERIVED = 9
+
+
+class _IdentityGraph(Graph):
+    """A Graph whose `col(quotient column, rotation)` is the plan's slot of that opening: the terms of `_evaluate_h_terms` name the prover's
+    columns, the verifier holds one evaluation per opened (kind, index, rotation) triple.  l_0 / l_last / l_active are the derived columns."""
+
+    def __init__(self, cs: ConstraintSystem, plan, k: int):
+        super().__init__()
+        qc = quotient_columns(cs)
+        self.n, self.n_evals = 1 << k, len(plan)
+        self.slot: Dict[Tuple[str, int, int], int] = {}
+        for i, (kind, idx, rot) in enumerate(plan):
+            self.slot.setdefault((kind, idx, rot % self.n), i)
+        self.kind_of = {qc.fixed + i: ("fixed", i) for i in range(cs.num_fixed)}
+        self.kind_of.update({qc.advice + i: ("advice", i) for i in range(cs.num_advice)})
+        self.kind_of.update({qc.sigma + i: ("sigma", i) for i in range(len(cs.permutation_columns))})
+        self.kind_of.update({qc.perm_product + i: ("perm", i) for i in range(cs.num_permutation_sets)})
+        for li in range(len(cs.lookups)):
+            self.kind_of.update({qc.lookup + 3 * li + j: (kind, li) for j, kind in enumerate(("lookup_z", "lookup_pa", "lookup_ps"))})
+        self.derived_of = {qc.l0: ID_L0, qc.l_last: ID_L_LAST, qc.l_active_row: ID_L_ACTIVE}
+
+    def derived(self, which: int) -> int:
+        return self._add(("col", self.n_evals + which, 0))
+
+    def opened(self, kind: str, idx: int, rot: int = 0) -> int:
+        key = (kind, idx, rot % self.n)
+        if key not in self.slot:
+            raise ValueError(f"identity_program: the identity reads {kind} {idx} at rotation {rot}, which the plan does not open")
+        return self._add(("col", self.slot[key], 0))
+
+    def col(self, column: int, rot: int = 0) -> int:
+        if column in self.derived_of:
+            return self.derived(self.derived_of[column])
+        return self.opened(*self.kind_of[column], rot)
+
+
+def _expression_kinds(e: Expr, out: set) -> set:
+    out.add(e.kind)
+    for child in (e.a, e.b):
+        if isinstance(child, Expr):
+            _expression_kinds(child, out)
+    return out
+
+
+def identity_program(cs: ConstraintSystem, plan, k: int) -> RowProgram:
+    """The quotient identity at x as a row program over ONE PROOF PER ROW (zkhip_verify_identity_device): the y-fold of exactly the terms of
+    `_evaluate_h_terms` -- custom gates, permutation, lookups, the source the prover's quotient program is built from, so that the two cannot
+    drift apart -- minus (h_0 + x^n h_1 + x^2n h_2)(x^n - 1): zero exactly when the evaluations of a proof satisfy the circuit at x.
+    `plan`: the opened (kind, index, rotation) triples in the order a proof's evaluations are written (prover.opening_plan); a column at a
+    rotation reads the slot of (kind, index, rotation mod 2^k).  theta, beta, gamma, y, x and x^n, l_0, l_last, l_active are the nine columns
+    behind the evaluations.  ValueError: a triple the expressions need and the plan does not open; instance columns and `Challenge`
+    expressions (multi-phase challenges), neither of which is built."""
+    kinds = set()
+    for e in [p for polys in cs.gates for p in polys] + [e for lk in cs.lookups for e in list(lk.input_expressions) + list(lk.table_expressions)]:
+        _expression_kinds(e, kinds)
+    if cs.num_instance or "instance" in kinds or any(kind == "instance" for kind, _ in cs.permutation_columns):
+        raise ValueError("identity_program: instance columns are not built (the verifier would evaluate them from the public inputs)")
+    if "challenge" in kinds:
+        raise ValueError("identity_program: Challenge expressions (multi-phase challenges) are not built")
+    g = _IdentityGraph(cs, plan, k)
+    theta, beta, gamma, x = (lambda g_, which=which: g_.derived(which) for which in (ID_THETA, ID_BETA, ID_GAMMA, ID_X))
+    Y, value = g.derived(ID_Y), g.const(0)
+    for term in _evaluate_h_terms(cs, beta, gamma, theta, (), 1, point=x):
+        value = g.mad(value, Y, term(g))
+    xn = g.derived(ID_XN)
+    h = g.mad(g.mad(g.opened("h", 2), xn, g.opened("h", 1)), xn, g.opened("h", 0))
+    prog = compile_graph(g, g.sub(value, g.mul(h, g.sub(xn, g.const(1)))))
+    prog.n_columns = len(plan) + IDENTITY_DERIVED
+    return prog
+
+
+def domain_points_device(k: int, usable_rows: int, x, out=None, stream=None):
+    """x^n, l_0(x), l_last(x), l_active(x) at every point of `x` ((points, 4) int64 device tensor): a (4, points, 4) tensor
+    (zkhip_fr_domain_points_device); a point of the domain gets four zeros."""
+    import torch
+
+    points = x.shape[0]
+    if out is None:
+        out = torch.empty((4, points, 4), dtype=torch.int64, device=x.device)
+    if not x.is_cuda or not x.is_contiguous() or not out.is_contiguous() or out.numel() < 16 * points:
+        raise ValueError("domain_points_device: contiguous device tensors, the output four times the points")
+    omega = F.fr_encode([F.omega_for(k)])[0]
+    _lib.check(_lib.load().zkhip_fr_domain_points_device(k, usable_rows, omega.ctypes.data, x.data_ptr(), points, out.data_ptr(), stream))
+    return out
+
+
+def verify_identity_device(prog, evals, challenges, k: int, usable_rows: int, stream=None):
+    """The identity of a batch in one call (zkhip_verify_identity_device).  prog: `identity_program(...)` or its `_marshal()` pair (a caller
+    that verifies many batches under one key marshals once); evals: (proofs, n_evals, 4), challenges: (proofs, 5, 4) = theta, beta, gamma, y,
+    x, int64 device tensors.  Returns (status, (failures, first)): an int32 array per proof -- 0 holds, 1 does not, 2 x lies in the domain --
+    and the report as integers (first = 2^64 - 1: none).  Waits for the verdicts."""
+    import torch
+
+    proofs, n_evals = evals.shape[0], evals.shape[1]
+    if not (evals.is_cuda and evals.is_contiguous() and challenges.is_cuda and challenges.is_contiguous()) or tuple(challenges.shape) != (proofs, 5, 4):
+        raise ValueError("verify_identity_device: contiguous device tensors, (proofs, n_evals, 4) and (proofs, 5, 4)")
+    marshalled, keep = prog._marshal() if isinstance(prog, RowProgram) else prog
+    status = torch.empty(max(proofs, 1), dtype=torch.int32, device=evals.device)
+    report = torch.empty(2, dtype=torch.int64, device=evals.device)
+    omega = F.fr_encode([F.omega_for(k)])[0]
+    _lib.check(_lib.load().zkhip_verify_identity_device(C.byref(marshalled), evals.data_ptr(), n_evals, challenges.data_ptr(), k, usable_rows, omega.ctypes.data,
+                                                        proofs, status.data_ptr(), report.data_ptr(), stream))
+    if stream is not None:
+        _lib.check(_lib.load().zkhip_stream_sync(stream))
+    failures, first = (int(v) for v in report.cpu().numpy().view(np.uint64))
+    del keep
+    return status[:proofs].cpu().numpy(), (failures, first)
 
 
 def run_programs_sum_device(progs: Sequence[RowProgram], weights: Sequence[int], columns: Sequence[int], log_rows: int, out: int, stream: int = 0) -> None:

@@ -9,7 +9,8 @@ multi-open -- the steps of [DEP] halo2-axiom plonk/prover.rs, each a method of `
   SeededChallenges / TranscriptChallenges where challenges come from; each has its own order of steps (Prover._seeded, Prover._transcript)
   opening_plan        the opened (kind, index, rotation) triples; the prover and both verifiers turn them into queries through one
                       (kind, index) map each
-  verify_transcript_proof                 the verifier of a proof given as bytes
+  verify_transcript_proofs                the verifier of a batch of proofs given as bytes: the quotient identity at x of all of them in one device
+                      call, then the openings of those that passed (verify_transcript_proof: the batch of one)
 
 `lap` is a callable handed a name at every phase boundary (tools/prove_flow.py times the phases with it); None: no laps, so no synchronisation
 is added for timing (the phases that read a value back -- whether a product closes, the evaluations as integers -- still wait for it)."""
@@ -218,45 +219,107 @@ def multiopen_classes(multiopen):
     return MULTIOPEN[multiopen]
 
 
-def verify_transcript_proof(params, vk, k, proof, shape, plan, hash="blake2b", multiopen="shplonk"):
-    """The verifier of a proof written through TranscriptChallenges: it is handed the parameters, the verifying key, the proof BYTES, and what a
-    verifier knows of the circuit -- `shape` (how many advice columns, lookups, permutation sets, whether a random polynomial is committed) and
-    `plan` (the opened (kind, index, rotation) triples, in the order their evaluations were written).  It replays the prover's order with reads
-    -- commitments land on the device as affine points, evaluations as integers --, derives every challenge itself and ends in
-    `VerifierSHPLONK.verify_proof_transcript` (multiopen="gwc": `VerifierGWC.verify_proof_transcript`); hash: the transcript the proof was
-    written under ("blake2b" or "poseidon").  The verifier's scalar half (the gates' identity at x) is out of scope.
-    Bytes that do not decode reject."""
+def _read_proof_head(r, vk_repr, shape, plan):
+    """a proof up to its evaluations, in the prover's order: (commitments by (kind, index), (theta, beta, gamma, y, x), the evaluations as
+    integers); the reader is left in front of the multi-open's part.  ZkhipError(-1): bytes that do not decode"""
     def xyz(points):                                       # device affine points -> Jacobian limbs with z = 1 for the host-side accumulation
         return [MO._affine_to_xyz(p_) for p_ in points.cpu().numpy().view(np.uint64).reshape(-1, 8)]
 
+    n_adv, n_lk, n_sets = shape["advice"], shape["lookups"], shape["permutation_sets"]
+    r.common_scalar(vk_repr)
+    com = {("advice", i): c_ for i, c_ in enumerate(xyz(r.read_points(n_adv)))}
+    theta = r.squeeze_challenge()
+    if n_lk:
+        for j, c_ in enumerate(xyz(r.read_points(2 * n_lk))):
+            com[("lookup_pa" if j % 2 == 0 else "lookup_ps", j // 2)] = c_
+    beta, gamma = r.squeeze_challenge(), r.squeeze_challenge()
+    for j, c_ in enumerate(xyz(r.read_points(n_sets + n_lk))):
+        com[("perm", j) if j < n_sets else ("lookup_z", j - n_sets)] = c_
+    if shape["random_poly"]:
+        com[("random", 0)] = xyz(r.read_points(1))[0]
+    y = r.squeeze_challenge()
+    for i, c_ in enumerate(xyz(r.read_points(3))):
+        com[("h", i)] = c_
+    x = r.squeeze_challenge()
+    return com, (theta, beta, gamma, y, x), r.read_scalars(len(plan))
+
+
+def identity_program_of(vk, plan, k):
+    """the quotient identity of the key's circuit over `plan` (evaluation.identity_program), compiled and marshalled once per (key, plan): kept
+    on the key object, so it lives as long as the key does.  ValueError: a key without its constraint system"""
+    if getattr(vk, "cs", None) is None:
+        raise ValueError("the verifying key carries no constraint system (vk.cs): the verifier cannot state the circuit's identity")
+    cache = vk.__dict__.setdefault("_identity_programs", {})
+    key = (k, tuple(plan))
+    if key not in cache:
+        cache[key] = E.identity_program(vk.cs, plan, k)._marshal()
+    return cache[key]
+
+
+def identity_statuses(vk, k, plan, evals, challenges):
+    """zkhip_verify_identity_device over a batch: evals[i] the integers of proof i in the plan's order, challenges[i] = (theta, beta, gamma, y,
+    x).  An int32 array: 0 the identity holds, 1 it does not, 2 x lies in the domain."""
+    if not evals:
+        return np.zeros(0, dtype=np.int32)
+    prog = identity_program_of(vk, plan, k)
+    d_evals = torch.from_numpy(F.fr_encode([e_ for row in evals for e_ in row]).view(np.int64).reshape(len(evals), len(plan), 4)).to(DEV)
+    d_challenges = torch.from_numpy(F.fr_encode([c_ for row in challenges for c_ in row]).view(np.int64).reshape(len(evals), 5, 4)).to(DEV)
+    return E.verify_identity_device(prog, d_evals, d_challenges, k, (1 << k) - (vk.cs.blinding_factors + 1))[0]
+
+
+def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b", multiopen="shplonk", *, identity=True):
+    """The verifier of a BATCH of proofs of one circuit, each written through TranscriptChallenges: it is handed the parameters, the verifying key
+    (with its constraint system, `vk.cs`), the proofs' BYTES, and what a verifier knows of the circuit -- `shape` (how many advice columns,
+    lookups, permutation sets, whether a random polynomial is committed) and `plan` (the opened (kind, index, rotation) triples, in the order
+    their evaluations were written).  Every proof's head is replayed with reads -- commitments land on the device as affine points, evaluations
+    as integers, every challenge is derived here --; then the two halves of halo2's `verify_proof`:
+      the identity   the gate, permutation and lookup expressions at x against h(x) (x^n - 1), for ALL proofs in one device call
+                     (zkhip_verify_identity_device; the program is compiled once per key and plan);
+      the openings   for the proofs whose identity holds, `VerifierSHPLONK.verify_proof_transcript` (multiopen="gwc":
+                     `VerifierGWC.verify_proof_transcript`), one pairing check each.
+    A proof is accepted when both accept; bytes that do not decode reject that proof alone.  hash: the transcript the proofs were written under
+    ("blake2b" or "poseidon").  identity=False leaves the first half out (the openings alone: what a test uses to show WHICH half refused).
+    Not built: one folded pairing check for the batch (halo2's BatchVerifier), instance columns, multi-phase challenges.
+    Returns a list of bools."""
+    import contextlib
+
+    verifier = multiopen_classes(multiopen)[1]
+    reader = transcript_classes(hash)[1]
+    if identity:
+        identity_program_of(vk, plan, k)                   # a key that cannot state its identity is the caller's error, whatever the proofs are
     vk_io = io.BytesIO()
     vk.write(vk_io, KG.RAW_BYTES)
-    n_adv, n_lk, n_sets = shape["advice"], shape["lookups"], shape["permutation_sets"]
-    verifier = multiopen_classes(multiopen)[1]
-    with transcript_classes(hash)[1](bytes(proof)) as r:
-        try:
-            r.common_scalar(vk_transcript_repr(vk_io.getvalue()))
-            com = {("advice", i): c_ for i, c_ in enumerate(xyz(r.read_points(n_adv)))}
-            r.squeeze_challenge()                          # theta
-            if n_lk:
-                for j, c_ in enumerate(xyz(r.read_points(2 * n_lk))):
-                    com[("lookup_pa" if j % 2 == 0 else "lookup_ps", j // 2)] = c_
-            r.squeeze_challenge(), r.squeeze_challenge()   # beta, gamma
-            for j, c_ in enumerate(xyz(r.read_points(n_sets + n_lk))):
-                com[("perm", j) if j < n_sets else ("lookup_z", j - n_sets)] = c_
-            if shape["random_poly"]:
-                com[("random", 0)] = xyz(r.read_points(1))[0]
-            r.squeeze_challenge()                          # y
-            for i, c_ in enumerate(xyz(r.read_points(3))):
-                com[("h", i)] = c_
-            x = r.squeeze_challenge()
-            evals = r.read_scalars(len(plan))
-        except _lib.ZkhipError as e:
-            if e.code == -1:
-                return False
-            raise
-        com.update(_key_commitments(vk))
-        return verifier(params).verify_proof_transcript(verifier_queries(plan, com, evals, x, k), r)
+    vk_repr = vk_transcript_repr(vk_io.getvalue())
+    verdicts = [False] * len(proofs)
+    with contextlib.ExitStack() as stack:
+        heads = {}
+        for i, proof in enumerate(proofs):
+            r = stack.enter_context(reader(bytes(proof)))
+            try:
+                heads[i] = (r,) + _read_proof_head(r, vk_repr, shape, plan)
+            except _lib.ZkhipError as e:
+                if e.code != -1:
+                    raise
+        order = sorted(heads)
+        if identity:
+            status = identity_statuses(vk, k, plan, [heads[i][3] for i in order], [heads[i][2] for i in order])
+            order = [i for i, s_ in zip(order, status) if s_ == 0]
+        key_com = _key_commitments(vk)
+        for i in order:
+            r, com, challenges, evals = heads[i]
+            com.update(key_com)
+            try:
+                verdicts[i] = bool(verifier(params).verify_proof_transcript(verifier_queries(plan, com, evals, challenges[4], k), r))
+            except _lib.ZkhipError as e:                   # the multi-open's own points do not decode
+                if e.code != -1:
+                    raise
+    return verdicts
+
+
+def verify_transcript_proof(params, vk, k, proof, shape, plan, hash="blake2b", multiopen="shplonk"):
+    """The verifier of one proof given as bytes: `verify_transcript_proofs` over a batch of one -- the identity at x and the openings, accepted
+    when both accept.  ValueError: a verifying key without its constraint system."""
+    return verify_transcript_proofs(params, vk, k, [proof], shape, plan, hash, multiopen)[0]
 
 
 # ---- the witness -------------------------------------------------------------------------------------------------------------------------------

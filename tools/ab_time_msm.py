@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """A/B helper: median / min time of the prepared MSM (2^L) over many runs, and the median of every phase (in-library HIP events).
-  ab_time_msm.py [log_n=20] [reps=100] [label]      knobs: ZKHIP_MAX_WINDOW (cap the prepared window), ZKHIP_TASK_SHIFT (task length 2^s),
-  ZKHIP_MSM_PIECES (bucket-range pieces of the wide path), ZKHIP_NO_OVERLAP=1 (no second stream: the pieces run one after the other)
-Run the variants alternately in one gpurun call: box-to-box differences (+-4 %) exceed most single-kernel effects."""
+  ab_time_msm.py [log_n=20] [reps=100] [label]
+To compare two variants, build each into its own libzkhip.so and select it with ZKHIP_LIB_PATH=<path to the library> (_lib.py); the library
+has no tuning variables.  Run the variants alternately in one job on one box: box-to-box differences (+-4 %) exceed most single-kernel effects."""
 import os, sys, ctypes as C, statistics as st
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import numpy as np, torch

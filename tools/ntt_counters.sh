@@ -1,5 +1,6 @@
 #!/bin/bash
-# SQ counters of the NTT kernel alone (NTT 2^24, 5 transforms), for A/B variants selected by environment knobs.
+# SQ counters of the NTT kernel alone (NTT 2^24, 5 transforms).  To compare two variants, build each into its own libzkhip.so and pass
+# ZKHIP_LIB_PATH=<path to the library> (_lib.py): the library has no tuning variables.
 #   bash tools/ntt_counters.sh <tag> [VAR=value ...]      -> gpurun_out/<tag>_ntt_sq.txt
 set -e
 TAG=$1; shift

@@ -48,18 +48,13 @@ struct win_layout { int c, W, narrow; };
 __host__ __device__ __forceinline__ int win_bits(const win_layout& L, int w) { return w < L.W - L.narrow ? L.c : L.c - 1; }
 __host__ __device__ __forceinline__ int win_off(const win_layout& L, int w) { const int full = L.W - L.narrow; return w <= full ? w * L.c : full * L.c + (w - full) * (L.c - 1); }
 static int msm_narrow_windows(int c, int W) {
-  static const bool uniform = getenv("ZKHIP_UNIFORM_WINDOWS") != nullptr;      // A/B knob (read once: tables and digits of a process agree)
-  if (c <= 16 || uniform) return 0;
+  if (c <= 16) return 0;
   const int narrow = W * c - 256;
   return narrow > 0 && narrow <= W ? narrow : 0;
 }
 constexpr int MAX_TASK_LEN = 128;       // tasks are 2^task_shift entries, task_shift <= 7 (length histograms hold MAX_TASK_LEN + 1 counters)
 constexpr int TASK_SHIFT = 6;           // 64 entries per accumulate task: short tasks keep the tail of the launch balanced
                                         // (measured at 2^22: 5.9 ms with 64-entry tasks, 6.9 ms with 256, 8.1 ms with 512)
-
-struct task_t {
-  uint32_t bucket, start, len;
-};
 
 // ------------------------------------------------------------------------------------------------
 // XYZZ <-> global memory (array of 36-word structs)
@@ -113,8 +108,8 @@ __device__ __forceinline__ void store_fe9_generic(uint32_t* p, size_t idx, const
 // ------------------------------------------------------------------------------------------------
 // 1. digits
 // ------------------------------------------------------------------------------------------------
-template <typename DIGIT>   // int16_t for c <= 16, int32_t for the wide windows of the prepared path
-__global__ void __launch_bounds__(256) k_digits(const uint32_t* __restrict__ scalars, DIGIT* __restrict__ digits,
+// int16 digits of the one-level sort (c <= 16); the two-level sort's int32 digits come from k_digits_wide and k_digits_glv
+__global__ void __launch_bounds__(256) k_digits(const uint32_t* __restrict__ scalars, int16_t* __restrict__ digits,
                                                 uint32_t n, uint32_t n_pad, int c, int W, uint32_t K, size_t scalar_stride, int narrow) {
   // batch: K scalar vectors (vector k at scalars + k * scalar_stride elements); digits are laid out [W][K][n_pad]
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -149,7 +144,7 @@ __global__ void __launch_bounds__(256) k_digits(const uint32_t* __restrict__ sca
     v += carry;
     int32_t d;
     if (v >= half) { d = (int32_t)v - (int32_t)(1u << cw); carry = 1; } else { d = (int32_t)v; carry = 0; }
-    digits[(size_t)win * row + i] = (DIGIT)d;
+    digits[(size_t)win * row + i] = (int16_t)d;
   }
 }
 
@@ -427,8 +422,8 @@ __global__ void __launch_bounds__(1024) k_sort_pass(const int16_t* __restrict__ 
 
 // (Recomputing the digits from the scalars in both passes instead of storing them as int32 was tried and measured slower:
 // 0.139 vs 0.117 ms at 2^20, 1.75 vs 1.3 ms at 2^24.)
-// The group counts as a pass of their own over the stored digits: what the pipeline ran until round 3, when the counts moved into the digit
-// kernel (k_digits_wide); kept as the A/B reference (ZKHIP_NO_FUSED_COUNT=1).
+// The group counts as a pass of their own over the stored digits, for the GLV digits only: the prepared path's digit kernel (k_digits_wide)
+// has counted the groups on the way since round 3.
 __global__ void __launch_bounds__(1024) k_coarse_count(const int32_t* __restrict__ digits, uint32_t n_pad, uint32_t chunk, uint32_t* __restrict__ gcount, uint32_t gstride) {
   __shared__ uint32_t cnt[MAX_GROUPS];
   const int win = blockIdx.y;
@@ -600,10 +595,7 @@ __global__ void __launch_bounds__(64) k_group_offsets(const uint32_t* __restrict
 // LDS histogram of the fine bucket ids of staged entries [start, end).  The sort kernels spent 77 - 84 % of their cycles parked
 // (profiles/r02_rocprofv3_pmc_sq_issue.txt): with one load per lane and iteration, each feeding an LDS atomic, every trip exposes a full
 // memory latency.  Four independent loads are issued before the first atomic.
-#ifndef ZKHIP_FINE_BATCH
-#define ZKHIP_FINE_BATCH 7
-#endif
-constexpr int FINE_BATCH = ZKHIP_FINE_BATCH;      // measured (2 / 4 / 7 / 14 / 28 loads in flight per lane): see (profiles/r03_msm_sort_pipelining_ab.txt)
+constexpr int FINE_BATCH = 7;      // measured (2 / 4 / 7 / 14 / 28 loads in flight per lane): see (profiles/r03_msm_sort_pipelining_ab.txt)
 __device__ __forceinline__ void fine_histogram(const uint16_t* __restrict__ stage_fine, uint32_t start, uint32_t end, uint32_t* __restrict__ cur) {
   for (uint32_t p = start + threadIdx.x; p < end; p += FINE_BATCH * blockDim.x) {
     uint32_t f[FINE_BATCH];
@@ -1285,8 +1277,7 @@ __global__ void __launch_bounds__(128) k_pyramid_step(const uint32_t* __restrict
   const int win = blockIdx.y;
   const uint32_t* wi = in + (size_t)win * in_stride * 36;
   uint32_t* wo = out + (size_t)win * out_stride * 36;
-  // grid stride: the host may launch fewer threads than additions (ZKHIP_PYR_PERSIST: one resident round of waves that loop, instead of
-  // several rounds of one-addition waves that all start with their loads at the same moment)
+  // grid stride: correct for a grid of fewer threads than additions (the host launches one thread per addition)
 #pragma unroll 1
   for (uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x; tid < per_win; tid += gridDim.x * blockDim.x) {
     uint32_t ia, ib;
@@ -1427,12 +1418,7 @@ static bool msm_top_window_is_degenerate(int c) {
   return top_bits > 0 && top_bits < 6;
 }
 
-// general path: GLV halves the scalars (k_digits_glv): 2n points, 127-bit magnitudes, W = ceil(128 / c) windows.  ZKHIP_NO_GLV=1: the
-// plain 254-bit digits (A/B knob).
-static bool msm_glv_enabled() {
-  static const bool on = getenv("ZKHIP_NO_GLV") == nullptr;
-  return on;
-}
+// general path: GLV halves the scalars (k_digits_glv): 2n points, 127-bit magnitudes, W = ceil(128 / c) windows.
 // windows of c bits: ceil(256 / c) for 254-bit scalars (the signed recoding's last carry lands in the spare top bits); for the GLV halves
 // (magnitudes below 0.979 * 2^127) ceil(128 / c), plus one when the top window would otherwise overflow: with c W = 128 the top window
 // holds up to 0.49 * 2^c and a carry of 1 must still leave it below 2^(c-1) -- true for c = 8 (125 + 1 < 128) and c = 16, not for c = 2
@@ -1443,15 +1429,14 @@ static inline int msm_windows(int c, bool glv) {
 }
 
 int msm_pick_window(size_t n) {
-  // cost model in field multiplications: W * (10 n' + 2 * 14 * 2^(c-1)); c <= 16 (int16 digits, 128 KiB LDS).  Without GLV n' = n points
-  // and W = ceil(256 / c); with it n' = 2 n and W = ceil(128 / c).  Window sizes whose top window would hold 1..5 bits are skipped.
-  const bool glv = msm_glv_enabled();
+  // cost model in field multiplications: W * (10 n' + 2 * 14 * 2^(c-1)); c <= 16 (int16 digits, 128 KiB LDS).  The general path splits its
+  // scalars (GLV): n' = 2 n points and W = ceil(128 / c).  Window sizes whose top window would hold 1..5 bits are skipped.
   int best = 16;
   double best_cost = 1e300;
   for (int c = 2; c <= 16; c++) {
-    const int Wi = msm_windows(c, glv), top_bits = (glv ? 127 : 254) - (Wi - 1) * c;
+    const int Wi = msm_windows(c, true), top_bits = 127 - (Wi - 1) * c;
     if (top_bits > 0 && top_bits < 6) continue;
-    const double cost = (double)Wi * (10.0 * (double)(glv ? 2 * n : n) + 28.0 * (double)(1u << (c - 1)));
+    const double cost = (double)Wi * (10.0 * (double)(2 * n) + 28.0 * (double)(1u << (c - 1)));
     if (cost < best_cost) { best_cost = cost; best = c; }
   }
   return best;
@@ -1495,7 +1480,6 @@ int msm_pick_window_prepared(size_t n) {
   // does not see): measured end to end under every window size (tools/small_window_probe.py), the model's choice is the fastest or within
   // 1 % of it except at 2^14 .. 2^15 points, where 15 bits beat its 13 / 16 (2^14: 0.257 vs 0.270 ms, 2^15: 0.310 vs 0.336 ms)
   if (n >= ((size_t)1 << 14) && n < ((size_t)3 << 14)) best = 15;
-  if (const char* e = getenv("ZKHIP_MAX_WINDOW")) { int m = atoi(e); if (m >= 2 && best > m) best = m; }   // A/B knob
   return best;
 }
 
@@ -1527,9 +1511,7 @@ static uint32_t msm_task_shift(size_t entries /* W n K */, size_t NB, size_t xyz
   // 128-entry tasks halve the partials the combine step has to add, and pay once the launch is many rounds of waves deep even
   // so: measured (6 / 7) 2^24 21.40 / 21.00 ms (combine 0.71 -> 0.27), but 2^22 6.00 / 6.07 and 2^20 1.72 / 1.85 (too few tasks).
   // Round 3 (W = 13): 2^22 4.78 / 4.89, 2^23 9.24 / 9.02, 2^24 17.99 / 17.70 ms -- the switch sits between 2^22 and 2^23 points.
-  static const int knob = [] { const char* e = getenv("ZKHIP_TASK_SHIFT"); return e ? atoi(e) : 0; }();
-  if (knob >= 2 && knob <= 7) task_shift = (uint32_t)knob;
-  else if ((entries >> 7) >= ((size_t)3 << 16)) task_shift = 7;      // (with the balanced windows: 2^21 2.397 / 2.380 ms, 2^22 4.812 / 4.815 -- from 2^21 points on)
+  if ((entries >> 7) >= ((size_t)3 << 16)) task_shift = 7;      // (with the balanced windows: 2^21 2.397 / 2.380 ms, 2^22 4.812 / 4.815 -- from 2^21 points on)
   // G2 (xyzz_bytes 288): a general addition costs ~1.4 mixed ones in instructions but runs in the combine step's thinly occupied lanes, and the
   // accumulation holds 2 waves per SIMD: the chip is full from 2^16 tasks, and a partial is priced at 3 mixed additions
   const bool g2 = xyzz_bytes == 288;
@@ -1549,13 +1531,13 @@ static uint32_t msm_task_shift(size_t entries /* W n K */, size_t NB, size_t xyz
 // round 3, the general path's GLV MSMs at c = 16: there a window has its own 2^15 buckets = 8 groups, 8 windows = 64 groups.  The one-level
 // scatter it replaces stores every reference with its own 4-byte write (PMC: 8.7 bytes reach memory per byte of payload).
 // The same holds for prepared tables with 16-bit windows (2^16 <= n < 2^20: one shared set of 2^15 buckets = 8 groups).
+constexpr size_t GLV_TWO_LEVEL_MIN = (size_t)1 << 18;      // scalars from which a 16-bit window takes the two-level sort: the general path's GLV MSMs,
+constexpr size_t PREP_TWO_LEVEL_MIN = (size_t)1 << 16;     // and single MSMs over a prepared table
 static bool msm_two_level(int c, bool glv, size_t n_in, bool shared_buckets, size_t K) {
   if (c > 16) return true;
-  static const long thr_glv = [] { const char* e = getenv("ZKHIP_GLV_TWO_LEVEL_MIN"); return e ? atol(e) : (1L << 18); }();      // A/B knobs (0 = never)
-  static const long thr_prep = [] { const char* e = getenv("ZKHIP_PREP_TWO_LEVEL_MIN"); return e ? atol(e) : (1L << 16); }();
   if (c != 16 || K != 1) return false;
-  if (glv) return thr_glv > 0 && n_in >= (size_t)thr_glv;
-  return shared_buckets && thr_prep > 0 && n_in >= (size_t)thr_prep;
+  if (glv) return n_in >= GLV_TWO_LEVEL_MIN;
+  return shared_buckets && n_in >= PREP_TWO_LEVEL_MIN;
 }
 
 // n_in: scalars per vector.  glv: the sort sees 2 n_in points (a point and its endomorphism image) and ceil(128 / c) windows.
@@ -1604,9 +1586,9 @@ static msm_layout msm_lay_out(char* base, size_t n_in, size_t K, int c, bool pre
   return L;
 }
 
-// GLV applies to the general path of both curves (xyzz_bytes 144 = G1, 288 = G2; round 5: the twist has the same endomorphism with beta^2):
+// GLV applies to the general path of both curves (round 5: the twist has the same endomorphism with beta^2):
 // arbitrary bases, one scalar vector (the prepared path has its doublings in the table already)
-bool msm_uses_glv(bool prepared, size_t batch, size_t xyzz_bytes) { return !prepared && batch == 1 && (xyzz_bytes == 144 || xyzz_bytes == 288) && msm_glv_enabled(); }
+static bool msm_uses_glv(bool prepared, size_t batch) { return !prepared && batch == 1; }
 int msm_glv_windows(int c) { return msm_windows(c, true); }
 
 // Direct tables (below: "Direct tables") serve single MSMs over prepared sets of at most 2^ZKHIP_DIRECT_MAX_LOG points (default 15; 0 = never; at most 18)
@@ -1618,7 +1600,7 @@ static inline bool msm_direct_wanted(size_t n) { const int L = msm_direct_max_lo
 
 size_t msm_workspace_bytes(size_t n_one, int c, bool prepared, size_t batch, size_t xyzz_bytes) {
   if (n_one == 0 || batch == 0) return 0;
-  size_t b = msm_lay_out(nullptr, n_one, batch, c, prepared, xyzz_bytes, msm_uses_glv(prepared, batch, xyzz_bytes)).total;
+  size_t b = msm_lay_out(nullptr, n_one, batch, c, prepared, xyzz_bytes, msm_uses_glv(prepared, batch)).total;
   if (prepared && batch == 1 && xyzz_bytes == 144 && msm_direct_wanted(n_one)) b = std::max(b, msm_direct_workspace_bytes(n_one));   // the same call may take the direct path
   return b;
 }
@@ -1663,19 +1645,13 @@ int msm_build_tasks(const uint32_t* d_scalars, size_t n_in, size_t batch, size_t
   if (glv && wide) hipLaunchKernelGGL(k_digits_glv<int32_t>, dim3((unsigned)((std::max<size_t>(n_in, 8) + 255) / 256)), dim3(256), 0, stream, d_scalars, (int32_t*)digits, (uint32_t)n_in, n_pad, c, W);
   else if (glv) hipLaunchKernelGGL(k_digits_glv<int16_t>, dim3((unsigned)((std::max<size_t>(n_in, 8) + 255) / 256)), dim3(256), 0, stream, d_scalars, (int16_t*)digits, (uint32_t)n_in, n_pad, c, W);
   else if (wide) {
-    static const bool fused_count = getenv("ZKHIP_NO_FUSED_COUNT") == nullptr;      // A/B knob
-    if (fused_count) {
-      // workgroups: 512 up to 2^21 scalars, 1024 above (measured 256 / 512 / 1024 at 2^20: digits 0.041 / 0.036 / 0.040 ms; 256 / 1024 / 4096 at
-      // 2^22: 0.129 / 0.110 / 0.112 -- fewer workgroups leave a lane several scalars with exposed loads, more multiply the contended atomics)
-      static const unsigned wg_knob = [] { const char* e = getenv("ZKHIP_DIGIT_WGS"); const int v = e ? atoi(e) : 0; return v >= 64 && v <= 4096 ? (unsigned)v : 0u; }();   // A/B knob
-      const unsigned wg_cap = wg_knob ? wg_knob : (n_pad > (1u << 21) ? 1024u : 512u);
-      const unsigned wblocks = (unsigned)std::min<size_t>(((size_t)n_pad + 1023) / 1024, wg_cap);
-      hipLaunchKernelGGL(k_digits_wide, dim3(wblocks), dim3(1024), 0, stream, d_scalars, (int32_t*)digits, (uint32_t)n, n_pad, c, W, gcounters + 1024, narrow);
-    } else {
-      hipLaunchKernelGGL(k_digits<int32_t>, dim3(dblocks), dim3(256), 0, stream, d_scalars, (int32_t*)digits, (uint32_t)n, n_pad, c, W, K, sstride, narrow);
-    }
+    // workgroups: 512 up to 2^21 scalars, 1024 above (measured 256 / 512 / 1024 at 2^20: digits 0.041 / 0.036 / 0.040 ms; 256 / 1024 / 4096 at
+    // 2^22: 0.129 / 0.110 / 0.112 -- fewer workgroups leave a lane several scalars with exposed loads, more multiply the contended atomics)
+    const unsigned wg_cap = n_pad > (1u << 21) ? 1024u : 512u;
+    const unsigned wblocks = (unsigned)std::min<size_t>(((size_t)n_pad + 1023) / 1024, wg_cap);
+    hipLaunchKernelGGL(k_digits_wide, dim3(wblocks), dim3(1024), 0, stream, d_scalars, (int32_t*)digits, (uint32_t)n, n_pad, c, W, gcounters + 1024, narrow);
   }
-  else hipLaunchKernelGGL(k_digits<int16_t>, dim3(dblocks), dim3(256), 0, stream, d_scalars, (int16_t*)digits, (uint32_t)n, n_pad, c, W, K, sstride, 0);
+  else hipLaunchKernelGGL(k_digits, dim3(dblocks), dim3(256), 0, stream, d_scalars, (int16_t*)digits, (uint32_t)n, n_pad, c, W, K, sstride, 0);
   prof_mark(stream, "digits");
   // 2. count
   uint32_t chunks = (uint32_t)((n + 65535) / 65536);
@@ -1703,9 +1679,8 @@ int msm_build_tasks(const uint32_t* d_scalars, size_t n_in, size_t batch, size_t
   const uint32_t sort_chunks = (uint32_t)(((size_t)W * n + sort_chunk - 1) / sort_chunk) + (uint32_t)G;     // upper bound of the fine passes' chunks; surplus workgroups return at once
   const uint32_t wb_stride = shared_buckets ? 0u : B;
   if (wide) {
-    static const bool fused_count2 = getenv("ZKHIP_NO_FUSED_COUNT") == nullptr;
-    if (!fused_count2 || glv)        // (otherwise k_digits_wide has counted the groups; the GLV digit kernel -- one scalar per thread, thousands of
-                                     // workgroups -- leaves the counting to this pass: its merges would be that many same-address atomics)
+    if (glv)        // (otherwise k_digits_wide has counted the groups; the GLV digit kernel -- one scalar per thread, thousands of
+                    // workgroups -- leaves the counting to this pass: its merges would be that many same-address atomics)
       hipLaunchKernelGGL(k_coarse_count, dim3(chunks, W), dim3(1024), 0, stream, (const int32_t*)digits, n_pad, chunk, gcounters + 1024, gstride);
     hipLaunchKernelGGL(k_group_offsets, dim3(1), dim3(64), 0, stream, gcounters + 1024, W, G, gcounters + 128, gcounters + 3072, gcounters + 512, sort_chunk);
     static_assert(MAX_GROUPS == 128, "k_coarse_sorted scans two groups per lane of one wavefront");
@@ -1736,8 +1711,7 @@ int msm_build_tasks(const uint32_t* d_scalars, size_t n_in, size_t batch, size_t
   else hipLaunchKernelGGL(k_sort_pass<true>, dim3(chunks, W, K), dim3(1024), lds, stream, (const int16_t*)digits, n_pad, chunk, c, cursor, sorted, wb_stride, ref_base, ref_stride);
   prof_mark(stream, "scatter");
   // 5. tasks
-  static const unsigned task_wg_cap = [] { const char* e = getenv("ZKHIP_TASK_WGS"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 4096 ? (unsigned)v : 256u; }();   // A/B knob (anything else: the default)
-  const unsigned task_blocks = (unsigned)std::min<size_t>((NB + 255) / 256, task_wg_cap);
+  const unsigned task_blocks = (unsigned)std::min<size_t>((NB + 255) / 256, 256);
   if (scan_single) {
     hipLaunchKernelGGL(k_scan_single<1>, dim3(1), dim3(1024), 0, stream, count, (uint32_t)NB, counters + 1, task_off, (uint32_t*)nullptr, task_shift, counters + 192);
     hipLaunchKernelGGL(k_make_tasks, dim3(task_blocks), dim3(256), 0, stream, offset, task_off, NB, tasks, task_shift, counters + 2, (uint32_t*)nullptr, lay.seq_parts,
@@ -1764,7 +1738,7 @@ int msm_build_tasks(const uint32_t* d_scalars, size_t n_in, size_t batch, size_t
 static int msm_accumulate_combine(const msm_tasks_view& tv, const uint32_t* d_bases, bool prepared, bool glv, size_t n, uint32_t* buckets, hipStream_t stream) {
   const uint32_t NB = tv.NB;
   const size_t max_tasks = tv.max_tasks;
-  const task_t* const tasks = (const task_t*)tv.tasks;
+  const task_t* const tasks = tv.tasks;
   uint32_t* const counters = tv.ntasks - 1;
   const uint4* const order = tv.order;
   const uint32_t *const sorted = tv.sorted, *const task_off = tv.task_off;
@@ -1784,14 +1758,13 @@ static int msm_accumulate_combine(const msm_tasks_view& tv, const uint32_t* d_ba
     const uint32_t seq_parts = tv.seq_parts;
     const size_t lanes_total = (size_t)NB * combine_lanes;
     const bool quad = lanes_total * 4 <= 131072;        // far below the chip's lane count: the additions' latency is the step time
-    static const uint32_t heavy_quad_max = [] { const char* e = getenv("ZKHIP_HEAVY_QUAD_MAX"); const long v = e ? atol(e) : -1; return v >= 0 && v <= 2048 ? (uint32_t)v : HEAVY_QUAD_MAX; }();   // A/B knob (0 = the 128-lane slice sums only)
     const unsigned blocks = (unsigned)((lanes_total * (quad ? 4 : 1) + 127) / 128);
 #define ZK_LAUNCH_COMBINE(L)                                                                                                                        \
     do {                                                                                                                                              \
       if (quad) hipLaunchKernelGGL(k_combine_seq_quad<L>, dim3(blocks + HEAVY_WGS), dim3(128), 0, stream, task_off, NB, partials, buckets, seq_parts, blocks,   \
-                                   tv.heavy_count, (const uint2*)tv.heavy, tv.heavy_cap, tv.heavy_done, heavy_quad_max);                              \
+                                   tv.heavy_count, (const uint2*)tv.heavy, tv.heavy_cap, tv.heavy_done, HEAVY_QUAD_MAX);                              \
       else hipLaunchKernelGGL(k_combine_seq<L>, dim3(blocks + HEAVY_WGS), dim3(128), 0, stream, task_off, NB, partials, buckets, seq_parts, blocks,             \
-                              tv.heavy_count, (const uint2*)tv.heavy, tv.heavy_cap, tv.heavy_done, heavy_quad_max);                                   \
+                              tv.heavy_count, (const uint2*)tv.heavy, tv.heavy_cap, tv.heavy_done, HEAVY_QUAD_MAX);                                   \
     } while (0)
     if (combine_lanes == 1) ZK_LAUNCH_COMBINE(1);
     else if (combine_lanes == 2) ZK_LAUNCH_COMBINE(2);
@@ -1807,8 +1780,7 @@ static int msm_accumulate_combine(const msm_tasks_view& tv, const uint32_t* d_ba
 // prepared: every bucket set's weighted sum is a result (K = WB of them); otherwise the WB window sums are folded into one.
 static int msm_reduce_buckets(int WB, uint32_t B, int c, uint32_t K, bool prepared, uint32_t* cur, uint32_t* nxt, uint32_t* winsum, uint32_t* d_out, hipStream_t stream) {
   // 8. pyramid: buckets were written with window stride B (dense).  Steps 1 .. c-2 leave X with 2 elements.
-  static const size_t quad_max = [] { const char* e = getenv("ZKHIP_PYR_QUAD_MAX"); const long v = e ? atol(e) : 0; return v >= 256 && v <= (1 << 20) ? (size_t)v : (size_t)65536; }();   // A/B knob
-  static const long pyr_persist = [] { const char* e = getenv("ZKHIP_PYR_PERSIST"); const long v = e ? atol(e) : 0; return v >= 64 && v <= 65536 ? v : 0L; }();   // A/B knob: workgroup cap of the single-lane steps (0 = one addition per thread)
+  constexpr size_t PYR_QUAD_MAX = 65536;     // additions of a step up to which four lanes share one (profiles/r04_pyramid_quad_threshold_ab.txt)
   uint32_t in_stride = B;
   int nz = 0;
   {
@@ -1818,12 +1790,8 @@ static int msm_reduce_buckets(int WB, uint32_t B, int c, uint32_t K, bool prepar
       uint32_t per_win = N / 2 + (uint32_t)s * (N / 4);
       uint32_t out_stride = per_win;
       // below ~1/4 of the chip's lanes an addition's latency is the step time: four lanes per addition
-      if ((size_t)per_win * WB <= quad_max) hipLaunchKernelGGL(k_pyramid_step_quad, dim3((4 * per_win + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, N, s, in_stride, out_stride);
-      else {
-        unsigned blocks = (per_win + 127) / 128;
-        if (pyr_persist > 0 && WB == 1) blocks = std::min<unsigned>(blocks, (unsigned)pyr_persist);
-        hipLaunchKernelGGL(k_pyramid_step, dim3(blocks, WB), dim3(128), 0, stream, cur, nxt, N, s, in_stride, out_stride);
-      }
+      if ((size_t)per_win * WB <= PYR_QUAD_MAX) hipLaunchKernelGGL(k_pyramid_step_quad, dim3((4 * per_win + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, N, s, in_stride, out_stride);
+      else hipLaunchKernelGGL(k_pyramid_step, dim3((per_win + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, N, s, in_stride, out_stride);
       uint32_t* t = cur; cur = nxt; nxt = t;
       in_stride = out_stride;
       N >>= 1;
@@ -1870,7 +1838,7 @@ int msm_g1_device(const uint32_t* d_scalars, const uint32_t* d_bases, size_t n, 
     if (prepared->direct && batch == 1) return msm_g1_direct(d_scalars, n, prepared, prepared_off, d_out, ws, ws_bytes, stream);     // small fixed base set: no buckets
   }
   msm_tasks_view tv;
-  const bool glv = msm_uses_glv(prepared != nullptr, batch, 144);
+  const bool glv = msm_uses_glv(prepared != nullptr, batch);
   int rc = msm_build_tasks(d_scalars, n, batch, scalar_stride, c, prepared != nullptr, prepared ? (uint32_t)prepared_off : 0u, prepared ? (uint32_t)prepared->n : 0u,
                            144, ws, ws_bytes, stream, &tv, glv);
   if (rc != ZKHIP_OK) return rc;

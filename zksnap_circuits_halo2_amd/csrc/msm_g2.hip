@@ -21,10 +21,6 @@
 
 namespace zkhip {
 
-struct task_t {
-  uint32_t bucket, start, len;
-};
-
 // beta^2 (Montgomery-256 words): the cube root of unity in Fq with (beta^2 x, y) = lambda (x, y) on G2 for the lambda of msm.hip's GLV split
 __device__ constexpr uint32_t BETA2_EXT[8] = {0x13e80b9cu, 0x3350c88eu, 0xdb5e56b9u, 0x7dce557cu, 0xb615564au, 0x6001b4b8u, 0x020217e0u, 0x2682e617u};
 
@@ -279,22 +275,22 @@ __global__ void __launch_bounds__(64) k2_test_op(int op, const uint32_t* __restr
   store_jacobian2(acc, out + i * 48);
 }
 
-static int pick_window_g2(size_t n, bool glv) {
-  // the model of msm_pick_window (W windows x (n' mixed additions + 2 general additions per bucket)) with G2's costs in G1 multiplications:
+static int pick_window_g2(size_t n) {
+  // the model of msm_pick_window (W windows x (n' = 2 n mixed additions + 2 general additions per bucket)) with G2's costs in G1 multiplications:
   // a mixed addition 8 M2 + 2 S2 ~ 28 + the Fq2 additions ~ 34, a general one ~ 48; plus the fold's c (W - 1) dependent quad doublings at
   // ~8 us each, i.e. ~1.3 M multiplication slots of the accumulation kernel per doubling (what makes small windows lose at small n)
   int best = 2;
   double best_cost = 1e300;
   for (int c = 2; c <= 16; c++) {
-    const int W = glv ? msm_glv_windows(c) : (256 + c - 1) / c, top_bits = (glv ? 127 : 254) - (W - 1) * c;
+    const int W = msm_glv_windows(c), top_bits = 127 - (W - 1) * c;
     if (top_bits > 0 && top_bits < 6) continue;
-    const double cost = (double)W * (34.0 * (double)(glv ? 2 * n : n) + 96.0 * (double)(1u << (c - 1))) + 1.3e6 * (double)c * (double)(W - 1) / 16.0;
+    const double cost = (double)W * (34.0 * (double)(2 * n) + 96.0 * (double)(1u << (c - 1))) + 1.3e6 * (double)c * (double)(W - 1) / 16.0;
     if (cost < best_cost) { best_cost = cost; best = c; }
   }
   return best;
 }
 
-size_t msm_g2_workspace_bytes(size_t n) { return n ? msm_workspace_bytes(n, pick_window_g2(n, msm_uses_glv(false, 1, 288)), false, 1, 288) : 0; }
+size_t msm_g2_workspace_bytes(size_t n) { return n ? msm_workspace_bytes(n, pick_window_g2(n), false, 1, 288) : 0; }
 
 // d_scalars: n x 8 words (Fr, Montgomery), d_bases: n x 32 words (G2Affine), d_out: 48 words (G2 Jacobian)
 int msm_g2_device(const uint32_t* d_scalars, const uint32_t* d_bases, size_t n, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream) {
@@ -304,17 +300,15 @@ int msm_g2_device(const uint32_t* d_scalars, const uint32_t* d_bases, size_t n, 
     return ZKHIP_OK;
   }
   if (n >= (1ull << 31)) { set_error("msm_g2: n = %zu too large", n); return ZKHIP_EINVAL; }
-  const bool glv = msm_uses_glv(false, 1, 288);
-  const int c = pick_window_g2(n, glv);
+  const int c = pick_window_g2(n);
   msm_tasks_view tv;
-  int rc = msm_build_tasks(d_scalars, n, 1, n, c, false, 0u, 0u, 288, ws, ws_bytes, stream, &tv, glv);
+  int rc = msm_build_tasks(d_scalars, n, 1, n, c, false, 0u, 0u, 288, ws, ws_bytes, stream, &tv, true);     // one vector of the general path: GLV digits
   if (rc != ZKHIP_OK) return rc;
-  if (glv) hipLaunchKernelGGL(k2_endo_bases, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_bases, (uint32_t)n, tv.endo);
+  hipLaunchKernelGGL(k2_endo_bases, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_bases, (uint32_t)n, tv.endo);
   {
     uint32_t blocks = (uint32_t)((tv.max_tasks + 63) / 64);
     if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(k2_accumulate, dim3(blocks), dim3(64), 0, stream, tv.ntasks, tv.order, tv.sorted, d_bases, tv.partials, tv.pyrA, (const uint32_t*)tv.endo,
-                       glv ? (uint32_t)n : 0xffffffffu);
+    hipLaunchKernelGGL(k2_accumulate, dim3(blocks), dim3(64), 0, stream, tv.ntasks, tv.order, tv.sorted, d_bases, tv.partials, tv.pyrA, (const uint32_t*)tv.endo, (uint32_t)n);
   }
   prof_mark(stream, "accumulate_g2");
   {

@@ -10,7 +10,7 @@
 //     dst[(j/Ns) Ns R + k + r Ns].  No bit-reversal pass, every pass streams coalesced runs.
 //   * One workgroup owns a tile of J consecutive j (J * R = 1024 elements, 36 KiB of LDS as 9-limb values; up to 2048):
 //     cooperative coalesced load -> LDS, rounds of 2 radix-2 stages in registers (4 elements per
-//     thread; 3 stages / 8 elements as a variant), LDS exchange between rounds, cooperative coalesced store.
+//     thread), LDS exchange between rounds, cooperative coalesced store.
 //   * B <= 9 bits per pass: 2^24 is three passes.  Twiddles w_M^(k r) come from an M-entry table (laid out [r][k], the order read) when
 //     M <= 2^24 (HBM is plentiful: 36 B * M per (omega, log_n), cached) and from two 2^(log M / 2)-entry
 //     tables (one extra multiply) above that.
@@ -36,6 +36,14 @@ namespace zkhip {
 
 using Fr = FrParams;
 constexpr uint32_t NTT_TILE_MAX = 2048;   // largest tile the LDS layout and the launch bounds are sized for
+// Elements per workgroup.  1024 (256 threads, 36 KiB of LDS, four workgroups per CU) against the 2048 the kernel was written for (two
+// workgroups per CU): a barrier or an LDS round trip parks 4 of a SIMD's waves instead of 8, and a pass keeps 128-byte runs on both
+// sides.  Measured on one box, 2048 / 1024 / 512: 2^13 0.0465 / 0.0355 / 0.0349 ms, 2^22 0.586 / 0.557 / 0.590, 2^24 2.341 / 2.301 / 2.452
+// (profiles/r03_ntt_tile_ab.txt).
+constexpr uint32_t NTT_TILE = 1024;
+// Single-chain product columns (fp29.hpp fe_mul<P, CHAIN>: one run of multiply-adds per column instead of the partial sums LLVM's
+// reassociation makes): -3 % at every size with 4 elements per thread (2^24: 2.35 -> 2.27 ms, same box).
+constexpr bool NTT_CHAIN = true;
 constexpr int NTT_MAX_BITS = 9;
 constexpr uint32_t NTT_DIRECT_TABLE_BITS = 24;   // pass twiddles w_M^t as one M-entry table up to M = 2^24 (604 MB), two-level above
 
@@ -112,7 +120,6 @@ __device__ __forceinline__ fe scale_pick(const scale_arg& s, uint32_t idx) {
 
 // One element from global memory, ready for the first round: zero-padded / input-scaled on the first pass, multiplied by the pass
 // twiddle w_M^(k r) on the later ones (row r, column j of the pass's source matrix: element j + r N/R).
-template <bool CH>
 __device__ __forceinline__ fe ntt_fetch(const pass_args& a, const uint32_t* __restrict__ src, uint32_t r, uint32_t j, uint32_t NR, uint32_t Ns) {
   const uint32_t g = j + r * NR;
   if (a.first) {
@@ -120,7 +127,7 @@ __device__ __forceinline__ fe ntt_fetch(const pass_args& a, const uint32_t* __re
     uint32_t w[8];
     load_words(src + (size_t)g * 8, w);
     fe x = fe_unpack<0>(w);
-    if (a.in_scale.period) x = fe_mul<Fr, CH>(scale_pick(a.in_scale, g), x);
+    if (a.in_scale.period) x = fe_mul<Fr, NTT_CHAIN>(scale_pick(a.in_scale, g), x);
     return x;
   }
   uint32_t w[8];
@@ -130,20 +137,19 @@ __device__ __forceinline__ fe ntt_fetch(const pass_args& a, const uint32_t* __re
   if (a.tw_hi == nullptr) {
     tw = load_fe9(a.tw_lo, a.tw_rk ? (r << a.S) + (j & (Ns - 1)) : t);
   } else {
-    tw = fe_mul<Fr, CH>(load_fe9(a.tw_lo, t & ((1u << a.h) - 1)), load_fe9(a.tw_hi, t >> a.h));
+    tw = fe_mul<Fr, NTT_CHAIN>(load_fe9(a.tw_lo, t & ((1u << a.h) - 1)), load_fe9(a.tw_hi, t >> a.h));
   }
-  return fe_mul<Fr, CH>(tw, fe_unpack<0>(w));
+  return fe_mul<Fr, NTT_CHAIN>(tw, fe_unpack<0>(w));
 }
 
 // One result to global memory: destination index d of (row rp, column j) in the Stockham order; the caller's scale or a soft reduction
 // on the last pass, the 32-byte intermediate format otherwise.
-template <bool CH>
 __device__ __forceinline__ void ntt_emit(const pass_args& a, uint32_t* __restrict__ dst, uint32_t rp, uint32_t j, uint32_t B, uint32_t Ns, fe x) {
   const uint32_t d = ((j >> a.S) << (a.S + B)) + (j & (Ns - 1)) + (rp << a.S);
   uint32_t w[8];
   if (a.last) {
     if (d >= a.out_len) return;
-    if (a.out_scale.period) fe_pack(fe_canon_lt2p<Fr>(fe_mul<Fr, CH>(scale_pick(a.out_scale, d), x)), w);
+    if (a.out_scale.period) fe_pack(fe_canon_lt2p<Fr>(fe_mul<Fr, NTT_CHAIN>(scale_pick(a.out_scale, d), x)), w);
     else fe_pack(fe_canon_lt3p<Fr>(fe_reduce_soft<Fr>(x)), w);   // x is N-form < 29p after the last round
   } else {
     fe_pack(fe_reduce_soft<Fr>(x), w);         // < 2p + 2^233 < 2^256: fits the 32-byte intermediate format
@@ -151,14 +157,12 @@ __device__ __forceinline__ void ntt_emit(const pass_args& a, uint32_t* __restric
   store_words(dst + (size_t)d * 8, w);
 }
 
-// CH: fe_mul with single-chain product columns (see the launch site).
-// E = elements a thread holds in a round (log2 E radix-2 stages per LDS round trip).  E = 8: 256 threads per 2048-element tile, 3 stages
-// per round, 202 VGPRs -> 2 waves per SIMD.  E = 4 (default): 512 threads per tile, 2 stages per round, 123 VGPRs -> 4 waves per SIMD at
-// the price of one more LDS round trip per 8-bit pass (+5.6 % VALU instructions).  Measured equal within noise at 2^22 .. 2^26 (the
-// kernel runs at the VALU issue rate of its instruction mix either way: DESIGN.md section 4), E = 4 ahead on small transforms.
-template <int E, bool CH>
-__global__ void __launch_bounds__(2048 / E) __attribute__((amdgpu_waves_per_eu(E == 8 ? 2 : 4, E == 8 ? 2 : 4))) k_ntt_pass(pass_args a) {
-  constexpr int VM = E == 8 ? 3 : 2;
+// E = elements a thread holds in a round, VM = log2 E radix-2 stages per LDS round trip: 512 threads per 2048-element tile, 123 VGPRs
+// -> 4 waves per SIMD.  (The 8-element shape of round 1, 3 stages per round at 2 waves per SIMD, measured equal within noise at
+// 2^22 .. 2^26 and behind on small transforms: profiles/r02_ntt_variants_ab.txt.  The kernel runs at the VALU issue rate of its
+// instruction mix either way: DESIGN.md section 4.)
+__global__ void __launch_bounds__(NTT_TILE_MAX / 4) __attribute__((amdgpu_waves_per_eu(4, 4))) k_ntt_pass(pass_args a) {
+  constexpr int E = 4, VM = 2;
   extern __shared__ uint32_t lds[];
   const uint32_t B = a.B, R = 1u << B, L = a.L;
   const uint32_t N = 1u << L;
@@ -192,7 +196,7 @@ __global__ void __launch_bounds__(2048 / E) __attribute__((amdgpu_waves_per_eu(E
           if ((e >> u) & 1) continue;          // e is the upper element of a pair
           const int f = e | (1 << u);
           const uint32_t lo_i = pos[e] & ((1u << st) - 1);
-          fe t = fe_mul<Fr, CH>(load_fe9(a.tw_local, lo_i << (B - 1 - st)), x[f]);   // N x (limbs < 2^31.5)
+          fe t = fe_mul<Fr, NTT_CHAIN>(load_fe9(a.tw_local, lo_i << (B - 1 - st)), x[f]);   // N x (limbs < 2^31.5)
           x[f] = fe_sub_red(x[e], t, Fr::P3_S1);                                   // x - t + 3p
           x[e] = fe_add(x[e], t);
         }
@@ -218,16 +222,16 @@ __global__ void __launch_bounds__(2048 / E) __attribute__((amdgpu_waves_per_eu(E
     // indexes x[] dynamically, i.e. keeps it in scratch)
     static_for<0, E>([&](auto ec) {
       constexpr int e = decltype(ec)::value;
-      x[e] = ntt_fetch<CH>(a, src, __brev(pos[e]) >> (32 - B), j0 + jj, NR, Ns);
+      x[e] = ntt_fetch(a, src, __brev(pos[e]) >> (32 - B), j0 + jj, NR, Ns);
     });
-    if (E == 4 && v == (uint32_t)VM && a.first && a.in_len <= (NR << (B - 2))) {
+    if (v == (uint32_t)VM && a.first && a.in_len <= (NR << (B - 2))) {
       // zero-padded input of at most N / 4 elements (coeff_to_extended: n coefficients on the 4n-point coset): only source rows below R / 4
       // are non-zero, and those are the thread's element 0 (rows bitrev(4 m + e): e = 1, 2, 3 select the upper three quarters).  Both
       // stages of the round then add or subtract zeros: all four outputs equal x[0] (the general code below would compute x[0] + 3p,
       // x[0] + 6p and x[0] + 3p - w4 * 0 with one multiplication); the three fetches above returned zero without touching memory.
       x[1] = x[0]; x[2] = x[0]; x[3] = x[0];
     } else if (v == (uint32_t)VM) {
-      // v == VM, lo == 0: twiddles depend only on the register index and 7 of the 12 (E = 4: 3 of the 4) are w^0 = 1, so
+      // v == VM, lo == 0: twiddles depend only on the register index and 3 of the 4 are w^0 = 1, so
       // those butterflies need no multiply.  Inputs are N-form < 2p.  Bounds (value / limb) are noted per stage.
       const fe w4 = load_fe9(a.tw_local, 1u << (B - 2));
 #pragma unroll
@@ -241,30 +245,15 @@ __global__ void __launch_bounds__(2048 / E) __attribute__((amdgpu_waves_per_eu(E
         fe t = fe_norm(x[e + 2]);                         // trivial pair (e, e+2): t < 4p, N
         x[e + 2] = fe_sub_red(x[e], t, Fr::P6_S1);        // < 10p / 2^31
         x[e] = fe_add(x[e], t);                           // < 8p / 1.5*2^30
-        fe u1 = fe_mul<Fr, CH>(w4, x[e + 3]);                 // pair (e+1, e+3): input < 5p / 1.5*2^30
+        fe u1 = fe_mul<Fr, NTT_CHAIN>(w4, x[e + 3]);      // pair (e+1, e+3): input < 5p / 1.5*2^30
         x[e + 3] = fe_sub_red(x[e + 1], u1, Fr::P3_S1);   // < 8p / 2.5*2^30
         x[e + 1] = fe_add(x[e + 1], u1);                  // < 7p / 2^31
-      }
-      if constexpr (E == 8) {                             // stage 2
-        const fe w8 = load_fe9(a.tw_local, 1u << (B - 3)), w83 = load_fe9(a.tw_local, 3u << (B - 3));
-        fe t = fe_norm(x[4]);                             // trivial pair (0, 4): t < 8p, N
-        x[4] = fe_sub_red(x[0], t, Fr::P10_S1);           // < 18p / 2.5*2^30
-        x[0] = fe_add(x[0], t);                           // < 16p / 2^31
-        fe u1 = fe_mul<Fr, CH>(w8, x[5]);                     // inputs: limbs <= 2.5*2^30 < 2^31.5
-        x[5] = fe_sub_red(x[1], u1, Fr::P3_S1);
-        x[1] = fe_add(x[1], u1);
-        fe u2 = fe_mul<Fr, CH>(w4, x[6]);
-        x[6] = fe_sub_red(x[2], u2, Fr::P3_S1);
-        x[2] = fe_add(x[2], u2);
-        fe u3 = fe_mul<Fr, CH>(w83, x[7]);
-        x[7] = fe_sub_red(x[3], u3, Fr::P3_S1);
-        x[3] = fe_add(x[3], u3);
       }
     } else {
       stages(x, pos, 0, v);
     }
     if (v == B && direct_store) {
-      static_for<0, E>([&](auto ec) { constexpr int e = decltype(ec)::value; ntt_emit<CH>(a, dst, pos[e], j0 + jj, B, Ns, fe_norm(x[e])); });
+      static_for<0, E>([&](auto ec) { constexpr int e = decltype(ec)::value; ntt_emit(a, dst, pos[e], j0 + jj, B, Ns, fe_norm(x[e])); });
     } else {
 #pragma unroll
       for (int e = 0; e < E; e++) store_lds9(lds, pos[e] * J + jj, fe_norm(x[e]));
@@ -281,7 +270,7 @@ __global__ void __launch_bounds__(2048 / E) __attribute__((amdgpu_waves_per_eu(E
     for (int e = 0; e < E; e++) x[e] = load_lds9(lds, pos[e] * J + jj);
     stages(x, pos, s, v);
     if (s + v == B && direct_store) {
-      static_for<0, E>([&](auto ec) { constexpr int e = decltype(ec)::value; ntt_emit<CH>(a, dst, pos[e], j0 + jj, B, Ns, fe_norm(x[e])); });
+      static_for<0, E>([&](auto ec) { constexpr int e = decltype(ec)::value; ntt_emit(a, dst, pos[e], j0 + jj, B, Ns, fe_norm(x[e])); });
     } else {
 #pragma unroll
       for (int e = 0; e < E; e++) store_lds9(lds, pos[e] * J + jj, fe_norm(x[e]));
@@ -297,7 +286,7 @@ __global__ void __launch_bounds__(2048 / E) __attribute__((amdgpu_waves_per_eu(E
   for (uint32_t idx = threadIdx.x; idx < tile; idx += nthreads) {
     const uint32_t b = idx & (q - 1), rp = (idx >> logq) & (R - 1), aa = idx >> (logq + B);
     const uint32_t jj = aa * q + b;
-    ntt_emit<CH>(a, dst, rp, j0 + jj, B, Ns, load_lds9(lds, rp * J + jj));
+    ntt_emit(a, dst, rp, j0 + jj, B, Ns, load_lds9(lds, rp * J + jj));
   }
 }
 
@@ -552,17 +541,11 @@ int ntt_transform(const uint32_t* d_in, uint32_t in_len, uint32_t in_stride, uin
     HIPCHK(hipGetDevice(&cur_dev));
     std::lock_guard<std::mutex> ag(attr_mu);
     if (!attr_set_dev[cur_dev & 63]) {
-      HIPCHK(hipFuncSetAttribute((const void*)k_ntt_pass<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NTT_LDS_WORDS * 4));
-      HIPCHK(hipFuncSetAttribute((const void*)k_ntt_pass<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NTT_LDS_WORDS * 4));
+      HIPCHK(hipFuncSetAttribute((const void*)k_ntt_pass, hipFuncAttributeMaxDynamicSharedMemorySize, NTT_LDS_WORDS * 4));
       attr_set_dev[cur_dev & 63] = true;
     }
   }
-  // Elements per workgroup.  1024 (256 threads, 36 KiB of LDS, four workgroups per CU) against the 2048 the kernel was written for (two
-  // workgroups per CU): a barrier or an LDS round trip parks 4 of a SIMD's waves instead of 8, and a pass keeps 128-byte runs on both
-  // sides.  Measured on one box, 2048 / 1024 / 512: 2^13 0.0465 / 0.0355 / 0.0349 ms, 2^22 0.586 / 0.557 / 0.590, 2^24 2.341 / 2.301 / 2.452
-  // (profiles/r03_ntt_tile_ab.txt).  ZKHIP_NTT_TILE = 512 | 1024 | 2048 is the A/B knob.
-  static const uint32_t tile_knob = [] { const char* e = getenv("ZKHIP_NTT_TILE"); const int v = e ? atoi(e) : 0; return (v == 512 || v == 1024 || v == 2048) ? (uint32_t)v : 1024u; }();
-  const uint32_t tile = N < tile_knob ? N : tile_knob;
+  const uint32_t tile = N < NTT_TILE ? N : NTT_TILE;
   if ((p->npass >= 2 && !tmp0) || (p->npass >= 3 && !tmp1)) { set_error("ntt: missing scratch buffer"); return ZKHIP_EINVAL; }
   uint32_t* tmp[2] = {tmp0, tmp1};
   prof_begin(stream);
@@ -579,13 +562,8 @@ int ntt_transform(const uint32_t* d_in, uint32_t in_len, uint32_t in_stride, uin
     a.dst = a.last ? d_out : tmp[i & 1];
     a.src_stride = i == 0 ? in_stride : N;
     a.dst_stride = a.last ? out_stride : N;
-    // single-chain product columns (fp29.hpp fe_mul<P, CHAIN>: one run of multiply-adds per column instead of the partial sums LLVM's
-    // reassociation makes): -3 % at every size with 4 elements per thread (2^24: 2.35 -> 2.27 ms, same box).  The 8-elements-per-thread
-    // shape of round 1 (2 waves per SIMD) measured equal within noise in round 2 and is no longer instantiated.
-    static const bool chain = getenv("ZKHIP_NTT_PLAIN") == nullptr;       // A/B knob
     const unsigned threads = tile >= 4 ? tile / 4 : 1;
-    if (chain) hipLaunchKernelGGL((k_ntt_pass<4, true>), dim3(N / tile, batch), dim3(threads), (size_t)(lds_word_host(tile) + 16) * 4, stream, a);
-    else hipLaunchKernelGGL((k_ntt_pass<4, false>), dim3(N / tile, batch), dim3(threads), (size_t)(lds_word_host(tile) + 16) * 4, stream, a);
+    hipLaunchKernelGGL(k_ntt_pass, dim3(N / tile, batch), dim3(threads), (size_t)(lds_word_host(tile) + 16) * 4, stream, a);
     prof_mark(stream, i == 0 ? "ntt_pass0" : (i == 1 ? "ntt_pass1" : (i == 2 ? "ntt_pass2" : "ntt_pass3")));
   }
   HIPCHK(hipGetLastError());

@@ -28,12 +28,16 @@ int g1_fixed_base_table_build(uint32_t* d_table, void* ws, size_t ws_bytes, hipS
 int g1_fixed_base_mul_device(const uint32_t* d_scalars, size_t n, const uint32_t* d_table, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream);
 int msm_pick_window(size_t n);
 size_t msm_workspace_bytes(size_t n, int c, bool prepared = false, size_t batch = 1, size_t xyzz_bytes = 144);
+// one run of a bucket's sorted point references, handed to one accumulate lane (or lane group) of either curve
+struct task_t {
+  uint32_t bucket, start, len;
+};
 // what the curve-specific kernels (accumulate, combine, bucket reduction) need once the scalars are sorted into tasks
 struct msm_tasks_view {
   int c, W, WB;                    // window bits, windows, bucket sets
   uint32_t B, NB, task_shift;      // buckets per set, buckets in all, log2 task length
   size_t max_tasks, nk;
-  const void* tasks;               // task_t {bucket, start, len}
+  const task_t* tasks;
   uint32_t* ntasks;                // device: number of tasks
   uint32_t* max_parts;             // device: largest task count of one bucket
   const uint4* order;              // execution order records (task | 0x80000000 + bucket, start, len, first reference)
@@ -50,7 +54,6 @@ struct msm_tasks_view {
 };
 // glv (general path of either curve): the scalars are split with the curve's endomorphism (msm.hip k_digits_glv): the sort sees 2 n points and
 // ceil(128 / c) windows, point references >= n mean "the image of point ref - n"
-bool msm_uses_glv(bool prepared, size_t batch, size_t xyzz_bytes);
 int msm_glv_windows(int c);
 int msm_build_tasks(const uint32_t* d_scalars, size_t n, size_t batch, size_t scalar_stride, int c, bool shared_buckets, uint32_t ref_base, uint32_t ref_stride,
                     size_t xyzz_bytes, void* ws, size_t ws_bytes, hipStream_t stream, msm_tasks_view* out, bool glv = false);

@@ -106,6 +106,36 @@ template <class P> static void field_tests(const char* name) {
     fe_to_ext<P>(in, w2);
     CHECK(memcmp(w, w2, 32) == 0, name);
   }
+  // The unscaled last pass of the NTT (ntt.hip ntt_emit) canonicalises k p + y, k <= 28, with fe_reduce_soft and conditional subtractions and no
+  // multiplication.  Every representative k p of zero must come out as the word 0, and every k p + y as y.  The quotient estimate of
+  // fe_reduce_soft is at least k - 1 for these k (k p_top / (p_top + 1) > k - 1), so its result is below 2p, not only below 2p + 2^233:
+  // one conditional subtraction already gives the canonical value, and the second one of fe_canon_lt3p never fires.
+  {
+    const big one_b = [] { big o = big_zero(); o.w[0] = 1; return o; }();
+    big low_full = big_zero();                                    // eight full 29-bit limbs
+    for (int i = 0; i < 3; i++) low_full.w[i] = ~0ULL;
+    low_full.w[3] = (1ULL << (8 * LB - 192)) - 1;
+    big kp = big_zero();
+    for (unsigned k = 0; k <= 28; k++, kp = big_add(kp, p)) {
+      for (int it = 0; it < 12; it++) {
+        big y = rnd_below(p);
+        if (it == 0) y = big_zero();
+        if (it == 1) y = one_b;
+        if (it == 2) y = big_sub(p, one_b);
+        if (it == 3) y = low_full;
+        const fe x = fe_from_big(big_add(kp, y));
+        CHECK(is_N(x) && big_cmp(fe_value(x), big_add(kp, y)) == 0, name);
+        const fe soft = fe_reduce_soft<P>(x);
+        CHECK(is_N(soft) && below(soft, 2, p) && big_cmp(big_mod(fe_value(soft), p), y) == 0, name);
+        const fe c2 = fe_canon_lt2p<P>(soft), c3 = fe_canon_lt3p<P>(soft);
+        CHECK(is_N(c3) && big_cmp(fe_value(c3), y) == 0 && big_cmp(fe_value(c2), y) == 0, name);
+        if (it == 0) CHECK(fe_is_zero_limbs(c3) && fe_is_zero_limbs(c2), name);
+        uint32_t w[8];
+        fe_pack(c3, w);
+        for (int i = 0; i < 8; i++) CHECK(w[i] == (uint32_t)(y.w[i >> 1] >> ((i & 1) * 32)), name);
+      }
+    }
+  }
   // inversion by division steps (fe_inverse.hpp) against the big-integer a^(p-2): plain integers and Montgomery-261 values, edge values,
   // and lazily reduced inputs (0 -> 0)
   const big one_b = [] { big o = big_zero(); o.w[0] = 1; return o; }();

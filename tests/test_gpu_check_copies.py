@@ -1,36 +1,29 @@
 """GPU: `zkhip_check_copies_device` -- how many cells of the permutation's columns differ from the cell they are mapped to, and which is the
 first (column 2^log_n + row).  Expected values come from `mock.verify_host` (Python integers) or from positions the test planted."""
+import functools
 import random
 
 import numpy as np
 import pytest
+import torch
 
 from zksnap_circuits_halo2_amd import evaluation as E, fields as F, mock as M
 from zksnap_circuits_halo2_amd.keygen import Assembly
+from zksnap_circuits_halo2_amd.tensors import fr_words
 
 pytestmark = pytest.mark.gpu
 R = F.R_MOD
+DEV = torch.device("cuda", 0)
+words = functools.partial(fr_words, device=DEV)
 NONE = (1 << 64) - 1
 PATTERN = 0x5A5A5A5A5A5A5A5A
 
 
-def _torch():
-    import torch
-
-    return torch, torch.device("cuda", 0)
-
-
-def words(vals):
-    torch, dev = _torch()
-    return torch.from_numpy(F.fr_encode(vals).view(np.int64)).to(dev)
-
-
 def check(cols, k, map_col, map_row):
     """cols: device tensors; map_col / map_row: [columns][2^k] integer arrays, uploaded as u32 in the layout keygen uploads them"""
-    torch, dev = _torch()
-    mc = torch.from_numpy(np.ascontiguousarray(np.asarray(map_col, dtype=np.uint32)).view(np.int32)).to(dev)
-    mr = torch.from_numpy(np.ascontiguousarray(np.asarray(map_row, dtype=np.uint32)).view(np.int32)).to(dev)
-    buf = torch.full((1, 2), PATTERN, dtype=torch.int64, device=dev)
+    mc = torch.from_numpy(np.ascontiguousarray(np.asarray(map_col, dtype=np.uint32)).view(np.int32)).to(DEV)
+    mr = torch.from_numpy(np.ascontiguousarray(np.asarray(map_row, dtype=np.uint32)).view(np.int32)).to(DEV)
+    buf = torch.full((1, 2), PATTERN, dtype=torch.int64, device=DEV)
     M.enqueue_check_copies(cols, k, mc.data_ptr(), mr.data_ptr(), buf.data_ptr())
     torch.cuda.synchronize()
     a = buf.cpu().numpy().view(np.uint64)
@@ -138,7 +131,6 @@ def test_out_of_range_map_entries_are_reduced(nc, k):
 @pytest.mark.parametrize("word", [0, 3])
 def test_values_that_differ_in_one_word_only(word):
     """raw words, not field encodings: the cells' 32 bytes are compared"""
-    torch, dev = _torch()
     k, n, nc = 6, 64, 3
     rng = random.Random(word)
     raw = np.array([[[rng.getrandbits(64) for _ in range(4)] for _ in range(n)] for _ in range(nc)], dtype=np.uint64)
@@ -147,7 +139,7 @@ def test_values_that_differ_in_one_word_only(word):
     asm.copy(1, 0, 1, 40)
     raw[2, 63] = raw[0, 5]
     raw[1, 40] = raw[1, 0]
-    cols = lambda a: [torch.from_numpy(a[c].view(np.int64)).to(dev) for c in range(nc)]
+    cols = lambda a: [torch.from_numpy(a[c].view(np.int64)).to(DEV) for c in range(nc)]
     assert check(cols(raw), k, asm.map_col, asm.map_row) == (0, NONE)
     for bit in (0, 63):
         bad = raw.copy()
@@ -161,18 +153,17 @@ def test_values_that_differ_in_one_word_only(word):
 def test_argument_errors_leave_the_record_untouched(lib):
     import ctypes as C
 
-    torch, dev = _torch()
     k, n = 4, 16
     col = words([1] * n)
     asm = Assembly(n, 1)
-    mc = torch.from_numpy(np.asarray(asm.map_col, dtype=np.int32)).to(dev)
-    mr = torch.from_numpy(np.asarray(asm.map_row, dtype=np.int32)).to(dev)
+    mc = torch.from_numpy(np.asarray(asm.map_col, dtype=np.int32)).to(DEV)
+    mr = torch.from_numpy(np.asarray(asm.map_row, dtype=np.int32)).to(DEV)
     ptrs = (C.c_void_p * 1)(col.data_ptr())
     null = (C.c_void_p * 1)(None)
     for args in ((ptrs, 0, k, mc.data_ptr(), mr.data_ptr()), (ptrs, 1, 29, mc.data_ptr(), mr.data_ptr()), (ptrs, 1, k, None, mr.data_ptr()),
                  (ptrs, 1, k, mc.data_ptr(), None), (None, 1, k, mc.data_ptr(), mr.data_ptr()), (null, 1, k, mc.data_ptr(), mr.data_ptr()),
                  (ptrs, 4097, k, mc.data_ptr(), mr.data_ptr())):
-        buf = torch.full((1, 2), PATTERN, dtype=torch.int64, device=dev)
+        buf = torch.full((1, 2), PATTERN, dtype=torch.int64, device=DEV)
         assert lib.zkhip_check_copies_device(args[0], args[1], args[2], C.c_void_p(args[3]), C.c_void_p(args[4]), C.c_void_p(buf.data_ptr()), None) == -1, args[1:3]
         torch.cuda.synchronize()
         assert buf.cpu().numpy().view(np.uint64).tolist() == [[PATTERN, PATTERN]]

@@ -2,16 +2,21 @@
 and which is the first.  Expected values come from `mock.verify_host` (Python sets of integers); the last test holds the call against
 `zkhip_lookup_permute_many_device`, which fails exactly when a lookup has a missing value and names the lowest such lookup."""
 import ctypes as C
+import functools
 import random
 import re
 
 import numpy as np
 import pytest
+import torch
 
 from zksnap_circuits_halo2_amd import _lib, evaluation as E, fields as F, mock as M
+from zksnap_circuits_halo2_amd.tensors import fr_words
 
 pytestmark = pytest.mark.gpu
 R = F.R_MOD
+DEV = torch.device("cuda", 0)
+words = functools.partial(fr_words, device=DEV)
 NONE = (1 << 64) - 1
 PATTERN = 0x5A5A5A5A5A5A5A5A
 K, N = 11, 2048
@@ -19,20 +24,8 @@ USABLE = [1, 2, 63, 64, 65, N - 6]
 GROUPS = {"shared": lambda l: 0, "distinct": lambda l: l, "aab": lambda l: (0, 0, 1)[l % 3]}
 
 
-def _torch():
-    import torch
-
-    return torch, torch.device("cuda", 0)
-
-
-def words(vals):
-    torch, dev = _torch()
-    return torch.from_numpy(F.fr_encode(vals).view(np.int64)).to(dev)
-
-
 def check(inputs, tables, u, k=K):
-    torch, dev = _torch()
-    buf = torch.full((max(len(inputs), 1), 2), PATTERN, dtype=torch.int64, device=dev)
+    buf = torch.full((max(len(inputs), 1), 2), PATTERN, dtype=torch.int64, device=DEV)
     M.enqueue_check_lookups(inputs, tables, k, u, buf.data_ptr())
     torch.cuda.synchronize()
     a = buf.cpu().numpy().view(np.uint64)
@@ -112,14 +105,13 @@ def test_full_width_keys_that_differ_in_the_top_limb_only():
 
 
 def test_no_lookups_and_no_usable_rows(lib):
-    torch, dev = _torch()
     t, i = words([1] * 64), words([2] * 64)
     assert check([], [], 10, k=6) == []
     assert check([i, i], [t, t], 0, k=6) == [(0, NONE)] * 2             # nothing to look up: the records say "no failure"
     ptrs = (C.c_void_p * 2)(i.data_ptr(), i.data_ptr())
     tabs = (C.c_void_p * 2)(t.data_ptr(), None)
     for args in ((ptrs, tabs, 2, 6, 10), (ptrs, ptrs, 2, 6, 65), (ptrs, ptrs, 2, 29, 10), (None, ptrs, 2, 6, 10), (ptrs, ptrs, 1366, 6, 10)):
-        buf = torch.full((2, 2), PATTERN, dtype=torch.int64, device=dev)
+        buf = torch.full((2, 2), PATTERN, dtype=torch.int64, device=DEV)
         assert lib.zkhip_check_lookups_device(args[0], args[1], args[2], args[3], args[4], C.c_void_p(buf.data_ptr()), None) == -1, args[2:]
         torch.cuda.synchronize()
         assert buf.cpu().numpy().view(np.uint64).tolist() == [[PATTERN, PATTERN]] * 2
@@ -129,7 +121,6 @@ def test_no_lookups_and_no_usable_rows(lib):
 @pytest.mark.parametrize("u", [64, N - 6])
 def test_agrees_with_the_permute_call(lib, u):
     """zkhip_lookup_permute_many_device returns ZKHIP_EINVAL exactly when some record has failures, and names the lowest such lookup"""
-    torch, dev = _torch()
     rng = random.Random(u)
     L = 3
     table_ints = [make_table(u, rng, 0), make_table(u, rng, 1)]
@@ -145,8 +136,8 @@ def test_agrees_with_the_permute_call(lib, u):
         got = check(inputs, tabs, u)
         assert got == host(ints, table_ints, group, u)
         assert [l for l in range(L) if got[l][0]] == list(failing)
-        pa = torch.zeros((L, N, 4), dtype=torch.int64, device=dev)
-        ps = torch.zeros((L, N, 4), dtype=torch.int64, device=dev)
+        pa = torch.zeros((L, N, 4), dtype=torch.int64, device=DEV)
+        ps = torch.zeros((L, N, 4), dtype=torch.int64, device=DEV)
         ip = (C.c_void_p * L)(*[t.data_ptr() for t in inputs])
         tp = (C.c_void_p * L)(*[t.data_ptr() for t in tabs])
         rc = lib.zkhip_lookup_permute_many_device(ip, tp, L, K, u, C.c_void_p(pa.data_ptr()), C.c_void_p(ps.data_ptr()), None)

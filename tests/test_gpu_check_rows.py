@@ -7,39 +7,31 @@ Shapes: 2^3 rows (less than a wavefront), 2^6 (one wavefront), 2^8 (one workgrou
 and end on and next to the wavefront (63 / 64) and workgroup (255 / 256) borders; result registers 5 / 7 / 11 / 15 so that each of the four
 kernel variants (6, 8, 12, 16 registers) runs."""
 import ctypes as C
+import functools
 import random
 
 import numpy as np
 import pytest
+import torch
 
 from zksnap_circuits_halo2_amd import _lib, evaluation as E, fields as F, mock as M
+from zksnap_circuits_halo2_amd.tensors import fr_words
 
 pytestmark = pytest.mark.gpu
 R = F.R_MOD
+DEV = torch.device("cuda", 0)
+words = functools.partial(fr_words, device=DEV)
 NONE = (1 << 64) - 1
 PATTERN = 0x5A5A5A5A5A5A5A5A
 EINVAL = -1
 REGS = (5, 7, 11, 15)
 
 
-def _torch():
-    import torch
-
-    return torch, torch.device("cuda", 0)
-
-
-def words(vals):
-    torch, dev = _torch()
-    return torch.from_numpy(F.fr_encode(vals).view(np.int64)).to(dev)
-
-
 def reports_buffer(count):
-    torch, dev = _torch()
-    return torch.full((max(count, 1), 2), PATTERN, dtype=torch.int64, device=dev)
+    return torch.full((max(count, 1), 2), PATTERN, dtype=torch.int64, device=DEV)
 
 
 def read(buf, count):
-    torch, _ = _torch()
     torch.cuda.synchronize()
     a = buf.cpu().numpy().view(np.uint64)
     return [(int(a[i, 0]), int(a[i, 1])) for i in range(count)]
@@ -235,7 +227,6 @@ def test_argument_errors_leave_the_records_untouched(lib):
 
 def test_counts_equal_the_nonzero_rows_of_the_evaluator():
     """2^11 rows, gate-shaped programs with rotations: what the check counts is what `zkhip_fr_eval_rows_device` writes as non-zero"""
-    torch, dev = _torch()
     k, n = 11, 2048
     rng = random.Random(2048)
     G = 3
@@ -249,7 +240,7 @@ def test_counts_equal_the_nonzero_rows_of_the_evaluator():
                             [[E.Fixed(1, 5) * (E.Advice(0, -1) * E.Advice(1, 2) - E.Advice(2, 0))]])      # rotations -1, 2 and 5, selected on a fifth of the rows
     progs = M.gate_programs(cs)
     cols = [words(c) for c in sel + adv]
-    out = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    out = torch.empty((n, 4), dtype=torch.int64, device=DEV)
     nonzero = []
     for p in progs:
         p.run_device([c.data_ptr() for c in cols], k, out.data_ptr())

@@ -9,6 +9,7 @@ import sys
 
 import numpy as np
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -19,14 +20,9 @@ from zksnap_circuits_halo2_amd import _lib, arithmetic as A, evaluation as E
 
 pytestmark = pytest.mark.gpu
 ZKHIP_EINVAL = -1
+DEV = torch.device("cuda", 0)
 M64 = (1 << 64) - 1
 SENTINEL = 0x5E5E5E5E5E5E5E5E
-
-
-def _torch():
-    import torch
-
-    return torch, torch.device("cuda", 0)
 
 
 def _host(t):
@@ -34,8 +30,7 @@ def _host(t):
 
 
 def _sentinel(rows):
-    torch, dev = _torch()
-    return torch.full((rows, 4), SENTINEL, dtype=torch.int64, device=dev)
+    return torch.full((rows, 4), SENTINEL, dtype=torch.int64, device=DEV)
 
 
 def test_pins_through_the_host_form(lib):
@@ -43,7 +38,6 @@ def test_pins_through_the_host_form(lib):
         got = A.random_fr(SEED, 1, first=first, stream_id=stream_id)
         assert got.shape == (1, 4) and stored_number(got[0]) == stored, hex(first)
     # ... and a run of the host form equals the device form
-    torch, dev = _torch()
     host = A.random_fr(SEED, 1000, first=12345, stream_id=9)
     device = E.random_fr_device(SEED, 1000, first=12345, stream_id=9)
     torch.cuda.synchronize()
@@ -51,7 +45,6 @@ def test_pins_through_the_host_form(lib):
 
 
 def test_a_column_equals_the_restatement_in_full(lib):
-    torch, dev = _torch()
     n = (1 << 16) + 37
     got = E.random_fr_device(SEED, n)
     torch.cuda.synchronize()
@@ -59,7 +52,6 @@ def test_a_column_equals_the_restatement_in_full(lib):
 
 
 def test_one_call_equals_the_range_cut_at_uneven_points(lib):
-    torch, dev = _torch()
     n = 1 << 22
     seed, stream_id, first = bytes(range(7, 39)), 0xABCDEF0123, (1 << 32) - (1 << 21) - 11           # the counter's low word wraps inside the range
     whole = E.random_fr_device(seed, n, first=first, stream_id=stream_id)
@@ -75,12 +67,11 @@ def test_one_call_equals_the_range_cut_at_uneven_points(lib):
     while len(idx) < 4096:
         idx.add(rng.randrange(n))
     idx = sorted(idx)
-    sample = _host(whole[torch.tensor(idx, device=dev)])
+    sample = _host(whole[torch.tensor(idx, device=DEV)])
     assert np.array_equal(sample, restate(seed, stream_id, [first + i for i in idx]))
 
 
 def test_counters_at_their_edges_and_the_end_of_the_stream(lib):
-    torch, dev = _torch()
     for first in ((1 << 32) - 5, (1 << 64) - 64):
         got = E.random_fr_device(SEED, 64, first=first, stream_id=3)
         torch.cuda.synchronize()
@@ -98,7 +89,6 @@ def test_counters_at_their_edges_and_the_end_of_the_stream(lib):
 @pytest.mark.parametrize("count", [1, 5, 6])
 @pytest.mark.parametrize("n_cols", [1, 3, 270, 2048])
 def test_rows_form_equals_the_flat_stream_and_touches_nothing_else(lib, n_cols, count):
-    torch, dev = _torch()
     rows = 1 << 13
     row0 = rows - count
     seed, stream_id, first = bytes(range(100, 132)), 5, (1 << 32) - 1000
@@ -114,11 +104,10 @@ def test_rows_form_equals_the_flat_stream_and_touches_nothing_else(lib, n_cols, 
 
 def test_seed_and_pointer_array_are_consumed_before_the_call_returns(lib):
     """both are overwritten as soon as the call returns, with work still queued on the stream in front of it"""
-    torch, dev = _torch()
     rows, n_cols, count = 1 << 13, 270, 5
-    side = torch.cuda.Stream(device=dev)
+    side = torch.cuda.Stream(device=DEV)
     sid = side.cuda_stream
-    busy = torch.empty((1 << 24, 4), dtype=torch.int64, device=dev)
+    busy = torch.empty((1 << 24, 4), dtype=torch.int64, device=DEV)
     cols = [_sentinel(rows) for _ in range(n_cols)]
     decoy = _sentinel(rows)
     flat = _sentinel(1 << 20)
@@ -142,7 +131,6 @@ def test_seed_and_pointer_array_are_consumed_before_the_call_returns(lib):
 
 
 def test_no_ops_and_bad_arguments_return_a_status(lib):
-    torch, dev = _torch()
     seed = (C.c_uint8 * 32)(*SEED)
     buf = _sentinel(64)
     ptrs = (C.c_void_p * 2)(buf.data_ptr(), buf.data_ptr() + 32 * 32)
@@ -174,13 +162,12 @@ def test_no_ops_and_bad_arguments_return_a_status(lib):
 def test_a_filled_column_commits_to_the_oracles_point(lib, cref):
     """the vanishing argument's use: fill a column of 2^16 coefficients in HBM, commit it against params.g -- the same point as the oracle's
     multi-exponentiation over the RESTATED coefficients"""
-    torch, dev = _torch()
     k = 16
     n = 1 << k
     seed = bytes(range(200, 232))
     with Z.ParamsKZG.setup(k, 0x5EED5) as params:
         col = E.random_fr_device(seed, n, first=0, stream_id=1)
-        point = torch.zeros(12, dtype=torch.int64, device=dev)
+        point = torch.zeros(12, dtype=torch.int64, device=DEV)
         params.commit_device(col.data_ptr(), n, point.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         coeffs = restate(seed, 1, list(range(n)))

@@ -13,6 +13,7 @@ import pytest
 
 from oracle import bn254 as O
 from zksnap_circuits_halo2_amd import _lib, fields as F
+from zksnap_circuits_halo2_amd.tensors import from_words
 
 pytestmark = pytest.mark.gpu
 
@@ -56,7 +57,7 @@ class Dev:
 
 def to_ints(a):
     """(n, 4) uint64 limbs -> the n raw integers"""
-    return [r[0] | r[1] << 64 | r[2] << 128 | r[3] << 192 for r in np.asarray(a, dtype=np.uint64).reshape(-1, 4).tolist()]
+    return from_words(np.asarray(a, dtype=np.uint64).reshape(-1, 4))
 
 
 def all_below_q(a):

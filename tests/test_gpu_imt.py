@@ -8,13 +8,13 @@ leaf the previous new leaf, descending order sends every step to leaf 0, and dep
 import ctypes as C
 import random
 
-import numpy as np
 import pytest
 import torch
 
 import poseidon_reference as PR
 from oracle import bn254 as O
 from zksnap_circuits_halo2_amd import _lib, fields as F, poseidon as PS
+from zksnap_circuits_halo2_amd.tensors import fr_ints as ints
 
 pytestmark = pytest.mark.gpu
 R = O.R_MOD
@@ -73,10 +73,6 @@ def host_hash(values):
 
 def ref_hash(values):
     return PR.hash(*values)
-
-
-def ints(t):
-    return F.fr_decode(np.ascontiguousarray(t.cpu().numpy()).view(np.uint64).reshape(-1, 4))
 
 
 def witnesses(batch):

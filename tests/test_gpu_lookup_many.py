@@ -8,6 +8,7 @@ Switches of method inside the two calls, each with a size on both sides here:
   single_call_route                    the Python mirror hands ONE lookup of 2^20 usable rows or more to the single-lookup call (same bytes)
   product_levels                       the prefix product of the products call adds a level at n = 32, 512, 8192, 2^17 (16 elements per thread)"""
 import ctypes as C
+import functools
 import os
 import random
 import re
@@ -15,48 +16,29 @@ import sys
 
 import numpy as np
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from oracle import bn254 as O
 from zksnap_circuits_halo2_amd import _lib, evaluation as E, fields as F
+from zksnap_circuits_halo2_amd.tensors import fr_from_small, fr_ints as ints, fr_words
 
 pytestmark = pytest.mark.gpu
 R = F.R_MOD
+DEV = torch.device("cuda", 0)
+words = functools.partial(fr_words, device=DEV)
 BETA, GAMMA, THETA = 0x1234567 * 0x10001 + (1 << 200), (1 << 250) + 99, 7
 SENTINEL = 0x5E5E5E5E5E5E5E5E5E5E5E5E5E5E5E5E
 
 
-def _torch():
-    import torch
-
-    return torch, torch.device("cuda", 0)
-
-
-def words(vals):
-    torch, dev = _torch()
-    return torch.from_numpy(F.fr_encode(vals).view(np.int64)).to(dev)
-
-
-def ints(t):
-    return F.fr_decode(t.cpu().numpy().view(np.uint64))
-
-
 def small_ints(v, k):
     """int64 device tensor of n = 2^k small non-negative integers -> Montgomery words, on the current stream"""
-    torch, dev = _torch()
-    prog = E.RowProgram()
-    prog.emit(E.OP_MUL, 0, prog.column(0), prog.constant(pow(2, 256, R)))
-    a = torch.zeros((v.shape[0], 4), dtype=torch.int64, device=dev)
-    a[:, 0] = v
-    out = torch.empty_like(a)
-    prog.run_device([a.data_ptr()], k, out.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
-    return out
+    return fr_from_small(v, k, stream=torch.cuda.current_stream().cuda_stream)
 
 
 def sentinel(shape_rows, count=None):
-    torch, dev = _torch()
     row = words([SENTINEL])[0]
     shape = (shape_rows, 4) if count is None else (count, shape_rows, 4)
     return row.expand(shape).contiguous()
@@ -122,12 +104,11 @@ _PROGS = {}
 
 
 def composed_product(lib, lk, table, pa, ps, k):
-    torch, dev = _torch()
     if "p" not in _PROGS:
         _PROGS["p"] = E.lookup_product_programs(1, 1, BETA, GAMMA, THETA)
     pn, pd = _PROGS["p"]
     n = 1 << k
-    zl, den = torch.empty((n, 4), dtype=torch.int64, device=dev), torch.empty((n, 4), dtype=torch.int64, device=dev)
+    zl, den = torch.empty((n, 4), dtype=torch.int64, device=DEV), torch.empty((n, 4), dtype=torch.int64, device=DEV)
     pn.run_device([lk.data_ptr(), table.data_ptr()], k, zl.data_ptr())
     pd.run_device([pa.data_ptr(), ps.data_ptr()], k, den.data_ptr())
     _lib.check(lib.zkhip_fr_grand_product_device(zl.data_ptr(), den.data_ptr(), n, zl.data_ptr(), None))
@@ -135,7 +116,6 @@ def composed_product(lib, lk, table, pa, ps, k):
 
 
 def check_case(lib, L, combo, shape, k, u, seed, oracle_permute=True, oracle_product=False):
-    torch, dev = _torch()
     n = 1 << k
     inputs, tabs, input_ints, table_ints = build(L, combo, shape, n, u, seed)
     pa, ps = E.permute_expression_pairs_device(inputs, tabs, u, k, sentinel(n, L), sentinel(n, L))
@@ -198,22 +178,20 @@ def test_scan_depth_switch(lib, name, k, u, shape):
 
 
 def _range_columns(k, L, bits, seed):
-    torch, dev = _torch()
     n = 1 << k
-    g = torch.Generator(device=dev)
+    g = torch.Generator(device=DEV)
     g.manual_seed(seed)
-    rows = torch.arange(n, dtype=torch.int64, device=dev)
+    rows = torch.arange(n, dtype=torch.int64, device=DEV)
     tv = rows % (1 << bits)
     ivs = []
     for _ in range(L):
-        iv = torch.randint(0, 1 << bits, (n,), dtype=torch.int64, device=dev, generator=g)
-        iv[torch.rand(n, device=dev, generator=g) < 0.4] = 0                                  # padding zeros: one heavy slot
+        iv = torch.randint(0, 1 << bits, (n,), dtype=torch.int64, device=DEV, generator=g)
+        iv[torch.rand(n, device=DEV, generator=g) < 0.4] = 0                                  # padding zeros: one heavy slot
         ivs.append(iv)
     return tv, ivs, small_ints(tv, k), [small_ints(iv, k) for iv in ivs]
 
 
 def test_2p20_against_numpy_oracle_and_single_call(lib):
-    torch, dev = _torch()
     k, L = 20, 2
     n, u = 1 << k, (1 << k) - 6
     tv, ivs, table, inputs = _range_columns(k, L, 16, 20)
@@ -221,8 +199,8 @@ def test_2p20_against_numpy_oracle_and_single_call(lib):
     z = E.lookup_products_device(inputs, [table] * L, pa, ps, u, k, BETA, GAMMA)
     for l in range(L):
         ea, es = O.permute_expression_pair_np(ivs[l].cpu().numpy(), tv.cpu().numpy(), u)
-        assert torch.equal(pa[l, :u], small_ints(torch.from_numpy(np.concatenate([ea, np.zeros(n - u, dtype=np.int64)])).to(dev), k)[:u])
-        assert torch.equal(ps[l, :u], small_ints(torch.from_numpy(np.concatenate([es, np.zeros(n - u, dtype=np.int64)])).to(dev), k)[:u])
+        assert torch.equal(pa[l, :u], small_ints(torch.from_numpy(np.concatenate([ea, np.zeros(n - u, dtype=np.int64)])).to(DEV), k)[:u])
+        assert torch.equal(ps[l, :u], small_ints(torch.from_numpy(np.concatenate([es, np.zeros(n - u, dtype=np.int64)])).to(DEV), k)[:u])
         ra, rs = single_permute(lib, inputs[l], table, u, n)
         assert torch.equal(pa[l, :u], ra[:u]) and torch.equal(ps[l, :u], rs[:u])
         assert torch.equal(pa[l, u:], ra[u:]) and torch.equal(ps[l, u:], rs[u:])               # the sentinel rows
@@ -233,7 +211,6 @@ def test_2p20_against_numpy_oracle_and_single_call(lib):
 
 @pytest.mark.parametrize("name,u", [("scan_two_levels", (1 << 22) - 1), ("scan_three_levels", 1 << 22)])
 def test_scan_third_level_switch(lib, name, u):
-    torch, dev = _torch()
     k = 22
     n = 1 << k
     tv, ivs, table, inputs = _range_columns(k, 1, 18, u)
@@ -251,7 +228,6 @@ def test_scan_third_level_switch(lib, name, u):
 
 @pytest.mark.parametrize("name,u", [("many_lookup_call", (1 << 20) - 6), ("single_call_route", 1 << 20)])
 def test_single_lookup_route(lib, name, u):
-    torch, dev = _torch()
     k = 20
     n = 1 << k
     assert (u >= E.SINGLE_LOOKUP_ROWS) == (name == "single_call_route")
@@ -270,7 +246,6 @@ def _five(k=10):
 
 @pytest.mark.parametrize("bad,lowest", [((2,), 2), ((1, 3), 1), ((3, 1), 1), ((4, 0), 0)])
 def test_missing_value_names_the_lowest_lookup_and_the_next_call_works(lib, bad, lowest):
-    torch, dev = _torch()
     n, u, k, inputs, tabs = _five()
     good = [c.clone() for c in inputs]
     for l in bad:
@@ -302,7 +277,6 @@ def test_wide_input_against_a_narrow_table_is_an_error(lib):
 
 
 def test_argument_errors_and_empty_calls(lib):
-    torch, dev = _torch()
     n, u, k, inputs, tabs = _five()
     iptr = (C.c_void_p * 5)(*[c.data_ptr() for c in inputs])
     tptr = (C.c_void_p * 5)(*[c.data_ptr() for c in tabs])
@@ -335,7 +309,6 @@ def test_argument_errors_and_empty_calls(lib):
 
 # ---- streams ----------------------------------------------------------------------------------------------------------------------------------
 def _reference(lib, inputs, tabs, u, k):
-    torch, dev = _torch()
     n = 1 << k
     pas, pss, zs = [], [], []
     for lk, tb in zip(inputs, tabs):
@@ -345,13 +318,12 @@ def _reference(lib, inputs, tabs, u, k):
 
 
 def test_inputs_from_an_unsynchronised_kernel_on_a_side_stream(lib):
-    torch, dev = _torch()
     k, L, bits = 13, 8, 8
     n, u = 1 << k, (1 << k) - 6
     side = torch.cuda.Stream()
     torch.cuda.synchronize()
     with torch.cuda.stream(side):
-        rows = torch.arange(n, dtype=torch.int64, device=dev)
+        rows = torch.arange(n, dtype=torch.int64, device=DEV)
         table = small_ints(rows % (1 << bits), k)
         inputs = [small_ints((rows * (2 * l + 3) + l) % (1 << bits), k) for l in range(L)]      # produced on `side`, never waited for
         pa, ps = E.permute_expression_pairs_device(inputs, [table] * L, u, k, sentinel(n, L), sentinel(n, L), stream=side.cuda_stream)
@@ -362,7 +334,6 @@ def test_inputs_from_an_unsynchronised_kernel_on_a_side_stream(lib):
 
 
 def test_back_to_back_calls_reuse_the_scratch(lib):
-    torch, dev = _torch()
     k = 12
     n, u = 1 << k, (1 << k) - 6
     i8, t8, _, _ = build(8, "aab", "range", n, u, 8)
@@ -378,7 +349,6 @@ def test_back_to_back_calls_reuse_the_scratch(lib):
 
 
 def test_calls_on_two_streams_at_once(lib):
-    torch, dev = _torch()
     k = 13
     n, u = 1 << k, (1 << k) - 6
     ia, ta, _, _ = build(8, "shared", "range", n, u, 21)

@@ -1,29 +1,22 @@
 """GPU: `mock.MockProver` over device-resident columns against `mock.verify_host` (Python integers) on witnesses of the halo2-lib shape built
 the way tools/prove_flow.py builds them -- vertical gates on rows 0, 4, 8, ..., range-lookup columns against one table, copy cycles across
 advice columns and the constants column -- and the `mock=` step of the flow itself."""
+import functools
 import random
 
-import numpy as np
 import pytest
+import torch
 
 from zksnap_circuits_halo2_amd import evaluation as E, fields as F, mock as M
 from zksnap_circuits_halo2_amd.keygen import Assembly
+from zksnap_circuits_halo2_amd.tensors import fr_words
 
 pytestmark = pytest.mark.gpu
 R = F.R_MOD
+DEV = torch.device("cuda", 0)
+words = functools.partial(fr_words, device=DEV)
 BLIND = 5
 G, NL, BITS = 5, 2, 6
-
-
-def _torch():
-    import torch
-
-    return torch, torch.device("cuda", 0)
-
-
-def words(vals):
-    torch, dev = _torch()
-    return torch.from_numpy(F.fr_encode(vals).view(np.int64)).to(dev)
 
 
 def build_witness(k, seed):

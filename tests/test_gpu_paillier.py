@@ -8,6 +8,7 @@ import torch
 
 import paillier_cases as PC
 from zksnap_circuits_halo2_amd import paillier as P, poseidon
+from zksnap_circuits_halo2_amd.tensors import fr_ints
 
 pytestmark = pytest.mark.gpu
 
@@ -154,4 +155,4 @@ def test_nullifier_values(lib):
     for x, y in points:
         raw = x.to_bytes(32, "little")
         want.append(poseidon.hash([3 if y % 2 else 2] + [int.from_bytes(raw[at:at + 11], "little") for at in (0, 11, 22)]))
-    assert poseidon._ints(got) == want
+    assert fr_ints(got) == want

@@ -11,6 +11,7 @@ import torch
 import poseidon_reference as PR
 from oracle import bn254 as O
 from zksnap_circuits_halo2_amd import _lib, fields as F, poseidon as PS
+from zksnap_circuits_halo2_amd.tensors import fr_ints as to_ints
 
 pytestmark = pytest.mark.gpu
 R = O.R_MOD
@@ -21,10 +22,6 @@ EDGE = [0, 1, R - 1, 1 << 64, (1 << 253) + 5, R - (1 << 64)]
 
 def to_device(ints, *shape):
     return torch.from_numpy(F.fr_encode(ints).view(np.int64)).reshape(*shape, 4).to("cuda")
-
-
-def to_ints(t):
-    return F.fr_decode(t.cpu().numpy().view(np.uint64))
 
 
 @pytest.mark.parametrize("width", [1, 2, 3, 4, 5, PS.MAX_WIDTH])

@@ -10,7 +10,7 @@ import torch
 
 import plume_cases as PC
 from zksnap_circuits_halo2_amd import plume as PL, poseidon
-from zksnap_circuits_halo2_amd.fields import fr_decode
+from zksnap_circuits_halo2_amd.tensors import fr_ints as _ints
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +32,6 @@ def points():
 @functools.lru_cache(maxsize=None)
 def host_hashes(layout):
     return tuple(poseidon.hash(PACKERS[layout](p)) for p in points())
-
-
-def _ints(t):
-    return fr_decode(t.cpu().numpy().view("uint64"))
 
 
 def test_the_packers_cut_at_bytes_11_and_22():

@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.dirname(__file__))
 import torch
 
 from zksnap_circuits_halo2_amd import _lib, evaluation as E, fields as F
+from zksnap_circuits_halo2_amd.tensors import fr_from_small as small_ints
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=9)
@@ -31,16 +32,6 @@ dev = torch.device("cuda", 0)
 R = F.R_MOD
 BETA, GAMMA, THETA = 0xB17A % R, (1 << 201) + 5, 3
 torch.manual_seed(9)
-
-
-def small_ints(v, k):
-    prog = E.RowProgram()
-    prog.emit(E.OP_MUL, 0, prog.column(0), prog.constant(pow(2, 256, R)))
-    a = torch.zeros((v.shape[0], 4), dtype=torch.int64, device=dev)
-    a[:, 0] = v
-    out = torch.empty_like(a)
-    prog.run_device([a.data_ptr()], k, out.data_ptr())
-    return out
 
 
 def fmt(ts):

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from . import fields as F
+from .buffers import DeviceBuffer
 
 # operand kinds / opcodes of include/zkhip.h
 SRC_CONST, SRC_REG, SRC_COLUMN, SRC_PREV, SRC_ROWPOW = 0, 1, 2, 3, 4
@@ -631,16 +632,10 @@ class RowShards:
     def download(self, col: int) -> np.ndarray:
         """the whole column (2^ext_k elements) gathered to the primary and copied to the host"""
         n = 1 << self.ext_k
-        d = C.c_void_p()
-        _lib.check(self.lib.zkhip_alloc(n * 32, C.byref(d)))
-        try:
-            self.gather_device(col, d.value)
+        with DeviceBuffer(n * 32) as d:
+            self.gather_device(col, d.address)
             _lib.check(self.lib.zkhip_stream_sync(None))
-            out = np.empty((n, 4), dtype=np.uint64)
-            _lib.check(self.lib.zkhip_download(out.ctypes.data, d, out.nbytes))
-        finally:
-            self.lib.zkhip_free(d)
-        return out
+            return d.download((n, 4))
 
     def destroy(self) -> None:
         if self.handle:

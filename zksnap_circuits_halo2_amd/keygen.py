@@ -38,6 +38,7 @@ from typing import BinaryIO, List, Optional, Sequence
 import numpy as np
 
 from . import _lib, evaluation as E
+from .buffers import DeviceBuffer
 from .domain import EvaluationDomain
 from .fields import Q_MOD, R_MOD, fr_encode
 
@@ -105,37 +106,6 @@ def _omega(k: int) -> int:
     return omega_for(k)
 
 
-# ---------------------------------------------------------------------------------------------------
-# device helpers (no torch in the package: buffers come from the C ABI)
-# ---------------------------------------------------------------------------------------------------
-class _DeviceBuffer:
-    def __init__(self, nbytes: int):
-        self.lib = _lib.load()
-        self.ptr = C.c_void_p()
-        self.nbytes = nbytes
-        _lib.check(self.lib.zkhip_alloc(nbytes, C.byref(self.ptr)))
-
-    def upload(self, a: np.ndarray, offset: int = 0) -> None:
-        a = np.ascontiguousarray(a)
-        _lib.check(self.lib.zkhip_upload(C.c_void_p(self.ptr.value + offset), a.ctypes.data, a.nbytes))
-
-    def download(self, shape, offset: int = 0) -> np.ndarray:
-        out = np.empty(shape, dtype=np.uint64)
-        _lib.check(self.lib.zkhip_download(out.ctypes.data, C.c_void_p(self.ptr.value + offset), out.nbytes))
-        return out
-
-    def free(self) -> None:
-        if self.ptr:
-            self.lib.zkhip_free(self.ptr)
-            self.ptr = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-
-
 def _transform_columns(dom: EvaluationDomain, lagrange: Sequence[np.ndarray], want_cosets: bool = True, max_bytes: int = 1 << 32):
     """(polys, cosets) of Lagrange-basis columns: batched `lagrange_to_coeff` then batched `coeff_to_extended`, in groups of columns
     that keep the device buffers under `max_bytes`."""
@@ -147,13 +117,13 @@ def _transform_columns(dom: EvaluationDomain, lagrange: Sequence[np.ndarray], wa
     for g0 in range(0, len(lagrange), group):
         cols = lagrange[g0:g0 + group]
         m = len(cols)
-        with _DeviceBuffer(m * n * 32) as d_c:
+        with DeviceBuffer(m * n * 32) as d_c:
             d_c.upload(np.stack([np.ascontiguousarray(c, dtype=np.uint64).reshape(n, 4) for c in cols]))
             _lib.check(lib.zkhip_ifft_scaled_batch_device(d_c.ptr, dom.omega_inv.ctypes.data, dom.k, dom.ifft_divisor.ctypes.data, m, n, None))
             pc = d_c.download((m, n, 4))
             polys.extend(pc[i] for i in range(m))
             if want_cosets:
-                with _DeviceBuffer(m * en * 32) as d_e:
+                with DeviceBuffer(m * en * 32) as d_e:
                     _lib.check(lib.zkhip_coeff_to_extended_device(d_c.ptr, n, dom.k, d_e.ptr, en, dom.extended_k, m, dom.extended_omega.ctypes.data,
                                                                   dom.g_coset.ctypes.data, None))
                     ec = d_e.download((m, en, 4))
@@ -383,7 +353,7 @@ class DeviceProvingKey:
     `evaluation.quotient_halos`): each device of zkhip_init holds its rows of every coset, and the coset accessors return
     `RowShards.ref` addresses for COL_ROW_SHARDS.  The n-element columns stay on the primary either way."""
 
-    def __init__(self, vk: VerifyingKey, cs: E.ConstraintSystem, ext: Optional[_DeviceBuffer], base: _DeviceBuffer,
+    def __init__(self, vk: VerifyingKey, cs: E.ConstraintSystem, ext: Optional[DeviceBuffer], base: DeviceBuffer,
                  shards: Optional[E.RowShards] = None):
         self.vk, self.cs, self.k, self.n = vk, cs, vk.k, 1 << vk.k
         self.en = EvaluationDomain(cs.degree, vk.k).extended_len()
@@ -422,9 +392,9 @@ class DeviceProvingKey:
         if row_shards:
             shards = E.RowShards(ek, 3 + cols, *E.quotient_halos(cs, vk.k, ek))
         else:
-            ext = _DeviceBuffer(max(1, (3 + cols) * (1 << ek) * 32))
+            ext = DeviceBuffer(max(1, (3 + cols) * (1 << ek) * 32))
         try:
-            base = _DeviceBuffer(max(1, 2 * cols * n * 32))
+            base = DeviceBuffer(max(1, 2 * cols * n * 32))
         except Exception:
             if ext is not None:
                 ext.free()
@@ -496,7 +466,7 @@ def _sigma_to_device(assembly: Assembly, k: int, d_out: int) -> None:
     n, ncol = 1 << k, assembly.n_columns
     if ncol == 0:
         return
-    with _DeviceBuffer(n * 32) as d_pow, _DeviceBuffer(ncol * 32) as d_delta, _DeviceBuffer(2 * ncol * n * 4) as d_idx:
+    with DeviceBuffer(n * 32) as d_pow, DeviceBuffer(ncol * 32) as d_delta, DeviceBuffer(2 * ncol * n * 4) as d_idx:
         powers = E.RowProgram(omega=_omega(k))
         powers.emit(E.OP_MOV, 0, E.RowProgram.ROWPOW)
         powers.run_device([], k, d_pow.ptr.value)
@@ -517,7 +487,7 @@ def _commit_lagrange_device(params, d_columns: int, count: int) -> np.ndarray:
     if count == 0:
         return np.zeros((0, 8), dtype=np.uint64)
     n = 1 << params.k
-    with _DeviceBuffer(count * (96 + 64)) as d_out:
+    with DeviceBuffer(count * (96 + 64)) as d_out:
         # the columns lie back to back: ONE batched call (a launch set for all of them when they are small, overlapped pairs when they are large)
         _lib.check(lib.zkhip_msm_g1_registered_batch_device(params.g_lagrange.ctypes.data, C.c_void_p(d_columns), n, count, n, d_out.ptr, None))
         _lib.check(lib.zkhip_g1_batch_normalize_device(d_out.ptr, count, C.c_void_p(d_out.ptr.value + count * 96), None))
@@ -573,7 +543,7 @@ def keygen_device(params, cs: E.ConstraintSystem, fixed: Sequence[np.ndarray], a
         ind[0, 0] = one
         ind[1, u] = one
         ind[2, :u] = one
-        with _DeviceBuffer(3 * n * 32) as d_l:
+        with DeviceBuffer(3 * n * 32) as d_l:
             d_l.upload(ind)
             _lib.check(lib.zkhip_ifft_scaled_batch_device(d_l.ptr, dom.omega_inv.ctypes.data, k, dom.ifft_divisor.ctypes.data, 3, n, None))
             _lib.check(lib.zkhip_coeff_to_extended_device(d_l.ptr, n, k, C.c_void_p(pk._e(0)), en, dom.extended_k, 3, dom.extended_omega.ctypes.data,

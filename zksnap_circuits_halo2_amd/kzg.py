@@ -6,30 +6,18 @@ import numpy as np
 
 from . import _lib
 from .arithmetic import best_multiexp
+from .buffers import DeviceBuffer
 
 
 def g_to_lagrange(g: np.ndarray, k: int) -> np.ndarray:
     """`g_to_lagrange(g_projective, k)` [DEP poly/kzg/commitment.rs]: the Lagrange-basis SRS of a monomial-basis SRS whose trapdoor is not
     known, g_lagrange[i] = (1/n) sum_j omega^(-i j) g[j] -- an inverse FFT over G1 points on the GPU (`zkhip_g_to_lagrange_device`)."""
-    import ctypes as C
-
     n = 1 << k
     g = np.ascontiguousarray(g, dtype=np.uint64).reshape(n, 8)
-    lib = _lib.load()
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    _lib.check(lib.zkhip_alloc(n * 64, C.byref(d_in)))
-    try:
-        _lib.check(lib.zkhip_alloc(n * 64, C.byref(d_out)))
-        try:
-            _lib.check(lib.zkhip_upload(d_in, g.ctypes.data, n * 64))
-            _lib.check(lib.zkhip_g_to_lagrange_device(d_in, k, d_out, None))
-            out = np.zeros((n, 8), dtype=np.uint64)
-            _lib.check(lib.zkhip_download(out.ctypes.data, d_out, n * 64))
-            return out
-        finally:
-            lib.zkhip_free(d_out)
-    finally:
-        lib.zkhip_free(d_in)
+    with DeviceBuffer(n * 64) as d_in, DeviceBuffer(n * 64) as d_out:
+        d_in.upload(g)
+        _lib.check(_lib.load().zkhip_g_to_lagrange_device(d_in.ptr, k, d_out.ptr, None))
+        return d_out.download((n, 8))
 
 
 class ParamsKZG:
@@ -70,8 +58,6 @@ class ParamsKZG:
         benches and `gen_srs` test parameters amount to: /root/reference/voter/benches/voter_circuit.rs:60): g[i] = [s^i] G and
         g_lagrange[i] = [(s^n - 1)/n * w^i / (s - w^i)] G, both computed on the GPU -- the scalar vectors with the Fr primitives
         (prefix product, row programs, batch inversion), the points with the fixed-base multiplication."""
-        import ctypes as C
-
         from . import evaluation as E
         from .fields import R_MOD, fr_encode, omega_for
 
@@ -80,34 +66,25 @@ class ParamsKZG:
         omega = omega_for(k)
         assert pow(s, n, R_MOD) != 1, "the trapdoor lies in the evaluation domain"
         lib = _lib.load()
-        d_sc, d_tmp, d_pts = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        for ptr, size in ((d_sc, n * 32), (d_tmp, n * 32), (d_pts, n * 64)):
-            _lib.check(lib.zkhip_alloc(size, C.byref(ptr)))
-        try:
+        with DeviceBuffer(n * 32) as d_sc, DeviceBuffer(n * 32) as d_tmp, DeviceBuffer(n * 64) as d_pts:
             def points() -> np.ndarray:
-                _lib.check(lib.zkhip_g1_fixed_base_mul_device(d_sc, n, d_pts, None))
-                out = np.zeros((n, 8), dtype=np.uint64)
-                _lib.check(lib.zkhip_download(out.ctypes.data, d_pts, n * 64))
-                return out
+                _lib.check(lib.zkhip_g1_fixed_base_mul_device(d_sc.ptr, n, d_pts.ptr, None))
+                return d_pts.download((n, 8))
 
             # s^i: exclusive prefix product of the constant vector (s, s, ...)
-            const = np.ascontiguousarray(np.tile(fr_encode([s]), (n, 1)))
-            _lib.check(lib.zkhip_upload(d_sc, const.ctypes.data, n * 32))
-            _lib.check(lib.zkhip_fr_prefix_product_device(d_sc, n, d_sc, None))
+            d_sc.upload(np.tile(fr_encode([s]), (n, 1)))
+            _lib.check(lib.zkhip_fr_prefix_product_device(d_sc.ptr, n, d_sc.ptr, None))
             g = points()
             # Lagrange scalars: (s - w^i) -> inverse -> times w^i * (s^n - 1) / n
             den = E.RowProgram(omega=omega)
             den.emit(E.OP_SUB, 0, den.constant(s), E.RowProgram.ROWPOW)
-            den.run_device([], k, d_tmp.value)
-            _lib.check(lib.zkhip_fr_batch_invert_device(d_tmp, n, None))
+            den.run_device([], k, d_tmp.address)
+            _lib.check(lib.zkhip_fr_batch_invert_device(d_tmp.ptr, n, None))
             num = E.RowProgram(omega=omega)
             num.emit(E.OP_MUL, 0, E.RowProgram.ROWPOW, num.column(0))
             num.emit(E.OP_MUL, 0, E.RowProgram.reg(0), num.constant((pow(s, n, R_MOD) - 1) * pow(n, -1, R_MOD) % R_MOD))
-            num.run_device([d_tmp.value], k, d_sc.value)
+            num.run_device([d_tmp.address], k, d_sc.address)
             g_lagrange = points()
-        finally:
-            for ptr in (d_sc, d_tmp, d_pts):
-                lib.zkhip_free(ptr)
         from . import srs
 
         return cls(k, g, g_lagrange, srs.g2_encode(srs.G2_GENERATOR), srs.g2_encode(srs.g2_mul(s)))

@@ -30,6 +30,8 @@ import numpy as np
 from . import _lib
 from . import evaluation as E
 from . import fields as F
+from .buffers import DeviceBuffer
+from .tensors import fr_ints
 
 NONE = (1 << 64) - 1          # `first` of a record without failures
 DEFAULT_THETA = 0x2545F4914F6CDD1D_9E3779B97F4A7C15_BF58476D1CE4E5B9_94D049BB133111EB % F.R_MOD
@@ -127,8 +129,6 @@ class MockProver:
 
     def __init__(self, cs: E.ConstraintSystem, k: int, fixed, advice, instance=(), assembly=None, theta: int = DEFAULT_THETA, challenges: Sequence[int] = (),
                  stream=None):
-        from .keygen import _DeviceBuffer
-
         if len(fixed) != cs.num_fixed or len(advice) != cs.num_advice or len(instance) != cs.num_instance:
             raise ValueError("columns do not match the constraint system")
         self.cs, self.k, self.n, self.stream = cs, k, 1 << k, stream
@@ -141,7 +141,7 @@ class MockProver:
         self._buffers = []
 
         def buffer(nbytes):
-            b = _DeviceBuffer(nbytes)
+            b = DeviceBuffer(nbytes)
             self._buffers.append(b)
             return b
 
@@ -233,9 +233,7 @@ class MockProver:
 # the same contract in plain Python integers
 # ---------------------------------------------------------------------------------------------------
 def _ints(col) -> List[int]:
-    if isinstance(col, np.ndarray):
-        return F.fr_decode(np.ascontiguousarray(col).view(np.uint64).reshape(-1, 4))
-    return [int(v) % F.R_MOD for v in col]
+    return fr_ints(col) if isinstance(col, np.ndarray) else [int(v) % F.R_MOD for v in col]
 
 
 def _evaluate(e: E.Expr, cols, row: int, n: int, challenges: Sequence[int]) -> int:

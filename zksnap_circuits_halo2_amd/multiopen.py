@@ -22,6 +22,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 
 from . import _lib, evaluation as E
+from .buffers import DeviceBuffer
 from .fields import R_MOD, fr_decode, fr_encode
 
 
@@ -52,17 +53,12 @@ def evaluate_queries(queries: Sequence[ProverQuery], k: int, stream: int = 0) ->
     lib = _lib.load()
     n = 1 << k
     for point, qs in construct_intermediate_sets([q for q in queries if q.eval is None]):
-        out = C.c_void_p()
-        _lib.check(lib.zkhip_alloc(len(qs) * 32, C.byref(out)))
-        try:
+        with DeviceBuffer(len(qs) * 32) as out:
             ptrs = (C.c_void_p * len(qs))(*[q.poly for q in qs])
             x = fr_encode([point])[0]
-            _lib.check(lib.zkhip_fr_eval_polynomial_batch_device(ptrs, len(qs), n, x.ctypes.data, out, stream))
-            host = np.zeros((len(qs), 4), dtype=np.uint64)
+            _lib.check(lib.zkhip_fr_eval_polynomial_batch_device(ptrs, len(qs), n, x.ctypes.data, out.ptr, stream))
             _lib.check(lib.zkhip_stream_sync(stream))        # zkhip_download copies on the legacy default stream: not ordered behind a non-blocking `stream`
-            _lib.check(lib.zkhip_download(host.ctypes.data, out, host.nbytes))
-        finally:
-            lib.zkhip_free(out)
+            host = out.download((len(qs), 4))
         for q, e in zip(qs, fr_decode(host)):
             q.eval = e
 
@@ -89,18 +85,15 @@ class _BufferPool:
     def take(self) -> int:
         if self.free:
             return self.free.pop()
-        p = C.c_void_p()
-        _lib.check(_lib.load().zkhip_alloc(self.n * 32, C.byref(p)))
-        self.all.append(p)
-        return p.value
+        self.all.append(DeviceBuffer(self.n * 32))
+        return self.all[-1].address
 
     def give_back(self, taken: List[int]) -> None:
         self.free.extend(taken)
 
     def close(self) -> None:
-        lib = _lib.load()
-        for p in self.all:
-            lib.zkhip_free(p)
+        for b in self.all:
+            b.free()
         self.all, self.free = [], []
 
 

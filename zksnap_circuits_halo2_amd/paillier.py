@@ -15,6 +15,7 @@ from typing import List, Tuple
 import numpy as np
 
 from . import _lib
+from .tensors import from_words, raw_tensor, stream_of, to_words
 
 WORDS = _lib.ZKHIP_PAILLIER_WORDS
 MAX_N_BITS = _lib.ZKHIP_PAILLIER_MAX_N_BITS
@@ -31,95 +32,31 @@ def add_native(n: int, a: int, b: int) -> int:
     return a * b % (n * n)
 
 
-def _stream_of(stream) -> int:
-    return int(stream) if stream is not None else 0
-
-
-def _shape_of(values):
-    shape = []
-    while isinstance(values, (list, tuple)):
-        shape.append(len(values))
-        if not values:
-            break
-        values = values[0]
-    return shape
-
-
-def _flat(values):
-    if isinstance(values, (list, tuple)):
-        for v in values:
-            yield from _flat(v)
-    else:
-        yield int(values)
-
-
-def _to_words(values, words: int) -> np.ndarray:
-    """integers, nested to any depth -> a [..., words] uint64 array of little-endian words"""
-    shape = _shape_of(values)
-    flat = list(_flat(values))
-    if int(np.prod(shape, dtype=np.int64)) != len(flat):
-        raise ValueError("a ragged list of integers")
-    for v in flat:
-        if not 0 <= v < 1 << (64 * words):
-            raise ValueError(f"an integer outside [0, 2^{64 * words})")
-    raw = b"".join(v.to_bytes(8 * words, "little") for v in flat)
-    return np.frombuffer(raw, dtype=np.uint64).reshape(shape + [words]).copy()
-
-
-def _tensor(values, words: int, device):
-    import torch
-
-    t = torch.from_numpy(_to_words(values, words).view(np.int64))
-    return t.to(_device_of(device))
-
-
-def _device_of(device):
-    import torch
-
-    if device is None:
-        return torch.device("cuda", torch.cuda.current_device())
-    return torch.device(device)
-
-
 def encode(values, device=None):
     """integers below 2^384, nested to any depth -> a [..., 6] int64 tensor on the current device (or `device`)"""
-    return _tensor(values, WORDS, device)
+    return raw_tensor(values, WORDS, device)
 
 
 def encode_exponents(values, device=None):
     """votes below 2^256 (`fe_to_biguint` of an Fr) -> [..., 4] int64"""
-    return _tensor(values, 4, device)
+    return raw_tensor(values, 4, device)
 
 
 def encode_randomness(values, device=None):
     """the r of every encryption, below 2^192 -> [..., 3] int64"""
-    return _tensor(values, 3, device)
+    return raw_tensor(values, 3, device)
 
 
 def decode(tensor):
     """a [..., w] int64 tensor of little-endian words -> integers, nested as the leading dimensions are"""
-    a = np.ascontiguousarray(tensor.detach().cpu().numpy()).view(np.uint64)
-    words = a.shape[-1]
-    raw = a.tobytes()
-    flat = [int.from_bytes(raw[8 * words * i:8 * words * (i + 1)], "little") for i in range(a.size // words)]
-
-    def nest(shape, at):
-        if not shape:
-            return flat[at], at + 1
-        out = []
-        for _ in range(shape[0]):
-            v, at = nest(shape[1:], at)
-            out.append(v)
-        return out, at
-
-    return nest(list(a.shape[:-1]), 0)[0]
+    return from_words(tensor)
 
 
 def _n_words(n: int) -> np.ndarray:
     n = int(n)
     if not 0 <= n < 1 << MAX_N_BITS:
         raise ValueError(f"n must be below 2^{MAX_N_BITS}")
-    return _to_words(n, 3)
+    return to_words(n, 3)
 
 
 def _on_host(n: int) -> bool:
@@ -156,11 +93,11 @@ def mul_device(n: int, a, b, out=None, stream=None):
         raise ValueError("mul_device: out must be a contiguous tensor of a's shape")
     if _on_host(n):
         flat_a, flat_b = decode(a.reshape(-1, WORDS)), decode(b.reshape(-1, WORDS))
-        out.copy_(_tensor([add_native(n, x, y) for x, y in zip(flat_a, flat_b)], WORDS, out.device).reshape(out.shape))
+        out.copy_(raw_tensor([add_native(n, x, y) for x, y in zip(flat_a, flat_b)], WORDS, out.device).reshape(out.shape))
         return out
     _device_call("mul_device", a, b, out)
     nw = _n_words(n)
-    _lib.check(_lib.load().zkhip_paillier_mul_device(nw.ctypes.data, a.data_ptr(), b.data_ptr(), a.numel() // WORDS, out.data_ptr(), _stream_of(stream)))
+    _lib.check(_lib.load().zkhip_paillier_mul_device(nw.ctypes.data, a.data_ptr(), b.data_ptr(), a.numel() // WORDS, out.data_ptr(), stream_of(stream)))
     return out
 
 
@@ -179,11 +116,11 @@ def encrypt_many_device(n: int, g: int, m, r, stream=None):
     if not 0 <= g < 1 << 384:
         raise ValueError("encrypt_many_device: g must be below 2^384")
     if _on_host(n):
-        return _tensor([enc_native(n, g, x, y) for x, y in zip(decode(m), decode(r))], WORDS, m.device).reshape(m.shape[0], WORDS)
+        return raw_tensor([enc_native(n, g, x, y) for x, y in zip(decode(m), decode(r))], WORDS, m.device).reshape(m.shape[0], WORDS)
     _device_call("encrypt_many_device", m, r)
     out = torch.empty((m.shape[0], WORDS), dtype=torch.int64, device=m.device)
-    nw, gw = _n_words(n), _to_words(g, WORDS)
-    _lib.check(_lib.load().zkhip_paillier_encrypt_device(nw.ctypes.data, gw.ctypes.data, m.data_ptr(), r.data_ptr(), m.shape[0], out.data_ptr(), _stream_of(stream)))
+    nw, gw = _n_words(n), to_words(g, WORDS)
+    _lib.check(_lib.load().zkhip_paillier_encrypt_device(nw.ctypes.data, gw.ctypes.data, m.data_ptr(), r.data_ptr(), m.shape[0], out.data_ptr(), stream_of(stream)))
     return out
 
 
@@ -225,10 +162,10 @@ def tally_device(n: int, ballots, init=None, stream=None) -> Tally:
         rows = [[v % n2 for v in decode(init)] if init is not None else [1 % n2] * C]
         for ballot in decode(ballots):
             rows.append([add_native(n, acc, v) for acc, v in zip(rows[-1], ballot)])
-        return Tally(n, ballots, _tensor(rows, WORDS, ballots.device))
+        return Tally(n, ballots, raw_tensor(rows, WORDS, ballots.device))
     _device_call("tally_device", ballots, init)
     running = torch.empty((B + 1, C, WORDS), dtype=torch.int64, device=ballots.device)
     nw = _n_words(n)
     _lib.check(_lib.load().zkhip_paillier_tally_device(nw.ctypes.data, ballots.data_ptr() if B else None, B, C, init.data_ptr() if init is not None else None,
-                                                       running.data_ptr(), _stream_of(stream)))
+                                                       running.data_ptr(), stream_of(stream)))
     return Tally(n, ballots, running)

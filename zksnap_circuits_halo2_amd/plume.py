@@ -18,6 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from .tensors import from_words, raw_tensor, stream_of, to_words
 
 MAX_MSG = _lib.ZKHIP_PLUME_MAX_MSG
 P = 2**256 - 2**32 - 977
@@ -159,54 +160,29 @@ def gen_native(sk: int, msg: bytes, r: int) -> Tuple[Point, Point, int, int]:
 
 
 # ---- tensors -----------------------------------------------------------------------------------------------------------------------------------
-def _stream_of(stream) -> int:
-    return int(stream) if stream is not None else 0
-
-
-def _device_of(device):
-    import torch
-
-    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-
-
 def _words(values: Sequence[int]) -> np.ndarray:
-    for v in values:
-        if not 0 <= int(v) < 1 << 256:
-            raise ValueError("an integer outside [0, 2^256)")
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in values), dtype=np.uint64).copy()
+    return to_words(list(values), 4)
 
 
 def encode_scalars(values: Sequence[int], device=None):
     """integers below 2^256 -> an [n, 4] int64 tensor on the current device (or `device`)"""
-    import torch
-
-    return torch.from_numpy(_words(list(values)).view(np.int64).reshape(len(values), 4)).to(_device_of(device))
+    return raw_tensor(list(values), 4, device)
 
 
 def encode_points(points: Sequence[Point], device=None):
     """(x, y) pairs, any 256-bit coordinates -> [n, 8] int64"""
-    import torch
-
     flat = [int(v) for pt in points for v in pt]
     if len(flat) != 2 * len(points):
         raise ValueError("a point is a pair (x, y)")
-    return torch.from_numpy(_words(flat).view(np.int64).reshape(len(points), 8)).to(_device_of(device))
-
-
-def _decode(tensor, words: int) -> List[int]:
-    a = tensor if isinstance(tensor, np.ndarray) else tensor.detach().cpu().numpy()
-    a = np.ascontiguousarray(a).view(np.uint64).reshape(-1, words)
-    raw = a.tobytes()
-    return [int.from_bytes(raw[8 * words * i:8 * words * (i + 1)], "little") for i in range(a.shape[0])]
+    return raw_tensor(flat, 4, device).reshape(len(points), 8)
 
 
 def decode_scalars(tensor) -> List[int]:
-    return _decode(tensor, 4)
+    return from_words(tensor.reshape(-1, 4))
 
 
 def decode_points(tensor) -> List[Point]:
-    flat = _decode(tensor.reshape(-1, 4), 4)
-    return [(flat[2 * i], flat[2 * i + 1]) for i in range(len(flat) // 2)]
+    return [tuple(pt) for pt in from_words(tensor.reshape(-1, 2, 4))]
 
 
 def _want(t, words: int, who: str, count: Optional[int] = None):
@@ -238,7 +214,7 @@ def hash_to_curve_host(msg: bytes, pk: Point) -> Tuple[Point, int]:
     msg = _msg(msg, "hash_to_curve_host")
     key, out, status = _words([pk[0], pk[1]]), np.zeros(8, dtype=np.uint64), C.c_uint32(0)
     _lib.check(_lib.load().zkhip_secp256k1_hash_to_curve(msg, len(msg), key.ctypes.data, out.ctypes.data, C.addressof(status)))
-    x, y = _decode(out, 4)
+    x, y = from_words(out.reshape(2, 4))
     return (x, y), status.value
 
 
@@ -250,7 +226,7 @@ def verify_host(msg: bytes, nullifier: Point, pk: Point, s: int, c: int) -> Tupl
     key, nul, sw, cw = _words([pk[0], pk[1]]), _words([nullifier[0], nullifier[1]]), _words([s]), _words([c])
     h, verdict = np.zeros(8, dtype=np.uint64), C.c_uint32(0)
     _lib.check(_lib.load().zkhip_plume_verify(msg, len(msg), key.ctypes.data, nul.ctypes.data, sw.ctypes.data, cw.ctypes.data, C.addressof(verdict), h.ctypes.data))
-    x, y = _decode(h, 4)
+    x, y = from_words(h.reshape(2, 4))
     return verdict.value, (x, y)
 
 
@@ -265,7 +241,8 @@ def sign_host(msg: bytes, sk: int, r: int) -> Tuple[Point, Point, int, int, int,
     s, c, status = np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64), C.c_uint32(0)
     _lib.check(_lib.load().zkhip_plume_sign(msg, len(msg), skw.ctypes.data, rw.ctypes.data, pk.ctypes.data, nul.ctypes.data, s.ctypes.data, c.ctypes.data,
                                             C.addressof(status), h.ctypes.data))
-    return tuple(_decode(pk, 4)), tuple(_decode(nul, 4)), _decode(s, 4)[0], _decode(c, 4)[0], status.value, tuple(_decode(h, 4))
+    pk, nul, h = (tuple(from_words(a.reshape(2, 4))) for a in (pk, nul, h))
+    return pk, nul, from_words(s), from_words(c), status.value, h
 
 
 # ---- the device calls ----------------------------------------------------------------------------------------------------------------------------
@@ -279,7 +256,7 @@ def lincomb_device(a, p, b, q, stream=None):
     a, b, q = _want(a, 4, "lincomb_device", n), _want(b, 4, "lincomb_device", n), _want(q, 8, "lincomb_device", n)
     out = torch.empty((n, 8), dtype=torch.int64, device=p.device)
     status = torch.empty((n,), dtype=torch.int32, device=p.device)
-    _lib.check(_lib.load().zkhip_secp256k1_lincomb_device(_ptr(a), _ptr(p), _ptr(b), _ptr(q), n, _ptr(out), _ptr(status), _stream_of(stream)))
+    _lib.check(_lib.load().zkhip_secp256k1_lincomb_device(_ptr(a), _ptr(p), _ptr(b), _ptr(q), n, _ptr(out), _ptr(status), stream_of(stream)))
     return out, status
 
 
@@ -291,7 +268,7 @@ def hash_to_curve_many_device(msg: bytes, pk, stream=None):
     n = pk.shape[0]
     out = torch.empty((n, 8), dtype=torch.int64, device=pk.device)
     status = torch.empty((n,), dtype=torch.int32, device=pk.device)
-    _lib.check(_lib.load().zkhip_secp256k1_hash_to_curve_device(msg, len(msg), _ptr(pk), n, _ptr(out), _ptr(status), _stream_of(stream)))
+    _lib.check(_lib.load().zkhip_secp256k1_hash_to_curve_device(msg, len(msg), _ptr(pk), n, _ptr(out), _ptr(status), stream_of(stream)))
     return out, status
 
 
@@ -330,7 +307,7 @@ def verify_many_device(msg: bytes, pk, nullifier, s, c, stream=None) -> Verdicts
     h = torch.empty((n, 8), dtype=torch.int64, device=pk.device)
     report = torch.empty((2,), dtype=torch.int64, device=pk.device)
     _lib.check(_lib.load().zkhip_plume_verify_device(msg, len(msg), _ptr(pk), _ptr(nullifier), _ptr(s), _ptr(c), n, _ptr(status), report.data_ptr(), _ptr(h),
-                                                     _stream_of(stream)))
+                                                     stream_of(stream)))
     return Verdicts(status, h, report)
 
 
@@ -354,5 +331,5 @@ def sign_many_device(msg: bytes, sk, r, stream=None) -> Signatures:
     s, c = (torch.empty((n, 4), dtype=torch.int64, device=sk.device) for _ in range(2))
     status = torch.empty((n,), dtype=torch.int32, device=sk.device)
     _lib.check(_lib.load().zkhip_plume_sign_device(msg, len(msg), _ptr(sk), _ptr(r), n, _ptr(pk), _ptr(nullifier), _ptr(s), _ptr(c), _ptr(status), _ptr(h),
-                                                   _stream_of(stream)))
+                                                   stream_of(stream)))
     return Signatures(pk, nullifier, s, c, status, h)

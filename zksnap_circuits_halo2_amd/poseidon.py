@@ -14,13 +14,10 @@ import numpy as np
 
 from . import _lib
 from .fields import fr_decode, fr_encode
+from .tensors import device_of, fr_empty, fr_ints, fr_words, stream_of
 
 MAX_WIDTH = _lib.ZKHIP_POSEIDON_MAX_WIDTH
 SUBTREE = _lib.ZKHIP_POSEIDON_SUBTREE      # elements of a level one workgroup of the tree kernel folds: sizes around it take different paths
-
-
-def _stream_of(stream) -> int:
-    return int(stream) if stream is not None else 0
 
 
 def constants() -> Tuple[List[List[int]], List[List[int]]]:
@@ -60,7 +57,7 @@ def hash_many_device(messages, out=None, stream=None):
     n, width = messages.shape[0], messages.shape[1]
     if out is None:
         out = torch.empty((n, 4), dtype=torch.int64, device=messages.device)
-    _lib.check(_lib.load().zkhip_poseidon_hash_many_device(messages.data_ptr(), n, width, out.data_ptr(), _stream_of(stream)))
+    _lib.check(_lib.load().zkhip_poseidon_hash_many_device(messages.data_ptr(), n, width, out.data_ptr(), stream_of(stream)))
     return out
 
 
@@ -92,7 +89,7 @@ def hash_points_device(points, layout: int, stream=None):
     points = points.contiguous()
     n = points.shape[0]
     out = torch.empty((n, 4), dtype=torch.int64, device=points.device)
-    _lib.check(_lib.load().zkhip_poseidon_hash_points_device(points.data_ptr() if n else None, n, int(layout), out.data_ptr() if n else None, _stream_of(stream)))
+    _lib.check(_lib.load().zkhip_poseidon_hash_points_device(points.data_ptr() if n else None, n, int(layout), out.data_ptr() if n else None, stream_of(stream)))
     return out
 
 
@@ -100,13 +97,9 @@ def nullifier_values(points, stream=None):
     """secp256k1 affine points -- a sequence of (x, y) integers, or an (n, 8) int64 device tensor (`plume.sign_many_device(..).nullifier`) -> the
     (n, 4) device tensor of the values the state-transition circuit inserts into the nullifier tree: the width-4 hash of every compressed
     point, one launch.  A tensor is packed on the device.  `IndexedMerkleTree.insert_batch` takes its host copy."""
-    import torch
-
     if _is_point_tensor(points):
         return hash_points_device(points, LAYOUT_NULLIFIER, stream)
-    packed = fr_encode([v for P in points for v in compress_nullifier(P)]).reshape(len(points), 4, 4)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    return hash_many_device(torch.from_numpy(packed.view(np.int64)).to(dev), stream=stream)
+    return hash_many_device(fr_words([v for P in points for v in compress_nullifier(P)]).reshape(len(points), 4, 4), stream=stream)
 
 
 def pack_member(point: Tuple[int, int]) -> List[int]:
@@ -124,13 +117,9 @@ def pack_member(point: Tuple[int, int]) -> List[int]:
 def member_leaves(points, stream=None):
     """secp256k1 public keys -- a sequence of (x, y) integers, or an (n, 8) int64 device tensor (`plume.sign_many_device(..).pk`) -> the (n, 4)
     device tensor of the members tree's leaves: the width-6 hash of every packed key, one launch.  A tensor is packed on the device."""
-    import torch
-
     if _is_point_tensor(points):
         return hash_points_device(points, LAYOUT_MEMBER, stream)
-    packed = fr_encode([v for P in points for v in pack_member(P)]).reshape(len(points), 6, 4)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    return hash_many_device(torch.from_numpy(packed.view(np.int64)).to(dev), stream=stream)
+    return hash_many_device(fr_words([v for P in points for v in pack_member(P)]).reshape(len(points), 6, 4), stream=stream)
 
 
 def merkle_device(leaves, stream=None):
@@ -142,7 +131,7 @@ def merkle_device(leaves, stream=None):
     leaves = leaves.contiguous()
     n = leaves.shape[0]
     nodes = torch.empty((max(n - 1, 0), 4), dtype=torch.int64, device=leaves.device)
-    _lib.check(_lib.load().zkhip_poseidon_merkle_device(leaves.data_ptr(), n, nodes.data_ptr() if n > 1 else None, _stream_of(stream)))
+    _lib.check(_lib.load().zkhip_poseidon_merkle_device(leaves.data_ptr(), n, nodes.data_ptr() if n > 1 else None, stream_of(stream)))
     return nodes
 
 
@@ -165,7 +154,7 @@ class MerkleTree:
 
     def get_root(self) -> int:
         top = self.nodes[-1:] if self.n > 1 else self.leaves[:1]
-        return fr_decode(top.cpu().numpy().view(np.uint64))[0]
+        return fr_ints(top)[0]
 
     def get_proof(self, index: int) -> Tuple[List[int], List[int]]:
         """(siblings from the leaf's level up, 1 where the node on the path is a left child else 0)"""
@@ -180,7 +169,7 @@ class MerkleTree:
             index //= 2
         if not rows:
             return [], []
-        return fr_decode(torch.stack(rows).cpu().numpy().view(np.uint64)), helper
+        return fr_ints(torch.stack(rows)), helper
 
     @staticmethod
     def verify_proof(leaf: int, index: int, root: int, proof: Sequence[int]) -> bool:
@@ -193,10 +182,6 @@ class MerkleTree:
 
 
 IMT_MAX_DEPTH = _lib.ZKHIP_IMT_MAX_DEPTH
-
-
-def _ints(t) -> List[int]:
-    return fr_decode(np.ascontiguousarray(t.cpu().numpy()).view(np.uint64).reshape(-1, 4))
 
 
 def _helper(index: int, depth: int) -> List[int]:
@@ -229,13 +214,10 @@ class ImtBatch:
     def __init__(self, n: int, depth: int, first_index: int, device):
         import torch
 
-        def fr(*shape):
-            return torch.empty(shape + (4,), dtype=torch.int64, device=device)
-
         self.n, self.depth, self.first_index = n, depth, first_index
-        self.roots, self.low_leaves, self.new_leaves = fr(n + 1), fr(n, 3), fr(n, 3)
+        self.roots, self.low_leaves, self.new_leaves = (fr_empty(*shape, device=device) for shape in ((n + 1,), (n, 3), (n, 3)))
         self.low_indices = torch.empty((n,), dtype=torch.int32, device=device)
-        self.low_proofs, self.new_proofs = fr(n, depth), fr(n, depth)
+        self.low_proofs, self.new_proofs = fr_empty(n, depth, device=device), fr_empty(n, depth, device=device)
 
     def _c(self):
         return _lib.ImtWitness(*(t.data_ptr() for t in (self.roots, self.low_leaves, self.new_leaves, self.low_indices, self.low_proofs, self.new_proofs)))
@@ -246,10 +228,10 @@ class ImtBatch:
         (val, next_val, next_idx)"""
         if not 0 <= i < self.n:
             raise IndexError("round: no such insertion")
-        old_root, new_root = _ints(self.roots[i:i + 2])
-        low_leaf, new_leaf = tuple(_ints(self.low_leaves[i])), tuple(_ints(self.new_leaves[i]))
+        old_root, new_root = fr_ints(self.roots[i:i + 2])
+        low_leaf, new_leaf = tuple(fr_ints(self.low_leaves[i])), tuple(fr_ints(self.new_leaves[i]))
         low, index = int(self.low_indices[i].item()), self.first_index + i
-        return (old_root, low_leaf, _ints(self.low_proofs[i]), _helper(low, self.depth), new_root, new_leaf, index, _ints(self.new_proofs[i]),
+        return (old_root, low_leaf, fr_ints(self.low_proofs[i]), _helper(low, self.depth), new_root, new_leaf, index, fr_ints(self.new_proofs[i]),
                 _helper(index, self.depth), 1 if new_leaf[1] == 0 else 0)
 
 
@@ -290,18 +272,16 @@ class IndexedMerkleTree:
     def insert_batch(self, values: Sequence[int], witness: bool = True, stream=None):
         """values in insertion order -- integers, or an (n, 4) uint64 array of Montgomery limbs -- -> an ImtBatch (None with witness=False: the
         tree alone is updated); no host wait"""
-        import torch
-
         if isinstance(values, np.ndarray) and values.dtype == np.uint64 and values.ndim == 2 and values.shape[1] == 4:
             w = np.ascontiguousarray(values)
         else:
             w = fr_encode([int(v) for v in values])
         first = self.used
-        out = ImtBatch(len(w), self.depth, first, torch.device("cuda", torch.cuda.current_device())) if witness else None
+        out = ImtBatch(len(w), self.depth, first, device_of()) if witness else None
         c = out._c() if out is not None else None
         bad = _lib.C.c_size_t(0)
         rc = _lib.load().zkhip_imt_insert(self._h, w.ctypes.data if len(w) else None, len(w), _lib.C.byref(c) if c is not None else None, _lib.C.byref(bad),
-                                          _stream_of(stream))
+                                          stream_of(stream))
         _check_index(rc, bad)
         if out is not None and len(w) == 0:
             out.roots[0] = self.export()[1][-1]
@@ -335,11 +315,6 @@ class IndexedMerkleTree:
 
     def export(self, stream=None):
         """(leaves (n, 4), inner nodes (n - 1, 4) in merkle_device's order, preimages (n, 3, 4)): device copies of the tree as it stands"""
-        import torch
-
-        dev = torch.device("cuda", torch.cuda.current_device())
-        leaves = torch.empty((self.n, 4), dtype=torch.int64, device=dev)
-        nodes = torch.empty((self.n - 1, 4), dtype=torch.int64, device=dev)
-        pre = torch.empty((self.n, 3, 4), dtype=torch.int64, device=dev)
-        _lib.check(_lib.load().zkhip_imt_export_device(self._h, leaves.data_ptr(), nodes.data_ptr(), pre.data_ptr(), _stream_of(stream)))
+        leaves, nodes, pre = fr_empty(self.n), fr_empty(self.n - 1), fr_empty(self.n, 3)
+        _lib.check(_lib.load().zkhip_imt_export_device(self._h, leaves.data_ptr(), nodes.data_ptr(), pre.data_ptr(), stream_of(stream)))
         return leaves, nodes, pre

@@ -15,6 +15,7 @@ multi-open -- the steps of [DEP] halo2-axiom plonk/prover.rs, each a method of `
 `lap` is a callable handed a name at every phase boundary (tools/prove_flow.py times the phases with it); None: no laps, so no synchronisation
 is added for timing (the phases that read a value back -- whether a product closes, the evaluations as integers -- still wait for it)."""
 import ctypes as C
+import functools
 import io
 import random
 from dataclasses import dataclass
@@ -22,7 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib, evaluation as E, fields as F, keygen as KG, multiopen as MO
+from . import _lib, evaluation as E, fields as F, keygen as KG, multiopen as MO, tensors as T
 from .domain import EvaluationDomain
 from .transcript import transcript_classes, vk_transcript_repr
 
@@ -30,7 +31,6 @@ R = F.R_MOD
 BLIND = 5
 DEV = torch.device("cuda", 0)
 
-TO_MONT = E.to_mont_program()
 _SIDE_STREAM = None
 
 
@@ -42,18 +42,10 @@ def side_stream():
     return _SIDE_STREAM
 
 
-def empty(*shape):
-    return torch.empty(shape + (4,), dtype=torch.int64, device=DEV)
-
-
-def rand_fr(m):                          # uniformly random canonical word patterns = random field elements
-    a = torch.randint(-(1 << 63), (1 << 63) - 1, (m, 4), dtype=torch.int64, device=DEV)
-    a[:, 3] = torch.randint(0, 1 << 61, (m,), dtype=torch.int64, device=DEV)
-    return a
-
-
-def words(vals):                         # python ints -> device tensor of Montgomery words
-    return torch.from_numpy(F.fr_encode(vals).view(np.int64)).to(DEV)
+empty = functools.partial(T.fr_empty, device=DEV)
+rand_fr = functools.partial(T.fr_random, device=DEV)
+words = functools.partial(T.fr_words, device=DEV)      # python ints -> device tensor of Montgomery words
+small_ints = T.fr_from_small                           # int64 tensor of 2^k small non-negative integers on DEV -> Montgomery words
 
 
 def run_prog(prog, cols, log_rows, out=None):
@@ -61,12 +53,6 @@ def run_prog(prog, cols, log_rows, out=None):
         out = empty(1 << log_rows)
     prog.run_device([c.data_ptr() for c in cols], log_rows, out.data_ptr())
     return out
-
-
-def small_ints(v, k):                    # int64 tensor of 2^k small non-negative integers -> Montgomery words
-    a = torch.zeros((v.shape[0], 4), dtype=torch.int64, device=DEV)
-    a[:, 0] = v
-    return run_prog(TO_MONT, [a], k)
 
 
 def affine(jac):
@@ -262,8 +248,8 @@ def identity_statuses(vk, k, plan, evals, challenges):
     if not evals:
         return np.zeros(0, dtype=np.int32)
     prog = identity_program_of(vk, plan, k)
-    d_evals = torch.from_numpy(F.fr_encode([e_ for row in evals for e_ in row]).view(np.int64).reshape(len(evals), len(plan), 4)).to(DEV)
-    d_challenges = torch.from_numpy(F.fr_encode([c_ for row in challenges for c_ in row]).view(np.int64).reshape(len(evals), 5, 4)).to(DEV)
+    d_evals = words([e_ for row in evals for e_ in row]).reshape(len(evals), len(plan), 4)
+    d_challenges = words([c_ for row in challenges for c_ in row]).reshape(len(evals), 5, 4)
     return E.verify_identity_device(prog, d_evals, d_challenges, k, (1 << k) - (vk.cs.blinding_factors + 1))[0]
 
 
@@ -555,7 +541,7 @@ class Prover:
         consts = [F.fr_encode([v_])[0] for v_ in (self.beta, self.gamma, E.DELTA, F.omega_for(k))]
         _lib.check(_lib.load().zkhip_permutation_products_device(vptr, sptr, npc, cs.chunk_len, k, u, *[c_.ctypes.data for c_ in consts], self.z_all.data_ptr(), None))
         self.z_sets = [self.z_all[si] for si in range(sets)]
-        self.permutation_closes = F.fr_decode(self.z_all[sets - 1, u:u + 1].cpu().numpy().view(np.uint64))[0] == 1
+        self.permutation_closes = T.fr_ints(self.z_all[sets - 1, u:u + 1])[0] == 1
         for z in self.z_sets:
             self.blinding.made(z, u + 1)
         self.blinding.step(self.z_sets, u + 1)
@@ -575,7 +561,7 @@ class Prover:
         """every lookup's product column in one call"""
         NL, u = self.w.lookups, self.u
         z_lk = E.lookup_products_device(self.w.lookup_inputs, [self.w.table] * NL, self.pa_all, self.ps_all, u, self.k, self.beta, self.gamma)
-        self.lookup_closes = all(v_ == 1 for v_ in F.fr_decode(z_lk[:, u].contiguous().cpu().numpy().view(np.uint64)))
+        self.lookup_closes = all(v_ == 1 for v_ in T.fr_ints(z_lk[:, u]))
         for j, tail in enumerate(self.lookup_tails):
             if tail is not None:
                 z_lk[j, u + 1:] = tail
@@ -593,7 +579,7 @@ class Prover:
             zl = run_prog(pn, [lk, table], k)
             den = run_prog(pd, [pa, ps], k)
             _lib.check(lib.zkhip_fr_grand_product_device(zl.data_ptr(), den.data_ptr(), n, zl.data_ptr(), None))
-            self.lookup_closes = self.lookup_closes and F.fr_decode(zl[u].cpu().numpy().view(np.uint64))[0] == 1
+            self.lookup_closes = self.lookup_closes and T.fr_ints(zl[u])[0] == 1
             b.made(zl, u + 1)
             b.step([zl], u + 1)
             self.lookup_cols += [zl, pa, ps]
@@ -743,7 +729,7 @@ class Prover:
         evals_plan = grouped[torch.tensor(where, dtype=torch.int64, device=DEV)].contiguous()
         self.lap("evaluations")
         self.ch.write_scalars(evals_plan)
-        for q_, e_ in zip(queries, F.fr_decode(evals_plan.cpu().numpy().view(np.uint64))):
+        for q_, e_ in zip(queries, T.fr_ints(evals_plan)):
             q_.eval = e_                                        # the multi-open's R_ij need them as integers
 
     def multiopen(self):
@@ -766,7 +752,7 @@ class Prover:
         com = {kind: c_.cpu().numpy().view(np.uint64).reshape(12).copy() for kind, c_ in self.commitments.items()}
         com.update(_key_commitments(self.dpk.vk))
         slot = {kind: i for i, kind in enumerate(self.polynomials()[0])}
-        at_x = F.fr_decode(self.evals.cpu().numpy().view(np.uint64))
+        at_x = T.fr_ints(self.evals)
         evals = [at_x[slot[(kind, idx)]] if r == 0 else q.eval for (kind, idx, r), q in zip(self.plan, self.queries)]
         return verifier_queries(self.plan, com, evals, self.x, self.k)
 

@@ -17,14 +17,11 @@ import numpy as np
 
 from . import _lib
 from .fields import R_MOD, fr_decode, fr_encode
+from .tensors import stream_of
 
 
 def _is_device(x) -> bool:
     return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
-
-
-def _stream_of(stream) -> int:
-    return int(stream) if stream is not None else 0
 
 
 class _Transcript:
@@ -84,7 +81,7 @@ class _Write(_Transcript):
         """Jacobian commitments, 12 limbs each: a torch tensor on the device (one launch, one copy, one wait on `stream`) or host limbs"""
         if _is_device(points):
             n = points.numel() // 12
-            _lib.check(self._lib.zkhip_transcript_write_points_device(self._t, points.data_ptr(), n, _stream_of(stream)))
+            _lib.check(self._lib.zkhip_transcript_write_points_device(self._t, points.data_ptr(), n, stream_of(stream)))
         else:
             w = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
             _lib.check(self._lib.zkhip_transcript_write_points(self._t, w.ctypes.data, len(w)))
@@ -92,7 +89,7 @@ class _Write(_Transcript):
     def write_scalars(self, scalars, stream=None) -> None:
         """a torch tensor of Montgomery Fr on the device (4 limbs each), or Python integers"""
         if _is_device(scalars):
-            _lib.check(self._lib.zkhip_transcript_write_scalars_device(self._t, scalars.data_ptr(), scalars.numel() // 4, _stream_of(stream)))
+            _lib.check(self._lib.zkhip_transcript_write_scalars_device(self._t, scalars.data_ptr(), scalars.numel() // 4, stream_of(stream)))
         else:
             w = fr_encode([int(s) for s in scalars])
             _lib.check(self._lib.zkhip_transcript_write_scalars(self._t, w.ctypes.data, len(w)))
@@ -112,7 +109,7 @@ class _Read(_Transcript):
             import torch
 
             out = torch.empty((n, 8), dtype=torch.int64, device="cuda")
-            _lib.check(self._lib.zkhip_transcript_read_points_device(self._t, n, out.data_ptr(), _stream_of(stream)))
+            _lib.check(self._lib.zkhip_transcript_read_points_device(self._t, n, out.data_ptr(), stream_of(stream)))
             return out
         out = np.zeros((n, 8), dtype=np.uint64)
         _lib.check(self._lib.zkhip_transcript_read_points(self._t, n, out.ctypes.data))

@@ -852,14 +852,28 @@ int zkhip_verify_identity_device(const zkhip_vm_program *prog, const void *d_eva
                                  uint32_t usable_rows, const uint64_t omega[4], size_t n_proofs, void *d_status, void *d_report, void *stream);
 
 /* ---- parity hooks for the field / curve layer (rows a1/a2 of SURVEY.md section 8) ------------------ */
-/* field: 0 = Fq, 1 = Fr.  op: 0 mul, 1 add, 2 sub, 3 square (b ignored).  Elementwise on n elements. */
+/* field: 0 = Fq, 1 = Fr.  op: 0 mul, 1 add, 2 sub, 3 square (b ignored).  Elementwise on n elements.
+ * The shapes the MSM / NTT kernels instantiate: 4 = mul and 5 = square as single-chain product columns (the asm blocks of mac_blocks.hpp; same
+ * values as 0 and 3), 6 = fe_mul_add in the compiler's shape and 7 = in the chain shape: out[i] = a[i] b[i] + a[i ^ 1] b[i ^ 1], two products
+ * under one Montgomery reduction (n must be even, else ZKHIP_EINVAL).
+ * op + 256, for op 4 .. 7: the same operation with every operand first replaced by the largest representative of its residue that the
+ * operation's documented limb / value bounds allow (csrc/fe_lift.hpp); the outputs are those of the plain op. */
 int zkhip_test_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);
 /* op: 0 = affine a[i] + affine b[i], 1 = 2 * a[i], 2 = a[i] + (-b[i]); with the quad-cooperative formulas of the reduction tail:
- * 3 = 2 a[i] + 2 b[i], 4 = 4 a[i].  out: n Jacobian points. */
+ * 3 = 2 a[i] + 2 b[i], 4 = 4 a[i]; through the bucket kernels' mixed addition xyzz_madd<true> (Y3 as one fused product pair), twice:
+ * 5 = a[i] + b[i], 6 = a[i] + (-b[i]).  5 + 256, 6 + 256: the same with the loaded coordinates lifted to the top of 64p and the accumulator,
+ * after the first addition, to the top of the stored-point invariant of csrc/ec.hpp.  out: n Jacobian points. */
 int zkhip_test_g1_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out_xyz, size_t n);
 
 /* G2 (Fq2 + twist curve arithmetic): op 0 = a[i] + b[i], 1 = 2 a[i], 2 = a[i] - b[i]; with the quad-cooperative formulas of the MSM's
  * latency-bound end: 3 = 2 a[i] + b[i], 4 = 4 a[i]; with their lazy forms chained as in the window fold: 5 = 4 a[i] + b[i], 6 = 16 a[i].
+ * The lazy Fq2 layer of the bucket kernels (csrc/ec2.hpp), coordinates unpacked without a multiplication as the accumulation does:
+ * 7 = a[i] + b[i] and 8 = a[i] - b[i] (the negated load) through xyzz2_madd_lazy<true> twice, then xyzz2_to_std; 9 = 2 a[i] + b[i] through
+ * xyzz2_add_lazy<true>; 10 = the same sum with both operands stored as 288-byte work points: even rows through xyzz2_add_lazy_mem<true>, odd rows
+ * through xyzz2_add_lazy_regmem<true>; 11 = xyzz2_add_lazy<true>(2 a[i], 2 a[i]), the doubling inside the general addition.
+ * op + 256, for op 5 .. 11: the same with every operand of the formula under test (for 5 and 6: the lazy quad point between the links of
+ * the chain) lifted to the top of its documented magnitude bound (csrc/fe_lift.hpp); the outputs are those of the plain op.
+ * No op checks that a point is on the curve: the formulas never use the curve constant.
  * a, b: n G2Affine points, out: n G2 Jacobian points */
 int zkhip_test_g2_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out_xyz, size_t n);
 

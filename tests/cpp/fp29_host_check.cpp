@@ -1,80 +1,11 @@
 // CPU unit test of the *device* arithmetic: csrc/fp29.hpp and csrc/ec.hpp are host-compilable, so the lazy radix-2^29
 // field and the XYZZ point formulas are exercised here (built with -fsanitize=address,undefined by tests/test_host_arith.py)
-// against an independent schoolbook big-integer implementation written in this file.  Besides equality it checks the
-// magnitude discipline the GPU kernels rely on: every stored coordinate is in N form with the documented value bound.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include "ec.hpp"
+// against an independent schoolbook big-integer implementation (bigint_ref.hpp, shared with ec2_host_check.cpp).  Besides equality
+// it checks the magnitude discipline the GPU kernels rely on: every stored coordinate is in N form with the documented value bound,
+// also when every operand enters at the top of its own bound (fe_lift.hpp).
+#include "bigint_ref.hpp"   // the big-integer reference, conversions, rnd() and CHECK
 #include "fe_inverse.hpp"
-
-using namespace zkhip;
-typedef unsigned __int128 u128;
-
-// ---- tiny big-int reference: 320-bit little-endian numbers in 5 x u64 ---------------------------------------------
-struct big { uint64_t w[5]; };
-static big big_zero() { big r; memset(&r, 0, sizeof(r)); return r; }
-static int big_cmp(const big& a, const big& b) { for (int i = 4; i >= 0; i--) if (a.w[i] != b.w[i]) return a.w[i] > b.w[i] ? 1 : -1; return 0; }
-static big big_sub(const big& a, const big& b) { big r; uint64_t br = 0; for (int i = 0; i < 5; i++) { u128 d = (u128)a.w[i] - b.w[i] - br; r.w[i] = (uint64_t)d; br = (uint64_t)(d >> 64) & 1; } return r; }
-static big big_add(const big& a, const big& b) { big r; uint64_t c = 0; for (int i = 0; i < 5; i++) { u128 s = (u128)a.w[i] + b.w[i] + c; r.w[i] = (uint64_t)s; c = (uint64_t)(s >> 64); } return r; }
-static big big_shl1(const big& a) { big r; uint64_t c = 0; for (int i = 0; i < 5; i++) { r.w[i] = (a.w[i] << 1) | c; c = a.w[i] >> 63; } return r; }
-static big big_mod(big a, const big& p) { while (big_cmp(a, p) >= 0) a = big_sub(a, p); return a; }
-// a * b mod p for a, b < p < 2^255, odd p: 4 x 64-bit Montgomery (CIOS) with R = 2^256, then one more Montgomery multiply by
-// R^2 to leave the Montgomery domain -- a different radix and algorithm from the code under test.
-static uint64_t neg_inv64(uint64_t p0) { uint64_t x = 1; for (int i = 0; i < 6; i++) x *= 2 - p0 * x; return (uint64_t)0 - x; }
-static big mont4(const big& a, const big& b, const big& p, uint64_t inv) {
-  uint64_t t[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < 4; i++) {
-    uint64_t carry = 0;
-    for (int j = 0; j < 4; j++) { u128 s = (u128)a.w[j] * b.w[i] + t[j] + carry; t[j] = (uint64_t)s; carry = (uint64_t)(s >> 64); }
-    u128 s = (u128)t[4] + carry; t[4] = (uint64_t)s; t[5] = (uint64_t)(s >> 64);
-    const uint64_t m = t[0] * inv;
-    s = (u128)m * p.w[0] + t[0]; carry = (uint64_t)(s >> 64);
-    for (int j = 1; j < 4; j++) { s = (u128)m * p.w[j] + t[j] + carry; t[j - 1] = (uint64_t)s; carry = (uint64_t)(s >> 64); }
-    s = (u128)t[4] + carry; t[3] = (uint64_t)s; t[4] = t[5] + (uint64_t)(s >> 64);
-  }
-  big r = big_zero();
-  for (int i = 0; i < 5; i++) r.w[i] = t[i];
-  return big_mod(r, p);
-}
-static big r2_for(const big& p) {   // 2^512 mod p by repeated doubling (once per modulus)
-  big r = big_zero(); r.w[0] = 1;
-  for (int i = 0; i < 512; i++) r = big_mod(big_shl1(r), p);
-  return r;
-}
-static big mulmod(const big& a, const big& b, const big& p) {
-  static big cached_p = big_zero(), cached_r2 = big_zero();
-  static uint64_t cached_inv = 0;
-  if (big_cmp(cached_p, p) != 0) { cached_p = p; cached_r2 = r2_for(p); cached_inv = neg_inv64(p.w[0]); }
-  return mont4(mont4(a, b, p, cached_inv), cached_r2, p, cached_inv);   // (ab/R) * R^2 / R = ab
-}
-static big addmod(const big& a, const big& b, const big& p) { return big_mod(big_add(a, b), p); }
-static big submod(const big& a, const big& b, const big& p) { return big_cmp(a, b) >= 0 ? big_sub(a, b) : big_sub(big_add(a, p), b); }
-static big powmod(big a, const big& e, const big& p) { big r = big_zero(); r.w[0] = 1; for (int i = 0; i < 256; i++) { if ((e.w[i >> 6] >> (i & 63)) & 1) r = mulmod(r, a, p); a = mulmod(a, a, p); } return r; }
-static big invmod(const big& a, const big& p) { big e = p; big two = big_zero(); two.w[0] = 2; e = big_sub(e, two); return powmod(a, e, p); }
-
-template <class P> static big modulus() { big p = big_zero(); for (int i = 0; i < NL; i++) { int bit = LB * i; p.w[bit >> 6] |= (uint64_t)P::P[i] << (bit & 63); if ((bit & 63) + LB > 64 && (bit >> 6) + 1 < 5) p.w[(bit >> 6) + 1] |= (uint64_t)P::P[i] >> (64 - (bit & 63)); } return p; }
-static big fe_value(const fe& a) {   // integer value of a (possibly unnormalised) limb vector
-  big r = big_zero();
-  for (int i = 0; i < NL; i++) { big t = big_zero(); int bit = LB * i; t.w[bit >> 6] = (uint64_t)a.l[i] << (bit & 63); if ((bit & 63) + 32 > 64) t.w[(bit >> 6) + 1] = (uint64_t)a.l[i] >> (64 - (bit & 63)); r = big_add(r, t); }
-  return r;
-}
-static fe fe_from_big(const big& v) { fe r; for (int i = 0; i < NL; i++) { int bit = LB * i; uint64_t x = v.w[bit >> 6] >> (bit & 63); if ((bit & 63) + LB > 64) x |= v.w[(bit >> 6) + 1] << (64 - (bit & 63)); r.l[i] = (uint32_t)x & LMASK; } return r; }
-
-static uint64_t rng_state = 0x5A4B534E41500009ULL;
-static uint64_t rnd() { rng_state += 0x9E3779B97F4A7C15ULL; uint64_t z = rng_state; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL; return z ^ (z >> 31); }
-static big rnd_below(const big& p) { big r; for (int i = 0; i < 4; i++) r.w[i] = rnd(); r.w[4] = 0; r.w[3] &= (1ULL << 62) - 1; return big_mod(r, p); }
-
-static int fails = 0;
-#define CHECK(c, msg) do { if (!(c)) { if (fails < 20) printf("FAIL %s (line %d)\n", msg, __LINE__); fails++; } } while (0)
-
-template <class P> static big R261() { big r = big_zero(); r.w[4] = 1ULL << (261 - 256); return big_mod(r, modulus<P>()); }
-template <class P> static big to_int(const fe& a, const big& rinv) { return mulmod(big_mod(fe_value(a), modulus<P>()), rinv, modulus<P>()); }   // Montgomery-261 -> plain
-template <class P> static fe to_fe(const big& x) { return fe_from_big(mulmod(x, R261<P>(), modulus<P>())); }                                  // plain -> Montgomery-261, canonical
-
-static bool is_N(const fe& a) { for (int i = 0; i < NL - 1; i++) if (a.l[i] > LMASK) return false; return true; }
-static bool below(const fe& a, unsigned k, const big& p) { big kp = big_zero(); for (unsigned i = 0; i < k; i++) kp = big_add(kp, p); return big_cmp(fe_value(a), kp) < 0; }
+#include "fe_lift.hpp"
 
 template <class P> static void field_tests(const char* name) {
   const big p = modulus<P>(), rinv = invmod(R261<P>(), p);
@@ -220,10 +151,82 @@ static void curve_tests() {
   }
 }
 
+// ---- the shapes the MSM kernels instantiate, at the top of their documented operand bounds (fe_lift.hpp) -----------------------------
+// fe_mul_add<P, CHAIN> against a b + c d, and fe_mul / fe_sqr at their limb limits.  (On the host both CHAIN values run the portable
+// column code; the device's asm-block shape is reached through zkhip_test_field_op ops 4-7.)
+template <class P, bool CHAIN> static void mul_add_tests(const char* name) {
+  const big p = modulus<P>(), rinv = invmod(R261<P>(), p), one_b = big_small(1), pm1 = big_sub(p, one_b);
+  const big edge[3] = {big_zero(), one_b, pm1};
+  for (int it = 0; it < 1500; it++) {
+    big x = rnd_below(p), y = rnd_below(p), z = rnd_below(p), w = rnd_below(p);
+    if (it < 81) { x = edge[it % 3]; y = edge[(it / 3) % 3]; z = edge[(it / 9) % 3]; w = edge[(it / 27) % 3]; }
+    if (it >= 81 && it < 120) { z = submod(big_zero(), x, p); w = y; }                      // c = -a, d = b: the sum is = 0 mod p
+    if (it >= 120 && it < 130) { x = edge[it % 3]; z = submod(big_zero(), x, p); w = y; }
+    const big want = addmod(mulmod(x, y, p), mulmod(z, w, p), p);
+    const fe a = to_fe<P>(x), b = to_fe<P>(y), c = to_fe<P>(z), d = to_fe<P>(w);
+    const fe r = fe_mul_add<P, CHAIN>(a, b, c, d);
+    CHECK(mulout_ok(r, a, b, &c, &d, p) && big_cmp(to_int<P>(r, rinv), want) == 0, name);
+    if (it >= 81 && it < 130) CHECK(fe_mulout_is_zero<P>(r) && big_cmp(want, big_zero()) == 0, name);
+    // the limit ec.hpp uses: a, c in N form; b with limbs < 3 * 2^29 (T = Q + 10p - X3); d with limbs < 2^30 (6p - Y1)
+    const fe aN = fe_lift<P>(a, 2), cN = fe_lift<P>(c, 2), bL = fe_lift_lazy<P>(b, 3), dL = fe_lift_lazy<P>(d, 2);
+    CHECK(is_N(aN) && is_N(cN) && !below(aN, 1, p) && below(aN, 2, p) && big_cmp(to_int<P>(bL, rinv), y) == 0 && big_cmp(to_int<P>(dL, rinv), w) == 0, name);
+    const fe rl = fe_mul_add<P, CHAIN>(aN, bL, cN, dL);
+    CHECK(mulout_ok(rl, aN, bL, &cN, &dL, p) && below(rl, 2, p) && big_cmp(to_int<P>(rl, rinv), want) == 0, name);
+    if (it >= 81 && it < 130) CHECK(fe_mulout_is_zero<P>(rl), name);
+    // Y3 of xyzz_madd_nz<true> with its own operands at their largest: R < 8p (N), T = Q + 10p - X3 < 12p with X3 small (limb-wise, not
+    // normalised), PPP (N, < 2p here: more than its 1.14p), 6p - Y1 with Y1 small: the result must stay below the 1.7p of ec.hpp's comment
+    const fe R8 = fe_lift<P>(a, 8), T12 = fe_sub_red(fe_lift<P>(b, 2), fe_canon<P>(d), P::P10_S1), negY = fe_neg_red(d, P::P6_S1);
+    const fe y3 = fe_mul_add<P, CHAIN>(R8, T12, cN, negY);
+    CHECK(mulout_ok(y3, R8, T12, &cN, &negY, p) && below_frac(y3, 170, 100, p), name);
+    CHECK(big_cmp(to_int<P>(y3, rinv), submod(mulmod(x, submod(y, w, p), p), mulmod(z, w, p), p)) == 0, name);
+    // fe_mul: N x limbs < 2^31.5 (5 * 2^29 = 2^31.3); fe_sqr: limbs < 2^30.3 (2 * 2^29)
+    const fe b5 = fe_lift_lazy<P>(b, 5), a2 = fe_lift_lazy<P>(a, 2);
+    const fe m = fe_mul<P, CHAIN>(aN, b5), s = fe_sqr<P, CHAIN>(a2);
+    CHECK(mulout_ok(m, aN, b5, nullptr, nullptr, p) && below(m, 2, p) && big_cmp(to_int<P>(m, rinv), mulmod(x, y, p)) == 0, name);
+    CHECK(mulout_ok(s, a2, a2, nullptr, nullptr, p) && below(s, 2, p) && big_cmp(to_int<P>(s, rinv), mulmod(x, x, p)) == 0, name);
+  }
+}
+
+// the chain of curve_tests through xyzz_madd<true> (what the bucket kernels instantiate: Y3 = R T + PPP (6p - Y1) under one reduction),
+// unlifted and with every operand lifted to the top of its bound between the links: X 9p, Y 5p, ZZ / ZZZ 2p, x2 / y2 64p
+static void chain_shape_curve_tests(bool lifted) {
+  const big q = modulus<Fq>(), rinv = invmod(R261<Fq>(), q);
+  apt G; G.x = big_small(1); G.y = big_small(2); G.inf = false;
+  std::vector<apt> pts;
+  apt cur = G;
+  for (int i = 0; i < 40; i++) { pts.push_back(cur); cur = a_add(cur, (i % 3 == 0) ? cur : G, q); }
+  auto lazy_in = [&](const big& v) { fe t = to_fe<Fq>(v); fe k; for (int i = 0; i < NL; i++) k.l[i] = Fq::P32_S1[i]; return fe_norm(fe_add(t, k)); };
+  for (int it = 0; it < 600; it++) {
+    xyzz acc = xyzz_identity();
+    apt ref{big_zero(), big_zero(), true};
+    int len = 1 + (int)(rnd() % 12);
+    for (int j = 0; j < len; j++) {
+      apt P = pts[rnd() % pts.size()];
+      uint64_t mode = rnd() % 8;
+      if (mode == 0 && !ref.inf) P = ref;                                   // acc += acc  -> doubling inside madd
+      if (mode == 1 && !ref.inf) { P = ref; P.y = submod(big_zero(), P.y, q); }   // acc += -acc -> identity
+      fe x2 = (j & 1) ? lazy_in(P.x) : to_fe<Fq>(P.x), y2 = (j & 1) ? lazy_in(P.y) : to_fe<Fq>(P.y);
+      if (lifted) { x2 = fe_lift<Fq>(x2, 64); y2 = fe_lift<Fq>(y2, 64); }
+      if (mode == 2) { y2 = fe_neg_red(to_fe<Fq>(P.y), Fq::P64_S1); P.y = submod(big_zero(), P.y, q); }   // negated load: 64p - y, already at the top
+      if (lifted) { acc = xyzz_lift(acc); CHECK(xyzz_is_identity(acc) || (stored_ok(acc, q) && !below(acc.X, 8, q) && !below(acc.Y, 4, q) && !below(acc.ZZ, 1, q)), "xyzz_lift"); }
+      xyzz_madd<true>(acc, x2, y2);
+      ref = a_add(ref, P, q);
+      CHECK(xyzz_is_identity(acc) || stored_ok(acc, q), lifted ? "madd<true> stored-point invariant (lifted)" : "madd<true> stored-point invariant");
+      CHECK(same(xyzz_to_affine(acc, q, rinv), ref), lifted ? "madd<true> value (lifted)" : "madd<true> value");
+    }
+  }
+}
+
 int main() {
   field_tests<FqParams>("Fq");
   field_tests<FrParams>("Fr");
   curve_tests();
+  mul_add_tests<FqParams, false>("Fq fe_mul_add<false>");
+  mul_add_tests<FqParams, true>("Fq fe_mul_add<true>");
+  mul_add_tests<FrParams, false>("Fr fe_mul_add<false>");
+  mul_add_tests<FrParams, true>("Fr fe_mul_add<true>");
+  chain_shape_curve_tests(false);
+  chain_shape_curve_tests(true);
   printf(fails ? "FAILED: %d checks\n" : "fp29/ec host check OK\n", fails);
   return fails ? 1 : 0;
 }

@@ -3,6 +3,11 @@
 * tests/cpp/fp29_host_check.cpp includes csrc/fp29.hpp + csrc/ec.hpp (the code the kernels run) and checks the lazy radix-2^29
   field, the external-format conversions and the XYZZ formulas -- values *and* the documented magnitude bounds -- against an
   independent 4x64 Montgomery big-integer implementation.
+  It also runs the shapes the MSM kernels instantiate (fe_mul_add, xyzz_madd<true>) with every operand lifted to the top of its documented
+  bound (csrc/fe_lift.hpp).
+* tests/cpp/ec2_host_check.cpp does the same for csrc/ec2.hpp: Fq2 and the G2 formulas, the standard-form layer and the lazy layer of the
+  bucket kernels, unlifted and lifted, with an equal-x table over the Fq2 shapes whose square has a vanishing component.  Both share the
+  big-integer reference of tests/cpp/bigint_ref.hpp.
 * tests/cpp/oracle_sanitize.c drives oracle/cpu_ref.c (threads, both FFT paths, row a7).
 GPU AddressSanitizer is not available on this pool, so this is where the sanitizers run."""
 import os
@@ -24,6 +29,15 @@ def test_device_field_and_curve_arithmetic_on_host_with_sanitizers(tmp_path):
     assert build.returncode == 0, build.stdout
     run = _run([str(exe)])
     assert run.returncode == 0 and "host check OK" in run.stdout, run.stdout
+
+
+def test_device_g2_arithmetic_on_host_with_sanitizers(tmp_path):
+    exe = tmp_path / "ec2_host_check"
+    build = _run(["g++", "-std=c++17", *SAN, "-I", os.path.join(ROOT, "zksnap_circuits_halo2_amd", "csrc"),
+                  os.path.join(ROOT, "tests", "cpp", "ec2_host_check.cpp"), "-o", str(exe)])
+    assert build.returncode == 0, build.stdout
+    run = _run([str(exe)])
+    assert run.returncode == 0 and "ec2 host check OK" in run.stdout, run.stdout
 
 
 def test_c_oracle_with_sanitizers(tmp_path):

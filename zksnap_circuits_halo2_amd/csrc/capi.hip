@@ -3042,7 +3042,9 @@ int zkhip_g1_decompress(const uint8_t* in32, size_t n, uint64_t* points, int fla
 // ---- parity hooks ----------------------------------------------------------------------------------
 int zkhip_test_field_op(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
   ZK_API_RANGE();
-  if (field < 0 || field > 1 || op < 0 || op > 3 || (n && (!a || !b || !out))) { set_error("test_field_op: bad argument"); return ZKHIP_EINVAL; }
+  const bool field_op_ok = (op >= 0 && op <= 7) || (op >= 256 + 4 && op <= 256 + 7);
+  if (field < 0 || field > 1 || !field_op_ok || (n && (!a || !b || !out))) { set_error("test_field_op: bad argument"); return ZKHIP_EINVAL; }
+  if ((op & 255) >= 6 && (n & 1)) { set_error("test_field_op: ops 6 and 7 pair element i with i ^ 1: n must be even"); return ZKHIP_EINVAL; }
   if (n == 0) return ZKHIP_OK;
   lane_hold H;
   if (H.rc != ZKHIP_OK) return H.rc;
@@ -3059,7 +3061,7 @@ int zkhip_test_field_op(int field, int op, const uint64_t* a, const uint64_t* b,
 
 int zkhip_test_g1_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out_xyz, size_t n) {
   ZK_API_RANGE();
-  if (op < 0 || op > 4 || (n && (!a || !b || !out_xyz))) { set_error("test_g1_op: bad argument"); return ZKHIP_EINVAL; }
+  if (!((op >= 0 && op <= 6) || op == 256 + 5 || op == 256 + 6) || (n && (!a || !b || !out_xyz))) { set_error("test_g1_op: bad argument"); return ZKHIP_EINVAL; }
   if (n == 0) return ZKHIP_OK;
   lane_hold H;
   if (H.rc != ZKHIP_OK) return H.rc;
@@ -3076,17 +3078,20 @@ int zkhip_test_g1_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out
 
 int zkhip_test_g2_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out_xyz, size_t n) {
   ZK_API_RANGE();
-  if (op < 0 || op > 6 || (n && (!a || !b || !out_xyz))) { set_error("test_g2_op: bad argument"); return ZKHIP_EINVAL; }
+  if (!((op >= 0 && op <= 11) || (op >= 256 + 5 && op <= 256 + 11)) || (n && (!a || !b || !out_xyz))) { set_error("test_g2_op: bad argument"); return ZKHIP_EINVAL; }
   if (n == 0) return ZKHIP_OK;
   lane_hold H;
   if (H.rc != ZKHIP_OK) return H.rc;
   int rc;
   hipStream_t s = H.s;
-  if ((rc = H.sc->poly.reserve(n * (128 + 128 + 192))) != ZKHIP_OK) return rc;
+  const bool formula_op = op >= 7;                                   // selftest.hip; op 10 keeps its two operands as work points (2 x 288 bytes a row)
+  if ((rc = H.sc->poly.reserve(n * (128 + 128 + 192 + ((op & 255) == 10 ? 2 * 288 : 0)))) != ZKHIP_OK) return rc;
   char* d = (char*)H.sc->poly.p;
   HIPCHK(hipMemcpyAsync(d, a, n * 128, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(d + n * 128, b, n * 128, hipMemcpyHostToDevice, s));
-  if ((rc = test_g2_op(op, (uint32_t*)d, (uint32_t*)(d + n * 128), (uint32_t*)(d + n * 256), n, s)) != ZKHIP_OK) return rc;
+  if (formula_op) rc = test_g2_formula_op(op, (uint32_t*)d, (uint32_t*)(d + n * 128), (uint32_t*)(d + n * 256), (uint32_t*)(d + n * 448), n, s);
+  else rc = test_g2_op(op, (uint32_t*)d, (uint32_t*)(d + n * 128), (uint32_t*)(d + n * 256), n, s);
+  if (rc != ZKHIP_OK) return rc;
   HIPCHK(hipMemcpyAsync(out_xyz, d + n * 256, n * 192, hipMemcpyDeviceToHost, s));
   return H.finish();
 }

@@ -61,6 +61,7 @@ int msm_build_tasks(const uint32_t* d_scalars, size_t n, size_t batch, size_t sc
 size_t msm_g2_workspace_bytes(size_t n);
 int msm_g2_device(const uint32_t* d_scalars, const uint32_t* d_bases, size_t n, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream);
 int test_g2_op(int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);
+int test_g2_formula_op(int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, uint32_t* d_work, size_t n, hipStream_t stream);   // selftest.hip: ops 7 .. 11 and 256 + 5 .. 256 + 11
 // pairing.hip: n <= ZKHIP_MAX_PAIRS; d_ok one uint32.  which: bit 0 the quad policy (d_out), bit 1 the single-lane policy (d_out + 96 words)
 int pairing_check_device(const uint32_t* d_g1, const uint32_t* d_g2, size_t n, uint32_t* d_ok, hipStream_t stream);
 int test_fq12_op(int op, int which, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, hipStream_t stream);

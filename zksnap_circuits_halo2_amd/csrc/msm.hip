@@ -461,6 +461,7 @@ __global__ void __launch_bounds__(1024) k_coarse_sorted(const int32_t* __restric
   __shared__ uint32_t refs[COARSE_CHUNK];
   __shared__ uint16_t fines[COARSE_CHUNK];
   __shared__ uint32_t mask[COARSE_CHUNK / 32], wpre[COARSE_CHUNK / 32];      // run-start bits of the sorted chunk and their word prefixes
+  __shared__ uint32_t total_s;                                                // entries of the chunk (digits that are not zero)
   const int win = blockIdx.y;
   // gstride = 0: one bucket set shared by all windows (prepared tables), group = bucket >> 12.  gstride = B >> 12: a bucket set per window
   // (general path), group = window * gstride + (bucket >> 12) -- the groups of a window are contiguous, as its buckets are
@@ -478,10 +479,11 @@ __global__ void __launch_bounds__(1024) k_coarse_sorted(const int32_t* __restric
   const uint32_t vi = v_lo + threadIdx.x, vj = vi + 1024u;
   const uint4 q0 = vi < v_hi ? dv[vi] : make_uint4(0, 0, 0, 0), q1 = vj < v_hi ? dv[vj] : make_uint4(0, 0, 0, 0);
   const int32_t d8[8] = {(int32_t)q0.x, (int32_t)q0.y, (int32_t)q0.z, (int32_t)q0.w, (int32_t)q1.x, (int32_t)q1.y, (int32_t)q1.z, (int32_t)q1.w};
+  uint32_t rk[8];                      // rank of the entry inside its group, as the histogram's atomic returns it: the placement needs no second one
 #pragma unroll
   for (int k = 0; k < 8; k++) {
     const int32_t d = d8[k];
-    if (d != 0) atomicAdd(&cur[gbase + (((uint32_t)(d < 0 ? -d : d) - 1) >> FINE_BITS)], 1u);
+    rk[k] = d != 0 ? atomicAdd(&cur[gbase + (((uint32_t)(d < 0 ? -d : d) - 1) >> FINE_BITS)], 1u) : 0u;
   }
   __syncthreads();
   if (threadIdx.x < 64) {            // one wavefront: exclusive scan of the MAX_GROUPS = 128 counts (two per lane), then the reservations
@@ -493,6 +495,7 @@ __global__ void __launch_bounds__(1024) k_coarse_sorted(const int32_t* __restric
       if ((int)threadIdx.x >= off) x += y;
     }
     const uint32_t l0 = x - s, l1 = l0 + c0;
+    if (threadIdx.x == 63) total_s = x;
     // The reservation cursors are per (window, group): a group's staging region is laid out window after window (k_group_offsets).  With one
     // cursor per group every workgroup of every window hit the same 128 words -- 6656 workgroups at 2^22 -- and the kernel's time WAS those
     // atomics: it scaled with the number of workgroups, not with the bytes (0.27 / 0.50 / 0.97 ms at 2^22 with 8 Ki / 4 Ki / 2 Ki-digit chunks:
@@ -535,13 +538,13 @@ __global__ void __launch_bounds__(1024) k_coarse_sorted(const int32_t* __restric
     const int32_t d = d8[k];
     if (d != 0) {
       const uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1;
-      const uint32_t pos = atomicAdd(&cur[gbase + (b >> FINE_BITS)], 1u);
+      const uint32_t pos = cur[gbase + (b >> FINE_BITS)] + rk[k];             // cur[g] = start of group g's run
       refs[pos] = (rbase + (k < 4 ? vi : vj) * 4 + (k & 3)) | (d < 0 ? 0x80000000u : 0u);
       fines[pos] = (uint16_t)(b & ((1u << FINE_BITS) - 1));
     }
   }
   __syncthreads();
-  const uint32_t total = cur[MAX_GROUPS - 1];                  // cur[g] = end of group g's run
+  const uint32_t total = total_s;
   for (uint32_t i = threadIdx.x; i < total; i += blockDim.x) {
     const uint32_t r = wpre[i >> 5] + (uint32_t)__popc(mask[i >> 5] & ((2u << (i & 31)) - 1u)) - 1u;      // rank of the run position i lies in
     const uint32_t pos = delta[r] + i;
@@ -550,7 +553,9 @@ __global__ void __launch_bounds__(1024) k_coarse_sorted(const int32_t* __restric
   }
 }
 
-constexpr uint32_t SORT_CHUNK = 28672;   // entries per workgroup of the sorted fine scatter: 112 KiB of references in LDS
+constexpr uint32_t SORT_CHUNK = 28672;   // entries per workgroup of the sorted fine scatter: 112 KiB of references in LDS, one workgroup per CU.
+                                         // Half chunks (14336, two workgroups per CU) lose at every size: k_fine_sorted 76 -> 99 us at 2^20, the scatter
+                                         // phase 0.251 -> 0.300 ms at 2^22 (profiles/r26_wide_sort_bookkeeping.txt): no crossover
 
 // goff[g] = start of group g in the staging array (exclusive scan of the group counts), gcursor = copy; cstart[g] = index of the
 // group's first SORT_CHUNK-sized chunk in the numbering of k_fine_sorted's workgroups
@@ -588,11 +593,12 @@ __global__ void __launch_bounds__(64) k_group_offsets(const uint32_t* __restrict
 // 4-byte write, and PMC shows what that costs: 8.7 bytes reach memory per byte of payload (32-byte sectors).  Here a workgroup
 // owns SORT_CHUNK staged entries of one group of 2^FINE_BITS buckets, counting-sorts their references by bucket inside LDS, and
 // writes bucket runs: neighbouring lanes store neighbouring words (~7 entries per bucket and chunk).
-//   LDS: cur[FB] (histogram -> run starts -> run ends) | delta[FB] (global slot of a run minus its LDS position) | refs[SORT_CHUNK]
+//   LDS: cur[FB] (histogram -> run starts) | delta[FB] (global slot of a run minus its LDS position) | refs[SORT_CHUNK]
 //        | run-start bit mask and its word prefixes (SORT_CHUNK / 16 words)
 // (A second shape that kept every entry's 16-bit bucket id in LDS -- 20 Ki entries per chunk -- served the smallest wide size until the
 // rank structure below made the way out three reads for any chunk: 2^20 scatter 0.110 -> 0.101 ms, and the variant was removed.)
-// LDS histogram of the fine bucket ids of staged entries [start, end).  The sort kernels spent 77 - 84 % of their cycles parked
+// LDS histogram of the fine bucket ids of staged entries [start, end) (k_fine_count; k_fine_sorted keeps a lane's entries in registers
+// instead).  The sort kernels spent 77 - 84 % of their cycles parked
 // (profiles/r02_rocprofv3_pmc_sq_issue.txt): with one load per lane and iteration, each feeding an LDS atomic, every trip exposes a full
 // memory latency.  Four independent loads are issued before the first atomic.
 constexpr int FINE_BATCH = 7;      // measured (2 / 4 / 7 / 14 / 28 loads in flight per lane): see (profiles/r03_msm_sort_pipelining_ab.txt)
@@ -612,106 +618,92 @@ __global__ void __launch_bounds__(1024) k_fine_sorted(const uint16_t* __restrict
   extern __shared__ uint32_t hist[];
   constexpr uint32_t FB = 1u << FINE_BITS;
   constexpr uint32_t CHUNK = SORT_CHUNK;
+  constexpr int PER_LANE = CHUNK / 1024;                      // 28 entries of the chunk per lane
   static_assert(FB == 4096, "one thread owns four buckets in the scan");
-  __shared__ uint32_t wsum[16];
+  static_assert(CHUNK % 1024 == 0 && CHUNK / 32 <= 1024, "a lane owns CHUNK / 1024 entries; one mask word per thread");
+  __shared__ uint32_t wsum[3][16];                            // wave totals of the three scans (counts, non-empty buckets, run-start bits)
   uint32_t* cur = hist;
   uint32_t* delta = hist + FB;
   uint32_t* refs = hist + 2 * FB;
+  uint32_t* mask = refs + CHUNK;                              // CHUNK / 32 words
+  uint32_t* wpre = mask + CHUNK / 32;                         // CHUNK / 32 words
   const uint32_t w = blockIdx.x;
   if (w >= cstart[G]) return;
   uint32_t glo = 0, ghi = (uint32_t)G;                      // group of chunk w: last g with cstart[g] <= w
   while (ghi - glo > 1) { const uint32_t mid = (glo + ghi) >> 1; if (cstart[mid] <= w) glo = mid; else ghi = mid; }
   const uint32_t g = glo;
   const uint32_t start = goff[g] + (w - cstart[g]) * CHUNK, end = min(goff[g + 1], start + CHUNK), cnt_n = end - start;
+  // The chunk is read ONCE: a lane's 28 (fine id, reference) pairs stay in registers from the histogram to the placement (1024 threads
+  // leave 128 VGPRs), and all of its loads are issued before the first LDS atomic waits for one of them.
+  uint32_t f[PER_LANE], r[PER_LANE];
+#pragma unroll
+  for (int k = 0; k < PER_LANE; k++) { const uint32_t q = start + threadIdx.x + k * 1024u; f[k] = q < end ? stage_fine[q] : 0xffffffffu; }
+#pragma unroll
+  for (int k = 0; k < PER_LANE; k++) { const uint32_t q = start + threadIdx.x + k * 1024u; r[k] = q < end ? stage_ref[q] : 0u; }
   for (uint32_t b = threadIdx.x; b < FB; b += blockDim.x) cur[b] = 0;
+  if (threadIdx.x < CHUNK / 32) mask[threadIdx.x] = 0;
   __syncthreads();
-  fine_histogram(stage_fine, start, end, cur);
+  // The histogram's atomic returns the entry's rank inside its bucket; kept above the 12-bit fine id (rank < CHUNK < 2^15), it makes the
+  // placement below a read of the run start and a write, where a second returning atomic per entry stood.
+  static_assert(CHUNK <= (1u << 15) && FINE_BITS + 15 < 32, "fine id and rank share a register, and 0xffffffff stays the mark of no entry");
+#pragma unroll
+  for (int k = 0; k < PER_LANE; k++) if (f[k] != 0xffffffffu) f[k] |= atomicAdd(&cur[f[k]], 1u) << FINE_BITS;
   __syncthreads();
   // exclusive scan over the 4096 counts: thread t owns buckets 4t .. 4t + 3
   uint32_t c[4], l[4], s = 0;
 #pragma unroll
   for (int k = 0; k < 4; k++) { c[k] = cur[4 * threadIdx.x + k]; s += c[k]; }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t x = s;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  uint32_t before = 0;
-#pragma unroll
-  for (int i = 0; i < 16; i++) if (i < wave) before += wsum[i];
-  uint32_t run = before + x - s;
   uint32_t* gl = cursor + (size_t)g * FB;
   uint32_t gb[4];
 #pragma unroll
+  for (int k = 0; k < 4; k++) gb[k] = c[k] ? atomicAdd(&gl[4 * threadIdx.x + k], c[k]) : 0u;      // reserve the runs' slots (in flight under the scans)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // Way out without a search: a bit per sorted position marks the run starts, wpre[w] counts the starts before 32-position word w, and
+  // delta is indexed by a run's RANK among the non-empty buckets -- entry i then finds its slot with three LDS reads (mask word and
+  // word prefix, then delta) where a binary search over the 4096 run ends took twelve dependent ones (30 % of this kernel at 2^22).
+  const uint32_t nz = (c[0] != 0) + (c[1] != 0) + (c[2] != 0) + (c[3] != 0);
+  uint32_t x = s, y = nz;                                      // run starts, and the rank of this thread's first non-empty bucket: two scans of one shape
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t xs = __shfl_up(x, off, 64), ys = __shfl_up(y, off, 64);
+    if (lane >= off) { x += xs; y += ys; }
+  }
+  if (lane == 63) { wsum[0][wave] = x; wsum[1][wave] = y; }
+  __syncthreads();
+  uint32_t run = x - s, rank = y - nz;
+#pragma unroll
+  for (int i = 0; i < 16; i++) if (i < wave) { run += wsum[0][i]; rank += wsum[1][i]; }
+#pragma unroll
   for (int k = 0; k < 4; k++) { l[k] = run; run += c[k]; }
 #pragma unroll
-  for (int k = 0; k < 4; k++) gb[k] = c[k] ? atomicAdd(&gl[4 * threadIdx.x + k], c[k]) : 0u;      // reserve the runs' slots
-  {
-    // Way out without a search: a bit per sorted position marks the run starts, wpre[w] counts the starts before 32-position word w, and
-    // delta is indexed by a run's RANK among the non-empty buckets -- entry i then finds its slot with three LDS reads (mask word and
-    // word prefix, then delta) where a binary search over the 4096 run ends took twelve dependent ones (30 % of this kernel at 2^22).
-    uint32_t* mask = refs + CHUNK;                             // CHUNK / 32 words
-    uint32_t* wpre = mask + CHUNK / 32;                        // CHUNK / 32 words
-    const uint32_t nz = (c[0] != 0) + (c[1] != 0) + (c[2] != 0) + (c[3] != 0);
-    uint32_t y = nz;                                           // rank of this thread's first non-empty bucket: a second scan, same shape
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t t = __shfl_up(y, off, 64);
-      if (lane >= off) y += t;
+  for (int k = 0; k < 4; k++) {
+    cur[4 * threadIdx.x + k] = l[k];
+    if (c[k]) {
+      delta[rank++] = gb[k] - l[k];
+      atomicOr(&mask[l[k] >> 5], 1u << (l[k] & 31));
     }
-    __syncthreads();                                           // wsum is read by everyone above
-    if (lane == 63) wsum[wave] = y;
-    for (uint32_t w2 = threadIdx.x; w2 < CHUNK / 32; w2 += blockDim.x) mask[w2] = 0;
-    __syncthreads();
-    uint32_t rank = y - nz;
-#pragma unroll
-    for (int i = 0; i < 16; i++) if (i < wave) rank += wsum[i];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      cur[4 * threadIdx.x + k] = l[k];
-      if (c[k]) {
-        delta[rank++] = gb[k] - l[k];
-        atomicOr(&mask[l[k] >> 5], 1u << (l[k] & 31));
-      }
-    }
-    __syncthreads();
-    // word prefixes: CHUNK / 32 = 896 <= 1024 words, one per thread
-    const uint32_t pc = threadIdx.x < CHUNK / 32 ? (uint32_t)__popc(mask[threadIdx.x]) : 0u;
-    uint32_t z = pc;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t t = __shfl_up(z, off, 64);
-      if (lane >= off) z += t;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wave] = z;
-    __syncthreads();
-    uint32_t zb = z - pc;
-#pragma unroll
-    for (int i = 0; i < 16; i++) if (i < wave) zb += wsum[i];
-    if (threadIdx.x < CHUNK / 32) wpre[threadIdx.x] = zb;
   }
   __syncthreads();
-  {
-    // (FINE_BATCH entries per lane in flight, as in fine_histogram)
-    for (uint32_t p = start + threadIdx.x; p < end; p += FINE_BATCH * blockDim.x) {
-      uint32_t f[FINE_BATCH], r[FINE_BATCH];
+  // placement from the registers; the word prefixes (CHUNK / 32 = 896 <= 1024 words, one per thread) are only read on the way out
 #pragma unroll
-      for (int k = 0; k < FINE_BATCH; k++) { const uint32_t q = p + k * blockDim.x; f[k] = q < end ? stage_fine[q] : 0xffffffffu; r[k] = q < end ? stage_ref[q] : 0u; }
+  for (int k = 0; k < PER_LANE; k++) if (f[k] != 0xffffffffu) refs[cur[f[k] & (FB - 1)] + (f[k] >> FINE_BITS)] = r[k];
+  const uint32_t pc = threadIdx.x < CHUNK / 32 ? (uint32_t)__popc(mask[threadIdx.x]) : 0u;
+  uint32_t z = pc;
 #pragma unroll
-      for (int k = 0; k < FINE_BATCH; k++) if (f[k] != 0xffffffffu) refs[atomicAdd(&cur[f[k]], 1u)] = r[k];
-    }
-    __syncthreads();
-    const uint32_t* mask = refs + CHUNK;
-    const uint32_t* wpre = mask + CHUNK / 32;
-    for (uint32_t i = threadIdx.x; i < cnt_n; i += blockDim.x) {
-      const uint32_t r = wpre[i >> 5] + (uint32_t)__popc(mask[i >> 5] & ((2u << (i & 31)) - 1u)) - 1u;     // rank of the run position i lies in
-      sorted[delta[r] + i] = refs[i];
-    }
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t t = __shfl_up(z, off, 64);
+    if (lane >= off) z += t;
+  }
+  if (lane == 63) wsum[2][wave] = z;
+  __syncthreads();
+  uint32_t zb = z - pc;
+#pragma unroll
+  for (int i = 0; i < 16; i++) if (i < wave) zb += wsum[2][i];
+  if (threadIdx.x < CHUNK / 32) wpre[threadIdx.x] = zb;
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < cnt_n; i += blockDim.x) {
+    const uint32_t rk = wpre[i >> 5] + (uint32_t)__popc(mask[i >> 5] & ((2u << (i & 31)) - 1u)) - 1u;     // rank of the run position i lies in
+    sorted[delta[rk] + i] = refs[i];
   }
 }
 
@@ -743,6 +735,7 @@ __global__ void __launch_bounds__(1024) k_fine_count(const uint16_t* __restrict_
 // ------------------------------------------------------------------------------------------------
 constexpr int SCAN_BLOCK = 256, SCAN_PER_THREAD = 4,     // (16 -> 4: 4 x the workgroups and 16-byte lane strides: scan phase 0.024 -> 0.0155 ms at 2^20)
           SCAN_TILE = SCAN_BLOCK * SCAN_PER_THREAD;
+constexpr uint32_t SCAN_APPLY_WGS = 256;                 // workgroups of k_scan_apply2: each merges a task-length histogram into the same global words
 
 template <int MODE>
 __device__ __forceinline__ uint32_t scan_xform(uint32_t v, uint32_t task_shift) {
@@ -805,27 +798,58 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_top2(uint32_t* __restrict__
 __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_apply2(const uint32_t* __restrict__ in, uint32_t n, const uint32_t* __restrict__ sums0,
                                                             const uint32_t* __restrict__ sums1, const uint32_t* __restrict__ total0,
                                                             const uint32_t* __restrict__ total1, uint32_t* __restrict__ offset,
-                                                            uint32_t* __restrict__ cursor, uint32_t* __restrict__ task_off, uint32_t task_shift) {
+                                                            uint32_t* __restrict__ cursor, uint32_t* __restrict__ task_off, uint32_t task_shift,
+                                                            uint32_t nblk, uint32_t* __restrict__ len_count) {
+  // This pass sees every bucket count, so the task-length histogram (len_count[L] = tasks of L entries; k_make_order scans it) comes out of
+  // it as well.  The grid is capped at SCAN_APPLY_WGS workgroups that walk the nblk tiles: a workgroup merges its LDS histogram with one
+  // global atomic per length on the same words, and with a workgroup per tile those are the contended atomics k_make_tasks' capped grid avoids.
   __shared__ uint32_t lds[4];
-  const uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_PER_THREAD;
-  uint32_t v[SCAN_PER_THREAD], s0 = 0, s1 = 0;
+  __shared__ uint32_t lh[MAX_TASK_LEN + 1];
+  static_assert(SCAN_BLOCK > MAX_TASK_LEN, "one thread per length");
+  if (threadIdx.x <= MAX_TASK_LEN) lh[threadIdx.x] = 0;
+  __syncthreads();
+  uint32_t n_full = 0;
+  auto load_tile = [&](uint32_t blk, uint32_t (&v)[SCAN_PER_THREAD]) {
+    const uint32_t base = blk * SCAN_TILE + threadIdx.x * SCAN_PER_THREAD;
 #pragma unroll
-  for (int i = 0; i < SCAN_PER_THREAD; i++) { v[i] = base + i < n ? in[base + i] : 0; s0 += v[i]; s1 += scan_xform<1>(v[i], task_shift); }
-  uint32_t t0, t1;
-  uint32_t e0 = block_exclusive_scan(s0, lds, t0) + sums0[blockIdx.x];
-  uint32_t e1 = block_exclusive_scan(s1, lds, t1) + sums1[blockIdx.x];
+    for (int i = 0; i < SCAN_PER_THREAD; i++) v[i] = (blk < nblk && base + i < n) ? in[base + i] : 0;
+  };
+  uint32_t v[SCAN_PER_THREAD], vn[SCAN_PER_THREAD];
+  load_tile(blockIdx.x, v);
+  for (uint32_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {              // uniform per workgroup
+    const uint32_t base = blk * SCAN_TILE + threadIdx.x * SCAN_PER_THREAD;
+    load_tile(blk + gridDim.x, vn);                                            // the next tile's counts arrive under this tile's scans
+    uint32_t s0 = 0, s1 = 0;
 #pragma unroll
-  for (int i = 0; i < SCAN_PER_THREAD; i++) {
-    if (base + i < n) { offset[base + i] = e0; cursor[base + i] = e0; task_off[base + i] = e1; }
-    e0 += v[i];
-    e1 += scan_xform<1>(v[i], task_shift);
+    for (int i = 0; i < SCAN_PER_THREAD; i++) { s0 += v[i]; s1 += scan_xform<1>(v[i], task_shift); }
+    uint32_t t0, t1;
+    uint32_t e0 = block_exclusive_scan(s0, lds, t0) + sums0[blk];
+    uint32_t e1 = block_exclusive_scan(s1, lds, t1) + sums1[blk];
+#pragma unroll
+    for (int i = 0; i < SCAN_PER_THREAD; i++) {
+      if (base + i < n) { offset[base + i] = e0; cursor[base + i] = e0; task_off[base + i] = e1; }
+      const uint32_t m = scan_xform<1>(v[i], task_shift);
+      if (m) {   // m - 1 full tasks and one of the remaining length
+        n_full += m - 1;
+        atomicAdd(&lh[v[i] - ((m - 1) << task_shift)], 1u);
+      }
+      e0 += v[i];
+      e1 += m;
+    }
+#pragma unroll
+    for (int i = 0; i < SCAN_PER_THREAD; i++) v[i] = vn[i];
   }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) n_full += (uint32_t)__shfl_xor((int)n_full, off, 64);
+  if ((threadIdx.x & 63) == 0 && n_full) atomicAdd(&lh[1u << task_shift], n_full);
+  __syncthreads();
+  if (threadIdx.x <= MAX_TASK_LEN && lh[threadIdx.x]) atomicAdd(&len_count[threadIdx.x], lh[threadIdx.x]);
   if (blockIdx.x == 0 && threadIdx.x == 0) { offset[n] = *total0; task_off[n] = *total1; }
 }
 
 // The same scan as ONE workgroup, for up to SCAN_SINGLE_MAX values = one tile of 1024 threads x 8 (bucket sets of c <= 14: the
 // small, latency-bound MSMs): three dependent launches become one, and with MODE 1 the task-length histogram and its cursors
-// (k_make_tasks' atomics and k_order_offsets) come out of the same pass -- five launches of ~5 us less per MSM (2^13: 0.254 ->
+// (once k_make_tasks' atomics and a launch of their own for the scan) come out of the same pass -- five launches of ~5 us less per MSM (2^13: 0.254 ->
 // 0.245 ms).  More tiles in one workgroup lose: 2^15 values take 47 us this way against 17 us with the three kernels.
 constexpr uint32_t SCAN_SINGLE_MAX = 8192;
 template <int MODE>
@@ -899,13 +923,10 @@ constexpr uint32_t HEAVY_SLICE = 2048;   // partials of a heavy bucket one workg
 constexpr uint32_t COOP_TASKS = 32;
 __global__ void __launch_bounds__(256) k_make_tasks(const uint32_t* __restrict__ offset, const uint32_t* __restrict__ task_off,
                                                     uint32_t nbuckets, task_t* __restrict__ tasks, uint32_t task_shift,
-                                                    uint32_t* __restrict__ max_parts, uint32_t* __restrict__ len_count, uint32_t seq_parts,
+                                                    uint32_t* __restrict__ max_parts, uint32_t seq_parts,
                                                     uint32_t* __restrict__ heavy_count, uint2* __restrict__ heavy, uint32_t heavy_cap) {
-  __shared__ uint32_t lh[MAX_TASK_LEN + 1];
-  if (threadIdx.x <= MAX_TASK_LEN) lh[threadIdx.x] = 0;
-  __syncthreads();
-  // a capped grid walks the buckets: the length histogram costs one global atomic per (workgroup, length) on the same 65 words,
-  // and with one workgroup per 256 buckets those were 2048 x 65 contended atomics at 2^19 buckets (99 us of a 6 ms MSM)
+  // Bucket sets of at most SCAN_SINGLE_MAX buckets only (k_scan_single<1> made their length histogram); above that k_make_order writes
+  // the records, the heavy list and max_parts in its own walk over the buckets.
   uint32_t nt = 0;
   const uint32_t lane = threadIdx.x & 63u;
   for (uint32_t base = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base < nbuckets; base += gridDim.x * blockDim.x) {   // uniform per wavefront
@@ -921,10 +942,6 @@ __global__ void __launch_bounds__(256) k_make_tasks(const uint32_t* __restrict__
         tk.len = min(1u << task_shift, e - tk.start);
         tasks[t + j] = tk;
       }
-    }
-    if (m) {   // m - 1 full tasks and one of the remaining length
-      if (m > 1) atomicAdd(&lh[1u << task_shift], m - 1);
-      atomicAdd(&lh[(e - s) - ((m - 1) << task_shift)], 1u);
     }
     if (m > seq_parts) {      // more partials than the per-bucket step of the combine kernel sums: listed for its heavy-bucket workgroups,
       const uint32_t P = (m + HEAVY_SLICE - 1) / HEAVY_SLICE;     // one entry (bucket, slice) per HEAVY_SLICE partials, consecutive in the list
@@ -948,8 +965,6 @@ __global__ void __launch_bounds__(256) k_make_tasks(const uint32_t* __restrict__
       }
     }
   }
-  __syncthreads();
-  if (len_count && threadIdx.x <= MAX_TASK_LEN && lh[threadIdx.x]) atomicAdd(&len_count[threadIdx.x], lh[threadIdx.x]);   // nullptr: k_scan_single<1> made the histogram
   // block max -> one atomic per wave
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) nt = max(nt, (uint32_t)__shfl_xor((int)nt, off, 64));
@@ -957,40 +972,48 @@ __global__ void __launch_bounds__(256) k_make_tasks(const uint32_t* __restrict__
 }
 
 // Execution order of the tasks: longest first, so that the 64 tasks of a wave have equal length (a wave runs as long as its
-// longest task) and the launch tail consists of short tasks.  len_cursor[L] = first slot of length L.
-__global__ void k_order_offsets(const uint32_t* __restrict__ len_count, uint32_t* __restrict__ len_cursor) {
-  // one wavefront: lengths MAX_TASK_LEN - 2 lane and MAX_TASK_LEN - 2 lane - 1 per lane, an exclusive scan by shuffles (longest first).  (The
-  // single-thread loop this replaces was 128 dependent loads and stores: 5 us.)
-  static_assert(MAX_TASK_LEN == 128, "two lengths per lane of one wavefront");
-  if (blockIdx.x != 0 || threadIdx.x >= 64) return;
-  const int lane = threadIdx.x, L0 = MAX_TASK_LEN - 2 * lane, L1 = L0 - 1;         // L0 = 128 ... 2, L1 = 127 ... 1
-  const uint32_t c0 = len_count[L0], c1 = len_count[L1];
-  uint32_t x = c0 + c1;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  const uint32_t ex = x - (c0 + c1);
-  len_cursor[L0] = ex;
-  len_cursor[L1] = ex + c0;
-}
-
+// longest task) and the launch tail consists of short tasks.
+//
 // Within the class of full-length tasks the order is j-major per workgroup (j = the task's index inside its
 // bucket): a wavefront of k_accumulate then runs 64 tasks that sit at the same depth of 64 neighbouring buckets.  The sort fills
 // every bucket roughly window by window, so those 64 tasks gather their points from the same one or two window slices of the
 // prepared table instead of from all of it -- the table of a 2^24-point MSM is 13 GiB, and the gathers' address-translation
 // footprint, not their bandwidth, is what costs (an emulated dense 16 GiB footprint slows the 2^20 accumulation by 11 %).
+//
+// Slots of length L: lbase[L] + len_cursor[L], the cursor advanced once per workgroup.
+//   len_count != nullptr (k_scan_apply2 made the histogram): every workgroup scans the MAX_TASK_LEN counters itself, longest first, into
+//     lbase, and len_cursor starts at zero -- a launch of one wavefront (k_order_offsets) did that scan until it moved here.
+//   len_count == nullptr (k_scan_single<1>): len_cursor already holds the first slot of every length, lbase = 0.
+// tasks != nullptr: the same walk over the buckets also writes the task_t records, the heavy-bucket list and max_parts (k_make_tasks'
+//   work above SCAN_SINGLE_MAX buckets: one launch and one pass over offset / task_off less).
 constexpr int ORDER_JMAX = 64;
 __global__ void __launch_bounds__(256) k_make_order(const uint32_t* __restrict__ offset, const uint32_t* __restrict__ task_off,
                                                     uint32_t nbuckets, uint32_t task_shift, uint32_t* __restrict__ len_cursor,
-                                                    const uint32_t* __restrict__ sorted, uint4* __restrict__ order) {
-  __shared__ uint32_t lh[MAX_TASK_LEN + 1];
+                                                    const uint32_t* __restrict__ sorted, uint4* __restrict__ order,
+                                                    const uint32_t* __restrict__ len_count, task_t* __restrict__ tasks,
+                                                    uint32_t* __restrict__ max_parts, uint32_t seq_parts, uint32_t* __restrict__ heavy_count,
+                                                    uint2* __restrict__ heavy, uint32_t heavy_cap) {
+  __shared__ uint32_t lh[MAX_TASK_LEN + 1], lbase[MAX_TASK_LEN + 1];
   __shared__ uint32_t jcnt[ORDER_JMAX + 1], joff[ORDER_JMAX + 1];
+  static_assert(MAX_TASK_LEN == 128, "two lengths per lane of one wavefront");
   if (threadIdx.x <= MAX_TASK_LEN) lh[threadIdx.x] = 0;
   if (threadIdx.x <= ORDER_JMAX) jcnt[threadIdx.x] = 0;
+  if (threadIdx.x >= 192) {              // the last wavefront: lengths MAX_TASK_LEN - 2 lane and MAX_TASK_LEN - 2 lane - 1 per lane, exclusive scan by shuffles
+    const int lane = threadIdx.x - 192, L0 = MAX_TASK_LEN - 2 * lane, L1 = L0 - 1;         // L0 = 128 ... 2, L1 = 127 ... 1
+    const uint32_t c0 = len_count ? len_count[L0] : 0u, c1 = len_count ? len_count[L1] : 0u;
+    uint32_t x = c0 + c1;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t y = __shfl_up(x, off, 64);
+      if (lane >= off) x += y;
+    }
+    const uint32_t ex = x - (c0 + c1);
+    lbase[L0] = ex;
+    lbase[L1] = ex + c0;
+    if (lane == 0) lbase[0] = 0;
+  }
   __syncthreads();
-  const uint32_t full = 1u << task_shift, step = gridDim.x * blockDim.x;     // capped grid, as k_make_tasks
+  const uint32_t full = 1u << task_shift, step = gridDim.x * blockDim.x;     // capped grid: one cursor atomic per (workgroup, length)
   for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < nbuckets; k += step) {
     const uint32_t nt = task_off[k + 1] - task_off[k];
     if (nt) {
@@ -1005,14 +1028,15 @@ __global__ void __launch_bounds__(256) k_make_order(const uint32_t* __restrict__
   if (threadIdx.x == 0) {                      // offsets of the depth classes inside this workgroup's range of full tasks
     uint32_t run = 0;
     for (int j = 0; j <= ORDER_JMAX; j++) { joff[j] = run; run += jcnt[j]; }
-    const uint32_t base = run ? atomicAdd(&len_cursor[full], run) : 0u;
+    const uint32_t base = run ? lbase[full] + atomicAdd(&len_cursor[full], run) : 0u;
     for (int j = 0; j <= ORDER_JMAX; j++) joff[j] += base;
   }
-  if (threadIdx.x <= MAX_TASK_LEN && threadIdx.x != full) { const uint32_t v = lh[threadIdx.x]; lh[threadIdx.x] = v ? atomicAdd(&len_cursor[threadIdx.x], v) : 0u; }
+  if (threadIdx.x <= MAX_TASK_LEN && threadIdx.x != full) { const uint32_t v = lh[threadIdx.x]; lh[threadIdx.x] = v ? lbase[threadIdx.x] + atomicAdd(&len_cursor[threadIdx.x], v) : 0u; }
   __syncthreads();
-  if (threadIdx.x == 0 && lh[full]) lh[full] = atomicAdd(&len_cursor[full], lh[full]);     // remainder tasks of full length, after the depth classes
+  if (threadIdx.x == 0 && lh[full]) lh[full] = lbase[full] + atomicAdd(&len_cursor[full], lh[full]);     // remainder tasks of full length, after the depth classes
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63u;
+  uint32_t mx = 0;
   for (uint32_t base = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base < nbuckets; base += step) {     // uniform per wavefront
     const uint32_t k = base + lane;
     uint32_t t = 0, nt = 0, s0 = 0, pos = 0, nfull = 0, head = 0;
@@ -1027,11 +1051,20 @@ __global__ void __launch_bounds__(256) k_make_order(const uint32_t* __restrict__
       for (uint32_t j = 0; j < head; j++) {
         const uint32_t st = s0 + (j << task_shift);
         order[atomicAdd(&joff[j], 1u)] = make_uint4(t + j, st, full, sorted[st]);
+        if (tasks) tasks[t + j] = task_t{k, st, full};
       }
       if (nfull > head) pos = atomicAdd(&joff[ORDER_JMAX], nfull - head);
       const uint32_t st = s0 + ((nt - 1) << task_shift);
       // a bucket that is a single task needs no combining: its sum goes straight to the bucket array (bit 31 = "x is the bucket")
       order[atomicAdd(&lh[rem], 1u)] = make_uint4(nt == 1 ? (0x80000000u | k) : t + nt - 1, st, rem, sorted[st]);
+      if (tasks) tasks[t + nt - 1] = task_t{k, st, rem};
+      if (tasks && nt > seq_parts) {      // more partials than the per-bucket step of the combine kernel sums: listed for its heavy-bucket workgroups,
+        const uint32_t P = (nt + HEAVY_SLICE - 1) / HEAVY_SLICE;     // one entry (bucket, slice) per HEAVY_SLICE partials, consecutive in the list
+        const uint32_t idx = atomicAdd(heavy_count, P);
+        for (uint32_t i = 0; i < P; i++)
+          if (idx + i < heavy_cap) heavy[idx + i] = make_uint2(k, i);   // (the cap cannot be exceeded: msm_lay_out)
+      }
+      mx = max(mx, nt);
     }
     // full tasks beyond depth ORDER_JMAX: a short run is written by its owner, a long one by the wavefront (see k_make_tasks)
     const bool coop = nfull - head > COOP_TASKS;
@@ -1039,6 +1072,7 @@ __global__ void __launch_bounds__(256) k_make_order(const uint32_t* __restrict__
       for (uint32_t j = head; j < nfull; j++) {
         const uint32_t st = s0 + (j << task_shift);
         order[pos + j - head] = make_uint4(t + j, st, full, sorted[st]);
+        if (tasks) tasks[t + j] = task_t{k, st, full};
       }
     }
     unsigned long long big = __ballot(coop);
@@ -1050,8 +1084,14 @@ __global__ void __launch_bounds__(256) k_make_order(const uint32_t* __restrict__
       for (uint32_t j = bhead + lane; j < bnfull; j += 64) {
         const uint32_t st = bs0 + (j << task_shift);
         order[bpos + j - bhead] = make_uint4(bt + j, st, full, sorted[st]);
+        if (tasks) tasks[bt + j] = task_t{base + (uint32_t)src, st, full};
       }
     }
+  }
+  if (tasks) {      // largest task count of one bucket: workgroup max -> one atomic per wave, none when every bucket is a single task
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, 64));
+    if (lane == 0 && mx > 1) atomicMax(max_parts, mx);
   }
 }
 
@@ -1700,7 +1740,8 @@ int msm_build_tasks(const uint32_t* d_scalars, size_t n_in, size_t batch, size_t
   } else {
     hipLaunchKernelGGL(k_scan_sums2, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, count, NB, bsum1, bsum2, task_shift);
     hipLaunchKernelGGL(k_scan_top2, dim3(1), dim3(SCAN_BLOCK), 0, stream, bsum1, bsum2, nblk, counters + 0, counters + 1);
-    hipLaunchKernelGGL(k_scan_apply2, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, count, NB, bsum1, bsum2, counters + 0, counters + 1, offset, cursor, task_off, task_shift);
+    hipLaunchKernelGGL(k_scan_apply2, dim3(std::min(nblk, SCAN_APPLY_WGS)), dim3(SCAN_BLOCK), 0, stream, count, NB, bsum1, bsum2, counters + 0, counters + 1, offset, cursor, task_off,
+                       task_shift, nblk, counters + 32);
   }
   prof_mark(stream, "scan");
   // 4. scatter
@@ -1714,15 +1755,15 @@ int msm_build_tasks(const uint32_t* d_scalars, size_t n_in, size_t batch, size_t
   const unsigned task_blocks = (unsigned)std::min<size_t>((NB + 255) / 256, 256);
   if (scan_single) {
     hipLaunchKernelGGL(k_scan_single<1>, dim3(1), dim3(1024), 0, stream, count, (uint32_t)NB, counters + 1, task_off, (uint32_t*)nullptr, task_shift, counters + 192);
-    hipLaunchKernelGGL(k_make_tasks, dim3(task_blocks), dim3(256), 0, stream, offset, task_off, NB, tasks, task_shift, counters + 2, (uint32_t*)nullptr, lay.seq_parts,
+    hipLaunchKernelGGL(k_make_tasks, dim3(task_blocks), dim3(256), 0, stream, offset, task_off, NB, tasks, task_shift, counters + 2, lay.seq_parts,
                        counters + 3, lay.heavy, lay.heavy_cap);
+    hipLaunchKernelGGL(k_make_order, dim3(task_blocks), dim3(256), 0, stream, offset, task_off, NB, task_shift, counters + 192, sorted, order,
+                       (const uint32_t*)nullptr, (task_t*)nullptr, counters + 2, lay.seq_parts, counters + 3, lay.heavy, lay.heavy_cap);
   } else {
-    // (the task offsets came out of the dual scan of step 3)
-    hipLaunchKernelGGL(k_make_tasks, dim3(task_blocks), dim3(256), 0, stream, offset, task_off, NB, tasks, task_shift, counters + 2, counters + 32, lay.seq_parts,
-                       counters + 3, lay.heavy, lay.heavy_cap);
-    hipLaunchKernelGGL(k_order_offsets, dim3(1), dim3(64), 0, stream, counters + 32, counters + 192);
+    // (the task offsets and the task-length histogram came out of the dual scan of step 3; k_make_order writes the task records as well)
+    hipLaunchKernelGGL(k_make_order, dim3(task_blocks), dim3(256), 0, stream, offset, task_off, NB, task_shift, counters + 192, sorted, order,
+                       (const uint32_t*)(counters + 32), tasks, counters + 2, lay.seq_parts, counters + 3, lay.heavy, lay.heavy_cap);
   }
-  hipLaunchKernelGGL(k_make_order, dim3(task_blocks), dim3(256), 0, stream, offset, task_off, NB, task_shift, counters + 192, sorted, order);
   prof_mark(stream, "tasks");
   out->c = c; out->W = W; out->WB = WB; out->B = B; out->NB = NB; out->task_shift = task_shift; out->max_tasks = lay.max_tasks; out->nk = n * K;
   out->tasks = tasks; out->ntasks = counters + 1; out->max_parts = counters + 2; out->order = order; out->sorted = sorted; out->task_off = task_off;

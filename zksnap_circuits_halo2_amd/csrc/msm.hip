@@ -30,6 +30,7 @@
 #include <mutex>
 #include "ec_quad.hpp"
 #include "fe_inverse.hpp"
+#include "reduce_plan.hpp"
 #include "zkhip_internal.hpp"
 
 namespace zkhip {
@@ -1357,6 +1358,39 @@ __global__ void __launch_bounds__(128) k_pyramid_step_quad(const uint32_t* __res
   if (q == 0) store_xyzz(wo, tid, r);
 }
 
+// Steps s and s + 1 in one launch, for the levels where a launch holds one dependent addition and costs more than it: the state
+// [X (N) | Z^0 .. Z^(s-2) (N/2 each)] becomes [X'' (N/4) | Z''^0 .. Z''^s (N/8 each)], every output the sum of four inputs
+//      X''[t]      = (X[4t] + X[4t+1]) + (X[4t+2] + X[4t+3])
+//      Z''^l[u]    = (Z^l[4u] + Z^l[4u+1]) + (Z^l[4u+2] + Z^l[4u+3])          (l <= s-2)
+//      Z''^(s-1)[v] = (X[8v+1] + X[8v+3]) + (X[8v+5] + X[8v+7])
+//      Z''^s[v]     = (X[8v+2] + X[8v+3]) + (X[8v+6] + X[8v+7])
+// -- the additions of the two single steps in the same order, except that the two X-derived rows each form their own pair sums (12 additions
+// per 8 X elements instead of 10; the lanes are idle anyway).  Two quads per output: each adds one pair, the second operand of the last
+// addition crosses with a shuffle of 4 lanes.  N >= 8.
+__global__ void __launch_bounds__(128) k_pyramid_pair_quad(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                           uint32_t N, int s, uint32_t in_stride, uint32_t out_stride) {
+  const uint32_t outs = N / 4 + (uint32_t)(s + 1) * (N / 8);
+  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t o = gid >> 3, half = (gid >> 2) & 1, q = gid & 3;
+  if (o >= outs) return;                               // whole groups of 8 lanes leave together
+  const int win = blockIdx.y;
+  const uint32_t* wi = in + (size_t)win * in_stride * 36;
+  uint32_t* wo = out + (size_t)win * out_stride * 36;
+  uint32_t ia, ib;
+  if (o < N / 4) {
+    ia = 4 * o + 2 * half; ib = ia + 1;
+  } else {
+    const uint32_t r = o - N / 4;
+    const uint32_t l = r / (N / 8), v = r % (N / 8);
+    if ((int)l == s - 1) { ia = 8 * v + 4 * half + 1; ib = ia + 2; }
+    else if ((int)l == s) { ia = 8 * v + 4 * half + 2; ib = ia + 1; }
+    else { ia = N + l * (N / 2) + 4 * v + 2 * half; ib = ia + 1; }
+  }
+  const xyzz p = xyzz_add_quad(load_xyzz(wi, ia), load_xyzz(wi, ib), q);
+  const xyzz r = xyzz_add_quad(p, xyzz_shfl_xor(p, 4), q);      // (both quads of the output: the shuffle needs both, the addition costs the first nothing)
+  if ((gid & 7) == 0) store_xyzz(wo, o, r);
+}
+
 // 9a. per-window weighted sum.  Input state after the last pyramid step: X has 2 elements, Z^0..Z^(nz-1) one each.
 //     window sum = X0 + X1 + sum_l 2^l Z^l + 2^nz X1.  One 32-lane group per window: lane l < nz computes 2^l Z^l by l
 //     doublings, lane nz computes 2^nz X1, lane nz + 1 holds X0 + X1; a 4-step shuffle tree adds the terms.
@@ -1405,6 +1439,98 @@ __global__ void __launch_bounds__(128) k_window_horner_quad(const uint32_t* __re
       if (jac_out) store_jacobian(acc, jac_out + (size_t)win * 24);     // prepared path: a bucket set's weighted sum is a final result
       else store_xyzz(winsum, win, acc);
     }
+  }
+}
+
+// 8 + 9a in one workgroup per bucket set, from the first step whose additions fit the workgroup's quads (reduce_plan.hpp: FINISH): the
+// remaining pyramid steps, the weighted sum and the store.  The levels below that point are one dependent quad addition each, so a launch
+// per level is mostly launch; here they are separated by a workgroup barrier only.  The first level reads the state from global memory,
+// the later ones ping-pong between two LDS buffers (REDUCE_FINISH_ADDS and REDUCE_FINISH_ADDS2 elements: every level's output fits the
+// buffer of its parity, see reduce_make_plan).  No workgroup waits for another.
+//
+// Weighted sum (same identity as k_window_horner_quad: X0 + X1 + sum_l 2^l Z^l + 2^nz X1), the terms laid out by the length of their
+// doubling chains so that the additions of the short ones run while the long ones still double -- a wavefront executes the trip count of
+// its longest quad, and a tree step costs about 1.3 doublings:
+//   wavefront 0   chains of 0 .. 11 doublings, X0 and X1                      (<= 14 quads, 4 tree steps: done after ~16 doublings' time)
+//   wavefront 1   chains of 12 .. 15 doublings                                (<= 4 quads, 2 tree steps: ~17.5)
+//   wavefront 2   chains of 16 and 17 doublings                               (<= 2 quads, 1 tree step: ~18.3)
+//   wavefront 3   chains of 18 doublings and more                             (c = 20: the one quad of 2^18 X1, no tree step)
+// The four sums meet through LDS after one barrier and wavefront 0 adds them with two more steps of the same tree loop (one copy of the
+// addition's code for both): at c = 20 two dependent additions follow the longest chain, where the uniform layout had a 5-step tree, the
+// LDS step and a divergent X0 + X1 in front.
+constexpr int FINISH_THREADS = 512;          // 128 quads.  (1024 threads leave a wavefront 128 VGPRs: the quad addition then spills ~400 of them)
+constexpr int FINISH_CHAIN0 = 11, FINISH_CHAIN1 = 15, FINISH_CHAIN2 = 17;      // longest chain of wavefronts 0, 1, 2
+
+__global__ void __launch_bounds__(FINISH_THREADS) k_reduce_finish(const uint32_t* __restrict__ in, uint32_t in_stride, uint32_t N, int s,
+                                                                  uint32_t* __restrict__ winsum, uint32_t* __restrict__ jac_out) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[(REDUCE_FINISH_ADDS + REDUCE_FINISH_ADDS2) * 36];
+  __shared__ __attribute__((aligned(16))) uint32_t xch[3 * 36];
+  constexpr uint32_t BUF1 = REDUCE_FINISH_ADDS * 36;    // word offset of the second buffer
+  const int win = blockIdx.x;
+  const uint32_t q = threadIdx.x & 3, quad = threadIdx.x >> 2;
+  const uint32_t* wi = in + (size_t)win * in_stride * 36;
+  const bool levels = N > 2;
+  uint32_t cur = 0;                                     // word offset in lds of the current state (once a level has run)
+  bool first = true;
+#pragma unroll 1
+  while (N > 2) {                                       // uniform over the workgroup
+    const uint32_t per_win = N / 2 + (uint32_t)s * (N / 4);
+    const uint32_t nxt = first ? 0u : (cur == 0 ? BUF1 : 0u);
+    static_assert(FINISH_THREADS / 4 >= (int)REDUCE_FINISH_ADDS, "one quad per addition of the widest level");
+    if (quad < per_win) {                               // whole quads
+      uint32_t ia, ib;
+      if (quad < N / 2) {
+        ia = 2 * quad; ib = 2 * quad + 1;
+      } else {
+        const uint32_t r = quad - N / 2;
+        const uint32_t l = r / (N / 4), u = r % (N / 4);
+        if ((int)l == s - 1) { ia = 4 * u + 1; ib = 4 * u + 3; }
+        else { ia = N + l * (N / 2) + 2 * u; ib = ia + 1; }
+      }
+      xyzz a, b;
+      if (first) { a = load_xyzz(wi, ia); b = load_xyzz(wi, ib); }
+      else { a = load_xyzz(lds + cur, ia); b = load_xyzz(lds + cur, ib); }
+      const xyzz r = xyzz_add_quad(a, b, q);
+      if (q == 0) store_xyzz(lds + nxt, quad, r);
+    }
+    __syncthreads();
+    cur = nxt; first = false;
+    N >>= 1;
+    s++;
+  }
+  // final state [X0, X1, Z^0 .. Z^(nz-1)], nz = s - 1
+  const int nz = s - 1;
+  const int wave = threadIdx.x >> 6, j = (threadIdx.x & 63) >> 2;      // quad j of its wavefront
+  const int n0 = min(nz, FINISH_CHAIN0) + 1;                           // chains in wavefront 0; its next two quads hold X0 and X1
+  int dbl = 0;                                                         // doublings of this quad's term
+  int idx = -1;                                                        // the term's element of the state, -1: no term
+  int count = 0;                                                       // quads of this wavefront that hold a term
+  auto chains = [&](int lo, int hi) {                                  // this wavefront takes the chains of lo .. hi doublings
+    count = max(0, min(nz, hi) - lo + 1);
+    if (j < count) { dbl = lo + j; idx = dbl < nz ? 2 + dbl : 1; }     // Z^dbl, or X1 for the chain of nz doublings
+  };
+  if (wave == 0) { chains(0, FINISH_CHAIN0); count = n0 + 2; if (j == n0) idx = 0; else if (j == n0 + 1) idx = 1; }
+  else if (wave == 1) chains(FINISH_CHAIN0 + 1, FINISH_CHAIN1);
+  else if (wave == 2) chains(FINISH_CHAIN1 + 1, FINISH_CHAIN2);
+  else if (wave == 3) chains(FINISH_CHAIN2 + 1, 63);
+  xyzz acc = xyzz_identity();
+  if (idx >= 0) { if (levels) acc = load_xyzz(lds + cur, idx); else acc = load_xyzz(wi, idx); }
+#pragma unroll 1
+  for (int i = 0; i < dbl; i++) acc = xyzz_dbl_quad(acc, q);
+#pragma unroll 1
+  for (int phase = 0; phase < 2; phase++) {                            // 0: every wavefront's own sum; 1: wavefront 0 adds the four sums
+    if (phase == 1) {
+      __syncthreads();
+      count = wave == 0 ? 4 : 0;
+      if (wave == 0 && j >= 1) acc = j < 4 ? load_xyzz(xch, j - 1) : xyzz_identity();
+    }
+#pragma unroll 1
+    for (int mask = 4; (mask >> 2) < count; mask <<= 1) acc = xyzz_add_quad(acc, xyzz_shfl_xor(acc, mask), q);   // count is uniform over the wavefront
+    if (phase == 0 && wave >= 1 && wave <= 3 && (threadIdx.x & 63) == 0) store_xyzz(xch, wave - 1, acc);
+  }
+  if (threadIdx.x == 0) {
+    if (jac_out) store_jacobian(acc, jac_out + (size_t)win * 24);     // prepared path: a bucket set's weighted sum is a final result
+    else store_xyzz(winsum, win, acc);
   }
 }
 
@@ -1500,6 +1626,10 @@ int msm_pick_window_prepared(size_t n) {
   //              bucket at 2^20), which costs the task list its uniformity; measured 64.9 / 64.3 / 68.4 / 60.6 ps per addition at 2^20
   // The tail's latency part is why wider windows lose below 2^20 points and why c = 19 never wins on uniform scalars (2^20: 1.521 vs 1.385 ms,
   // 2^23: 9.78 vs 9.08): halving the buckets returns 0.07 ms of pyramid and costs 7.7 % + 13 % of the accumulation.
+  // With two levels per launch and the one-workgroup finish (profiles/r27_reduce_tail.txt) pyramid + weighted sum + combine measure 0.207 / 0.265 /
+  // 0.273 / 0.313 ms at c = 16 / 18 / 19 / 20 at 2^20 where these constants give 0.182 / 0.219 / 0.257 / 0.326: the narrow windows' combine is
+  // under-priced and c = 20 over-priced by 13 us -- both errors against c = 20, which the model picks all the same and which was measured fastest
+  // again at 2^20 .. 2^22 (uniform scalars).  Four windows do not pin three constants (a free fit gives a negative constant term), so they stay.
   const bool large = n >= ((size_t)1 << 20);
   int best = 2;
   double best_cost = 1e300;
@@ -1820,32 +1950,32 @@ static int msm_accumulate_combine(const msm_tasks_view& tv, const uint32_t* d_ba
 // Steps 8 - 9: dense buckets (WB sets of B, at `cur`; `nxt` = a second array of the same size, both are overwritten) -> the MSM's result(s) at d_out.
 // prepared: every bucket set's weighted sum is a result (K = WB of them); otherwise the WB window sums are folded into one.
 static int msm_reduce_buckets(int WB, uint32_t B, int c, uint32_t K, bool prepared, uint32_t* cur, uint32_t* nxt, uint32_t* winsum, uint32_t* d_out, hipStream_t stream) {
-  // 8. pyramid: buckets were written with window stride B (dense).  Steps 1 .. c-2 leave X with 2 elements.
-  constexpr size_t PYR_QUAD_MAX = 65536;     // additions of a step up to which four lanes share one (profiles/r04_pyramid_quad_threshold_ab.txt)
-  uint32_t in_stride = B;
-  int nz = 0;
-  {
-    uint32_t N = B;
-    int s = 1;
-    while (N > 2) {
-      uint32_t per_win = N / 2 + (uint32_t)s * (N / 4);
-      uint32_t out_stride = per_win;
-      // below ~1/4 of the chip's lanes an addition's latency is the step time: four lanes per addition
-      if ((size_t)per_win * WB <= PYR_QUAD_MAX) hipLaunchKernelGGL(k_pyramid_step_quad, dim3((4 * per_win + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, N, s, in_stride, out_stride);
-      else hipLaunchKernelGGL(k_pyramid_step, dim3((per_win + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, N, s, in_stride, out_stride);
-      uint32_t* t = cur; cur = nxt; nxt = t;
-      in_stride = out_stride;
-      N >>= 1;
-      s++;
-    }
-    nz = s - 1;   // number of Z rows, one element each (B == 2: none)
-  }
-  prof_mark(stream, "pyramid");
-  // 9. Horner + fold
+  // 8. pyramid: buckets were written with window stride B (dense).  Steps 1 .. c-2 leave X with 2 elements.  The launches are a function of
+  // (B, WB) alone (reduce_plan.hpp): single-lane steps while a step fills the chip, then a quad per addition -- two levels per launch where
+  // that stays far below the chip's lane count --, and up to REDUCE_FINISH_MAX_SETS bucket sets end in one workgroup each (k_reduce_finish:
+  // the last levels, the weighted sum and, for prepared bases, the store).  Larger batches are throughput-bound and keep a launch per level.
   if (B == 1) { set_error("msm: internal: B == 1"); return ZKHIP_EINVAL; }     // (c >= 2, so B >= 2 always)
+  reduce_plan plan;
+  if (!reduce_make_plan(B, WB, &plan)) { set_error("msm: internal: no reduction plan for %u buckets x %d sets", B, WB); return ZKHIP_EINVAL; }
   const bool direct = prepared && WB <= 2048;     // the weighted-sum kernel writes the results itself (one launch less)
-  if (WB <= 2048) hipLaunchKernelGGL(k_window_horner_quad, dim3(WB), dim3(128), 0, stream, cur, in_stride, nz, winsum, direct ? d_out : (uint32_t*)nullptr);
-  else hipLaunchKernelGGL(k_window_horner, dim3((WB * 32 + 63) / 64), dim3(64), 0, stream, cur, in_stride, nz, winsum, WB);
+  for (int i = 0; i < plan.n; i++) {
+    const reduce_launch& L = plan.l[i];
+    if (L.kind == REDUCE_FINISH) {
+      prof_mark(stream, "pyramid");               // (the finish kernel's own levels are timed with the weighted sum)
+      hipLaunchKernelGGL(k_reduce_finish, dim3(WB), dim3(FINISH_THREADS), 0, stream, cur, L.in_stride, L.N, L.s, winsum, direct ? d_out : (uint32_t*)nullptr);
+      break;
+    }
+    if (L.kind == REDUCE_STEP) hipLaunchKernelGGL(k_pyramid_step, dim3((L.out_stride + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride);
+    else if (L.kind == REDUCE_STEP_QUAD) hipLaunchKernelGGL(k_pyramid_step_quad, dim3((4 * L.out_stride + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride);
+    else hipLaunchKernelGGL(k_pyramid_pair_quad, dim3((8 * L.out_stride + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride);
+    uint32_t* t = cur; cur = nxt; nxt = t;
+  }
+  // 9. Horner + fold
+  if (!plan.finish) {
+    prof_mark(stream, "pyramid");
+    if (WB <= 2048) hipLaunchKernelGGL(k_window_horner_quad, dim3(WB), dim3(128), 0, stream, cur, plan.last_stride, plan.nz, winsum, direct ? d_out : (uint32_t*)nullptr);
+    else hipLaunchKernelGGL(k_window_horner, dim3((WB * 32 + 63) / 64), dim3(64), 0, stream, cur, plan.last_stride, plan.nz, winsum, WB);
+  }
   prof_mark(stream, "horner");
   if (prepared) { if (!direct) hipLaunchKernelGGL(k_store_results, dim3((K + 63) / 64), dim3(64), 0, stream, winsum, K, d_out); }   // one result per bucket set
   else hipLaunchKernelGGL(k_fold, dim3(1), dim3(64), 0, stream, winsum, WB, c, d_out);

@@ -846,10 +846,35 @@ int zkhip_plume_sign(const uint8_t *msg, size_t msg_len, const uint64_t sk[4], c
  * rotation table holds a non-zero rotation, or that reads ZKHIP_SRC_PREV or ZKHIP_SRC_ROWPOW; n_evals == 0 or n_evals + 9 > 65536;
  * n_proofs > 2^24; the domain arguments as above; a null pointer, d_evals / d_challenges not 16-byte aligned, d_status not 4-byte or d_report
  * not 8-byte aligned (with n_proofs == 0 the three arrays may be null, d_report never).
- * Not built: instance columns, multi-phase challenges, folding a batch's pairing checks into one (halo2's BatchVerifier) -- DESIGN.md section 10. */
+ *
+ * Instance columns (public inputs).  With halo2's KZG scheme an instance polynomial is neither committed nor opened: the verifier evaluates it
+ * at x omega^rot from the public inputs.  A circuit has n_columns instance columns, column c of column_lens[c] values (zeros behind them);
+ * d_instances: [n_proofs][total_len] elements, total_len = the sum of column_lens, column c's values at offset sum_{c' < c} column_lens[c'].
+ * A QUERY q is a pair (query_columns[q], query_rotations[q]), the rotation reduced mod 2^k as an unsigned value (rotation -1 is 2^k - 1):
+ *   e[q][p] = sum_{i < len_c} v[p][c][i] l_((i - rot) mod n)(x_p)          (len_c = 0 gives 0; x_p in the domain gives 0, nothing is divided)
+ * The three host arrays are consumed before a call returns.
+ * zkhip_fr_instance_evals_device: d_x [n_proofs] points, d_out [n_queries][n_proofs] (the layout of zkhip_fr_domain_points_device); a group of
+ * lanes per (query, proof), one inversion per group.  n_proofs == 0 or n_queries == 0: ZKHIP_OK, nothing is written.  ZKHIP_EINVAL: k == 0 or
+ * k > 28, omega null or not canonical, n_columns or n_queries above 64, a null host array that is not empty, a query column >= n_columns, a
+ * rotation >= 2^k, column_lens[c] > 2^k, n_proofs > 2^24, d_x or d_out null or misaligned where there is something to write, d_instances
+ * null or misaligned where total_len * n_proofs > 0.
+ * zkhip_verify_identity_instances_device: zkhip_verify_identity_device for a circuit with instance columns.  COLUMNS OF THE PROGRAM
+ * (normative): columns 0 .. n_evals + 8 as above; column n_evals + 9 + q is query q, evaluated at the record's x; the program is validated
+ * over n_evals + 9 + n_queries columns.  With n_queries == 0 it does what zkhip_verify_identity_device does.  Status 2 is unchanged (the
+ * instance columns of such a proof are zero).  ZKHIP_EINVAL: the conditions of zkhip_verify_identity_device; n_columns or n_queries above 64;
+ * a query column >= n_columns; a rotation >= 2^k; column_lens[c] > usable_rows (halo2's `InstanceTooLarge`); d_instances null or misaligned
+ * where total_len * n_proofs > 0.
+ * Not built: committed instance columns (`QUERY_INSTANCE = true`, the IPA scheme), multi-phase challenges, folding a batch's pairing checks
+ * into one (halo2's BatchVerifier) -- DESIGN.md section 10. */
 int zkhip_fr_domain_points_device(uint32_t k, uint32_t usable_rows, const uint64_t omega[4], const void *d_x, size_t n_points, void *d_out, void *stream);
 int zkhip_verify_identity_device(const zkhip_vm_program *prog, const void *d_evals, uint32_t n_evals, const void *d_challenges, uint32_t k,
                                  uint32_t usable_rows, const uint64_t omega[4], size_t n_proofs, void *d_status, void *d_report, void *stream);
+int zkhip_fr_instance_evals_device(uint32_t k, const uint64_t omega[4], const void *d_x, const void *d_instances, const uint32_t *column_lens, uint32_t n_columns,
+                                   const uint32_t *query_columns, const uint32_t *query_rotations, uint32_t n_queries, size_t n_proofs, void *d_out, void *stream);
+int zkhip_verify_identity_instances_device(const zkhip_vm_program *prog, const void *d_evals, uint32_t n_evals, const void *d_challenges, uint32_t k,
+                                           uint32_t usable_rows, const uint64_t omega[4], const void *d_instances, const uint32_t *column_lens, uint32_t n_columns,
+                                           const uint32_t *query_columns, const uint32_t *query_rotations, uint32_t n_queries, size_t n_proofs,
+                                           void *d_status, void *d_report, void *stream);
 
 /* ---- parity hooks for the field / curve layer (rows a1/a2 of SURVEY.md section 8) ------------------ */
 /* field: 0 = Fq, 1 = Fr.  op: 0 mul, 1 add, 2 sub, 3 square (b ignored).  Elementwise on n elements.

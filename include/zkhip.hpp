@@ -1402,6 +1402,41 @@ inline IdentityVerdicts verify_identity_device(const RowProgram& identity, const
   if (n_proofs) check(zkhip_download(out.status.data(), d_status, n_proofs * sizeof(int32_t)), "verify_identity_device");
   return out;
 }
+// Instance columns (public inputs): `instances` = [n_proofs][sum of column_lens], `queries` = (instance column, rotation mod 2^k) pairs.
+// out = [queries][n_proofs]: e[q][p] = sum_i v[p][c][i] l_((i - rot) mod n)(x[p]); a point of the domain gets zeros
+inline void instance_evals_device(uint32_t k, const Fr& omega, const DeviceVec& x, const DeviceVec& instances, const std::vector<uint32_t>& column_lens,
+                                  const std::vector<std::pair<uint32_t, uint32_t>>& queries, DeviceVec& out) {
+  size_t total = 0;
+  for (uint32_t len : column_lens) total += len;
+  if (instances.size() < total * x.size() || out.size() < queries.size() * x.size()) throw std::invalid_argument("instance_evals_device: arrays shorter than the batch");
+  std::vector<uint32_t> cols, rots;
+  for (const auto& q : queries) { cols.push_back(q.first); rots.push_back(q.second); }
+  check(zkhip_fr_instance_evals_device(k, omega.l, x.data(), instances.data(), column_lens.data(), (uint32_t)column_lens.size(), cols.data(), rots.data(),
+                                       (uint32_t)queries.size(), x.size(), out.data(), nullptr), "instance_evals_device");
+}
+// verify_identity_device for a circuit with instance columns: query q is column n_evals + 9 + q of `identity`
+inline IdentityVerdicts verify_identity_device(const RowProgram& identity, const DeviceVec& evals, uint32_t n_evals, const DeviceVec& challenges, uint32_t k,
+                                               uint32_t usable_rows, const Fr& omega, const DeviceVec& instances, const std::vector<uint32_t>& column_lens,
+                                               const std::vector<std::pair<uint32_t, uint32_t>>& queries, size_t n_proofs) {
+  size_t total = 0;
+  for (uint32_t len : column_lens) total += len;
+  if (evals.size() < n_proofs * n_evals || challenges.size() < n_proofs * 5 || instances.size() < n_proofs * total)
+    throw std::invalid_argument("verify_identity_device: records shorter than the batch");
+  std::vector<uint32_t> cols, rots;
+  for (const auto& q : queries) { cols.push_back(q.first); rots.push_back(q.second); }
+  IdentityVerdicts out;
+  out.status.assign(n_proofs, 0);
+  const zkhip_vm_program prog = vm_program_of(identity);
+  void* d_status = nullptr;
+  check(zkhip_alloc(n_proofs * sizeof(int32_t) + 16, &d_status), "verify_identity_device");
+  struct release { void* p; ~release() { (void)zkhip_free(p); } } held{d_status};
+  out.report = read_check_reports([&](void* d) {
+    return zkhip_verify_identity_instances_device(&prog, evals.data(), n_evals, challenges.data(), k, usable_rows, omega.l, instances.data(), column_lens.data(),
+                                                  (uint32_t)column_lens.size(), cols.data(), rots.data(), (uint32_t)queries.size(), n_proofs, d_status, d, nullptr); },
+    1, "verify_identity_device")[0];
+  if (n_proofs) check(zkhip_download(out.status.data(), d_status, n_proofs * sizeof(int32_t)), "verify_identity_device");
+  return out;
+}
 // Random field elements drawn in HBM (zkhip.h, "random field elements": element i of stream (seed, stream_id) is one ChaCha20 block reduced mod r).
 // The library holds no entropy: `seed` comes from the caller's generator, and a (seed, stream_id, index) triple is never reused across proofs.
 // out[j] = element first + j for every j < out.size(): the vanishing argument's random polynomial, never on the host

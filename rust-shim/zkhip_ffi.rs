@@ -89,6 +89,14 @@ extern "C" {
                                      stream: *mut c_void) -> c_int;
     fn zkhip_verify_identity_device(prog: *const VmProgram, d_evals: *const c_void, n_evals: u32, d_challenges: *const c_void, k: u32, usable_rows: u32,
                                     omega: *const u64, n_proofs: usize, d_status: *mut c_void, d_report: *mut c_void, stream: *mut c_void) -> c_int;
+    // instance columns (public inputs): evaluated at x omega^rot from the values, never committed or opened (halo2's KZG scheme)
+    fn zkhip_fr_instance_evals_device(k: u32, omega: *const u64, d_x: *const c_void, d_instances: *const c_void, column_lens: *const u32, n_columns: u32,
+                                      query_columns: *const u32, query_rotations: *const u32, n_queries: u32, n_proofs: usize, d_out: *mut c_void,
+                                      stream: *mut c_void) -> c_int;
+    fn zkhip_verify_identity_instances_device(prog: *const VmProgram, d_evals: *const c_void, n_evals: u32, d_challenges: *const c_void, k: u32, usable_rows: u32,
+                                              omega: *const u64, d_instances: *const c_void, column_lens: *const u32, n_columns: u32, query_columns: *const u32,
+                                              query_rotations: *const u32, n_queries: u32, n_proofs: usize, d_status: *mut c_void, d_report: *mut c_void,
+                                              stream: *mut c_void) -> c_int;
     fn zkhip_stream_sync(stream: *mut c_void) -> c_int;
     fn zkhip_fr_eval_polynomial_batch_device(d_polys: *const *const c_void, count: usize, n: usize, point: *const u64, d_out: *mut c_void,
                                              stream: *mut c_void) -> c_int;
@@ -662,6 +670,31 @@ impl DevCols {
         DevCols::check_reports(1, "zkhip_verify_identity_device", |d| unsafe {
             zkhip_verify_identity_device(&ffi, evals, n_evals, challenges, k, usable_rows, omega as *const F as *const u64, n_proofs, status, d,
                                          std::ptr::null_mut()) }).map(|v| v[0])
+    }
+    /// `verify_identity` for a circuit with instance columns: `instances` = [n_proofs][sum of column_lens] public inputs, `queries` = the
+    /// (instance column, rotation mod 2^k) pairs the identity reads, query q as the program's column n_evals + 9 + q
+    pub(crate) fn verify_identity_instances<F: 'static>(prog: &VmProgramOwned, evals: *const c_void, n_evals: u32, challenges: *const c_void, k: u32,
+                                                        usable_rows: u32, omega: &F, instances: *const c_void, column_lens: &[u32], queries: &[(u32, u32)],
+                                                        n_proofs: usize, status: *mut c_void) -> Option<CheckReport> {
+        if !is::<F, Fr>() { return None; }
+        let ffi = prog.as_ffi();
+        let (columns, rotations): (Vec<u32>, Vec<u32>) = queries.iter().copied().unzip();
+        // SAFETY: as `verify_identity`; the three host arrays live until the call returns, which is when the library has consumed them
+        DevCols::check_reports(1, "zkhip_verify_identity_instances_device", |d| unsafe {
+            zkhip_verify_identity_instances_device(&ffi, evals, n_evals, challenges, k, usable_rows, omega as *const F as *const u64, instances,
+                                                   column_lens.as_ptr(), column_lens.len() as u32, columns.as_ptr(), rotations.as_ptr(),
+                                                   queries.len() as u32, n_proofs, status, d, std::ptr::null_mut()) }).map(|v| v[0])
+    }
+    /// the evaluations alone: `out` = [queries][n_proofs] for the points `x`
+    pub(crate) fn instance_evals<F: 'static>(k: u32, omega: &F, x: *const c_void, instances: *const c_void, column_lens: &[u32], queries: &[(u32, u32)],
+                                             n_proofs: usize, out: *mut c_void) -> bool {
+        if !is::<F, Fr>() { return false; }
+        let (columns, rotations): (Vec<u32>, Vec<u32>) = queries.iter().copied().unzip();
+        // SAFETY: the device arrays hold what the sizes say; the host arrays live until the call returns
+        let rc = unsafe { zkhip_fr_instance_evals_device(k, omega as *const F as *const u64, x, instances, column_lens.as_ptr(), column_lens.len() as u32,
+                                                         columns.as_ptr(), rotations.as_ptr(), queries.len() as u32, n_proofs, out, std::ptr::null_mut()) };
+        if rc != 0 { warn_once("zkhip_fr_instance_evals_device", rc); }
+        rc == 0
     }
     /// rows [0, n) of column `col` = elements first .. first + n - 1 of stream (seed, stream_id) (zkhip.h "random field elements"): the vanishing
     /// argument's random polynomial, drawn where it is committed and opened.  `seed` = `random_seed(&mut rng)`, once per proof

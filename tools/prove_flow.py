@@ -100,7 +100,8 @@ def _verify_seeded(pv, params, corrupt_proof, on_proof, lap):
             both = np.stack([Hp_mo, MO._generator_xyz(params)])
             _lib.check(_lib.load().zkhip_g1_sum(both.ctypes.data, 2, moved.ctypes.data))     # H' + G: another curve point
             Hp_mo = moved
-        holds = P.identity_statuses(pv.dpk.vk, pv.k, pv.plan, [[q.eval for q in vqueries]], [(pv.theta, pv.beta, pv.gamma, pv.y, pv.x)])[0] == 0
+        public = [pv.w.instance_values] if pv.cs.num_instance else None       # the instance columns are evaluated from these, inside the identity call
+        holds = P.identity_statuses(pv.dpk.vk, pv.k, pv.plan, [[q.eval for q in vqueries]], [(pv.theta, pv.beta, pv.gamma, pv.y, pv.x)], public)[0] == 0
         ok = bool(holds) and MO.VerifierSHPLONK(params).verify_proof(vqueries, H_mo, Hp_mo, *challenges)
     lap("verify")
     if on_proof is not None and pv.multiopen_proof is not None:
@@ -110,8 +111,14 @@ def _verify_seeded(pv, params, corrupt_proof, on_proof, lap):
 
 
 def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False,
-        sharded_key=False, lookups_one_call=True, device_randomness=False, mock=False, on_witness=None, verify=False, corrupt_proof=None, on_proof=None, transcript=False, multiopen="shplonk"):
-    """mock: what the reference's `gen_proof` does before it proves (`MockProver::run(..).assert_satisfied()`,
+        sharded_key=False, lookups_one_call=True, device_randomness=False, mock=False, on_witness=None, verify=False, corrupt_proof=None, on_proof=None, transcript=False, multiopen="shplonk", instances=0,
+        instance_len=4):
+    """instances: that many instance columns of `instance_len` public values each (prover.halo2_lib_witness ties every one to a gate input by a
+    copy constraint): the mock step checks the witness against them, the prover absorbs them into the transcript behind the key and carries
+    their columns through the permutation argument and the quotient without committing or opening them, and the verify step hands the values
+    to the verifier, which evaluates the columns at x from them (zkhip_verify_identity_instances_device); the result gains `instances`, the
+    values as integers.  corrupt="instance" breaks the copy constraint of the first public value.  With instances=0 nothing of this runs.
+    mock: what the reference's `gen_proof` does before it proves (`MockProver::run(..).assert_satisfied()`,
     /root/reference/aggregator/src/wrapper.rs:117-123), over the columns where they lie: `mock.MockProver(..).assert_satisfied()` once the
     witness columns and the copy constraints exist, as lap `mock_prover` (not part of `prove_ms`).  A witness broken with `corrupt=` then raises
     an AssertionError that says where -- ("gate", gate, polynomial, row, rows) / ("copy", column, row, cells) / ("lookup", lookup, row, rows) --
@@ -172,14 +179,14 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
     params = Z.ParamsKZG.setup(k, seeded.s)
     lap("setup_srs")
     try:
-        w = P.halo2_lib_witness(k, gate_cols, lookups, blinding, lookup_bits, corrupt)
+        w = P.halo2_lib_witness(k, gate_cols, lookups, blinding, lookup_bits, corrupt, instances, instance_len)
         pv = P.Prover(params, w, blinding, batched, lap, multiopen)
         lap("witness_columns")
         pv.commit_advice()
         if mock:
             from zksnap_circuits_halo2_amd import mock as MK
 
-            with MK.MockProver(w.cs, k, w.fixed, w.advice, (), w.assembly, theta=seeded.theta()) as mock_prover:
+            with MK.MockProver(w.cs, k, w.fixed, w.advice, w.instance, w.assembly, theta=seeded.theta()) as mock_prover:
                 mock_prover.assert_satisfied()
             lap("mock_prover")
         if on_witness is not None:
@@ -201,6 +208,8 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
                "program_insns": pv.program_insns, "program_registers": pv.program_registers, "h_commitments": [P.affine(c) for c in pv.h_commit],
                "keygen_ms": None, "pk_file_bytes": pk_bytes,
                "vanishing_random_commitment": P.affine(pv.commitments[("random", 0)]) if device_randomness else None}
+        if instances:
+            res["instances"] = public = [list(column) for column in w.instance_values]
         if transcript:
             res.update(proof=pv.proof, proof_bytes=len(pv.proof), proof_plan=pv.plan, proof_shape=shape)
         proved, batched, ek = pv.multiopen_proof is not None, pv.batched, pv.dom.extended_k
@@ -216,7 +225,10 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
                 if byte_flip:
                     checked[corrupt_proof[1]] ^= 1
                 how = () if (tr_hash, multiopen) == ("blake2b", "shplonk") else (tr_hash, multiopen)      # the verifier's defaults
-                proof_verifies = verify_transcript_proof(params, vk, k, bytes(checked), dict(shape), list(res["proof_plan"]), *how)
+                if instances:
+                    proof_verifies = verify_transcript_proof(params, vk, k, bytes(checked), dict(shape), list(res["proof_plan"]), *how, instances=public)
+                else:
+                    proof_verifies = verify_transcript_proof(params, vk, k, bytes(checked), dict(shape), list(res["proof_plan"]), *how)
             lap("verify")
         if verify:
             checks["proof_verifies"] = proof_verifies

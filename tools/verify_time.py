@@ -14,7 +14,11 @@ timed region ends with the verdict on the host.
       printed beside it), a timed region is the call and the statuses and the report back on the host
   the `verify` lap of the transcript flow with the identity and without it -- the openings alone are what the verifier was before the identity was
       added --, the two sides in turn in this one process
-    python tools/verify_time.py [--reps 9] [--shapes 22:4:1,13:256:8,15:64:8] [--no-pairing] [--no-flow] [--no-srs] [--no-identity]"""
+  the identity call with and without ONE instance column of 30 public values (zkhip_verify_identity_instances_device against
+      zkhip_verify_identity_device on the same records), the repetitions of the two alternating, a second series of the call without as the A/A
+      figure; beside it the host path a caller had before the device evaluated instance columns: the same evaluations on Python integers with
+      one batched inversion per proof, and their upload
+    python tools/verify_time.py [--reps 9] [--shapes 22:4:1,13:256:8,15:64:8] [--no-pairing] [--no-flow] [--no-srs] [--no-identity] [--no-instances]"""
 import argparse
 import os
 import statistics
@@ -38,6 +42,8 @@ ap.add_argument("--srs-k", type=int, default=22)
 ap.add_argument("--no-pairing", action="store_true")
 ap.add_argument("--no-identity", action="store_true")
 ap.add_argument("--batches", default="1,64,4096")
+ap.add_argument("--no-instances", action="store_true")
+ap.add_argument("--instance-len", type=int, default=30)
 args = ap.parse_args()
 lib = _lib.load()
 R = O.R_MOD
@@ -152,15 +158,16 @@ if not args.no_flow:
             laps.append((res["timings_ms"]["verify"], res["prove_ms"]))
         print("    flow, three warm proofs: verify lap / prove_ms = " + ", ".join(f"{a:.1f} / {b:.1f}" for a, b in laps))
 
+def random_elements(*shape):
+    a = torch.randint(-(1 << 63), (1 << 63) - 1, shape + (4,), dtype=torch.int64, device="cuda")
+    a[..., 3] = torch.randint(0, 1 << 61, shape, dtype=torch.int64, device="cuda")          # below r: canonical words
+    return a
+
+
 # ---- the quotient identity at x: the call on its own, and the flow's verify lap with and without it ------------------------------------------------
 if not args.no_identity:
     import prove_flow
     from zksnap_circuits_halo2_amd import evaluation as E, prover as P
-
-    def random_elements(*shape):
-        a = torch.randint(-(1 << 63), (1 << 63) - 1, shape + (4,), dtype=torch.int64, device="cuda")
-        a[..., 3] = torch.randint(0, 1 << 61, shape, dtype=torch.int64, device="cuda")          # below r: canonical words
-        return a
 
     for shape in args.shapes.split(","):
         k, g, l = (int(x) for x in shape.split(":"))
@@ -196,3 +203,58 @@ if not args.no_identity:
                 prove_flow.verify_transcript_proof = with_identity
             for name, ts in laps.items():
                 print(f"    transcript flow, verify lap, {name:22s}      {fmt(ts)}   (three proofs; every run makes its key anew, so every lap compiles and marshals the identity once)")
+
+# ---- instance columns: what the identity call pays for evaluating one on the device, against the host path -----------------------------------------
+if not args.no_instances:
+    import random
+
+    from zksnap_circuits_halo2_amd import evaluation as E, prover as P
+
+    def host_instance_evals(k, xs, values, length):
+        """e[p] = sum_i v[p][i] l_i(x_p) on Python integers: the denominators x_p - omega^i of a proof share one inversion (Montgomery's trick)"""
+        n, w = 1 << k, [pow(F.omega_for(k), i, R) for i in range(length)]
+        n_inv, out = pow(n, R - 2, R), []
+        for x, v in zip(xs, values):
+            den, run = [(x - wi) % R for wi in w], [1]
+            for d in den:
+                run.append(run[-1] * d % R)
+            inv, acc = pow(run[-1], R - 2, R), 0
+            for i in range(length - 1, -1, -1):
+                acc = (acc + v[i] * w[i] % R * (inv * run[i] % R)) % R
+                inv = inv * den[i] % R
+            out.append(acc * (pow(x, n, R) - 1) % R * n_inv % R)
+        return out
+
+    length = args.instance_len
+    for shape in args.shapes.split(","):
+        k, g, l = (int(x) for x in shape.split(":"))
+        plain_cs, cs = E.halo2_lib_shape(g, l), E.halo2_lib_shape(g, l, instances=1)
+        u = (1 << k) - (cs.blinding_factors + 1)
+        plain_plan, plan = P.opening_plan(plain_cs, g, l, u, False, "halo2"), P.opening_plan(cs, g, l, u, False, "halo2")
+        queries = E.instance_queries(cs)
+        plain_prog, prog = E.identity_program(plain_cs, plain_plan, k)._marshal(), E.identity_program(cs, plan, k, instance_queries=queries)._marshal()
+        print(f"==== identity at x with one instance column of {length} values, shape k = {k}, {g} gate columns, {l} lookups: {len(plain_plan)} / {len(plan)} evaluations "
+              f"without / with ({args.reps} alternating repetitions, wall ms, medians) ====")
+        rng = random.Random(k)
+        for B in (int(b) for b in args.batches.split(",")):
+            plain_evals, evals, challenges, instances = random_elements(B, len(plain_plan)), random_elements(B, len(plan)), random_elements(B, 5), random_elements(B, length)
+            xs, values = [rng.randrange(R) for _ in range(B)], [[rng.randrange(R) for _ in range(length)] for _ in range(B)]
+            without = lambda: E.verify_identity_device(plain_prog, plain_evals, challenges, k, u)
+            with_column = lambda: E.verify_identity_device(prog, evals, challenges, k, u, instances=instances, column_lens=[length], queries=queries)
+            def host():
+                e = host_instance_evals(k, xs, values, length)
+                torch.from_numpy(F.fr_encode(e).view(np.int64)).cuda()
+                torch.cuda.synchronize()
+            series = {"without": [], "with": [], "without (A/A)": [], "host": []}
+            timed(with_column, reps=1)                                     # clocks and scratch warm
+            for _ in range(args.reps):
+                for name, fn in (("without", without), ("with", with_column), ("without (A/A)", without), ("host", host)):
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    fn()
+                    series[name].append((time.perf_counter() - t) * 1e3)
+            med = {name: statistics.median(ts) for name, ts in series.items()}
+            for name, ts in series.items():
+                print(f"    B = {B:5d}  {name:15s}                              {fmt(ts)}")
+            print(f"    B = {B:5d}  added by the column on the device {med['with'] - med['without']:+.3f} ms (A/A {med['without (A/A)'] - med['without']:+.3f} ms); "
+                  f"host integers + upload {med['host']:.3f} ms")

@@ -1928,27 +1928,75 @@ int zkhip_fr_domain_points_device(uint32_t k, uint32_t usable_rows, const uint64
   return fr_domain_points_device(k, usable_rows, omega, (const uint32_t*)d_x, n_points, (uint32_t*)d_out, caller_stream(stream));
 }
 
-int zkhip_verify_identity_device(const zkhip_vm_program* prog, const void* d_evals, uint32_t n_evals, const void* d_challenges, uint32_t k, uint32_t usable_rows,
-                                 const uint64_t omega[4], size_t n_proofs, void* d_status, void* d_report, void* stream) {
-  ZK_API_RANGE();
-  if (n_evals == 0) { set_error("verify_identity: no evaluations"); return ZKHIP_EINVAL; }
-  int rc = verify_identity_validate(prog, n_evals);
-  if (rc != ZKHIP_OK) return rc;
-  if ((rc = identity_domain_validate("verify_identity", k, usable_rows, omega)) != ZKHIP_OK) return rc;
-  if (n_proofs > ((size_t)1 << 24)) { set_error("verify_identity: %zu proofs in one call", n_proofs); return ZKHIP_EINVAL; }
-  const bool arrays_ok = elems_ptr_ok(d_evals) && elems_ptr_ok(d_challenges) && d_status && ((uintptr_t)d_status & 3u) == 0;
+// the identity with `lay` resolved (n_queries = 0: no instance columns); `who` names the call in the error text
+static int verify_identity_call(const char* who, const zkhip_vm_program* prog, const void* d_evals, uint32_t n_evals, const void* d_challenges, uint32_t k,
+                                uint32_t usable_rows, const uint64_t omega[4], const void* d_instances, const instance_layout& lay, size_t n_proofs, void* d_status,
+                                void* d_report, void* stream) {
+  int rc;
+  if (n_proofs > ((size_t)1 << 24)) { set_error("%s: %zu proofs in one call", who, n_proofs); return ZKHIP_EINVAL; }
+  const bool arrays_ok = elems_ptr_ok(d_evals) && elems_ptr_ok(d_challenges) && d_status && ((uintptr_t)d_status & 3u) == 0 &&
+                         (lay.total_len == 0 || elems_ptr_ok(d_instances));
   if (!report_ptr_ok(d_report) || (n_proofs && !arrays_ok)) {      // (an empty batch names no array)
-    set_error("verify_identity: null or misaligned pointer");
+    set_error("%s: null or misaligned pointer", who);
     return ZKHIP_EINVAL;
   }
   guard_t g(g_mu);
   if ((rc = ensure_init()) != ZKHIP_OK) return rc;
   hipStream_t s = caller_stream(stream);
   scratch* sc = scratch_for(primary(), s);
-  if (n_proofs && (rc = sc->poly2.reserve(verify_identity_columns_bytes(n_evals, n_proofs))) != ZKHIP_OK) return rc;
-  if (n_proofs && (rc = sc->vm.reserve(verify_identity_vm_bytes(prog, n_evals))) != ZKHIP_OK) return rc;
-  return verify_identity_device(prog, (const uint32_t*)d_evals, n_evals, (const uint32_t*)d_challenges, k, usable_rows, omega, n_proofs, (int32_t*)d_status, d_report,
-                                sc->poly2.p, sc->vm.p, sc->vm.cap, s, &sc->vm_stage);
+  if (n_proofs && (rc = sc->poly2.reserve(verify_identity_columns_bytes(n_evals, lay.n_queries, n_proofs))) != ZKHIP_OK) return rc;
+  if (n_proofs && (rc = sc->vm.reserve(verify_identity_vm_bytes(prog, n_evals, lay.n_queries))) != ZKHIP_OK) return rc;
+  return verify_identity_device(prog, (const uint32_t*)d_evals, n_evals, (const uint32_t*)d_challenges, k, usable_rows, omega, (const uint32_t*)d_instances, lay, n_proofs,
+                                (int32_t*)d_status, d_report, sc->poly2.p, sc->vm.p, sc->vm.cap, s, &sc->vm_stage);
+}
+
+int zkhip_verify_identity_device(const zkhip_vm_program* prog, const void* d_evals, uint32_t n_evals, const void* d_challenges, uint32_t k, uint32_t usable_rows,
+                                 const uint64_t omega[4], size_t n_proofs, void* d_status, void* d_report, void* stream) {
+  ZK_API_RANGE();
+  if (n_evals == 0) { set_error("verify_identity: no evaluations"); return ZKHIP_EINVAL; }
+  int rc = verify_identity_validate(prog, n_evals, 0);
+  if (rc != ZKHIP_OK) return rc;
+  if ((rc = identity_domain_validate("verify_identity", k, usable_rows, omega)) != ZKHIP_OK) return rc;
+  return verify_identity_call("verify_identity", prog, d_evals, n_evals, d_challenges, k, usable_rows, omega, nullptr, instance_layout(), n_proofs, d_status, d_report, stream);
+}
+
+int zkhip_verify_identity_instances_device(const zkhip_vm_program* prog, const void* d_evals, uint32_t n_evals, const void* d_challenges, uint32_t k, uint32_t usable_rows,
+                                           const uint64_t omega[4], const void* d_instances, const uint32_t* column_lens, uint32_t n_columns,
+                                           const uint32_t* query_columns, const uint32_t* query_rotations, uint32_t n_queries, size_t n_proofs, void* d_status,
+                                           void* d_report, void* stream) {
+  ZK_API_RANGE();
+  const char* who = "verify_identity_instances";
+  if (n_evals == 0) { set_error("%s: no evaluations", who); return ZKHIP_EINVAL; }
+  if (n_columns > INSTANCE_MAX_QUERIES || n_queries > INSTANCE_MAX_QUERIES) {
+    set_error("%s: %u instance columns, %u queries: at most %u of each", who, n_columns, n_queries, INSTANCE_MAX_QUERIES);
+    return ZKHIP_EINVAL;
+  }
+  int rc = verify_identity_validate(prog, n_evals, n_queries);
+  if (rc != ZKHIP_OK) return rc;
+  if ((rc = identity_domain_validate(who, k, usable_rows, omega)) != ZKHIP_OK) return rc;
+  instance_layout lay;                                             // the three host arrays are consumed here
+  if ((rc = instance_queries_validate(who, k, usable_rows, "usable_rows", column_lens, n_columns, query_columns, query_rotations, n_queries, &lay)) != ZKHIP_OK) return rc;
+  return verify_identity_call(who, prog, d_evals, n_evals, d_challenges, k, usable_rows, omega, d_instances, lay, n_proofs, d_status, d_report, stream);
+}
+
+int zkhip_fr_instance_evals_device(uint32_t k, const uint64_t omega[4], const void* d_x, const void* d_instances, const uint32_t* column_lens, uint32_t n_columns,
+                                   const uint32_t* query_columns, const uint32_t* query_rotations, uint32_t n_queries, size_t n_proofs, void* d_out, void* stream) {
+  ZK_API_RANGE();
+  const char* who = "fr_instance_evals";
+  if (k < 1) { set_error("%s: k = 0", who); return ZKHIP_EINVAL; }
+  int rc = identity_domain_validate(who, k, k <= 28 ? ((uint64_t)1 << k) - 1 : 1, omega);      // k and omega; the call has no usable_rows: 2^k - 1 is valid for every k
+  if (rc != ZKHIP_OK) return rc;
+  instance_layout lay;
+  if ((rc = instance_queries_validate(who, k, (uint64_t)1 << k, "2^k", column_lens, n_columns, query_columns, query_rotations, n_queries, &lay)) != ZKHIP_OK) return rc;
+  if (n_proofs > ((size_t)1 << 24)) { set_error("%s: %zu proofs in one call", who, n_proofs); return ZKHIP_EINVAL; }
+  if (n_proofs && ((n_queries && (!elems_ptr_ok(d_x) || !elems_ptr_ok(d_out))) || (lay.total_len && !elems_ptr_ok(d_instances)))) {
+    set_error("%s: null or misaligned pointer", who);
+    return ZKHIP_EINVAL;
+  }
+  if (n_proofs == 0 || n_queries == 0) return ZKHIP_OK;            // nothing to write
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  return fr_instance_evals_device(k, omega, (const uint32_t*)d_x, (const uint32_t*)d_instances, lay, n_proofs, (uint32_t*)d_out, caller_stream(stream));
 }
 
 int zkhip_lookup_permute(const uint64_t* input, const uint64_t* table, size_t usable_rows, uint64_t* permuted_input, uint64_t* permuted_table) {

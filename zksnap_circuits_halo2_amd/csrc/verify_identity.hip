@@ -21,6 +21,7 @@
 #include "check_report.hpp"
 #include "fr_vec.hpp"
 #include "identity_points.hpp"
+#include "instance_evals.hpp"
 #include "zkhip_internal.hpp"
 
 namespace zkhip {
@@ -114,6 +115,74 @@ __global__ void __launch_bounds__(64) k_domain_points(const uint32_t* __restrict
   id_store_ext(out + (3 * n_points + i) * 8, v.l_active);
 }
 
+// ---- instance columns: e[q][p] for every (query, proof) pair (instance_evals.hpp) ----------------------------------------------------------------
+// A group of IE_GROUP lanes per pair, pairs in the order of the output ([query][proof]): the lanes of a group read consecutive 32-byte elements of
+// one proof's public inputs per step, the first lanes of consecutive groups write consecutive elements of one output column.  A group never
+// leaves its 16-lane row, and the joins exchange nine limbs per fraction half with __shfl_xor at distances 1 and 2 (4 and 8 as well in a group of
+// 16).  The gfx950 build lowers them to ds_bpermute_b32 -- 36 of the kernel's ~7700 instructions, through the LDS crossbar with no LDS allocated --
+// so a hand-written DPP exchange has nothing to win here.  Every lane of a group reaches the joins: a lane with no term carries 0 / 1.
+// The group size is a build-time constant, 4 by measurement (profiles/r28_instance_columns.txt: at 4096 proofs of 30 / 70 values 0.093 / 0.116 ms
+// a call against 0.159 / 0.281 ms with 1 lane and 0.237 / 0.241 ms with 16; at one proof 0.091 ms against 0.085 .. 0.094 ms with 16, inside the
+// spread of two series of the same build, and 0.172 ms with 1).  -DZKHIP_INSTANCE_GROUP=1|4|16 builds the others for that measurement; nothing
+// reads it at run time.
+#ifndef ZKHIP_INSTANCE_GROUP
+#define ZKHIP_INSTANCE_GROUP 4
+#endif
+constexpr uint32_t IE_GROUP = ZKHIP_INSTANCE_GROUP;
+constexpr uint32_t IE_THREADS = 256;
+static_assert(IE_GROUP == 1 || IE_GROUP == 4 || IE_GROUP == 16, "a lane group is 1, 4 or 16 lanes: it stays inside one 16-lane row");
+
+struct instance_query_table {                            // by value: per query, where its column lies in a proof's inputs and how it is rotated
+  uint32_t offset[INSTANCE_MAX_QUERIES], len[INSTANCE_MAX_QUERIES], rot[INSTANCE_MAX_QUERIES];
+};
+
+struct instance_domain {
+  fe_arg omega, omega_g, n_inv;                          // omega_g = omega^IE_GROUP
+  uint32_t k;
+};
+
+__device__ __forceinline__ fe ie_shfl_xor(const fe& a, int mask) {
+  fe r;
+#pragma unroll
+  for (int i = 0; i < NL; i++) r.l[i] = (uint32_t)__shfl_xor((int)a.l[i], mask, 64);
+  return r;
+}
+
+__device__ __forceinline__ fe ie_arg(const fe_arg& c) {
+  uint32_t w[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) w[i] = c.w[i];
+  return fe_from_ext_lazy(w);
+}
+
+// x of proof p: x[p * x_stride] words (a plain array of points, or the fifth challenge of every record)
+__global__ void __launch_bounds__(IE_THREADS) k_instance_evals(const uint32_t* __restrict__ x, uint32_t x_stride, const uint32_t* __restrict__ instances,
+                                                               uint64_t total_len, const instance_query_table qt, uint32_t n_queries, uint64_t n_proofs,
+                                                               const instance_domain dom, uint32_t* __restrict__ out) {
+  const uint64_t pair = ((uint64_t)blockIdx.x * IE_THREADS + threadIdx.x) / IE_GROUP;
+  const uint32_t g = threadIdx.x % IE_GROUP;
+  if (pair >= (uint64_t)n_queries * n_proofs) return;    // a whole group at a time: the lanes of a join are all here
+  const uint32_t q = (uint32_t)(pair / n_proofs);
+  const uint64_t p = pair % n_proofs;
+  uint32_t xw[8];
+  load_words(x + p * x_stride, xw);
+  const fe xv = fe_from_ext_lazy(xw);
+  const uint32_t* column = instances + (p * total_len + qt.offset[q]) * 8;
+  ie_fraction f = ie_lane<Fr>(xv, dom.k, ie_arg(dom.omega), ie_arg(dom.omega_g), qt.rot[q], qt.len[q], g, IE_GROUP, [&](uint32_t i) {
+    uint32_t vw[8];
+    load_words(column + (uint64_t)i * 8, vw);
+    return fe_from_ext_lazy(vw);
+  });
+#pragma unroll
+  for (uint32_t d = 1; d < IE_GROUP; d <<= 1) {
+    ie_fraction other;
+    other.num = ie_shfl_xor(f.num, (int)d);
+    other.den = ie_shfl_xor(f.den, (int)d);
+    f = ie_join<Fr>(f, other);
+  }
+  if (g == 0) id_store_ext(out + pair * 8, ie_finish<Fr>(f, xv, dom.k, ie_arg(dom.n_inv)));
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
 static bool id_canonical(const uint64_t* w) {
   static const uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
@@ -155,10 +224,13 @@ int fr_domain_points_device(uint32_t k, uint32_t usable_rows, const uint64_t* om
   return ZKHIP_OK;
 }
 
-int verify_identity_validate(const zkhip_vm_program* p, uint32_t n_evals) {
+int verify_identity_validate(const zkhip_vm_program* p, uint32_t n_evals, uint32_t n_queries) {
   if (!p) { set_error("verify_identity: null program"); return ZKHIP_EINVAL; }
-  if ((uint64_t)n_evals + ID_DERIVED > 65536) { set_error("verify_identity: %u evaluations + %u derived columns exceed 65536", n_evals, ID_DERIVED); return ZKHIP_EINVAL; }
-  const int rc = row_vm_validate(p, n_evals + ID_DERIVED, 0, 0);      // every column below n_evals + 9, every index inside its table
+  if ((uint64_t)n_evals + ID_DERIVED + n_queries > 65536) {
+    set_error("verify_identity: %u evaluations + %u derived and instance columns exceed 65536", n_evals, ID_DERIVED + n_queries);
+    return ZKHIP_EINVAL;
+  }
+  const int rc = row_vm_validate(p, n_evals + ID_DERIVED + n_queries, 0, 0);      // every column below n_evals + 9 + n_queries, every index inside its table
   if (rc != ZKHIP_OK) return rc;
   // the rotation TABLE, named by an instruction or not: the window launch sizes its halos by every entry
   for (uint32_t i = 0; i < p->n_rotations; i++)
@@ -176,18 +248,77 @@ int verify_identity_validate(const zkhip_vm_program* p, uint32_t n_evals) {
   return ZKHIP_OK;
 }
 
-size_t verify_identity_columns_bytes(uint32_t n_evals, uint64_t n_proofs) {
-  return ((size_t)n_evals + ID_DERIVED + 1) * n_proofs * 32 + n_proofs * 4;      // the columns, the result column, the flags
+size_t verify_identity_columns_bytes(uint32_t n_evals, uint32_t n_queries, uint64_t n_proofs) {
+  return ((size_t)n_evals + ID_DERIVED + n_queries + 1) * n_proofs * 32 + n_proofs * 4;      // the columns, the result column, the flags
 }
 
-size_t verify_identity_vm_bytes(const zkhip_vm_program* p, uint32_t n_evals) { return row_vm_workspace_bytes(p, n_evals + ID_DERIVED, 0); }
+size_t verify_identity_vm_bytes(const zkhip_vm_program* p, uint32_t n_evals, uint32_t n_queries) {
+  return row_vm_workspace_bytes(p, n_evals + ID_DERIVED + n_queries, 0);
+}
+
+int instance_queries_validate(const char* who, uint32_t k, uint64_t max_len, const char* max_name, const uint32_t* column_lens, uint32_t n_columns,
+                              const uint32_t* query_columns, const uint32_t* query_rotations, uint32_t n_queries, instance_layout* out) {
+  if (n_columns > INSTANCE_MAX_QUERIES || n_queries > INSTANCE_MAX_QUERIES) {
+    set_error("%s: %u instance columns, %u queries: at most %u of each", who, n_columns, n_queries, INSTANCE_MAX_QUERIES);
+    return ZKHIP_EINVAL;
+  }
+  if ((n_columns && !column_lens) || (n_queries && (!query_columns || !query_rotations))) { set_error("%s: null instance column or query array", who); return ZKHIP_EINVAL; }
+  if (k > 28) { set_error("%s: k = %u > 28", who, k); return ZKHIP_EINVAL; }
+  uint64_t offsets[INSTANCE_MAX_QUERIES], total = 0;
+  for (uint32_t c = 0; c < n_columns; c++) {
+    if (column_lens[c] > max_len) { set_error("%s: instance column %u holds %u values, more than %s = %llu", who, c, column_lens[c], max_name, (unsigned long long)max_len); return ZKHIP_EINVAL; }
+    offsets[c] = total;
+    total += column_lens[c];
+  }
+  out->total_len = total;
+  out->n_queries = n_queries;
+  for (uint32_t q = 0; q < n_queries; q++) {
+    if (query_columns[q] >= n_columns) { set_error("%s: query %u names instance column %u of %u", who, q, query_columns[q], n_columns); return ZKHIP_EINVAL; }
+    if (query_rotations[q] >= ((uint64_t)1 << k)) { set_error("%s: query %u: rotation %u is not reduced mod 2^%u", who, q, query_rotations[q], k); return ZKHIP_EINVAL; }
+    out->offset[q] = (uint32_t)offsets[query_columns[q]];      // (64 columns of at most 2^28 values: below 2^34 ... checked next)
+    out->len[q] = column_lens[query_columns[q]];
+    out->rot[q] = query_rotations[q];
+  }
+  if (total > 0xffffffffull) { set_error("%s: %llu public inputs per proof", who, (unsigned long long)total); return ZKHIP_EINVAL; }
+  return ZKHIP_OK;
+}
+
+static instance_domain ie_make_domain(uint32_t k, const uint64_t* omega) {
+  const identity_domain base = id_make_domain(k, 0, omega);
+  instance_domain d;
+  d.omega = base.omega;
+  d.n_inv = base.n_inv;
+  d.k = k;
+  uint32_t w[8];
+  std::memcpy(w, omega, 32);
+  fe_to_ext<Fr>(ip_pow<Fr>(fe_mul<Fr>(fe_one<Fr>(), fe_from_ext_lazy(w)), IE_GROUP), d.omega_g.w);
+  return d;
+}
+
+static int instance_evals_launch(const instance_domain& dom, const uint32_t* d_x, uint32_t x_stride, const uint32_t* d_instances, const instance_layout& lay,
+                                 uint64_t n_proofs, uint32_t* d_out, hipStream_t stream) {
+  instance_query_table qt;
+  std::memset(&qt, 0, sizeof qt);
+  for (uint32_t q = 0; q < lay.n_queries; q++) { qt.offset[q] = lay.offset[q]; qt.len[q] = lay.len[q]; qt.rot[q] = lay.rot[q]; }
+  const uint64_t lanes = (uint64_t)lay.n_queries * n_proofs * IE_GROUP;
+  hipLaunchKernelGGL(k_instance_evals, dim3((unsigned)((lanes + IE_THREADS - 1) / IE_THREADS)), dim3(IE_THREADS), 0, stream, d_x, x_stride, d_instances,
+                     lay.total_len, qt, lay.n_queries, n_proofs, dom, d_out);
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
+}
+
+int fr_instance_evals_device(uint32_t k, const uint64_t* omega, const uint32_t* d_x, const uint32_t* d_instances, const instance_layout& lay, uint64_t n_proofs,
+                             uint32_t* d_out, hipStream_t stream) {
+  if (lay.n_queries == 0 || n_proofs == 0) return ZKHIP_OK;
+  return instance_evals_launch(ie_make_domain(k, omega), d_x, 8, d_instances, lay, n_proofs, d_out, stream);
+}
 
 int verify_identity_device(const zkhip_vm_program* prog, const uint32_t* d_evals, uint32_t n_evals, const uint32_t* d_challenges, uint32_t k, uint32_t usable_rows,
-                           const uint64_t* omega, uint64_t n_proofs, int32_t* d_status, void* d_report, void* cols_ws, void* vm_ws, size_t vm_ws_bytes,
-                           hipStream_t stream, vm_staging* staging) {
+                           const uint64_t* omega, const uint32_t* d_instances, const instance_layout& lay, uint64_t n_proofs, int32_t* d_status, void* d_report,
+                           void* cols_ws, void* vm_ws, size_t vm_ws_bytes, hipStream_t stream, vm_staging* staging) {
   int rc = check_reports_init_device(d_report, 1, stream);
   if (rc != ZKHIP_OK || n_proofs == 0) return rc;
-  const uint32_t n_columns = n_evals + ID_DERIVED;
+  const uint32_t n_columns = n_evals + ID_DERIVED + lay.n_queries;
   uint32_t* cols = (uint32_t*)cols_ws;
   uint32_t* result = cols + (size_t)n_columns * n_proofs * 8;
   uint32_t* flags = result + n_proofs * 8;
@@ -196,6 +327,9 @@ int verify_identity_device(const zkhip_vm_program* prog, const uint32_t* d_evals
   hipLaunchKernelGGL(k_identity_columns, dim3((unsigned)((n_proofs + ID_TILE - 1) / ID_TILE), eval_tiles + 1), dim3(ID_THREADS), 0, stream, (const uint4*)d_evals,
                      n_evals, d_challenges, n_proofs, dom, (uint4*)cols, flags, eval_tiles);
   HIPCHK(hipGetLastError());
+  // the instance columns behind the derived ones, x read from the records (the fifth challenge)
+  if (lay.n_queries && (rc = instance_evals_launch(ie_make_domain(k, omega), d_challenges + 4 * 8, 5 * 8, d_instances, lay, n_proofs,
+                                                   cols + (size_t)(n_evals + ID_DERIVED) * n_proofs * 8, stream)) != ZKHIP_OK) return rc;
   std::vector<const void*> columns(n_columns);
   for (uint32_t c = 0; c < n_columns; c++) columns[c] = cols + (size_t)c * n_proofs * 8;
   if ((rc = row_vm_rows_device(prog, columns.data(), n_columns, n_proofs, result, vm_ws, vm_ws_bytes, stream, staging)) != ZKHIP_OK) return rc;

@@ -296,12 +296,25 @@ int plume_sign_device(const h2c_prefix& pre, const uint64_t* d_sk, const uint64_
 // verify_identity.hip (include/zkhip.h, "the quotient identity at x").  The two validators touch no device; `who` names the call in the error text.
 int identity_domain_validate(const char* who, uint32_t k, uint64_t usable_rows, const uint64_t* omega);
 int fr_domain_points_device(uint32_t k, uint32_t usable_rows, const uint64_t* omega, const uint32_t* d_x, uint64_t n_points, uint32_t* d_out, hipStream_t stream);
-int verify_identity_validate(const zkhip_vm_program* p, uint32_t n_evals);
-size_t verify_identity_columns_bytes(uint32_t n_evals, uint64_t n_proofs);      // cols_ws: the column-major image, the result column, the in-domain flags
-size_t verify_identity_vm_bytes(const zkhip_vm_program* p, uint32_t n_evals);   // vm_ws: the interpreter's workspace
+// Instance columns: `instance_layout` is the host arrays of a call, validated and resolved per query (offset of the query's column in a proof's
+// public inputs, its length, its rotation mod 2^k); an empty layout (n_queries = 0) is the identity without instance columns.
+constexpr uint32_t INSTANCE_MAX_QUERIES = 64;
+struct instance_layout {
+  uint64_t total_len = 0;
+  uint32_t n_queries = 0;
+  uint32_t offset[INSTANCE_MAX_QUERIES], len[INSTANCE_MAX_QUERIES], rot[INSTANCE_MAX_QUERIES];
+};
+// every column_lens[c] <= max_len (`max_name` says what that is in the error text), every query inside its tables
+int instance_queries_validate(const char* who, uint32_t k, uint64_t max_len, const char* max_name, const uint32_t* column_lens, uint32_t n_columns,
+                              const uint32_t* query_columns, const uint32_t* query_rotations, uint32_t n_queries, instance_layout* out);
+int fr_instance_evals_device(uint32_t k, const uint64_t* omega, const uint32_t* d_x, const uint32_t* d_instances, const instance_layout& lay, uint64_t n_proofs,
+                             uint32_t* d_out, hipStream_t stream);
+int verify_identity_validate(const zkhip_vm_program* p, uint32_t n_evals, uint32_t n_queries);
+size_t verify_identity_columns_bytes(uint32_t n_evals, uint32_t n_queries, uint64_t n_proofs);      // cols_ws: the column-major image, the result column, the in-domain flags
+size_t verify_identity_vm_bytes(const zkhip_vm_program* p, uint32_t n_evals, uint32_t n_queries);   // vm_ws: the interpreter's workspace
 int verify_identity_device(const zkhip_vm_program* prog, const uint32_t* d_evals, uint32_t n_evals, const uint32_t* d_challenges, uint32_t k, uint32_t usable_rows,
-                           const uint64_t* omega, uint64_t n_proofs, int32_t* d_status, void* d_report, void* cols_ws, void* vm_ws, size_t vm_ws_bytes,
-                           hipStream_t stream, vm_staging* staging = nullptr);
+                           const uint64_t* omega, const uint32_t* d_instances, const instance_layout& lay, uint64_t n_proofs, int32_t* d_status, void* d_report,
+                           void* cols_ws, void* vm_ws, size_t vm_ws_bytes, hipStream_t stream, vm_staging* staging = nullptr);
 
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);

@@ -10,7 +10,7 @@ libzkhip.so; there is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -474,15 +474,19 @@ class _IdentityGraph(Graph):
     """A Graph whose `col(quotient column, rotation)` is the plan's slot of that opening: the terms of `_evaluate_h_terms` name the prover's
     columns, the verifier holds one evaluation per opened (kind, index, rotation) triple.  l_0 / l_last / l_active are the derived columns."""
 
-    def __init__(self, cs: ConstraintSystem, plan, k: int):
+    def __init__(self, cs: ConstraintSystem, plan, k: int, instance_queries=()):
         super().__init__()
         qc = quotient_columns(cs)
         self.n, self.n_evals = 1 << k, len(plan)
+        self.instance_slot: Dict[Tuple[int, int], int] = {}
+        for i, (c, rot) in enumerate(instance_queries):
+            self.instance_slot.setdefault((c, rot % self.n), self.n_evals + IDENTITY_DERIVED + i)
         self.slot: Dict[Tuple[str, int, int], int] = {}
         for i, (kind, idx, rot) in enumerate(plan):
             self.slot.setdefault((kind, idx, rot % self.n), i)
         self.kind_of = {qc.fixed + i: ("fixed", i) for i in range(cs.num_fixed)}
         self.kind_of.update({qc.advice + i: ("advice", i) for i in range(cs.num_advice)})
+        self.kind_of.update({qc.instance + i: ("instance", i) for i in range(cs.num_instance)})
         self.kind_of.update({qc.sigma + i: ("sigma", i) for i in range(len(cs.permutation_columns))})
         self.kind_of.update({qc.perm_product + i: ("perm", i) for i in range(cs.num_permutation_sets)})
         for li in range(len(cs.lookups)):
@@ -493,6 +497,10 @@ class _IdentityGraph(Graph):
         return self._add(("col", self.n_evals + which, 0))
 
     def opened(self, kind: str, idx: int, rot: int = 0) -> int:
+        if kind == "instance":                       # never opened: evaluated from the public inputs, one column per query
+            if (idx, rot % self.n) not in self.instance_slot:
+                raise ValueError(f"identity_program: the identity reads instance {idx} at rotation {rot}, which the instance queries do not name")
+            return self._add(("col", self.instance_slot[(idx, rot % self.n)], 0))
         key = (kind, idx, rot % self.n)
         if key not in self.slot:
             raise ValueError(f"identity_program: the identity reads {kind} {idx} at rotation {rot}, which the plan does not open")
@@ -512,22 +520,56 @@ def _expression_kinds(e: Expr, out: set) -> set:
     return out
 
 
-def identity_program(cs: ConstraintSystem, plan, k: int) -> RowProgram:
+def _identity_expressions(cs: ConstraintSystem):
+    return [p for polys in cs.gates for p in polys] + [e for lk in cs.lookups for e in list(lk.input_expressions) + list(lk.table_expressions)]
+
+
+def _instance_reads(e: Expr, out: list) -> list:
+    if e.kind == "instance":
+        out.append((e.a, e.b or 0))
+    for child in (e.a, e.b):
+        if isinstance(child, Expr):
+            _instance_reads(child, out)
+    return out
+
+
+def instance_queries(cs: ConstraintSystem):
+    """The distinct (instance column, rotation) pairs a verifier evaluates from the public inputs, in a fixed order: every `Instance(c, r)` of
+    the gates and the lookups as the expressions name them, then (c, 0) for every ("instance", c) among the permutation columns.  Query q is
+    column len(plan) + 9 + q of `identity_program(..., instance_queries=...)` (zkhip_verify_identity_instances_device)."""
+    pairs = []
+    for e in _identity_expressions(cs):
+        _instance_reads(e, pairs)
+    pairs += [(idx, 0) for kind, idx in cs.permutation_columns if kind == "instance"]
+    return list(dict.fromkeys(pairs))
+
+
+_instance_queries_of = instance_queries      # (identity_program takes a keyword of the same name)
+
+
+def identity_program(cs: ConstraintSystem, plan, k: int, instance_queries=None) -> RowProgram:
     """The quotient identity at x as a row program over ONE PROOF PER ROW (zkhip_verify_identity_device): the y-fold of exactly the terms of
     `_evaluate_h_terms` -- custom gates, permutation, lookups, the source the prover's quotient program is built from, so that the two cannot
     drift apart -- minus (h_0 + x^n h_1 + x^2n h_2)(x^n - 1): zero exactly when the evaluations of a proof satisfy the circuit at x.
     `plan`: the opened (kind, index, rotation) triples in the order a proof's evaluations are written (prover.opening_plan); a column at a
     rotation reads the slot of (kind, index, rotation mod 2^k).  theta, beta, gamma, y, x and x^n, l_0, l_last, l_active are the nine columns
-    behind the evaluations.  ValueError: a triple the expressions need and the plan does not open; instance columns and `Challenge`
-    expressions (multi-phase challenges), neither of which is built."""
+    behind the evaluations.  `instance_queries`: the (instance column, rotation) pairs the verifier evaluates from the public inputs
+    (`instance_queries(cs)`); `Instance(c, r)` and an instance permutation column read column len(plan) + 9 + the index of (c, r mod 2^k).
+    ValueError: a triple the expressions need and the plan does not open; an instance pair the queries do not name; a system that has instance
+    columns with `instance_queries=None`; `Challenge` expressions (multi-phase challenges), which are not built."""
     kinds = set()
-    for e in [p for polys in cs.gates for p in polys] + [e for lk in cs.lookups for e in list(lk.input_expressions) + list(lk.table_expressions)]:
+    for e in _identity_expressions(cs):
         _expression_kinds(e, kinds)
-    if cs.num_instance or "instance" in kinds or any(kind == "instance" for kind, _ in cs.permutation_columns):
-        raise ValueError("identity_program: instance columns are not built (the verifier would evaluate them from the public inputs)")
+    has_instance = cs.num_instance or "instance" in kinds or any(kind == "instance" for kind, _ in cs.permutation_columns)
+    if has_instance and instance_queries is None:
+        raise ValueError("identity_program: the system has instance columns and no instance queries were given (the verifier evaluates them from the public inputs)")
     if "challenge" in kinds:
         raise ValueError("identity_program: Challenge expressions (multi-phase challenges) are not built")
-    g = _IdentityGraph(cs, plan, k)
+    queries = list(instance_queries or ())
+    named = [c for c, _ in _instance_queries_of(cs)]
+    if named and cs.num_instance <= max(named):          # (a system built by hand may name an instance column without counting it)
+        cs = replace(cs, num_instance=1 + max(named))
+    g = _IdentityGraph(cs, plan, k, queries)
     theta, beta, gamma, x = (lambda g_, which=which: g_.derived(which) for which in (ID_THETA, ID_BETA, ID_GAMMA, ID_X))
     Y, value = g.derived(ID_Y), g.const(0)
     for term in _evaluate_h_terms(cs, beta, gamma, theta, (), 1, point=x):
@@ -535,7 +577,7 @@ def identity_program(cs: ConstraintSystem, plan, k: int) -> RowProgram:
     xn = g.derived(ID_XN)
     h = g.mad(g.mad(g.opened("h", 2), xn, g.opened("h", 1)), xn, g.opened("h", 0))
     prog = compile_graph(g, g.sub(value, g.mul(h, g.sub(xn, g.const(1)))))
-    prog.n_columns = len(plan) + IDENTITY_DERIVED
+    prog.n_columns = len(plan) + IDENTITY_DERIVED + len(queries)
     return prog
 
 
@@ -554,11 +596,40 @@ def domain_points_device(k: int, usable_rows: int, x, out=None, stream=None):
     return out
 
 
-def verify_identity_device(prog, evals, challenges, k: int, usable_rows: int, stream=None):
+def _instance_arrays(column_lens, queries, k: int):
+    """the three host arrays of the instance calls (ctypes, with their counts): lengths, query columns, query rotations mod 2^k"""
+    lens = (C.c_uint32 * max(len(column_lens), 1))(*column_lens)
+    cols = (C.c_uint32 * max(len(queries), 1))(*[c for c, _ in queries])
+    rots = (C.c_uint32 * max(len(queries), 1))(*[r % (1 << k) for _, r in queries])
+    return lens, len(column_lens), cols, rots, len(queries)
+
+
+def instance_evals_device(k: int, x, instances, column_lens, queries, out=None, stream=None):
+    """The instance columns' evaluations at x omega^rot from the public inputs (zkhip_fr_instance_evals_device): x (proofs, 4), instances
+    (proofs, sum(column_lens), 4) int64 device tensors -- column c's values at offset sum(column_lens[:c]) --, queries = (column, rotation)
+    pairs.  Returns a (queries, proofs, 4) tensor; a point of the domain gets zeros."""
+    import torch
+
+    proofs, total = x.shape[0], sum(column_lens)
+    if out is None:
+        out = torch.empty((len(queries), proofs, 4), dtype=torch.int64, device=x.device)
+    if not (x.is_cuda and x.is_contiguous() and out.is_contiguous() and instances.is_cuda and instances.is_contiguous()) or \
+            out.numel() < 4 * len(queries) * proofs or instances.numel() != 4 * total * proofs:
+        raise ValueError("instance_evals_device: contiguous device tensors, (proofs, 4), (proofs, total_len, 4) and an output of (queries, proofs, 4)")
+    omega = F.fr_encode([F.omega_for(k)])[0]
+    lens, n_columns, cols, rots, n_queries = _instance_arrays(column_lens, queries, k)
+    _lib.check(_lib.load().zkhip_fr_instance_evals_device(k, omega.ctypes.data, x.data_ptr(), instances.data_ptr() if total * proofs else None, lens, n_columns, cols, rots,
+                                                          n_queries, proofs, out.data_ptr(), stream))
+    return out
+
+
+def verify_identity_device(prog, evals, challenges, k: int, usable_rows: int, stream=None, instances=None, column_lens=None, queries=None):
     """The identity of a batch in one call (zkhip_verify_identity_device).  prog: `identity_program(...)` or its `_marshal()` pair (a caller
     that verifies many batches under one key marshals once); evals: (proofs, n_evals, 4), challenges: (proofs, 5, 4) = theta, beta, gamma, y,
-    x, int64 device tensors.  Returns (status, (failures, first)): an int32 array per proof -- 0 holds, 1 does not, 2 x lies in the domain --
-    and the report as integers (first = 2^64 - 1: none).  Waits for the verdicts."""
+    x, int64 device tensors.  With `instances` ((proofs, sum(column_lens), 4), the public inputs), `column_lens` and `queries`
+    (`instance_queries(cs)`, the list the program was built with) the call is zkhip_verify_identity_instances_device.  Returns
+    (status, (failures, first)): an int32 array per proof -- 0 holds, 1 does not, 2 x lies in the domain -- and the report as integers
+    (first = 2^64 - 1: none).  Waits for the verdicts."""
     import torch
 
     proofs, n_evals = evals.shape[0], evals.shape[1]
@@ -568,8 +639,18 @@ def verify_identity_device(prog, evals, challenges, k: int, usable_rows: int, st
     status = torch.empty(max(proofs, 1), dtype=torch.int32, device=evals.device)
     report = torch.empty(2, dtype=torch.int64, device=evals.device)
     omega = F.fr_encode([F.omega_for(k)])[0]
-    _lib.check(_lib.load().zkhip_verify_identity_device(C.byref(marshalled), evals.data_ptr(), n_evals, challenges.data_ptr(), k, usable_rows, omega.ctypes.data,
-                                                        proofs, status.data_ptr(), report.data_ptr(), stream))
+    if instances is None and column_lens is None and queries is None:
+        _lib.check(_lib.load().zkhip_verify_identity_device(C.byref(marshalled), evals.data_ptr(), n_evals, challenges.data_ptr(), k, usable_rows, omega.ctypes.data,
+                                                            proofs, status.data_ptr(), report.data_ptr(), stream))
+    else:
+        column_lens, queries = list(column_lens or ()), list(queries or ())
+        total = sum(column_lens)
+        if total * proofs and (instances is None or not (instances.is_cuda and instances.is_contiguous()) or instances.numel() != 4 * total * proofs):
+            raise ValueError("verify_identity_device: instances is a contiguous (proofs, sum(column_lens), 4) device tensor")
+        lens, n_columns, cols, rots, n_queries = _instance_arrays(column_lens, queries, k)
+        _lib.check(_lib.load().zkhip_verify_identity_instances_device(C.byref(marshalled), evals.data_ptr(), n_evals, challenges.data_ptr(), k, usable_rows,
+                                                                      omega.ctypes.data, instances.data_ptr() if total * proofs else None, lens, n_columns, cols, rots,
+                                                                      n_queries, proofs, status.data_ptr(), report.data_ptr(), stream))
     if stream is not None:
         _lib.check(_lib.load().zkhip_stream_sync(stream))
     failures, first = (int(v) for v in report.cpu().numpy().view(np.uint64))
@@ -850,16 +931,19 @@ def blind_rows_device(columns, row0: int, count: int, seed, first: int = 0, stre
 # ---------------------------------------------------------------------------------------------------
 # the row programs of one proof, written out for a host that is not Python (rust-shim/prover_patch.rs, tests/cpp/prover_sequence.c)
 # ---------------------------------------------------------------------------------------------------
-def halo2_lib_shape(gate_cols: int, lookups: int, blinding: int = 5) -> ConstraintSystem:
+def halo2_lib_shape(gate_cols: int, lookups: int, blinding: int = 5, instances: int = 0) -> ConstraintSystem:
     """The halo2-lib `BaseConfig` shape the reference's circuits use (/root/reference/aggregator/benches/wrapper_circuit.rs:61-68,
     state_transition_circuit.rs:48-50): `gate_cols` advice columns with the vertical gate q (a + b c - d), `lookups` range-lookup advice
-    columns against one table, one constants column; every advice column and the constants column take part in the permutation."""
+    columns against one table, one constants column; every advice column and the constants column take part in the permutation, and behind
+    them the `instances` instance columns (the public inputs, tied to advice cells by copy constraints; `BaseConfig` enables equality on
+    them last)."""
     G, NL = gate_cols, lookups
     return ConstraintSystem(
-        num_fixed=G + 2, num_advice=G + NL, num_instance=0,
+        num_fixed=G + 2, num_advice=G + NL, num_instance=instances,
         gates=[[Fixed(i) * (Advice(i, 0) + Advice(i, 1) * Advice(i, 2) - Advice(i, 3))] for i in range(G)],
         lookups=[Lookup([Advice(G + j)], [Fixed(G + 1)]) for j in range(NL)],
-        permutation_columns=[("advice", i) for i in range(G + NL)] + [("fixed", G)], blinding_factors=blinding, degree=4)
+        permutation_columns=[("advice", i) for i in range(G + NL)] + [("fixed", G)] + [("instance", j) for j in range(instances)],
+        blinding_factors=blinding, degree=4)
 
 
 def to_mont_program() -> RowProgram:

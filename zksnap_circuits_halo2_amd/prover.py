@@ -18,7 +18,7 @@ import ctypes as C
 import functools
 import io
 import random
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 import torch
@@ -115,6 +115,7 @@ class SeededChallenges:
         self._beta, self._gamma, self._theta, self._y, self._x, self.s = (rng.randrange(1, R) for _ in range(6))
         self.multiopen_challenges = tuple(rng.randrange(1, R) for _ in range(3))
 
+    def instances(self, values): pass
     def theta(self, points=()): return self._theta
     def beta_gamma(self, points=()): return self._beta, self._gamma
     def y(self, points=()): return self._y
@@ -137,6 +138,13 @@ class TranscriptChallenges:
         vk.write(vk_io, KG.RAW_BYTES)
         self.transcript = transcript_classes(hash)[0]()
         self.transcript.common_scalar(vk_transcript_repr(vk_io.getvalue()))      # a stand-in for halo2's vk.transcript_repr (transcript.py)
+
+    def instances(self, values):
+        """the public inputs, absorbed (never written) between the key and the advice commitments: every value of every instance column, as
+        halo2's `create_proof` and `verify_proof` both do.  No instance column: nothing is absorbed."""
+        for column in values:
+            for v_ in column:
+                self.transcript.common_scalar(v_)
 
     def _after(self, points):
         if len(points):
@@ -205,14 +213,18 @@ def multiopen_classes(multiopen):
     return MULTIOPEN[multiopen]
 
 
-def _read_proof_head(r, vk_repr, shape, plan):
+def _read_proof_head(r, vk_repr, shape, plan, instances=()):
     """a proof up to its evaluations, in the prover's order: (commitments by (kind, index), (theta, beta, gamma, y, x), the evaluations as
-    integers); the reader is left in front of the multi-open's part.  ZkhipError(-1): bytes that do not decode"""
+    integers); the reader is left in front of the multi-open's part.  instances: the proof's public inputs, one list of integers per instance
+    column, absorbed behind the key.  ZkhipError(-1): bytes that do not decode"""
     def xyz(points):                                       # device affine points -> Jacobian limbs with z = 1 for the host-side accumulation
         return [MO._affine_to_xyz(p_) for p_ in points.cpu().numpy().view(np.uint64).reshape(-1, 8)]
 
     n_adv, n_lk, n_sets = shape["advice"], shape["lookups"], shape["permutation_sets"]
     r.common_scalar(vk_repr)
+    for column in instances:
+        for v_ in column:
+            r.common_scalar(v_ % R)
     com = {("advice", i): c_ for i, c_ in enumerate(xyz(r.read_points(n_adv)))}
     theta = r.squeeze_challenge()
     if n_lk:
@@ -238,41 +250,74 @@ def identity_program_of(vk, plan, k):
     cache = vk.__dict__.setdefault("_identity_programs", {})
     key = (k, tuple(plan))
     if key not in cache:
-        cache[key] = E.identity_program(vk.cs, plan, k)._marshal()
+        cache[key] = E.identity_program(vk.cs, plan, k, instance_queries=E.instance_queries(vk.cs) if vk.cs.num_instance else None)._marshal()
     return cache[key]
 
 
-def identity_statuses(vk, k, plan, evals, challenges):
+def _check_instances(cs, k, instances, proofs):
+    """instances[p][c] = the integers of instance column c of proof p: one entry per proof, one list per column, every proof the same lengths
+    (a circuit fixes them), none longer than the usable rows (halo2's `InstanceTooLarge`).  Returns the columns' lengths."""
+    if len(instances) != proofs or any(len(per_proof) != cs.num_instance for per_proof in instances):
+        raise ValueError(f"instances: {cs.num_instance} columns of public inputs for each of the {proofs} proofs")
+    lens = [len(column) for column in instances[0]] if instances else [0] * cs.num_instance
+    if any([len(column) for column in per_proof] != lens for per_proof in instances):
+        raise ValueError("instances: the proofs of one circuit have instance columns of the same lengths")
+    if any(length > (1 << k) - (cs.blinding_factors + 1) for length in lens):
+        raise ValueError("instances: a column holds more values than the circuit has usable rows")
+    return lens
+
+
+def identity_statuses(vk, k, plan, evals, challenges, instances=None):
     """zkhip_verify_identity_device over a batch: evals[i] the integers of proof i in the plan's order, challenges[i] = (theta, beta, gamma, y,
-    x).  An int32 array: 0 the identity holds, 1 it does not, 2 x lies in the domain."""
+    x); for a circuit with instance columns instances[i] = proof i's public inputs, a list of integers per column, evaluated on the device
+    (zkhip_verify_identity_instances_device).  An int32 array: 0 the identity holds, 1 it does not, 2 x lies in the domain."""
+    n_instance = vk.cs.num_instance if getattr(vk, "cs", None) is not None else 0
+    if n_instance and instances is None:
+        raise ValueError("identity_statuses: the circuit has instance columns: hand in the proofs' public inputs (instances=)")
     if not evals:
         return np.zeros(0, dtype=np.int32)
     prog = identity_program_of(vk, plan, k)
     d_evals = words([e_ for row in evals for e_ in row]).reshape(len(evals), len(plan), 4)
     d_challenges = words([c_ for row in challenges for c_ in row]).reshape(len(evals), 5, 4)
-    return E.verify_identity_device(prog, d_evals, d_challenges, k, (1 << k) - (vk.cs.blinding_factors + 1))[0]
+    usable = (1 << k) - (vk.cs.blinding_factors + 1)
+    if not n_instance:
+        return E.verify_identity_device(prog, d_evals, d_challenges, k, usable)[0]
+    lens = _check_instances(vk.cs, k, instances, len(evals))
+    flat = [v_ % R for per_proof in instances for column in per_proof for v_ in column]
+    d_instances = words(flat).reshape(len(evals), sum(lens), 4) if flat else None
+    return E.verify_identity_device(prog, d_evals, d_challenges, k, usable, instances=d_instances, column_lens=lens, queries=E.instance_queries(vk.cs))[0]
 
 
-def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b", multiopen="shplonk", *, identity=True):
+def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b", multiopen="shplonk", *, identity=True, instances=None):
     """The verifier of a BATCH of proofs of one circuit, each written through TranscriptChallenges: it is handed the parameters, the verifying key
     (with its constraint system, `vk.cs`), the proofs' BYTES, and what a verifier knows of the circuit -- `shape` (how many advice columns,
     lookups, permutation sets, whether a random polynomial is committed) and `plan` (the opened (kind, index, rotation) triples, in the order
     their evaluations were written).  Every proof's head is replayed with reads -- commitments land on the device as affine points, evaluations
     as integers, every challenge is derived here --; then the two halves of halo2's `verify_proof`:
       the identity   the gate, permutation and lookup expressions at x against h(x) (x^n - 1), for ALL proofs in one device call
-                     (zkhip_verify_identity_device; the program is compiled once per key and plan);
+                     (zkhip_verify_identity_device; the program is compiled once per key and plan); the instance columns are evaluated
+                     at x from the public inputs inside that call (zkhip_verify_identity_instances_device);
       the openings   for the proofs whose identity holds, `VerifierSHPLONK.verify_proof_transcript` (multiopen="gwc":
                      `VerifierGWC.verify_proof_transcript`), one pairing check each.
     A proof is accepted when both accept; bytes that do not decode reject that proof alone.  hash: the transcript the proofs were written under
     ("blake2b" or "poseidon").  identity=False leaves the first half out (the openings alone: what a test uses to show WHICH half refused).
-    Not built: one folded pairing check for the batch (halo2's BatchVerifier), instance columns, multi-phase challenges.
-    Returns a list of bools."""
+    instances: for a circuit with instance columns, instances[i][c] = the integers of column c that proof i is verified AGAINST (the public
+    inputs; never part of the proof).  They are absorbed into proof i's transcript behind the key, as the prover absorbed its own, so wrong
+    inputs change every challenge, and they enter the identity through the instance columns' evaluations at x.  ValueError: a key whose
+    circuit has instance columns and no `instances`; lengths that differ between the proofs or exceed the usable rows.
+    Not built: one folded pairing check for the batch (halo2's BatchVerifier), committed instance columns, multi-phase challenges (DESIGN.md
+    section 10).  Returns a list of bools."""
     import contextlib
 
     verifier = multiopen_classes(multiopen)[1]
     reader = transcript_classes(hash)[1]
     if identity:
         identity_program_of(vk, plan, k)                   # a key that cannot state its identity is the caller's error, whatever the proofs are
+    n_instance = vk.cs.num_instance if getattr(vk, "cs", None) is not None else 0
+    if n_instance and instances is None:
+        raise ValueError("verify_transcript_proofs: the key's circuit has instance columns: hand in the public inputs of every proof (instances=)")
+    if n_instance:
+        _check_instances(vk.cs, k, instances, len(proofs))
     vk_io = io.BytesIO()
     vk.write(vk_io, KG.RAW_BYTES)
     vk_repr = vk_transcript_repr(vk_io.getvalue())
@@ -282,13 +327,13 @@ def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b",
         for i, proof in enumerate(proofs):
             r = stack.enter_context(reader(bytes(proof)))
             try:
-                heads[i] = (r,) + _read_proof_head(r, vk_repr, shape, plan)
+                heads[i] = (r,) + (_read_proof_head(r, vk_repr, shape, plan, instances[i]) if n_instance else _read_proof_head(r, vk_repr, shape, plan))
             except _lib.ZkhipError as e:
                 if e.code != -1:
                     raise
         order = sorted(heads)
         if identity:
-            status = identity_statuses(vk, k, plan, [heads[i][3] for i in order], [heads[i][2] for i in order])
+            status = identity_statuses(vk, k, plan, [heads[i][3] for i in order], [heads[i][2] for i in order], [instances[i] for i in order] if n_instance else None)
             order = [i for i, s_ in zip(order, status) if s_ == 0]
         key_com = _key_commitments(vk)
         for i in order:
@@ -302,10 +347,11 @@ def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b",
     return verdicts
 
 
-def verify_transcript_proof(params, vk, k, proof, shape, plan, hash="blake2b", multiopen="shplonk"):
+def verify_transcript_proof(params, vk, k, proof, shape, plan, hash="blake2b", multiopen="shplonk", instances=None):
     """The verifier of one proof given as bytes: `verify_transcript_proofs` over a batch of one -- the identity at x and the openings, accepted
-    when both accept.  ValueError: a verifying key without its constraint system."""
-    return verify_transcript_proofs(params, vk, k, [proof], shape, plan, hash, multiopen)[0]
+    when both accept.  instances: the proof's public inputs, a list of integers per instance column.  ValueError: a verifying key without its
+    constraint system; a circuit with instance columns and no `instances`."""
+    return verify_transcript_proofs(params, vk, k, [proof], shape, plan, hash, multiopen, instances=None if instances is None else [instances])[0]
 
 
 # ---- the witness -------------------------------------------------------------------------------------------------------------------------------
@@ -319,20 +365,28 @@ class Witness:
     fixed: list                           # q_0 .., the constants column, the table
     advice: list                          # the gate columns, then the lookup inputs
     assembly: KG.Assembly
+    instance: list = field(default_factory=list)           # the public inputs: values in the first rows, zeros behind them, NO blinding rows (halo2 pads with zeros)
+    instance_values: list = field(default_factory=list)    # ... and as integers, a list per column: what a verifier is handed
 
     @property
     def lookup_inputs(self): return self.advice[self.gate_cols:]
     @property
     def table(self): return self.fixed[self.gate_cols + 1]
 
-    def permutation_column(self, c):      # every advice column, then the constants column
-        return self.advice[c] if c < len(self.advice) else self.fixed[self.gate_cols]
+    def permutation_column(self, c):      # every advice column, then the constants column, then the instance columns
+        if c < len(self.advice):
+            return self.advice[c]
+        return self.fixed[self.gate_cols] if c == len(self.advice) else self.instance[c - len(self.advice) - 1]
 
 
-def halo2_lib_witness(k, gate_cols, lookups, blinding, lookup_bits=8, corrupt=None):
+def halo2_lib_witness(k, gate_cols, lookups, blinding, lookup_bits=8, corrupt=None, instances=0, instance_len=4, public_inputs=None):
     """A satisfied circuit: `gate_cols` advice columns with the vertical gate q (a + b c - d) on rows 0, 4, 8, ..., `lookups` range-lookup
     columns against a 2^lookup_bits-entry table, copy constraints across advice and constants columns, BLIND blinding rows.
-    corrupt: "gate" / "copy" break the witness; "lookup" puts a value outside the table into lookup column 1."""
+    instances: that many instance columns of `instance_len` public values each; public value t (counted through the columns) is tied by a
+    copy constraint to the gate input in row 4 (t // gate_cols) + 2 of gate column t % gate_cols, whose value it takes -- or, with
+    public_inputs (a list of `instance_len` integers per column), which is given that value first: proofs of one key over different inputs.
+    corrupt: "gate" / "copy" break the witness; "lookup" puts a value outside the table into lookup column 1; "instance" gives the gate
+    input behind the first public value another value (the gates stay satisfied, the copy constraint does not)."""
     G, NL = gate_cols, lookups
     n, u = 1 << k, (1 << k) - (BLIND + 1)
     lookup_bits = min(lookup_bits, k - 1)            # every table value must occur among the usable rows
@@ -347,7 +401,12 @@ def halo2_lib_witness(k, gate_cols, lookups, blinding, lookup_bits=8, corrupt=No
         lk = small_ints(torch.randint(0, 1 << lookup_bits, (n,), dtype=torch.int64, device=DEV), k)
         blinding.made(lk, u)
         advice.append(lk)
-    w = Witness(k, G, NL, E.halo2_lib_shape(G, NL, BLIND), fixed, advice, KG.Assembly(n, G + NL + 1))
+    public_cells = [(t % G, 4 * (t // G) + 2) for t in range(instances * instance_len)] if instances else []
+    if public_cells and (public_cells[-1][1] >= u or instance_len > u):
+        raise ValueError(f"halo2_lib_witness: {instances} x {instance_len} public values do not fit the gate inputs of {G} columns over {u} usable rows")
+    if corrupt == "instance" and not public_cells:
+        raise ValueError("corrupt=\"instance\" needs an instance column with a value")
+    w = Witness(k, G, NL, E.halo2_lib_shape(G, NL, BLIND, instances), fixed, advice, KG.Assembly(n, G + NL + 1 + instances))
     FC = G + NL                                                                # index of the constants column among the permutation columns
     cycles = [[(0, 1), (FC, 2)], [(G, 10), (G, 20)], [(0, 13), (G, 30)], [(0, 17), (0, 21), (FC, 5)]]
     cycles += [[(G + j, 40 + j), (G, 60 + j)] for j in range(1, NL)]           # lookup column j <-> lookup column 0
@@ -360,6 +419,22 @@ def halo2_lib_witness(k, gate_cols, lookups, blinding, lookup_bits=8, corrupt=No
             w.permutation_column(c)[r] = v
         for (c1, r1), (c2, r2) in zip(cyc, cyc[1:]):
             w.assembly.copy(c1, r1, c2, r2)
+    if public_inputs is not None and [len(column) for column in public_inputs] != [instance_len] * instances:
+        raise ValueError(f"public_inputs: {instances} lists of {instance_len} integers")
+    for j in range(instances):            # the public inputs take the values of their cells (gate inputs: the gate program leaves them as they are)
+        column = torch.zeros((n, 4), dtype=torch.int64, device=DEV)
+        chosen = words([v_ % R for v_ in public_inputs[j]]) if public_inputs is not None and instance_len else None
+        for i in range(instance_len):
+            c, r = public_cells[j * instance_len + i]
+            if chosen is not None:
+                advice[c][r] = chosen[i]
+            column[i] = advice[c][r]
+            w.assembly.copy(c, r, FC + 1 + j, i)
+        w.instance.append(column)
+        w.instance_values.append(T.fr_ints(column[:instance_len]) if instance_len else [])
+    if corrupt == "instance":
+        c, r = public_cells[0]
+        advice[c][r] = advice[c][r - 1].clone()                                # before the gate outputs are computed: every gate still holds
     gate = E.RowProgram()                 # out = a + sel3 * ((a[-3] + a[-2] a[-1]) - a): the gate outputs, everything else unchanged
     gate.emit(E.OP_MUL, 0, gate.column(0, -2), gate.column(0, -1))
     gate.emit(E.OP_ADD, 0, E.RowProgram.reg(0), gate.column(0, -3))
@@ -483,7 +558,8 @@ class Prover:
         gamma; permutation then lookup product commitments (Lagrange basis: the same group elements as the commitments to their coefficients), the
         random polynomial's commitment, y; the quotient pieces, x; the evaluations; the multi-open"""
         ch, lap, NL = self.ch, self.lap, self.w.lookups
-        self.theta = ch.theta(self.adv_commit)          # no instance columns: nothing between the key and the advice commitments
+        ch.instances(self.w.instance_values)            # between the key and the advice commitments; nothing for a circuit without instance columns
+        self.theta = ch.theta(self.adv_commit)
         lap("transcript")
         self.load_sigma()
         if NL:
@@ -605,7 +681,8 @@ class Prover:
         l_last = torch.zeros((n, 4), dtype=torch.int64, device=DEV); l_last[u] = ONE
         rows = torch.arange(n, dtype=torch.int64, device=DEV)
         l_active = torch.where((rows < u)[:, None], ONE[None, :], torch.zeros_like(ONE)[None, :]).contiguous()
-        lagrange = w.fixed + w.advice + [l0, l_last, l_active] + self.sigma + self.z_sets + self.lookup_cols
+        # the instance columns sit between the advice and l_0: transformed per proof with the advice, never committed, never opened
+        lagrange = w.fixed + w.advice + w.instance + [l0, l_last, l_active] + self.sigma + self.z_sets + self.lookup_cols
         assert len(lagrange) == qc.total
         self.coeff = coeff = torch.stack(lagrange).contiguous()                     # [ncol][n][4]
         npc = len(cs.permutation_columns)
@@ -689,7 +766,7 @@ class Prover:
         """the (kind, index) of every column and quotient piece (None: not a polynomial of the proof) and the device addresses of their
         coefficients, in the order of `evals`: the one map a plan becomes queries through"""
         qc, cs, n = self.qc, self.cs, self.n
-        kinds = ([("fixed", i) for i in range(cs.num_fixed)] + [("advice", i) for i in range(cs.num_advice)] + [None, None, None]
+        kinds = ([("fixed", i) for i in range(cs.num_fixed)] + [("advice", i) for i in range(cs.num_advice)] + [None] * (cs.num_instance + 3)
                  + [("sigma", i) for i in range(len(cs.permutation_columns))] + self.product_kinds() + [("h", i) for i in range(3)])
         return kinds, [self.coeff[i].data_ptr() for i in range(qc.total)] + [self.h_coeff[i * n:].data_ptr() for i in range(3)]
 

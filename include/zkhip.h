@@ -864,8 +864,7 @@ int zkhip_plume_sign(const uint8_t *msg, size_t msg_len, const uint64_t sk[4], c
  * instance columns of such a proof are zero).  ZKHIP_EINVAL: the conditions of zkhip_verify_identity_device; n_columns or n_queries above 64;
  * a query column >= n_columns; a rotation >= 2^k; column_lens[c] > usable_rows (halo2's `InstanceTooLarge`); d_instances null or misaligned
  * where total_len * n_proofs > 0.
- * Not built: committed instance columns (`QUERY_INSTANCE = true`, the IPA scheme), multi-phase challenges, folding a batch's pairing checks
- * into one (halo2's BatchVerifier) -- DESIGN.md section 10. */
+ * Not built: committed instance columns (`QUERY_INSTANCE = true`, the IPA scheme), multi-phase challenges -- DESIGN.md section 10. */
 int zkhip_fr_domain_points_device(uint32_t k, uint32_t usable_rows, const uint64_t omega[4], const void *d_x, size_t n_points, void *d_out, void *stream);
 int zkhip_verify_identity_device(const zkhip_vm_program *prog, const void *d_evals, uint32_t n_evals, const void *d_challenges, uint32_t k,
                                  uint32_t usable_rows, const uint64_t omega[4], size_t n_proofs, void *d_status, void *d_report, void *stream);
@@ -925,6 +924,59 @@ int zkhip_pairing_check_device(const void *d_g1, const void *d_g2, size_t n, voi
  * a = 2 G1Affine | 2 G2Affine run as one serial chain.  op + 256: quad policy only, op + 512: single-lane policy only (the other half of out
  * is left as it was). */
 int zkhip_test_fq12_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out);
+
+/* ---- the batch verifier: the opening checks of a batch folded into one pairing check ---------------------------------------------------------
+ * The openings of proof i accept exactly when e(A_i, g2) e(-C_i, [s]g2) = 1, A_i and C_i linear combinations of the proof's commitments, the
+ * key's commitments and G.  With random r_i the batch accepts, except with probability about 1 / r, exactly when
+ * e(sum r_i A_i, g2) e(-sum r_i C_i, [s]g2) = 1: two MSMs and one pairing check (halo2's `BatchVerifier`; the reference's aggregator folds its
+ * KZG accumulators the same way, `KzgAs<Bn256, Gwc19>`).  The two calls below are the scalar side: the scalars of A_i and C_i for the GWC
+ * multi-open of every proof, and the scaling and folding of such ROWS of scalars by the r_i; multiopen.fold_check is the sequence around them.
+ * Both are asynchronous on `stream`, wait for nothing on the host and take their scratch from the stream's scratch set.  Elements are in the
+ * external Fr format (4 x u64 Montgomery-256, canonical); device arrays are 16-byte aligned.  Argument errors are ZKHIP_EINVAL, decided on the
+ * host before the device is touched, with nothing enqueued.
+ *
+ * zkhip_gwc_plan: a key's opening plan as the GWC verifier groups it, fixed per key, host memory, consumed before the call returns.  Query q is
+ * evaluation q of a proof's record.  n_sets point sets: set_rotation[i] is the rotation of set i reduced mod 2^k as an unsigned value, the
+ * sets in order of first appearance among the queries (multiopen.construct_intermediate_sets grouped by rotation).  n_slots opened polynomials,
+ * one slot each, the proof's own polynomials first and the key's behind them.  query_set[q], query_slot[q]: the set and the polynomial of
+ * query q; query_pos[q]: its position inside its set, the exponent of v.  (A tagged struct: its ctypes mirror _lib.GwcPlan is checked by
+ * tests/test_gwc_fold_host.py.)
+ *
+ * zkhip_gwc_scalars_device.  d_evals: [n_proofs][n_evals]; d_points: [n_proofs][3] = x, v, u.  COLUMNS OF A ROW OF d_rows_a (normative), with
+ * n_cols = n_sets + n_slots + 1:
+ *   column i < n_sets (witness W_i):          u^i x omega^set_rotation[i]
+ *   column n_sets + p (polynomial slot p):    sum over the queries q with query_slot[q] = p of u^query_set[q] v^query_pos[q]
+ *   column n_cols - 1 (G):                    - sum_q u^query_set[q] v^query_pos[q] evals[q]
+ * d_rows_a is [n_proofs][n_cols]; d_rows_c is [n_proofs][n_sets], column j = u^j.  One workgroup per proof, one lane per column.
+ * The plan is validated, marshalled (its CSR lists, omega^set_rotation[i]) and uploaded inside every call, in pieces of 32 KB through the
+ * stream's ring of eight pinned slots: a plan above 256 KB of tables (2 n_evals + n_slots + 8 n_sets + 1 words of 4 bytes) waits on the host
+ * for its own first pieces to be copied -- the one exception to "no host wait"; the plans of this project are at most 24 KB.
+ * n_proofs == 0: ZKHIP_OK, nothing is written.  ZKHIP_EINVAL: a null plan or plan array; n_sets outside 1 .. 64; n_evals outside 1 .. 65527;
+ * n_slots outside 1 .. 65536; k > 28; omega null or not canonical; set_rotation[i] >= 2^k; query_set[q] >= n_sets; query_pos[q] >= n_evals;
+ * query_slot[q] >= n_slots; n_proofs > 2^24; with n_proofs > 0 a device pointer that is null or not 16-byte aligned.
+ *
+ * zkhip_fr_fold_rows_device.  d_rows: [n_rows][n_cols]; d_r: [n_rows]; negate: 0 or 1, the sign of every output.
+ *   d_out_own    [n_rows][n_own]      out_own[i][j] = +- r_i rows[i][j]                          for j < n_own
+ *   d_out_shared [n_cols - n_own]     out_shared[j] = +- sum_i r_i rows[i][n_own + j]            exact for every n_rows (a second level joins the
+ *                                                                                                 workgroups' sums above 4096 rows)
+ * n_own == 0, n_own == n_cols and n_rows == 0 are legal; with n_rows == 0 the shared part is written as zeros.  A sub-range of a batch is the
+ * same call with offset pointers.  The outputs must not overlap the inputs.  ZKHIP_EINVAL: n_cols outside 1 .. 65536; n_own > n_cols; negate
+ * other than 0 or 1; n_rows > 2^24 or n_rows n_cols > 2^32; a pointer that is read or written and is null or not 16-byte aligned (d_rows, d_r
+ * and d_out_own only where n_rows > 0, d_out_own only where n_own > 0, d_out_shared only where n_own < n_cols).
+ * Not built: the SHPLONK scalars on the device (the host's shplonk_accumulate makes those rows), folding across different circuits or
+ * parameter sets, a batch sharded over devices. */
+struct zkhip_gwc_plan {
+  uint32_t n_evals, n_sets, n_slots, reserved;
+  const uint32_t *set_rotation;     /* [n_sets] */
+  const uint32_t *query_set;        /* [n_evals] */
+  const uint32_t *query_pos;        /* [n_evals] */
+  const uint32_t *query_slot;       /* [n_evals] */
+};
+typedef struct zkhip_gwc_plan zkhip_gwc_plan;
+int zkhip_gwc_scalars_device(const zkhip_gwc_plan *plan, const void *d_evals, const void *d_points, uint32_t k, const uint64_t omega[4], size_t n_proofs,
+                             void *d_rows_a, void *d_rows_c, void *stream);
+int zkhip_fr_fold_rows_device(const void *d_rows, uint32_t n_cols, uint32_t n_own, const void *d_r, int negate, size_t n_rows, void *d_out_own,
+                              void *d_out_shared, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1437,6 +1437,36 @@ inline IdentityVerdicts verify_identity_device(const RowProgram& identity, const
   if (n_proofs) check(zkhip_download(out.status.data(), d_status, n_proofs * sizeof(int32_t)), "verify_identity_device");
   return out;
 }
+// The batch verifier's scalar side (zkhip.h, "the batch verifier").  A key's opening plan as the GWC verifier groups it: query q is evaluation q of
+// a record; its set (sets in order of first appearance, one rotation each), its position inside the set, the slot of its polynomial
+struct GwcPlan {
+  std::vector<uint32_t> set_rotation, query_set, query_pos, query_slot;
+  uint32_t n_slots = 0;
+};
+// rows_a = [n_proofs][n_sets + n_slots + 1], rows_c = [n_proofs][n_sets]: the scalars of every proof's two accumulated points (layout: zkhip.h)
+inline void gwc_scalars_device(const GwcPlan& plan, const DeviceVec& evals, const DeviceVec& points, uint32_t k, const Fr& omega, size_t n_proofs, DeviceVec& rows_a,
+                               DeviceVec& rows_c) {
+  const size_t n_evals = plan.query_set.size(), n_sets = plan.set_rotation.size();
+  if (plan.query_pos.size() != n_evals || plan.query_slot.size() != n_evals) throw std::invalid_argument("gwc_scalars_device: the plan's query arrays differ in length");
+  if (evals.size() < n_proofs * n_evals || points.size() < n_proofs * 3 || rows_a.size() < n_proofs * (n_sets + plan.n_slots + 1) || rows_c.size() < n_proofs * n_sets)
+    throw std::invalid_argument("gwc_scalars_device: arrays shorter than the batch");
+  zkhip_gwc_plan p{};
+  p.n_evals = (uint32_t)n_evals;
+  p.n_sets = (uint32_t)n_sets;
+  p.n_slots = plan.n_slots;
+  p.set_rotation = plan.set_rotation.data();
+  p.query_set = plan.query_set.data();
+  p.query_pos = plan.query_pos.data();
+  p.query_slot = plan.query_slot.data();
+  check(zkhip_gwc_scalars_device(&p, evals.data(), points.data(), k, omega.l, n_proofs, rows_a.data(), rows_c.data(), nullptr), "gwc_scalars_device");
+}
+// out_own[i][j] = +- r[i] rows[i][j] for j < n_own; out_shared[j] = +- sum_i r[i] rows[i][n_own + j]
+inline void fold_rows_device(const DeviceVec& rows, uint32_t n_cols, uint32_t n_own, const DeviceVec& r, bool negate, size_t n_rows, DeviceVec& out_own,
+                             DeviceVec& out_shared) {
+  if (n_own > n_cols || rows.size() < n_rows * n_cols || r.size() < n_rows || out_own.size() < n_rows * n_own || out_shared.size() < n_cols - n_own)
+    throw std::invalid_argument("fold_rows_device: arrays shorter than the batch");
+  check(zkhip_fr_fold_rows_device(rows.data(), n_cols, n_own, r.data(), negate ? 1 : 0, n_rows, out_own.data(), out_shared.data(), nullptr), "fold_rows_device");
+}
 // Random field elements drawn in HBM (zkhip.h, "random field elements": element i of stream (seed, stream_id) is one ChaCha20 block reduced mod r).
 // The library holds no entropy: `seed` comes from the caller's generator, and a (seed, stream_id, index) triple is never reused across proofs.
 // out[j] = element first + j for every j < out.size(): the vanishing argument's random polynomial, never on the host

@@ -105,6 +105,10 @@ extern "C" {
     fn zkhip_fr_random(seed: *const u8, stream_id: u64, first: u64, n: usize, out: *mut u64) -> c_int;
     fn zkhip_fr_random_rows_device(seed: *const u8, stream_id: u64, first: u64, d_cols: *const *const c_void,
                                    n_cols: u32, row0: usize, count: usize, stream: *mut c_void) -> c_int;
+    // ---- the batch verifier's fold (zkhip.h "the batch verifier"): rows of scalars scaled and summed by per-proof multipliers.  The GWC scalars
+    // call takes a plan struct and is not bound here: a Rust verifier makes its rows with its own accumulation scheme ------------------------
+    fn zkhip_fr_fold_rows_device(d_rows: *const c_void, n_cols: u32, n_own: u32, d_r: *const c_void, negate: c_int, n_rows: usize, d_out_own: *mut c_void,
+                                 d_out_shared: *mut c_void, stream: *mut c_void) -> c_int;
     // ---- pairing check (zkhip.h "pairing check"): is prod_i e(g1[i], g2[i]) the identity of Gt?  Only the verdict leaves the device ----------
     fn zkhip_pairing_check(g1: *const u64, g2: *const u64, n: usize, ok: *mut c_int) -> c_int;
     fn zkhip_pairing_check_device(d_g1: *const c_void, d_g2: *const c_void, n: usize, d_ok: *mut c_void, stream: *mut c_void) -> c_int;
@@ -694,6 +698,15 @@ impl DevCols {
         let rc = unsafe { zkhip_fr_instance_evals_device(k, omega as *const F as *const u64, x, instances, column_lens.as_ptr(), column_lens.len() as u32,
                                                          columns.as_ptr(), rotations.as_ptr(), queries.len() as u32, n_proofs, out, std::ptr::null_mut()) };
         if rc != 0 { warn_once("zkhip_fr_instance_evals_device", rc); }
+        rc == 0
+    }
+    /// the batch verifier's fold: `rows` = [n_rows][n_cols] scalars, `r` = [n_rows] multipliers; `out_own` = [n_rows][n_own] = +- r_i rows[i][j],
+    /// `out_shared` = [n_cols - n_own] = +- sum_i r_i rows[i][n_own + j]
+    pub(crate) fn fold_rows(rows: *const c_void, n_cols: u32, n_own: u32, r: *const c_void, negate: bool, n_rows: usize, out_own: *mut c_void,
+                            out_shared: *mut c_void) -> bool {
+        // SAFETY: the device arrays hold what the sizes say
+        let rc = unsafe { zkhip_fr_fold_rows_device(rows, n_cols, n_own, r, negate as c_int, n_rows, out_own, out_shared, std::ptr::null_mut()) };
+        if rc != 0 { warn_once("zkhip_fr_fold_rows_device", rc); }
         rc == 0
     }
     /// rows [0, n) of column `col` = elements first .. first + n - 1 of stream (seed, stream_id) (zkhip.h "random field elements"): the vanishing

@@ -1,0 +1,215 @@
+"""GPU (-m gpu): the batch verifier -- multiopen.fold_check and prover.verify_transcript_proofs(..., fold=True).
+
+  (a) synthetic accumulators with a known trapdoor (ParamsKZG.setup(k, s), points from zkhip_g1_fixed_base_mul_device): with W = w G, Q = q G and
+      A = a W + b Q + c G the openings accept exactly when a w + b q + c = s w.  16 valid proofs accept with exactly one pairing check; one bad
+      proof among 16 is located with at most 9; two bad proofs whose errors cancel in the unweighted sum (A_1 + d G, A_2 - d G) are both refused,
+      while the plain sum of the sixteen passes
+  (b) proofs of one key at k = 7, (3, 2), made as test_gpu_verify_identity's five are, for both multi-opens: fold=True answers what fold=False
+      answers -- on the honest batch (one pairing check), with two proofs of a broken witness (the identity refuses), with two differing
+      evaluations swapped in one proof's bytes and identity=False (that proof alone), with truncated proofs, on an empty batch; one case with an
+      instance column and one under hash="poseidon"
+The final check goes through multiopen._pairing_verdict, which the tests wrap to count the calls."""
+import functools
+import random
+
+import numpy as np
+import pytest
+import torch
+
+import zksnap_circuits_halo2_amd as Z
+from zksnap_circuits_halo2_amd import _lib, fields as F, keygen as KG, multiopen as MO, prover as P, tensors as T
+from zksnap_circuits_halo2_amd.arithmetic import pairing_check
+
+pytestmark = pytest.mark.gpu
+R = F.R_MOD
+DEV = torch.device("cuda", 0)
+SEED = bytes(range(32))
+
+
+@pytest.fixture
+def checks(monkeypatch):
+    """the number of final pairing checks made, as a one-element list"""
+    count, real = [0], MO._pairing_verdict
+
+    def counted(*args, **kw):
+        count[0] += 1
+        return real(*args, **kw)
+
+    monkeypatch.setattr(MO, "_pairing_verdict", counted)
+    return count
+
+
+# ---- (a) synthetic accumulators --------------------------------------------------------------------------------------------------------------------
+def g_multiples(scalars):
+    """[s G] as an (n, 8) int64 device tensor of affine points"""
+    d = T.fr_words(scalars, DEV)
+    out = torch.empty((len(scalars), 8), dtype=torch.int64, device=DEV)
+    _lib.check(_lib.load().zkhip_g1_fixed_base_mul_device(d.data_ptr(), len(scalars), out.data_ptr(), None))
+    return out
+
+
+@functools.lru_cache(None)
+def synthetic(B=16):
+    s = P.SeededChallenges(1).s
+    rng = random.Random("accumulators")
+    w, q, a, b = ([rng.randrange(1, R) for _ in range(B)] for _ in range(4))
+    c = [(s * w[i] - a[i] * w[i] - b[i] * q[i]) % R for i in range(B)]
+    own = g_multiples([v for i in range(B) for v in (w[i], q[i])]).reshape(B, 2, 8).contiguous()
+    return s, w, q, a, b, c, own, g_multiples([1])
+
+
+def run_synthetic(params, c, a=None):
+    s, w, q, a0, b, _, own, shared = synthetic()
+    a = a0 if a is None else a
+    rows_a = T.fr_words([v for i in range(len(c)) for v in (a[i], b[i], c[i])], DEV).reshape(len(c), 3, 4)
+    rows_c = T.fr_words([1] * len(c), DEV).reshape(len(c), 1, 4)
+    return MO.fold_check(params, rows_a, rows_c, own, shared, SEED)
+
+
+@pytest.fixture(scope="module")
+def params4():
+    with Z.ParamsKZG.setup(4, P.SeededChallenges(1).s) as params:
+        yield params
+
+
+def test_sixteen_valid_accumulators_accept_with_one_pairing_check(params4, checks):
+    c = synthetic()[5]
+    assert run_synthetic(params4, c) == [True] * 16 and checks == [1]
+
+
+@pytest.mark.parametrize("bad", [0, 7, 8, 15])
+def test_one_bad_accumulator_among_sixteen_is_located_with_at_most_nine_checks(params4, checks, bad):
+    c = list(synthetic()[5])
+    c[bad] = (c[bad] + 1) % R
+    assert run_synthetic(params4, c) == [i != bad for i in range(16)] and 2 <= checks[0] <= 9
+
+
+def test_a_wrong_witness_scalar_is_refused_as_well(params4, checks):
+    a = list(synthetic()[3])
+    a[5] = (a[5] + 1) % R                                       # the own part of a row, scaled by r_5
+    assert run_synthetic(params4, synthetic()[5], a) == [i != 5 for i in range(16)] and checks[0] <= 9
+
+
+def test_two_errors_that_cancel_in_the_plain_sum_are_both_refused(params4, checks):
+    s, w, q, a, b, c, own, shared = synthetic()
+    d = 0x1234567
+    c = list(c)
+    c[1], c[2] = (c[1] + d) % R, (c[2] - d) % R                 # A_1 + d G and A_2 - d G
+    # the unweighted sum of the sixteen passes: in the exponent, and as a pairing check of the two plain sums
+    total_a = sum(a[i] * w[i] + b[i] * q[i] + c[i] for i in range(16)) % R
+    total_c = sum(w) % R
+    assert total_a == s * total_c % R
+    pair = g_multiples([total_a, (R - total_c) % R]).cpu().numpy().view(np.uint64)
+    assert pairing_check(pair, np.stack([params4.g2, params4.s_g2])) is True
+    assert run_synthetic(params4, c) == [i not in (1, 2) for i in range(16)] and checks[0] <= 16
+
+
+def test_a_batch_of_one_and_an_empty_batch(params4, checks):
+    s, w, q, a, b, c, own, shared = synthetic()
+    one = lambda ci: MO.fold_check(params4, T.fr_words([a[0], b[0], ci], DEV).reshape(1, 3, 4), T.fr_words([1], DEV).reshape(1, 1, 4), own[:1].contiguous(), shared, SEED)
+    assert one(c[0]) == [True] and one((c[0] + 1) % R) == [False] and checks == [2]
+    assert MO.fold_check(params4, torch.empty((0, 3, 4), dtype=torch.int64, device=DEV), torch.empty((0, 1, 4), dtype=torch.int64, device=DEV),
+                         torch.empty((0, 2, 8), dtype=torch.int64, device=DEV), shared, None) == [] and checks == [2]
+    assert MO.fold_check(params4, T.fr_words([a[0], b[0], c[0]], DEV).reshape(1, 3, 4), T.fr_words([1], DEV).reshape(1, 1, 4), own[:1].contiguous(), shared, None) == [True]      # os.urandom
+
+
+# ---- (b) proofs of one key -------------------------------------------------------------------------------------------------------------------------
+K, GATE_COLS, LOOKUPS = 7, 3, 2
+
+
+class Batch:
+    """proofs of one circuit under one key: `honest` of them, then `broken` of a witness whose gate fails"""
+
+    def __init__(self, multiopen, hash="blake2b", honest=5, broken=2, instances=0):
+        self.multiopen, self.hash = multiopen, hash
+        self.params = Z.ParamsKZG.setup(K, P.SeededChallenges(1).s)
+        self.proofs, self.public, self.dpk = [], [], None
+        for seed in range(1, honest + broken + 1):
+            torch.manual_seed(1)                                                   # one circuit: the constants column is drawn from torch's generator
+            blinding = P.DeviceBlinding(random.Random(seed).randbytes(32))
+            public = [[1000 * seed + 10 * j + i for i in range(5)] for j in range(instances)] if instances else None      # every proof its own public inputs
+            w = P.halo2_lib_witness(K, GATE_COLS, LOOKUPS, blinding, corrupt="gate" if seed > honest else None, instances=instances, instance_len=5, public_inputs=public)
+            if self.dpk is None:
+                self.dpk = KG.keygen_device(self.params, w.cs, [f.cpu().numpy().view(np.uint64).reshape(-1, 4) for f in w.fixed], w.assembly)
+            pv = P.create_proof(self.params, self.dpk, w, P.TranscriptChallenges(self.dpk.vk, hash), blinding, lap=None, multiopen=multiopen)
+            self.proofs.append(pv.proof)
+            self.public.append([list(col) for col in w.instance_values])
+            self.plan = pv.plan
+            del pv, w
+        self.shape = {"advice": GATE_COLS + LOOKUPS, "lookups": LOOKUPS, "permutation_sets": self.dpk.vk.cs.num_permutation_sets, "random_poly": True}
+        self.honest, self.instances = honest, instances
+
+    def verify(self, proofs, public=None, **kw):
+        if self.instances:
+            kw["instances"] = self.public[:len(proofs)] if public is None else public
+        return P.verify_transcript_proofs(self.params, self.dpk.vk, K, proofs, self.shape, self.plan, self.hash, self.multiopen, **kw)
+
+    def close(self):
+        self.dpk.free()
+        self.params.close()
+
+
+@pytest.fixture(scope="module", params=["gwc", "shplonk"])
+def batch(request):
+    b = Batch(request.param)
+    yield b
+    b.close()
+
+
+def test_fold_equals_one_by_one_on_the_honest_batch_with_one_pairing_check(batch, checks):
+    honest = batch.proofs[:batch.honest]
+    assert len(set(honest)) == 5
+    assert batch.verify(honest, fold=True, fold_seed=SEED) == [True] * 5 and checks == [1]
+    assert batch.verify(honest) == [True] * 5 and checks == [1]                     # the one-by-one path makes none of these
+    assert batch.verify(honest, fold=True) == [True] * 5 and checks == [2]          # multipliers from os.urandom
+    assert P.verify_transcript_proof(batch.params, batch.dpk.vk, K, honest[0], batch.shape, batch.plan, batch.hash, batch.multiopen, fold=True) is True
+
+
+def test_the_identity_refuses_the_broken_witnesses_in_both_modes(batch, checks):
+    mixed = [batch.proofs[0], batch.proofs[5], batch.proofs[1], batch.proofs[6], batch.proofs[2]]
+    assert batch.verify(mixed) == [True, False, True, False, True]
+    assert batch.verify(mixed, fold=True, fold_seed=SEED) == [True, False, True, False, True] and checks == [1]
+    assert batch.verify(mixed, fold=True, fold_seed=SEED, identity=False) == [True] * 5 == batch.verify(mixed, identity=False)       # the openings alone accept all five
+
+
+def test_swapped_evaluations_refuse_that_proof_alone_in_both_modes(batch, checks):
+    shape, plan = batch.shape, batch.plan
+    first = 32 * (shape["advice"] + 3 * shape["lookups"] + shape["permutation_sets"] + int(shape["random_poly"]) + 3)      # the evaluations follow the commitments
+    a, b = plan.index(("advice", 0, 1)), plan.index(("advice", 2, 2))
+    proof = batch.proofs[3]
+    ea, eb = proof[first + 32 * a:first + 32 * a + 32], proof[first + 32 * b:first + 32 * b + 32]
+    assert ea != eb
+    swapped = bytearray(proof)
+    swapped[first + 32 * a:first + 32 * a + 32], swapped[first + 32 * b:first + 32 * b + 32] = eb, ea
+    proofs = batch.proofs[:3] + [bytes(swapped)] + [batch.proofs[4]]
+    want = [True, True, True, False, True]
+    assert batch.verify(proofs, identity=False) == want
+    assert batch.verify(proofs, identity=False, fold=True, fold_seed=SEED) == want and 2 <= checks[0] <= 1 + 2 * 3
+
+
+def test_truncated_proofs_are_refused_alone_and_an_empty_batch_is_empty(batch, checks):
+    cut = list(batch.proofs[:5])
+    cut[2] = cut[2][:-40]                                                          # the multi-open's last point is incomplete
+    cut[4] = cut[4][:200]                                                          # ... and this one ends among its commitments
+    assert batch.verify(cut) == [True, True, False, True, False]
+    assert batch.verify(cut, fold=True, fold_seed=SEED) == [True, True, False, True, False] and checks == [1]
+    assert batch.verify([], fold=True) == [] and checks == [1]
+
+
+def test_fold_with_an_instance_column(checks):
+    b = Batch("gwc", honest=3, broken=0, instances=1)
+    try:
+        assert b.verify(b.proofs, fold=True, fold_seed=SEED) == [True] * 3 == b.verify(b.proofs) and checks == [1]
+        wrong = [b.public[0], b.public[0], b.public[2]]                             # proof 1 against proof 0's public inputs
+        assert b.public[0] != b.public[1]
+        assert b.verify(b.proofs, wrong, fold=True, fold_seed=SEED) == [True, False, True] == b.verify(b.proofs, wrong)
+    finally:
+        b.close()
+
+
+def test_fold_under_the_poseidon_transcript(checks):
+    b = Batch("gwc", hash="poseidon", honest=2, broken=1)
+    try:
+        assert b.verify(b.proofs, fold=True, fold_seed=SEED) == [True, True, False] == b.verify(b.proofs) and checks == [1]
+    finally:
+        b.close()

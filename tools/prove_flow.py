@@ -112,7 +112,7 @@ def _verify_seeded(pv, params, corrupt_proof, on_proof, lap):
 
 def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk_file=None, lookups=1, batched=None, sharded_quotient=False,
         sharded_key=False, lookups_one_call=True, device_randomness=False, mock=False, on_witness=None, verify=False, corrupt_proof=None, on_proof=None, transcript=False, multiopen="shplonk", instances=0,
-        instance_len=4):
+        instance_len=4, fold=False):
     """instances: that many instance columns of `instance_len` public values each (prover.halo2_lib_witness ties every one to a gate input by a
     copy constraint): the mock step checks the witness against them, the prover absorbs them into the transcript behind the key and carries
     their columns through the permutation argument and the quotient without committing or opening them, and the verify step hands the values
@@ -138,7 +138,7 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
     Poseidon transcript (transcript.PoseidonWrite; True and "blake2b" are Blake2b); multiopen="gwc" (transcript flows only): the GWC multi-open
     instead of SHPLONK, lap `multiopen_gwc`.  run(transcript="poseidon", multiopen="gwc") is the pair the reference's `gen_snark` proves under
     (/root/reference/aggregator/src/wrapper.rs:111-158).  With verify as well, `verify_transcript_proof` gets
-    (params, vk, the proof bytes, shape and plan) after the prover's tensors are dropped, and checks the identity at x and the openings.  corrupt_proof=("byte", i) flips bit 0 of proof byte i
+    (params, vk, the proof bytes, shape and plan) after the prover's tensors are dropped, and checks the identity at x and the openings (fold=True: the openings through the batch verifier, multiopen.fold_check).  corrupt_proof=("byte", i) flips bit 0 of proof byte i
     before that; the three named values belong to the seeded flow.  The mock step keeps the seeded theta.
     on_proof (with verify): a callable handed (params, k, queries, verifier queries, commit, (H, H'), (y, v, u)) after the verdict, while the
     polynomials are still in HBM (tools/verify_time.py measures the verifiers there, on the flow's own plan); its time goes to the lap `verify`.
@@ -225,10 +225,11 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
                 if byte_flip:
                     checked[corrupt_proof[1]] ^= 1
                 how = () if (tr_hash, multiopen) == ("blake2b", "shplonk") else (tr_hash, multiopen)      # the verifier's defaults
+                extra = {"fold": True} if fold else {}                                                     # (the default call is spelled as it always was)
                 if instances:
-                    proof_verifies = verify_transcript_proof(params, vk, k, bytes(checked), dict(shape), list(res["proof_plan"]), *how, instances=public)
+                    proof_verifies = verify_transcript_proof(params, vk, k, bytes(checked), dict(shape), list(res["proof_plan"]), *how, instances=public, **extra)
                 else:
-                    proof_verifies = verify_transcript_proof(params, vk, k, bytes(checked), dict(shape), list(res["proof_plan"]), *how)
+                    proof_verifies = verify_transcript_proof(params, vk, k, bytes(checked), dict(shape), list(res["proof_plan"]), *how, **extra)
             lap("verify")
         if verify:
             checks["proof_verifies"] = proof_verifies

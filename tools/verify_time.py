@@ -18,7 +18,11 @@ timed region ends with the verdict on the host.
       zkhip_verify_identity_device on the same records), the repetitions of the two alternating, a second series of the call without as the A/A
       figure; beside it the host path a caller had before the device evaluated instance columns: the same evaluations on Python integers with
       one batched inversion per proof, and their upload
-    python tools/verify_time.py [--reps 9] [--shapes 22:4:1,13:256:8,15:64:8] [--no-pairing] [--no-flow] [--no-srs] [--no-identity] [--no-instances]"""
+  the batch verifier: verify_transcript_proofs one by one against fold=True (one folded pairing check per batch, multiopen.fold_check) in this one
+      process, the two sides alternating, for B in {1, 4, 16, 64} proofs and both multi-opens on the same shapes; the batch is ONE proof's bytes
+      repeated B times (an honest input for timing: every copy is read, checked and folded like any other proof; the output says so); and the two
+      calls behind it alone, zkhip_gwc_scalars_device and zkhip_fr_fold_rows_device, at B = 1, 64 and 4096 on random records
+    python tools/verify_time.py [--reps 9] [--shapes 22:4:1,13:256:8,15:64:8] [--no-pairing] [--no-flow] [--no-srs] [--no-identity] [--no-instances] [--no-batch]"""
 import argparse
 import os
 import statistics
@@ -44,6 +48,9 @@ ap.add_argument("--no-identity", action="store_true")
 ap.add_argument("--batches", default="1,64,4096")
 ap.add_argument("--no-instances", action="store_true")
 ap.add_argument("--instance-len", type=int, default=30)
+ap.add_argument("--no-batch", action="store_true")
+ap.add_argument("--fold-batches", default="1,4,16,64")
+ap.add_argument("--batch-reps", type=int, default=3)
 args = ap.parse_args()
 lib = _lib.load()
 R = O.R_MOD
@@ -258,3 +265,66 @@ if not args.no_instances:
                 print(f"    B = {B:5d}  {name:15s}                              {fmt(ts)}")
             print(f"    B = {B:5d}  added by the column on the device {med['with'] - med['without']:+.3f} ms (A/A {med['without (A/A)'] - med['without']:+.3f} ms); "
                   f"host integers + upload {med['host']:.3f} ms")
+
+# ---- the batch verifier: one folded pairing check per batch against one check per proof ------------------------------------------------------------
+if not args.no_batch:
+    import prove_flow
+    from zksnap_circuits_halo2_amd import evaluation as E, prover as P
+
+    def series(sides, reps):
+        """the sides in turn, `reps` times, after one round that warms clocks and scratch: {name: [ms]}"""
+        out = {name: [] for name, _ in sides}
+        for rep in range(reps + 1):
+            for name, fn in sides:
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if rep:
+                    out[name].append((time.perf_counter() - t) * 1e3)
+        return out
+
+    for shape in args.shapes.split(","):
+        k, g, l = (int(x) for x in shape.split(":"))
+        for mo in ("gwc", "shplonk"):
+            print(f"==== batch verifier, shape k = {k}, {g} gate columns, {l} lookups, multiopen = {mo}: one proof's bytes repeated B times "
+                  f"({args.batch_reps} alternating repetitions, wall ms) ====")
+
+            def measure(params, vk, k_, proof, shape_, plan_, *how):
+                for B in (int(b) for b in args.fold_batches.split(",")):
+                    batch = [proof] * B
+                    one_by_one = lambda: P.verify_transcript_proofs(params, vk, k_, batch, shape_, plan_, *how)
+                    folded = lambda: P.verify_transcript_proofs(params, vk, k_, batch, shape_, plan_, *how, fold=True)
+                    assert one_by_one() == [True] * B == folded()
+                    got = series((("one by one", one_by_one), ("fold=True", folded)), args.batch_reps)
+                    for name, ts in got.items():
+                        print(f"    B = {B:3d}  {name:12s}                                  {fmt(ts)}   ({statistics.median(ts) / B:.2f} ms a proof)")
+                    print(f"    B = {B:3d}  one by one / fold = {statistics.median(got['one by one']) / statistics.median(got['fold=True']):.2f}")
+                return True
+
+            real = prove_flow.verify_transcript_proof
+            prove_flow.verify_transcript_proof = measure
+            try:
+                prove_flow.run(k, g, lookups=l, verbose=False, transcript=True, verify=True, multiopen=mo)
+            finally:
+                prove_flow.verify_transcript_proof = real
+        # the two calls alone, on random records
+        cs = E.halo2_lib_shape(g, l)
+        plan = P.opening_plan(cs, g, l, (1 << k) - (cs.blinding_factors + 1), False, "halo2")
+        gp = MO.gwc_plan(plan)
+        n_cols, n_own = gp.n_sets + gp.n_slots + 1, gp.n_sets + len(gp.own_keys)
+        print(f"==== the batch verifier's two calls alone, shape k = {k}, {g} gate columns, {l} lookups: {gp.n_evals} queries, {gp.n_sets} sets, {gp.n_slots} polynomials "
+              f"({n_cols} columns, {n_own} own); random records in HBM, a timed region ends with a device synchronise ====")
+        for B in (int(b) for b in args.batches.split(",")):
+            evals, points, r = random_elements(B, gp.n_evals), random_elements(B, 3), random_elements(B)
+            def scalars():
+                MO.gwc_scalars_device(gp, evals, points, k)
+                torch.cuda.synchronize()
+            rows_a, _ = MO.gwc_scalars_device(gp, evals, points, k)
+            out_own, out_shared = torch.empty((B * n_own, 4), dtype=torch.int64, device="cuda"), torch.empty((n_cols - n_own, 4), dtype=torch.int64, device="cuda")
+            def fold():
+                MO.fold_rows_device(rows_a, n_own, r, False, out_own, out_shared)
+                torch.cuda.synchronize()
+            print(f"    B = {B:5d}  zkhip_gwc_scalars_device (plan marshalled in the call)   {fmt(timed(scalars))}")
+            print(f"    B = {B:5d}  zkhip_fr_fold_rows_device                                {fmt(timed(fold))}")
+            del evals, points, r, rows_a, out_own, out_shared

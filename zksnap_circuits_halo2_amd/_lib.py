@@ -184,6 +184,8 @@ _SIGS = {
     "zkhip_verify_identity_instances_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                          C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_size_t,
                                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkhip_gwc_scalars_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkhip_fr_fold_rows_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_test_reduce512": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zkhip_test_transcript_chunk": (C.c_uint32, [C.c_size_t]),
     "zkhip_profile_enable": (C.c_int, [C.c_int]),
@@ -205,6 +207,12 @@ class ProverQueryC(C.Structure):   # zkhip_prover_query (80 bytes)
 class ImtWitness(C.Structure):      # zkhip_imt_witness: six device pointers
     _fields_ = [("d_roots", C.c_void_p), ("d_low_leaves", C.c_void_p), ("d_new_leaves", C.c_void_p), ("d_low_indices", C.c_void_p),
                 ("d_low_proofs", C.c_void_p), ("d_new_proofs", C.c_void_p)]
+
+
+class GwcPlan(C.Structure):         # struct zkhip_gwc_plan (48 bytes): passed by address (ctypes.byref) where the table above says c_void_p
+    _fields_ = [("n_evals", C.c_uint32), ("n_sets", C.c_uint32), ("n_slots", C.c_uint32), ("reserved", C.c_uint32),
+                ("set_rotation", C.POINTER(C.c_uint32)), ("query_set", C.POINTER(C.c_uint32)), ("query_pos", C.POINTER(C.c_uint32)),
+                ("query_slot", C.POINTER(C.c_uint32))]
 
 
 class CheckReport(C.Structure):     # zkhip_check_report (16 bytes)

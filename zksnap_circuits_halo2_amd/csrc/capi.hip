@@ -1999,6 +1999,50 @@ int zkhip_fr_instance_evals_device(uint32_t k, const uint64_t omega[4], const vo
   return fr_instance_evals_device(k, omega, (const uint32_t*)d_x, (const uint32_t*)d_instances, lay, n_proofs, (uint32_t*)d_out, caller_stream(stream));
 }
 
+// ---- the batch verifier's scalar side (include/zkhip.h; gwc_fold.hip): refusals before the device is touched, then nothing waits for the stream ----
+int zkhip_gwc_scalars_device(const zkhip_gwc_plan* plan, const void* d_evals, const void* d_points, uint32_t k, const uint64_t omega[4], size_t n_proofs,
+                             void* d_rows_a, void* d_rows_c, void* stream) {
+  ZK_API_RANGE();
+  int rc = gwc_plan_validate(plan, k, omega);
+  if (rc != ZKHIP_OK) return rc;
+  if (n_proofs > ((size_t)1 << 24)) { set_error("gwc_scalars: %zu proofs in one call", n_proofs); return ZKHIP_EINVAL; }
+  if (n_proofs == 0) return ZKHIP_OK;                                // nothing to write
+  if (!elems_ptr_ok(d_evals) || !elems_ptr_ok(d_points) || !elems_ptr_ok(d_rows_a) || !elems_ptr_ok(d_rows_c)) {
+    set_error("gwc_scalars: null or misaligned pointer");
+    return ZKHIP_EINVAL;
+  }
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->ws.reserve(gwc_scalars_workspace_bytes(plan))) != ZKHIP_OK) return rc;
+  return gwc_scalars_device(plan, (const uint32_t*)d_evals, (const uint32_t*)d_points, k, omega, n_proofs, (uint32_t*)d_rows_a, (uint32_t*)d_rows_c, sc->ws.p, sc->ws.cap, s,
+                            &sc->args);
+}
+
+int zkhip_fr_fold_rows_device(const void* d_rows, uint32_t n_cols, uint32_t n_own, const void* d_r, int negate, size_t n_rows, void* d_out_own, void* d_out_shared,
+                              void* stream) {
+  ZK_API_RANGE();
+  const char* who = "fr_fold_rows";
+  if (n_cols < 1 || n_cols > 65536 || n_own > n_cols) { set_error("%s: n_cols = %u (1 .. 65536), n_own = %u", who, n_cols, n_own); return ZKHIP_EINVAL; }
+  if (negate != 0 && negate != 1) { set_error("%s: negate = %d", who, negate); return ZKHIP_EINVAL; }
+  if (n_rows > ((size_t)1 << 24) || (uint64_t)n_rows * n_cols > ((uint64_t)1 << 32)) { set_error("%s: %zu rows of %u columns", who, n_rows, n_cols); return ZKHIP_EINVAL; }
+  const uint32_t n_shared = n_cols - n_own;
+  if ((n_rows && (!elems_ptr_ok(d_rows) || !elems_ptr_ok(d_r) || (n_own && !elems_ptr_ok(d_out_own)))) || (n_shared && !elems_ptr_ok(d_out_shared))) {
+    set_error("%s: null or misaligned pointer", who);
+    return ZKHIP_EINVAL;
+  }
+  if (n_rows == 0 && n_shared == 0) return ZKHIP_OK;                 // nothing to write
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->ws.reserve(fold_rows_workspace_bytes(n_cols, n_own, n_rows))) != ZKHIP_OK) return rc;
+  return fold_rows_device((const uint32_t*)d_rows, n_cols, n_own, (const uint32_t*)d_r, (uint32_t)negate, n_rows, (uint32_t*)d_out_own, (uint32_t*)d_out_shared, sc->ws.p,
+                          sc->ws.cap, s);
+}
+
 int zkhip_lookup_permute(const uint64_t* input, const uint64_t* table, size_t usable_rows, uint64_t* permuted_input, uint64_t* permuted_table) {
   ZK_API_RANGE();
   if (usable_rows && (!input || !table || !permuted_input || !permuted_table)) { set_error("lookup_permute: null pointer"); return ZKHIP_EINVAL; }

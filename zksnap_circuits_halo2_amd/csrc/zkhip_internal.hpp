@@ -316,6 +316,16 @@ int verify_identity_device(const zkhip_vm_program* prog, const uint32_t* d_evals
                            const uint64_t* omega, const uint32_t* d_instances, const instance_layout& lay, uint64_t n_proofs, int32_t* d_status, void* d_report,
                            void* cols_ws, void* vm_ws, size_t vm_ws_bytes, hipStream_t stream, vm_staging* staging = nullptr);
 
+// gwc_fold.hip (include/zkhip.h, "the batch verifier").  The validator touches no device; `ws` holds the plan as the kernel reads it / the
+// second level's partial sums.
+int gwc_plan_validate(const zkhip_gwc_plan* plan, uint32_t k, const uint64_t* omega);
+size_t gwc_scalars_workspace_bytes(const zkhip_gwc_plan* plan);
+int gwc_scalars_device(const zkhip_gwc_plan* plan, const uint32_t* d_evals, const uint32_t* d_points, uint32_t k, const uint64_t* omega, uint64_t n_proofs,
+                       uint32_t* d_rows_a, uint32_t* d_rows_c, void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
+size_t fold_rows_workspace_bytes(uint32_t n_cols, uint32_t n_own, uint64_t n_rows);
+int fold_rows_device(const uint32_t* d_rows, uint32_t n_cols, uint32_t n_own, const uint32_t* d_r, uint32_t negate, uint64_t n_rows, uint32_t* d_out_own,
+                     uint32_t* d_out_shared, void* ws, size_t ws_bytes, hipStream_t stream);
+
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);
 int g1_check_points_device(const uint32_t* d_points, size_t n, unsigned long long* d_first_bad, hipStream_t stream);

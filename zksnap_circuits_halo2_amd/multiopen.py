@@ -517,3 +517,193 @@ class VerifierSHPLONK:
                 return False
             raise
         return self.verify_proof(queries, H, Hp, y, v, u)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The batch verifier: the opening checks of a batch folded into one pairing check (halo2's `BatchVerifier`; the reference's aggregator folds
+# its KZG accumulators with random powers the same way, `KzgAs<Bn256, Gwc19>`, /root/reference/aggregator/src/wrapper.rs).  The openings of
+# proof i accept exactly when e(A_i, g2) e(-C_i, [s]g2) = 1; with random r_i the batch accepts, except with probability about 1 / r, exactly
+# when e(sum r_i A_i, g2) e(-sum r_i C_i, [s]g2) = 1.  A_i and C_i are given as ROWS of scalars over points: the proof's own points (different
+# in every proof: their scalars are scaled by r_i) and shared points (the key's commitments and G: their scalars are summed over the proofs).
+# BN254 G1 has cofactor 1 and the transcript readers check every point, so nothing here checks a subgroup.
+# ---------------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class GwcPlan:
+    """An opening plan as the GWC verifier groups it (include/zkhip.h, zkhip_gwc_plan): query q is triple q of the plan.  `set_rotation`: the
+    rotations as the plan spells them, in order of first appearance -- `construct_intermediate_sets` grouped by rotation, which is what grouping
+    by point gives for every x but 0; `query_pos`: a query's position inside its set (the exponent of v); `query_slot`: the slot of its
+    polynomial, the proof's own polynomials (`own_keys`, in order of first appearance) first and the key's (`shared_keys`) behind them.
+    `repeated`: a (kind, index, rotation) triple occurs twice, which the set construction would fold into one query: such a plan is verified
+    one by one, as is one with two rotations equal mod 2^k (`foldable`)."""
+    n_evals: int
+    set_rotation: List[int]
+    query_set: List[int]
+    query_pos: List[int]
+    query_slot: List[int]
+    own_keys: List[tuple]
+    shared_keys: List[tuple]
+    repeated: bool
+
+    @property
+    def n_sets(self) -> int:
+        return len(self.set_rotation)
+
+    @property
+    def n_slots(self) -> int:
+        return len(self.own_keys) + len(self.shared_keys)
+
+    def foldable(self, k: int) -> bool:
+        """may the batch verifier group this plan by rotation at 2^k rows?  Not with a repeated triple, and not with two rotations equal mod 2^k
+        (their sets are one set of points): such plans are verified one by one, which groups by point"""
+        return not self.repeated and len({r % (1 << k) for r in self.set_rotation}) == len(self.set_rotation)
+
+    def marshal(self, k: int):
+        """-> (_lib.GwcPlan, the arrays it points into): rotations reduced mod 2^k.  ValueError: two rotations of the plan are equal mod 2^k
+        (their sets would be one set)"""
+        rot = [r % (1 << k) for r in self.set_rotation]
+        if len(set(rot)) != len(rot):
+            raise ValueError("gwc_plan: two rotations of the plan are equal mod 2^k")
+        arrays = [np.array(a, dtype=np.uint32) for a in (rot, self.query_set, self.query_pos, self.query_slot)]
+        ptr = [a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in arrays]
+        return _lib.GwcPlan(self.n_evals, self.n_sets, self.n_slots, 0, *ptr), arrays
+
+
+def gwc_plan(plan_triples, shared_kinds=("fixed", "sigma")) -> GwcPlan:
+    """the GwcPlan of the opened (kind, index, rotation) triples (prover.opening_plan); polynomials of a kind in `shared_kinds` are the key's"""
+    rotations, counts, slots = [], [], {}
+    q_set, q_pos, keys = [], [], []
+    for kind, idx, rot in plan_triples:
+        if rot not in rotations:
+            rotations.append(rot)
+            counts.append(0)
+        s = rotations.index(rot)
+        q_set.append(s)
+        q_pos.append(counts[s])
+        counts[s] += 1
+        keys.append((kind, idx))
+    own = list(dict.fromkeys(key for key in keys if key[0] not in shared_kinds))
+    shared = list(dict.fromkeys(key for key in keys if key[0] in shared_kinds))
+    for key in own + shared:
+        slots[key] = len(slots)
+    triples = [tuple(t) for t in plan_triples]
+    return GwcPlan(len(triples), rotations, q_set, q_pos, [slots[key] for key in keys], own, shared, len(set(triples)) != len(triples))
+
+
+def gwc_scalars_device(plan: GwcPlan, evals, points, k: int, stream=None):
+    """zkhip_gwc_scalars_device: evals (B, n_evals, 4), points (B, 3, 4) = x, v, u, contiguous int64 device tensors -> (rows_a (B, n_sets +
+    n_slots + 1, 4), rows_c (B, n_sets, 4)), the column layout of include/zkhip.h.  Asynchronous on `stream`."""
+    import torch
+
+    from .fields import omega_for
+
+    B = evals.shape[0]
+    if not (evals.is_cuda and evals.is_contiguous() and points.is_cuda and points.is_contiguous()) or tuple(evals.shape) != (B, plan.n_evals, 4) or \
+            tuple(points.shape) != (B, 3, 4):
+        raise ValueError("gwc_scalars_device: contiguous device tensors, (B, n_evals, 4) and (B, 3, 4)")
+    struct, keep = plan.marshal(k)
+    rows_a = torch.empty((B, plan.n_sets + plan.n_slots + 1, 4), dtype=torch.int64, device=evals.device)
+    rows_c = torch.empty((B, plan.n_sets, 4), dtype=torch.int64, device=evals.device)
+    omega = fr_encode([omega_for(k)])[0]
+    _lib.check(_lib.load().zkhip_gwc_scalars_device(C.byref(struct), evals.data_ptr(), points.data_ptr(), k, omega.ctypes.data, B, rows_a.data_ptr(),
+                                                    rows_c.data_ptr(), stream))
+    del keep
+    return rows_a, rows_c
+
+
+def fold_rows_device(rows, n_own: int, r, negate: bool, out_own, out_shared, stream=None) -> None:
+    """zkhip_fr_fold_rows_device over rows (n, n_cols, 4) and multipliers r (n, 4): out_own (n * n_own elements) = +- r_i rows[i][j],
+    out_shared (n_cols - n_own elements) = +- sum_i r_i rows[i][n_own + j]; either output may be None where it has no element"""
+    n, n_cols = rows.shape[0], rows.shape[1]
+    _lib.check(_lib.load().zkhip_fr_fold_rows_device(rows.data_ptr() if n else None, n_cols, n_own, r.data_ptr() if n else None, int(bool(negate)), n,
+                                                     out_own.data_ptr() if out_own is not None and out_own.numel() else None,
+                                                     out_shared.data_ptr() if out_shared is not None and out_shared.numel() else None, stream))
+
+
+def _pairing_verdict(d_g1, d_g2, stream=None) -> bool:
+    """THE final check of the batch verifier: zkhip_pairing_check_device over two pairs; its uint32 verdict is the only thing read back, behind the
+    one host wait of a folded check.  Every folded check goes through this function (a test counts the calls)."""
+    import torch
+
+    lib = _lib.load()
+    ok = torch.empty(1, dtype=torch.int32, device=d_g1.device)
+    _lib.check(lib.zkhip_pairing_check_device(d_g1.data_ptr(), d_g2.data_ptr(), 2, ok.data_ptr(), stream))
+    if stream:
+        _lib.check(lib.zkhip_stream_sync(stream))
+    return bool(int(ok.cpu()[0]))
+
+
+def fold_check(params, rows_a, rows_c, own_points, shared_points, seed=None, stream_id: int = 0, stream=None) -> List[bool]:
+    """The openings of B proofs decided by folded pairing checks -> B bools.  Device tensors (int64, contiguous): own_points (B, m, 8) affine, the
+    multi-open's own points first; shared_points (t, 8); rows_a (B, m + t, 4), the scalars of A_i over [own points | shared points]; rows_c
+    (B, c, 4), the scalars of C_i over the first c own points.  One check: r_0 .. r_(B-1) from zkhip_fr_random_device, two folds (the C side
+    negated), two zkhip_msm_g1_device -- the A side over [own points | shared] with [r_i-scaled own scalars | shared sums], the C side over
+    the B c own points --, zkhip_g1_batch_normalize_device on the two sums and one pairing check (`_pairing_verdict`).  A batch that fails is
+    bisected with the same r_i: a failing range is split, its left half checked; if that passes the right half fails by bilinearity and is
+    split in turn without a check of its own; a failing range of one proof is refused.  One bad proof among 16 costs at most 9 checks.
+    seed: 32 bytes, the seed of the library's random stream (`stream_id`, elements 0 .. B - 1); None draws them from os.urandom -- the library
+    holds no entropy.  A prover must not be able to predict r: a fixed seed is for tests.  r_i = 0 (probability 2^-254) is not handled.
+    `stream`: None (torch's default stream, on which the tensors here are allocated) or a stream the caller keeps ordered with them."""
+    import os
+
+    import torch
+
+    B, m = own_points.shape[0], own_points.shape[1]
+    t, c = shared_points.shape[0], rows_c.shape[1]
+    for name, ten, shape in (("rows_a", rows_a, (B, m + t, 4)), ("rows_c", rows_c, (B, c, 4)), ("own_points", own_points, (B, m, 8)), ("shared_points", shared_points, (t, 8))):
+        if not (ten.is_cuda and ten.is_contiguous() and ten.dtype == torch.int64) or tuple(ten.shape) != shape:
+            raise ValueError(f"fold_check: {name} is a contiguous int64 device tensor of shape {shape}")
+    if not 1 <= c <= m:
+        raise ValueError("fold_check: rows_c runs over the first c own points, 1 <= c <= m")
+    if B == 0:
+        return []
+    if params.g2 is None or params.s_g2 is None:
+        raise ValueError("the verifier needs g2 and s_g2")
+    seed = os.urandom(32) if seed is None else bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("the seed is 32 bytes")
+    lib = _lib.load()
+    dev = own_points.device
+    r = torch.empty((B, 4), dtype=torch.int64, device=dev)
+    _lib.check(lib.zkhip_fr_random_device(seed, stream_id, 0, B, r.data_ptr(), stream))
+    g2 = torch.from_numpy(np.stack([np.asarray(params.g2, dtype=np.uint64).reshape(16), np.asarray(params.s_g2, dtype=np.uint64).reshape(16)]).view(np.int64)).to(dev)
+    c_points = own_points[:, :c, :].contiguous()
+    scal_a = torch.empty((B * m + t, 4), dtype=torch.int64, device=dev)
+    scal_c = torch.empty((B * c, 4), dtype=torch.int64, device=dev)
+    sums = torch.empty((2, 12), dtype=torch.int64, device=dev)
+    pair = torch.empty((2, 8), dtype=torch.int64, device=dev)
+    all_bases = torch.cat([own_points.reshape(B * m, 8), shared_points])
+
+    def check(lo, hi):
+        n = hi - lo
+        fold_rows_device(rows_a[lo:hi], m, r[lo:hi], False, scal_a[:n * m], scal_a[n * m:n * m + t], stream)
+        fold_rows_device(rows_c[lo:hi], c, r[lo:hi], True, scal_c[:n * c], None, stream)
+        bases = all_bases if n == B else torch.cat([own_points[lo:hi].reshape(n * m, 8), shared_points])
+        _lib.check(lib.zkhip_msm_g1_device(scal_a.data_ptr(), bases.data_ptr(), n * m + t, sums[0].data_ptr(), stream))
+        _lib.check(lib.zkhip_msm_g1_device(scal_c.data_ptr(), c_points[lo:hi].data_ptr(), n * c, sums[1].data_ptr(), stream))
+        _lib.check(lib.zkhip_g1_batch_normalize_device(sums.data_ptr(), 2, pair.data_ptr(), stream))
+        return _pairing_verdict(pair, g2, stream)
+
+    verdicts = [False] * B
+
+    def accept(lo, hi):
+        verdicts[lo:hi] = [True] * (hi - lo)
+
+    def failing(lo, hi):                      # a range known to fail
+        if hi - lo == 1:
+            return
+        mid = (lo + hi) // 2
+        if check(lo, mid):
+            accept(lo, mid)
+            failing(mid, hi)                  # by bilinearity
+            return
+        failing(lo, mid)
+        if check(mid, hi):
+            accept(mid, hi)
+        else:
+            failing(mid, hi)
+
+    if check(0, B):
+        accept(0, B)
+    else:
+        failing(0, B)
+    return verdicts

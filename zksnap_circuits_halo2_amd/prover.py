@@ -213,11 +213,14 @@ def multiopen_classes(multiopen):
     return MULTIOPEN[multiopen]
 
 
-def _read_proof_head(r, vk_repr, shape, plan, instances=()):
+def _read_proof_head(r, vk_repr, shape, plan, instances=(), on_device=False):
     """a proof up to its evaluations, in the prover's order: (commitments by (kind, index), (theta, beta, gamma, y, x), the evaluations as
     integers); the reader is left in front of the multi-open's part.  instances: the proof's public inputs, one list of integers per instance
-    column, absorbed behind the key.  ZkhipError(-1): bytes that do not decode"""
+    column, absorbed behind the key.  on_device: the commitments stay in HBM, each an (8,) affine device tensor (the batch verifier's MSMs read
+    them there).  ZkhipError(-1): bytes that do not decode"""
     def xyz(points):                                       # device affine points -> Jacobian limbs with z = 1 for the host-side accumulation
+        if on_device:
+            return list(points)
         return [MO._affine_to_xyz(p_) for p_ in points.cpu().numpy().view(np.uint64).reshape(-1, 8)]
 
     n_adv, n_lk, n_sets = shape["advice"], shape["lookups"], shape["permutation_sets"]
@@ -267,17 +270,19 @@ def _check_instances(cs, k, instances, proofs):
     return lens
 
 
-def identity_statuses(vk, k, plan, evals, challenges, instances=None):
+def identity_statuses(vk, k, plan, evals, challenges, instances=None, d_evals=None):
     """zkhip_verify_identity_device over a batch: evals[i] the integers of proof i in the plan's order, challenges[i] = (theta, beta, gamma, y,
     x); for a circuit with instance columns instances[i] = proof i's public inputs, a list of integers per column, evaluated on the device
-    (zkhip_verify_identity_instances_device).  An int32 array: 0 the identity holds, 1 it does not, 2 x lies in the domain."""
+    (zkhip_verify_identity_instances_device).  d_evals: the evaluations as a (proofs, len(plan), 4) device tensor where the caller has uploaded
+    them already (the batch verifier reads the same records).  An int32 array: 0 the identity holds, 1 it does not, 2 x lies in the domain."""
     n_instance = vk.cs.num_instance if getattr(vk, "cs", None) is not None else 0
     if n_instance and instances is None:
         raise ValueError("identity_statuses: the circuit has instance columns: hand in the proofs' public inputs (instances=)")
     if not evals:
         return np.zeros(0, dtype=np.int32)
     prog = identity_program_of(vk, plan, k)
-    d_evals = words([e_ for row in evals for e_ in row]).reshape(len(evals), len(plan), 4)
+    if d_evals is None:
+        d_evals = words([e_ for row in evals for e_ in row]).reshape(len(evals), len(plan), 4)
     d_challenges = words([c_ for row in challenges for c_ in row]).reshape(len(evals), 5, 4)
     usable = (1 << k) - (vk.cs.blinding_factors + 1)
     if not n_instance:
@@ -288,7 +293,83 @@ def identity_statuses(vk, k, plan, evals, challenges, instances=None):
     return E.verify_identity_device(prog, d_evals, d_challenges, k, usable, instances=d_instances, column_lens=lens, queries=E.instance_queries(vk.cs))[0]
 
 
-def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b", multiopen="shplonk", *, identity=True, instances=None):
+def gwc_plan_of(vk, plan):
+    """multiopen.gwc_plan of `plan`, made once per (key, plan) and kept on the key object beside the identity program"""
+    cache = vk.__dict__.setdefault("_gwc_plans", {})
+    key = tuple(plan)
+    if key not in cache:
+        cache[key] = MO.gwc_plan(plan)
+    return cache[key]
+
+
+def _host_xyz(point):
+    """an (8,) affine device tensor -> Jacobian limbs with z = 1 on the host"""
+    return MO._affine_to_xyz(point.cpu().numpy().view(np.uint64))
+
+
+def _fold_openings(params, vk, k, plan, multiopen, heads, order, d_evals, rows_of, fold_seed, verdicts):
+    """The openings of the proofs `order` (their heads read with on_device=True, the readers in front of the multi-open's part) decided by
+    multiopen.fold_check.  d_evals: the uploaded evaluations, rows_of[i] the row of proof i in them.  A proof whose multi-open part does not
+    decode is refused alone; a proof with x = 0 mod r (where the grouping by rotation and halo2's grouping by point differ) is verified on its
+    own by the multi-open's verifier."""
+    gp = gwc_plan_of(vk, plan)
+    key_points = {("fixed", i): c for i, c in enumerate(vk.fixed_commitments)}
+    key_points.update({("sigma", i): c for i, c in enumerate(vk.permutation_commitments)})
+    shared = np.stack([np.asarray(key_points[key_], dtype=np.uint64).reshape(8) for key_ in gp.shared_keys] + [np.asarray(params.g[0], dtype=np.uint64).reshape(8)])
+    d_shared = torch.from_numpy(shared.view(np.int64)).to(DEV)
+    folded, own, points, rows_a, rows_c = [], [], [], [], []
+    for i in order:
+        r, com, challenges, evals = heads[i]
+        x = challenges[4]
+        try:
+            if x % R == 0:
+                host = {key_: _host_xyz(c_) for key_, c_ in com.items()}
+                host.update(_key_commitments(vk))
+                verdicts[i] = bool(multiopen_classes(multiopen)[1](params).verify_proof_transcript(verifier_queries(plan, host, evals, x, k), r))
+                continue
+            if multiopen == "gwc":
+                v = r.squeeze_challenge()
+                mine = r.read_points(gp.n_sets)
+                u = r.squeeze_challenge()
+                points.append((x, v, u))
+            else:
+                y, v = r.squeeze_challenge(), r.squeeze_challenge()
+                H = r.read_points(1)
+                u = r.squeeze_challenge()
+                Hp = r.read_points(1)
+                mine = torch.cat([Hp, H])
+                # the host's accumulation groups by (kind, index) and reads no commitment: one placeholder stands for all of them
+                nothing = np.zeros(12, dtype=np.uint64)
+                queries = verifier_queries(plan, {key_: nothing for key_ in gp.own_keys + gp.shared_keys}, evals, x, k)
+                scalars, keys = MO.shplonk_accumulate(queries, y, v, u)
+                by_key = {}
+                for key_, s_ in zip(keys, scalars):
+                    by_key[key_] = (by_key.get(key_, 0) + s_) % R
+                g_scalar, h_scalar, hp_scalar = scalars[len(keys):]
+                rows_a.append([hp_scalar, h_scalar] + [by_key[key_] for key_ in gp.own_keys] + [by_key[key_] for key_ in gp.shared_keys] + [g_scalar])
+                rows_c.append([1])
+        except _lib.ZkhipError as e:                       # the multi-open's own points do not decode
+            if e.code != -1:
+                raise
+            continue
+        folded.append(i)
+        own.append(torch.cat([mine, torch.stack([com[key_] for key_ in gp.own_keys])]) if gp.own_keys else mine)
+    if not folded:
+        return
+    d_own = torch.stack(own).contiguous()
+    if multiopen == "gwc":
+        index = torch.tensor([rows_of[i] for i in folded], dtype=torch.int64, device=DEV)
+        d_points = words([c_ for row in points for c_ in row]).reshape(len(folded), 3, 4)
+        d_rows_a, d_rows_c = MO.gwc_scalars_device(gp, d_evals.index_select(0, index).contiguous(), d_points, k)
+    else:
+        d_rows_a = words([s_ for row in rows_a for s_ in row]).reshape(len(folded), len(rows_a[0]), 4)
+        d_rows_c = words([s_ for row in rows_c for s_ in row]).reshape(len(folded), 1, 4)
+    for i, ok in zip(folded, MO.fold_check(params, d_rows_a, d_rows_c, d_own, d_shared, fold_seed)):
+        verdicts[i] = bool(ok)
+
+
+def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b", multiopen="shplonk", *, identity=True, instances=None, fold=False,
+                             fold_seed=None):
     """The verifier of a BATCH of proofs of one circuit, each written through TranscriptChallenges: it is handed the parameters, the verifying key
     (with its constraint system, `vk.cs`), the proofs' BYTES, and what a verifier knows of the circuit -- `shape` (how many advice columns,
     lookups, permutation sets, whether a random polynomial is committed) and `plan` (the opened (kind, index, rotation) triples, in the order
@@ -305,8 +386,15 @@ def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b",
     inputs; never part of the proof).  They are absorbed into proof i's transcript behind the key, as the prover absorbed its own, so wrong
     inputs change every challenge, and they enter the identity through the instance columns' evaluations at x.  ValueError: a key whose
     circuit has instance columns and no `instances`; lengths that differ between the proofs or exceed the usable rows.
-    Not built: one folded pairing check for the batch (halo2's BatchVerifier), committed instance columns, multi-phase challenges (DESIGN.md
-    section 10).  Returns a list of bools."""
+    fold=True: the openings of the proofs that passed the identity are decided together by multiopen.fold_check (halo2's `BatchVerifier`): the
+    commitments stay in HBM, every proof's two accumulated points are rows of scalars -- multiopen="gwc": made by zkhip_gwc_scalars_device from
+    the evaluations the identity call read; "shplonk": by `shplonk_accumulate` on the host, as [H', H, own polynomials | key polynomials, G] --,
+    and ONE pairing check accepts the batch; a batch that fails is bisected.  The verdicts are those of fold=False (a wrong proof passes a
+    folded check with probability about 1 / r).  A proof with x = 0 mod r, a plan that repeats a triple and a plan with two rotations equal mod 2^k take the one-by-one path.
+    fold_seed: the 32 bytes the random multipliers are drawn from; None (what a verifier uses) draws them from os.urandom, a fixed seed is for
+    tests.
+    Not built: committed instance columns, multi-phase challenges; the SHPLONK scalars on the device, folding across
+    different circuits or parameter sets, a batch sharded over devices.  Returns a list of bools."""
     import contextlib
 
     verifier = multiopen_classes(multiopen)[1]
@@ -322,19 +410,28 @@ def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b",
     vk.write(vk_io, KG.RAW_BYTES)
     vk_repr = vk_transcript_repr(vk_io.getvalue())
     verdicts = [False] * len(proofs)
+    fold = bool(fold) and bool(proofs) and gwc_plan_of(vk, plan).foldable(k)
     with contextlib.ExitStack() as stack:
         heads = {}
         for i, proof in enumerate(proofs):
             r = stack.enter_context(reader(bytes(proof)))
             try:
-                heads[i] = (r,) + (_read_proof_head(r, vk_repr, shape, plan, instances[i]) if n_instance else _read_proof_head(r, vk_repr, shape, plan))
+                heads[i] = (r,) + _read_proof_head(r, vk_repr, shape, plan, instances[i] if n_instance else (), on_device=fold)
             except _lib.ZkhipError as e:
                 if e.code != -1:
                     raise
         order = sorted(heads)
+        rows_of = {i: row for row, i in enumerate(order)}
+        d_evals = None
+        if fold and order:                                 # uploaded once: the identity call and the GWC scalars read the same records
+            d_evals = words([e_ for i in order for e_ in heads[i][3]]).reshape(len(order), len(plan), 4)
         if identity:
-            status = identity_statuses(vk, k, plan, [heads[i][3] for i in order], [heads[i][2] for i in order], [instances[i] for i in order] if n_instance else None)
+            status = identity_statuses(vk, k, plan, [heads[i][3] for i in order], [heads[i][2] for i in order], [instances[i] for i in order] if n_instance else None,
+                                       d_evals=d_evals)
             order = [i for i, s_ in zip(order, status) if s_ == 0]
+        if fold:
+            _fold_openings(params, vk, k, plan, multiopen, heads, order, d_evals, rows_of, fold_seed, verdicts)
+            return verdicts
         key_com = _key_commitments(vk)
         for i in order:
             r, com, challenges, evals = heads[i]
@@ -347,11 +444,13 @@ def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b",
     return verdicts
 
 
-def verify_transcript_proof(params, vk, k, proof, shape, plan, hash="blake2b", multiopen="shplonk", instances=None):
+def verify_transcript_proof(params, vk, k, proof, shape, plan, hash="blake2b", multiopen="shplonk", instances=None, fold=False, fold_seed=None):
     """The verifier of one proof given as bytes: `verify_transcript_proofs` over a batch of one -- the identity at x and the openings, accepted
-    when both accept.  instances: the proof's public inputs, a list of integers per instance column.  ValueError: a verifying key without its
-    constraint system; a circuit with instance columns and no `instances`."""
-    return verify_transcript_proofs(params, vk, k, [proof], shape, plan, hash, multiopen, instances=None if instances is None else [instances])[0]
+    when both accept.  instances: the proof's public inputs, a list of integers per instance column.  fold, fold_seed: passed on (the openings
+    through the batch verifier's path).  ValueError: a verifying key without its constraint system; a circuit with instance columns and no
+    `instances`."""
+    return verify_transcript_proofs(params, vk, k, [proof], shape, plan, hash, multiopen, instances=None if instances is None else [instances], fold=fold,
+                                    fold_seed=fold_seed)[0]
 
 
 # ---- the witness -------------------------------------------------------------------------------------------------------------------------------

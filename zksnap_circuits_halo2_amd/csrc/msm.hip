@@ -31,6 +31,7 @@
 #include "ec_quad.hpp"
 #include "fe_inverse.hpp"
 #include "reduce_plan.hpp"
+#include "reduce_fuse.hpp"
 #include "zkhip_internal.hpp"
 
 namespace zkhip {
@@ -1391,6 +1392,35 @@ __global__ void __launch_bounds__(128) k_pyramid_pair_quad(const uint32_t* __res
   if ((gid & 7) == 0) store_xyzz(wo, o, r);
 }
 
+// Steps 1 and 2 in one launch where they fill the chip (reduce_fuse.hpp), one lane per chain of additions and the additions of the two single
+// steps exactly -- 10 per 8 buckets, same operands, same order -- so the output words are those of two k_pyramid_step launches, while the
+// state between the steps never goes to memory and every bucket is read once: [X (N)] becomes [X'' (N/4) | Z''^0 (N/8) | Z''^1 (N/8)].
+// Lane t < N/4 owns X[4t .. 4t+3]:
+//      z = X[4t+1] + X[4t+3]     a = X[4t] + X[4t+1]     b = X[4t+2] + X[4t+3]     X''[t] = a + b
+// and the lane pair (2v, 2v+1) exchanges one point: the even lane stores Z''^0[v] = z(2v) + z(2v+1), the odd one Z''^1[v] = b(2v) + b(2v+1).
+// At most four points are live at a time (z, X[4t+3], a, the load): 210 VGPRs, no scratch, two wavefronts per SIMD.  N >= 8, so N / 4 is even:
+// both lanes of a pair are live or dead together.
+__global__ void __launch_bounds__(128) k_pyramid_pair(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                      uint32_t N, uint32_t in_stride, uint32_t out_stride) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= N / 4) return;
+  const int win = blockIdx.y;
+  const uint32_t* wi = in + (size_t)win * in_stride * 36;
+  uint32_t* wo = out + (size_t)win * out_stride * 36;
+  const xyzz p3 = load_xyzz(wi, 4 * t + 3);
+  xyzz z, a;
+  {
+    const xyzz p1 = load_xyzz(wi, 4 * t + 1);
+    z = xyzz_add(p1, p3);
+    a = xyzz_add(load_xyzz(wi, 4 * t), p1);
+  }
+  const xyzz b = xyzz_add(load_xyzz(wi, 4 * t + 2), p3);
+  store_xyzz(wo, t, xyzz_add(a, b));
+  const bool odd = t & 1;
+  const xyzz other = xyzz_shfl_xor(odd ? z : b, 1);    // the even lane receives z(2v+1), the odd one b(2v)
+  store_xyzz(wo, N / 4 + (odd ? N / 8 : 0) + t / 2, xyzz_add(odd ? other : z, odd ? b : other));   // (one addition for both)
+}
+
 // 9a. per-window weighted sum.  Input state after the last pyramid step: X has 2 elements, Z^0..Z^(nz-1) one each.
 //     window sum = X0 + X1 + sum_l 2^l Z^l + 2^nz X1.  One 32-lane group per window: lane l < nz computes 2^l Z^l by l
 //     doublings, lane nz computes 2^nz X1, lane nz + 1 holds X0 + X1; a 4-step shuffle tree adds the terms.
@@ -1951,13 +1981,15 @@ static int msm_accumulate_combine(const msm_tasks_view& tv, const uint32_t* d_ba
 // prepared: every bucket set's weighted sum is a result (K = WB of them); otherwise the WB window sums are folded into one.
 static int msm_reduce_buckets(int WB, uint32_t B, int c, uint32_t K, bool prepared, uint32_t* cur, uint32_t* nxt, uint32_t* winsum, uint32_t* d_out, hipStream_t stream) {
   // 8. pyramid: buckets were written with window stride B (dense).  Steps 1 .. c-2 leave X with 2 elements.  The launches are a function of
-  // (B, WB) alone (reduce_plan.hpp): single-lane steps while a step fills the chip, then a quad per addition -- two levels per launch where
-  // that stays far below the chip's lane count --, and up to REDUCE_FINISH_MAX_SETS bucket sets end in one workgroup each (k_reduce_finish:
+  // (B, WB) alone (reduce_plan.hpp): single-lane steps while a step fills the chip -- the first two in one launch where that launch is
+  // one round of two wavefronts per SIMD (reduce_fuse.hpp) --, then a quad per addition -- two levels per launch where that stays far below the chip's
+  // lane count --, and up to REDUCE_FINISH_MAX_SETS bucket sets end in one workgroup each (k_reduce_finish:
   // the last levels, the weighted sum and, for prepared bases, the store).  Larger batches are throughput-bound and keep a launch per level.
   if (B == 1) { set_error("msm: internal: B == 1"); return ZKHIP_EINVAL; }     // (c >= 2, so B >= 2 always)
   reduce_plan plan;
   if (!reduce_make_plan(B, WB, &plan)) { set_error("msm: internal: no reduction plan for %u buckets x %d sets", B, WB); return ZKHIP_EINVAL; }
   const bool direct = prepared && WB <= 2048;     // the weighted-sum kernel writes the results itself (one launch less)
+  const bool fuse_first = reduce_fuse_first_pair(plan, WB);      // (reduce_fuse.hpp)
   for (int i = 0; i < plan.n; i++) {
     const reduce_launch& L = plan.l[i];
     if (L.kind == REDUCE_FINISH) {
@@ -1965,7 +1997,11 @@ static int msm_reduce_buckets(int WB, uint32_t B, int c, uint32_t K, bool prepar
       hipLaunchKernelGGL(k_reduce_finish, dim3(WB), dim3(FINISH_THREADS), 0, stream, cur, L.in_stride, L.N, L.s, winsum, direct ? d_out : (uint32_t*)nullptr);
       break;
     }
-    if (L.kind == REDUCE_STEP) hipLaunchKernelGGL(k_pyramid_step, dim3((L.out_stride + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride);
+    if (i == 0 && fuse_first) {                     // steps 1 and 2 in one launch: the buckets in, the state of l[1] out
+      hipLaunchKernelGGL(k_pyramid_pair, dim3((L.N / 4 + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.in_stride, plan.l[1].out_stride);
+      i++;
+    }
+    else if (L.kind == REDUCE_STEP) hipLaunchKernelGGL(k_pyramid_step, dim3((L.out_stride + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride);
     else if (L.kind == REDUCE_STEP_QUAD) hipLaunchKernelGGL(k_pyramid_step_quad, dim3((4 * L.out_stride + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride);
     else hipLaunchKernelGGL(k_pyramid_pair_quad, dim3((8 * L.out_stride + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride);
     uint32_t* t = cur; cur = nxt; nxt = t;

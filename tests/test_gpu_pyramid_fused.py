@@ -1,5 +1,5 @@
 """GPU: steps 1 - 4 of the bucket reduction, the chip-wide ones, of which steps 1 and 2 go in one launch where that launch is one round of two
-wavefronts per SIMD (csrc/msm.hip: k_pyramid_pair, msm_reduce_buckets; csrc/reduce_fuse.hpp), in the pattern of
+wavefronts per SIMD (csrc/msm.hip: k_pyramid_pair, msm_reduce_buckets; csrc/reduce_plan.hpp), in the pattern of
 tests/test_gpu_reduce_tail.py: 2^10 + 3 walk bases, tables forced to a window size, every result compared as an affine point with the
 structured identity of the bases (`bench.structured_point`), every expected point checked not to be the identity.  The cases are chosen by
 the steps they reach, not by which of them a build fuses: they hold for single steps as well.  One bucket set of 2^19 (c = 20) and the

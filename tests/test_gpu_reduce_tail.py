@@ -186,6 +186,36 @@ def test_bucket_sets_at_the_bound_of_the_finish_kernel(lib, walk_tables, batch):
     _check_batch(lib, walk_tables, 8, batch, 0x27B2 + batch)
 
 
+def test_more_bucket_sets_than_the_quad_weighted_sum_takes(lib):
+    """2049 vectors at c = 7, (B, WB) = (64, 2049): steps 1 and 2 are single-lane steps (48 x 2049 and 32 x 2049 additions exceed 65536),
+    steps 3 - 5 quad steps, then the single-lane k_window_horner and k_store_results, every launch with 2049 grid rows.  The table has its
+    own walk of 2^6 + 3 bases, so the sort sees about 5 M entries.  Rows 0, 1024, 2047 and 2048 carry vectors of their own; every other
+    row carries one shared vector, checked once against its identity and compared with the rest for equality."""
+    import torch
+
+    n, c, batch, t0 = (1 << 6) + 3, 7, 2049, T0 + 3
+    own = [0, 1024, 2047, 2048]
+    sc = np.broadcast_to(bench.synth_scalars(n, 0x27C0), (batch, n, 4)).copy()
+    for i, b in enumerate(own):
+        sc[b] = bench.synth_scalars(n, 0x27C1 + i)
+    bases = _walk(lib, torch, n, t0)
+    dsc = torch.from_numpy(sc.view(np.int64)).cuda().reshape(-1)
+    out = torch.zeros(12 * batch, dtype=torch.int64, device="cuda")
+    h = C.c_uint64(0)
+    _lib.check(lib.zkhip_prepare_bases_device_c(bases.data_ptr(), n, c, C.byref(h)))
+    try:
+        assert lib.zkhip_prepared_window_bits(h) == c
+        _lib.check(lib.zkhip_msm_g1_prepared_batch_device(h, 0, dsc.data_ptr(), n, batch, n, out.data_ptr(), _stream(torch)))
+        torch.cuda.synchronize()
+    finally:
+        _lib.check(lib.zkhip_release_bases(h))
+    got = bench.affine_words(lib, _lib, out.cpu().numpy().view(np.uint64).reshape(batch, 12))
+    for b in own + [1]:                                  # row 1 stands for the shared vector
+        assert np.array_equal(got[b], _want(lib, torch, dsc[b * n * 4:(b + 1) * n * 4], n, t0)), b
+    rest = np.delete(got, own, axis=0)
+    assert rest.shape[0] == batch - len(own) and (rest == rest[0]).all()
+
+
 def test_chunked_host_buffer_call(lib):
     """zkhip_msm_g1 on registered bases at 2^21 scalars: two pieces accumulated into one bucket set, reduced once (msm_chunk_finish)"""
     import torch

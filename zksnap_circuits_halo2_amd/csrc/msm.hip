@@ -31,7 +31,6 @@
 #include "ec_quad.hpp"
 #include "fe_inverse.hpp"
 #include "reduce_plan.hpp"
-#include "reduce_fuse.hpp"
 #include "zkhip_internal.hpp"
 
 namespace zkhip {
@@ -1312,8 +1311,9 @@ __global__ void __launch_bounds__(128) k_combine_seq_quad(const uint32_t* __rest
 //      X'[t]        = X[2t] + X[2t+1]
 //      Z'^l[u]      = Z^l[2u] + Z^l[2u+1]          (l <= s-2)
 //      Z'^(s-1)[u]  = X[4u+1] + X[4u+3]            (odd elements of X start their own tree)
+//    reduce_plan.hpp holds these index maps (shared with msm_g2.hip; tests/cpp/reduce_plan_host_check.cpp executes them) and the launches.
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(128) k_pyramid_step(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+__global__ void __launch_bounds__(PYRAMID_THREADS) k_pyramid_step(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
                                                       uint32_t N, int s, uint32_t in_stride, uint32_t out_stride) {
   const uint32_t per_win = N / 2 + (uint32_t)s * (N / 4);
   const int win = blockIdx.y;
@@ -1323,21 +1323,14 @@ __global__ void __launch_bounds__(128) k_pyramid_step(const uint32_t* __restrict
 #pragma unroll 1
   for (uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x; tid < per_win; tid += gridDim.x * blockDim.x) {
     uint32_t ia, ib;
-    if (tid < N / 2) {
-      ia = 2 * tid; ib = 2 * tid + 1;
-    } else {
-      uint32_t r = tid - N / 2;
-      uint32_t l = r / (N / 4), u = r % (N / 4);
-      if ((int)l == s - 1) { ia = 4 * u + 1; ib = 4 * u + 3; }
-      else { ia = N + l * (N / 2) + 2 * u; ib = ia + 1; }
-    }
+    reduce_step_operands(N, s, tid, ia, ib);
     store_xyzz(wo, tid, xyzz_add(load_xyzz(wi, ia), load_xyzz(wi, ib)));
   }
 }
 
 // the same step with the 4 lanes of a quad per addition (ec_quad.hpp): every pyramid level is far smaller than the chip, so the
 // step time is the latency of one addition -- 4 stages of one multiplication instead of 14 dependent ones
-__global__ void __launch_bounds__(128) k_pyramid_step_quad(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+__global__ void __launch_bounds__(PYRAMID_THREADS) k_pyramid_step_quad(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
                                                            uint32_t N, int s, uint32_t in_stride, uint32_t out_stride) {
   const uint32_t per_win = N / 2 + (uint32_t)s * (N / 4);
   const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1347,14 +1340,7 @@ __global__ void __launch_bounds__(128) k_pyramid_step_quad(const uint32_t* __res
   const uint32_t* wi = in + (size_t)win * in_stride * 36;
   uint32_t* wo = out + (size_t)win * out_stride * 36;
   uint32_t ia, ib;
-  if (tid < N / 2) {
-    ia = 2 * tid; ib = 2 * tid + 1;
-  } else {
-    uint32_t r = tid - N / 2;
-    uint32_t l = r / (N / 4), u = r % (N / 4);
-    if ((int)l == s - 1) { ia = 4 * u + 1; ib = 4 * u + 3; }
-    else { ia = N + l * (N / 2) + 2 * u; ib = ia + 1; }
-  }
+  reduce_step_operands(N, s, tid, ia, ib);
   const xyzz r = xyzz_add_quad(load_xyzz(wi, ia), load_xyzz(wi, ib), q);
   if (q == 0) store_xyzz(wo, tid, r);
 }
@@ -1368,7 +1354,7 @@ __global__ void __launch_bounds__(128) k_pyramid_step_quad(const uint32_t* __res
 // -- the additions of the two single steps in the same order, except that the two X-derived rows each form their own pair sums (12 additions
 // per 8 X elements instead of 10; the lanes are idle anyway).  Two quads per output: each adds one pair, the second operand of the last
 // addition crosses with a shuffle of 4 lanes.  N >= 8.
-__global__ void __launch_bounds__(128) k_pyramid_pair_quad(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+__global__ void __launch_bounds__(PYRAMID_THREADS) k_pyramid_pair_quad(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
                                                            uint32_t N, int s, uint32_t in_stride, uint32_t out_stride) {
   const uint32_t outs = N / 4 + (uint32_t)(s + 1) * (N / 8);
   const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1378,21 +1364,13 @@ __global__ void __launch_bounds__(128) k_pyramid_pair_quad(const uint32_t* __res
   const uint32_t* wi = in + (size_t)win * in_stride * 36;
   uint32_t* wo = out + (size_t)win * out_stride * 36;
   uint32_t ia, ib;
-  if (o < N / 4) {
-    ia = 4 * o + 2 * half; ib = ia + 1;
-  } else {
-    const uint32_t r = o - N / 4;
-    const uint32_t l = r / (N / 8), v = r % (N / 8);
-    if ((int)l == s - 1) { ia = 8 * v + 4 * half + 1; ib = ia + 2; }
-    else if ((int)l == s) { ia = 8 * v + 4 * half + 2; ib = ia + 1; }
-    else { ia = N + l * (N / 2) + 4 * v + 2 * half; ib = ia + 1; }
-  }
+  reduce_pair_quad_operands(N, s, o, half, ia, ib);
   const xyzz p = xyzz_add_quad(load_xyzz(wi, ia), load_xyzz(wi, ib), q);
   const xyzz r = xyzz_add_quad(p, xyzz_shfl_xor(p, 4), q);      // (both quads of the output: the shuffle needs both, the addition costs the first nothing)
   if ((gid & 7) == 0) store_xyzz(wo, o, r);
 }
 
-// Steps 1 and 2 in one launch where they fill the chip (reduce_fuse.hpp), one lane per chain of additions and the additions of the two single
+// Steps 1 and 2 in one launch where they fill the chip (reduce_plan.hpp: PAIR), one lane per chain of additions and the additions of the two single
 // steps exactly -- 10 per 8 buckets, same operands, same order -- so the output words are those of two k_pyramid_step launches, while the
 // state between the steps never goes to memory and every bucket is read once: [X (N)] becomes [X'' (N/4) | Z''^0 (N/8) | Z''^1 (N/8)].
 // Lane t < N/4 owns X[4t .. 4t+3]:
@@ -1400,32 +1378,32 @@ __global__ void __launch_bounds__(128) k_pyramid_pair_quad(const uint32_t* __res
 // and the lane pair (2v, 2v+1) exchanges one point: the even lane stores Z''^0[v] = z(2v) + z(2v+1), the odd one Z''^1[v] = b(2v) + b(2v+1).
 // At most four points are live at a time (z, X[4t+3], a, the load): 210 VGPRs, no scratch, two wavefronts per SIMD.  N >= 8, so N / 4 is even:
 // both lanes of a pair are live or dead together.
-__global__ void __launch_bounds__(128) k_pyramid_pair(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+__global__ void __launch_bounds__(PYRAMID_THREADS) k_pyramid_pair(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
                                                       uint32_t N, uint32_t in_stride, uint32_t out_stride) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= N / 4) return;
   const int win = blockIdx.y;
   const uint32_t* wi = in + (size_t)win * in_stride * 36;
   uint32_t* wo = out + (size_t)win * out_stride * 36;
-  const xyzz p3 = load_xyzz(wi, 4 * t + 3);
+  const xyzz p3 = load_xyzz(wi, reduce_pair_in(t, 3));
   xyzz z, a;
   {
-    const xyzz p1 = load_xyzz(wi, 4 * t + 1);
+    const xyzz p1 = load_xyzz(wi, reduce_pair_in(t, 1));
     z = xyzz_add(p1, p3);
-    a = xyzz_add(load_xyzz(wi, 4 * t), p1);
+    a = xyzz_add(load_xyzz(wi, reduce_pair_in(t, 0)), p1);
   }
-  const xyzz b = xyzz_add(load_xyzz(wi, 4 * t + 2), p3);
-  store_xyzz(wo, t, xyzz_add(a, b));
+  const xyzz b = xyzz_add(load_xyzz(wi, reduce_pair_in(t, 2)), p3);
+  store_xyzz(wo, reduce_pair_x_out(t), xyzz_add(a, b));
   const bool odd = t & 1;
   const xyzz other = xyzz_shfl_xor(odd ? z : b, 1);    // the even lane receives z(2v+1), the odd one b(2v)
-  store_xyzz(wo, N / 4 + (odd ? N / 8 : 0) + t / 2, xyzz_add(odd ? other : z, odd ? b : other));   // (one addition for both)
+  store_xyzz(wo, reduce_pair_z_out(N, t), xyzz_add(odd ? other : z, odd ? b : other));   // (one addition for both)
 }
 
 // 9a. per-window weighted sum.  Input state after the last pyramid step: X has 2 elements, Z^0..Z^(nz-1) one each.
 //     window sum = X0 + X1 + sum_l 2^l Z^l + 2^nz X1.  One 32-lane group per window: lane l < nz computes 2^l Z^l by l
 //     doublings, lane nz computes 2^nz X1, lane nz + 1 holds X0 + X1; a 4-step shuffle tree adds the terms.
 //     Depth nz doublings + 5 additions instead of nz (doubling + addition).  Needs nz + 2 <= 32 (c <= 21: nz = c - 2).
-__global__ void __launch_bounds__(64) k_window_horner(const uint32_t* __restrict__ in, uint32_t in_stride, int nz,
+__global__ void __launch_bounds__(HORNER_THREADS) k_window_horner(const uint32_t* __restrict__ in, uint32_t in_stride, int nz,
                                                       uint32_t* __restrict__ winsum, int W) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int win = gid >> 5, lane = gid & 31;
@@ -1488,7 +1466,6 @@ __global__ void __launch_bounds__(128) k_window_horner_quad(const uint32_t* __re
 // The four sums meet through LDS after one barrier and wavefront 0 adds them with two more steps of the same tree loop (one copy of the
 // addition's code for both): at c = 20 two dependent additions follow the longest chain, where the uniform layout had a 5-step tree, the
 // LDS step and a divergent X0 + X1 in front.
-constexpr int FINISH_THREADS = 512;          // 128 quads.  (1024 threads leave a wavefront 128 VGPRs: the quad addition then spills ~400 of them)
 constexpr int FINISH_CHAIN0 = 11, FINISH_CHAIN1 = 15, FINISH_CHAIN2 = 17;      // longest chain of wavefronts 0, 1, 2
 
 __global__ void __launch_bounds__(FINISH_THREADS) k_reduce_finish(const uint32_t* __restrict__ in, uint32_t in_stride, uint32_t N, int s,
@@ -1509,14 +1486,7 @@ __global__ void __launch_bounds__(FINISH_THREADS) k_reduce_finish(const uint32_t
     static_assert(FINISH_THREADS / 4 >= (int)REDUCE_FINISH_ADDS, "one quad per addition of the widest level");
     if (quad < per_win) {                               // whole quads
       uint32_t ia, ib;
-      if (quad < N / 2) {
-        ia = 2 * quad; ib = 2 * quad + 1;
-      } else {
-        const uint32_t r = quad - N / 2;
-        const uint32_t l = r / (N / 4), u = r % (N / 4);
-        if ((int)l == s - 1) { ia = 4 * u + 1; ib = 4 * u + 3; }
-        else { ia = N + l * (N / 2) + 2 * u; ib = ia + 1; }
-      }
+      reduce_step_operands(N, s, quad, ia, ib);
       xyzz a, b;
       if (first) { a = load_xyzz(wi, ia); b = load_xyzz(wi, ib); }
       else { a = load_xyzz(lds + cur, ia); b = load_xyzz(lds + cur, ib); }
@@ -1579,7 +1549,7 @@ __global__ void __launch_bounds__(64) k_fold(const uint32_t* __restrict__ winsum
 }
 
 // batched prepared MSM: every bucket set's weighted sum is a final result
-__global__ void __launch_bounds__(64) k_store_results(const uint32_t* __restrict__ winsum, uint32_t K, uint32_t* __restrict__ out) {
+__global__ void __launch_bounds__(STORE_THREADS) k_store_results(const uint32_t* __restrict__ winsum, uint32_t K, uint32_t* __restrict__ out) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < K) store_jacobian(load_xyzz(winsum, k), out + (size_t)k * 24);
 }
@@ -1838,8 +1808,6 @@ int msm_build_tasks(const uint32_t* d_scalars, size_t n_in, size_t batch, size_t
   HIPCHK(hipMemsetAsync(lay.zero_lo, 0, lay.zero_bytes, stream));
   // 1. digits
   const size_t sstride = K > 1 ? scalar_stride : n;
-  const size_t nk = n * K, max_tasks = lay.max_tasks;
-  (void)nk; (void)max_tasks;
   const unsigned dblocks = (unsigned)(((size_t)K * n_pad + 255) / 256);
   const int narrow = (shared_buckets && !glv) ? msm_narrow_windows(c, W) : 0;       // balanced windows of the wide prepared tables (k_build_table agrees)
   if (glv && wide) hipLaunchKernelGGL(k_digits_glv<int32_t>, dim3((unsigned)((std::max<size_t>(n_in, 8) + 255) / 256)), dim3(256), 0, stream, d_scalars, (int32_t*)digits, (uint32_t)n_in, n_pad, c, W);
@@ -1980,41 +1948,32 @@ static int msm_accumulate_combine(const msm_tasks_view& tv, const uint32_t* d_ba
 // Steps 8 - 9: dense buckets (WB sets of B, at `cur`; `nxt` = a second array of the same size, both are overwritten) -> the MSM's result(s) at d_out.
 // prepared: every bucket set's weighted sum is a result (K = WB of them); otherwise the WB window sums are folded into one.
 static int msm_reduce_buckets(int WB, uint32_t B, int c, uint32_t K, bool prepared, uint32_t* cur, uint32_t* nxt, uint32_t* winsum, uint32_t* d_out, hipStream_t stream) {
-  // 8. pyramid: buckets were written with window stride B (dense).  Steps 1 .. c-2 leave X with 2 elements.  The launches are a function of
-  // (B, WB) alone (reduce_plan.hpp): single-lane steps while a step fills the chip -- the first two in one launch where that launch is
-  // one round of two wavefronts per SIMD (reduce_fuse.hpp) --, then a quad per addition -- two levels per launch where that stays far below the chip's
-  // lane count --, and up to REDUCE_FINISH_MAX_SETS bucket sets end in one workgroup each (k_reduce_finish:
-  // the last levels, the weighted sum and, for prepared bases, the store).  Larger batches are throughput-bound and keep a launch per level.
+  // Every launch comes from the plan, a function of (B, WB, prepared) alone (reduce_plan.hpp).  8. pyramid: buckets were written with window
+  // stride B (dense); steps 1 .. c-2 leave X with 2 elements.  9. the weighted sum, then the store or the fold where that kernel did not
+  // write the results itself.
   if (B == 1) { set_error("msm: internal: B == 1"); return ZKHIP_EINVAL; }     // (c >= 2, so B >= 2 always)
   reduce_plan plan;
-  if (!reduce_make_plan(B, WB, &plan)) { set_error("msm: internal: no reduction plan for %u buckets x %d sets", B, WB); return ZKHIP_EINVAL; }
-  const bool direct = prepared && WB <= 2048;     // the weighted-sum kernel writes the results itself (one launch less)
-  const bool fuse_first = reduce_fuse_first_pair(plan, WB);      // (reduce_fuse.hpp)
+  if (!reduce_make_plan(B, WB, prepared, &plan)) { set_error("msm: internal: no reduction plan for %u buckets x %d sets", B, WB); return ZKHIP_EINVAL; }
+  uint32_t* const jac_out = plan.direct ? d_out : nullptr;
   for (int i = 0; i < plan.n; i++) {
     const reduce_launch& L = plan.l[i];
-    if (L.kind == REDUCE_FINISH) {
-      prof_mark(stream, "pyramid");               // (the finish kernel's own levels are timed with the weighted sum)
-      hipLaunchKernelGGL(k_reduce_finish, dim3(WB), dim3(FINISH_THREADS), 0, stream, cur, L.in_stride, L.N, L.s, winsum, direct ? d_out : (uint32_t*)nullptr);
-      break;
+    const dim3 rows(L.grid, WB), threads(PYRAMID_THREADS);      // the pyramid kernels: a grid row per bucket set
+    const bool sum = L.kind == REDUCE_FINISH || L.kind == REDUCE_HORNER_QUAD || L.kind == REDUCE_HORNER;
+    if (sum) prof_mark(stream, "pyramid");          // (the finish kernel's own levels are timed with the weighted sum)
+    switch (L.kind) {
+      case REDUCE_STEP: hipLaunchKernelGGL(k_pyramid_step, rows, threads, 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride); break;
+      case REDUCE_STEP_QUAD: hipLaunchKernelGGL(k_pyramid_step_quad, rows, threads, 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride); break;
+      case REDUCE_PAIR_QUAD: hipLaunchKernelGGL(k_pyramid_pair_quad, rows, threads, 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride); break;
+      case REDUCE_PAIR: hipLaunchKernelGGL(k_pyramid_pair, rows, threads, 0, stream, cur, nxt, L.N, L.in_stride, L.out_stride); break;
+      case REDUCE_FINISH: hipLaunchKernelGGL(k_reduce_finish, dim3(L.grid), dim3(FINISH_THREADS), 0, stream, cur, L.in_stride, L.N, L.s, winsum, jac_out); break;
+      case REDUCE_HORNER_QUAD: hipLaunchKernelGGL(k_window_horner_quad, dim3(L.grid), dim3(128), 0, stream, cur, L.in_stride, plan.nz, winsum, jac_out); break;
+      case REDUCE_HORNER: hipLaunchKernelGGL(k_window_horner, dim3(L.grid), dim3(HORNER_THREADS), 0, stream, cur, L.in_stride, plan.nz, winsum, WB); break;
+      case REDUCE_STORE: hipLaunchKernelGGL(k_store_results, dim3(L.grid), dim3(STORE_THREADS), 0, stream, winsum, K, d_out); break;   // one result per bucket set
+      case REDUCE_FOLD: hipLaunchKernelGGL(k_fold, dim3(L.grid), dim3(64), 0, stream, winsum, WB, c, d_out); break;
     }
-    if (i == 0 && fuse_first) {                     // steps 1 and 2 in one launch: the buckets in, the state of l[1] out
-      hipLaunchKernelGGL(k_pyramid_pair, dim3((L.N / 4 + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.in_stride, plan.l[1].out_stride);
-      i++;
-    }
-    else if (L.kind == REDUCE_STEP) hipLaunchKernelGGL(k_pyramid_step, dim3((L.out_stride + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride);
-    else if (L.kind == REDUCE_STEP_QUAD) hipLaunchKernelGGL(k_pyramid_step_quad, dim3((4 * L.out_stride + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride);
-    else hipLaunchKernelGGL(k_pyramid_pair_quad, dim3((8 * L.out_stride + 127) / 128, WB), dim3(128), 0, stream, cur, nxt, L.N, L.s, L.in_stride, L.out_stride);
-    uint32_t* t = cur; cur = nxt; nxt = t;
+    if (sum) prof_mark(stream, "horner");
+    if (L.out_stride) { uint32_t* t = cur; cur = nxt; nxt = t; }      // a pyramid launch: its output is the next launch's input
   }
-  // 9. Horner + fold
-  if (!plan.finish) {
-    prof_mark(stream, "pyramid");
-    if (WB <= 2048) hipLaunchKernelGGL(k_window_horner_quad, dim3(WB), dim3(128), 0, stream, cur, plan.last_stride, plan.nz, winsum, direct ? d_out : (uint32_t*)nullptr);
-    else hipLaunchKernelGGL(k_window_horner, dim3((WB * 32 + 63) / 64), dim3(64), 0, stream, cur, plan.last_stride, plan.nz, winsum, WB);
-  }
-  prof_mark(stream, "horner");
-  if (prepared) { if (!direct) hipLaunchKernelGGL(k_store_results, dim3((K + 63) / 64), dim3(64), 0, stream, winsum, K, d_out); }   // one result per bucket set
-  else hipLaunchKernelGGL(k_fold, dim3(1), dim3(64), 0, stream, winsum, WB, c, d_out);
   prof_mark(stream, "fold");
   HIPCHK(hipGetLastError());
   return ZKHIP_OK;

@@ -4,8 +4,9 @@
 // `params.g2()` / `params.s_g2()`: /root/reference/aggregator/src/wrapper.rs:1142-1144), so this path is built for correctness and
 // shares everything that depends on the scalars only with the G1 path (msm.hip `msm_build_tasks`: signed digits, LDS counting sorts,
 // tasks in longest-first order).  Curve-specific, here: bucket accumulation (one thread per task, XYZZ over Fq2 in registers),
-// per-bucket combination of the task partials, the log-depth bucket pyramid (same index algebra as k_pyramid_step in msm.hip), the
-// per-window weighted sum and the window fold.  One bucket set per window (no prepared tables: there is no fixed-base caller).
+// per-bucket combination of the task partials, the log-depth bucket pyramid (the operand map of k_pyramid_step in msm.hip: reduce_plan.hpp,
+// reduce_step_operands; the launch schedule is its own, none of the G1 thresholds was measured for a G2 addition), the per-window weighted sum and
+// the window fold.  One bucket set per window (no prepared tables: there is no fixed-base caller).
 // Work points are 288 bytes (8 x 9 limbs).
 //
 // Round 5: the general-path machinery of G1 applies unchanged, because it depends on the scalars only -- GLV digits (the twist E': y^2 = x^3 + 3 / (9 + u)
@@ -17,6 +18,7 @@
 #include <cstdint>
 #include "ec2.hpp"
 #include "ec2_quad.hpp"
+#include "reduce_plan.hpp"
 #include "zkhip_internal.hpp"
 
 namespace zkhip {
@@ -158,13 +160,7 @@ __global__ void __launch_bounds__(64) k2_pyramid_step(const uint32_t* __restrict
   const uint32_t* wi = in + (size_t)win * in_stride * 72;
   uint32_t* wo = out + (size_t)win * out_stride * 72;
   uint32_t ia, ib;
-  if (tid < N / 2) {
-    ia = 2 * tid; ib = 2 * tid + 1;
-  } else {
-    const uint32_t r = tid - N / 2, l = r / (N / 4), u = r % (N / 4);
-    if ((int)l == s - 1) { ia = 4 * u + 1; ib = 4 * u + 3; }
-    else { ia = N + l * (N / 2) + 2 * u; ib = ia + 1; }
-  }
+  reduce_step_operands(N, s, tid, ia, ib);
   store_xyzz2(wo, tid, xyzz2_add_lazy_mem<true>(wi, ia, wi, ib));
 }
 
@@ -179,13 +175,7 @@ __global__ void __launch_bounds__(64) k2_pyramid_step_quad(const uint32_t* __res
   const uint32_t* wi = in + (size_t)win * in_stride * 72;
   uint32_t* wo = out + (size_t)win * out_stride * 72;
   uint32_t ia, ib;
-  if (tid < N / 2) {
-    ia = 2 * tid; ib = 2 * tid + 1;
-  } else {
-    const uint32_t r = tid - N / 2, l = r / (N / 4), u = r % (N / 4);
-    if ((int)l == s - 1) { ia = 4 * u + 1; ib = 4 * u + 3; }
-    else { ia = N + l * (N / 2) + 2 * u; ib = ia + 1; }
-  }
+  reduce_step_operands(N, s, tid, ia, ib);
   const xyzz2 r = xyzz2_quad_to_std(xyzz2_add_quad_lazy(load_xyzz2(wi, ia), load_xyzz2(wi, ib), q));      // stored points are in standard form
   if (q == 0) store_xyzz2(wo, tid, r);
 }

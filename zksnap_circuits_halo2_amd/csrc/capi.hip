@@ -167,6 +167,14 @@ struct scratch {       // one user at a time: the calls of one stream
   dev_buf transcript;                  // the transcript calls' records: a head (TR_HEAD bytes, word 0 = the call's count of identity inputs) + the payload
   int pins = 0;                        // `_device` calls that wait on this set's stream WITHOUT g_mu (the transcript's): a pinned set is not evicted
   uint64_t last_use = 0;
+  // a launch of row programs on this set (rowvm.hip): the workspace reserved, the staging named; the form and the outputs are the caller's
+  int vm_call_for(hipStream_t s, const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, vm_call* c) {
+    const int rc = vm.reserve(row_vm_workspace_bytes(progs, n_progs, n_columns, log_rows));
+    if (rc != ZKHIP_OK) return rc;
+    c->progs = progs; c->n_progs = n_progs; c->d_columns = d_columns; c->n_columns = n_columns; c->log_rows = log_rows;
+    c->ws = vm.p; c->ws_bytes = vm.cap; c->stream = s; c->staging = &vm_stage;
+    return ZKHIP_OK;
+  }
   void release() { transcript.release(); ws.release(); scalars.release(); bases.release(); poly.release(); poly2.release(); small.release(); ntt_tmp.release(); vm.release(); gather.release(); q_ext.release(); vm_stage.release(); args.release(); }
 };
 
@@ -1671,14 +1679,10 @@ int zkhip_fr_kate_division_device(const void* d_a, size_t n, const uint64_t b[4]
 
 // the argument checks of both forms of divide_by_roots: nothing is enqueued before they pass
 static int check_roots(const uint64_t* roots, uint32_t m) {
-  static const uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};   // the modulus of Fr
   if (m == 0 || m > ZKHIP_MAX_ROOTS) { set_error("divide_by_roots: %u roots (1 .. %d)", m, ZKHIP_MAX_ROOTS); return ZKHIP_EINVAL; }
   if (!roots) { set_error("divide_by_roots: null pointer"); return ZKHIP_EINVAL; }
   for (uint32_t i = 0; i < m; i++) {
-    bool below = false;
-    for (int w = 3; w >= 0; w--)
-      if (roots[i * 4 + w] != R[w]) { below = roots[i * 4 + w] < R[w]; break; }
-    if (!below) { set_error("divide_by_roots: root %u is not canonical (>= r)", i); return ZKHIP_EINVAL; }
+    if (!fr_words_canonical(roots + (size_t)i * 4)) { set_error("divide_by_roots: root %u is not canonical (>= r)", i); return ZKHIP_EINVAL; }
     for (uint32_t j = 0; j < i; j++)
       if (memcmp(roots + i * 4, roots + j * 4, 32) == 0) { set_error("divide_by_roots: roots %u and %u are equal", j, i); return ZKHIP_EINVAL; }
   }
@@ -1872,8 +1876,10 @@ int zkhip_check_rows_device(const zkhip_vm_program* progs, uint32_t n_progs, con
     if (!d_columns[i]) { set_error("check_rows: column %u is null", i); return ZKHIP_EINVAL; }
   hipStream_t s = caller_stream(stream);
   scratch* sc = scratch_for(primary(), s);
-  if ((rc = sc->vm.reserve(row_vm_multi_workspace_bytes(progs, n_progs, n_columns, log_rows))) != ZKHIP_OK) return rc;
-  return row_vm_check_device(progs, n_progs, d_columns, n_columns, log_rows, row0, count, d_reports, sc->vm.p, sc->vm.cap, s, &sc->vm_stage);
+  vm_call c;
+  if ((rc = sc->vm_call_for(s, progs, n_progs, d_columns, n_columns, log_rows, &c)) != ZKHIP_OK) return rc;
+  c.form = VM_CHECK; c.row0 = row0; c.count = count; c.d_out = (uint32_t*)d_reports;
+  return row_vm_launch(c);
 }
 
 int zkhip_check_copies_device(const void* const* d_columns, uint32_t n_columns, uint32_t log_n, const void* d_map_col, const void* d_map_row, void* d_report,
@@ -2171,12 +2177,14 @@ int zkhip_fr_eval_rows_device(const zkhip_vm_program* prog, const void* const* d
   if (!d_out || (n_columns && !d_columns)) { set_error("eval_rows: null pointer"); return ZKHIP_EINVAL; }
   hipStream_t s = caller_stream(stream);
   scratch* sc = scratch_for(primary(), s);
-  if ((rc = sc->vm.reserve(row_vm_workspace_bytes(prog, n_columns, log_rows))) != ZKHIP_OK) return rc;
-  return row_vm_device(prog, d_columns, n_columns, log_rows, accumulate, (uint32_t*)d_out, sc->vm.p, sc->vm.cap, s, &sc->vm_stage);
+  vm_call c;
+  if ((rc = sc->vm_call_for(s, prog, 1, d_columns, n_columns, log_rows, &c)) != ZKHIP_OK) return rc;
+  c.accumulate = accumulate; c.d_out = (uint32_t*)d_out;
+  return row_vm_launch(c);
 }
 
 // out[row] = sum_p weights[p] * progs[p](row): independent row programs over the same columns in ONE launch (blockIdx.y = program:
-// row_vm_device_multi), their outputs combined by the linear-combination kernel.  What it is for: the quotient numerator of a circuit with
+// vm_call::d_outs), their outputs combined by the linear-combination kernel.  What it is for: the quotient numerator of a circuit with
 // hundreds of columns at 2^13 .. 2^15 rows is thousands of instructions over a few thousand rows -- one program is a handful of wavefronts
 // walking the whole list.  (Separate launches on side streams overlapped four at a time -- the hardware queues: 2.3 x where one grid gives 8 x.)
 int zkhip_fr_eval_rows_sum_device(const zkhip_vm_program* progs, const uint64_t* weights, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns,
@@ -2192,15 +2200,17 @@ int zkhip_fr_eval_rows_sum_device(const zkhip_vm_program* progs, const uint64_t*
   scratch* sc = scratch_for(primary(), s);
   const size_t rows = (size_t)1 << log_rows;
   if ((rc = sc->poly2.reserve((size_t)n_progs * rows * 32)) != ZKHIP_OK) return rc;
-  if ((rc = sc->vm.reserve(row_vm_multi_workspace_bytes(progs, n_progs, n_columns, log_rows))) != ZKHIP_OK) return rc;
+  vm_call c;
+  if ((rc = sc->vm_call_for(s, progs, n_progs, d_columns, n_columns, log_rows, &c)) != ZKHIP_OK) return rc;
   std::vector<uint32_t*> partial(n_progs);
   for (uint32_t p = 0; p < n_progs; p++) partial[p] = (uint32_t*)((char*)sc->poly2.p + (size_t)p * rows * 32);
-  if ((rc = row_vm_device_multi(progs, n_progs, d_columns, n_columns, log_rows, partial.data(), sc->vm.p, sc->vm.cap, s, &sc->vm_stage)) != ZKHIP_OK) return rc;
+  c.d_outs = partial.data();
+  if ((rc = row_vm_launch(c)) != ZKHIP_OK) return rc;
   if ((rc = sc->ws.reserve(lincomb_workspace_bytes(n_progs, rows))) != ZKHIP_OK) return rc;
   return fr_linear_combination_device((const void* const*)partial.data(), (const uint32_t*)weights, n_progs, rows, (uint32_t*)d_out, sc->ws.p, sc->ws.cap, s, &sc->args);
 }
 
-// Row program over window buffers: `count` rows from global row `row0` of a 2^log_rows domain (include/zkhip.h; rowvm.hip row_vm_window_device)
+// Row program over window buffers: `count` rows from global row `row0` of a 2^log_rows domain (include/zkhip.h; VM_WINDOW of rowvm.hip)
 int zkhip_fr_eval_rows_window_device(const zkhip_vm_program* prog, const void* const* d_windows, uint32_t n_columns, uint32_t log_rows, uint64_t row0,
                                      uint64_t count, int accumulate, void* d_out, void* stream) {
   ZK_API_RANGE();
@@ -2219,8 +2229,10 @@ int zkhip_fr_eval_rows_window_device(const zkhip_vm_program* prog, const void* c
   if (lo + hi >= ((uint64_t)1 << 31)) { set_error("eval_rows_window: halos %llu + %llu too wide", (unsigned long long)lo, (unsigned long long)hi); return ZKHIP_EINVAL; }
   hipStream_t s = caller_stream(stream);
   scratch* sc = scratch_for(primary(), s);
-  if ((rc = sc->vm.reserve(row_vm_workspace_bytes(prog, n_columns, log_rows))) != ZKHIP_OK) return rc;
-  return row_vm_window_device(prog, d_windows, n_columns, log_rows, row0, count, accumulate, (uint32_t*)d_out, sc->vm.p, sc->vm.cap, s, &sc->vm_stage);
+  vm_call c;
+  if ((rc = sc->vm_call_for(s, prog, 1, d_windows, n_columns, log_rows, &c)) != ZKHIP_OK) return rc;
+  c.form = VM_WINDOW; c.row0 = row0; c.count = count; c.accumulate = accumulate; c.d_out = (uint32_t*)d_out;
+  return row_vm_launch(c);
 }
 
 // The quotient numerator re-cut by rows over the devices of zkhip_init.  Device j of S: rows shard_range(2^ext_k, j, S),
@@ -2304,9 +2316,11 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     }
     prof_mark(s, "transform");
     prof_mark(s, "exchange");                              // (empty on one device: the same four phases for every S)
-    if ((rc = sc->vm.reserve(row_vm_workspace_bytes(prog, n_columns, ext_k))) != ZKHIP_OK) return rc;
     int compiled = 0;
-    if ((rc = row_vm_device(prog, cols.data(), n_columns, ext_k, 0, (uint32_t*)d_out, sc->vm.p, sc->vm.cap, s, &sc->vm_stage, &compiled)) != ZKHIP_OK) return rc;
+    vm_call c;
+    if ((rc = sc->vm_call_for(s, prog, 1, cols.data(), n_columns, ext_k, &c)) != ZKHIP_OK) return rc;
+    c.d_out = (uint32_t*)d_out; c.compiled = &compiled;
+    if ((rc = row_vm_launch(c)) != ZKHIP_OK) return rc;
     if ((rc = rs_touch(0, s)) != ZKHIP_OK) return rc;
     prof_mark(s, compiled ? "rows_compiled" : "rows_interpreted");
     prof_mark(s, "gather");
@@ -2346,7 +2360,7 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     if ((rc = D->q_ext.reserve(std::max<size_t>(own_n[j], 1) * N * 32)) != ZKHIP_OK) return rc;
     if ((rc = D->q_win.reserve(std::max<size_t>(n_copied, 1) * W * 32)) != ZKHIP_OK) return rc;
     if (j > 0 && (rc = D->q_out.reserve(std::max<size_t>(row_n[j], 1) * 32)) != ZKHIP_OK) return rc;
-    if ((rc = dsc[j]->vm.reserve(row_vm_workspace_bytes(prog, n_columns, ext_k))) != ZKHIP_OK) return rc;
+    if ((rc = dsc[j]->vm.reserve(row_vm_workspace_bytes(prog, 1, n_columns, ext_k))) != ZKHIP_OK) return rc;
   }
   for (int j = 0; j < S; j++) {
     if ((rc = F.dev(j)) != ZKHIP_OK) return rc;
@@ -2403,8 +2417,10 @@ int zkhip_fr_eval_rows_sharded_device(const zkhip_vm_program* prog, const void* 
     if (j == 0) prof_mark(s, "exchange");
     uint32_t* out = j == 0 ? (uint32_t*)d_out + row_lo[0] * 8 : (uint32_t*)D->q_out.p;
     int compiled = 0;
-    if ((rc = row_vm_window_device(prog, win.data(), n_columns, ext_k, row_lo[j], row_n[j], 0, out, dsc[j]->vm.p, dsc[j]->vm.cap, st[j], &dsc[j]->vm_stage,
-                                   &compiled)) != ZKHIP_OK) return rc;
+    vm_call c;
+    if ((rc = dsc[j]->vm_call_for(st[j], prog, 1, win.data(), n_columns, ext_k, &c)) != ZKHIP_OK) return rc;
+    c.form = VM_WINDOW; c.row0 = row_lo[j]; c.count = row_n[j]; c.d_out = out; c.compiled = &compiled;
+    if ((rc = row_vm_launch(c)) != ZKHIP_OK) return rc;
     if ((rc = rs_touch(j, st[j])) != ZKHIP_OK) return rc;
     if (j == 0) prof_mark(s, compiled ? "rows_compiled" : "rows_interpreted");
     else HIPCHK(hipMemcpyPeerAsync((uint32_t*)d_out + row_lo[j] * 8, P.device, out, D->device, row_n[j] * 32, st[j]));

@@ -125,15 +125,6 @@ __global__ void __launch_bounds__(FOLD_THREADS) k_fold_finish(const uint32_t* __
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
-static bool gf_canonical(const uint64_t* w) {
-  static const uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
-  for (int i = 3; i >= 0; i--) {
-    if (w[i] < R[i]) return true;
-    if (w[i] > R[i]) return false;
-  }
-  return false;
-}
-
 int gwc_plan_validate(const zkhip_gwc_plan* plan, uint32_t k, const uint64_t* omega) {
   const char* who = "gwc_scalars";
   if (!plan) { set_error("%s: null plan", who); return ZKHIP_EINVAL; }
@@ -142,7 +133,7 @@ int gwc_plan_validate(const zkhip_gwc_plan* plan, uint32_t k, const uint64_t* om
   if (plan->n_slots < 1 || plan->n_slots > GWC_MAX_SLOTS) { set_error("%s: %u polynomial slots: 1 .. %u", who, plan->n_slots, GWC_MAX_SLOTS); return ZKHIP_EINVAL; }
   if (!plan->set_rotation || !plan->query_set || !plan->query_pos || !plan->query_slot) { set_error("%s: null plan array", who); return ZKHIP_EINVAL; }
   if (k > 28) { set_error("%s: k = %u > 28", who, k); return ZKHIP_EINVAL; }
-  if (!omega || !gf_canonical(omega)) { set_error("%s: omega is null or not a canonical Fr", who); return ZKHIP_EINVAL; }
+  if (!omega || !fr_words_canonical(omega)) { set_error("%s: omega is null or not a canonical Fr", who); return ZKHIP_EINVAL; }
   for (uint32_t i = 0; i < plan->n_sets; i++)
     if (plan->set_rotation[i] >= ((uint64_t)1 << k)) { set_error("%s: set %u: rotation %u is not reduced mod 2^%u", who, i, plan->set_rotation[i], k); return ZKHIP_EINVAL; }
   for (uint32_t q = 0; q < plan->n_evals; q++)

@@ -22,12 +22,10 @@
 #include "check_report.hpp"
 #include "fp29.hpp"
 #include "fr_vec.hpp"
+#include "rowvm_blob.hpp"      // vm_uop, vm_part and the blob they live in: layout and fill, host arithmetic
 #include "zkhip_internal.hpp"
 
 namespace zkhip {
-
-constexpr int VM_MAX_REGS = ZKHIP_VM_REGS;   // kernel variants exist for 6 / 8 / 12 / 16 registers (occupancy 4 / 3 / 2 / 2 waves per SIMD)
-constexpr uint32_t POW_LO_BITS = 12;   // omega^row = hi[row >> 12] * lo[row & 4095]
 
 struct vm_launch {
   const void* prog;             // n_insns x vm_uop (64 bytes: the instruction with its operands' addresses resolved by the host)
@@ -41,20 +39,11 @@ struct vm_launch {
   uint32_t* out;                // CHECK: the program's report record instead
   uint64_t rows;                // rows this launch computes: the domain, a window's `count`, or a check's `count`
   uint32_t accumulate;
-  const struct vm_part* parts;  // nullptr, or one record per blockIdx.y: several programs over the same columns in ONE launch (row_vm_device_multi)
+  const struct vm_part* parts;  // nullptr, or one record per blockIdx.y: several programs over the same columns in ONE launch (sums, checks)
   uint64_t wrap;                // column index mask: domain - 1 for whole columns, all ones for window buffers (offsets include halo_lo)
   uint64_t row0;                // global row of local row 0 (0 for whole columns; CHECK: whole columns read from this row on)
   uint64_t dom_mask;            // domain - 1: ROWPOW is omega^((row0 + row) & dom_mask)
 };
-// what differs between the programs of a multi-program launch (the column table, the power tables and the rows are shared)
-struct vm_part {
-  const void* prog;
-  const uint32_t* consts;
-  const uint32_t* rot_off;
-  uint32_t* out;
-  uint32_t n_insns, result_reg;
-};
-static_assert(sizeof(vm_part) == 40, "the kernel reads a part record as five 64-bit words");
 
 // 2r as normalised limbs
 struct fr_two_p {
@@ -223,17 +212,7 @@ __device__ __forceinline__ void vm_execute(const vm_launch& L, uint32_t head, ui
   vm_reg_set(r, dst, t);
 }
 
-// One instruction as the kernel reads it: the 16-byte instruction of the ABI plus, for its operands a and b, everything the address of their
-// words needs -- base (a column's pointer, a constant's address, or a dummy for operands that are not in memory), rotation offset in rows and
-// a row mask (all ones for a column, zero otherwise).  Resolved on the host (row_vm_device), so a fetch is ONE scalar load of 64 bytes and the
-// operand loads depend on nothing else; the loop fetches two instructions ahead and loads operands one instruction ahead.
-struct vm_uop {
-  uint32_t head, oa, ob, oc;
-  uint64_t base_a, base_b;
-  uint32_t off_a, off_b, mask_a, mask_b;
-  uint32_t pad[4];
-};
-static_assert(sizeof(vm_uop) == 64, "micro-op layout");
+// one micro-op (vm_uop, rowvm_blob.hpp) in registers
 struct vm_decoded { uint32_t head, oa, ob, oc; uint64_t base_a, base_b; uint32_t off_a, off_b, mask_a, mask_b; };
 __device__ __forceinline__ vm_decoded vm_decode(const vm_launch& L, uint32_t pc) {
   const vm_c128 q = (vm_c128)L.prog + (size_t)pc * 4;          // same instruction for every lane: scalar loads, decoded on the scalar unit
@@ -403,17 +382,6 @@ __global__ void __launch_bounds__(256) k_check_report_init(unsigned long long* _
   reports[2 * (size_t)i + 1] = CHECK_NONE;
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static bool fr_is_canonical(const uint64_t* w) {
-  static const uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
-  for (int i = 3; i >= 0; i--) {
-    if (w[i] < R[i]) return true;
-    if (w[i] > R[i]) return false;
-  }
-  return false;
-}
-
 int row_vm_validate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, int accumulate) {
   (void)accumulate;
   if (!p) { set_error("eval_rows: null program"); return ZKHIP_EINVAL; }
@@ -424,8 +392,8 @@ int row_vm_validate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_
   if ((p->n_constants && !p->constants) || (p->n_rotations && !p->rotations)) { set_error("eval_rows: null table"); return ZKHIP_EINVAL; }
   if (p->n_constants > 65536 || n_columns > 65536 || p->n_rotations > 256) { set_error("eval_rows: table too large"); return ZKHIP_EINVAL; }
   for (uint32_t i = 0; i < p->n_constants; i++)
-    if (!fr_is_canonical(p->constants + (size_t)i * 4)) { set_error("eval_rows: constant %u is not a canonical Fr", i); return ZKHIP_EINVAL; }
-  if (p->omega && !fr_is_canonical(p->omega)) { set_error("eval_rows: omega is not a canonical Fr"); return ZKHIP_EINVAL; }
+    if (!fr_words_canonical(p->constants + (size_t)i * 4)) { set_error("eval_rows: constant %u is not a canonical Fr", i); return ZKHIP_EINVAL; }
+  if (p->omega && !fr_words_canonical(p->omega)) { set_error("eval_rows: omega is not a canonical Fr"); return ZKHIP_EINVAL; }
   for (uint32_t pc = 0; pc < p->n_insns; pc++) {
     const zkhip_vm_insn& in = p->insns[pc];
     if (in.op > ZKHIP_OP_MAD) { set_error("eval_rows: instruction %u: unknown op %u", pc, in.op); return ZKHIP_EINVAL; }
@@ -448,13 +416,6 @@ int row_vm_validate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_
   return ZKHIP_OK;
 }
 
-size_t row_vm_workspace_bytes(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows) {
-  const size_t rows = (size_t)1 << log_rows;
-  return align256(((size_t)p->n_insns + 4) * sizeof(vm_uop)) + align256((size_t)p->n_constants * 32 + 32) + align256((size_t)p->n_rotations * 4 + 4) +
-         align256((size_t)n_columns * 8 + 8) + 256 + align256(((size_t)1 << POW_LO_BITS) * 32) + align256(((rows >> POW_LO_BITS) + 1) * 32);
-}
-
-// the program, its tables and the column pointers are staged into `ws` (device), then one launch
 void vm_staging::release() {
   for (int i = 0; i < 2; i++) {
     if (copied[i]) { (void)hipEventSynchronize(copied[i]); (void)hipEventDestroy(copied[i]); copied[i] = nullptr; }
@@ -462,184 +423,31 @@ void vm_staging::release() {
   }
 }
 
-// One program's region of a staged blob -- [micro-ops (+ 4 padding no-ops) | constants | rotation offsets], `region` on the host, `dev`
-// its device address, the constants at `o_const` and the rotation offsets at `o_rot` from its start.
-// micro-ops: the instruction + its operands' resolved addresses; a product's second factor is fetched scaled by 2^5 -- free for a column /
-// constant (the other unpacking shift), a repack for a register -- so the memory operand goes second where the host did not put it there
-// window = true: the columns are window buffers (rowvm_window below) and a rotation's offset is halo_lo + rotation * rot_scale, not reduced.
-static void vm_fill_region(const zkhip_vm_program* p, const void* const* d_columns, uint64_t rows, unsigned char* region, uint64_t dev, size_t o_const, size_t o_rot,
-                           bool window = false) {
-  static_assert(sizeof(zkhip_vm_insn) == 16, "instruction layout");
-  std::vector<uint32_t> rot_rows(p->n_rotations ? p->n_rotations : 1, 0u);
-  uint64_t halo_lo = 0, halo_hi = 0;
-  if (window) row_vm_halos(p, &halo_lo, &halo_hi);
-  for (uint32_t i = 0; i < p->n_rotations; i++) {
-    if (window) { rot_rows[i] = (uint32_t)((int64_t)halo_lo + (int64_t)p->rotations[i] * (int64_t)p->rot_scale); continue; }
-    const int64_t off = ((int64_t)p->rotations[i] * (int64_t)p->rot_scale) % (int64_t)rows;
-    rot_rows[i] = (uint32_t)(off < 0 ? off + (int64_t)rows : off);
-  }
-  const uint64_t d_consts = dev + o_const;
-  vm_uop* uops = (vm_uop*)region;
-  for (uint32_t pc = 0; pc < p->n_insns + 4; pc++) {
-    vm_uop& u = uops[pc];
-    std::memset(&u, 0, sizeof(u));
-    u.base_a = u.base_b = d_consts;                      // dummy address for operands that are not in memory (and for the padding no-ops)
-    if (pc >= p->n_insns) { u.head = ZKHIP_OP_MOV | ((uint32_t)0 << 8); u.oa = ZKHIP_SRC_REG; continue; }   // MOV r0 <- r0 (never executed)
-    zkhip_vm_insn in = p->insns[pc];
-    const bool a_mem = in.a.kind == ZKHIP_SRC_COLUMN || in.a.kind == ZKHIP_SRC_CONST;
-    const bool b_mem = in.b.kind == ZKHIP_SRC_COLUMN || in.b.kind == ZKHIP_SRC_CONST;
-    if ((in.op == ZKHIP_OP_MUL || in.op == ZKHIP_OP_MAD) && a_mem && !b_mem) { const zkhip_vm_operand t = in.a; in.a = in.b; in.b = t; }
-    std::memcpy(&u, &in, 16);
-    const bool uses_b = in.op == ZKHIP_OP_MUL || in.op == ZKHIP_OP_MAD || in.op == ZKHIP_OP_ADD || in.op == ZKHIP_OP_SUB;
-    auto resolve = [&](const zkhip_vm_operand& o, bool used, uint64_t* base, uint32_t* off, uint32_t* mask) {
-      if (!used) return;
-      if (o.kind == ZKHIP_SRC_COLUMN) { *base = (uint64_t)d_columns[o.index]; *off = rot_rows[o.rot]; *mask = 0xffffffffu; }
-      else if (o.kind == ZKHIP_SRC_CONST) { *base = d_consts + (uint64_t)o.index * 32; }
-    };
-    resolve(in.a, true, &u.base_a, &u.off_a, &u.mask_a);
-    resolve(in.b, uses_b, &u.base_b, &u.off_b, &u.mask_b);
-  }
-  if (p->n_constants) std::memcpy(region + o_const, p->constants, (size_t)p->n_constants * 32);
-  for (uint32_t i = 0; i < p->n_rotations; i++) std::memcpy(region + o_rot + (size_t)i * 4, &rot_rows[i], 4);      // (a MAD's column addend still goes through the tables)
-}
-
-// highest register a program names (the kernel variant is sized for it)
-static uint32_t vm_top_register(const zkhip_vm_program* p) {
-  uint32_t top = p->result_reg;
-  for (uint32_t pc = 0; pc < p->n_insns; pc++) {
-    const zkhip_vm_insn& in = p->insns[pc];
-    if (in.dst > top) top = in.dst;
-    const zkhip_vm_operand* o[3] = {&in.a, &in.b, &in.c};
-    for (int k = 0; k < 3; k++) if (o[k]->kind == ZKHIP_SRC_REG && o[k]->index < (uint32_t)VM_MAX_REGS && o[k]->index > top) top = o[k]->index;
-  }
-  return top;
-}
-
-static int vm_launch_kernel(const vm_launch& L, uint32_t top, uint32_t n_parts, hipStream_t stream, bool check = false) {
-  const dim3 grid((unsigned)((L.rows + VM_THREADS - 1) / VM_THREADS), n_parts);
-  if (check) {
-    if (top < 6) hipLaunchKernelGGL((k_row_vm<6, true>), grid, dim3(VM_THREADS), 0, stream, L);
-    else if (top < 8) hipLaunchKernelGGL((k_row_vm<8, true>), grid, dim3(VM_THREADS), 0, stream, L);
-    else if (top < 12) hipLaunchKernelGGL((k_row_vm<12, true>), grid, dim3(VM_THREADS), 0, stream, L);
-    else hipLaunchKernelGGL((k_row_vm<16, true>), grid, dim3(VM_THREADS), 0, stream, L);
-  }
-  else if (top < 6) hipLaunchKernelGGL(k_row_vm<6>, grid, dim3(VM_THREADS), 0, stream, L);
-  else if (top < 8) hipLaunchKernelGGL(k_row_vm<8>, grid, dim3(VM_THREADS), 0, stream, L);
-  else if (top < 12) hipLaunchKernelGGL(k_row_vm<12>, grid, dim3(VM_THREADS), 0, stream, L);
-  else hipLaunchKernelGGL(k_row_vm<16>, grid, dim3(VM_THREADS), 0, stream, L);
-  HIPCHK(hipGetLastError());
-  return ZKHIP_OK;
-}
-
-// `n_progs` programs over the same columns in ONE launch (blockIdx.y = program), program p writing d_outs[p]: what
-// zkhip_fr_eval_rows_sum_device runs its parts with.  Separate launches on separate streams overlap four at a time (the hardware queues);
-// one grid has no such limit.  Blob: [columns | omega | part records | region of program 0 | region of program 1 | ...], power tables behind.
-// Programs that read ZKHIP_SRC_ROWPOW must agree on omega.  Interpreter only (these are long programs over few rows).
-size_t row_vm_multi_workspace_bytes(const zkhip_vm_program* progs, uint32_t n_progs, uint32_t n_columns, uint32_t log_rows) {
-  const size_t rows = (size_t)1 << log_rows;
-  size_t total = align256((size_t)n_columns * 8 + 8) + 256 + align256((size_t)n_progs * sizeof(vm_part));
-  for (uint32_t i = 0; i < n_progs; i++)
-    total += align256(((size_t)progs[i].n_insns + 4) * sizeof(vm_uop)) + align256((size_t)progs[i].n_constants * 32 + 32) + align256((size_t)progs[i].n_rotations * 4 + 4);
-  return total + align256(((size_t)1 << POW_LO_BITS) * 32) + align256(((rows >> POW_LO_BITS) + 1) * 32);
-}
-
-// the pinned buffer of `staging` whose turn it is, at least `bytes` long and zeroed (waits for the copy that last read it); nullptr = failure
-static unsigned char* vm_staging_acquire(vm_staging* staging, size_t bytes, int* slot_out) {
+// *slot: the pinned buffer of `staging` whose turn it is, at least `bytes` long and zeroed (waits for the copy that last read it)
+static int vm_staging_acquire(vm_staging* staging, size_t bytes, int* slot_out) {
   const int slot = staging->turn;
   staging->turn ^= 1;
-  if (staging->copied[slot]) { if (hipEventSynchronize(staging->copied[slot]) != hipSuccess) { set_error("eval_rows: event wait failed"); return nullptr; } }
-  else if (hipEventCreateWithFlags(&staging->copied[slot], hipEventDisableTiming) != hipSuccess) { set_error("eval_rows: hipEventCreate failed"); return nullptr; }
+  if (staging->copied[slot]) { if (hipEventSynchronize(staging->copied[slot]) != hipSuccess) { set_error("eval_rows: event wait failed"); return ZKHIP_EHIP; } }
+  else if (hipEventCreateWithFlags(&staging->copied[slot], hipEventDisableTiming) != hipSuccess) { set_error("eval_rows: hipEventCreate failed"); return ZKHIP_EHIP; }
   if (staging->cap[slot] < bytes) {
     if (staging->host[slot]) (void)hipHostFree(staging->host[slot]);
     staging->host[slot] = nullptr; staging->cap[slot] = 0;
-    const size_t want = align256(bytes + bytes / 2 + 4096);
-    if (hipHostMalloc(&staging->host[slot], want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("eval_rows: hipHostMalloc(%zu) failed", want); return nullptr; }
+    const size_t want = vm_align256(bytes + bytes / 2 + 4096);
+    if (hipHostMalloc(&staging->host[slot], want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("eval_rows: hipHostMalloc(%zu) failed", want); return ZKHIP_ENOMEM; }
     staging->cap[slot] = want;
   }
   std::memset(staging->host[slot], 0, bytes);
   *slot_out = slot;
-  return (unsigned char*)staging->host[slot];
+  return ZKHIP_OK;
 }
 
-// check: the check variant over rows [row0, row0 + count), d_outs[p] = program p's report record (initialised here, behind every argument check)
-static int row_vm_multi_run(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint32_t* const* d_outs,
-                            void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, bool check, uint64_t row0, uint64_t count) {
-  const uint64_t rows = (uint64_t)1 << log_rows;
-  if (n_progs == 0 || n_progs > 65535) { set_error("eval_rows: %u programs in one launch", n_progs); return ZKHIP_EINVAL; }
-  if (ws_bytes < row_vm_multi_workspace_bytes(progs, n_progs, n_columns, log_rows)) { set_error("eval_rows: workspace too small"); return ZKHIP_EINVAL; }
-  for (uint32_t i = 0; i < n_columns; i++)
-    if (!d_columns[i]) { set_error("eval_rows: column %u is null", i); return ZKHIP_EINVAL; }
-  const uint64_t* omega = nullptr;
-  uint32_t top = 0;
-  for (uint32_t i = 0; i < n_progs; i++) {
-    if (progs[i].omega) {
-      if (omega && std::memcmp(omega, progs[i].omega, 32) != 0) { set_error("eval_rows: programs of one launch disagree on omega"); return ZKHIP_EINVAL; }
-      omega = progs[i].omega;
-    }
-    const uint32_t t = vm_top_register(&progs[i]);
-    if (t > top) top = t;
-  }
-  const size_t o_cols = 0, o_omega = o_cols + align256((size_t)n_columns * 8 + 8), o_parts = o_omega + 256;
-  size_t off = o_parts + align256((size_t)n_progs * sizeof(vm_part));
-  std::vector<size_t> o_region(n_progs), o_const(n_progs), o_rot(n_progs);
-  for (uint32_t i = 0; i < n_progs; i++) {
-    o_region[i] = off;
-    o_const[i] = align256(((size_t)progs[i].n_insns + 4) * sizeof(vm_uop));
-    o_rot[i] = o_const[i] + align256((size_t)progs[i].n_constants * 32 + 32);
-    off += o_rot[i] + align256((size_t)progs[i].n_rotations * 4 + 4);
-  }
-  const size_t o_lo = off, o_hi = o_lo + align256(((size_t)1 << POW_LO_BITS) * 32);
-  // the blob: pinned staging of the caller's scratch set (no wait for the stream), or a local vector (then the stream is synchronised below)
-  std::vector<unsigned char> local;
-  int slot = -1;
-  struct { unsigned char* p; unsigned char* data() const { return p; } } blob{nullptr};
-  if (staging) {
-    blob.p = vm_staging_acquire(staging, o_lo, &slot);
-    if (!blob.p) return ZKHIP_EHIP;
-  } else {
-    local.assign(o_lo, 0);
-    blob.p = local.data();
-  }
-  char* d = (char*)ws;
-  if (check) { const int rc = check_reports_init_device(d_outs[0], n_progs, stream); if (rc != ZKHIP_OK) return rc; }
-  for (uint32_t i = 0; i < n_columns; i++) std::memcpy(blob.data() + o_cols + (size_t)i * 8, &d_columns[i], 8);
-  if (omega) std::memcpy(blob.data() + o_omega, omega, 32);
-  vm_part* parts = (vm_part*)(blob.data() + o_parts);
-  for (uint32_t i = 0; i < n_progs; i++) {
-    vm_fill_region(&progs[i], d_columns, rows, blob.data() + o_region[i], (uint64_t)(d + o_region[i]), o_const[i], o_rot[i]);
-    parts[i].prog = (const void*)(d + o_region[i]);
-    parts[i].consts = (const uint32_t*)(d + o_region[i] + o_const[i]);
-    parts[i].rot_off = (const uint32_t*)(d + o_region[i] + o_rot[i]);
-    parts[i].out = d_outs[i];
-    parts[i].n_insns = progs[i].n_insns;
-    parts[i].result_reg = progs[i].result_reg;
-  }
-  HIPCHK(hipMemcpyAsync(d, blob.data(), o_lo, hipMemcpyHostToDevice, stream));
-  if (staging) HIPCHK(hipEventRecord(staging->copied[slot], stream));
-  else HIPCHK(hipStreamSynchronize(stream));                 // the blob is a local
-  vm_launch L;
-  L.prog = parts[0].prog; L.n_insns = parts[0].n_insns; L.result_reg = parts[0].result_reg;
-  L.cols = (const uint32_t* const*)(d + o_cols);
-  L.consts = parts[0].consts; L.rot_off = parts[0].rot_off;
-  L.pow_lo = nullptr; L.pow_hi = nullptr;
-  L.out = d_outs[0];
-  L.rows = check ? count : rows;
-  L.accumulate = 0;
-  L.parts = (const vm_part*)(d + o_parts);
-  L.wrap = rows - 1; L.row0 = check ? row0 : 0; L.dom_mask = rows - 1;
-  if (omega) {
-    const uint32_t n_lo = 1u << POW_LO_BITS, n_hi = (uint32_t)((rows >> POW_LO_BITS) ? (rows >> POW_LO_BITS) : 1);
-    hipLaunchKernelGGL(k_vm_pow_table, dim3((n_lo + 255) / 256), dim3(256), 0, stream, (const fe_arg*)(d + o_omega), 0u, n_lo, (uint32_t*)(d + o_lo));
-    hipLaunchKernelGGL(k_vm_pow_table, dim3((n_hi + 255) / 256), dim3(256), 0, stream, (const fe_arg*)(d + o_omega), POW_LO_BITS, n_hi, (uint32_t*)(d + o_hi));
-    L.pow_lo = (const uint32_t*)(d + o_lo);
-    L.pow_hi = (const uint32_t*)(d + o_hi);
-  }
-  return vm_launch_kernel(L, top, n_progs, stream, check);
-}
-
-int row_vm_device_multi(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint32_t* const* d_outs,
-                        void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging) {
-  return row_vm_multi_run(progs, n_progs, d_columns, n_columns, log_rows, d_outs, ws, ws_bytes, stream, staging, false, 0, (uint64_t)1 << log_rows);
+// smallest register-file variant that holds every register the programs name (top = the highest)
+template <bool CHECK>
+static void vm_launch_variant(const vm_launch& L, uint32_t top, dim3 grid, hipStream_t stream) {
+  if (top < 6) hipLaunchKernelGGL((k_row_vm<6, CHECK>), grid, dim3(VM_THREADS), 0, stream, L);
+  else if (top < 8) hipLaunchKernelGGL((k_row_vm<8, CHECK>), grid, dim3(VM_THREADS), 0, stream, L);
+  else if (top < 12) hipLaunchKernelGGL((k_row_vm<12, CHECK>), grid, dim3(VM_THREADS), 0, stream, L);
+  else hipLaunchKernelGGL((k_row_vm<16, CHECK>), grid, dim3(VM_THREADS), 0, stream, L);
 }
 
 int check_reports_init_device(void* d_reports, uint32_t n, hipStream_t stream) {
@@ -649,16 +457,73 @@ int check_reports_init_device(void* d_reports, uint32_t n, hipStream_t stream) {
   return ZKHIP_OK;
 }
 
-int row_vm_check_device(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint64_t row0,
-                        uint64_t count, void* d_reports, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging) {
-  const uint64_t rows = (uint64_t)1 << log_rows;
-  if (count == 0 || count > rows || row0 > rows - count) {
-    set_error("check_rows: rows [%llu, +%llu) outside a domain of 2^%u rows", (unsigned long long)row0, (unsigned long long)count, log_rows);
+// Every launch of the interpreter (the forms: vm_call, zkhip_internal.hpp): the blob of rowvm_blob.hpp is filled in pinned staging and copied
+// into the workspace without a wait for the stream, the power tables are built behind it where a program names an omega, then one grid --
+// blockIdx.y = program where the programs run side by side.  Separate launches on separate streams overlap four at a time (the hardware
+// queues); one grid has no such limit.
+int row_vm_launch(const vm_call& c) {
+  const uint64_t rows = (uint64_t)1 << c.log_rows;
+  const bool check = c.form == VM_CHECK, window = c.form == VM_WINDOW, ranged = check || window, multi = check || c.d_outs;
+  if (c.compiled) *c.compiled = 0;
+  // every argument check, and the plan the workspace is measured against: nothing is staged or enqueued before they pass
+  if (check && (c.count == 0 || c.count > rows || c.row0 > rows - c.count)) {
+    set_error("check_rows: rows [%llu, +%llu) outside a domain of 2^%u rows", (unsigned long long)c.row0, (unsigned long long)c.count, c.log_rows);
     return ZKHIP_EINVAL;
   }
-  std::vector<uint32_t*> records(n_progs);
-  for (uint32_t p = 0; p < n_progs; p++) records[p] = (uint32_t*)((zkhip_check_report*)d_reports + p);
-  return row_vm_multi_run(progs, n_progs, d_columns, n_columns, log_rows, records.data(), ws, ws_bytes, stream, staging, true, row0, count);
+  if (c.n_progs == 0 || c.n_progs > 65535) { set_error("eval_rows: %u programs in one launch", c.n_progs); return ZKHIP_EINVAL; }
+  const vm_blob_plan P = vm_blob_make_plan(c.progs, c.n_progs, c.n_columns, c.log_rows);
+  if (c.ws_bytes < P.total) { set_error("eval_rows: workspace too small"); return ZKHIP_EINVAL; }
+  for (uint32_t i = 0; i < c.n_columns; i++)
+    if (!c.d_columns[i]) { set_error("eval_rows: column %u is null", i); return ZKHIP_EINVAL; }
+  const uint64_t* omega = nullptr;
+  uint32_t top = 0;
+  for (uint32_t i = 0; i < c.n_progs; i++) {
+    if (c.progs[i].omega) {
+      if (omega && std::memcmp(omega, c.progs[i].omega, 32) != 0) { set_error("eval_rows: programs of one launch disagree on omega"); return ZKHIP_EINVAL; }
+      omega = c.progs[i].omega;
+    }
+    top = std::max(top, vm_top_register(&c.progs[i]));
+  }
+  int slot = -1, rc = vm_staging_acquire(c.staging, P.staged, &slot);
+  if (rc != ZKHIP_OK) return rc;
+  unsigned char* blob = (unsigned char*)c.staging->host[slot];
+  char* d = (char*)c.ws;
+  vm_blob_fill(P, c.progs, c.n_progs, c.d_columns, c.n_columns, c.log_rows, window, omega, c.d_outs, c.d_out, check ? sizeof(zkhip_check_report) / 4 : 0, (uint64_t)d, blob);
+  if (check && (rc = check_reports_init_device(c.d_out, c.n_progs, c.stream)) != ZKHIP_OK) return rc;
+  HIPCHK(hipMemcpyAsync(d, blob, P.staged, hipMemcpyHostToDevice, c.stream));
+  HIPCHK(hipEventRecord(c.staging->copied[slot], c.stream));
+  const vm_part& first = *(const vm_part*)(blob + P.o_parts);      // (the kernel reads the records only where the programs run side by side)
+  vm_launch L;
+  L.prog = first.prog; L.n_insns = first.n_insns; L.result_reg = first.result_reg;
+  L.cols = (const uint32_t* const*)(d + P.o_cols);
+  L.consts = first.consts; L.rot_off = first.rot_off;
+  L.pow_lo = nullptr; L.pow_hi = nullptr;
+  L.out = first.out;
+  L.rows = ranged ? c.count : rows;
+  L.accumulate = c.accumulate ? 1u : 0u;
+  L.parts = multi ? (const vm_part*)(d + P.o_parts) : nullptr;
+  L.wrap = window ? ~0ull : rows - 1;        // window buffers: the rotation offsets include halo_lo and nothing wraps
+  L.row0 = ranged ? c.row0 : 0;
+  L.dom_mask = rows - 1;
+  if (omega) {
+    const uint32_t n_lo = 1u << POW_LO_BITS, n_hi = (uint32_t)((rows >> POW_LO_BITS) ? (rows >> POW_LO_BITS) : 1);
+    hipLaunchKernelGGL(k_vm_pow_table, dim3((n_lo + 255) / 256), dim3(256), 0, c.stream, (const fe_arg*)(d + P.o_omega), 0u, n_lo, (uint32_t*)(d + P.o_lo));
+    hipLaunchKernelGGL(k_vm_pow_table, dim3((n_hi + 255) / 256), dim3(256), 0, c.stream, (const fe_arg*)(d + P.o_omega), POW_LO_BITS, n_hi, (uint32_t*)(d + P.o_hi));
+    L.pow_lo = (const uint32_t*)(d + P.o_lo);
+    L.pow_hi = (const uint32_t*)(d + P.o_hi);
+  }
+  // one short program over many rows runs as compiled straight-line code when a kernel for its shape exists or can be built (rowvm_jit.hip);
+  // any failure there leaves nothing launched and the interpreter below takes the call
+  if (!multi && !c.interpreter_only && (window ? row_vm_jit_wanted_window(c.progs, c.n_columns, c.count) : row_vm_jit_wanted(c.progs, c.n_columns, c.log_rows)) &&
+      row_vm_jit_launch(c.progs, c.d_columns, c.n_columns, c.log_rows, window, L.row0, L.rows, c.accumulate, L.consts, L.pow_lo, L.pow_hi, c.d_out, c.stream) == ZKHIP_OK) {
+    if (c.compiled) *c.compiled = 1;
+    return ZKHIP_OK;
+  }
+  const dim3 grid((unsigned)((L.rows + VM_THREADS - 1) / VM_THREADS), c.n_progs);
+  if (check) vm_launch_variant<true>(L, top, grid, c.stream);
+  else vm_launch_variant<false>(L, top, grid, c.stream);
+  HIPCHK(hipGetLastError());
+  return ZKHIP_OK;
 }
 
 int check_copies_device(const void* d_columns_dev, uint32_t n_columns, uint32_t log_n, const uint32_t* d_map_col, const uint32_t* d_map_row, void* d_report,
@@ -670,116 +535,6 @@ int check_copies_device(const void* d_columns_dev, uint32_t n_columns, uint32_t 
                      (unsigned long long*)d_report);
   HIPCHK(hipGetLastError());
   return ZKHIP_OK;
-}
-
-void row_vm_halos(const zkhip_vm_program* p, uint64_t* lo, uint64_t* hi) {
-  int64_t l = 0, h = 0;
-  for (uint32_t i = 0; i < p->n_rotations; i++) {
-    const int64_t o = (int64_t)p->rotations[i] * (int64_t)p->rot_scale;
-    l = std::max(l, -o);
-    h = std::max(h, o);
-  }
-  *lo = (uint64_t)l;
-  *hi = (uint64_t)h;
-}
-
-// The whole-domain launch (window = false: row0 = 0, count = 2^log_rows, columns indexed modulo the domain) and the window launch (columns
-// are window buffers of halo_lo + count + halo_hi elements, indexed row + halo_lo + offset without a mask).  *compiled (if given): 1 when
-// the run-time compiled kernel took the call, 0 for the interpreter.  allow_jit = false: the interpreter, whatever the shape.
-static int row_vm_run(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, bool window, uint64_t row0, uint64_t count,
-                      int accumulate, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, int* compiled, bool allow_jit = true) {
-  const uint64_t rows = (uint64_t)1 << log_rows;
-  if (compiled) *compiled = 0;
-  if (ws_bytes < row_vm_workspace_bytes(p, n_columns, log_rows)) { set_error("eval_rows: workspace too small"); return ZKHIP_EINVAL; }
-  // one host blob, one copy
-  const size_t o_prog = 0;
-  const size_t o_const = o_prog + align256(((size_t)p->n_insns + 4) * sizeof(vm_uop));
-  const size_t o_rot = o_const + align256((size_t)p->n_constants * 32 + 32);
-  const size_t o_cols = o_rot + align256((size_t)p->n_rotations * 4 + 4);
-  const size_t o_omega = o_cols + align256((size_t)n_columns * 8 + 8);
-  const size_t o_lo = o_omega + 256;
-  const size_t o_hi = o_lo + align256(((size_t)1 << POW_LO_BITS) * 32);
-  // the blob: pinned staging of the caller's scratch set (no wait for the stream), or a local vector (then the stream is synchronised below)
-  std::vector<unsigned char> local;
-  unsigned char* blob_p = nullptr;
-  int slot = -1;
-  if (staging) {
-    slot = staging->turn;
-    staging->turn ^= 1;
-    if (staging->copied[slot]) HIPCHK(hipEventSynchronize(staging->copied[slot]));          // the copy that last read this buffer is done
-    else HIPCHK(hipEventCreateWithFlags(&staging->copied[slot], hipEventDisableTiming));
-    if (staging->cap[slot] < o_lo) {
-      if (staging->host[slot]) (void)hipHostFree(staging->host[slot]);
-      staging->host[slot] = nullptr; staging->cap[slot] = 0;
-      const size_t want = align256(o_lo + o_lo / 2 + 4096);
-      if (hipHostMalloc(&staging->host[slot], want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("eval_rows: hipHostMalloc(%zu) failed", want); return ZKHIP_ENOMEM; }
-      staging->cap[slot] = want;
-    }
-    blob_p = (unsigned char*)staging->host[slot];
-    std::memset(blob_p, 0, o_lo);
-  } else {
-    local.assign(o_lo, 0);
-    blob_p = local.data();
-  }
-  struct { unsigned char* p; unsigned char* data() const { return p; } } blob{blob_p};
-  for (uint32_t i = 0; i < n_columns; i++)
-    if (!d_columns[i]) { set_error("eval_rows: column %u is null", i); return ZKHIP_EINVAL; }
-  vm_fill_region(p, d_columns, rows, blob.data(), (uint64_t)(char*)ws, o_const, o_rot, window);
-  for (uint32_t i = 0; i < n_columns; i++) std::memcpy(blob.data() + o_cols + (size_t)i * 8, &d_columns[i], 8);
-  if (p->omega) std::memcpy(blob.data() + o_omega, p->omega, 32);
-  char* d = (char*)ws;
-  HIPCHK(hipMemcpyAsync(d, blob.data(), o_lo, hipMemcpyHostToDevice, stream));
-  if (staging) HIPCHK(hipEventRecord(staging->copied[slot], stream));
-  else HIPCHK(hipStreamSynchronize(stream));   // the blob is a local
-  vm_launch L;
-  L.parts = nullptr;
-  L.prog = (const void*)(d + o_prog);
-  L.n_insns = p->n_insns;
-  L.result_reg = p->result_reg;
-  L.cols = (const uint32_t* const*)(d + o_cols);
-  L.consts = (const uint32_t*)(d + o_const);
-  L.rot_off = (const uint32_t*)(d + o_rot);
-  L.pow_lo = nullptr;
-  L.pow_hi = nullptr;
-  L.out = d_out;
-  L.rows = window ? count : rows;
-  L.accumulate = accumulate ? 1u : 0u;
-  L.wrap = window ? ~0ull : rows - 1;
-  L.row0 = window ? row0 : 0;
-  L.dom_mask = rows - 1;
-  if (p->omega) {
-    const uint32_t n_lo = 1u << POW_LO_BITS, n_hi = (uint32_t)((rows >> POW_LO_BITS) ? (rows >> POW_LO_BITS) : 1);
-    hipLaunchKernelGGL(k_vm_pow_table, dim3((n_lo + 255) / 256), dim3(256), 0, stream, (const fe_arg*)(d + o_omega), 0u, n_lo, (uint32_t*)(d + o_lo));
-    hipLaunchKernelGGL(k_vm_pow_table, dim3((n_hi + 255) / 256), dim3(256), 0, stream, (const fe_arg*)(d + o_omega), POW_LO_BITS, n_hi, (uint32_t*)(d + o_hi));
-    L.pow_lo = (const uint32_t*)(d + o_lo);
-    L.pow_hi = (const uint32_t*)(d + o_hi);
-  }
-  // a short program over many rows runs as compiled straight-line code when a kernel for its shape exists or can be built (rowvm_jit.hip);
-  // any failure there leaves nothing launched and the interpreter below takes the call
-  if (allow_jit && (window ? row_vm_jit_wanted_window(p, n_columns, count) : row_vm_jit_wanted(p, n_columns, log_rows)) &&
-      row_vm_jit_launch(p, d_columns, n_columns, log_rows, window, L.row0, L.rows, accumulate, L.consts, L.pow_lo, L.pow_hi, d_out, stream) == ZKHIP_OK) {
-    if (compiled) *compiled = 1;
-    return ZKHIP_OK;
-  }
-  // smallest register-file variant that holds every register the program names
-  return vm_launch_kernel(L, vm_top_register(p), 1, stream);
-}
-
-int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, int accumulate,
-                  uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, int* compiled) {
-  return row_vm_run(p, d_columns, n_columns, log_rows, false, 0, (uint64_t)1 << log_rows, accumulate, d_out, ws, ws_bytes, stream, staging, compiled);
-}
-
-int row_vm_window_device(const zkhip_vm_program* p, const void* const* d_windows, uint32_t n_columns, uint32_t log_rows, uint64_t row0, uint64_t count,
-                         int accumulate, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging, int* compiled) {
-  return row_vm_run(p, d_windows, n_columns, log_rows, true, row0, count, accumulate, d_out, ws, ws_bytes, stream, staging, compiled);
-}
-
-// `count` independent rows: a window launch over a domain of one row, so that column i is simply `count` elements and nothing wraps.  The
-// program names no rotation but 0 and neither PREV nor ROWPOW (the caller has checked); workspace as row_vm_device with log_rows = 0.
-int row_vm_rows_device(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint64_t count, uint32_t* d_out, void* ws, size_t ws_bytes,
-                       hipStream_t stream, vm_staging* staging) {
-  return row_vm_run(p, d_columns, n_columns, 0, true, 0, count, 0, d_out, ws, ws_bytes, stream, staging, nullptr, false);
 }
 
 int fr_pointwise_mul_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t* d_out, hipStream_t stream) {

@@ -184,15 +184,6 @@ __global__ void __launch_bounds__(IE_THREADS) k_instance_evals(const uint32_t* _
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
-static bool id_canonical(const uint64_t* w) {
-  static const uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
-  for (int i = 3; i >= 0; i--) {
-    if (w[i] < R[i]) return true;
-    if (w[i] > R[i]) return false;
-  }
-  return false;
-}
-
 int identity_domain_validate(const char* who, uint32_t k, uint64_t usable_rows, const uint64_t* omega) {
   if (!omega) { set_error("%s: null omega", who); return ZKHIP_EINVAL; }
   if (k > 28) { set_error("%s: k = %u > 28", who, k); return ZKHIP_EINVAL; }
@@ -201,7 +192,7 @@ int identity_domain_validate(const char* who, uint32_t k, uint64_t usable_rows, 
     set_error("%s: usable_rows = %llu: needs 1 <= usable_rows < 2^%u and 2^%u - usable_rows <= %u", who, (unsigned long long)usable_rows, k, k, IDENTITY_MAX_TAIL);
     return ZKHIP_EINVAL;
   }
-  if (!id_canonical(omega)) { set_error("%s: omega is not a canonical Fr", who); return ZKHIP_EINVAL; }
+  if (!fr_words_canonical(omega)) { set_error("%s: omega is not a canonical Fr", who); return ZKHIP_EINVAL; }
   return ZKHIP_OK;
 }
 
@@ -253,7 +244,7 @@ size_t verify_identity_columns_bytes(uint32_t n_evals, uint32_t n_queries, uint6
 }
 
 size_t verify_identity_vm_bytes(const zkhip_vm_program* p, uint32_t n_evals, uint32_t n_queries) {
-  return row_vm_workspace_bytes(p, n_evals + ID_DERIVED + n_queries, 0);
+  return row_vm_workspace_bytes(p, 1, n_evals + ID_DERIVED + n_queries, 0);
 }
 
 int instance_queries_validate(const char* who, uint32_t k, uint64_t max_len, const char* max_name, const uint32_t* column_lens, uint32_t n_columns,
@@ -332,7 +323,13 @@ int verify_identity_device(const zkhip_vm_program* prog, const uint32_t* d_evals
                                                    cols + (size_t)(n_evals + ID_DERIVED) * n_proofs * 8, stream)) != ZKHIP_OK) return rc;
   std::vector<const void*> columns(n_columns);
   for (uint32_t c = 0; c < n_columns; c++) columns[c] = cols + (size_t)c * n_proofs * 8;
-  if ((rc = row_vm_rows_device(prog, columns.data(), n_columns, n_proofs, result, vm_ws, vm_ws_bytes, stream, staging)) != ZKHIP_OK) return rc;
+  // a proof is a row of its own: a window launch over a domain of ONE row, so that column i is simply n_proofs elements and nothing wraps (the
+  // program names no rotation but 0 and neither PREV nor ROWPOW: verify_identity_validate).  The interpreter, whatever the shape.
+  vm_call c;
+  c.progs = prog; c.d_columns = columns.data(); c.n_columns = n_columns; c.log_rows = 0;
+  c.form = VM_WINDOW; c.count = n_proofs; c.d_out = result; c.interpreter_only = true;
+  c.ws = vm_ws; c.ws_bytes = vm_ws_bytes; c.stream = stream; c.staging = staging;
+  if ((rc = row_vm_launch(c)) != ZKHIP_OK) return rc;
   hipLaunchKernelGGL(k_identity_verdict, dim3((unsigned)((n_proofs + 255) / 256)), dim3(256), 0, stream, (const uint4*)result, flags, n_proofs, d_status,
                      (unsigned long long*)d_report);
   HIPCHK(hipGetLastError());

@@ -7,10 +7,19 @@
 #include <cstring>
 #include "../../include/zkhip.h"
 #include "scan_plan.hpp"      // defines the *_workspace_bytes of the chunked scans declared below (inline, host-only)
+#include "rowvm_blob.hpp"     // the row programs' blob: its plan and row_vm_workspace_bytes (inline, host-only)
 
 namespace zkhip {
 
 void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+
+// four little-endian words below the modulus of Fr
+static inline bool fr_words_canonical(const uint64_t w[4]) {
+  constexpr uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
+  for (int i = 3; i >= 0; i--)
+    if (w[i] != R[i]) return w[i] < R[i];
+  return false;
+}
 
 // a failed HIP call ends the function it is in: its text and HIP's message become the thread's error, ZKHIP_EHIP the return value
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ::zkhip::set_error("%s failed: %s", #x, hipGetErrorString(e_)); return ZKHIP_EHIP; } } while (0)
@@ -172,12 +181,11 @@ int fr_lookup_products_device(const void* const* d_inputs_host, const void* cons
                               uint32_t n_lookups, uint32_t log_n, size_t usable, const uint32_t beta[8], const uint32_t gamma[8], uint32_t* d_z, void* ws,
                               size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
 
-// rowvm.hip
+// rowvm.hip (the blob a launch reads, its plan, row_vm_workspace_bytes and row_vm_halos: rowvm_blob.hpp)
 int row_vm_validate(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, int accumulate);
-size_t row_vm_workspace_bytes(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows);
-// Pinned host staging for the program blob of a row program (two buffers, used alternately; an event per buffer says when the copy that read
-// it has completed).  With it row_vm_device never waits for the stream: the host builds program i + 1 while program i runs.  Owned by the
-// caller's scratch set (one user at a time); nullptr = build the blob in a local buffer and synchronise the stream after the copy.
+// Pinned host staging for the blob of a launch (two buffers, used alternately; an event per buffer says when the copy that read it has
+// completed).  With it row_vm_launch never waits for the stream: the host builds launch i + 1 while launch i runs.  Owned by the caller's
+// scratch set (one user at a time).
 struct vm_staging {
   void* host[2] = {nullptr, nullptr};
   size_t cap[2] = {0, 0};
@@ -185,11 +193,37 @@ struct vm_staging {
   int turn = 0;
   void release();
 };
-size_t row_vm_multi_workspace_bytes(const zkhip_vm_program* progs, uint32_t n_progs, uint32_t n_columns, uint32_t log_rows);
-int row_vm_device_multi(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint32_t* const* d_outs,
-                        void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging = nullptr);
-// rowvm_jit.hip: row programs compiled at run time with hiprtc (straight-line code per program shape, cached per device); row_vm_device
-// tries it first for short programs over many rows and runs the interpreter otherwise
+// One launch of row programs over Fr columns.  The forms:
+//   VM_WHOLE   every row of a 2^log_rows domain, column i = 2^log_rows elements indexed modulo the domain.  One program writes d_out
+//              (accumulate: reads it first, ZKHIP_SRC_PREV); with d_outs set, n_progs programs run side by side in ONE launch, program p
+//              writing d_outs[p] (PREV reads 0; programs that read ZKHIP_SRC_ROWPOW must agree on omega)
+//   VM_WINDOW  one program over `count` rows from global row `row0`.  Column i is a window buffer of halo_lo + count + halo_hi elements,
+//              element t = column[(row0 - halo_lo + t) mod 2^log_rows] (row_vm_halos); ROWPOW is omega^((row0 + i) mod 2^log_rows); PREV / the
+//              output are d_out[i], i < count.  log_rows = 0 makes it `count` independent rows of programs without rotations or ROWPOW
+//   VM_CHECK   the witness checks' gates (include/zkhip.h, check_report.hpp): n_progs programs side by side over rows [row0, row0 + count) of
+//              whole-domain columns, nothing stored: d_out = n_progs zkhip_check_report records, initialised by the call
+// One program alone is tried on the run-time compiler first (rowvm_jit.hip: short programs over many rows) unless interpreter_only;
+// *compiled (if given): 1 when a compiled kernel took the call.  ws: row_vm_workspace_bytes(progs, n_progs, n_columns, log_rows).
+enum vm_form { VM_WHOLE, VM_WINDOW, VM_CHECK };
+struct vm_call {
+  const zkhip_vm_program* progs = nullptr;
+  uint32_t n_progs = 1;
+  const void* const* d_columns = nullptr;
+  uint32_t n_columns = 0, log_rows = 0;
+  vm_form form = VM_WHOLE;
+  uint64_t row0 = 0, count = 0;
+  int accumulate = 0;
+  uint32_t* d_out = nullptr;
+  uint32_t* const* d_outs = nullptr;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  hipStream_t stream = nullptr;
+  vm_staging* staging = nullptr;
+  bool interpreter_only = false;
+  int* compiled = nullptr;
+};
+int row_vm_launch(const vm_call& c);
+// rowvm_jit.hip: row programs compiled at run time with hiprtc (straight-line code per program shape, cached per device)
 bool row_vm_jit_wanted(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows);
 bool row_vm_jit_wanted_window(const zkhip_vm_program* p, uint32_t n_columns, uint64_t count);
 int row_vm_jit_launch(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, bool window, uint64_t row0, uint64_t count,
@@ -198,28 +232,12 @@ void row_vm_jit_clear();
 uint64_t row_vm_jit_launches();        // how many launches of this process went through a compiled kernel (never reset)
 int row_vm_jit_source(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, std::string* out);
 int row_vm_jit_compile_only(const zkhip_vm_program* p, uint32_t n_columns, uint32_t log_rows, size_t* code_bytes);
-int row_vm_device(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, int accumulate,
-                  uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging = nullptr, int* compiled = nullptr);
-// Window form: `count` rows from global row `row0` of a 2^log_rows domain.  Column i is a window buffer of halo_lo + count + halo_hi elements,
-// element t = column[(row0 - halo_lo + t) mod 2^log_rows]; halos from row_vm_halos (o = rotation * rot_scale, not reduced: halo_lo = max(0, -o),
-// halo_hi = max(0, o) over the rotations).  ROWPOW is omega^((row0 + i) mod 2^log_rows); PREV / the output are out[i], i < count.
-void row_vm_halos(const zkhip_vm_program* p, uint64_t* lo, uint64_t* hi);
-int row_vm_window_device(const zkhip_vm_program* p, const void* const* d_windows, uint32_t n_columns, uint32_t log_rows, uint64_t row0, uint64_t count,
-                         int accumulate, uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging = nullptr, int* compiled = nullptr);
-// `count` independent rows through the INTERPRETER (never the run-time compiler): column i holds `count` elements, d_out receives `count`.  For
-// programs whose rotations are all 0 and that read neither PREV nor ROWPOW (verify_identity.hip checks); workspace: row_vm_workspace_bytes(p, n_columns, 0)
-int row_vm_rows_device(const zkhip_vm_program* p, const void* const* d_columns, uint32_t n_columns, uint64_t count, uint32_t* d_out, void* ws, size_t ws_bytes,
-                       hipStream_t stream, vm_staging* staging = nullptr);
 int fr_pointwise_mul_device(const uint32_t* d_a, const uint32_t* d_b, size_t n, uint32_t* d_out, hipStream_t stream);
 int fr_gather_mul_device(const uint32_t* d_a, uint32_t a_len, const uint32_t* d_ia, const uint32_t* d_b, uint32_t b_len, const uint32_t* d_ib, size_t n,
                          uint32_t* d_out, hipStream_t stream);
 // The witness checks (include/zkhip.h, "witness checks"; check_report.hpp).  d_reports: zkhip_check_report records, initialised by the call.
 // reports[i] = (0, none) for i < n, on `stream`
 int check_reports_init_device(void* d_reports, uint32_t n, hipStream_t stream);
-// gates: the programs side by side in one launch of the check variant of the interpreter, rows [row0, row0 + count) of whole-domain columns;
-// workspace as row_vm_device_multi
-int row_vm_check_device(const zkhip_vm_program* progs, uint32_t n_progs, const void* const* d_columns, uint32_t n_columns, uint32_t log_rows, uint64_t row0,
-                        uint64_t count, void* d_reports, void* ws, size_t ws_bytes, hipStream_t stream, vm_staging* staging = nullptr);
 // copy constraints: d_columns_dev is the DEVICE array of the n_columns column addresses
 int check_copies_device(const void* d_columns_dev, uint32_t n_columns, uint32_t log_n, const uint32_t* d_map_col, const uint32_t* d_map_row, void* d_report,
                         hipStream_t stream);
@@ -314,7 +332,7 @@ size_t verify_identity_columns_bytes(uint32_t n_evals, uint32_t n_queries, uint6
 size_t verify_identity_vm_bytes(const zkhip_vm_program* p, uint32_t n_evals, uint32_t n_queries);   // vm_ws: the interpreter's workspace
 int verify_identity_device(const zkhip_vm_program* prog, const uint32_t* d_evals, uint32_t n_evals, const uint32_t* d_challenges, uint32_t k, uint32_t usable_rows,
                            const uint64_t* omega, const uint32_t* d_instances, const instance_layout& lay, uint64_t n_proofs, int32_t* d_status, void* d_report,
-                           void* cols_ws, void* vm_ws, size_t vm_ws_bytes, hipStream_t stream, vm_staging* staging = nullptr);
+                           void* cols_ws, void* vm_ws, size_t vm_ws_bytes, hipStream_t stream, vm_staging* staging);
 
 // gwc_fold.hip (include/zkhip.h, "the batch verifier").  The validator touches no device; `ws` holds the plan as the kernel reads it / the
 // second level's partial sums.

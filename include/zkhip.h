@@ -929,9 +929,9 @@ int zkhip_test_fq12_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *o
  * The openings of proof i accept exactly when e(A_i, g2) e(-C_i, [s]g2) = 1, A_i and C_i linear combinations of the proof's commitments, the
  * key's commitments and G.  With random r_i the batch accepts, except with probability about 1 / r, exactly when
  * e(sum r_i A_i, g2) e(-sum r_i C_i, [s]g2) = 1: two MSMs and one pairing check (halo2's `BatchVerifier`; the reference's aggregator folds its
- * KZG accumulators the same way, `KzgAs<Bn256, Gwc19>`).  The two calls below are the scalar side: the scalars of A_i and C_i for the GWC
- * multi-open of every proof, and the scaling and folding of such ROWS of scalars by the r_i; multiopen.fold_check is the sequence around them.
- * Both are asynchronous on `stream`, wait for nothing on the host and take their scratch from the stream's scratch set.  Elements are in the
+ * KZG accumulators the same way, `KzgAs<Bn256, Gwc19>`).  The calls below are the scalar side: the scalars of A_i and C_i of every proof for the
+ * GWC multi-open and for the SHPLONK multi-open, and the scaling and folding of such ROWS of scalars by the r_i; multiopen.fold_check is the
+ * sequence around them.  All are asynchronous on `stream`, wait for nothing on the host and take their scratch from the stream's scratch set.  Elements are in the
  * external Fr format (4 x u64 Montgomery-256, canonical); device arrays are 16-byte aligned.  Argument errors are ZKHIP_EINVAL, decided on the
  * host before the device is touched, with nothing enqueued.
  *
@@ -963,8 +963,39 @@ int zkhip_test_fq12_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *o
  * same call with offset pointers.  The outputs must not overlap the inputs.  ZKHIP_EINVAL: n_cols outside 1 .. 65536; n_own > n_cols; negate
  * other than 0 or 1; n_rows > 2^24 or n_rows n_cols > 2^32; a pointer that is read or written and is null or not 16-byte aligned (d_rows, d_r
  * and d_out_own only where n_rows > 0, d_out_own only where n_own > 0, d_out_shared only where n_own < n_cols).
- * Not built: the SHPLONK scalars on the device (the host's shplonk_accumulate makes those rows), folding across different circuits or
- * parameter sets, a batch sharded over devices. */
+ *
+ * zkhip_shplonk_plan: a key's opening plan as the SHPLONK verifier groups it, fixed per key and k, host memory, consumed before the call returns.
+ * n_points super points: point_rotation[t] is a distinct rotation of the plan reduced mod 2^k as an unsigned value.  n_sets rotation sets, the
+ * opened polynomials grouped by their set of rotations, sets in order of first appearance (multiopen.construct_rotation_sets grouped by
+ * rotation): set i holds the super points set_point[set_start[i] .. set_start[i + 1] - 1], at least one, none twice.  n_slots opened polynomials,
+ * one slot each, the proof's own first and the key's behind them: slot_set[p] is the set of polynomial p (it has exactly one), slot_pos[p] its
+ * position inside that set, the exponent of y.  Query q is evaluation q of a proof's record: polynomial query_slot[q] at super point
+ * query_point[q]; every (polynomial, point of its set) pair is queried exactly once.  (A tagged struct: its ctypes mirror _lib.ShplonkPlan is
+ * checked by tests/test_shplonk_fold_host.py.)
+ *
+ * zkhip_shplonk_scalars_device.  d_evals: [n_proofs][n_evals]; d_points: [n_proofs][4] = x, y, v, u; d_status: [n_proofs] uint32.  Per proof,
+ * with w = omega (the 2^k-th root the rotations are powers of; taken as given) and d_t = u - x w^point_rotation[t]:
+ *   Z_i = the product of d_t over the super points outside set i (the empty product is 1), Z_T = the product over all of them,
+ *   w_i = v^i Z_i / Z_0,
+ *   L_(i,a) = w_i prod_(b in set i, b != a) d_b / (x w^rot_a - x w^rot_b): w_i times the Lagrange basis of set i's points at u.
+ * COLUMNS OF A ROW OF d_rows_a (normative), with n_cols = 2 + n_slots + 1, the layout [H', H | own polynomials | key polynomials | G]:
+ *   column 0 (H'):                            u
+ *   column 1 (H):                             - Z_T / Z_0
+ *   column 2 + p (polynomial slot p):         w_slot_set[p] y^slot_pos[p]
+ *   column n_cols - 1 (G):                    - sum_q L_(slot_set[query_slot[q]], query_point[q]) y^slot_pos[query_slot[q]] evals[q]
+ * d_rows_a is [n_proofs][n_cols]; d_rows_c is [n_proofs][1], the column 1 (the scalar of H').  These are multiopen.shplonk_accumulate's scalars.
+ * status 0: the rows are written.  status 1: x Z_0 = 0 -- x = 0, or u on a point outside set 0 --, the proof has no such row: both of its rows are
+ * written as zeros, no other proof of the launch is affected, and the caller verifies that proof one by one.  u on a point of set 0 is status 0:
+ * Z_T = 0 and the H column is an exact zero.  One workgroup per proof and one field inversion per proof; 1 / prod (w^rot_a - w^rot_b) is
+ * computed on the host when the plan is marshalled.  The plan is validated, marshalled and uploaded inside every call, through the same ring
+ * of pinned slots as the GWC plan (its tables: 8 + 8 n_points + 9 pairs + n_sets + 1 + n_slots + n_evals words of 4 bytes, pairs = set_start[n_sets]).
+ * n_proofs == 0: ZKHIP_OK, nothing is written.  ZKHIP_EINVAL: a null plan or plan array; n_sets or n_points outside 1 .. 64; set_start not
+ * starting at 0, a set without a point, more than 256 (set, point) pairs in all; n_evals outside 1 .. 65527; n_slots outside 1 .. 65536; k > 28;
+ * omega null or not canonical; point_rotation[t] >= 2^k or repeated; set_point[j] >= n_points or repeated inside a set; slot_set[p] >= n_sets;
+ * slot_pos[p] >= 2^16; query_slot[q] >= n_slots; query_point[q] >= n_points or not in the set of its slot; a (slot, point) pair queried twice
+ * or not at all (n_evals is the sum over the slots of their sets' sizes); n_proofs > 2^24; with n_proofs > 0 a device pointer that is null or
+ * not 16-byte aligned.
+ * Not built: folding across different circuits or parameter sets, a batch sharded over devices. */
 struct zkhip_gwc_plan {
   uint32_t n_evals, n_sets, n_slots, reserved;
   const uint32_t *set_rotation;     /* [n_sets] */
@@ -977,6 +1008,19 @@ int zkhip_gwc_scalars_device(const zkhip_gwc_plan *plan, const void *d_evals, co
                              void *d_rows_a, void *d_rows_c, void *stream);
 int zkhip_fr_fold_rows_device(const void *d_rows, uint32_t n_cols, uint32_t n_own, const void *d_r, int negate, size_t n_rows, void *d_out_own,
                               void *d_out_shared, void *stream);
+struct zkhip_shplonk_plan {
+  uint32_t n_evals, n_sets, n_slots, n_points;
+  const uint32_t *point_rotation;   /* [n_points]  distinct, < 2^k */
+  const uint32_t *set_start;        /* [n_sets + 1] CSR over set_point */
+  const uint32_t *set_point;        /* [set_start[n_sets]] indices into point_rotation; distinct inside a set */
+  const uint32_t *slot_set;         /* [n_slots] */
+  const uint32_t *slot_pos;         /* [n_slots]  < 2^16 */
+  const uint32_t *query_slot;       /* [n_evals] */
+  const uint32_t *query_point;      /* [n_evals]  index into point_rotation */
+};
+typedef struct zkhip_shplonk_plan zkhip_shplonk_plan;
+int zkhip_shplonk_scalars_device(const zkhip_shplonk_plan *plan, const void *d_evals, const void *d_points, uint32_t k, const uint64_t omega[4], size_t n_proofs,
+                                 void *d_rows_a, void *d_rows_c, void *d_status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1460,6 +1460,41 @@ inline void gwc_scalars_device(const GwcPlan& plan, const DeviceVec& evals, cons
   p.query_slot = plan.query_slot.data();
   check(zkhip_gwc_scalars_device(&p, evals.data(), points.data(), k, omega.l, n_proofs, rows_a.data(), rows_c.data(), nullptr), "gwc_scalars_device");
 }
+// A key's opening plan as the SHPLONK verifier groups it: the distinct rotations (the super points), the rotation sets as a CSR list over them,
+// per polynomial slot its set and its position inside it, per query (evaluation q of a record) its slot and its super point
+struct ShplonkPlan {
+  std::vector<uint32_t> point_rotation, set_start, set_point, slot_set, slot_pos, query_slot, query_point;
+};
+// rows_a = [n_proofs][2 + n_slots + 1] over [H', H | slots | G], rows_c = [n_proofs][1]: the scalars of every proof's two accumulated points
+// (layout: zkhip.h).  -> the status of every proof: 1 where the proof has no such row (its rows are zeros: verify it one by one)
+inline std::vector<uint32_t> shplonk_scalars_device(const ShplonkPlan& plan, const DeviceVec& evals, const DeviceVec& points, uint32_t k, const Fr& omega, size_t n_proofs,
+                                                    DeviceVec& rows_a, DeviceVec& rows_c) {
+  const size_t n_evals = plan.query_slot.size(), n_slots = plan.slot_set.size();
+  if (plan.query_point.size() != n_evals || plan.slot_pos.size() != n_slots || plan.set_start.size() < 2 || plan.set_point.size() != plan.set_start.back())
+    throw std::invalid_argument("shplonk_scalars_device: the plan's arrays differ in length");
+  if (evals.size() < n_proofs * n_evals || points.size() < n_proofs * 4 || rows_a.size() < n_proofs * (n_slots + 3) || rows_c.size() < n_proofs)
+    throw std::invalid_argument("shplonk_scalars_device: arrays shorter than the batch");
+  zkhip_shplonk_plan p{};
+  p.n_evals = (uint32_t)n_evals;
+  p.n_sets = (uint32_t)plan.set_start.size() - 1;
+  p.n_slots = (uint32_t)n_slots;
+  p.n_points = (uint32_t)plan.point_rotation.size();
+  p.point_rotation = plan.point_rotation.data();
+  p.set_start = plan.set_start.data();
+  p.set_point = plan.set_point.data();
+  p.slot_set = plan.slot_set.data();
+  p.slot_pos = plan.slot_pos.data();
+  p.query_slot = plan.query_slot.data();
+  p.query_point = plan.query_point.data();
+  std::vector<uint32_t> status(n_proofs, 0);
+  if (n_proofs == 0) return status;
+  void* d_status = nullptr;
+  check(zkhip_alloc(n_proofs * sizeof(uint32_t) + 16, &d_status), "shplonk_scalars_device");
+  struct release { void* p; ~release() { (void)zkhip_free(p); } } held{d_status};
+  check(zkhip_shplonk_scalars_device(&p, evals.data(), points.data(), k, omega.l, n_proofs, rows_a.data(), rows_c.data(), d_status, nullptr), "shplonk_scalars_device");
+  check(zkhip_download(status.data(), d_status, n_proofs * sizeof(uint32_t)), "shplonk_scalars_device");
+  return status;
+}
 // out_own[i][j] = +- r[i] rows[i][j] for j < n_own; out_shared[j] = +- sum_i r[i] rows[i][n_own + j]
 inline void fold_rows_device(const DeviceVec& rows, uint32_t n_cols, uint32_t n_own, const DeviceVec& r, bool negate, size_t n_rows, DeviceVec& out_own,
                              DeviceVec& out_shared) {

@@ -1,0 +1,104 @@
+"""GPU (-m gpu): prover.verify_transcript_proofs(..., multiopen="shplonk", fold=True) with the SHPLONK rows made by zkhip_shplonk_scalars_device.
+On the small shape of tests/test_gpu_batch_verifier.py (k = 7, (3, 2), five proofs of one key): fold=True answers what fold=False answers on the
+honest batch (one pairing check), with two differing evaluations swapped in one proof's bytes, and with truncated proofs -- while
+multiopen.shplonk_accumulate, the host's accumulation, is patched to raise for as long as fold=True runs: the folded path does not call it.  A
+proof that the device call gives status 1 (forced here: a real u hits a point with probability about 2^-250) is handed to the one-by-one verifier
+and the rest of the batch is folded without it."""
+import pytest
+
+from test_gpu_batch_verifier import K, SEED, Batch, checks      # noqa: F401  (checks is a fixture)
+from zksnap_circuits_halo2_amd import multiopen as MO
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def batch():
+    b = Batch("shplonk", honest=5, broken=0)
+    yield b
+    b.close()
+
+
+def folded_without_the_host(batch, monkeypatch, proofs, **kw):
+    """fold=True with shplonk_accumulate raising; the patch is taken back before the caller runs fold=False, which needs the function"""
+    def refuse(*args, **kwargs):
+        raise AssertionError("fold=True called the host's shplonk_accumulate")
+
+    with monkeypatch.context() as m:
+        m.setattr(MO, "shplonk_accumulate", refuse)
+        return batch.verify(proofs, fold=True, fold_seed=SEED, **kw)
+
+
+def test_the_honest_batch_is_folded_on_the_device_with_one_pairing_check(batch, checks, monkeypatch):
+    honest = batch.proofs[:5]
+    assert len(set(honest)) == 5
+    assert folded_without_the_host(batch, monkeypatch, honest) == [True] * 5 and checks == [1]
+    assert batch.verify(honest) == [True] * 5 and checks == [1]                     # the one-by-one path makes none of these
+    assert folded_without_the_host(batch, monkeypatch, honest[:1]) == [True] and checks == [2]
+
+
+def test_swapped_evaluations_refuse_that_proof_alone(batch, checks, monkeypatch):
+    shape, plan = batch.shape, batch.plan
+    first = 32 * (shape["advice"] + 3 * shape["lookups"] + shape["permutation_sets"] + int(shape["random_poly"]) + 3)      # the evaluations follow the commitments
+    a, b = plan.index(("advice", 0, 1)), plan.index(("advice", 2, 2))
+    proof = batch.proofs[3]
+    ea, eb = proof[first + 32 * a:first + 32 * a + 32], proof[first + 32 * b:first + 32 * b + 32]
+    assert ea != eb
+    swapped = bytearray(proof)
+    swapped[first + 32 * a:first + 32 * a + 32], swapped[first + 32 * b:first + 32 * b + 32] = eb, ea
+    proofs = batch.proofs[:3] + [bytes(swapped)] + [batch.proofs[4]]
+    want = [True, True, True, False, True]
+    assert folded_without_the_host(batch, monkeypatch, proofs, identity=False) == want and 2 <= checks[0] <= 1 + 2 * 3
+    assert batch.verify(proofs, identity=False) == want
+
+
+def test_truncated_proofs_are_refused_alone(batch, checks, monkeypatch):
+    cut = list(batch.proofs[:5])
+    cut[2] = cut[2][:-40]                                                          # the multi-open's last point is incomplete
+    cut[4] = cut[4][:200]                                                          # ... and this one ends among its commitments
+    want = [True, True, False, True, False]
+    assert folded_without_the_host(batch, monkeypatch, cut) == want and checks == [1]
+    assert batch.verify(cut) == want
+
+
+def swapped_proof(batch, index):
+    """proof `index` with two differing evaluations swapped: it decodes, and its openings fail"""
+    shape, plan = batch.shape, batch.plan
+    first = 32 * (shape["advice"] + 3 * shape["lookups"] + shape["permutation_sets"] + int(shape["random_poly"]) + 3)
+    a, b = plan.index(("advice", 0, 1)), plan.index(("advice", 2, 2))
+    swapped = bytearray(batch.proofs[index])
+    swapped[first + 32 * a:first + 32 * a + 32], swapped[first + 32 * b:first + 32 * b + 32] = swapped[first + 32 * b:first + 32 * b + 32], swapped[first + 32 * a:first + 32 * a + 32]
+    assert bytes(swapped) != batch.proofs[index]
+    return bytes(swapped)
+
+
+@pytest.mark.parametrize("refused, bad", [((2,), None), ((0, 1, 2, 3, 4), None), ((3,), 3), ((1,), 3)], ids=["one", "all", "one-and-it-is-wrong", "one-beside-a-wrong-one"])
+def test_a_proof_with_status_one_is_verified_one_by_one(batch, checks, monkeypatch, refused, bad):
+    real, accumulate, host_calls = MO.shplonk_scalars_device, MO.shplonk_accumulate, [0]
+
+    def forced(*args, **kw):
+        rows_a, rows_c, status = real(*args, **kw)
+        for j in refused:                                                          # what the kernel leaves for such a proof: status 1, zero rows
+            status[j] = 1
+            rows_a[j].zero_()
+            rows_c[j].zero_()
+        return rows_a, rows_c, status
+
+    def counted(*args, **kw):
+        host_calls[0] += 1
+        return accumulate(*args, **kw)
+
+    proofs = list(batch.proofs[:5])
+    if bad is not None:
+        proofs[bad] = swapped_proof(batch, bad)
+    with monkeypatch.context() as m:
+        m.setattr(MO, "shplonk_scalars_device", forced)
+        m.setattr(MO, "shplonk_accumulate", counted)
+        got = batch.verify(proofs, fold=True, fold_seed=SEED, identity=False)
+    assert got == [i != bad for i in range(5)] and host_calls == [len(refused)]
+    if len(refused) == 5:
+        assert checks == [0]                                                       # nothing was left to fold
+    elif bad is None or bad in refused:
+        assert checks == [1]                                                       # the four others pass one folded check
+    else:
+        assert 2 <= checks[0] <= 1 + 2 * 2                                         # four proofs folded, one of them wrong: bisected

@@ -21,7 +21,8 @@ timed region ends with the verdict on the host.
   the batch verifier: verify_transcript_proofs one by one against fold=True (one folded pairing check per batch, multiopen.fold_check) in this one
       process, the two sides alternating, for B in {1, 4, 16, 64} proofs and both multi-opens on the same shapes; the batch is ONE proof's bytes
       repeated B times (an honest input for timing: every copy is read, checked and folded like any other proof; the output says so); and the two
-      calls behind it alone, zkhip_gwc_scalars_device and zkhip_fr_fold_rows_device, at B = 1, 64 and 4096 on random records
+      calls behind it alone, zkhip_gwc_scalars_device, zkhip_fr_fold_rows_device and zkhip_shplonk_scalars_device, at B = 1, 64 and 4096 on
+      random records
     python tools/verify_time.py [--reps 9] [--shapes 22:4:1,13:256:8,15:64:8] [--no-pairing] [--no-flow] [--no-srs] [--no-identity] [--no-instances] [--no-batch]"""
 import argparse
 import os
@@ -328,3 +329,14 @@ if not args.no_batch:
             print(f"    B = {B:5d}  zkhip_gwc_scalars_device (plan marshalled in the call)   {fmt(timed(scalars))}")
             print(f"    B = {B:5d}  zkhip_fr_fold_rows_device                                {fmt(timed(fold))}")
             del evals, points, r, rows_a, out_own, out_shared
+        sp = MO.shplonk_plan(plan)
+        print(f"==== the SHPLONK scalars alone, same shape: {sp.n_evals} queries, {sp.n_points} points, {sp.n_sets} rotation sets "
+              f"({sum(len(pts) for pts in sp.set_points)} pairs), {sp.n_slots} polynomials ({sp.n_slots + 3} columns) ====")
+        for B in (int(b) for b in args.batches.split(",")):
+            evals, points = random_elements(B, sp.n_evals), random_elements(B, 4)
+            def shplonk_scalars():
+                MO.shplonk_scalars_device(sp, evals, points, k)
+                torch.cuda.synchronize()
+            assert not bool(MO.shplonk_scalars_device(sp, evals, points, k)[2].any())
+            print(f"    B = {B:5d}  zkhip_shplonk_scalars_device (plan marshalled in the call) {fmt(timed(shplonk_scalars))}")
+            del evals, points

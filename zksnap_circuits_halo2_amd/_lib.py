@@ -186,6 +186,7 @@ _SIGS = {
                                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_gwc_scalars_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_fr_fold_rows_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zkhip_shplonk_scalars_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zkhip_test_reduce512": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zkhip_test_transcript_chunk": (C.c_uint32, [C.c_size_t]),
     "zkhip_profile_enable": (C.c_int, [C.c_int]),
@@ -213,6 +214,13 @@ class GwcPlan(C.Structure):         # struct zkhip_gwc_plan (48 bytes): passed b
     _fields_ = [("n_evals", C.c_uint32), ("n_sets", C.c_uint32), ("n_slots", C.c_uint32), ("reserved", C.c_uint32),
                 ("set_rotation", C.POINTER(C.c_uint32)), ("query_set", C.POINTER(C.c_uint32)), ("query_pos", C.POINTER(C.c_uint32)),
                 ("query_slot", C.POINTER(C.c_uint32))]
+
+
+class ShplonkPlan(C.Structure):     # struct zkhip_shplonk_plan (72 bytes): passed by address, as GwcPlan is
+    _fields_ = [("n_evals", C.c_uint32), ("n_sets", C.c_uint32), ("n_slots", C.c_uint32), ("n_points", C.c_uint32),
+                ("point_rotation", C.POINTER(C.c_uint32)), ("set_start", C.POINTER(C.c_uint32)), ("set_point", C.POINTER(C.c_uint32)),
+                ("slot_set", C.POINTER(C.c_uint32)), ("slot_pos", C.POINTER(C.c_uint32)), ("query_slot", C.POINTER(C.c_uint32)),
+                ("query_point", C.POINTER(C.c_uint32))]
 
 
 class CheckReport(C.Structure):     # zkhip_check_report (16 bytes)

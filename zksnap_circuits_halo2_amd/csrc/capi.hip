@@ -2049,6 +2049,27 @@ int zkhip_fr_fold_rows_device(const void* d_rows, uint32_t n_cols, uint32_t n_ow
                           sc->ws.cap, s);
 }
 
+int zkhip_shplonk_scalars_device(const zkhip_shplonk_plan* plan, const void* d_evals, const void* d_points, uint32_t k, const uint64_t omega[4], size_t n_proofs,
+                                 void* d_rows_a, void* d_rows_c, void* d_status, void* stream) {
+  ZK_API_RANGE();
+  std::vector<uint32_t> blob;
+  int rc = shplonk_plan_marshal(plan, k, omega, &blob);
+  if (rc != ZKHIP_OK) return rc;
+  if (n_proofs > ((size_t)1 << 24)) { set_error("shplonk_scalars: %zu proofs in one call", n_proofs); return ZKHIP_EINVAL; }
+  if (n_proofs == 0) return ZKHIP_OK;                                // nothing to write
+  if (!elems_ptr_ok(d_evals) || !elems_ptr_ok(d_points) || !elems_ptr_ok(d_rows_a) || !elems_ptr_ok(d_rows_c) || !elems_ptr_ok(d_status)) {
+    set_error("shplonk_scalars: null or misaligned pointer");
+    return ZKHIP_EINVAL;
+  }
+  guard_t g(g_mu);
+  if ((rc = ensure_init()) != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->ws.reserve(blob.size() * 4)) != ZKHIP_OK) return rc;
+  return shplonk_scalars_device(blob, (const uint32_t*)d_evals, (const uint32_t*)d_points, n_proofs, (uint32_t*)d_rows_a, (uint32_t*)d_rows_c, (uint32_t*)d_status, sc->ws.p,
+                                sc->ws.cap, s, &sc->args);
+}
+
 int zkhip_lookup_permute(const uint64_t* input, const uint64_t* table, size_t usable_rows, uint64_t* permuted_input, uint64_t* permuted_table) {
   ZK_API_RANGE();
   if (usable_rows && (!input || !table || !permuted_input || !permuted_table)) { set_error("lookup_permute: null pointer"); return ZKHIP_EINVAL; }

@@ -22,39 +22,7 @@
 
 namespace zkhip {
 
-__device__ __forceinline__ fe gf_load5(const uint32_t* p) {
-  uint32_t w[8];
-  load_words(p, w);
-  return fe_from_ext_lazy(w);
-}
-
-__device__ __forceinline__ fe gf_load0(const uint32_t* p) {
-  uint32_t w[8];
-  load_words(p, w);
-  return fe_unpack<0>(w);
-}
-
-__device__ __forceinline__ void gf_store_ext(uint32_t* p, const fe& internal) {
-  uint32_t w[8];
-  fe_to_ext<Fr>(internal, w);
-  store_words(p, w);
-}
-
-__device__ __forceinline__ void gf_store_packed(uint32_t* p, const fe& canonical) {
-  uint32_t w[8];
-  fe_pack(canonical, w);
-  store_words(p, w);
-}
-
-// the pairwise joins of a workgroup's T canonical values (T a power of two); the sum is left in part[0]
-__device__ __forceinline__ void gf_join_block(fe* part, uint32_t t, uint32_t T) {
-  __syncthreads();
-  for (uint32_t d = T >> 1; d; d >>= 1) {
-    if (t < d) part[t] = gf_join<Fr>(part[t], part[t + d]);
-    __syncthreads();
-  }
-}
-
+// (the element loads and stores and gf_join_block, the join through LDS, are gwc_fold.hpp's: shplonk_fold.hip uses the same)
 // plan: the words gwc_scalars_device uploads -- omega^rot per set (8 words each) | a word per query | slot_start [n_slots + 1] | slot_query [n_evals].
 // One pointer for the four tables: the kernel sits at the SGPR limit, and every argument kept for its whole length is a spilled scalar elsewhere.
 __global__ void __launch_bounds__(GWC_THREADS) k_gwc_scalars(const uint32_t* __restrict__ evals, const uint32_t* __restrict__ points, const uint32_t* __restrict__ plan,

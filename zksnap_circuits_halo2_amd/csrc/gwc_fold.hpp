@@ -141,4 +141,40 @@ ZK_HD fe gf_join_lane(uint32_t count, uint32_t t, uint32_t T, A&& partial) {
   return acc;
 }
 
+#if defined(__HIPCC__)
+// ---- what the kernels of gwc_fold.hip and shplonk_fold.hip share on the device: element loads and stores, and the join through LDS ----
+ZK_D fe gf_load5(const uint32_t* p) {
+  uint32_t w[8];
+  load_words(p, w);
+  return fe_from_ext_lazy(w);
+}
+
+ZK_D fe gf_load0(const uint32_t* p) {
+  uint32_t w[8];
+  load_words(p, w);
+  return fe_unpack<0>(w);
+}
+
+ZK_D void gf_store_ext(uint32_t* p, const fe& internal) {
+  uint32_t w[8];
+  fe_to_ext<FrParams>(internal, w);
+  store_words(p, w);
+}
+
+ZK_D void gf_store_packed(uint32_t* p, const fe& canonical) {
+  uint32_t w[8];
+  fe_pack(canonical, w);
+  store_words(p, w);
+}
+
+// the pairwise joins of a workgroup's T canonical values (T a power of two); the sum is left in part[0]
+ZK_D void gf_join_block(fe* part, uint32_t t, uint32_t T) {
+  __syncthreads();
+  for (uint32_t d = T >> 1; d; d >>= 1) {
+    if (t < d) part[t] = gf_join<FrParams>(part[t], part[t + d]);
+    __syncthreads();
+  }
+}
+#endif
+
 }  // namespace zkhip

@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 #include "../../include/zkhip.h"
 #include "scan_plan.hpp"      // defines the *_workspace_bytes of the chunked scans declared below (inline, host-only)
 #include "rowvm_blob.hpp"     // the row programs' blob: its plan and row_vm_workspace_bytes (inline, host-only)
@@ -343,6 +344,12 @@ int gwc_scalars_device(const zkhip_gwc_plan* plan, const uint32_t* d_evals, cons
 size_t fold_rows_workspace_bytes(uint32_t n_cols, uint32_t n_own, uint64_t n_rows);
 int fold_rows_device(const uint32_t* d_rows, uint32_t n_cols, uint32_t n_own, const uint32_t* d_r, uint32_t negate, uint64_t n_rows, uint32_t* d_out_own,
                      uint32_t* d_out_shared, void* ws, size_t ws_bytes, hipStream_t stream);
+
+// shplonk_fold.hip (include/zkhip.h, "the batch verifier").  The marshaller validates the plan and builds the words the kernel reads, touching no
+// device; `ws` holds those words.
+int shplonk_plan_marshal(const zkhip_shplonk_plan* plan, uint32_t k, const uint64_t* omega, std::vector<uint32_t>* blob);
+int shplonk_scalars_device(const std::vector<uint32_t>& blob, const uint32_t* d_evals, const uint32_t* d_points, uint64_t n_proofs, uint32_t* d_rows_a,
+                           uint32_t* d_rows_c, uint32_t* d_status, void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
 
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);

@@ -610,6 +610,110 @@ def gwc_scalars_device(plan: GwcPlan, evals, points, k: int, stream=None):
     return rows_a, rows_c
 
 
+@dataclass
+class ShplonkPlan:
+    """An opening plan as the SHPLONK verifier groups it (include/zkhip.h, zkhip_shplonk_plan): query q is triple q of the plan.
+    `point_rotation`: the distinct rotations as the plan spells them, in order of first appearance -- the super point set; `set_points`: per
+    rotation set the indices of its rotations -- `construct_rotation_sets` grouped by rotation, which is what grouping by point gives for every
+    x but 0: polynomials with the same set of rotations share a set, sets and the polynomials inside one in order of first appearance;
+    `slot_set`, `slot_pos`: a polynomial's set and its position inside it (the exponent of y), the slots ordered as GwcPlan orders them
+    (`own_keys` first, `shared_keys` behind them); `query_slot`, `query_point`: a query's polynomial and the index of its rotation.
+    `repeated`, `foldable`: GwcPlan's rule."""
+    n_evals: int
+    point_rotation: List[int]
+    set_points: List[List[int]]
+    slot_set: List[int]
+    slot_pos: List[int]
+    query_slot: List[int]
+    query_point: List[int]
+    own_keys: List[tuple]
+    shared_keys: List[tuple]
+    repeated: bool
+
+    @property
+    def n_sets(self) -> int:
+        return len(self.set_points)
+
+    @property
+    def n_slots(self) -> int:
+        return len(self.own_keys) + len(self.shared_keys)
+
+    @property
+    def n_points(self) -> int:
+        return len(self.point_rotation)
+
+    def foldable(self, k: int) -> bool:
+        """may the batch verifier group this plan by rotation at 2^k rows?  Not with a repeated triple, and not with two rotations equal mod 2^k
+        (they are one point): such plans are verified one by one, which groups by point"""
+        return not self.repeated and len({r % (1 << k) for r in self.point_rotation}) == len(self.point_rotation)
+
+    def marshal(self, k: int):
+        """-> (_lib.ShplonkPlan, the arrays it points into): rotations reduced mod 2^k.  ValueError: two rotations of the plan are equal mod 2^k
+        (they would be one point)"""
+        rot = [r % (1 << k) for r in self.point_rotation]
+        if len(set(rot)) != len(rot):
+            raise ValueError("shplonk_plan: two rotations of the plan are equal mod 2^k")
+        starts = [0]
+        for pts in self.set_points:
+            starts.append(starts[-1] + len(pts))
+        flat = [t for pts in self.set_points for t in pts]
+        arrays = [np.array(a, dtype=np.uint32) for a in (rot, starts, flat, self.slot_set, self.slot_pos, self.query_slot, self.query_point)]
+        ptr = [a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in arrays]
+        return _lib.ShplonkPlan(self.n_evals, self.n_sets, self.n_slots, self.n_points, *ptr), arrays
+
+
+def shplonk_plan(plan_triples, shared_kinds=("fixed", "sigma")) -> ShplonkPlan:
+    """the ShplonkPlan of the opened (kind, index, rotation) triples (prover.opening_plan); own and shared keys and the slots' order are gwc_plan's"""
+    rotations, by_poly, keys, q_point = [], {}, [], []
+    for kind, idx, rot in plan_triples:
+        if rot not in rotations:
+            rotations.append(rot)
+        t = rotations.index(rot)
+        pts = by_poly.setdefault((kind, idx), [])        # a polynomial's rotations, polynomials in order of first appearance
+        if t not in pts:
+            pts.append(t)
+        keys.append((kind, idx))
+        q_point.append(t)
+    set_index, set_points, counts, set_of, pos_of = {}, [], [], {}, {}
+    for key, pts in by_poly.items():
+        i = set_index.setdefault(frozenset(pts), len(set_points))
+        if i == len(set_points):
+            set_points.append(list(pts))
+            counts.append(0)
+        set_of[key], pos_of[key] = i, counts[i]
+        counts[i] += 1
+    own = list(dict.fromkeys(key for key in keys if key[0] not in shared_kinds))
+    shared = list(dict.fromkeys(key for key in keys if key[0] in shared_kinds))
+    slots = {key: s for s, key in enumerate(own + shared)}
+    triples = [tuple(t) for t in plan_triples]
+    return ShplonkPlan(len(triples), rotations, set_points, [set_of[key] for key in own + shared], [pos_of[key] for key in own + shared], [slots[key] for key in keys],
+                       q_point, own, shared, len(set(triples)) != len(triples))
+
+
+def shplonk_scalars_device(plan: ShplonkPlan, evals, points, k: int, stream=None):
+    """zkhip_shplonk_scalars_device: evals (B, n_evals, 4), points (B, 4, 4) = x, y, v, u, contiguous int64 device tensors -> (rows_a (B, 2 +
+    n_slots + 1, 4) over [H', H | own polynomials | key polynomials | G], rows_c (B, 1, 4), status (B,) int32), the column layout of
+    include/zkhip.h: what `shplonk_accumulate` returns for each proof.  status[i] = 1: x Z_0 = 0 for proof i, its rows are zeros and the caller
+    verifies it one by one.  Asynchronous on `stream`."""
+    import torch
+
+    from .fields import omega_for
+
+    B = evals.shape[0]
+    if not (evals.is_cuda and evals.is_contiguous() and points.is_cuda and points.is_contiguous()) or tuple(evals.shape) != (B, plan.n_evals, 4) or \
+            tuple(points.shape) != (B, 4, 4):
+        raise ValueError("shplonk_scalars_device: contiguous device tensors, (B, n_evals, 4) and (B, 4, 4)")
+    struct, keep = plan.marshal(k)
+    rows_a = torch.empty((B, 2 + plan.n_slots + 1, 4), dtype=torch.int64, device=evals.device)
+    rows_c = torch.empty((B, 1, 4), dtype=torch.int64, device=evals.device)
+    status = torch.empty((B,), dtype=torch.int32, device=evals.device)
+    omega = fr_encode([omega_for(k)])[0]
+    _lib.check(_lib.load().zkhip_shplonk_scalars_device(C.byref(struct), evals.data_ptr(), points.data_ptr(), k, omega.ctypes.data, B, rows_a.data_ptr(),
+                                                        rows_c.data_ptr(), status.data_ptr(), stream))
+    del keep
+    return rows_a, rows_c, status
+
+
 def fold_rows_device(rows, n_own: int, r, negate: bool, out_own, out_shared, stream=None) -> None:
     """zkhip_fr_fold_rows_device over rows (n, n_cols, 4) and multipliers r (n, 4): out_own (n * n_own elements) = +- r_i rows[i][j],
     out_shared (n_cols - n_own elements) = +- sum_i r_i rows[i][n_own + j]; either output may be None where it has no element"""

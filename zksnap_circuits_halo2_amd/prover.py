@@ -302,6 +302,15 @@ def gwc_plan_of(vk, plan):
     return cache[key]
 
 
+def shplonk_plan_of(vk, plan):
+    """multiopen.shplonk_plan of `plan`, kept on the key object as gwc_plan_of keeps its plan"""
+    cache = vk.__dict__.setdefault("_shplonk_plans", {})
+    key = tuple(plan)
+    if key not in cache:
+        cache[key] = MO.shplonk_plan(plan)
+    return cache[key]
+
+
 def _host_xyz(point):
     """an (8,) affine device tensor -> Jacobian limbs with z = 1 on the host"""
     return MO._affine_to_xyz(point.cpu().numpy().view(np.uint64))
@@ -311,13 +320,14 @@ def _fold_openings(params, vk, k, plan, multiopen, heads, order, d_evals, rows_o
     """The openings of the proofs `order` (their heads read with on_device=True, the readers in front of the multi-open's part) decided by
     multiopen.fold_check.  d_evals: the uploaded evaluations, rows_of[i] the row of proof i in them.  A proof whose multi-open part does not
     decode is refused alone; a proof with x = 0 mod r (where the grouping by rotation and halo2's grouping by point differ) is verified on its
-    own by the multi-open's verifier."""
+    own by the multi-open's verifier, and so is a SHPLONK proof that zkhip_shplonk_scalars_device gives status 1.  Both multi-opens make the
+    rows of the folded proofs on the device: the host's `gwc_accumulate` and `shplonk_accumulate` run only inside the one-by-one verifier."""
     gp = gwc_plan_of(vk, plan)
     key_points = {("fixed", i): c for i, c in enumerate(vk.fixed_commitments)}
     key_points.update({("sigma", i): c for i, c in enumerate(vk.permutation_commitments)})
     shared = np.stack([np.asarray(key_points[key_], dtype=np.uint64).reshape(8) for key_ in gp.shared_keys] + [np.asarray(params.g[0], dtype=np.uint64).reshape(8)])
     d_shared = torch.from_numpy(shared.view(np.int64)).to(DEV)
-    folded, own, points, rows_a, rows_c = [], [], [], [], []
+    folded, own, points = [], [], []
     for i in order:
         r, com, challenges, evals = heads[i]
         x = challenges[4]
@@ -338,16 +348,7 @@ def _fold_openings(params, vk, k, plan, multiopen, heads, order, d_evals, rows_o
                 u = r.squeeze_challenge()
                 Hp = r.read_points(1)
                 mine = torch.cat([Hp, H])
-                # the host's accumulation groups by (kind, index) and reads no commitment: one placeholder stands for all of them
-                nothing = np.zeros(12, dtype=np.uint64)
-                queries = verifier_queries(plan, {key_: nothing for key_ in gp.own_keys + gp.shared_keys}, evals, x, k)
-                scalars, keys = MO.shplonk_accumulate(queries, y, v, u)
-                by_key = {}
-                for key_, s_ in zip(keys, scalars):
-                    by_key[key_] = (by_key.get(key_, 0) + s_) % R
-                g_scalar, h_scalar, hp_scalar = scalars[len(keys):]
-                rows_a.append([hp_scalar, h_scalar] + [by_key[key_] for key_ in gp.own_keys] + [by_key[key_] for key_ in gp.shared_keys] + [g_scalar])
-                rows_c.append([1])
+                points.append((x, y, v, u))
         except _lib.ZkhipError as e:                       # the multi-open's own points do not decode
             if e.code != -1:
                 raise
@@ -357,13 +358,26 @@ def _fold_openings(params, vk, k, plan, multiopen, heads, order, d_evals, rows_o
     if not folded:
         return
     d_own = torch.stack(own).contiguous()
+    index = torch.tensor([rows_of[i] for i in folded], dtype=torch.int64, device=DEV)
+    d_points = words([c_ for row in points for c_ in row]).reshape(len(folded), len(points[0]), 4)
     if multiopen == "gwc":
-        index = torch.tensor([rows_of[i] for i in folded], dtype=torch.int64, device=DEV)
-        d_points = words([c_ for row in points for c_ in row]).reshape(len(folded), 3, 4)
         d_rows_a, d_rows_c = MO.gwc_scalars_device(gp, d_evals.index_select(0, index).contiguous(), d_points, k)
     else:
-        d_rows_a = words([s_ for row in rows_a for s_ in row]).reshape(len(folded), len(rows_a[0]), 4)
-        d_rows_c = words([s_ for row in rows_c for s_ in row]).reshape(len(folded), 1, 4)
+        d_rows_a, d_rows_c, d_status = MO.shplonk_scalars_device(shplonk_plan_of(vk, plan), d_evals.index_select(0, index).contiguous(), d_points, k)
+        refused = [j for j, s_ in enumerate(d_status.cpu().tolist()) if s_ != 0]
+        if refused:                                        # u on a point outside set 0: the row does not exist, the one-by-one verifier decides
+            for j in refused:
+                i = folded[j]
+                host = {key_: _host_xyz(c_) for key_, c_ in heads[i][1].items()}
+                host.update(_key_commitments(vk))
+                verdicts[i] = bool(MO.VerifierSHPLONK(params).verify_proof(verifier_queries(plan, host, heads[i][3], points[j][0], k), _host_xyz(d_own[j][1]),
+                                                                            _host_xyz(d_own[j][0]), *points[j][1:]))
+            kept = [j for j in range(len(folded)) if j not in refused]
+            if not kept:
+                return
+            keep = torch.tensor(kept, dtype=torch.int64, device=DEV)
+            folded = [folded[j] for j in kept]
+            d_own, d_rows_a, d_rows_c = (t_.index_select(0, keep).contiguous() for t_ in (d_own, d_rows_a, d_rows_c))
     for i, ok in zip(folded, MO.fold_check(params, d_rows_a, d_rows_c, d_own, d_shared, fold_seed)):
         verdicts[i] = bool(ok)
 
@@ -388,12 +402,14 @@ def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b",
     circuit has instance columns and no `instances`; lengths that differ between the proofs or exceed the usable rows.
     fold=True: the openings of the proofs that passed the identity are decided together by multiopen.fold_check (halo2's `BatchVerifier`): the
     commitments stay in HBM, every proof's two accumulated points are rows of scalars -- multiopen="gwc": made by zkhip_gwc_scalars_device from
-    the evaluations the identity call read; "shplonk": by `shplonk_accumulate` on the host, as [H', H, own polynomials | key polynomials, G] --,
+    the evaluations the identity call read; "shplonk": by zkhip_shplonk_scalars_device from the same records, as [H', H, own polynomials | key
+    polynomials, G], one inversion per proof; a proof whose u hits a point outside the first rotation set has no such row (status 1) and is
+    verified one by one --,
     and ONE pairing check accepts the batch; a batch that fails is bisected.  The verdicts are those of fold=False (a wrong proof passes a
     folded check with probability about 1 / r).  A proof with x = 0 mod r, a plan that repeats a triple and a plan with two rotations equal mod 2^k take the one-by-one path.
     fold_seed: the 32 bytes the random multipliers are drawn from; None (what a verifier uses) draws them from os.urandom, a fixed seed is for
     tests.
-    Not built: committed instance columns, multi-phase challenges; the SHPLONK scalars on the device, folding across
+    Not built: committed instance columns, multi-phase challenges; folding across
     different circuits or parameter sets, a batch sharded over devices.  Returns a list of bools."""
     import contextlib
 

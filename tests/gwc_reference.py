@@ -1,9 +1,9 @@
 """The batch verifier's scalar rows on Python integers (a helper module: no tests, no fixtures).  The GWC rows are `multiopen.gwc_accumulate` over
-`prover.verifier_queries`, that function's per-query scalars summed per polynomial and laid out as include/zkhip.h lays out a row; a fold is the
+`verifier.verifier_queries`, that function's per-query scalars summed per polynomial and laid out as include/zkhip.h lays out a row; a fold is the
 plain sum.  tests/test_gwc_fold_host.py and the GPU tests of the two calls share it."""
 import numpy as np
 
-from zksnap_circuits_halo2_amd import evaluation as E, fields as F, multiopen as MO, prover as P
+from zksnap_circuits_halo2_amd import evaluation as E, fields as F, multiopen as MO, prover as P, verifier as V
 
 R = F.R_MOD
 SHAPES = [(1, 1, 7), (3, 2, 7), (256, 8, 13)]                 # (gate columns, lookups, k); the last is the voter's shape
@@ -16,7 +16,7 @@ def plan_for(gate_cols, lookups, k, order="halo2", random_poly=False):
 
 
 def queries_of(triples, evals, x, k):
-    return P.verifier_queries(triples, {(kind, idx): _NOTHING for kind, idx, _ in triples}, evals, x, k)
+    return V.verifier_queries(triples, {(kind, idx): _NOTHING for kind, idx, _ in triples}, evals, x, k)
 
 
 def gwc_rows(triples, gp, k, evals, x, v, u):

@@ -1,6 +1,6 @@
 """The batch verifier's SHPLONK rows on Python integers (a helper module: no tests, no fixtures).  A row is `multiopen.shplonk_accumulate` over
-`prover.verifier_queries`, laid out as include/zkhip.h lays out a row of zkhip_shplonk_scalars_device: [H', H | own polynomials | key polynomials
-| G] -- what prover._fold_openings built on the host before that call existed.  The reference is the host function, never the code under test.
+`verifier.verifier_queries`, laid out as include/zkhip.h lays out a row of zkhip_shplonk_scalars_device: [H', H | own polynomials | key polynomials
+| G] -- what verifier._fold_openings built on the host before that call existed.  The reference is the host function, never the code under test.
 tests/test_shplonk_fold_host.py and the GPU tests of the call share it."""
 import gwc_reference as GR
 from zksnap_circuits_halo2_amd import fields as F, multiopen as MO

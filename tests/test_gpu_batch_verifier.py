@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the batch verifier -- multiopen.fold_check and prover.verify_transcript_proofs(..., fold=True).
+"""GPU (-m gpu): the batch verifier -- multiopen.fold_check and verifier.verify_transcript_proofs(..., fold=True).
 
   (a) synthetic accumulators with a known trapdoor (ParamsKZG.setup(k, s), points from zkhip_g1_fixed_base_mul_device): with W = w G, Q = q G and
       A = a W + b Q + c G the openings accept exactly when a w + b q + c = s w.  16 valid proofs accept with exactly one pairing check; one bad
@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import zksnap_circuits_halo2_amd as Z
-from zksnap_circuits_halo2_amd import _lib, fields as F, keygen as KG, multiopen as MO, prover as P, tensors as T
+from zksnap_circuits_halo2_amd import _lib, fields as F, keygen as KG, multiopen as MO, prover as P, verifier as V, tensors as T
 from zksnap_circuits_halo2_amd.arithmetic import pairing_check
 
 pytestmark = pytest.mark.gpu
@@ -142,7 +142,7 @@ class Batch:
     def verify(self, proofs, public=None, **kw):
         if self.instances:
             kw["instances"] = self.public[:len(proofs)] if public is None else public
-        return P.verify_transcript_proofs(self.params, self.dpk.vk, K, proofs, self.shape, self.plan, self.hash, self.multiopen, **kw)
+        return V.verify_transcript_proofs(self.params, self.dpk.vk, K, proofs, self.shape, self.plan, self.hash, self.multiopen, **kw)
 
     def close(self):
         self.dpk.free()
@@ -162,7 +162,7 @@ def test_fold_equals_one_by_one_on_the_honest_batch_with_one_pairing_check(batch
     assert batch.verify(honest, fold=True, fold_seed=SEED) == [True] * 5 and checks == [1]
     assert batch.verify(honest) == [True] * 5 and checks == [1]                     # the one-by-one path makes none of these
     assert batch.verify(honest, fold=True) == [True] * 5 and checks == [2]          # multipliers from os.urandom
-    assert P.verify_transcript_proof(batch.params, batch.dpk.vk, K, honest[0], batch.shape, batch.plan, batch.hash, batch.multiopen, fold=True) is True
+    assert V.verify_transcript_proof(batch.params, batch.dpk.vk, K, honest[0], batch.shape, batch.plan, batch.hash, batch.multiopen, fold=True) is True
 
 
 def test_the_identity_refuses_the_broken_witnesses_in_both_modes(batch, checks):

@@ -1,13 +1,16 @@
-"""GPU (-m gpu): prover.verify_transcript_proofs(..., multiopen="shplonk", fold=True) with the SHPLONK rows made by zkhip_shplonk_scalars_device.
+"""GPU (-m gpu): verifier.verify_transcript_proofs(..., multiopen="shplonk", fold=True) with the SHPLONK rows made by zkhip_shplonk_scalars_device.
 On the small shape of tests/test_gpu_batch_verifier.py (k = 7, (3, 2), five proofs of one key): fold=True answers what fold=False answers on the
 honest batch (one pairing check), with two differing evaluations swapped in one proof's bytes, and with truncated proofs -- while
 multiopen.shplonk_accumulate, the host's accumulation, is patched to raise for as long as fold=True runs: the folded path does not call it.  A
 proof that the device call gives status 1 (forced here: a real u hits a point with probability about 2^-250) is handed to the one-by-one verifier
-and the rest of the batch is folded without it."""
+and the rest of the batch is folded without it.  A fold builds the plan of its own multi-open and not the other's (both plan functions patched to
+raise in turn, on a key object that nothing has been kept on yet)."""
+import dataclasses
+
 import pytest
 
 from test_gpu_batch_verifier import K, SEED, Batch, checks      # noqa: F401  (checks is a fixture)
-from zksnap_circuits_halo2_amd import multiopen as MO
+from zksnap_circuits_halo2_amd import multiopen as MO, verifier as V
 
 pytestmark = pytest.mark.gpu
 
@@ -102,3 +105,23 @@ def test_a_proof_with_status_one_is_verified_one_by_one(batch, checks, monkeypat
         assert checks == [1]                                                       # the four others pass one folded check
     else:
         assert 2 <= checks[0] <= 1 + 2 * 2                                         # four proofs folded, one of them wrong: bisected
+
+
+@pytest.fixture(scope="module")
+def gwc_batch():
+    b = Batch("gwc", honest=5, broken=0)
+    yield b
+    b.close()
+
+
+@pytest.mark.parametrize("scheme, others_plan", [("shplonk", "gwc_plan"), ("gwc", "shplonk_plan")])
+def test_a_fold_builds_only_its_own_schemes_plan(request, checks, monkeypatch, scheme, others_plan):
+    b = request.getfixturevalue("batch" if scheme == "shplonk" else "gwc_batch")
+
+    def refuse(*args, **kwargs):
+        raise AssertionError(f"a {scheme} fold called multiopen.{others_plan}")
+
+    monkeypatch.setattr(MO, others_plan, refuse)
+    vk = dataclasses.replace(b.dpk.vk)                                             # the key as a verifier first meets it: nothing is kept on it yet
+    got = V.verify_transcript_proofs(b.params, vk, K, b.proofs[:5], b.shape, b.plan, b.hash, scheme, fold=True, fold_seed=SEED)
+    assert got == [True] * 5 and checks == [1]

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): zkhip_gwc_scalars_device against `multiopen.gwc_accumulate` over `prover.verifier_queries`, that function's per-query scalars
+"""GPU (-m gpu): zkhip_gwc_scalars_device against `multiopen.gwc_accumulate` over `verifier.verifier_queries`, that function's per-query scalars
 summed per polynomial (tests/gwc_reference.py): every column of both rows, for the plans of (1, 1) and (3, 2) at k = 7 and (256, 8) at k = 13 (the
 voter's shape, 1996 queries), B in {1, 17, 65}.  Evaluations and (x, v, u) are synthetic: no proof is made.  x, v and u are each also taken from
 {1, r - 1}, and v = 0; a plan whose longest set has one query; the refusals of the C call."""

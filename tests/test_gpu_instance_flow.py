@@ -20,7 +20,7 @@ import torch
 
 import instance_reference as NR
 import zksnap_circuits_halo2_amd as Z
-from zksnap_circuits_halo2_amd import fields as F, keygen as KG, prover as P
+from zksnap_circuits_halo2_amd import fields as F, keygen as KG, prover as P, verifier as V
 from zksnap_circuits_halo2_amd.transcript import transcript_classes, vk_transcript_repr
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +41,7 @@ def read_head(vk, proof, shape, plan, instances):
     vk_io = io.BytesIO()
     vk.write(vk_io, KG.RAW_BYTES)
     with transcript_classes("blake2b")[1](bytes(proof)) as r:
-        return P._read_proof_head(r, vk_transcript_repr(vk_io.getvalue()), shape, plan, instances=instances)
+        return V._read_proof_head(r, vk_transcript_repr(vk_io.getvalue()), shape, plan, instances=instances)
 
 
 def changed(instances, column=0, row=2):
@@ -59,16 +59,16 @@ def observed(flow, **how):
         seen["verdict"] = real(params, vk, k, proof, shape, plan, *rest, instances=instances)
         wrong = changed(instances)
         seen["verdict_wrong_inputs"] = real(params, vk, k, proof, shape, plan, *rest, instances=wrong)
-        seen["openings_alone"] = P.verify_transcript_proofs(params, vk, k, [proof], shape, plan, identity=False, instances=[instances])[0]
+        seen["openings_alone"] = V.verify_transcript_proofs(params, vk, k, [proof], shape, plan, identity=False, instances=[instances])[0]
         _, challenges, evals = read_head(vk, proof, shape, plan, instances)
         seen.update(cs=vk.cs, plan=list(plan), challenges=challenges, evals=evals)
-        seen["status"] = int(P.identity_statuses(vk, k, plan, [evals], [challenges], [instances])[0])
-        seen["status_wrong_inputs"] = int(P.identity_statuses(vk, k, plan, [evals], [challenges], [wrong])[0])
+        seen["status"] = int(V.identity_statuses(vk, k, plan, [evals], [challenges], [instances])[0])
+        seen["status_wrong_inputs"] = int(V.identity_statuses(vk, k, plan, [evals], [challenges], [wrong])[0])
         seen["reference_wrong_inputs"] = NR.identity_value(vk.cs, plan, k, evals, challenges, wrong)
         with pytest.raises(ValueError, match="instance columns"):
-            P.verify_transcript_proofs(params, vk, k, [proof], shape, plan)
+            V.verify_transcript_proofs(params, vk, k, [proof], shape, plan)
         with pytest.raises(ValueError, match="instance columns"):
-            P.identity_statuses(vk, k, plan, [evals], [challenges])
+            V.identity_statuses(vk, k, plan, [evals], [challenges])
         return seen["verdict"]
 
     flow.verify_transcript_proof = spy
@@ -123,11 +123,11 @@ def test_five_proofs_of_one_key_over_different_public_inputs_in_one_call():
             assert len({tuple(p[0]) for p in publics}) == 5
             shape = {"advice": G + NL, "lookups": NL, "permutation_sets": dpk.vk.cs.num_permutation_sets, "random_poly": True}
             handed = [publics[0], publics[3], publics[2], changed(publics[3], row=LEN - 1), publics[4]]      # another proof's inputs; one value off
-            assert P.verify_transcript_proofs(params, dpk.vk, K, proofs, shape, plan, instances=handed) == [True, False, True, False, True]
-            assert P.verify_transcript_proofs(params, dpk.vk, K, proofs, shape, plan, instances=publics) == [True] * 5
-            assert P.verify_transcript_proof(params, dpk.vk, K, proofs[1], shape, plan, instances=publics[1]) is True
+            assert V.verify_transcript_proofs(params, dpk.vk, K, proofs, shape, plan, instances=handed) == [True, False, True, False, True]
+            assert V.verify_transcript_proofs(params, dpk.vk, K, proofs, shape, plan, instances=publics) == [True] * 5
+            assert V.verify_transcript_proof(params, dpk.vk, K, proofs[1], shape, plan, instances=publics[1]) is True
             with pytest.raises(ValueError, match="same lengths"):
-                P.verify_transcript_proofs(params, dpk.vk, K, proofs[:2], shape, plan, instances=[publics[0], [publics[1][0][:-1]]])
+                V.verify_transcript_proofs(params, dpk.vk, K, proofs[:2], shape, plan, instances=[publics[0], [publics[1][0][:-1]]])
         finally:
             if dpk is not None:
                 dpk.free()

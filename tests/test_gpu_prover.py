@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import zksnap_circuits_halo2_amd as Z
-from zksnap_circuits_halo2_amd import keygen as KG, prover as P
+from zksnap_circuits_halo2_amd import keygen as KG, prover as P, verifier as V
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,9 +32,9 @@ def test_create_proof_without_laps_writes_the_bytes_of_the_timed_flow():
             del pv
             assert type(proof) is bytes and proof == timed["proof"]
             assert plan == timed["proof_plan"]
-            assert P.verify_transcript_proof(params, dpk.vk, k, proof, timed["proof_shape"], plan) is True
+            assert V.verify_transcript_proof(params, dpk.vk, k, proof, timed["proof_shape"], plan) is True
             flipped = proof[:-1] + bytes([proof[-1] ^ 1])
             try:
-                assert P.verify_transcript_proof(params, dpk.vk, k, flipped, timed["proof_shape"], plan) is False
+                assert V.verify_transcript_proof(params, dpk.vk, k, flipped, timed["proof_shape"], plan) is False
             except Z._lib.ZkhipError as e:                                  # H' no longer decodes
                 assert e.code == -1

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): zkhip_shplonk_scalars_device against `multiopen.shplonk_accumulate` over `prover.verifier_queries`, laid out as a row
+"""GPU (-m gpu): zkhip_shplonk_scalars_device against `multiopen.shplonk_accumulate` over `verifier.verifier_queries`, laid out as a row
 (tests/shplonk_reference.py): every column of both rows and the status, for the plans of (1, 1) and (3, 2) at k = 7 in both plan orders (set 0 is
 the one-point set in the seeded order and the four-point set in the halo2 order), B in {1, 17, 65}, and (256, 8) at k = 13 (the voter's shape,
 1996 queries), B in {1, 17}.  Evaluations and (x, y, v, u) are synthetic: no proof is made.  x, y, v, u are each also taken from {1, r - 1}, y = 0

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the quotient identity at x -- `zkhip_fr_domain_points_device`, `zkhip_verify_identity_device` and the verifiers built on them
-(prover.verify_transcript_proofs, tools/prove_flow.py) -- against tests/identity_reference.py, which evaluates the identity on Python integers
+(verifier.verify_transcript_proofs, tools/prove_flow.py) -- against tests/identity_reference.py, which evaluates the identity on Python integers
 from the ConstraintSystem directly.
 
   1  the domain values at 1, 63, 64, 65 and 257 points, the edge points of the host check among them
@@ -25,7 +25,7 @@ import torch
 
 import identity_reference as IR
 import zksnap_circuits_halo2_amd as Z
-from zksnap_circuits_halo2_amd import evaluation as E, fields as F, keygen as KG, multiopen as MO, prover as P
+from zksnap_circuits_halo2_amd import evaluation as E, fields as F, keygen as KG, multiopen as MO, prover as P, verifier as V
 from zksnap_circuits_halo2_amd.transcript import transcript_classes, vk_transcript_repr
 
 pytestmark = pytest.mark.gpu
@@ -148,7 +148,7 @@ def read_head(vk, proof, shape, plan):
     vk_io = io.BytesIO()
     vk.write(vk_io, KG.RAW_BYTES)
     with transcript_classes("blake2b")[1](bytes(proof)) as r:
-        return P._read_proof_head(r, vk_transcript_repr(vk_io.getvalue()), shape, plan)
+        return V._read_proof_head(r, vk_transcript_repr(vk_io.getvalue()), shape, plan)
 
 
 _OBSERVED = {}
@@ -165,9 +165,9 @@ def observed(flow, gate_cols, lookups, k=7, inside=None, **how):
 
     def spy(params, vk, k_, proof, shape, plan):
         seen["verdict"] = real(params, vk, k_, proof, shape, plan)
-        seen["openings_alone"] = P.verify_transcript_proofs(params, vk, k_, [proof], shape, plan, identity=False)[0]
+        seen["openings_alone"] = V.verify_transcript_proofs(params, vk, k_, [proof], shape, plan, identity=False)[0]
         _, challenges, evals = read_head(vk, proof, shape, plan)
-        seen.update(cs=vk.cs, plan=list(plan), challenges=challenges, evals=evals, status=int(P.identity_statuses(vk, k_, plan, [evals], [challenges])[0]))
+        seen.update(cs=vk.cs, plan=list(plan), challenges=challenges, evals=evals, status=int(V.identity_statuses(vk, k_, plan, [evals], [challenges])[0]))
         if inside is not None:
             seen["inside"] = inside(params, vk, k_, proof, shape, plan)
         return seen["verdict"]
@@ -231,7 +231,7 @@ def test_five_proofs_of_one_key_in_one_call():
                 del pv, w
             assert len(set(proofs)) == 5
             shape = {"advice": gate_cols + lookups, "lookups": lookups, "permutation_sets": dpk.vk.cs.num_permutation_sets, "random_poly": True}
-            verify = lambda batch, **kw: P.verify_transcript_proofs(params, dpk.vk, k, batch, shape, plan, **kw)
+            verify = lambda batch, **kw: V.verify_transcript_proofs(params, dpk.vk, k, batch, shape, plan, **kw)
             assert verify(proofs) == [True, False, True, False, True]
             assert verify(proofs, identity=False) == [True] * 5                    # the openings alone accept all five
             cut = list(proofs)
@@ -239,8 +239,8 @@ def test_five_proofs_of_one_key_in_one_call():
             cut[4] = cut[4][:200]                                                  # ... and this one ends among its commitments
             assert verify(cut) == [True, False, False, False, False]
             assert verify([]) == []
-            assert P.verify_transcript_proof(params, dpk.vk, k, proofs[0], shape, plan) is True
-            assert P.verify_transcript_proof(params, dpk.vk, k, proofs[1], shape, plan) is False
+            assert V.verify_transcript_proof(params, dpk.vk, k, proofs[0], shape, plan) is True
+            assert V.verify_transcript_proof(params, dpk.vk, k, proofs[1], shape, plan) is False
         finally:
             if dpk is not None:
                 dpk.free()
@@ -255,7 +255,7 @@ def test_the_voters_shape_verifies_and_a_swapped_evaluation_is_refused(flow):
         swapped = bytearray(proof)
         swapped[first + 32 * a:first + 32 * a + 32], swapped[first + 32 * b:first + 32 * b + 32] = eb, ea
         _, challenges, evals = read_head(vk, bytes(swapped), shape, plan)
-        return len(plan), int(P.identity_statuses(vk, k, plan, [evals], [challenges])[0]), P.verify_transcript_proof(params, vk, k, bytes(swapped), shape, plan)
+        return len(plan), int(V.identity_statuses(vk, k, plan, [evals], [challenges])[0]), V.verify_transcript_proof(params, vk, k, bytes(swapped), shape, plan)
 
     res, seen = observed(flow, 256, 8, k=13, inside=inside)
     assert all(res["checks"].values()) and seen["verdict"] is True and seen["status"] == 0

@@ -18,7 +18,7 @@ import pytest
 
 import abi_header as AH
 import identity_reference as IR
-from zksnap_circuits_halo2_amd import _lib, evaluation as E, fields as F, prover as P
+from zksnap_circuits_halo2_amd import _lib, evaluation as E, fields as F, prover as P, verifier as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-O1"]
@@ -172,12 +172,12 @@ def test_a_key_without_its_constraint_system_cannot_verify():
 
     vk = KG.VerifyingKey(7, np.zeros((0, 8), dtype=np.uint64), np.zeros((0, 8), dtype=np.uint64))
     with pytest.raises(ValueError, match="constraint system"):
-        P.identity_program_of(vk, [("h", i, 0) for i in range(3)], 7)
+        V.identity_program_of(vk, [("h", i, 0) for i in range(3)], 7)
     with pytest.raises(ValueError, match="constraint system"):
-        P.verify_transcript_proof(None, vk, 7, b"", {"advice": 0, "lookups": 0, "permutation_sets": 0, "random_poly": False}, [("h", i, 0) for i in range(3)])
+        V.verify_transcript_proof(None, vk, 7, b"", {"advice": 0, "lookups": 0, "permutation_sets": 0, "random_poly": False}, [("h", i, 0) for i in range(3)])
     vk.cs = E.halo2_lib_shape(1, 1)
     plan = plan_of(vk.cs, 1, 1, 7)
-    assert P.identity_program_of(vk, plan, 7) is P.identity_program_of(vk, list(plan), 7)      # compiled once per (key, plan)
+    assert V.identity_program_of(vk, plan, 7) is V.identity_program_of(vk, list(plan), 7)      # compiled once per (key, plan)
 
 
 def test_the_prover_programs_are_the_bytes_of_the_parent_commit():

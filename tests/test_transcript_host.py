@@ -11,8 +11,8 @@ import pytest
 
 from oracle import bn254 as O
 from transcript_reference import RefTranscript
-from zksnap_circuits_halo2_amd import _lib, fields as F
-from zksnap_circuits_halo2_amd.transcript import Blake2bRead, Blake2bWrite
+from zksnap_circuits_halo2_amd import _lib, fields as F, multiopen as MO
+from zksnap_circuits_halo2_amd.transcript import Blake2bRead, Blake2bWrite, decoded
 
 R = O.R_MOD
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -233,3 +233,50 @@ def test_cpp_mirror_transcript(tmp_path):
     assert res.returncode == 0, res.stdout + res.stderr
     words = np.array([int(w, 16) for w in res.stdout.split()], dtype=np.uint64)
     assert F.fr_decode(words.reshape(1, 4))[0] == PIN_FRESH
+
+
+# ---- the multi-opens' parts of a proof ---------------------------------------------------------------------------------------------------------
+# Points of a transcript are decoded and normalised on the device, so the reading functions meet real proof bytes in
+# tests/test_gpu_multiopen_reads.py; here a reader that records its calls shows the order, and what becomes of its errors.
+class RecordingReader:
+    """hands out 1, 2, 3 .. as challenges and as points, in the order of the calls; `fail`: (the call that raises, the error's code)"""
+
+    def __init__(self, fail=None):
+        self.calls, self.next, self.fail = [], 0, fail
+
+    def _step(self, call, n=1):
+        self.calls.append(call)
+        if self.fail and len(self.calls) == self.fail[0]:
+            raise _lib.ZkhipError(self.fail[1], "a stub's error")
+        self.next += n
+        return list(range(self.next - n + 1, self.next + 1))
+
+    def squeeze_challenge(self):
+        return self._step("squeeze")[0]
+
+    def read_points(self, n, device=True):
+        return np.array(self._step(("read", n, device), n), dtype=np.uint64)[:, None] * np.ones(8, dtype=np.uint64)
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_each_verifier_class_reads_its_part_in_its_provers_order(device):
+    gwc, shplonk = RecordingReader(), RecordingReader()
+    points, challenges = MO.VerifierGWC(None).read_proof(gwc, 3, device=device)
+    assert gwc.calls == ["squeeze", ("read", 3, device), "squeeze"]
+    assert [int(p[0]) for p in points] == [2, 3, 4] and challenges == (1, 5)                    # W_0 .., (v, u)
+    points, challenges = MO.VerifierSHPLONK(None).read_proof(shplonk, 3, device=device)
+    assert shplonk.calls == ["squeeze", "squeeze", ("read", 1, device), "squeeze", ("read", 1, device)]
+    assert [int(p[0]) for p in points] == [5, 3] and challenges == (1, 2, 4)                    # [H', H], (y, v, u)
+
+
+@pytest.mark.parametrize("verifier, last_read", [(MO.VerifierGWC, 2), (MO.VerifierSHPLONK, 5)])
+def test_a_part_that_does_not_decode_is_none_and_other_errors_pass_through(verifier, last_read):
+    cut = RecordingReader(fail=(last_read, EINVAL))
+    assert decoded(verifier(None).read_proof, cut, 3) is None and len(cut.calls) == last_read  # nothing is asked of the reader after the failing read
+    assert verifier(None).verify_proof_transcript([], RecordingReader(fail=(last_read, EINVAL))) is False
+    for code in (-2, -3):
+        with pytest.raises(_lib.ZkhipError) as other:
+            decoded(verifier(None).read_proof, RecordingReader(fail=(last_read, code)), 3)
+        assert other.value.code == code
+        with pytest.raises(_lib.ZkhipError):
+            verifier(None).verify_proof_transcript([], RecordingReader(fail=(last_read, code)))

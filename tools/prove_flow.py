@@ -2,7 +2,7 @@
 """A `create_proof` (seeded challenges; with `transcript=True` a Blake2b transcript and a proof as bytes) for a *satisfied* circuit of the halo2-lib shape, device-resident from witness columns to
 quotient commitments -- the steps of [DEP] halo2-axiom plonk/prover.rs in the order the reference's prover runs them
 (/root/reference/aggregator/src/wrapper.rs:129).  This file is the driver: the witness, the phases, the challenge and blinding sources, the
-opening plan and the verifier of proof bytes are zksnap_circuits_halo2_amd/prover.py; here are the arguments, the lap clock, the mock step,
+opening plan are zksnap_circuits_halo2_amd/prover.py, the verifier of proof bytes is verifier.py; here are the arguments, the lap clock, the mock step,
 keygen (or the key-file round trip), the corrupt_proof edits, the verify step, the invariants and the result.
 
   SRS (ParamsKZG.setup, known trapdoor) -> advice commitments (Lagrange basis) -> permutation and lookup arguments (row programs,
@@ -33,8 +33,8 @@ import numpy as np
 import torch
 
 import zksnap_circuits_halo2_amd as Z
-from zksnap_circuits_halo2_amd import _lib, fields as F, keygen as KG, multiopen as MO, prover as P
-from zksnap_circuits_halo2_amd.prover import verify_transcript_proof      # run() calls the verifier through this module's name
+from zksnap_circuits_halo2_amd import _lib, fields as F, keygen as KG, multiopen as MO, prover as P, verifier as V
+from zksnap_circuits_halo2_amd.verifier import verify_transcript_proof      # run() calls the verifier through this module's name
 
 R = F.R_MOD
 NOT_PROVING = ("setup_srs", "witness_columns", "mock_prover", "stack_columns", "pk_file_round_trip", "pk_upload", "verify", "on_proof")      # and keygen_*
@@ -86,7 +86,7 @@ def _keygen(params, w, lap, pk_file, sharded_key):
 
 def _verify_seeded(pv, params, corrupt_proof, on_proof, lap):
     """what a verifier holds -- commitments, evaluations, H and H' -- through both halves of `verify_proof`: the identity at x over the
-    evaluations and the seeded challenges (one device call, prover.identity_statuses), then the openings and one pairing check;
+    evaluations and the seeded challenges (one device call, verifier.identity_statuses), then the openings and one pairing check;
     corrupt_proof changes one of them first"""
     vqueries, challenges, ok = pv.verifier_queries(), pv.ch.multiopen_challenges, False
     if pv.multiopen_proof is not None:
@@ -101,7 +101,7 @@ def _verify_seeded(pv, params, corrupt_proof, on_proof, lap):
             _lib.check(_lib.load().zkhip_g1_sum(both.ctypes.data, 2, moved.ctypes.data))     # H' + G: another curve point
             Hp_mo = moved
         public = [pv.w.instance_values] if pv.cs.num_instance else None       # the instance columns are evaluated from these, inside the identity call
-        holds = P.identity_statuses(pv.dpk.vk, pv.k, pv.plan, [[q.eval for q in vqueries]], [(pv.theta, pv.beta, pv.gamma, pv.y, pv.x)], public)[0] == 0
+        holds = V.identity_statuses(pv.dpk.vk, pv.k, pv.plan, [[q.eval for q in vqueries]], [(pv.theta, pv.beta, pv.gamma, pv.y, pv.x)], public)[0] == 0
         ok = bool(holds) and MO.VerifierSHPLONK(params).verify_proof(vqueries, H_mo, Hp_mo, *challenges)
     lap("verify")
     if on_proof is not None and pv.multiopen_proof is not None:
@@ -159,7 +159,7 @@ def run(k=16, gate_cols=4, seed=1, lookup_bits=8, corrupt=None, verbose=True, pk
     tr_hash = "blake2b" if transcript is True else transcript      # False: seeded
     if transcript:
         P.transcript_classes(tr_hash)
-    P.multiopen_classes(multiopen)
+    MO.multiopen_classes(multiopen)
     if multiopen != "shplonk" and not transcript:
         raise ValueError("multiopen=\"gwc\" needs a transcript: the seeded flow opens with SHPLONK")
     byte_flip = isinstance(corrupt_proof, tuple) and len(corrupt_proof) == 2 and corrupt_proof[0] == "byte"

@@ -18,7 +18,7 @@ timed region ends with the verdict on the host.
       zkhip_verify_identity_device on the same records), the repetitions of the two alternating, a second series of the call without as the A/A
       figure; beside it the host path a caller had before the device evaluated instance columns: the same evaluations on Python integers with
       one batched inversion per proof, and their upload
-  the batch verifier: verify_transcript_proofs one by one against fold=True (one folded pairing check per batch, multiopen.fold_check) in this one
+  the batch verifier: verifier.verify_transcript_proofs one by one against fold=True (one folded pairing check per batch, multiopen.fold_check) in this one
       process, the two sides alternating, for B in {1, 4, 16, 64} proofs and both multi-opens on the same shapes; the batch is ONE proof's bytes
       repeated B times (an honest input for timing: every copy is read, checked and folded like any other proof; the output says so); and the two
       calls behind it alone, zkhip_gwc_scalars_device, zkhip_fr_fold_rows_device and zkhip_shplonk_scalars_device, at B = 1, 64 and 4096 on
@@ -175,7 +175,7 @@ def random_elements(*shape):
 # ---- the quotient identity at x: the call on its own, and the flow's verify lap with and without it ------------------------------------------------
 if not args.no_identity:
     import prove_flow
-    from zksnap_circuits_halo2_amd import evaluation as E, prover as P
+    from zksnap_circuits_halo2_amd import evaluation as E, prover as P, verifier as V
 
     for shape in args.shapes.split(","):
         k, g, l = (int(x) for x in shape.split(":"))
@@ -198,7 +198,7 @@ if not args.no_identity:
             del evals, challenges
         if not args.no_flow:
             with_identity = prove_flow.verify_transcript_proof
-            openings_alone = lambda params, vk, k_, proof, shape_, plan_, *how: P.verify_transcript_proofs(params, vk, k_, [proof], shape_, plan_, *how, identity=False)[0]
+            openings_alone = lambda params, vk, k_, proof, shape_, plan_, *how: V.verify_transcript_proofs(params, vk, k_, [proof], shape_, plan_, *how, identity=False)[0]
             laps = {"openings alone": [], "identity + openings": []}
             try:
                 for _ in range(3):
@@ -270,7 +270,7 @@ if not args.no_instances:
 # ---- the batch verifier: one folded pairing check per batch against one check per proof ------------------------------------------------------------
 if not args.no_batch:
     import prove_flow
-    from zksnap_circuits_halo2_amd import evaluation as E, prover as P
+    from zksnap_circuits_halo2_amd import evaluation as E, prover as P, verifier as V
 
     def series(sides, reps):
         """the sides in turn, `reps` times, after one round that warms clocks and scratch: {name: [ms]}"""
@@ -294,8 +294,8 @@ if not args.no_batch:
             def measure(params, vk, k_, proof, shape_, plan_, *how):
                 for B in (int(b) for b in args.fold_batches.split(",")):
                     batch = [proof] * B
-                    one_by_one = lambda: P.verify_transcript_proofs(params, vk, k_, batch, shape_, plan_, *how)
-                    folded = lambda: P.verify_transcript_proofs(params, vk, k_, batch, shape_, plan_, *how, fold=True)
+                    one_by_one = lambda: V.verify_transcript_proofs(params, vk, k_, batch, shape_, plan_, *how)
+                    folded = lambda: V.verify_transcript_proofs(params, vk, k_, batch, shape_, plan_, *how, fold=True)
                     assert one_by_one() == [True] * B == folded()
                     got = series((("one by one", one_by_one), ("fold=True", folded)), args.batch_reps)
                     for name, ts in got.items():

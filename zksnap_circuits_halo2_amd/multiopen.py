@@ -24,6 +24,7 @@ import numpy as np
 from . import _lib, evaluation as E
 from .buffers import DeviceBuffer
 from .fields import R_MOD, fr_decode, fr_encode
+from .transcript import _is_device, decoded
 
 
 @dataclass
@@ -391,9 +392,10 @@ def _affine_to_xyz(point: np.ndarray) -> np.ndarray:
     return out
 
 
-def _read_xyz(tr, n: int) -> List[np.ndarray]:
-    """n points read from a transcript, as Jacobian points with z = 1 (a transcript holds no identity)"""
-    return [_affine_to_xyz(p) for p in tr.read_points(n, device=False)]
+def _points_xyz(points) -> List[np.ndarray]:
+    """points read from a transcript, each 8 affine limbs on the host or an (8,) device tensor, as Jacobian points with z = 1 on the host (a
+    transcript holds no identity)"""
+    return [_affine_to_xyz(p.cpu().numpy().view(np.uint64) if _is_device(p) else p) for p in points]
 
 
 def _generator_xyz(params) -> np.ndarray:
@@ -470,18 +472,34 @@ class VerifierGWC:
         L_neg = g1_combination([-s for s in left], np.stack(W))
         return _final_check(self.params, R_pt, L_neg)
 
-    def verify_proof_transcript(self, queries: Sequence[VerifierQuery], tr) -> bool:
-        """`verify_proof(transcript, queries, ..)` with the transcript (transcript.Blake2bRead): v is squeezed, one witness per distinct point
-        read, then u squeezed.  Proof bytes that do not decode reject."""
+    def read_proof(self, tr, n_points: int, device: bool = False):
+        """GWC's part of a proof from a transcript reader, in the order ProverGWC.create_proof_transcript wrote it: v is squeezed, one witness per
+        distinct point read (`n_points` of them), then u squeezed -> (the witnesses W_0 .., each 8 affine limbs on the host or, device=True,
+        in HBM: the first columns of an A row; (v, u): what follows x in a `points` record).  ZkhipError(-1): the witnesses do not decode;
+        v has been squeezed by then, u has not."""
         v = tr.squeeze_challenge()
-        try:
-            W = _read_xyz(tr, len(construct_intermediate_sets(queries)))
-        except _lib.ZkhipError as e:
-            if e.code == -1:
-                return False
-            raise
-        u = tr.squeeze_challenge()
-        return self.verify_proof(queries, W, v, u)
+        W = tr.read_points(n_points, device=device)
+        return list(W), (v, tr.squeeze_challenge())
+
+    def verify_proof_read(self, queries: Sequence[VerifierQuery], W, challenges) -> bool:
+        """`verify_proof` over what `read_proof` returned, the points on the host or on the device"""
+        return self.verify_proof(queries, _points_xyz(W), *challenges)
+
+    def verify_proof_transcript(self, queries: Sequence[VerifierQuery], tr) -> bool:
+        """`verify_proof(transcript, queries, ..)` with the transcript (transcript.Blake2bRead): `read_proof` with host points, then
+        `verify_proof`.  Proof bytes that do not decode reject."""
+        part = decoded(self.read_proof, tr, len(construct_intermediate_sets(queries)))
+        return part is not None and self.verify_proof_read(queries, *part)
+
+    # the batch verifier's plan and rows: the module's functions, looked up when called (tests substitute them)
+    @staticmethod
+    def fold_plan(plan_triples):
+        return gwc_plan(plan_triples)
+
+    @staticmethod
+    def fold_scalars(plan, evals, points, k: int):
+        """-> (rows_a, rows_c, None): GWC has a row for every proof, so no status"""
+        return (*gwc_scalars_device(plan, evals, points, k), None)
 
 
 class VerifierSHPLONK:
@@ -503,20 +521,47 @@ class VerifierSHPLONK:
         right_neg = g1_combination([-1], Hp.reshape(1, 12))
         return _final_check(self.params, left, right_neg)
 
+    def read_proof(self, tr, n_points: int = None, device: bool = False):
+        """SHPLONK's part of a proof from a transcript reader, in the order ProverSHPLONK.create_proof_transcript wrote it: squeeze y, squeeze
+        v, read H, squeeze u, read H' (whatever `n_points`, the number of distinct points, is) -> ([H', H], each 8 affine limbs on the host
+        or, device=True, in HBM: the first columns of an A row; (y, v, u): what follows x in a `points` record).  ZkhipError(-1): H or H' does
+        not decode; the squeezes in front of the failing read have happened."""
+        y, v = tr.squeeze_challenge(), tr.squeeze_challenge()
+        H = tr.read_points(1, device=device)
+        u = tr.squeeze_challenge()
+        Hp = tr.read_points(1, device=device)
+        return [Hp[0], H[0]], (y, v, u)
+
+    def verify_proof_read(self, queries: Sequence[VerifierQuery], points, challenges) -> bool:
+        """`verify_proof` over what `read_proof` returned ([H', H]: `verify_proof` takes H first), the points on the host or on the device"""
+        Hp, H = _points_xyz(points)
+        return self.verify_proof(queries, H, Hp, *challenges)
+
     def verify_proof_transcript(self, queries: Sequence[VerifierQuery], tr) -> bool:
-        """`verify_proof(transcript, queries, ..)` with the transcript (transcript.Blake2bRead): squeeze y, squeeze v, read H, squeeze u, read
-        H'.  Proof bytes that do not decode reject."""
-        y = tr.squeeze_challenge()
-        v = tr.squeeze_challenge()
-        try:
-            H = _read_xyz(tr, 1)[0]
-            u = tr.squeeze_challenge()
-            Hp = _read_xyz(tr, 1)[0]
-        except _lib.ZkhipError as e:
-            if e.code == -1:
-                return False
-            raise
-        return self.verify_proof(queries, H, Hp, y, v, u)
+        """`verify_proof(transcript, queries, ..)` with the transcript (transcript.Blake2bRead): `read_proof` with host points, then
+        `verify_proof`.  Proof bytes that do not decode reject."""
+        part = decoded(self.read_proof, tr)
+        return part is not None and self.verify_proof_read(queries, *part)
+
+    # the batch verifier's plan and rows: the module's functions, looked up when called (tests substitute them)
+    @staticmethod
+    def fold_plan(plan_triples):
+        return shplonk_plan(plan_triples)
+
+    @staticmethod
+    def fold_scalars(plan, evals, points, k: int):
+        """-> (rows_a, rows_c, status): status 1 is a proof without a row (shplonk_scalars_device)"""
+        return shplonk_scalars_device(plan, evals, points, k)
+
+
+MULTIOPEN = {"shplonk": (ProverSHPLONK, VerifierSHPLONK), "gwc": (ProverGWC, VerifierGWC)}
+
+
+def multiopen_classes(multiopen):
+    """(prover, verifier) of a multi-open's name; ValueError on any other name"""
+    if multiopen not in MULTIOPEN:
+        raise ValueError(f"multiopen {multiopen!r}: 'shplonk' or 'gwc'")
+    return MULTIOPEN[multiopen]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -528,25 +573,32 @@ class VerifierSHPLONK:
 # BN254 G1 has cofactor 1 and the transcript readers check every point, so nothing here checks a subgroup.
 # ---------------------------------------------------------------------------------------------------------------------------------
 @dataclass
-class GwcPlan:
-    """An opening plan as the GWC verifier groups it (include/zkhip.h, zkhip_gwc_plan): query q is triple q of the plan.  `set_rotation`: the
-    rotations as the plan spells them, in order of first appearance -- `construct_intermediate_sets` grouped by rotation, which is what grouping
-    by point gives for every x but 0; `query_pos`: a query's position inside its set (the exponent of v); `query_slot`: the slot of its
-    polynomial, the proof's own polynomials (`own_keys`, in order of first appearance) first and the key's (`shared_keys`) behind them.
-    `repeated`: a (kind, index, rotation) triple occurs twice, which the set construction would fold into one query: such a plan is verified
-    one by one, as is one with two rotations equal mod 2^k (`foldable`)."""
+class FoldPlan:
+    """What the fold plans of both multi-opens hold of the opened (kind, index, rotation) triples (prover.opening_plan); query q is triple q of
+    the plan.  `rotations`: the distinct rotations as the plan spells them, in order of first appearance -- the verifiers' set constructions
+    grouped by rotation, which is what grouping by point gives for every x but 0; `query_rotation`: the index of a query's rotation;
+    `query_slot`: the slot of its polynomial, the proof's own polynomials (`own_keys`, in order of first appearance) first and the key's
+    (`shared_keys`) behind them.  `repeated`: a (kind, index, rotation) triple occurs twice, which the set constructions would fold into one
+    query: such a plan is verified one by one, as is one with two rotations equal mod 2^k (`foldable`)."""
     n_evals: int
-    set_rotation: List[int]
-    query_set: List[int]
-    query_pos: List[int]
+    rotations: List[int]
+    query_rotation: List[int]
     query_slot: List[int]
     own_keys: List[tuple]
     shared_keys: List[tuple]
     repeated: bool
 
-    @property
-    def n_sets(self) -> int:
-        return len(self.set_rotation)
+    @staticmethod
+    def fields_of(plan_triples, shared_kinds):
+        """-> (the fields above of `plan_triples`, in order; keys, keys[q] = the (kind, index) of query q): polynomials of a kind in
+        `shared_kinds` are the key's"""
+        triples = [tuple(t) for t in plan_triples]
+        rotations = list(dict.fromkeys(rot for _, _, rot in triples))
+        keys = [(kind, idx) for kind, idx, _ in triples]
+        own = list(dict.fromkeys(key for key in keys if key[0] not in shared_kinds))
+        shared = list(dict.fromkeys(key for key in keys if key[0] in shared_kinds))
+        slots = {key: s for s, key in enumerate(own + shared)}
+        return (len(triples), rotations, [rotations.index(rot) for _, _, rot in triples], [slots[key] for key in keys], own, shared, len(set(triples)) != len(triples)), keys
 
     @property
     def n_slots(self) -> int:
@@ -554,126 +606,114 @@ class GwcPlan:
 
     def foldable(self, k: int) -> bool:
         """may the batch verifier group this plan by rotation at 2^k rows?  Not with a repeated triple, and not with two rotations equal mod 2^k
-        (their sets are one set of points): such plans are verified one by one, which groups by point"""
-        return not self.repeated and len({r % (1 << k) for r in self.set_rotation}) == len(self.set_rotation)
+        (they are one point, their sets one set of points): such plans are verified one by one, which groups by point"""
+        return not self.repeated and len({r % (1 << k) for r in self.rotations}) == len(self.rotations)
 
-    def marshal(self, k: int):
-        """-> (_lib.GwcPlan, the arrays it points into): rotations reduced mod 2^k.  ValueError: two rotations of the plan are equal mod 2^k
-        (their sets would be one set)"""
-        rot = [r % (1 << k) for r in self.set_rotation]
+    def _marshal(self, k: int, struct, counts, lists):
+        """-> (struct(*counts, a pointer per list), the uint32 arrays they point into), the rotations reduced mod 2^k in front of `lists`.
+        ValueError: two rotations of the plan are equal mod 2^k"""
+        rot = [r % (1 << k) for r in self.rotations]
         if len(set(rot)) != len(rot):
-            raise ValueError("gwc_plan: two rotations of the plan are equal mod 2^k")
-        arrays = [np.array(a, dtype=np.uint32) for a in (rot, self.query_set, self.query_pos, self.query_slot)]
-        ptr = [a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in arrays]
-        return _lib.GwcPlan(self.n_evals, self.n_sets, self.n_slots, 0, *ptr), arrays
+            raise ValueError("fold plan: two rotations of the plan are equal mod 2^k")
+        arrays = [np.array(a, dtype=np.uint32) for a in [rot] + lists]
+        return struct(*counts, *[a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in arrays]), arrays
 
 
-def gwc_plan(plan_triples, shared_kinds=("fixed", "sigma")) -> GwcPlan:
-    """the GwcPlan of the opened (kind, index, rotation) triples (prover.opening_plan); polynomials of a kind in `shared_kinds` are the key's"""
-    rotations, counts, slots = [], [], {}
-    q_set, q_pos, keys = [], [], []
-    for kind, idx, rot in plan_triples:
-        if rot not in rotations:
-            rotations.append(rot)
-            counts.append(0)
-        s = rotations.index(rot)
-        q_set.append(s)
-        q_pos.append(counts[s])
-        counts[s] += 1
-        keys.append((kind, idx))
-    own = list(dict.fromkeys(key for key in keys if key[0] not in shared_kinds))
-    shared = list(dict.fromkeys(key for key in keys if key[0] in shared_kinds))
-    for key in own + shared:
-        slots[key] = len(slots)
-    triples = [tuple(t) for t in plan_triples]
-    return GwcPlan(len(triples), rotations, q_set, q_pos, [slots[key] for key in keys], own, shared, len(set(triples)) != len(triples))
-
-
-def gwc_scalars_device(plan: GwcPlan, evals, points, k: int, stream=None):
-    """zkhip_gwc_scalars_device: evals (B, n_evals, 4), points (B, 3, 4) = x, v, u, contiguous int64 device tensors -> (rows_a (B, n_sets +
-    n_slots + 1, 4), rows_c (B, n_sets, 4)), the column layout of include/zkhip.h.  Asynchronous on `stream`."""
+def _scalars_device(call: str, plan: FoldPlan, evals, points, n_challenges: int, k: int, stream, outs):
+    """zkhip_<call> for both multi-opens: the tensor checks, plan.marshal(k), one output per entry of `outs` = (the shape behind B, the torch
+    dtype's name) allocated beside `evals`, omega, the call.  -> the outputs.  Asynchronous on `stream`."""
     import torch
 
     from .fields import omega_for
 
     B = evals.shape[0]
     if not (evals.is_cuda and evals.is_contiguous() and points.is_cuda and points.is_contiguous()) or tuple(evals.shape) != (B, plan.n_evals, 4) or \
-            tuple(points.shape) != (B, 3, 4):
-        raise ValueError("gwc_scalars_device: contiguous device tensors, (B, n_evals, 4) and (B, 3, 4)")
+            tuple(points.shape) != (B, 1 + n_challenges, 4):
+        raise ValueError(f"{call}: contiguous device tensors, (B, n_evals, 4) and (B, {1 + n_challenges}, 4)")
     struct, keep = plan.marshal(k)
-    rows_a = torch.empty((B, plan.n_sets + plan.n_slots + 1, 4), dtype=torch.int64, device=evals.device)
-    rows_c = torch.empty((B, plan.n_sets, 4), dtype=torch.int64, device=evals.device)
+    made = [torch.empty((B,) + shape, dtype=getattr(torch, dtype), device=evals.device) for shape, dtype in outs]
     omega = fr_encode([omega_for(k)])[0]
-    _lib.check(_lib.load().zkhip_gwc_scalars_device(C.byref(struct), evals.data_ptr(), points.data_ptr(), k, omega.ctypes.data, B, rows_a.data_ptr(),
-                                                    rows_c.data_ptr(), stream))
+    _lib.check(getattr(_lib.load(), "zkhip_" + call)(C.byref(struct), evals.data_ptr(), points.data_ptr(), k, omega.ctypes.data, B, *[t_.data_ptr() for t_ in made], stream))
     del keep
-    return rows_a, rows_c
+    return tuple(made)
 
 
 @dataclass
-class ShplonkPlan:
-    """An opening plan as the SHPLONK verifier groups it (include/zkhip.h, zkhip_shplonk_plan): query q is triple q of the plan.
-    `point_rotation`: the distinct rotations as the plan spells them, in order of first appearance -- the super point set; `set_points`: per
-    rotation set the indices of its rotations -- `construct_rotation_sets` grouped by rotation, which is what grouping by point gives for every
-    x but 0: polynomials with the same set of rotations share a set, sets and the polynomials inside one in order of first appearance;
-    `slot_set`, `slot_pos`: a polynomial's set and its position inside it (the exponent of y), the slots ordered as GwcPlan orders them
-    (`own_keys` first, `shared_keys` behind them); `query_slot`, `query_point`: a query's polynomial and the index of its rotation.
-    `repeated`, `foldable`: GwcPlan's rule."""
-    n_evals: int
-    point_rotation: List[int]
+class GwcPlan(FoldPlan):
+    """An opening plan as the GWC verifier groups it (include/zkhip.h, zkhip_gwc_plan): `construct_intermediate_sets` grouped by rotation, so a
+    set is a rotation (`set_rotation`, `query_set`: FoldPlan's `rotations`, `query_rotation`); `query_pos`: a query's position inside its set
+    (the exponent of v)."""
+    query_pos: List[int]
+
+    set_rotation = property(lambda self: self.rotations)
+    query_set = property(lambda self: self.query_rotation)
+
+    @property
+    def n_sets(self) -> int:
+        return len(self.rotations)
+
+    def marshal(self, k: int):
+        """-> (_lib.GwcPlan, the arrays it points into): rotations reduced mod 2^k.  ValueError: two rotations of the plan are equal mod 2^k
+        (their sets would be one set)"""
+        return self._marshal(k, _lib.GwcPlan, (self.n_evals, self.n_sets, self.n_slots, 0), [self.query_rotation, self.query_pos, self.query_slot])
+
+
+def gwc_plan(plan_triples, shared_kinds=("fixed", "sigma")) -> GwcPlan:
+    """the GwcPlan of the opened (kind, index, rotation) triples (prover.opening_plan); polynomials of a kind in `shared_kinds` are the key's"""
+    common, _ = FoldPlan.fields_of(plan_triples, shared_kinds)
+    seen, q_pos = [0] * len(common[1]), []               # per rotation, the queries so far
+    for s in common[2]:
+        q_pos.append(seen[s])
+        seen[s] += 1
+    return GwcPlan(*common, q_pos)
+
+
+def gwc_scalars_device(plan: GwcPlan, evals, points, k: int, stream=None):
+    """zkhip_gwc_scalars_device: evals (B, n_evals, 4), points (B, 3, 4) = x, v, u, contiguous int64 device tensors -> (rows_a (B, n_sets +
+    n_slots + 1, 4), rows_c (B, n_sets, 4)), the column layout of include/zkhip.h.  Asynchronous on `stream`."""
+    return _scalars_device("gwc_scalars_device", plan, evals, points, 2, k, stream, [((plan.n_sets + plan.n_slots + 1, 4), "int64"), ((plan.n_sets, 4), "int64")])
+
+
+@dataclass
+class ShplonkPlan(FoldPlan):
+    """An opening plan as the SHPLONK verifier groups it (include/zkhip.h, zkhip_shplonk_plan): `construct_rotation_sets` grouped by rotation,
+    so the rotations are the super point set (`point_rotation`, `query_point`: FoldPlan's `rotations`, `query_rotation`).  `set_points`: per
+    rotation set the indices of its rotations: polynomials with the same set of rotations share a set, sets and the polynomials inside one in
+    order of first appearance; `slot_set`, `slot_pos`: a polynomial's set and its position inside it (the exponent of y)."""
     set_points: List[List[int]]
     slot_set: List[int]
     slot_pos: List[int]
-    query_slot: List[int]
-    query_point: List[int]
-    own_keys: List[tuple]
-    shared_keys: List[tuple]
-    repeated: bool
+
+    point_rotation = property(lambda self: self.rotations)
+    query_point = property(lambda self: self.query_rotation)
 
     @property
     def n_sets(self) -> int:
         return len(self.set_points)
 
     @property
-    def n_slots(self) -> int:
-        return len(self.own_keys) + len(self.shared_keys)
-
-    @property
     def n_points(self) -> int:
-        return len(self.point_rotation)
-
-    def foldable(self, k: int) -> bool:
-        """may the batch verifier group this plan by rotation at 2^k rows?  Not with a repeated triple, and not with two rotations equal mod 2^k
-        (they are one point): such plans are verified one by one, which groups by point"""
-        return not self.repeated and len({r % (1 << k) for r in self.point_rotation}) == len(self.point_rotation)
+        return len(self.rotations)
 
     def marshal(self, k: int):
         """-> (_lib.ShplonkPlan, the arrays it points into): rotations reduced mod 2^k.  ValueError: two rotations of the plan are equal mod 2^k
         (they would be one point)"""
-        rot = [r % (1 << k) for r in self.point_rotation]
-        if len(set(rot)) != len(rot):
-            raise ValueError("shplonk_plan: two rotations of the plan are equal mod 2^k")
         starts = [0]
         for pts in self.set_points:
             starts.append(starts[-1] + len(pts))
         flat = [t for pts in self.set_points for t in pts]
-        arrays = [np.array(a, dtype=np.uint32) for a in (rot, starts, flat, self.slot_set, self.slot_pos, self.query_slot, self.query_point)]
-        ptr = [a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in arrays]
-        return _lib.ShplonkPlan(self.n_evals, self.n_sets, self.n_slots, self.n_points, *ptr), arrays
+        return self._marshal(k, _lib.ShplonkPlan, (self.n_evals, self.n_sets, self.n_slots, self.n_points),
+                             [starts, flat, self.slot_set, self.slot_pos, self.query_slot, self.query_rotation])
 
 
 def shplonk_plan(plan_triples, shared_kinds=("fixed", "sigma")) -> ShplonkPlan:
-    """the ShplonkPlan of the opened (kind, index, rotation) triples (prover.opening_plan); own and shared keys and the slots' order are gwc_plan's"""
-    rotations, by_poly, keys, q_point = [], {}, [], []
-    for kind, idx, rot in plan_triples:
-        if rot not in rotations:
-            rotations.append(rot)
-        t = rotations.index(rot)
-        pts = by_poly.setdefault((kind, idx), [])        # a polynomial's rotations, polynomials in order of first appearance
+    """the ShplonkPlan of the opened (kind, index, rotation) triples (prover.opening_plan); polynomials of a kind in `shared_kinds` are the key's"""
+    common, keys = FoldPlan.fields_of(plan_triples, shared_kinds)
+    by_poly = {}
+    for key, t in zip(keys, common[2]):
+        pts = by_poly.setdefault(key, [])                # a polynomial's rotations, polynomials in order of first appearance
         if t not in pts:
             pts.append(t)
-        keys.append((kind, idx))
-        q_point.append(t)
     set_index, set_points, counts, set_of, pos_of = {}, [], [], {}, {}
     for key, pts in by_poly.items():
         i = set_index.setdefault(frozenset(pts), len(set_points))
@@ -682,12 +722,8 @@ def shplonk_plan(plan_triples, shared_kinds=("fixed", "sigma")) -> ShplonkPlan:
             counts.append(0)
         set_of[key], pos_of[key] = i, counts[i]
         counts[i] += 1
-    own = list(dict.fromkeys(key for key in keys if key[0] not in shared_kinds))
-    shared = list(dict.fromkeys(key for key in keys if key[0] in shared_kinds))
-    slots = {key: s for s, key in enumerate(own + shared)}
-    triples = [tuple(t) for t in plan_triples]
-    return ShplonkPlan(len(triples), rotations, set_points, [set_of[key] for key in own + shared], [pos_of[key] for key in own + shared], [slots[key] for key in keys],
-                       q_point, own, shared, len(set(triples)) != len(triples))
+    slot_keys = common[4] + common[5]                    # own, then shared
+    return ShplonkPlan(*common, set_points, [set_of[key] for key in slot_keys], [pos_of[key] for key in slot_keys])
 
 
 def shplonk_scalars_device(plan: ShplonkPlan, evals, points, k: int, stream=None):
@@ -695,23 +731,7 @@ def shplonk_scalars_device(plan: ShplonkPlan, evals, points, k: int, stream=None
     n_slots + 1, 4) over [H', H | own polynomials | key polynomials | G], rows_c (B, 1, 4), status (B,) int32), the column layout of
     include/zkhip.h: what `shplonk_accumulate` returns for each proof.  status[i] = 1: x Z_0 = 0 for proof i, its rows are zeros and the caller
     verifies it one by one.  Asynchronous on `stream`."""
-    import torch
-
-    from .fields import omega_for
-
-    B = evals.shape[0]
-    if not (evals.is_cuda and evals.is_contiguous() and points.is_cuda and points.is_contiguous()) or tuple(evals.shape) != (B, plan.n_evals, 4) or \
-            tuple(points.shape) != (B, 4, 4):
-        raise ValueError("shplonk_scalars_device: contiguous device tensors, (B, n_evals, 4) and (B, 4, 4)")
-    struct, keep = plan.marshal(k)
-    rows_a = torch.empty((B, 2 + plan.n_slots + 1, 4), dtype=torch.int64, device=evals.device)
-    rows_c = torch.empty((B, 1, 4), dtype=torch.int64, device=evals.device)
-    status = torch.empty((B,), dtype=torch.int32, device=evals.device)
-    omega = fr_encode([omega_for(k)])[0]
-    _lib.check(_lib.load().zkhip_shplonk_scalars_device(C.byref(struct), evals.data_ptr(), points.data_ptr(), k, omega.ctypes.data, B, rows_a.data_ptr(),
-                                                        rows_c.data_ptr(), status.data_ptr(), stream))
-    del keep
-    return rows_a, rows_c, status
+    return _scalars_device("shplonk_scalars_device", plan, evals, points, 3, k, stream, [((2 + plan.n_slots + 1, 4), "int64"), ((1, 4), "int64"), ((), "int32")])
 
 
 def fold_rows_device(rows, n_own: int, r, negate: bool, out_own, out_shared, stream=None) -> None:

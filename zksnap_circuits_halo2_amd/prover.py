@@ -9,8 +9,7 @@ multi-open -- the steps of [DEP] halo2-axiom plonk/prover.rs, each a method of `
   SeededChallenges / TranscriptChallenges where challenges come from; each has its own order of steps (Prover._seeded, Prover._transcript)
   opening_plan        the opened (kind, index, rotation) triples; the prover and both verifiers turn them into queries through one
                       (kind, index) map each
-  verify_transcript_proofs                the verifier of a batch of proofs given as bytes: the quotient identity at x of all of them in one device
-                      call, then the openings of those that passed (verify_transcript_proof: the batch of one)
+The verifier of the proofs written here is verifier.py; it is handed the plan.
 
 `lap` is a callable handed a name at every phase boundary (tools/prove_flow.py times the phases with it); None: no laps, so no synchronisation
 is added for timing (the phases that read a value back -- whether a product closes, the evaluations as integers -- still wait for it)."""
@@ -26,6 +25,7 @@ import torch
 from . import _lib, evaluation as E, fields as F, keygen as KG, multiopen as MO, tensors as T
 from .domain import EvaluationDomain
 from .transcript import transcript_classes, vk_transcript_repr
+from .verifier import key_commitments, verifier_queries
 
 R = F.R_MOD
 BLIND = 5
@@ -168,7 +168,7 @@ class TranscriptChallenges:
         return proof
 
 
-# ---- the opening plan and the queries made from it --------------------------------------------------------------------------------------------
+# ---- the opening plan ------------------------------------------------------------------------------------------------------------------------------
 def opening_plan(cs, gate_cols, lookups, usable_rows, random_poly=False, order="halo2"):
     """The opened (kind, index, rotation) triples of the halo2-lib shape.  order "halo2": the order halo2 writes its evaluations in -- advice;
     fixed; the random polynomial; sigma; per permutation set z(x), z(omega x) and, for all but the last set, z(omega^last x); per lookup
@@ -188,285 +188,6 @@ def opening_plan(cs, gate_cols, lookups, usable_rows, random_poly=False, order="
     if order == "seeded":
         return fixed + advice + random_ + rest
     raise ValueError("opening_plan: order is \"halo2\" or \"seeded\"")
-
-
-def verifier_queries(plan, commitments, evals, x, k):
-    """a VerifierQuery per triple of the plan; commitments: (kind, index) -> Jacobian limbs.  poly_id keeps polynomials with equal commitments
-    (two selector columns with the same rows) apart, as the prover does."""
-    w = F.omega_for(k)
-    return [MO.VerifierQuery(x * pow(w, r, R) % R, commitments[(kind, idx)], e, poly_id=(kind, idx)) for (kind, idx, r), e in zip(plan, evals)]
-
-
-def _key_commitments(vk):
-    com = {("fixed", i): MO._affine_to_xyz(c) for i, c in enumerate(vk.fixed_commitments)}
-    com.update({("sigma", i): MO._affine_to_xyz(c) for i, c in enumerate(vk.permutation_commitments)})
-    return com
-
-
-MULTIOPEN = {"shplonk": (MO.ProverSHPLONK, MO.VerifierSHPLONK), "gwc": (MO.ProverGWC, MO.VerifierGWC)}
-
-
-def multiopen_classes(multiopen):
-    """(prover, verifier) of a multi-open's name; ValueError on any other name"""
-    if multiopen not in MULTIOPEN:
-        raise ValueError(f"multiopen {multiopen!r}: 'shplonk' or 'gwc'")
-    return MULTIOPEN[multiopen]
-
-
-def _read_proof_head(r, vk_repr, shape, plan, instances=(), on_device=False):
-    """a proof up to its evaluations, in the prover's order: (commitments by (kind, index), (theta, beta, gamma, y, x), the evaluations as
-    integers); the reader is left in front of the multi-open's part.  instances: the proof's public inputs, one list of integers per instance
-    column, absorbed behind the key.  on_device: the commitments stay in HBM, each an (8,) affine device tensor (the batch verifier's MSMs read
-    them there).  ZkhipError(-1): bytes that do not decode"""
-    def xyz(points):                                       # device affine points -> Jacobian limbs with z = 1 for the host-side accumulation
-        if on_device:
-            return list(points)
-        return [MO._affine_to_xyz(p_) for p_ in points.cpu().numpy().view(np.uint64).reshape(-1, 8)]
-
-    n_adv, n_lk, n_sets = shape["advice"], shape["lookups"], shape["permutation_sets"]
-    r.common_scalar(vk_repr)
-    for column in instances:
-        for v_ in column:
-            r.common_scalar(v_ % R)
-    com = {("advice", i): c_ for i, c_ in enumerate(xyz(r.read_points(n_adv)))}
-    theta = r.squeeze_challenge()
-    if n_lk:
-        for j, c_ in enumerate(xyz(r.read_points(2 * n_lk))):
-            com[("lookup_pa" if j % 2 == 0 else "lookup_ps", j // 2)] = c_
-    beta, gamma = r.squeeze_challenge(), r.squeeze_challenge()
-    for j, c_ in enumerate(xyz(r.read_points(n_sets + n_lk))):
-        com[("perm", j) if j < n_sets else ("lookup_z", j - n_sets)] = c_
-    if shape["random_poly"]:
-        com[("random", 0)] = xyz(r.read_points(1))[0]
-    y = r.squeeze_challenge()
-    for i, c_ in enumerate(xyz(r.read_points(3))):
-        com[("h", i)] = c_
-    x = r.squeeze_challenge()
-    return com, (theta, beta, gamma, y, x), r.read_scalars(len(plan))
-
-
-def identity_program_of(vk, plan, k):
-    """the quotient identity of the key's circuit over `plan` (evaluation.identity_program), compiled and marshalled once per (key, plan): kept
-    on the key object, so it lives as long as the key does.  ValueError: a key without its constraint system"""
-    if getattr(vk, "cs", None) is None:
-        raise ValueError("the verifying key carries no constraint system (vk.cs): the verifier cannot state the circuit's identity")
-    cache = vk.__dict__.setdefault("_identity_programs", {})
-    key = (k, tuple(plan))
-    if key not in cache:
-        cache[key] = E.identity_program(vk.cs, plan, k, instance_queries=E.instance_queries(vk.cs) if vk.cs.num_instance else None)._marshal()
-    return cache[key]
-
-
-def _check_instances(cs, k, instances, proofs):
-    """instances[p][c] = the integers of instance column c of proof p: one entry per proof, one list per column, every proof the same lengths
-    (a circuit fixes them), none longer than the usable rows (halo2's `InstanceTooLarge`).  Returns the columns' lengths."""
-    if len(instances) != proofs or any(len(per_proof) != cs.num_instance for per_proof in instances):
-        raise ValueError(f"instances: {cs.num_instance} columns of public inputs for each of the {proofs} proofs")
-    lens = [len(column) for column in instances[0]] if instances else [0] * cs.num_instance
-    if any([len(column) for column in per_proof] != lens for per_proof in instances):
-        raise ValueError("instances: the proofs of one circuit have instance columns of the same lengths")
-    if any(length > (1 << k) - (cs.blinding_factors + 1) for length in lens):
-        raise ValueError("instances: a column holds more values than the circuit has usable rows")
-    return lens
-
-
-def identity_statuses(vk, k, plan, evals, challenges, instances=None, d_evals=None):
-    """zkhip_verify_identity_device over a batch: evals[i] the integers of proof i in the plan's order, challenges[i] = (theta, beta, gamma, y,
-    x); for a circuit with instance columns instances[i] = proof i's public inputs, a list of integers per column, evaluated on the device
-    (zkhip_verify_identity_instances_device).  d_evals: the evaluations as a (proofs, len(plan), 4) device tensor where the caller has uploaded
-    them already (the batch verifier reads the same records).  An int32 array: 0 the identity holds, 1 it does not, 2 x lies in the domain."""
-    n_instance = vk.cs.num_instance if getattr(vk, "cs", None) is not None else 0
-    if n_instance and instances is None:
-        raise ValueError("identity_statuses: the circuit has instance columns: hand in the proofs' public inputs (instances=)")
-    if not evals:
-        return np.zeros(0, dtype=np.int32)
-    prog = identity_program_of(vk, plan, k)
-    if d_evals is None:
-        d_evals = words([e_ for row in evals for e_ in row]).reshape(len(evals), len(plan), 4)
-    d_challenges = words([c_ for row in challenges for c_ in row]).reshape(len(evals), 5, 4)
-    usable = (1 << k) - (vk.cs.blinding_factors + 1)
-    if not n_instance:
-        return E.verify_identity_device(prog, d_evals, d_challenges, k, usable)[0]
-    lens = _check_instances(vk.cs, k, instances, len(evals))
-    flat = [v_ % R for per_proof in instances for column in per_proof for v_ in column]
-    d_instances = words(flat).reshape(len(evals), sum(lens), 4) if flat else None
-    return E.verify_identity_device(prog, d_evals, d_challenges, k, usable, instances=d_instances, column_lens=lens, queries=E.instance_queries(vk.cs))[0]
-
-
-def gwc_plan_of(vk, plan):
-    """multiopen.gwc_plan of `plan`, made once per (key, plan) and kept on the key object beside the identity program"""
-    cache = vk.__dict__.setdefault("_gwc_plans", {})
-    key = tuple(plan)
-    if key not in cache:
-        cache[key] = MO.gwc_plan(plan)
-    return cache[key]
-
-
-def shplonk_plan_of(vk, plan):
-    """multiopen.shplonk_plan of `plan`, kept on the key object as gwc_plan_of keeps its plan"""
-    cache = vk.__dict__.setdefault("_shplonk_plans", {})
-    key = tuple(plan)
-    if key not in cache:
-        cache[key] = MO.shplonk_plan(plan)
-    return cache[key]
-
-
-def _host_xyz(point):
-    """an (8,) affine device tensor -> Jacobian limbs with z = 1 on the host"""
-    return MO._affine_to_xyz(point.cpu().numpy().view(np.uint64))
-
-
-def _fold_openings(params, vk, k, plan, multiopen, heads, order, d_evals, rows_of, fold_seed, verdicts):
-    """The openings of the proofs `order` (their heads read with on_device=True, the readers in front of the multi-open's part) decided by
-    multiopen.fold_check.  d_evals: the uploaded evaluations, rows_of[i] the row of proof i in them.  A proof whose multi-open part does not
-    decode is refused alone; a proof with x = 0 mod r (where the grouping by rotation and halo2's grouping by point differ) is verified on its
-    own by the multi-open's verifier, and so is a SHPLONK proof that zkhip_shplonk_scalars_device gives status 1.  Both multi-opens make the
-    rows of the folded proofs on the device: the host's `gwc_accumulate` and `shplonk_accumulate` run only inside the one-by-one verifier."""
-    gp = gwc_plan_of(vk, plan)
-    key_points = {("fixed", i): c for i, c in enumerate(vk.fixed_commitments)}
-    key_points.update({("sigma", i): c for i, c in enumerate(vk.permutation_commitments)})
-    shared = np.stack([np.asarray(key_points[key_], dtype=np.uint64).reshape(8) for key_ in gp.shared_keys] + [np.asarray(params.g[0], dtype=np.uint64).reshape(8)])
-    d_shared = torch.from_numpy(shared.view(np.int64)).to(DEV)
-    folded, own, points = [], [], []
-    for i in order:
-        r, com, challenges, evals = heads[i]
-        x = challenges[4]
-        try:
-            if x % R == 0:
-                host = {key_: _host_xyz(c_) for key_, c_ in com.items()}
-                host.update(_key_commitments(vk))
-                verdicts[i] = bool(multiopen_classes(multiopen)[1](params).verify_proof_transcript(verifier_queries(plan, host, evals, x, k), r))
-                continue
-            if multiopen == "gwc":
-                v = r.squeeze_challenge()
-                mine = r.read_points(gp.n_sets)
-                u = r.squeeze_challenge()
-                points.append((x, v, u))
-            else:
-                y, v = r.squeeze_challenge(), r.squeeze_challenge()
-                H = r.read_points(1)
-                u = r.squeeze_challenge()
-                Hp = r.read_points(1)
-                mine = torch.cat([Hp, H])
-                points.append((x, y, v, u))
-        except _lib.ZkhipError as e:                       # the multi-open's own points do not decode
-            if e.code != -1:
-                raise
-            continue
-        folded.append(i)
-        own.append(torch.cat([mine, torch.stack([com[key_] for key_ in gp.own_keys])]) if gp.own_keys else mine)
-    if not folded:
-        return
-    d_own = torch.stack(own).contiguous()
-    index = torch.tensor([rows_of[i] for i in folded], dtype=torch.int64, device=DEV)
-    d_points = words([c_ for row in points for c_ in row]).reshape(len(folded), len(points[0]), 4)
-    if multiopen == "gwc":
-        d_rows_a, d_rows_c = MO.gwc_scalars_device(gp, d_evals.index_select(0, index).contiguous(), d_points, k)
-    else:
-        d_rows_a, d_rows_c, d_status = MO.shplonk_scalars_device(shplonk_plan_of(vk, plan), d_evals.index_select(0, index).contiguous(), d_points, k)
-        refused = [j for j, s_ in enumerate(d_status.cpu().tolist()) if s_ != 0]
-        if refused:                                        # u on a point outside set 0: the row does not exist, the one-by-one verifier decides
-            for j in refused:
-                i = folded[j]
-                host = {key_: _host_xyz(c_) for key_, c_ in heads[i][1].items()}
-                host.update(_key_commitments(vk))
-                verdicts[i] = bool(MO.VerifierSHPLONK(params).verify_proof(verifier_queries(plan, host, heads[i][3], points[j][0], k), _host_xyz(d_own[j][1]),
-                                                                            _host_xyz(d_own[j][0]), *points[j][1:]))
-            kept = [j for j in range(len(folded)) if j not in refused]
-            if not kept:
-                return
-            keep = torch.tensor(kept, dtype=torch.int64, device=DEV)
-            folded = [folded[j] for j in kept]
-            d_own, d_rows_a, d_rows_c = (t_.index_select(0, keep).contiguous() for t_ in (d_own, d_rows_a, d_rows_c))
-    for i, ok in zip(folded, MO.fold_check(params, d_rows_a, d_rows_c, d_own, d_shared, fold_seed)):
-        verdicts[i] = bool(ok)
-
-
-def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b", multiopen="shplonk", *, identity=True, instances=None, fold=False,
-                             fold_seed=None):
-    """The verifier of a BATCH of proofs of one circuit, each written through TranscriptChallenges: it is handed the parameters, the verifying key
-    (with its constraint system, `vk.cs`), the proofs' BYTES, and what a verifier knows of the circuit -- `shape` (how many advice columns,
-    lookups, permutation sets, whether a random polynomial is committed) and `plan` (the opened (kind, index, rotation) triples, in the order
-    their evaluations were written).  Every proof's head is replayed with reads -- commitments land on the device as affine points, evaluations
-    as integers, every challenge is derived here --; then the two halves of halo2's `verify_proof`:
-      the identity   the gate, permutation and lookup expressions at x against h(x) (x^n - 1), for ALL proofs in one device call
-                     (zkhip_verify_identity_device; the program is compiled once per key and plan); the instance columns are evaluated
-                     at x from the public inputs inside that call (zkhip_verify_identity_instances_device);
-      the openings   for the proofs whose identity holds, `VerifierSHPLONK.verify_proof_transcript` (multiopen="gwc":
-                     `VerifierGWC.verify_proof_transcript`), one pairing check each.
-    A proof is accepted when both accept; bytes that do not decode reject that proof alone.  hash: the transcript the proofs were written under
-    ("blake2b" or "poseidon").  identity=False leaves the first half out (the openings alone: what a test uses to show WHICH half refused).
-    instances: for a circuit with instance columns, instances[i][c] = the integers of column c that proof i is verified AGAINST (the public
-    inputs; never part of the proof).  They are absorbed into proof i's transcript behind the key, as the prover absorbed its own, so wrong
-    inputs change every challenge, and they enter the identity through the instance columns' evaluations at x.  ValueError: a key whose
-    circuit has instance columns and no `instances`; lengths that differ between the proofs or exceed the usable rows.
-    fold=True: the openings of the proofs that passed the identity are decided together by multiopen.fold_check (halo2's `BatchVerifier`): the
-    commitments stay in HBM, every proof's two accumulated points are rows of scalars -- multiopen="gwc": made by zkhip_gwc_scalars_device from
-    the evaluations the identity call read; "shplonk": by zkhip_shplonk_scalars_device from the same records, as [H', H, own polynomials | key
-    polynomials, G], one inversion per proof; a proof whose u hits a point outside the first rotation set has no such row (status 1) and is
-    verified one by one --,
-    and ONE pairing check accepts the batch; a batch that fails is bisected.  The verdicts are those of fold=False (a wrong proof passes a
-    folded check with probability about 1 / r).  A proof with x = 0 mod r, a plan that repeats a triple and a plan with two rotations equal mod 2^k take the one-by-one path.
-    fold_seed: the 32 bytes the random multipliers are drawn from; None (what a verifier uses) draws them from os.urandom, a fixed seed is for
-    tests.
-    Not built: committed instance columns, multi-phase challenges; folding across
-    different circuits or parameter sets, a batch sharded over devices.  Returns a list of bools."""
-    import contextlib
-
-    verifier = multiopen_classes(multiopen)[1]
-    reader = transcript_classes(hash)[1]
-    if identity:
-        identity_program_of(vk, plan, k)                   # a key that cannot state its identity is the caller's error, whatever the proofs are
-    n_instance = vk.cs.num_instance if getattr(vk, "cs", None) is not None else 0
-    if n_instance and instances is None:
-        raise ValueError("verify_transcript_proofs: the key's circuit has instance columns: hand in the public inputs of every proof (instances=)")
-    if n_instance:
-        _check_instances(vk.cs, k, instances, len(proofs))
-    vk_io = io.BytesIO()
-    vk.write(vk_io, KG.RAW_BYTES)
-    vk_repr = vk_transcript_repr(vk_io.getvalue())
-    verdicts = [False] * len(proofs)
-    fold = bool(fold) and bool(proofs) and gwc_plan_of(vk, plan).foldable(k)
-    with contextlib.ExitStack() as stack:
-        heads = {}
-        for i, proof in enumerate(proofs):
-            r = stack.enter_context(reader(bytes(proof)))
-            try:
-                heads[i] = (r,) + _read_proof_head(r, vk_repr, shape, plan, instances[i] if n_instance else (), on_device=fold)
-            except _lib.ZkhipError as e:
-                if e.code != -1:
-                    raise
-        order = sorted(heads)
-        rows_of = {i: row for row, i in enumerate(order)}
-        d_evals = None
-        if fold and order:                                 # uploaded once: the identity call and the GWC scalars read the same records
-            d_evals = words([e_ for i in order for e_ in heads[i][3]]).reshape(len(order), len(plan), 4)
-        if identity:
-            status = identity_statuses(vk, k, plan, [heads[i][3] for i in order], [heads[i][2] for i in order], [instances[i] for i in order] if n_instance else None,
-                                       d_evals=d_evals)
-            order = [i for i, s_ in zip(order, status) if s_ == 0]
-        if fold:
-            _fold_openings(params, vk, k, plan, multiopen, heads, order, d_evals, rows_of, fold_seed, verdicts)
-            return verdicts
-        key_com = _key_commitments(vk)
-        for i in order:
-            r, com, challenges, evals = heads[i]
-            com.update(key_com)
-            try:
-                verdicts[i] = bool(verifier(params).verify_proof_transcript(verifier_queries(plan, com, evals, challenges[4], k), r))
-            except _lib.ZkhipError as e:                   # the multi-open's own points do not decode
-                if e.code != -1:
-                    raise
-    return verdicts
-
-
-def verify_transcript_proof(params, vk, k, proof, shape, plan, hash="blake2b", multiopen="shplonk", instances=None, fold=False, fold_seed=None):
-    """The verifier of one proof given as bytes: `verify_transcript_proofs` over a batch of one -- the identity at x and the openings, accepted
-    when both accept.  instances: the proof's public inputs, a list of integers per instance column.  fold, fold_seed: passed on (the openings
-    through the batch verifier's path).  ValueError: a verifying key without its constraint system; a circuit with instance columns and no
-    `instances`."""
-    return verify_transcript_proofs(params, vk, k, [proof], shape, plan, hash, multiopen, instances=None if instances is None else [instances], fold=fold,
-                                    fold_seed=fold_seed)[0]
 
 
 # ---- the witness -------------------------------------------------------------------------------------------------------------------------------
@@ -582,7 +303,7 @@ class Prover:
 
     def __init__(self, params, witness, blinding, batched=None, lap=None, multiopen="shplonk"):
         self.params, self.w, self.blinding = params, witness, blinding
-        self.multiopen_name, self.multiopen_prover = multiopen, multiopen_classes(multiopen)[0]
+        self.multiopen_name, self.multiopen_prover = multiopen, MO.multiopen_classes(multiopen)[0]
         self.cs, self.qc = witness.cs, E.quotient_columns(witness.cs)
         self.k, self.n, self.u = witness.k, 1 << witness.k, (1 << witness.k) - (BLIND + 1)
         self.dom = EvaluationDomain(4, self.k)
@@ -633,7 +354,7 @@ class Prover:
     def prove(self, dpk, challenges, lookups_one_call=True, sharded_quotient=False, sharded_key=False):
         NL, with_transcript = self.w.lookups, challenges.transcript is not None
         check_options(with_transcript, NL, lookups_one_call, sharded_quotient, sharded_key)
-        if self.multiopen_name != "shplonk" and not with_transcript:
+        if not with_transcript and self.multiopen_prover is not MO.ProverSHPLONK:      # SeededChallenges draws SHPLONK's y, v, u
             raise ValueError("multiopen=\"gwc\" writes its witnesses to a transcript: the seeded flow opens with SHPLONK")
         self.dpk, self.ch, self.sharded_quotient, self.sharded_key = dpk, challenges, sharded_quotient, sharded_key
         # a single lookup over 2^20 rows or more stays with the loop
@@ -942,7 +663,7 @@ class Prover:
         """what a verifier holds of a seeded proof: the commitments (advice, products, quotient pieces, the verifying key's fixed and sigma
         commitments) and the evaluations (`evals` at x, the rotated openings from the multi-open), as VerifierQuerys in the plan's order"""
         com = {kind: c_.cpu().numpy().view(np.uint64).reshape(12).copy() for kind, c_ in self.commitments.items()}
-        com.update(_key_commitments(self.dpk.vk))
+        com.update(key_commitments(self.dpk.vk))
         slot = {kind: i for i, kind in enumerate(self.polynomials()[0])}
         at_x = T.fr_ints(self.evals)
         evals = [at_x[slot[(kind, idx)]] if r == 0 else q.eval for (kind, idx, r), q in zip(self.plan, self.queries)]

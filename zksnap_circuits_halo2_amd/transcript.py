@@ -164,6 +164,16 @@ def transcript_classes(hash: str):
     return WRITERS[hash], READERS[hash]
 
 
+def decoded(read, *args, **kw):
+    """read(*args, **kw), or None where a reader's bytes do not decode (ZkhipError with ZKHIP_EINVAL, -1): such bytes reject one proof, the
+    caller's and no other; every other error of the library passes through.  The reader is left where the failing read left it."""
+    try:
+        return read(*args, **kw)
+    except _lib.ZkhipError as e:
+        if e.code != -1:
+            raise
+        return None
+
 
 def vk_transcript_repr(vk_bytes: bytes) -> int:
     """The scalar a proof's transcript starts with.  halo2's value hashes the `Debug` string of the pinned verifying key, which cannot be

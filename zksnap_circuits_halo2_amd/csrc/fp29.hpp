@@ -205,6 +205,35 @@ ZK_HD fe fe_mul(const fe& a, const fe& b) {
   return r;
 }
 
+// The Montgomery reduction alone: a * 2^-261 mod p for an N-form a < 2^261 -- fe_mul(a, 1) written without the product: the 81
+// m_i * p_j multiply-adds (p is the constant operand) and one addition per column for a's limb.  Result in N form, value
+// (a + m p) / 2^261 < a / 2^261 + p, so at most p for every a < 2^261.  The compiler's shape (no CHAIN): its callers are the conversion
+// kernels, a few wavefronts per SIMD.
+template <class P>
+ZK_HD fe fe_mont_reduce(const fe& a) {
+  uint64_t acc = 0;
+  uint32_t m[NL];
+  fe r;
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    acc += a.l[k];
+#pragma unroll
+    for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * P::P[k - i];
+    m[k] = ((uint32_t)acc * P::INV) & LMASK;
+    acc += (uint64_t)m[k] * P::P[0];
+    acc >>= LB;
+  }
+#pragma unroll
+  for (int k = NL; k < 2 * NL - 1; k++) {
+#pragma unroll
+    for (int i = k - NL + 1; i < NL; i++) acc += (uint64_t)m[i] * P::P[k - i];
+    r.l[k - NL] = (uint32_t)acc & LMASK;
+    acc >>= LB;
+  }
+  r.l[NL - 1] = (uint32_t)acc;
+  return r;
+}
+
 // (a*b + c*d) * 2^-261 mod p with ONE reduction: the two product columns share the accumulator, so the 81 multiply-adds (and
 // the carry handling) of a second Montgomery reduction disappear.  Used for Y3 = R*T - PPP*Y1 with d = K p - Y1.
 // Needs 9 * (max a_i * max b_j + max c_i * max d_j) + 9 * 2^58 + 2^35 < 2^64; value < p * ((ab + cd) / (p 2^261) + 1).

@@ -30,6 +30,7 @@
 #include <mutex>
 #include "ec_quad.hpp"
 #include "fe_inverse.hpp"
+#include "msm_digits.hpp"
 #include "reduce_plan.hpp"
 #include "zkhip_internal.hpp"
 
@@ -40,14 +41,7 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 constexpr int FINE_BITS = 12;           // wide windows: a bucket id = (coarse group, 12-bit fine id); MAX_GROUPS = 2^(20 - 1 - 12) groups at c = 20
 constexpr int MAX_GROUPS = 128;
 constexpr int MAX_WIDE_W = 16;          // windows of the wide path (c >= 17: at most 16): the coarse groups are counted and reserved per (window, group)
-// Balanced windows of the wide prepared path.  W = ceil(256 / c) windows of c bits cover W c >= 256 bits, and with uniform widths the surplus sits
-// in the top window: at c = 20 it holds 15 bits, so its 2^20 digits fall into the lowest 2^14 buckets, which then hold ~90 entries = two tasks
-// (a combining addition each, and the longest chains of the accumulation) while every other bucket holds ~26.  Here the last `narrow` = W c - 256
-// windows are c - 1 bits wide instead (c = 20: nine windows of 20 bits, four of 19): every window fills at least half of the bucket range.  The top
-// window still ends at bit 256, two bits above any scalar, so the signed recoding never carries out of it.  Offsets: win_off(w).
-struct win_layout { int c, W, narrow; };
-__host__ __device__ __forceinline__ int win_bits(const win_layout& L, int w) { return w < L.W - L.narrow ? L.c : L.c - 1; }
-__host__ __device__ __forceinline__ int win_off(const win_layout& L, int w) { const int full = L.W - L.narrow; return w <= full ? w * L.c : full * L.c + (w - full) * (L.c - 1); }
+// The window layout (win_layout, win_bits, win_off: balanced windows of the wide prepared path) and the recoding live in msm_digits.hpp.
 static int msm_narrow_windows(int c, int W) {
   if (c <= 16) return 0;
   const int narrow = W * c - 256;
@@ -124,29 +118,10 @@ __global__ void __launch_bounds__(256) k_digits(const uint32_t* __restrict__ sca
   }
   uint32_t w[8];
   load_words(scalars + ((size_t)kb * scalar_stride + i) * 8, w);
-  // Montgomery-256 -> plain integer: mont261(a*2^256, 2^5) = a
-  fe c32;
-#pragma unroll
-  for (int k = 0; k < NL; k++) c32.l[k] = FrParams::FROM_EXT_CANON[k];
-  fe s = fe_canon_lt2p<FrParams>(fe_mul<FrParams>(c32, fe_unpack<0>(w)));
-  fe_pack(s, w);
+  fe_pack(fr_ext_to_canon(w), w);                 // Montgomery-256 word (any 256-bit value) -> the canonical integer a < r, packed
   const win_layout lay{c, W, narrow};
   uint32_t carry = 0;
-  for (int win = 0; win < W; win++) {
-    const int bit = win_off(lay, win), cw = win_bits(lay, win);
-    const uint32_t half = 1u << (cw - 1), mask = (1u << cw) - 1;
-    uint32_t v = 0;
-    if (bit < 256) {
-      int wi = bit >> 5, sh = bit & 31;
-      uint64_t two = w[wi];
-      if (wi + 1 < 8) two |= (uint64_t)w[wi + 1] << 32;
-      v = (uint32_t)(two >> sh) & mask;
-    }
-    v += carry;
-    int32_t d;
-    if (v >= half) { d = (int32_t)v - (int32_t)(1u << cw); carry = 1; } else { d = (int32_t)v; carry = 0; }
-    digits[(size_t)win * row + i] = (int16_t)d;
-  }
+  for (int win = 0; win < W; win++) digits[(size_t)win * row + i] = (int16_t)recode_window(w, lay, win, carry);
 }
 
 // Wide windows (one vector, int32 digits): the same digits, and the coarse groups' entry counts on the way -- the two-level sort needs the
@@ -154,9 +129,16 @@ __global__ void __launch_bounds__(256) k_digits(const uint32_t* __restrict__ sca
 // (k_coarse_count).  A workgroup of 1024 threads walks its scalars with a grid stride, counts in LDS and merges its 2^(c-13) counters
 // with one global atomic each at the end: 512 - 1024 workgroups, so at most 128 K atomics on the 128 words (the naive form -- one
 // 256-thread workgroup per 256 scalars, 0.5 M atomics -- was measured in round 1: +39 us in this kernel for the -33 us it saved).
+// The digit loop costs more instructions than the conversion when the layout is a run-time value (a window's offset, width and word index are
+// computed, and the word is picked by a chain of selects: ~35 vector instructions per window), so the layout the wide tables ship with is a
+// template argument: C != 0 takes the windows (C, WT, NARROW) unrolled from the canonical limbs (recode_fixed); C = 0 is the generic kernel
+// for every other layout.  The LDS group counters and their merge are the same code.
+template <int C, int WT, int NARROW>
 __global__ void __launch_bounds__(1024) k_digits_wide(const uint32_t* __restrict__ scalars, int32_t* __restrict__ digits, uint32_t n, uint32_t n_pad,
                                                        int c, int W, uint32_t* __restrict__ gcount, int narrow) {
   __shared__ uint32_t cnt[MAX_WIDE_W * MAX_GROUPS];          // [window][group]
+  static_assert(WT <= MAX_WIDE_W, "a counter row per window");
+  if constexpr (C != 0) W = WT;
   for (uint32_t t = threadIdx.x; t < (uint32_t)W * MAX_GROUPS; t += blockDim.x) cnt[t] = 0;
   __syncthreads();
   const win_layout lay{c, W, narrow};
@@ -167,27 +149,23 @@ __global__ void __launch_bounds__(1024) k_digits_wide(const uint32_t* __restrict
     }
     uint32_t w[8];
     load_words(scalars + (size_t)i * 8, w);
-    fe c32;
+    const fe sv = fr_ext_to_canon(w);               // Montgomery-256 word (any 256-bit value) -> the canonical integer a < r
+    if constexpr (C != 0) {
+      int32_t d[WT];
+      recode_fixed<C, WT, NARROW>(sv, d);
 #pragma unroll
-    for (int k = 0; k < NL; k++) c32.l[k] = FrParams::FROM_EXT_CANON[k];
-    fe sv = fe_canon_lt2p<FrParams>(fe_mul<FrParams>(c32, fe_unpack<0>(w)));
-    fe_pack(sv, w);
-    uint32_t carry = 0;
-    for (int win = 0; win < W; win++) {
-      const int bit = win_off(lay, win), cw = win_bits(lay, win);
-      const uint32_t half = 1u << (cw - 1), mask = (1u << cw) - 1;
-      uint32_t v = 0;
-      if (bit < 256) {
-        const int wi = bit >> 5, sh = bit & 31;
-        uint64_t two = w[wi];
-        if (wi + 1 < 8) two |= (uint64_t)w[wi + 1] << 32;
-        v = (uint32_t)(two >> sh) & mask;
+      for (int win = 0; win < WT; win++) {
+        digits[(size_t)win * n_pad + i] = d[win];
+        if (d[win] != 0) atomicAdd(&cnt[win * MAX_GROUPS + (((uint32_t)(d[win] < 0 ? -d[win] : d[win]) - 1) >> FINE_BITS)], 1u);
       }
-      v += carry;
-      int32_t d;
-      if (v >= half) { d = (int32_t)v - (int32_t)(1u << cw); carry = 1; } else { d = (int32_t)v; carry = 0; }
-      digits[(size_t)win * n_pad + i] = d;
-      if (d != 0) atomicAdd(&cnt[win * MAX_GROUPS + (((uint32_t)(d < 0 ? -d : d) - 1) >> FINE_BITS)], 1u);
+    } else {
+      fe_pack(sv, w);
+      uint32_t carry = 0;
+      for (int win = 0; win < W; win++) {
+        const int32_t d = recode_window(w, lay, win, carry);
+        digits[(size_t)win * n_pad + i] = d;
+        if (d != 0) atomicAdd(&cnt[win * MAX_GROUPS + (((uint32_t)(d < 0 ? -d : d) - 1) >> FINE_BITS)], 1u);
+      }
     }
   }
   __syncthreads();
@@ -293,11 +271,7 @@ __global__ void __launch_bounds__(256) k_digits_glv(const uint32_t* __restrict__
   if (i >= n) return;
   uint32_t w[8];
   load_words(scalars + (size_t)i * 8, w);
-  fe c32;
-#pragma unroll
-  for (int k = 0; k < NL; k++) c32.l[k] = FrParams::FROM_EXT_CANON[k];
-  fe s = fe_canon_lt2p<FrParams>(fe_mul<FrParams>(c32, fe_unpack<0>(w)));      // Montgomery-256 -> the integer k < r
-  fe_pack(s, w);
+  fe_pack(fr_ext_to_canon(w), w);                   // Montgomery-256 word (any 256-bit value) -> the canonical integer k < r, packed
   uint32_t m[2][4];
   bool neg[2];
   glv::decompose(w, m[0], neg[0], m[1], neg[1]);
@@ -567,11 +541,15 @@ __global__ void __launch_bounds__(64) k_group_offsets(const uint32_t* __restrict
   // windows one after the other and wcursor[w][g] is where window w's workgroups start to reserve.
   if (blockIdx.x != 0 || threadIdx.x >= 64) return;
   const int lane = threadIdx.x;
+  // The lane's W x 2 counts are loaded before the first add -- W loads in flight together where a `for (w < W)` loop of loads and adds
+  // exposed W memory latencies, twice -- and stay in registers for the cursor rows below.  (W <= MAX_WIDE_W: msm_build_tasks.  A row has
+  // MAX_GROUPS words, so the pair 2 lane, 2 lane + 1 is inside it for every lane; the counts of groups >= G are zero.)
+  uint2 a[MAX_WIDE_W];
+#pragma unroll
+  for (int w = 0; w < MAX_WIDE_W; w++) a[w] = w < W ? reinterpret_cast<const uint2*>(wcount + w * MAX_GROUPS)[lane] : make_uint2(0u, 0u);
   uint32_t c0 = 0, c1 = 0;
-  for (int w = 0; w < W; w++) {
-    if (2 * lane < G) c0 += wcount[w * MAX_GROUPS + 2 * lane];
-    if (2 * lane + 1 < G) c1 += wcount[w * MAX_GROUPS + 2 * lane + 1];
-  }
+#pragma unroll
+  for (int w = 0; w < MAX_WIDE_W; w++) { c0 += a[w].x; c1 += a[w].y; }
   const uint32_t k0 = (c0 + chunk - 1) / chunk, k1 = (c1 + chunk - 1) / chunk;
   uint32_t x = c0 + c1, y = k0 + k1;
 #pragma unroll
@@ -583,9 +561,13 @@ __global__ void __launch_bounds__(64) k_group_offsets(const uint32_t* __restrict
   if (2 * lane < G) { goff[2 * lane] = ex; cstart[2 * lane] = ey; }
   if (2 * lane + 1 < G) { goff[2 * lane + 1] = ex + c0; cstart[2 * lane + 1] = ey + k0; }
   uint32_t r0 = ex, r1 = ex + c0;
-  for (int w = 0; w < W; w++) {
-    if (2 * lane < G) { wcursor[w * MAX_GROUPS + 2 * lane] = r0; r0 += wcount[w * MAX_GROUPS + 2 * lane]; }
-    if (2 * lane + 1 < G) { wcursor[w * MAX_GROUPS + 2 * lane + 1] = r1; r1 += wcount[w * MAX_GROUPS + 2 * lane + 1]; }
+#pragma unroll
+  for (int w = 0; w < MAX_WIDE_W; w++) {
+    if (w < W) {
+      if (2 * lane < G) wcursor[w * MAX_GROUPS + 2 * lane] = r0;
+      if (2 * lane + 1 < G) wcursor[w * MAX_GROUPS + 2 * lane + 1] = r1;
+    }
+    r0 += a[w].x; r1 += a[w].y;
   }
   if (lane == 63) { goff[G] = x; cstart[G] = y; }
 }
@@ -1817,7 +1799,10 @@ int msm_build_tasks(const uint32_t* d_scalars, size_t n_in, size_t batch, size_t
     // 2^22: 0.129 / 0.110 / 0.112 -- fewer workgroups leave a lane several scalars with exposed loads, more multiply the contended atomics)
     const unsigned wg_cap = n_pad > (1u << 21) ? 1024u : 512u;
     const unsigned wblocks = (unsigned)std::min<size_t>(((size_t)n_pad + 1023) / 1024, wg_cap);
-    hipLaunchKernelGGL(k_digits_wide, dim3(wblocks), dim3(1024), 0, stream, d_scalars, (int32_t*)digits, (uint32_t)n, n_pad, c, W, gcounters + 1024, narrow);
+    if (c == 20 && W == 13 && narrow == 4)      // the layout of the wide tables (msm_pick_window_prepared from 2^20 points): its own instantiation
+      hipLaunchKernelGGL((k_digits_wide<20, 13, 4>), dim3(wblocks), dim3(1024), 0, stream, d_scalars, (int32_t*)digits, (uint32_t)n, n_pad, c, W, gcounters + 1024, narrow);
+    else
+      hipLaunchKernelGGL((k_digits_wide<0, MAX_WIDE_W, 0>), dim3(wblocks), dim3(1024), 0, stream, d_scalars, (int32_t*)digits, (uint32_t)n, n_pad, c, W, gcounters + 1024, narrow);
   }
   else hipLaunchKernelGGL(k_digits, dim3(dblocks), dim3(256), 0, stream, d_scalars, (int16_t*)digits, (uint32_t)n, n_pad, c, W, K, sstride, 0);
   prof_mark(stream, "digits");

@@ -327,7 +327,8 @@ int zkhip_multiopen_shplonk_abort(zkhip_shplonk *state);
  * generator.  z is [ceil(n_columns / chunk_len)][2^log_n], dense:
  *     z_0[0] = 1,  z_s[0] = z_(s-1)[usable_rows],  z_s[i + 1] = z_s[i] prod_j (v_j[i] + beta delta^c omega^i + gamma) / (v_j[i] + beta sigma_j[i] + gamma)
  * for i < usable_rows; the rows after usable_rows repeat z_s[usable_rows] (the caller overwrites them with its blinding scalars, as the
- * reference does).  Zero denominators count as zero, like BatchInvert.  A handful of launches whatever the number of sets: the chained
+ * reference does).  With usable_rows = 2^log_n there is no row z_(s-1)[usable_rows]: a later set then starts from the product over all 2^log_n
+ * rows of the earlier sets.  Zero denominators count as zero, like BatchInvert.  A handful of launches whatever the number of sets: the chained
  * products of all sets are one prefix product over the [sets][n] array. */
 int zkhip_permutation_products(const uint64_t *const *values, const uint64_t *const *sigmas, uint32_t n_columns, uint32_t chunk_len, uint32_t log_n,
                                size_t usable_rows, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t delta[4], const uint64_t omega[4],
@@ -355,7 +356,8 @@ int zkhip_lookup_permute_many_device(const void *const *d_inputs, const void *co
                                      void *d_permuted_inputs, void *d_permuted_tables, void *stream);
 /* z[l][0] = 1, z[l][i+1] = z[l][i] (a_l[i] + beta)(s_l[i] + gamma) / ((a'_l[i] + beta)(s'_l[i] + gamma)) for i < usable_rows; the rows after
  * usable_rows repeat z[l][usable_rows] (the caller overwrites them, as with zkhip_permutation_products). Zero denominators count as zero.
- * d_permuted_inputs / d_permuted_tables / d_z: [n_lookups][2^log_n] dense; rows >= usable_rows of the permuted columns are not read. */
+ * d_permuted_inputs / d_permuted_tables / d_z: [n_lookups][2^log_n] dense; rows >= usable_rows of the permuted columns are not read.
+ * n_lookups == 0 or usable_rows == 0: ZKHIP_OK, nothing written. */
 int zkhip_lookup_products_device(const void *const *d_inputs, const void *const *d_tables, const void *d_permuted_inputs, const void *d_permuted_tables,
                                  uint32_t n_lookups, uint32_t log_n, size_t usable_rows, const uint64_t beta[4], const uint64_t gamma[4], void *d_z,
                                  void *stream);

@@ -1024,6 +1024,46 @@ typedef struct zkhip_shplonk_plan zkhip_shplonk_plan;
 int zkhip_shplonk_scalars_device(const zkhip_shplonk_plan *plan, const void *d_evals, const void *d_points, uint32_t k, const uint64_t omega[4], size_t n_proofs,
                                  void *d_rows_a, void *d_rows_c, void *d_status, void *stream);
 
+/* ---- KZG accumulators -------------------------------------------------------------------------------------------------------------------
+ * A KZG accumulator is a pair of G1 points (lhs, rhs) with e(lhs, g2) = e(rhs, [s] g2): what a proof's opening check leaves when the pairing
+ * is not taken (`PlonkSuccinctVerifier::verify` of the reference, aggregator/src/wrapper.rs:433-536), what `KzgAs` folds, and what the
+ * wrapper carries from round to round as 12 public inputs.  lhs is the A point of the batch verifier's rows above, rhs the C point.
+ *
+ * zkhip_g1_row_msm_device: n_rows independent small MSMs in one launch set (csrc/row_msm.hip),
+ *     out[i] = sum_{j < n_own} rows[i][j] own[i][j]  +  sum_{n_own <= j < n_cols} rows[i][j] shared[j - n_own].
+ *   d_rows           [n_rows][n_cols] Fr, 4 Montgomery words each, canonical (the rows of zkhip_gwc_scalars_device / zkhip_shplonk_scalars_device)
+ *   d_own_points     row i's own points start at element i * own_stride: 64-byte affine points.  own_stride >= n_own lets the C side of a batch
+ *                    read the first c own points of every row of the A side's array without a copy
+ *   d_shared_points  [n_cols - n_own] affine points shared by every row
+ *   d_out_xyz        [n_rows] 96-byte Jacobian points, the format the MSM calls leave: it goes straight into zkhip_g1_batch_normalize_device and
+ *                    zkhip_transcript_write_points_device
+ * The affine identity (0, 0) is a legal point anywhere; a zero scalar, two equal points in a row, P beside -P and a row that sums to the identity
+ * give what the group law says.  One launch set of at most two launches (one for n_cols <= 64; wider rows are cut into chunks of 64 columns
+ * whose partial sums meet in the second), no host wait, no allocation beyond the stream's scratch (144 bytes per chunk of a row, rows wider than
+ * 64 columns only).  A lane runs a GLV joint ladder over its column, so the call's latency is that of ~128 dependent point doublings and
+ * additions whatever n_rows is, until the chip is full.  n_rows == 0: ZKHIP_OK, nothing is written.  ZKHIP_EINVAL, decided before HIP is
+ * touched and with nothing enqueued: n_cols == 0; n_own > n_cols; own_stride < n_own; n_rows * n_cols above 2^31; own points spread over more
+ * than 2^40 elements ((n_rows - 1) * own_stride); with n_rows > 0 a pointer that is needed (d_rows, d_out_xyz, d_own_points where n_own > 0,
+ * d_shared_points where n_own < n_cols) and is null or not 16-byte aligned; d_out_xyz overlapping an input.
+ *
+ * Limbs (csrc/kzg_limbs.hpp has the normative text and the arithmetic, for host and device): ZKHIP_KZG_LIMBS = 3 limbs of
+ * ZKHIP_KZG_LIMB_BITS = 88 bits per coordinate.  A point becomes 6 Fr values: x's canonical integer cut little-endian into three 88-bit limbs,
+ * then y's, each limb an Fr in Montgomery words; an accumulator is lhs then rhs, 12 values (`[lhs.x, lhs.y, rhs.x, rhs.y].flat_map(fe_to_limbs)`).
+ * `affine`: n points of 8 words; `fr_out` / `fr_in`: n x 6 values of 4 words; `status`: n uint32.  Encode splits whatever canonical coordinates
+ * it is given.  Decode is strict and never a failed call: status 0 accepted, 1 a limb >= 2^88 (or a value that is no canonical Fr), 2 a
+ * coordinate >= q, 3 not on y^2 = x^3 + 3 -- (0, 0) gets status 3, as `from_xy` would refuse it; a refused point is written as (0, 0).
+ * (1, 2) |-> [1, 0, 0, 2, 0, 0].  The host forms touch no GPU and work in a process that never initialises HIP.  ZKHIP_EINVAL: with n > 0 a null
+ * pointer; for the device forms also a pointer that is not 16-byte aligned (d_status: 4-byte) and n > 2^31.
+ * Not built: blinded `KzgAs` (the reference's keys have no zk), the in-circuit side of the accumulation, a batch sharded over devices. */
+#define ZKHIP_KZG_LIMBS 3
+#define ZKHIP_KZG_LIMB_BITS 88
+int zkhip_g1_row_msm_device(const void *d_rows, size_t n_cols, const void *d_own_points, size_t n_own, size_t own_stride, const void *d_shared_points,
+                            size_t n_rows, void *d_out_xyz, void *stream);
+int zkhip_kzg_limbs_encode(const uint64_t *affine, size_t n, uint64_t *fr_out);
+int zkhip_kzg_limbs_decode(const uint64_t *fr_in, size_t n, uint64_t *affine, uint32_t *status);
+int zkhip_kzg_limbs_encode_device(const void *d_affine, size_t n, void *d_fr_out, void *stream);
+int zkhip_kzg_limbs_decode_device(const void *d_fr_in, size_t n, void *d_affine, void *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

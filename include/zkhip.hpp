@@ -1502,6 +1502,33 @@ inline void fold_rows_device(const DeviceVec& rows, uint32_t n_cols, uint32_t n_
     throw std::invalid_argument("fold_rows_device: arrays shorter than the batch");
   check(zkhip_fr_fold_rows_device(rows.data(), n_cols, n_own, r.data(), negate ? 1 : 0, n_rows, out_own.data(), out_shared.data(), nullptr), "fold_rows_device");
 }
+// KZG accumulators (zkhip.h, "KZG accumulators").  out[i] = sum_j rows[i][j] * (j < n_own ? own[i * own_stride + j] : shared[j - n_own]): Jacobian points
+inline void g1_row_msm_device(const DeviceVec& rows, size_t n_cols, const void* d_own_points, size_t n_own, size_t own_stride, const void* d_shared_points,
+                              size_t n_rows, void* d_out_xyz) {
+  if (rows.size() < n_rows * n_cols) throw std::invalid_argument("g1_row_msm_device: rows shorter than the batch");
+  check(zkhip_g1_row_msm_device(rows.data(), n_cols, d_own_points, n_own, own_stride, d_shared_points, n_rows, d_out_xyz, nullptr), "g1_row_msm_device");
+}
+// n affine points <-> n x 6 limbs in Fr (3 limbs of 88 bits per coordinate); the host forms need no device
+inline std::vector<Fr> kzg_limbs_encode(const std::vector<G1>& points) {
+  std::vector<Fr> out(points.size() * 2 * ZKHIP_KZG_LIMBS);
+  check(zkhip_kzg_limbs_encode(reinterpret_cast<const uint64_t*>(points.data()), points.size(), reinterpret_cast<uint64_t*>(out.data())), "kzg_limbs_encode");
+  return out;
+}
+inline std::vector<uint32_t> kzg_limbs_decode(const std::vector<Fr>& limbs, std::vector<G1>& points) {
+  const size_t n = limbs.size() / (2 * ZKHIP_KZG_LIMBS);
+  points.resize(n);
+  std::vector<uint32_t> status(n, 0);
+  check(zkhip_kzg_limbs_decode(reinterpret_cast<const uint64_t*>(limbs.data()), n, reinterpret_cast<uint64_t*>(points.data()), status.data()), "kzg_limbs_decode");
+  return status;
+}
+inline void kzg_limbs_encode_device(const void* d_affine, size_t n, DeviceVec& fr_out) {
+  if (fr_out.size() < n * 2 * ZKHIP_KZG_LIMBS) throw std::invalid_argument("kzg_limbs_encode_device: output shorter than 6 n");
+  check(zkhip_kzg_limbs_encode_device(d_affine, n, fr_out.data(), nullptr), "kzg_limbs_encode_device");
+}
+inline void kzg_limbs_decode_device(const DeviceVec& fr_in, size_t n, void* d_affine, void* d_status) {
+  if (fr_in.size() < n * 2 * ZKHIP_KZG_LIMBS) throw std::invalid_argument("kzg_limbs_decode_device: input shorter than 6 n");
+  check(zkhip_kzg_limbs_decode_device(fr_in.data(), n, d_affine, d_status, nullptr), "kzg_limbs_decode_device");
+}
 // Random field elements drawn in HBM (zkhip.h, "random field elements": element i of stream (seed, stream_id) is one ChaCha20 block reduced mod r).
 // The library holds no entropy: `seed` comes from the caller's generator, and a (seed, stream_id, index) triple is never reused across proofs.
 // out[j] = element first + j for every j < out.size(): the vanishing argument's random polynomial, never on the host

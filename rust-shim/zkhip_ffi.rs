@@ -109,6 +109,14 @@ extern "C" {
     // call takes a plan struct and is not bound here: a Rust verifier makes its rows with its own accumulation scheme ------------------------
     fn zkhip_fr_fold_rows_device(d_rows: *const c_void, n_cols: u32, n_own: u32, d_r: *const c_void, negate: c_int, n_rows: usize, d_out_own: *mut c_void,
                                  d_out_shared: *mut c_void, stream: *mut c_void) -> c_int;
+    // ---- KZG accumulators (zkhip.h "KZG accumulators"): the two points of every proof's opening check as B small MSMs in one launch set, and an
+    // accumulator as 12 public inputs (3 limbs of 88 bits per coordinate) and back.  Declared for a Rust `PlonkSuccinctVerifier`; not called yet ---
+    fn zkhip_g1_row_msm_device(d_rows: *const c_void, n_cols: usize, d_own_points: *const c_void, n_own: usize, own_stride: usize,
+                               d_shared_points: *const c_void, n_rows: usize, d_out_xyz: *mut c_void, stream: *mut c_void) -> c_int;
+    fn zkhip_kzg_limbs_encode(affine: *const u64, n: usize, fr_out: *mut u64) -> c_int;
+    fn zkhip_kzg_limbs_decode(fr_in: *const u64, n: usize, affine: *mut u64, status: *mut u32) -> c_int;
+    fn zkhip_kzg_limbs_encode_device(d_affine: *const c_void, n: usize, d_fr_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn zkhip_kzg_limbs_decode_device(d_fr_in: *const c_void, n: usize, d_affine: *mut c_void, d_status: *mut c_void, stream: *mut c_void) -> c_int;
     // ---- pairing check (zkhip.h "pairing check"): is prod_i e(g1[i], g2[i]) the identity of Gt?  Only the verdict leaves the device ----------
     fn zkhip_pairing_check(g1: *const u64, g2: *const u64, n: usize, ok: *mut c_int) -> c_int;
     fn zkhip_pairing_check_device(d_g1: *const c_void, d_g2: *const c_void, n: usize, d_ok: *mut c_void, stream: *mut c_void) -> c_int;

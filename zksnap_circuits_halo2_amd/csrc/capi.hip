@@ -33,6 +33,8 @@
 #include "imt.hpp"
 #include "modn.hpp"
 #include "secp256k1_h2c.hpp"
+#include "row_msm.hpp"
+#include "kzg_limbs.hpp"
 #include "../../include/zkhip.hpp"   // host-side 4 x 64 Montgomery arithmetic for domain constants (zkhip::halo2::detail)
 
 namespace zkhip {
@@ -2068,6 +2070,62 @@ int zkhip_shplonk_scalars_device(const zkhip_shplonk_plan* plan, const void* d_e
   if ((rc = sc->ws.reserve(blob.size() * 4)) != ZKHIP_OK) return rc;
   return shplonk_scalars_device(blob, (const uint32_t*)d_evals, (const uint32_t*)d_points, n_proofs, (uint32_t*)d_rows_a, (uint32_t*)d_rows_c, (uint32_t*)d_status, sc->ws.p,
                                 sc->ws.cap, s, &sc->args);
+}
+
+// ---- KZG accumulators (include/zkhip.h; row_msm.hip, row_msm.hpp, kzg_limbs.hpp): refusals before the device is touched, nothing waits for the stream ----
+int zkhip_g1_row_msm_device(const void* d_rows, size_t n_cols, const void* d_own_points, size_t n_own, size_t own_stride, const void* d_shared_points, size_t n_rows,
+                            void* d_out_xyz, void* stream) {
+  ZK_API_RANGE();
+  if (const char* why = row_msm_refusal(d_rows, n_cols, d_own_points, n_own, own_stride, d_shared_points, n_rows, d_out_xyz)) {
+    set_error("g1_row_msm: %s (%zu rows of %zu columns, %zu own at stride %zu)", why, n_rows, n_cols, n_own, own_stride);
+    return ZKHIP_EINVAL;
+  }
+  if (n_rows == 0) return ZKHIP_OK;                                  // nothing to write
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  hipStream_t s = caller_stream(stream);
+  scratch* sc = scratch_for(primary(), s);
+  if ((rc = sc->ws.reserve(g1_row_msm_workspace(n_rows, n_cols))) != ZKHIP_OK) return rc;
+  return g1_row_msm_device((const uint32_t*)d_rows, n_cols, (const uint32_t*)d_own_points, n_own, own_stride, (const uint32_t*)d_shared_points, n_rows, (uint32_t*)d_out_xyz,
+                           sc->ws.p, sc->ws.cap, s);
+}
+
+int zkhip_kzg_limbs_encode(const uint64_t* affine, size_t n, uint64_t* fr_out) {
+  if (n && (!affine || !fr_out)) { set_error("kzg_limbs_encode: null pointer"); return ZKHIP_EINVAL; }
+  for (size_t i = 0; i < n; i++) kzg_limbs::encode_point(affine + i * 8, fr_out + i * 24);
+  return ZKHIP_OK;
+}
+
+int zkhip_kzg_limbs_decode(const uint64_t* fr_in, size_t n, uint64_t* affine, uint32_t* status) {
+  if (n && (!fr_in || !affine || !status)) { set_error("kzg_limbs_decode: null pointer"); return ZKHIP_EINVAL; }
+  for (size_t i = 0; i < n; i++) status[i] = kzg_limbs::decode_point(fr_in + i * 24, affine + i * 8);
+  return ZKHIP_OK;
+}
+
+int zkhip_kzg_limbs_encode_device(const void* d_affine, size_t n, void* d_fr_out, void* stream) {
+  ZK_API_RANGE();
+  if (n > ((size_t)1 << 31)) { set_error("kzg_limbs_encode: %zu points in one call", n); return ZKHIP_EINVAL; }
+  if (n && (!elems_ptr_ok(d_affine) || !elems_ptr_ok(d_fr_out))) { set_error("kzg_limbs_encode: null or misaligned pointer"); return ZKHIP_EINVAL; }
+  if (n == 0) return ZKHIP_OK;
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  return kzg_limbs_encode_device((const uint64_t*)d_affine, n, (uint64_t*)d_fr_out, caller_stream(stream));
+}
+
+int zkhip_kzg_limbs_decode_device(const void* d_fr_in, size_t n, void* d_affine, void* d_status, void* stream) {
+  ZK_API_RANGE();
+  if (n > ((size_t)1 << 31)) { set_error("kzg_limbs_decode: %zu points in one call", n); return ZKHIP_EINVAL; }
+  if (n && (!elems_ptr_ok(d_fr_in) || !elems_ptr_ok(d_affine) || !d_status || ((uintptr_t)d_status & 3u) != 0)) {
+    set_error("kzg_limbs_decode: null or misaligned pointer");
+    return ZKHIP_EINVAL;
+  }
+  if (n == 0) return ZKHIP_OK;
+  guard_t g(g_mu);
+  int rc = ensure_init();
+  if (rc != ZKHIP_OK) return rc;
+  return kzg_limbs_decode_device((const uint64_t*)d_fr_in, n, (uint64_t*)d_affine, (uint32_t*)d_status, caller_stream(stream));
 }
 
 int zkhip_lookup_permute(const uint64_t* input, const uint64_t* table, size_t usable_rows, uint64_t* permuted_input, uint64_t* permuted_table) {

@@ -351,6 +351,14 @@ int shplonk_plan_marshal(const zkhip_shplonk_plan* plan, uint32_t k, const uint6
 int shplonk_scalars_device(const std::vector<uint32_t>& blob, const uint32_t* d_evals, const uint32_t* d_points, uint64_t n_proofs, uint32_t* d_rows_a,
                            uint32_t* d_rows_c, uint32_t* d_status, void* ws, size_t ws_bytes, hipStream_t stream, arg_ring* ring = nullptr);
 
+// row_msm.hip (include/zkhip.h, "KZG accumulators"; row_msm.hpp has the refusals and the launch arithmetic, kzg_limbs.hpp the limbs).
+// `ws`: g1_row_msm_workspace(n_rows, n_cols) bytes, the partial sums of rows wider than one chunk.
+size_t g1_row_msm_workspace(size_t n_rows, size_t n_cols);
+int g1_row_msm_device(const uint32_t* d_rows, size_t n_cols, const uint32_t* d_own, size_t n_own, size_t own_stride, const uint32_t* d_shared, size_t n_rows,
+                      uint32_t* d_out, void* ws, size_t ws_bytes, hipStream_t stream);
+int kzg_limbs_encode_device(const uint64_t* d_affine, size_t n, uint64_t* d_out, hipStream_t stream);
+int kzg_limbs_decode_device(const uint64_t* d_in, size_t n, uint64_t* d_affine, uint32_t* d_status, hipStream_t stream);
+
 // selftest.hip
 int test_field_op(int field, int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, size_t n, hipStream_t stream);
 int g1_check_points_device(const uint32_t* d_points, size_t n, unsigned long long* d_first_bad, hipStream_t stream);

@@ -445,6 +445,18 @@ def shplonk_accumulate(queries: Sequence[VerifierQuery], y: int, v: int, u: int)
     return coeffs + [g_scalar, h_scalar, u % R_MOD], commitments
 
 
+_Q_MOD = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47
+
+
+def negate_affine(point: np.ndarray) -> np.ndarray:
+    """-(x, y) = (x, q - y) on the 8 affine limbs (Montgomery words: the negation is the same subtraction); the identity (0, 0) stays"""
+    out = np.array(point, dtype=np.uint64).reshape(8)
+    y = sum(int(w) << (64 * i) for i, w in enumerate(out[4:]))
+    if y:
+        out[4:] = [((_Q_MOD - y) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+    return out
+
+
 def _final_check(params, left_affine: np.ndarray, right_affine_negated: np.ndarray) -> bool:
     from .arithmetic import pairing_check
 
@@ -460,17 +472,26 @@ class VerifierGWC:
     def __init__(self, params):
         self.params = params
 
-    def verify_proof(self, queries: Sequence[VerifierQuery], witnesses: Sequence[np.ndarray], v: int, u: int) -> bool:
+    def accumulator_points(self, queries: Sequence[VerifierQuery], witnesses: Sequence[np.ndarray], v: int, u: int):
+        """the two points the pairing would check, (lhs, rhs) with e(lhs, g2) = e(rhs, [s]g2) for an honest proof, each 8 affine limbs:
+        lhs = sum_i u^i (z_i W_i + sum_j v^j C_ij - (sum_j v^j e_ij) G), rhs = sum_i u^i W_i.  None: inconsistent queries"""
         from .arithmetic import g1_combination
 
         try:
             left, right, commitments = gwc_accumulate(queries, len(witnesses), v, u)
         except InconsistentQueries:
-            return False
+            return None
         W = [np.ascontiguousarray(w, dtype=np.uint64).reshape(12) for w in witnesses]
-        R_pt = g1_combination(right, np.stack(W + commitment_points(queries, commitments) + [_generator_xyz(self.params)]))
-        L_neg = g1_combination([-s for s in left], np.stack(W))
-        return _final_check(self.params, R_pt, L_neg)
+        lhs = g1_combination(right, np.stack(W + commitment_points(queries, commitments) + [_generator_xyz(self.params)]))
+        return lhs, g1_combination(left, np.stack(W))
+
+    def verify_proof(self, queries: Sequence[VerifierQuery], witnesses: Sequence[np.ndarray], v: int, u: int) -> bool:
+        points = self.accumulator_points(queries, witnesses, v, u)
+        return points is not None and _final_check(self.params, points[0], negate_affine(points[1]))
+
+    def accumulator_points_read(self, queries: Sequence[VerifierQuery], W, challenges):
+        """`accumulator_points` over what `read_proof` returned"""
+        return self.accumulator_points(queries, _points_xyz(W), *challenges)
 
     def read_proof(self, tr, n_points: int, device: bool = False):
         """GWC's part of a proof from a transcript reader, in the order ProverGWC.create_proof_transcript wrote it: v is squeezed, one witness per
@@ -508,18 +529,30 @@ class VerifierSHPLONK:
     def __init__(self, params):
         self.params = params
 
-    def verify_proof(self, queries: Sequence[VerifierQuery], H: np.ndarray, Hp: np.ndarray, y: int, v: int, u: int) -> bool:
+    def accumulator_points(self, queries: Sequence[VerifierQuery], H: np.ndarray, Hp: np.ndarray, y: int, v: int, u: int):
+        """the two points the pairing would check, (lhs, rhs) = (Lc + u H', H') with e(lhs, g2) = e(rhs, [s]g2) for an honest proof, each 8
+        affine limbs.  None: inconsistent queries"""
         from .arithmetic import g1_combination
 
         try:
             scalars, commitments = shplonk_accumulate(queries, y, v, u)
         except InconsistentQueries:
-            return False
+            return None
         H = np.ascontiguousarray(H, dtype=np.uint64).reshape(12)
         Hp = np.ascontiguousarray(Hp, dtype=np.uint64).reshape(12)
-        left = g1_combination(scalars, np.stack(commitment_points(queries, commitments) + [_generator_xyz(self.params), H, Hp]))
-        right_neg = g1_combination([-1], Hp.reshape(1, 12))
-        return _final_check(self.params, left, right_neg)
+        lhs = g1_combination(scalars, np.stack(commitment_points(queries, commitments) + [_generator_xyz(self.params), H, Hp]))
+        if np.array_equal(Hp[8:], _FQ_ONE):                # read from a transcript: affine already (z = 1)
+            return lhs, Hp[:8].copy()
+        return lhs, g1_combination([1], Hp.reshape(1, 12))  # a prover's Jacobian point
+
+    def verify_proof(self, queries: Sequence[VerifierQuery], H: np.ndarray, Hp: np.ndarray, y: int, v: int, u: int) -> bool:
+        points = self.accumulator_points(queries, H, Hp, y, v, u)
+        return points is not None and _final_check(self.params, points[0], negate_affine(points[1]))
+
+    def accumulator_points_read(self, queries: Sequence[VerifierQuery], points, challenges):
+        """`accumulator_points` over what `read_proof` returned ([H', H])"""
+        Hp, H = _points_xyz(points)
+        return self.accumulator_points(queries, H, Hp, *challenges)
 
     def read_proof(self, tr, n_points: int = None, device: bool = False):
         """SHPLONK's part of a proof from a transcript reader, in the order ProverSHPLONK.create_proof_transcript wrote it: squeeze y, squeeze

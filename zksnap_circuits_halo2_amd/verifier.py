@@ -163,8 +163,23 @@ def _fold_openings(params, fold_plan, k, heads, order, d_evals, rows_of, fold_se
         verdicts[i] = bool(ok)
 
 
+def _decide_carried(params, instances, accumulator_indices, verdicts):
+    """the carried accumulators of the proofs accepted so far (accumulator.carried_accumulators): a proof with one that does not decode is
+    refused; the rest are decided together and, where that fails, proof by proof"""
+    from . import accumulator as A
+
+    carried, status = A.carried_accumulators(instances, accumulator_indices, len(verdicts))
+    for i, bad in enumerate((status.reshape(len(verdicts), -1) != 0).any(dim=1).cpu().tolist()):
+        verdicts[i] = verdicts[i] and not bad
+    live = [i for i, ok in enumerate(verdicts) if ok]
+    if not live or A.decide_all(params, carried[live].reshape(-1, 2, 8).contiguous()):
+        return
+    for i in live:
+        verdicts[i] = all(A.decide(params, acc.contiguous()) for acc in carried[i])
+
+
 def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b", multiopen="shplonk", *, identity=True, instances=None, fold=False,
-                             fold_seed=None):
+                             fold_seed=None, accumulator_indices=()):
     """The verifier of a BATCH of proofs of one circuit, each written through TranscriptChallenges: it is handed the parameters, the verifying key
     (with its constraint system, `vk.cs`), the proofs' BYTES, and what a verifier knows of the circuit -- `shape` (how many advice columns,
     lookups, permutation sets, whether a random polynomial is committed) and `plan` (the opened (kind, index, rotation) triples, in the order
@@ -190,6 +205,10 @@ def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b",
     folded check with probability about 1 / r).  A proof with x = 0 mod r, a plan that repeats a triple and a plan with two rotations equal mod 2^k take the one-by-one path.
     fold_seed: the 32 bytes the random multipliers are drawn from; None (what a verifier uses) draws them from os.urandom, a fixed seed is for
     tests.
+    accumulator_indices: (column, lo) pairs (`with_accumulator_indices`): instances[i][column][lo : lo + 12] are the limbs of a KZG accumulator
+    that proof i carries (accumulator.to_limbs).  With them a proof is accepted when its identity holds, its openings hold, and every carried
+    accumulator decodes and decides: one accumulator.decide_all over the carried accumulators of the proofs that got that far and, if that
+    fails, proof by proof.  With () nothing new runs.
     Not built: committed instance columns, multi-phase challenges; folding across
     different circuits or parameter sets, a batch sharded over devices.  Returns a list of bools."""
     scheme = MO.multiopen_classes(multiopen)[1]
@@ -241,6 +260,8 @@ def verify_transcript_proofs(params, vk, k, proofs, shape, plan, hash="blake2b",
         else:
             for i in order:
                 verdicts[i] = one_by_one(i)
+    if tuple(accumulator_indices) and proofs:
+        _decide_carried(params, instances, accumulator_indices, verdicts)
     return verdicts
 
 
